@@ -6,6 +6,11 @@ MFMA path), batch 64 per GPU, synthetic 224x224x3 inputs resident in HBM.
 One "step" = InceptionV3 forward + keys projection + teacher-forced decoder forward and
 backward + (N>1: RCCL all-reduce of the 22.8 MB flat gradient) + fused TF-Adam update.
 Prints ONE JSON line on rank 0 (contract in the task statement).
+
+A plain run sets up, warms up, times --steps steps and prints the headline.  --full adds what takes runs
+of its own: the encoder forward and the decoder step alone (rooflines), the heaviest conv launch, the
+secondary configurations (`extras`) and the CPU baseline.  --dump-outputs DIR writes what the last timed
+step computed as float32 .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -701,6 +706,17 @@ def pick_encoder_group(steps):
     return 1 if steps <= 1 else DEFAULT_ENC_GROUP
 
 
+def dump_outputs(d, res, decoder):
+    """--dump-outputs: what the last timed step hands its caller -- the loss, the logits [B,T,V] and the attention maps
+    [B,H,T',M] -- and the decoder's parameters and gradients after it, as float32 .npy files under `d` (49 MB at the
+    benchmarked geometry).  The inputs come from fixed seeds, so two builds can be compared array by array."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {'loss': res['loss'].reshape(1), 'logits': res['logits'], 'attn_maps': res['attn_maps'],
+              'decoder_params': decoder.params.flat, 'decoder_grads': decoder.grads.flat}
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def launch_ranks(n):
     """`python -m torch.distributed.run --nnodes=1 --nproc-per-node n --master-addr 127.0.0.1 --master-port P bench.py
     <the same arguments>` as a child process; returns its exit code.  The port is one the kernel has just handed out."""
@@ -722,8 +738,11 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the rooflines, the heaviest conv launch, the extras and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: leave out the secondary configurations')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed step to DIR/<name>.npy')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -912,48 +931,73 @@ def main():
     dt = float(t.item())
     assert n_fwd[0] * ENC_BATCH >= args.steps * BATCH, 'fewer images encoded than consumed inside the timed region'
     cnn_ms = float(np.mean([a.elapsed_time(b) for a, b in ev[:n_fwd[0]]])) if EVENTS else float('nan')
-    # the same forward alone on the GPU (not overlapped with the decoder), for reference
-    tr.enable_overlap(0)                 # full occupancy again (the overlapped forward ran 1 workgroup per CU)
-    for _ in range(3):
-        tr.encoder.forward(images, use_graph=GRAPH_CNN)
-    iso = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
-    for a, b in iso:      # the input buffer already holds a group: the forward itself, no copy
-        a.record(); tr.encoder.forward(inbuf, use_graph=GRAPH_CNN); b.record()
-    torch.cuda.synchronize()
-    cnn_iso_ms = float(np.mean([a.elapsed_time(b) for a, b in iso]))
-    # the decoder step alone on the GPU (forward + backward + Adam on resident features, nothing beside it), HIP events
-    dfm, dim = fm[:BATCH].clone(), im_embed[:BATCH].clone()
-    for i in range(3):
-        tr.decoder.train_step(dfm, dim, cap_sets[i % 4], training=True, use_graph=GRAPH_DEC)
-        tr.opt.step(tr.decoder.grads, tr.lr())
-    dec_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(12)]
-    for i, (a, b) in enumerate(dec_ev):
-        a.record()
-        rd = tr.decoder.train_step(dfm, dim, cap_sets[i % 4], training=True, use_graph=GRAPH_DEC)
-        tr.opt.step(tr.decoder.grads, tr.lr())
-        b.record()
-    torch.cuda.synchronize()
-    dec_ms = float(np.mean([a.elapsed_time(b) for a, b in dec_ev]))
-    dec_Tp = int(rd['Tp'])
-    dec_path = int(tr.decoder.lib.comic_decoder_train_path())
+    # `res` holds views of the decoder's buffers for this caption shape: read them before any other step of that shape
     loss = float(res['loss'])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, tr.decoder)
+    if args.full:
+        # the same forward alone on the GPU (not overlapped with the decoder), for reference
+        tr.enable_overlap(0)                 # full occupancy again (the overlapped forward ran 1 workgroup per CU)
+        for _ in range(3):
+            tr.encoder.forward(images, use_graph=GRAPH_CNN)
+        iso = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
+        for a, b in iso:      # the input buffer already holds a group: the forward itself, no copy
+            a.record(); tr.encoder.forward(inbuf, use_graph=GRAPH_CNN); b.record()
+        torch.cuda.synchronize()
+        cnn_iso_ms = float(np.mean([a.elapsed_time(b) for a, b in iso]))
+        # the decoder step alone on the GPU (forward + backward + Adam on resident features, nothing beside it), HIP events
+        dfm, dim = fm[:BATCH].clone(), im_embed[:BATCH].clone()
+        for i in range(3):
+            tr.decoder.train_step(dfm, dim, cap_sets[i % 4], training=True, use_graph=GRAPH_DEC)
+            tr.opt.step(tr.decoder.grads, tr.lr())
+        dec_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(12)]
+        for i, (a, b) in enumerate(dec_ev):
+            a.record()
+            rd = tr.decoder.train_step(dfm, dim, cap_sets[i % 4], training=True, use_graph=GRAPH_DEC)
+            tr.opt.step(tr.decoder.grads, tr.lr())
+            b.record()
+        torch.cuda.synchronize()
+        dec_ms = float(np.mean([a.elapsed_time(b) for a, b in dec_ev]))
+        dec_Tp = int(rd['Tp'])
+        dec_path = int(tr.decoder.lib.comic_decoder_train_path())
     voided = tr.decoder.voided_steps()          # steps the device voided (persistent-loop timeout): must be none
     if world > 1:
         voided = int(dp.max_scalar(voided))
     assert voided == 0, 'the device voided %d training step(s) inside the run ("voided_steps": %d): no valid bench line' % (voided, voided)
     assert np.isfinite(loss), 'non-finite loss'
-    top = heaviest_conv_launch(tr.encoder, plan) if rank == 0 else None
+    top = heaviest_conv_launch(tr.encoder, plan) if rank == 0 and args.full else None
 
     if rank == 0:
         plan = tr.encoder.plan          # (the encoder's own op table)
         n_conv = sum(1 for o in plan.ops if o['kind'] in (0, 1, 8, 9)) + sum(1 for o in plan.ops if o['kind'] == 8) + 2 * sum(1 for o in plan.ops if o['kind'] == 9)
         n_launch = sum(1 for o in plan.ops if o['kind'] in (0, 1, 8, 9) and not o.get('group')) + len({o['group'] for o in plan.ops if o.get('group')})
-        # Kernel quality is judged on the forward ALONE on the GPU (HIP events in this process, same graph /
-        # launches, right after the timed loop); inside the timed region the same forward is deliberately
-        # run at one workgroup per CU underneath the decoder step, so its wall time there says how well
-        # the two overlap, not how good the kernel is.  Both are reported.
-        achieved = FLOP_PER_IMAGE_CNN * ENC_BATCH / (cnn_iso_ms * 1e-3)
+        kernel = ('conv_igemm_dma / conv_patch (+ _grouped) / conv_img_chain kernels <bf16> (%d convs in %d launches per forward of '
+                  '%d images, whole InceptionV3 forward timed with HIP events)' % (n_conv, n_launch, ENC_BATCH))
         achieved_in = FLOP_PER_IMAGE_CNN * ENC_BATCH / (cnn_ms * 1e-3)
+        in_region = {'cnn_forward_ms': round(cnn_ms, 4), 'achieved': round(achieved_in / 1e12, 3),
+                     'frac': round(achieved_in / PEAK_BF16_MFMA, 5), 'overlapped': bool(overlap)}
+        in_region_note = ('in_timed_region: the same forward while it runs on a second stream under the decoder step of the '
+                          'previous batch%s (frozen CNN) at one conv workgroup per CU' %
+                          (' group: one forward per %d steps' % GROUP if GROUP > 1 else ''))
+        if args.full:
+            # Kernel quality is judged on the forward ALONE on the GPU (HIP events in this process, same graph /
+            # launches, right after the timed loop); inside the timed region the same forward is deliberately
+            # run at one workgroup per CU underneath the decoder step, so its wall time there says how well
+            # the two overlap, not how good the kernel is.  Both are reported.
+            achieved = FLOP_PER_IMAGE_CNN * ENC_BATCH / (cnn_iso_ms * 1e-3)
+            roofline = {'bound': 'mfma', 'kernel': kernel,
+                        'achieved': round(achieved / 1e12, 3), 'peak': PEAK_BF16_MFMA / 1e12, 'unit': 'TFLOP/s',
+                        'frac': round(achieved / PEAK_BF16_MFMA, 5), 'traffic': None,
+                        'cnn_forward_ms': round(cnn_iso_ms, 4), 'images_per_forward': ENC_BATCH, 'heaviest_launch': top,
+                        'in_timed_region': in_region,
+                        'note': ('achieved/frac: the forward alone on the GPU, HIP events on its stream, measured in this '
+                                 'process after the timed loop (agrees with profiles/*kernel_stats.csv).  ' + in_region_note)
+                                if overlap else ''}
+        else:
+            roofline = {'bound': 'mfma', 'kernel': kernel, 'peak': PEAK_BF16_MFMA / 1e12, 'unit': 'TFLOP/s',
+                        'images_per_forward': ENC_BATCH, 'in_timed_region': in_region,
+                        'note': in_region_note + '.  The forward alone (achieved / frac) and the decoder roofline: --full'
+                                if overlap else 'the forward alone (achieved / frac) and the decoder roofline: --full'}
         out = {
             'metric': 'images/sec (decoder-mode XE training, COMIC-256, InceptionV3 frozen)',
             'value': round(BATCH * world * args.steps / dt, 2), 'unit': 'images/sec', 'n_gpus': world,
@@ -966,20 +1010,13 @@ def main():
                        'encoder_group': GROUP, 'encoder_forwards_in_timed_region': n_fwd[0],
                        'inputs': 'pinned host memory, H2D copy per group inside the timed region' if h2d else
                                  'resident in HBM, %d distinct image groups in rotation' % N_IMG_SETS},
-            'roofline': {'bound': 'mfma', 'kernel': 'conv_igemm_dma / conv_patch (+ _grouped) / conv_img_chain kernels <bf16> (%d convs in %d '
-                                                    'launches per forward of %d images, whole InceptionV3 forward timed with HIP events)' % (n_conv, n_launch, ENC_BATCH),
-                         'achieved': round(achieved / 1e12, 3), 'peak': PEAK_BF16_MFMA / 1e12, 'unit': 'TFLOP/s',
-                         'frac': round(achieved / PEAK_BF16_MFMA, 5), 'traffic': None,
-                         'cnn_forward_ms': round(cnn_iso_ms, 4), 'images_per_forward': ENC_BATCH, 'heaviest_launch': top,
-                         'in_timed_region': {'cnn_forward_ms': round(cnn_ms, 4), 'achieved': round(achieved_in / 1e12, 3),
-                                             'frac': round(achieved_in / PEAK_BF16_MFMA, 5), 'overlapped': bool(overlap)},
-                         'note': ('achieved/frac: the forward alone on the GPU, HIP events on its stream, measured in this '
-                                  'process after the timed loop (agrees with profiles/*kernel_stats.csv).  in_timed_region: '
-                                  'the same forward while it runs on a second stream under the decoder step of the '
-                                  'previous batch%s (frozen CNN) at one conv workgroup per CU' %
-                                  (' group: one forward per %d steps' % GROUP if GROUP > 1 else '')) if overlap else ''},
+            'roofline': roofline,
             'final_loss': round(loss, 5), 'voided_steps': voided,
         }
+        if not args.full:
+            out['cpu_baseline'] = None
+            out['summary'] = {'images_per_sec': out['value'], 'ms_per_step': out['ms_per_step'], 'voided_steps': voided}
+    if rank == 0 and args.full:
         # Second roofline entry: the decoder chain.  Algorithmic HBM bytes of one decoder step = every tensor of the step
         # moved once in each direction it is needed: parameters read in forward and backward, gradients written, Adam
         # (p, g, m, v read; p, m, v written), the feature map read by the key projection and by d W_m, and the per-step
@@ -1033,6 +1070,7 @@ def main():
                           'xe_299': _g(ex, 'xe_299', 'images_per_sec'), 'xe_v1': _g(ex, 'xe_v1', 'images_per_sec'),
                           'input_pipeline': _g(ex, 'input_pipeline', 'images_per_sec'),
                           'cpu_images_per_sec': _g(out, 'cpu_baseline', 'value'), 'voided_steps': voided}
+    if rank == 0:
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

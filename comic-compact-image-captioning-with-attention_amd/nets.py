@@ -715,6 +715,18 @@ def plan_grad_buckets(plan, w_flat, b_flat, n=6):
     return out
 
 
+def store_tune_cache(cache, key, tiles):
+    """Adds {key: tiles} to the JSON tune cache `cache`.  The ranks of a data-parallel run tune into the same file of the
+    shared run directory, so the new contents go to a file of this process beside it that then replaces it: a reader
+    sees the old file or the new one, never one cut short by a writer."""
+    db = json.load(open(cache)) if os.path.isfile(cache) else {}
+    db[key] = tiles
+    tmp = '%s.%d.tmp' % (cache, os.getpid())
+    with open(tmp, 'w') as f:
+        json.dump(db, f)
+    os.replace(tmp, cache)
+
+
 class CnnEncoder:
     """Device-resident encoder: packed weights, folded BN, activation buffers, one native
     forward call.  `dtype` 'bf16' (throughput path) or 'f32' (exact-fp32 MFMA, parity path)."""
@@ -1144,9 +1156,7 @@ class CnnEncoder:
                     dict((tl, ms) for ms, tl in cands)[0] * 1e3))
         t.gflat.zero_()
         if cache:
-            db = json.load(open(cache)) if os.path.isfile(cache) else {}
-            db[key] = [int(t.grads[i].bwd_tile) for i in range(len(plan.weights))]
-            json.dump(db, open(cache, 'w'))
+            store_tune_cache(cache, key, [int(t.grads[i].bwd_tile) for i in range(len(plan.weights))])
         return chosen
 
     def grad_buckets(self, n=6):
@@ -1325,9 +1335,7 @@ class CnnEncoder:
                 return {i: (None, t) for i, t in enumerate(tiles)}
         chosen = self._autotune(reps, verbose, torch, st)      # op.min_lds: tuned under the occupancy the forward runs with
         if cache:
-            db = json.load(open(cache)) if os.path.isfile(cache) else {}
-            db[self._tune_key()] = [int(self._ops[i].tile) for i in range(len(self.plan.ops))]
-            json.dump(db, open(cache, 'w'))
+            store_tune_cache(cache, self._tune_key(), [int(self._ops[i].tile) for i in range(len(self.plan.ops))])
         return chosen
 
     def _autotune(self, reps, verbose, torch, st):

@@ -660,6 +660,49 @@ def test_bench_encoder_group_divides_the_timed_steps():
         assert 1 <= g <= max(bench.DEFAULT_ENC_GROUP, 1) and (k % g == 0 or g == bench.DEFAULT_ENC_GROUP)
 
 
+def test_bench_dump_outputs_writes_the_step_outputs_as_float32(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per output of the last timed step (loss, logits, attention maps) and
+    the decoder's parameters and gradients after it, values unchanged (the logits arrive as a permuted device view)."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    logits = rng.standard_normal((3, 2, 5)).astype(np.float32)
+    attn = rng.standard_normal((2, 4, 3, 6)).astype(np.float32)
+    params, grads = rng.standard_normal(70).astype(np.float32), rng.standard_normal(70).astype(np.float32)
+    res = {'loss': torch.tensor([2.5, 9.0])[0], 'logits': torch.from_numpy(logits).permute(1, 0, 2),
+           'attn_maps': torch.from_numpy(attn), 'Tp': 3}
+    decoder = types.SimpleNamespace(params=types.SimpleNamespace(flat=torch.from_numpy(params)),
+                                    grads=types.SimpleNamespace(flat=torch.from_numpy(grads)))
+    bench.dump_outputs(str(tmp_path / 'out'), res, decoder)
+    want = {'loss': np.array([2.5], np.float32), 'logits': logits.transpose(1, 0, 2), 'attn_maps': attn,
+            'decoder_params': params, 'decoder_grads': grads}
+    assert sorted(os.listdir(tmp_path / 'out')) == sorted(k + '.npy' for k in want)
+    for k, v in want.items():
+        got = np.load(str(tmp_path / 'out' / (k + '.npy')))
+        assert got.dtype == np.float32 and np.array_equal(got, v), k
+
+
+
+def test_tune_cache_is_replaced_whole(tmp_path, monkeypatch):
+    """nets.store_tune_cache: the ranks of a run share the tune cache of the run directory, so an update never rewrites
+    the file in place (a rank reading it meanwhile would parse a file cut short): until the rename the file holds its
+    old contents, after it the merged ones, and no file of the writer is left behind."""
+    cache = str(tmp_path / 'conv_variants.json')
+    nets.store_tune_cache(cache, 'a', [1, 2])
+    seen = []
+    real_replace = os.replace
+
+    def replace(src, dst):
+        seen.append(json.load(open(dst)))
+        real_replace(src, dst)
+    monkeypatch.setattr(os, 'replace', replace)
+    nets.store_tune_cache(cache, 'b', [3])
+    assert seen == [{'a': [1, 2]}]
+    assert json.load(open(cache)) == {'a': [1, 2], 'b': [3]} and os.listdir(tmp_path) == ['conv_variants.json']
+
 
 def test_backward_schedule_of_the_branch_lanes():
     """nets.backward_schedule (comic_cnn_backward_sched): every op of the plan exactly once, consumers before producers
