@@ -59,6 +59,56 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
 
+// IEEE half storage of the f16 plans (COMIC_F16): a type of its own, so the kernel templates tell it from bf16_t
+typedef _Float16 f16_t;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+
+// What a kernel needs to know about its 16-bit storage format H (bf16_t or f16_t): the two halves of a packed pair as
+// fp32, the RNE pack of two floats, one element to / from fp32, and the 16x16x32 MFMA on 8-element fragments.  The
+// fragments travel as bf16x8_t bit containers whatever H is (the load / LDS paths only move 16-bit words).
+template <typename H>
+struct Half16;
+template <>
+struct Half16<bf16_t> {
+  static constexpr int code = COMIC_BF16;
+  __device__ static __forceinline__ float lo(uint32_t u) { return __uint_as_float(u << 16); }
+  __device__ static __forceinline__ float hi(uint32_t u) { return __uint_as_float(u & 0xFFFF0000u); }
+  __device__ static __forceinline__ uint32_t pack(float a, float b) { return pack_bf16x2(a, b); }
+  __device__ static __forceinline__ float to_f32(bf16_t v) { return bf16_to_f32(v); }
+  __device__ static __forceinline__ bf16_t from_f32(float f) { return f32_to_bf16(f); }
+  __device__ static __forceinline__ f32x4_t mfma(bf16x8_t a, bf16x8_t b, f32x4_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+};
+template <>
+struct Half16<f16_t> {
+  static constexpr int code = COMIC_F16;
+  __device__ static __forceinline__ float lo(uint32_t u) { return (float)__builtin_bit_cast(f16_t, (unsigned short)(u & 0xFFFFu)); }
+  __device__ static __forceinline__ float hi(uint32_t u) { return (float)__builtin_bit_cast(f16_t, (unsigned short)(u >> 16)); }
+  __device__ static __forceinline__ uint32_t pack(float a, float b) {   // v_cvt_pk_f16_f32 (RNE)
+    const f32x2_t v = {a, b};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));
+  }
+  __device__ static __forceinline__ float to_f32(f16_t v) { return (float)v; }
+  __device__ static __forceinline__ f16_t from_f32(float f) { return (f16_t)f; }
+  __device__ static __forceinline__ f32x4_t mfma(bf16x8_t a, bf16x8_t b, f32x4_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+  }
+};
+// The 16-bit format of a plan element type T: f16_t for f16_t, bf16_t otherwise (templates over T in {float, bf16_t, f16_t}
+// name Half16 in branches the fp32 instantiation never takes).
+template <typename T>
+struct Half16Of {
+  typedef bf16_t type;
+};
+template <>
+struct Half16Of<f16_t> {
+  typedef f16_t type;
+};
+template <typename T>
+using H16 = Half16<typename Half16Of<T>::type>;
+
 // Wave-wide reductions on the DPP data path (VALU-latency lane exchanges) instead of __shfl_xor
 // (ds_bpermute: an LDS round trip per step): 4 row rotations give every lane its 16-lane row total,
 // row_bcast:15 / row_bcast:31 fold the four rows into lane 63, v_readlane broadcasts it.

@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(ConvArgs a) {
       if (sizeof(T) == 4 || a.out_f32) {
         *(float4*)((float*)a.y + off + j) = make_float4(v[0], v[1], v[2], v[3]);
       } else {
-        *(uint2*)((bf16_t*)a.y + off + j) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+        *(uint2*)((bf16_t*)a.y + off + j) = make_uint2(H16<T>::pack(v[0], v[1]), H16<T>::pack(v[2], v[3]));
       }
     }
   }
@@ -411,8 +411,8 @@ __global__ __launch_bounds__(256) void conv_stem_mfma_kernel(ConvArgs a) {
           if (a.relu) {
             v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f);
           }
-          pk[i][0] = pack_bf16x2(v0, v1);
-          pk[i][1] = pack_bf16x2(v2, v3);
+          pk[i][0] = H16<T>::pack(v0, v1);
+          pk[i][1] = H16<T>::pack(v2, v3);
         }
         const auto s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
         const auto s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
@@ -447,7 +447,7 @@ __global__ __launch_bounds__(256) void conv_stem_mfma_kernel(ConvArgs a) {
         *(uint2*)(yp + a.x3) = make_uint2(l01, l23);
         *(uint2*)(yp + 2 * a.x3) = make_uint2(h01, h23);
       } else {
-        *(uint2*)((bf16_t*)a.y + off) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+        *(uint2*)((bf16_t*)a.y + off) = make_uint2(H16<T>::pack(v0, v1), H16<T>::pack(v2, v3));
       }
     }
   }
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(256) void conv_stem_mfma_kernel(ConvArgs a) {
 
 // The same product for stems with a LARGE filter and padding (Inception-V1's Conv2d_1a_7x7: 7x7 / stride 2, SAME, 3 -> 64,
 // common/nets/inception_v1.py:59-60; K = 147).  The direct kernel above spent 4.3 ms on 640 images (47 % of the
-// Inception-V1 forward).  bf16 plans only.
+// Inception-V1 forward).  16-bit plans only.
 //   * a workgroup owns kStemRows output rows of one image; the input rows they need are staged ONCE in LDS as fp32 with
 //     zeroed halo columns / rows (SAME padding costs no per-element test);
 //   * k is re-indexed as k' = 24 kh + j, j = kw * Cin + ci < KW * Cin <= 24 (weights of the pad positions are zero): the
@@ -467,7 +467,7 @@ __global__ __launch_bounds__(256) void conv_stem_mfma_kernel(ConvArgs a) {
 constexpr int kStemRows = 2;          // output rows per workgroup
 constexpr int kStemKRow = 24;         // k' per filter row
 constexpr int kStemFetch = 12;        // float2 a thread moves per staged unit: (rows with weights) * W * Cin / 2 <= 12 * 256
-template <int NT, int KC>
+template <typename HT, int NT, int KC>
 __global__ __launch_bounds__(256) void conv_stem_wide_kernel(ConvArgs a, int lrow, int blocks_per_image, int total_units) {
   extern __shared__ __attribute__((aligned(16))) float xs[];      // two buffers of [(kStemRows - 1) * SH + 8][lrow]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -595,7 +595,7 @@ __global__ __launch_bounds__(256) void conv_stem_wide_kernel(ConvArgs a, int lro
         if (a.out_f32)
           *(float4*)((float*)a.y + o) = make_float4(v0, v1, v2, v3);
         else
-          *(uint2*)((bf16_t*)a.y + o) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+          *(uint2*)((bf16_t*)a.y + o) = make_uint2(Half16<HT>::pack(v0, v1), Half16<HT>::pack(v2, v3));
       }
     }
     if (next < total_units) stash(xs + ((it + 1) & 1) * nrows * lrow, pre);
@@ -621,6 +621,16 @@ __device__ __forceinline__ void load_vec<bf16_t>(const bf16_t* p, float* v) {
     v[2 * i + 1] = __uint_as_float(u[i] & 0xFFFF0000u);
   }
 }
+template <>
+__device__ __forceinline__ void load_vec<f16_t>(const f16_t* p, float* v) {
+  const uint4 t = *(const uint4*)p;
+  const uint32_t u[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = Half16<f16_t>::lo(u[i]);
+    v[2 * i + 1] = Half16<f16_t>::hi(u[i]);
+  }
+}
 template <typename T>
 __device__ __forceinline__ void store_vec(T* p, const float* v);
 template <>
@@ -631,6 +641,11 @@ template <>
 __device__ __forceinline__ void store_vec<bf16_t>(bf16_t* p, const float* v) {
   *(uint4*)p = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
                           pack_bf16x2(v[6], v[7]));
+}
+template <>
+__device__ __forceinline__ void store_vec<f16_t>(f16_t* p, const float* v) {
+  typedef Half16<f16_t> F;
+  *(uint4*)p = make_uint4(F::pack(v[0], v[1]), F::pack(v[2], v[3]), F::pack(v[4], v[5]), F::pack(v[6], v[7]));
 }
 
 // MODE 0: max-pool (VALID or padded with -inf)   MODE 1: avg-pool dividing by valid taps
@@ -786,10 +801,11 @@ __global__ __launch_bounds__(256) void maxpool3_rows_kernel(ConvArgs a) {
   }
 }
 
-// bf16 store of four channels of a kind-7 output; a.x3 (COMIC_OP_X3): as the three regions [hi | lo | hi]
-__device__ __forceinline__ void pbr_store_bf16(const ConvArgs& a, size_t off, float v0, float v1, float v2, float v3) {
+// 16-bit store of four channels of a kind-7 output; a.x3 (COMIC_OP_X3, bf16 plans): as the three regions [hi | lo | hi]
+template <typename HT>
+__device__ __forceinline__ void pbr_store_16(const ConvArgs& a, size_t off, float v0, float v1, float v2, float v3) {
   bf16_t* yp = (bf16_t*)a.y + off;
-  const uint32_t h01 = pack_bf16x2(v0, v1), h23 = pack_bf16x2(v2, v3);
+  const uint32_t h01 = Half16<HT>::pack(v0, v1), h23 = Half16<HT>::pack(v2, v3);
   *(uint2*)yp = make_uint2(h01, h23);
   if (a.x3) {
     const uint32_t l01 = pack_bf16x2(v0 - __uint_as_float(h01 << 16), v1 - __uint_as_float(h01 & 0xFFFF0000u));
@@ -801,6 +817,7 @@ __device__ __forceinline__ void pbr_store_bf16(const ConvArgs& a, size_t off, fl
 
 // kind 7: 3x3 s1 SAME average (divisor = taps inside the image) of an fp32 map, then the folded
 // BatchNorm + ReLU of the projection that produced it.  One thread per (pixel, 4 channels).
+template <typename HT>
 __device__ __forceinline__ void pool_bn_relu_item(const ConvArgs& a, const long idx, const int cvecs) {
   const int cv = (int)(idx % cvecs);
   int mm = (int)(idx / cvecs);
@@ -845,19 +862,21 @@ __device__ __forceinline__ void pool_bn_relu_item(const ConvArgs& a, const long 
   if (a.out_f32)
     *(float4*)((float*)a.y + off) = make_float4(v0, v1, v2, v3);
   else
-    pbr_store_bf16(a, off, v0, v1, v2, v3);
+    pbr_store_16<HT>(a, off, v0, v1, v2, v3);
 }
 
+template <typename HT>
 __global__ __launch_bounds__(256) void pool_bn_relu_kernel(ConvArgs a) {
   const int cvecs = a.Cin / 4;
   const long total = (long)a.M * cvecs;
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx < total) pool_bn_relu_item(a, idx, cvecs);
+  if (idx < total) pool_bn_relu_item<HT>(a, idx, cvecs);
 }
 
 // The same op as one thread per (image row, 4 channels): the thread walks the row and keeps the sums of the last three
 // columns over the (up to three) valid source rows, so every source element is loaded once per output ROW that needs it
 // (3 loads per output instead of 9).  Summation order: rows inside a column first, then the columns left to right.
+template <typename HT>
 __global__ __launch_bounds__(256) void pool_bn_relu_rows_kernel(ConvArgs a) {
   const int cvecs = a.Cin / 4;
   const long total = (long)a.B * a.H * cvecs;
@@ -914,7 +933,7 @@ __global__ __launch_bounds__(256) void pool_bn_relu_rows_kernel(ConvArgs a) {
       if (a.out_f32)
         *(float4*)((float*)a.y + off) = make_float4(v0, v1, v2, v3);
       else
-        pbr_store_bf16(a, off, v0, v1, v2, v3);
+        pbr_store_16<HT>(a, off, v0, v1, v2, v3);
       c0 = c1;
       c1 = c2;
     }
@@ -924,6 +943,7 @@ __global__ __launch_bounds__(256) void pool_bn_relu_rows_kernel(ConvArgs a) {
 // The same work as a member of a grouped conv launch: workgroup `local` of this member handles
 // kPoolItemsPerThread x blockDim.x consecutive (pixel, 4-channel) items.
 constexpr int kPoolItemsPerThread = 4;
+template <typename HT>
 __device__ __forceinline__ void pool_bn_relu_member(const ConvArgs& a, const int local) {
   const int cvecs = a.Cin / 4;
   const long total = (long)a.M * cvecs;
@@ -931,7 +951,7 @@ __device__ __forceinline__ void pool_bn_relu_member(const ConvArgs& a, const int
 #pragma unroll
   for (int r = 0; r < kPoolItemsPerThread; ++r) {
     const long idx = base + (long)r * blockDim.x;
-    if (idx < total) pool_bn_relu_item(a, idx, cvecs);
+    if (idx < total) pool_bn_relu_item<HT>(a, idx, cvecs);
   }
 }
 
@@ -978,7 +998,7 @@ __global__ void pack_conv_weights_kernel(const float* __restrict__ w, T* __restr
   if (sizeof(T) == 4)
     ((float*)out)[idx] = v;
   else
-    ((bf16_t*)out)[idx] = f32_to_bf16(v);
+    ((typename Half16Of<T>::type*)out)[idx] = H16<T>::from_f32(v);
 }
 
 __global__ void fold_bn_kernel(const float* beta, const float* mean, const float* var, float eps, float* scale,
@@ -1018,7 +1038,7 @@ constexpr int kLoaderWaves = 20;
 constexpr int ring_stages(int nstage) { return nstage % 10; }
 constexpr int dma_threads(int wm, int wn, int nstage) { return (wm * wn + (nstage >= kLoaderWaves ? 4 : 0)) * 64; }
 
-template <int BM, int BN, int WM, int WN, int NSTAGE_, bool ALIGNED, bool MASK = false>
+template <typename HT, int BM, int BN, int WM, int WN, int NSTAGE_, bool ALIGNED, bool MASK = false>
 __device__ __forceinline__ void conv_igemm_dma_body(const ConvArgs& a, const int block_m, const int block_n) {
   constexpr int BKE = 64;                       // bf16 elements per k-tile = 128 bytes per row
   constexpr int ROWS = BM + BN;
@@ -1238,8 +1258,8 @@ __device__ __forceinline__ void conv_igemm_dma_body(const ConvArgs& a, const int
     for (int i = 0; i < TN; ++i)
 #pragma unroll
       for (int j = 0; j < TM; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf0[i]),
-                                                            __builtin_bit_cast(bf16x8_t, xf0[j]), acc[i][j], 0, 0, 0);
+        acc[i][j] = Half16<HT>::mfma(__builtin_bit_cast(bf16x8_t, wf0[i]),
+                                                            __builtin_bit_cast(bf16x8_t, xf0[j]), acc[i][j]);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
@@ -1247,8 +1267,8 @@ __device__ __forceinline__ void conv_igemm_dma_body(const ConvArgs& a, const int
     for (int i = 0; i < TN; ++i)
 #pragma unroll
       for (int j = 0; j < TM; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf1[i]),
-                                                            __builtin_bit_cast(bf16x8_t, xf1[j]), acc[i][j], 0, 0, 0);
+        acc[i][j] = Half16<HT>::mfma(__builtin_bit_cast(bf16x8_t, wf1[i]),
+                                                            __builtin_bit_cast(bf16x8_t, xf1[j]), acc[i][j]);
   }
 
   STAMP(2);
@@ -1262,7 +1282,7 @@ __device__ __forceinline__ void conv_igemm_dma_body(const ConvArgs& a, const int
     const int m = bm0 + wm * (BM / WM) + j * 16 + (lane & 15);
     mrow[j] = m < a.M ? m : -1;
   }
-  conv_store_tiles<TN, TM, MASK>(a, acc, bn0 + wn * (BN / WN), (lane >> 4) * 4, mrow);
+  conv_store_tiles<HT, TN, TM, MASK>(a, acc, bn0 + wn * (BN / WN), (lane >> 4) * 4, mrow);
   STAMP(3);
 }
 
@@ -1277,7 +1297,7 @@ __device__ __forceinline__ void conv_igemm_dma_body(const ConvArgs& a, const int
 // Here the k-tile stream of the loader waves runs on across the out-channel tiles (the ring never drains: the first
 // k-tiles of the next tile land under the epilogue of this one), and after the first tile the pixel rows come from the
 // L2 this workgroup has just filled.  Same operands in the same order per accumulator as conv_igemm_dma_body: identical bits.
-template <int BM, int BN, int WM, int WN, int NSTAGE_, bool ALIGNED>
+template <typename HT, int BM, int BN, int WM, int WN, int NSTAGE_, bool ALIGNED>
 __device__ __forceinline__ void conv_igemm_dma_walk_body(const ConvArgs* __restrict__ args, const int n_members, const int block_m,
                                                          const int r_begin, const int r_end) {   // out-channel tiles [r_begin, r_end) of the walk
   constexpr int BKE = 64;
@@ -1476,8 +1496,8 @@ __device__ __forceinline__ void conv_igemm_dma_walk_body(const ConvArgs* __restr
       for (int i = 0; i < TN; ++i)
 #pragma unroll
         for (int j = 0; j < TM; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf0[i]),
-                                                              __builtin_bit_cast(bf16x8_t, xf0[j]), acc[i][j], 0, 0, 0);
+          acc[i][j] = Half16<HT>::mfma(__builtin_bit_cast(bf16x8_t, wf0[i]),
+                                                              __builtin_bit_cast(bf16x8_t, xf0[j]), acc[i][j]);
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
@@ -1485,17 +1505,17 @@ __device__ __forceinline__ void conv_igemm_dma_walk_body(const ConvArgs* __restr
       for (int i = 0; i < TN; ++i)
 #pragma unroll
         for (int j = 0; j < TM; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf1[i]),
-                                                              __builtin_bit_cast(bf16x8_t, xf1[j]), acc[i][j], 0, 0, 0);
+          acc[i][j] = Half16<HT>::mfma(__builtin_bit_cast(bf16x8_t, wf1[i]),
+                                                              __builtin_bit_cast(bf16x8_t, xf1[j]), acc[i][j]);
     }
     int p = 0;
     for (int i = 1; i < n_members; ++i)
       if (r >= args[i].blk0) p = i;
-    conv_store_tiles<TN, TM>(args[p], acc, (r - args[p].blk0) * BN + wn * (BN / WN), (lane >> 4) * 4, mrow);
+    conv_store_tiles<HT, TN, TM>(args[p], acc, (r - args[p].blk0) * BN + wn * (BN / WN), (lane >> 4) * 4, mrow);
   }
 }
 
-template <int BM, int BN, int WM, int WN, int NSTAGE>
+template <typename HT, int BM, int BN, int WM, int WN, int NSTAGE>
 __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_igemm_dma_walk_kernel(const ConvArgs* __restrict__ args, int n, int total,
                                                                                          int split) {
   // split 2 ("paired walk"): the walk of a pixel tile is shared by two workgroups with consecutive logical ids -- they start
@@ -1508,12 +1528,12 @@ __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_igemm_dma_wa
   const int r0 = R * part / split, r1 = R * (part + 1) / split;
   if (r0 >= r1) return;
   if (args[0].Cin % 64 == 0)
-    conv_igemm_dma_walk_body<BM, BN, WM, WN, NSTAGE, true>(args, n, bm, r0, r1);
+    conv_igemm_dma_walk_body<HT, BM, BN, WM, WN, NSTAGE, true>(args, n, bm, r0, r1);
   else
-    conv_igemm_dma_walk_body<BM, BN, WM, WN, NSTAGE, false>(args, n, bm, r0, r1);
+    conv_igemm_dma_walk_body<HT, BM, BN, WM, WN, NSTAGE, false>(args, n, bm, r0, r1);
 }
 
-template <int BM, int BN, int WM, int WN, int NSTAGE, bool ALIGNED>
+template <typename HT, int BM, int BN, int WM, int WN, int NSTAGE, bool ALIGNED>
 __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_igemm_dma_kernel(ConvArgs a) {
   const int tiles_n = (a.Cout + BN - 1) / BN;
   int bm, bn;
@@ -1527,14 +1547,14 @@ __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_igemm_dma_ke
     bm = blockIdx.x % a.tiles_m;
     bn = blockIdx.x / a.tiles_m;
   }
-  conv_igemm_dma_body<BM, BN, WM, WN, NSTAGE, ALIGNED>(a, bm, bn);
+  conv_igemm_dma_body<HT, BM, BN, WM, WN, NSTAGE, ALIGNED>(a, bm, bn);
 }
 
 // Grouped launch: blockIdx.z selects one of several independent convolutions (the same-depth
 // ops of the parallel Inception branches) whose argument records live in device memory.  One
 // launch then carries 2-4x the workgroups of a single 12x12 / 5x5 layer, which is what those
 // layers lack to fill 256 CUs at batch 64.
-template <int BM, int BN, int WM, int WN, int NSTAGE>
+template <typename HT, int BM, int BN, int WM, int WN, int NSTAGE>
 __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_igemm_dma_grouped_kernel(const ConvArgs* __restrict__ args, int n, int total) {
   int bid = blockIdx.x;
   const int remap = args[0].remap;
@@ -1555,9 +1575,9 @@ __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_igemm_dma_gr
       if (r >= args[i].blk0) p = i;
     const ConvArgs a = args[p];
     if (a.Cin % 64 == 0)
-      conv_igemm_dma_body<BM, BN, WM, WN, NSTAGE, true>(a, bm, r - a.blk0);
+      conv_igemm_dma_body<HT, BM, BN, WM, WN, NSTAGE, true>(a, bm, r - a.blk0);
     else
-      conv_igemm_dma_body<BM, BN, WM, WN, NSTAGE, false>(a, bm, r - a.blk0);
+      conv_igemm_dma_body<HT, BM, BN, WM, WN, NSTAGE, false>(a, bm, r - a.blk0);
     return;
   }
   int p = 0;
@@ -1566,7 +1586,7 @@ __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_igemm_dma_gr
   const ConvArgs a = args[p];
   const int local = bid - a.blk0;
   if (a.member_kind == 1) {
-    pool_bn_relu_member(a, local);
+    pool_bn_relu_member<HT>(a, local);
     return;
   }
   int bm, bn;
@@ -1593,9 +1613,9 @@ __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_igemm_dma_gr
     }
   }
   if (a.Cin % 64 == 0)
-    conv_igemm_dma_body<BM, BN, WM, WN, NSTAGE, true>(a, bm, bn);
+    conv_igemm_dma_body<HT, BM, BN, WM, WN, NSTAGE, true>(a, bm, bn);
   else
-    conv_igemm_dma_body<BM, BN, WM, WN, NSTAGE, false>(a, bm, bn);
+    conv_igemm_dma_body<HT, BM, BN, WM, WN, NSTAGE, false>(a, bm, bn);
 }
 
 // comic_cnn_op::min_lds: lower bound on the dynamic LDS a DMA conv workgroup requests.  84 KiB admits one
@@ -1605,45 +1625,45 @@ __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_igemm_dma_gr
 
 #include "conv_patch.inc"
 
-template <int BM, int BN, int WM, int WN, int NSTAGE>
+template <typename HT, int BM, int BN, int WM, int WN, int NSTAGE>
 int launch_dma_grouped(const ConvArgs* args_dev, int n, int total_blocks, int min_lds, hipStream_t st) {
   constexpr int lds0 = ring_stages(NSTAGE) * (BM + BN) * 128;
   const int lds = std::max(lds0, min_lds);
   static PerDeviceOnce attr_once__;
   bool& attr_set = attr_once__.slot();   // hipFuncSetAttribute holds per device
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)conv_igemm_dma_grouped_kernel<BM, BN, WM, WN, NSTAGE>,
+    if (hipFuncSetAttribute((const void*)conv_igemm_dma_grouped_kernel<HT, BM, BN, WM, WN, NSTAGE>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
       comic_set_error("conv: cannot reserve %d bytes of LDS", lds);
       return 1;
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((conv_igemm_dma_grouped_kernel<BM, BN, WM, WN, NSTAGE>), dim3((total_blocks + 7) / 8 * 8),
+  hipLaunchKernelGGL((conv_igemm_dma_grouped_kernel<HT, BM, BN, WM, WN, NSTAGE>), dim3((total_blocks + 7) / 8 * 8),
                      dim3(dma_threads(WM, WN, NSTAGE)), lds, st, args_dev, n, total_blocks);
   return 0;
 }
 
-template <int BM, int BN, int WM, int WN, int NSTAGE>
+template <typename HT, int BM, int BN, int WM, int WN, int NSTAGE>
 int launch_dma_walk(const ConvArgs* args_dev, int n, int total_blocks, int min_lds, hipStream_t st, int split = 1) {
   constexpr int lds0 = ring_stages(NSTAGE) * (BM + BN) * 128;
   const int lds = std::max(lds0, min_lds);
   static PerDeviceOnce attr_once__;
   bool& attr_set = attr_once__.slot();
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)conv_igemm_dma_walk_kernel<BM, BN, WM, WN, NSTAGE>,
+    if (hipFuncSetAttribute((const void*)conv_igemm_dma_walk_kernel<HT, BM, BN, WM, WN, NSTAGE>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
       comic_set_error("conv: cannot reserve %d bytes of LDS", lds);
       return 1;
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((conv_igemm_dma_walk_kernel<BM, BN, WM, WN, NSTAGE>), dim3((total_blocks + 7) / 8 * 8),
+  hipLaunchKernelGGL((conv_igemm_dma_walk_kernel<HT, BM, BN, WM, WN, NSTAGE>), dim3((total_blocks + 7) / 8 * 8),
                      dim3(dma_threads(WM, WN, NSTAGE)), lds, st, args_dev, n, total_blocks, split);
   return 0;
 }
 
-template <int BM, int BN, int WM, int WN, int NSTAGE = 3>
+template <typename HT, int BM, int BN, int WM, int WN, int NSTAGE = 3>
 int launch_dma(const ConvArgs& a, hipStream_t st) {
   static_assert(ring_stages(NSTAGE) >= 2 && ring_stages(NSTAGE) <= 4, "pipeline depth");
   constexpr int lds0 = ring_stages(NSTAGE) * (BM + BN) * 128;
@@ -1652,9 +1672,9 @@ int launch_dma(const ConvArgs& a, hipStream_t st) {
   static PerDeviceOnce attr_once__;
   bool& attr_set = attr_once__.slot();   // hipFuncSetAttribute holds per device
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)conv_igemm_dma_kernel<BM, BN, WM, WN, NSTAGE, true>,
+    if (hipFuncSetAttribute((const void*)conv_igemm_dma_kernel<HT, BM, BN, WM, WN, NSTAGE, true>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)conv_igemm_dma_kernel<BM, BN, WM, WN, NSTAGE, false>,
+        hipFuncSetAttribute((const void*)conv_igemm_dma_kernel<HT, BM, BN, WM, WN, NSTAGE, false>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
       comic_set_error("conv: cannot reserve %d bytes of LDS", lds);
       return 1;
@@ -1670,9 +1690,9 @@ int launch_dma(const ConvArgs& a, hipStream_t st) {
   }
   dim3 grid((unsigned)((total + 7) / 8 * 8));
   if (a.Cin % 64 == 0)
-    hipLaunchKernelGGL((conv_igemm_dma_kernel<BM, BN, WM, WN, NSTAGE, true>), grid, dim3(dma_threads(WM, WN, NSTAGE)), lds, st, b);
+    hipLaunchKernelGGL((conv_igemm_dma_kernel<HT, BM, BN, WM, WN, NSTAGE, true>), grid, dim3(dma_threads(WM, WN, NSTAGE)), lds, st, b);
   else
-    hipLaunchKernelGGL((conv_igemm_dma_kernel<BM, BN, WM, WN, NSTAGE, false>), grid, dim3(dma_threads(WM, WN, NSTAGE)), lds, st, b);
+    hipLaunchKernelGGL((conv_igemm_dma_kernel<HT, BM, BN, WM, WN, NSTAGE, false>), grid, dim3(dma_threads(WM, WN, NSTAGE)), lds, st, b);
   return 0;
 }
 
@@ -1683,7 +1703,7 @@ __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_igemm_dma_ma
   const int tiles_n = (a.Cout + BN - 1) / BN;
   const int l = xcd_tile_index(a.tiles_m * tiles_n);
   if (l < 0) return;
-  conv_igemm_dma_body<BM, BN, WM, WN, NSTAGE, ALIGNED, true>(a, l / tiles_n, l % tiles_n);
+  conv_igemm_dma_body<bf16_t, BM, BN, WM, WN, NSTAGE, ALIGNED, true>(a, l / tiles_n, l % tiles_n);
 }
 
 template <int BM, int BN, int WM, int WN, int NSTAGE = 3>
@@ -1737,6 +1757,7 @@ int img_config(const ConvArgs& a) {
 bool img_same_shape(const ConvArgs& p, const ConvArgs& q) {
   return p.H == q.H && p.W == q.W && p.Cin == q.Cin && p.Cout == q.Cout && p.B == q.B;
 }
+template <typename HT>
 int launch_img_convs(const ConvArgs* a, int n, hipStream_t st) {
   const int cfg = img_config(a[0]);
   if (cfg < 0 || n < 1 || n > kImgMaxMembers) {
@@ -1747,6 +1768,7 @@ int launch_img_convs(const ConvArgs* a, int n, hipStream_t st) {
   ComicImgArgs ia;
   memset(&ia, 0, sizeof(ia));
   ia.n_members = n;
+  ia.f16 = std::is_same<HT, f16_t>::value;
   ia.B = a[0].B; ia.H = a[0].H; ia.W = a[0].W; ia.Cin = a[0].Cin; ia.Cout = a[0].Cout;
   ia.G = comic_img_images_per_group(cfg);
   ia.groups = cdiv(ia.B, ia.G);
@@ -1770,10 +1792,12 @@ int validate_grouped_conv(const comic_cnn_op* op, int xc, int yc, const comic_co
 // Chains of image-resident convs (COMIC_CHAIN_TILE, conv_img.hip conv_img_chain_kernel): the n ops of the group are one or
 // two chains, chain after chain; an op with COMIC_OP_CHAIN_LINK hands its output to the NEXT op of the table through the LDS
 // (its dst buffer is not written), an op without it ends its chain and stores to its dst slice.
+template <typename HT>
 int launch_img_chains(const comic_cnn_op* op, int n, void* const* buffers, const int32_t* buf_channels,
                       const comic_conv_weight* weights, int batch, hipStream_t st) {
   ComicChainArgs ca;
   memset(&ca, 0, sizeof(ca));
+  ca.f16 = std::is_same<HT, f16_t>::value;
   ca.B = batch; ca.H = op[0].H; ca.W = op[0].W; ca.Cin = op[0].Cin;
   const int pxb = ca.Cin * 2;
   ca.PXBp = pxb + ((pxb % 64 == 0) ? 32 : 0);
@@ -1840,65 +1864,66 @@ constexpr int kWalkTile0 = 56, kNumWalkTiles = 6;      // 56..58: one workgroup 
 inline int walk_split(int t) { return t >= kWalkTile0 + 3 ? 2 : 1; }
 inline bool is_walk_tile(int t) { return t >= kWalkTile0 && t < kWalkTile0 + kNumWalkTiles; }
 inline bool is_im2col_tile(int t) { return t <= kNumConvTiles || (t >= kWideTile0 && t < kWideTile0 + kNumWideTiles) || is_walk_tile(t); }
+template <typename HT>
 int launch_dma_tile(int tile, const ConvArgs& a, hipStream_t st) {
   switch (tile) {
-    case 26: return launch_dma<128, 128, 2, 2, 2>(a, st);
-    case 27: return launch_dma<128, 192, 2, 2, 2>(a, st);
-    case 28: return launch_dma<192, 128, 2, 2, 2>(a, st);
-    case 29: return launch_dma<256, 128, 4, 2, 2>(a, st);
-    case 30: return launch_dma<256, 192, 2, 4, 2>(a, st);
-    case 31: return launch_dma<256, 256, 2, 4, 2>(a, st);
-    case 32: return launch_dma<128, 160, 2, 2, 2>(a, st);      // 160-channel layers without a ragged column tile
-    case 33: return launch_dma<256, 64, 4, 1, 2>(a, st);
-    case 34: return launch_dma<192, 96, 2, 2, 2>(a, st);
-    case 35: return launch_dma<128, 192, 2, 2, kLoaderWaves + 3>(a, st);
-    case 36: return launch_dma<128, 128, 2, 2, kLoaderWaves + 3>(a, st);
-    case 37: return launch_dma<128, 256, 2, 2, kLoaderWaves + 3>(a, st);
-    case 38: return launch_dma<192, 128, 2, 2, kLoaderWaves + 3>(a, st);
-    case 39: return launch_dma<128, 160, 2, 2, kLoaderWaves + 3>(a, st);
-    case 40: return launch_dma<192, 192, 2, 2, kLoaderWaves + 2>(a, st);
-    case 41: return launch_dma<128, 192, 2, 2, kLoaderWaves + 4>(a, st);
-    case 42: return launch_dma<160, 192, 2, 2, kLoaderWaves + 3>(a, st);
-    case 43: return launch_dma<192, 160, 2, 2, kLoaderWaves + 3>(a, st);
-    case 44: return launch_dma<192, 192, 2, 2, kLoaderWaves + 3>(a, st);
-    case 45: return launch_dma<64, 128, 2, 2, kLoaderWaves + 3>(a, st);        // small-batch shapes
-    case 46: return launch_dma<128, 64, 2, 2, kLoaderWaves + 3>(a, st);
-    case 47: return launch_dma<64, 64, 2, 2, kLoaderWaves + 4>(a, st);
-    case 1: return launch_dma<128, 128, 2, 2, 3>(a, st);
-    case 2: return launch_dma<128, 64, 2, 2, 3>(a, st);
-    case 3: return launch_dma<64, 64, 2, 2, 3>(a, st);
-    case 4: return launch_dma<32, 64, 1, 4, 3>(a, st);
-    case 5: return launch_dma<128, 32, 4, 1, 3>(a, st);
-    case 6: return launch_dma<64, 128, 2, 2, 3>(a, st);
-    case 7: return launch_dma<256, 64, 4, 1, 3>(a, st);
-    case 8: return launch_dma<128, 64, 2, 2, 4>(a, st);
-    case 9: return launch_dma<64, 64, 2, 2, 4>(a, st);
-    case 10: return launch_dma<32, 64, 1, 4, 4>(a, st);
-    case 11: return launch_dma<64, 128, 2, 2, 4>(a, st);
-    case 12: return launch_dma<128, 32, 4, 1, 4>(a, st);
+    case 26: return launch_dma<HT, 128, 128, 2, 2, 2>(a, st);
+    case 27: return launch_dma<HT, 128, 192, 2, 2, 2>(a, st);
+    case 28: return launch_dma<HT, 192, 128, 2, 2, 2>(a, st);
+    case 29: return launch_dma<HT, 256, 128, 4, 2, 2>(a, st);
+    case 30: return launch_dma<HT, 256, 192, 2, 4, 2>(a, st);
+    case 31: return launch_dma<HT, 256, 256, 2, 4, 2>(a, st);
+    case 32: return launch_dma<HT, 128, 160, 2, 2, 2>(a, st);      // 160-channel layers without a ragged column tile
+    case 33: return launch_dma<HT, 256, 64, 4, 1, 2>(a, st);
+    case 34: return launch_dma<HT, 192, 96, 2, 2, 2>(a, st);
+    case 35: return launch_dma<HT, 128, 192, 2, 2, kLoaderWaves + 3>(a, st);
+    case 36: return launch_dma<HT, 128, 128, 2, 2, kLoaderWaves + 3>(a, st);
+    case 37: return launch_dma<HT, 128, 256, 2, 2, kLoaderWaves + 3>(a, st);
+    case 38: return launch_dma<HT, 192, 128, 2, 2, kLoaderWaves + 3>(a, st);
+    case 39: return launch_dma<HT, 128, 160, 2, 2, kLoaderWaves + 3>(a, st);
+    case 40: return launch_dma<HT, 192, 192, 2, 2, kLoaderWaves + 2>(a, st);
+    case 41: return launch_dma<HT, 128, 192, 2, 2, kLoaderWaves + 4>(a, st);
+    case 42: return launch_dma<HT, 160, 192, 2, 2, kLoaderWaves + 3>(a, st);
+    case 43: return launch_dma<HT, 192, 160, 2, 2, kLoaderWaves + 3>(a, st);
+    case 44: return launch_dma<HT, 192, 192, 2, 2, kLoaderWaves + 3>(a, st);
+    case 45: return launch_dma<HT, 64, 128, 2, 2, kLoaderWaves + 3>(a, st);        // small-batch shapes
+    case 46: return launch_dma<HT, 128, 64, 2, 2, kLoaderWaves + 3>(a, st);
+    case 47: return launch_dma<HT, 64, 64, 2, 2, kLoaderWaves + 4>(a, st);
+    case 1: return launch_dma<HT, 128, 128, 2, 2, 3>(a, st);
+    case 2: return launch_dma<HT, 128, 64, 2, 2, 3>(a, st);
+    case 3: return launch_dma<HT, 64, 64, 2, 2, 3>(a, st);
+    case 4: return launch_dma<HT, 32, 64, 1, 4, 3>(a, st);
+    case 5: return launch_dma<HT, 128, 32, 4, 1, 3>(a, st);
+    case 6: return launch_dma<HT, 64, 128, 2, 2, 3>(a, st);
+    case 7: return launch_dma<HT, 256, 64, 4, 1, 3>(a, st);
+    case 8: return launch_dma<HT, 128, 64, 2, 2, 4>(a, st);
+    case 9: return launch_dma<HT, 64, 64, 2, 2, 4>(a, st);
+    case 10: return launch_dma<HT, 32, 64, 1, 4, 4>(a, st);
+    case 11: return launch_dma<HT, 64, 128, 2, 2, 4>(a, st);
+    case 12: return launch_dma<HT, 128, 32, 4, 1, 4>(a, st);
     // patch-resident variants (stride 1, Cin >= 32): 64*TM pixels x 16*TN channels
-    case 13: return launch_patch<4, 4>(a, st);
-    case 14: return launch_patch<4, 2>(a, st);
-    case 15: return launch_patch<4, 6>(a, st);
-    case 16: return launch_patch<2, 4>(a, st);
-    case 17: return launch_patch<2, 2>(a, st);
-    case 18: return launch_patch<2, 6>(a, st);
+    case 13: return launch_patch<HT, 4, 4>(a, st);
+    case 14: return launch_patch<HT, 4, 2>(a, st);
+    case 15: return launch_patch<HT, 4, 6>(a, st);
+    case 16: return launch_patch<HT, 2, 4>(a, st);
+    case 17: return launch_patch<HT, 2, 2>(a, st);
+    case 18: return launch_patch<HT, 2, 6>(a, st);
     // patch-resident, 8 / 12 waves per workgroup (2-3 per SIMD) over one patch
-    case 19: return launch_patch<4, 4, 4, 2>(a, st);    // 256 px x 128 ch
-    case 20: return launch_patch<4, 4, 4, 3>(a, st);    // 256 px x 192 ch
-    case 21: return launch_patch<4, 4, 8, 1>(a, st);    // 512 px x 64 ch
-    case 22: return launch_patch<4, 2, 4, 2>(a, st);    // 256 px x 64 ch, 8 waves
-    case 23: return launch_patch<4, 6, 4, 2>(a, st);    // 256 px x 192 ch, 8 waves
-    case 24: return launch_patch<2, 4, 4, 2>(a, st);    // 128 px x 128 ch
-    case 25: return launch_patch<2, 6, 4, 2>(a, st);    // 128 px x 192 ch, 8 waves
+    case 19: return launch_patch<HT, 4, 4, 4, 2>(a, st);    // 256 px x 128 ch
+    case 20: return launch_patch<HT, 4, 4, 4, 3>(a, st);    // 256 px x 192 ch
+    case 21: return launch_patch<HT, 4, 4, 8, 1>(a, st);    // 512 px x 64 ch
+    case 22: return launch_patch<HT, 4, 2, 4, 2>(a, st);    // 256 px x 64 ch, 8 waves
+    case 23: return launch_patch<HT, 4, 6, 4, 2>(a, st);    // 256 px x 192 ch, 8 waves
+    case 24: return launch_patch<HT, 2, 4, 4, 2>(a, st);    // 128 px x 128 ch
+    case 25: return launch_patch<HT, 2, 6, 4, 2>(a, st);    // 128 px x 192 ch, 8 waves
     // patch-resident, four MFMA waves + four loader waves
-    case 48: return launch_patch<4, 4, 4, 1, kLoaderWaves + 3>(a, st);   // 256 px x 64 ch
-    case 49: return launch_patch<4, 2, 4, 1, kLoaderWaves + 3>(a, st);   // 256 px x 32 ch
-    case 50: return launch_patch<4, 6, 4, 1, kLoaderWaves + 3>(a, st);   // 256 px x 96 ch
-    case 51: return launch_patch<2, 6, 4, 1, kLoaderWaves + 3>(a, st);   // 128 px x 96 ch
-    case 52: return launch_patch<4, 6, 2, 2, kLoaderWaves + 3>(a, st);   // 128 px x 192 ch
-    case 53: return launch_patch<4, 4, 2, 2, kLoaderWaves + 3>(a, st);   // 128 px x 128 ch
-    case COMIC_IMG_TILE: return launch_img_convs(&a, 1, st);             // image-resident (conv_img.hip)
+    case 48: return launch_patch<HT, 4, 4, 4, 1, kLoaderWaves + 3>(a, st);   // 256 px x 64 ch
+    case 49: return launch_patch<HT, 4, 2, 4, 1, kLoaderWaves + 3>(a, st);   // 256 px x 32 ch
+    case 50: return launch_patch<HT, 4, 6, 4, 1, kLoaderWaves + 3>(a, st);   // 256 px x 96 ch
+    case 51: return launch_patch<HT, 2, 6, 4, 1, kLoaderWaves + 3>(a, st);   // 128 px x 96 ch
+    case 52: return launch_patch<HT, 4, 6, 2, 2, kLoaderWaves + 3>(a, st);   // 128 px x 192 ch
+    case 53: return launch_patch<HT, 4, 4, 2, 2, kLoaderWaves + 3>(a, st);   // 128 px x 128 ch
+    case COMIC_IMG_TILE: return launch_img_convs<HT>(&a, 1, st);             // image-resident (conv_img.hip)
     default:
       comic_set_error("conv: unknown tile id %d", tile);
       return 2;
@@ -1915,48 +1940,49 @@ inline int im2col_tile_threads(int t) { return (t >= 29 && t <= 31) || t >= 35 ?
 inline int tile_bm(int t) { return is_walk_tile(t) ? kWideBM[kWalkBase[t - kWalkTile0] - kWideTile0] : t >= kWideTile0 ? kWideBM[t - kWideTile0] : kTileBM[t]; }
 inline int tile_bn(int t) { return is_walk_tile(t) ? kWideBN[kWalkBase[t - kWalkTile0] - kWideTile0] : t >= kWideTile0 ? kWideBN[t - kWideTile0] : kTileBN[t]; }
 
+template <typename HT>
 int launch_dma_grouped_tile(int tile, const ConvArgs* args_dev, int n, int total_blocks, int min_lds, hipStream_t st) {
   switch (tile) {
-    case 26: return launch_dma_grouped<128, 128, 2, 2, 2>(args_dev, n, total_blocks, min_lds, st);
-    case 27: return launch_dma_grouped<128, 192, 2, 2, 2>(args_dev, n, total_blocks, min_lds, st);
-    case 28: return launch_dma_grouped<192, 128, 2, 2, 2>(args_dev, n, total_blocks, min_lds, st);
-    case 29: return launch_dma_grouped<256, 128, 4, 2, 2>(args_dev, n, total_blocks, min_lds, st);
-    case 30: return launch_dma_grouped<256, 192, 2, 4, 2>(args_dev, n, total_blocks, min_lds, st);
-    case 31: return launch_dma_grouped<256, 256, 2, 4, 2>(args_dev, n, total_blocks, min_lds, st);
-    case 32: return launch_dma_grouped<128, 160, 2, 2, 2>(args_dev, n, total_blocks, min_lds, st);
-    case 33: return launch_dma_grouped<256, 64, 4, 1, 2>(args_dev, n, total_blocks, min_lds, st);
-    case 34: return launch_dma_grouped<192, 96, 2, 2, 2>(args_dev, n, total_blocks, min_lds, st);
-    case 35: return launch_dma_grouped<128, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 36: return launch_dma_grouped<128, 128, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 37: return launch_dma_grouped<128, 256, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 38: return launch_dma_grouped<192, 128, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 39: return launch_dma_grouped<128, 160, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 40: return launch_dma_grouped<192, 192, 2, 2, kLoaderWaves + 2>(args_dev, n, total_blocks, min_lds, st);
-    case 41: return launch_dma_grouped<128, 192, 2, 2, kLoaderWaves + 4>(args_dev, n, total_blocks, min_lds, st);
-    case 42: return launch_dma_grouped<160, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 43: return launch_dma_grouped<192, 160, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 44: return launch_dma_grouped<192, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 45: return launch_dma_grouped<64, 128, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 46: return launch_dma_grouped<128, 64, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 47: return launch_dma_grouped<64, 64, 2, 2, kLoaderWaves + 4>(args_dev, n, total_blocks, min_lds, st);
-    case 56: return launch_dma_walk<192, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 57: return launch_dma_walk<192, 128, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 58: return launch_dma_walk<128, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
-    case 59: return launch_dma_walk<192, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st, 2);
-    case 60: return launch_dma_walk<192, 128, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st, 2);
-    case 61: return launch_dma_walk<128, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st, 2);
-    case 1: return launch_dma_grouped<128, 128, 2, 2, 3>(args_dev, n, total_blocks, min_lds, st);
-    case 2: return launch_dma_grouped<128, 64, 2, 2, 3>(args_dev, n, total_blocks, min_lds, st);
-    case 3: return launch_dma_grouped<64, 64, 2, 2, 3>(args_dev, n, total_blocks, min_lds, st);
-    case 4: return launch_dma_grouped<32, 64, 1, 4, 3>(args_dev, n, total_blocks, min_lds, st);
-    case 5: return launch_dma_grouped<128, 32, 4, 1, 3>(args_dev, n, total_blocks, min_lds, st);
-    case 6: return launch_dma_grouped<64, 128, 2, 2, 3>(args_dev, n, total_blocks, min_lds, st);
-    case 7: return launch_dma_grouped<256, 64, 4, 1, 3>(args_dev, n, total_blocks, min_lds, st);
-    case 8: return launch_dma_grouped<128, 64, 2, 2, 4>(args_dev, n, total_blocks, min_lds, st);
-    case 9: return launch_dma_grouped<64, 64, 2, 2, 4>(args_dev, n, total_blocks, min_lds, st);
-    case 10: return launch_dma_grouped<32, 64, 1, 4, 4>(args_dev, n, total_blocks, min_lds, st);
-    case 11: return launch_dma_grouped<64, 128, 2, 2, 4>(args_dev, n, total_blocks, min_lds, st);
-    case 12: return launch_dma_grouped<128, 32, 4, 1, 4>(args_dev, n, total_blocks, min_lds, st);
+    case 26: return launch_dma_grouped<HT, 128, 128, 2, 2, 2>(args_dev, n, total_blocks, min_lds, st);
+    case 27: return launch_dma_grouped<HT, 128, 192, 2, 2, 2>(args_dev, n, total_blocks, min_lds, st);
+    case 28: return launch_dma_grouped<HT, 192, 128, 2, 2, 2>(args_dev, n, total_blocks, min_lds, st);
+    case 29: return launch_dma_grouped<HT, 256, 128, 4, 2, 2>(args_dev, n, total_blocks, min_lds, st);
+    case 30: return launch_dma_grouped<HT, 256, 192, 2, 4, 2>(args_dev, n, total_blocks, min_lds, st);
+    case 31: return launch_dma_grouped<HT, 256, 256, 2, 4, 2>(args_dev, n, total_blocks, min_lds, st);
+    case 32: return launch_dma_grouped<HT, 128, 160, 2, 2, 2>(args_dev, n, total_blocks, min_lds, st);
+    case 33: return launch_dma_grouped<HT, 256, 64, 4, 1, 2>(args_dev, n, total_blocks, min_lds, st);
+    case 34: return launch_dma_grouped<HT, 192, 96, 2, 2, 2>(args_dev, n, total_blocks, min_lds, st);
+    case 35: return launch_dma_grouped<HT, 128, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 36: return launch_dma_grouped<HT, 128, 128, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 37: return launch_dma_grouped<HT, 128, 256, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 38: return launch_dma_grouped<HT, 192, 128, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 39: return launch_dma_grouped<HT, 128, 160, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 40: return launch_dma_grouped<HT, 192, 192, 2, 2, kLoaderWaves + 2>(args_dev, n, total_blocks, min_lds, st);
+    case 41: return launch_dma_grouped<HT, 128, 192, 2, 2, kLoaderWaves + 4>(args_dev, n, total_blocks, min_lds, st);
+    case 42: return launch_dma_grouped<HT, 160, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 43: return launch_dma_grouped<HT, 192, 160, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 44: return launch_dma_grouped<HT, 192, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 45: return launch_dma_grouped<HT, 64, 128, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 46: return launch_dma_grouped<HT, 128, 64, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 47: return launch_dma_grouped<HT, 64, 64, 2, 2, kLoaderWaves + 4>(args_dev, n, total_blocks, min_lds, st);
+    case 56: return launch_dma_walk<HT, 192, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 57: return launch_dma_walk<HT, 192, 128, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 58: return launch_dma_walk<HT, 128, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st);
+    case 59: return launch_dma_walk<HT, 192, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st, 2);
+    case 60: return launch_dma_walk<HT, 192, 128, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st, 2);
+    case 61: return launch_dma_walk<HT, 128, 192, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, min_lds, st, 2);
+    case 1: return launch_dma_grouped<HT, 128, 128, 2, 2, 3>(args_dev, n, total_blocks, min_lds, st);
+    case 2: return launch_dma_grouped<HT, 128, 64, 2, 2, 3>(args_dev, n, total_blocks, min_lds, st);
+    case 3: return launch_dma_grouped<HT, 64, 64, 2, 2, 3>(args_dev, n, total_blocks, min_lds, st);
+    case 4: return launch_dma_grouped<HT, 32, 64, 1, 4, 3>(args_dev, n, total_blocks, min_lds, st);
+    case 5: return launch_dma_grouped<HT, 128, 32, 4, 1, 3>(args_dev, n, total_blocks, min_lds, st);
+    case 6: return launch_dma_grouped<HT, 64, 128, 2, 2, 3>(args_dev, n, total_blocks, min_lds, st);
+    case 7: return launch_dma_grouped<HT, 256, 64, 4, 1, 3>(args_dev, n, total_blocks, min_lds, st);
+    case 8: return launch_dma_grouped<HT, 128, 64, 2, 2, 4>(args_dev, n, total_blocks, min_lds, st);
+    case 9: return launch_dma_grouped<HT, 64, 64, 2, 2, 4>(args_dev, n, total_blocks, min_lds, st);
+    case 10: return launch_dma_grouped<HT, 32, 64, 1, 4, 4>(args_dev, n, total_blocks, min_lds, st);
+    case 11: return launch_dma_grouped<HT, 64, 128, 2, 2, 4>(args_dev, n, total_blocks, min_lds, st);
+    case 12: return launch_dma_grouped<HT, 128, 32, 4, 1, 4>(args_dev, n, total_blocks, min_lds, st);
     default:
       comic_set_error("conv: unknown tile id %d", tile);
       return 2;
@@ -1991,6 +2017,7 @@ bool ws_group_eligible(const comic_cnn_op* ops, int n) {
   return comic_ws_supported(o.Cin, tiles);
 }
 
+template <typename HT>
 int run_ws_group(const comic_cnn_op* ops, int n, void* const* buffers, const int32_t* buf_channels,
                  const comic_conv_weight* weights, int batch, hipStream_t st) {
   COMIC_REQUIRE(ws_group_eligible(ops, n), "conv_ws: ops are not an eligible 1x1 group (kind %d, %dx%d, Cin %d)", ops[0].kind,
@@ -2007,6 +2034,7 @@ int run_ws_group(const comic_cnn_op* ops, int n, void* const* buffers, const int
   a.Ho = o.Ho; a.Wo = o.Wo; a.M = batch * o.Ho * o.Wo;
   a.pooled = (o.flags & COMIC_OP_POOLED_SRC) ? 1 : 0;
   a.n_members = n;
+  a.f16 = std::is_same<HT, f16_t>::value;
   a.tiles_m = cdiv(a.M, 64);
   int t0 = 0;
   for (int j = 0; j < n; ++j) {
@@ -2078,23 +2106,24 @@ long member_blocks(int tile, ConvArgs& a, int* lds) {
   return (long)a.tiles_m * cdiv(a.Cout, pt.BN);
 }
 
+template <typename HT>
 int dispatch_igemm_dma(const ConvArgs& a, hipStream_t st) {
   // thin-channel stride-1 layers with many pixels (the 109x109 / 52x52 / 25x25 3x3 and 5x5 convs, forward and
   // backward-data): the patch-resident kernel, variants as the autotuner picks them at batch 64
   if (a.SH == 1 && a.SW == 1 && a.Cin >= 32 && a.Cin <= 96 && a.KH * a.KW > 1 && a.M >= 16384) {
     PatchGeo g;
-    if (a.Cout <= 32 && patch_geometry(a, 256, 32, 3, g)) return launch_patch<4, 2>(a, st);
-    if (a.Cout == 96 && patch_geometry(a, 128, 96, 3, g)) return launch_patch<2, 6>(a, st);
-    if (patch_geometry(a, 256, 64, 3, g)) return launch_patch<4, 2, 4, 2>(a, st);
+    if (a.Cout <= 32 && patch_geometry(a, 256, 32, 3, g)) return launch_patch<HT, 4, 2>(a, st);
+    if (a.Cout == 96 && patch_geometry(a, 128, 96, 3, g)) return launch_patch<HT, 2, 6>(a, st);
+    if (patch_geometry(a, 256, 64, 3, g)) return launch_patch<HT, 4, 2, 4, 2>(a, st);
   }
   const long b128x128 = (long)cdiv(a.M, 128) * cdiv(a.Cout, 128);
   const long b128x64 = (long)cdiv(a.M, 128) * cdiv(a.Cout, 64);
   const long b64x64 = (long)cdiv(a.M, 64) * cdiv(a.Cout, 64);
-  if (a.Cout <= 32) return launch_dma<128, 32, 4, 1>(a, st);
-  if (a.Cout % 128 == 0 && b128x128 >= 512) return launch_dma<128, 128, 2, 2>(a, st);
-  if (b128x64 >= 512) return launch_dma<128, 64, 2, 2>(a, st);
-  if (b64x64 >= 384) return launch_dma<64, 64, 2, 2>(a, st);
-  return launch_dma<32, 64, 1, 4>(a, st);
+  if (a.Cout <= 32) return launch_dma<HT, 128, 32, 4, 1>(a, st);
+  if (a.Cout % 128 == 0 && b128x128 >= 512) return launch_dma<HT, 128, 128, 2, 2>(a, st);
+  if (b128x64 >= 512) return launch_dma<HT, 128, 64, 2, 2>(a, st);
+  if (b64x64 >= 384) return launch_dma<HT, 64, 64, 2, 2>(a, st);
+  return launch_dma<HT, 32, 64, 1, 4>(a, st);
 }
 
 const void* zero_page_address() {
@@ -2213,16 +2242,17 @@ int run_op(const comic_cnn_op* op, const void* x, int xc, void* y, int yc, const
       COMIC_REQUIRE(op->Cout % 16 == 0 && op->dst_coff % 4 == 0 && yc % 4 == 0,
                     "conv: Cout must be a multiple of 16 (got %d)", op->Cout);
       COMIC_REQUIRE(op->dst_coff + op->Cout <= (a.x3 ? a.x3 : yc), "conv: destination channel slice out of range");
-      COMIC_REQUIRE(!(op->flags & COMIC_OP_X3) || (sizeof(T) == 2 && yc % 3 == 0 && (yc / 3) % 4 == 0 && !accum),
+      COMIC_REQUIRE(!(op->flags & COMIC_OP_X3) || (std::is_same<T, bf16_t>::value && yc % 3 == 0 && (yc / 3) % 4 == 0 && !accum),
                     "conv: COMIC_OP_X3 needs a bf16 plan and a destination of three equal channel regions");
       if constexpr (sizeof(T) == 2) {
         COMIC_REQUIRE(a.zero, "conv: zero page symbol not resolvable");
         COMIC_REQUIRE((long)batch * op->H * op->W * xc * 2 < (1L << 31), "conv: activation tensor too large");
         if (mask) {
+          COMIC_REQUIRE((std::is_same<T, bf16_t>::value), "conv: the fused activation gradient is a bf16-plan launch");
           if (int rc = dispatch_igemm_dma_mask(a, st)) return rc;
         } else if (op->tile > 0) {
-          if (int rc = launch_dma_tile(op->tile, a, st)) return rc;
-        } else if (int rc = dispatch_igemm_dma(a, st)) {
+          if (int rc = launch_dma_tile<T>(op->tile, a, st)) return rc;
+        } else if (int rc = dispatch_igemm_dma<T>(a, st)) {
           return rc;
         }
       } else if (mask) {
@@ -2254,7 +2284,7 @@ int run_op(const comic_cnn_op* op, const void* x, int xc, void* y, int yc, const
         const int lds_w = 2 * lrow * ((kStemRows - 1) * op->SH + 8) * 4;
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        hipLaunchKernelGGL((conv_stem_wide_kernel<4, 6>), dim3(std::min(total, cus)), dim3(256), lds_w, st, a, lrow, bpi, total);
+        hipLaunchKernelGGL((conv_stem_wide_kernel<typename Half16Of<T>::type, 4, 6>), dim3(std::min(total, cus)), dim3(256), lds_w, st, a, lrow, bpi, total);
       }
       else
         hipLaunchKernelGGL((conv_stem_kernel<T>), dim3(cdiv(a.M, 256)), dim3(256), lds, st, a);
@@ -2268,7 +2298,7 @@ int run_op(const comic_cnn_op* op, const void* x, int xc, void* y, int yc, const
       COMIC_REQUIRE(op->dst_coff + op->Cin <= yc, "pool: destination channel slice out of range");
       const long total = (long)a.M * (op->Cin / EPC);
       if (op->flags & COMIC_OP_X3) {
-        if constexpr (sizeof(T) == 2) {
+        if constexpr (std::is_same<T, bf16_t>::value) {
           COMIC_REQUIRE(xc % 3 == 0 && yc % 3 == 0 && a.x3 > 0 && a.x3_src > 0 && op->src_coff + op->Cin <= a.x3_src &&
                             op->dst_coff + op->Cin <= a.x3 && a.x3 % 8 == 0 && a.x3_src % 8 == 0,
                         "pool (x3): channel regions do not fit the buffers");
@@ -2313,10 +2343,10 @@ int run_op(const comic_cnn_op* op, const void* x, int xc, void* y, int yc, const
       a.out_f32 = (op->out_f32 || sizeof(T) == 4) ? 1 : 0;
       // row-walking form when there are enough rows to occupy the chip (op->tile: 1 forces it, 2 forces the per-pixel form)
       if (op->tile == 1 || (op->tile == 0 && (long)batch * op->H * (op->Cin / 4) >= 256L * 256))
-        hipLaunchKernelGGL(pool_bn_relu_rows_kernel, dim3((unsigned)cdiv64((long)batch * op->H * (op->Cin / 4), 256)), dim3(256),
+        hipLaunchKernelGGL(pool_bn_relu_rows_kernel<typename Half16Of<T>::type>, dim3((unsigned)cdiv64((long)batch * op->H * (op->Cin / 4), 256)), dim3(256),
                            0, st, a);
       else
-        hipLaunchKernelGGL(pool_bn_relu_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(pool_bn_relu_kernel<typename Half16Of<T>::type>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, a);
       break;
     }
     default:
@@ -2449,7 +2479,8 @@ extern "C" int comic_conv2d_bn_relu(const comic_cnn_op* op, const void* x, int x
                                     const comic_conv_weight* wt, int batch, int dtype, void* stream) {
   COMIC_REQUIRE(op, "null op");
   hipStream_t st = (hipStream_t)stream;
-  if (op->kind == 0 && dtype == COMIC_BF16 &&
+  const bool half = dtype == COMIC_BF16 || dtype == COMIC_F16;   // the 16-bit plans
+  if (op->kind == 0 && half &&
       ((op->flags & COMIC_OP_POOLED_SRC) || op->tile == COMIC_WS_TILE || (op->tile == 0 && ws_group_selected(op, 1, batch)))) {
     // a single 1x1 conv on the weight-stationary kernel (conv_ws.hip): one-member group over a two-entry buffer table
     comic_cnn_op o = *op;
@@ -2457,15 +2488,18 @@ extern "C" int comic_conv2d_bn_relu(const comic_cnn_op* op, const void* x, int x
     void* const bufs[2] = {(void*)x, y};
     const int32_t chans[2] = {x_channels, y_channels};
     COMIC_REQUIRE(wt, "conv: missing weights");
-    return run_ws_group(&o, 1, bufs, chans, wt, batch, st);
+    if (dtype == COMIC_F16) return run_ws_group<f16_t>(&o, 1, bufs, chans, wt, batch, st);
+    return run_ws_group<bf16_t>(&o, 1, bufs, chans, wt, batch, st);
   }
-  COMIC_REQUIRE(!(op->kind == 0 && (op->flags & COMIC_OP_POOLED_SRC)), "conv: COMIC_OP_POOLED_SRC needs a bf16 plan");
-  if (dtype == COMIC_BF16 && op->src_f32) {
+  COMIC_REQUIRE(!(op->kind == 0 && (op->flags & COMIC_OP_POOLED_SRC)), "conv: COMIC_OP_POOLED_SRC needs a bf16 or f16 plan");
+  if (half && op->src_f32) {
     COMIC_REQUIRE(op->kind == 4 || op->kind == 7, "src_f32 is only supported by the global average pool and pool+bn");
+    if (op->kind == 7 && dtype == COMIC_F16) return run_op<f16_t>(op, x, x_channels, y, y_channels, wt, batch, st);
     if (op->kind == 7) return run_op<bf16_t>(op, x, x_channels, y, y_channels, wt, batch, st);
     return run_op<float>(op, x, x_channels, y, y_channels, wt, batch, st);
   }
   if (dtype == COMIC_BF16) return run_op<bf16_t>(op, x, x_channels, y, y_channels, wt, batch, st);
+  if (dtype == COMIC_F16) return run_op<f16_t>(op, x, x_channels, y, y_channels, wt, batch, st);
   if (dtype == COMIC_F32) return run_op<float>(op, x, x_channels, y, y_channels, wt, batch, st);
   COMIC_REQUIRE(false, "unknown dtype %d", dtype);
   return 2;
@@ -2496,6 +2530,8 @@ Lanes* get_lanes() {
 }
 }  // namespace
 
+// HT: the 16-bit format of the grouped launches and the stem stream (bf16_t for the fp32 plans, which have neither)
+template <typename HT>
 static int cnn_forward_impl(const comic_cnn_op* ops, int n_ops, void* const* buffers, const int32_t* buf_channels,
                             const comic_conv_weight* weights, int batch, int dtype, const void* group_args_dev,
                             void* stream) {
@@ -2526,11 +2562,11 @@ static int cnn_forward_impl(const comic_cnn_op* ops, int n_ops, void* const* buf
       continue;
     }
     if (gargs && op->group > 0) {
-      COMIC_REQUIRE(dtype == COMIC_BF16 && (op->kind == 0 || op->kind == 7) && op->lane == 0,
-                    "grouped launch needs a bf16 plan and conv / pool+bn ops on the caller's stream");
+      COMIC_REQUIRE(dtype == Half16<HT>::code && (op->kind == 0 || op->kind == 7) && op->lane == 0,
+                    "grouped launch needs a bf16 or f16 plan and conv / pool+bn ops on the caller's stream");
       const int n = group_run(ops, n_ops, i);
       if (ws_group_selected(op, n, batch)) {
-        if (int rc = run_ws_group(op, n, buffers, buf_channels, weights, batch, main_st)) return rc;
+        if (int rc = run_ws_group<HT>(op, n, buffers, buf_channels, weights, batch, main_st)) return rc;
         gargs += n;
         i += n - 1;
         continue;
@@ -2541,7 +2577,7 @@ static int cnn_forward_impl(const comic_cnn_op* ops, int n_ops, void* const* buf
         COMIC_REQUIRE(tile == COMIC_CHAIN_TILE || !(op[j].flags & COMIC_OP_CHAIN_LINK),
                       "conv: COMIC_OP_CHAIN_LINK ops depend on each other -- their group runs on COMIC_CHAIN_TILE only (got tile %d)", tile);
       if (tile == COMIC_CHAIN_TILE) {
-        if (int rc = launch_img_chains(op, n, buffers, buf_channels, weights, batch, main_st)) return rc;
+        if (int rc = launch_img_chains<HT>(op, n, buffers, buf_channels, weights, batch, main_st)) return rc;
         COMIC_LAUNCH_CHECK("image-resident conv chains");
         gargs += n;
         i += n - 1;
@@ -2567,7 +2603,7 @@ static int cnn_forward_impl(const comic_cnn_op* ops, int n_ops, void* const* buf
               run[nr++] = ma[q];
               done[q] = true;
             }
-          if (int rc = launch_img_convs(run, nr, main_st)) return rc;
+          if (int rc = launch_img_convs<HT>(run, nr, main_st)) return rc;
         }
         COMIC_LAUNCH_CHECK("image-resident conv group");
         gargs += n;
@@ -2590,8 +2626,8 @@ static int cnn_forward_impl(const comic_cnn_op* ops, int n_ops, void* const* buf
       COMIC_REQUIRE(blocks > 0 && blocks < (1L << 31), "grouped launch: bad workgroup count");
       if (is_walk_tile(tile)) blocks = (long)cdiv(batch * op->Ho * op->Wo, tile_bm(tile)) * walk_split(tile);   // one (or two) workgroups per pixel tile
       if (!is_im2col_tile(tile)) {
-        if (int rc = launch_patch_grouped_tile(tile, gargs, n, (int)blocks, std::max(lds_max, op->min_lds), main_st)) return rc;
-      } else if (int rc = launch_dma_grouped_tile(tile, gargs, n, (int)blocks, op->min_lds, main_st)) {
+        if (int rc = launch_patch_grouped_tile<HT>(tile, gargs, n, (int)blocks, std::max(lds_max, op->min_lds), main_st)) return rc;
+      } else if (int rc = launch_dma_grouped_tile<HT>(tile, gargs, n, (int)blocks, op->min_lds, main_st)) {
         return rc;
       }
       COMIC_LAUNCH_CHECK("grouped conv");
@@ -2611,7 +2647,7 @@ static int cnn_forward_impl(const comic_cnn_op* ops, int n_ops, void* const* buf
       // Conv2d_1a (stem layout), Conv2d_2a, Conv2d_2b
       const bool with_1a = op->kind == 9;
       const int H0 = with_1a ? (op->H - 3) / 2 + 1 : op->H, W0 = with_1a ? (op->W - 3) / 2 + 1 : op->W;
-      COMIC_REQUIRE(dtype == COMIC_BF16 && op->lane == 0, "stem stream: bf16 plans on the caller's stream only");
+      COMIC_REQUIRE(dtype == Half16<HT>::code && op->lane == 0, "stem stream: bf16 / f16 plans on the caller's stream only");
       COMIC_REQUIRE(op->Cin == (with_1a ? 3 : 32) && op->Cout == 64 && op->KH == 3 && op->KW == 3 && op->SH == 1 && op->SW == 1,
                     "stem stream: expects the (3 ->) 32 -> 32 -> 64 3x3 stem (got Cin %d, Cout %d)", op->Cin, op->Cout);
       COMIC_REQUIRE(comic_stem_stream_supported(H0, W0) && (!with_1a || comic_stem_stream_1a_supported(op->H, op->W)),
@@ -2642,6 +2678,7 @@ static int cnn_forward_impl(const comic_cnn_op* ops, int n_ops, void* const* buf
       sa.sc1 = wa->scale; sa.sh1 = wa->shift; sa.sc2 = wb->scale; sa.sh2 = wb->shift;
       sa.y = (bf16_t*)buffers[op->dst]; sa.y_cs = yc; sa.y_co = op->dst_coff; sa.Hp = Hp; sa.Wp = Wp;
       sa.n_tasks = 2 * batch;
+      sa.f16 = std::is_same<HT, f16_t>::value;
       if (int rc = comic_stem_stream_launch(sa, main_st)) return rc;
       COMIC_LAUNCH_CHECK("stem stream");
       continue;
@@ -2656,7 +2693,8 @@ static int cnn_forward_impl(const comic_cnn_op* ops, int n_ops, void* const* buf
 
 extern "C" int comic_cnn_forward(const comic_cnn_op* ops, int n_ops, void* const* buffers, const int32_t* buf_channels,
                                  const comic_conv_weight* weights, int batch, int dtype, void* stream) {
-  return cnn_forward_impl(ops, n_ops, buffers, buf_channels, weights, batch, dtype, nullptr, stream);
+  if (dtype == COMIC_F16) return cnn_forward_impl<f16_t>(ops, n_ops, buffers, buf_channels, weights, batch, dtype, nullptr, stream);
+  return cnn_forward_impl<bf16_t>(ops, n_ops, buffers, buf_channels, weights, batch, dtype, nullptr, stream);
 }
 
 extern "C" int comic_cnn_forward_grouped(const comic_cnn_op* ops, int n_ops, void* const* buffers,
@@ -2664,7 +2702,9 @@ extern "C" int comic_cnn_forward_grouped(const comic_cnn_op* ops, int n_ops, voi
                                          int dtype, const void* group_args_dev, void* stream) {
   COMIC_REQUIRE(group_args_dev || comic_cnn_group_args_bytes(ops, n_ops) == 0,
                 "comic_cnn_forward_grouped: plan has grouped ops but no argument records");
-  return cnn_forward_impl(ops, n_ops, buffers, buf_channels, weights, batch, dtype, group_args_dev, stream);
+  if (dtype == COMIC_F16)
+    return cnn_forward_impl<f16_t>(ops, n_ops, buffers, buf_channels, weights, batch, dtype, group_args_dev, stream);
+  return cnn_forward_impl<bf16_t>(ops, n_ops, buffers, buf_channels, weights, batch, dtype, group_args_dev, stream);
 }
 
 extern "C" int comic_pack_conv_weights(const float* w_hwio, void* w_packed, int kh, int kw, int cin, int cout,
@@ -2675,6 +2715,9 @@ extern "C" int comic_pack_conv_weights(const float* w_hwio, void* w_packed, int 
   if (dtype == COMIC_BF16)
     hipLaunchKernelGGL((pack_conv_weights_kernel<bf16_t>), dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st,
                        w_hwio, (bf16_t*)w_packed, K, Kpad, cout);
+  else if (dtype == COMIC_F16)
+    hipLaunchKernelGGL((pack_conv_weights_kernel<f16_t>), dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st,
+                       w_hwio, (f16_t*)w_packed, K, Kpad, cout);
   else
     hipLaunchKernelGGL((pack_conv_weights_kernel<float>), dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st,
                        w_hwio, (float*)w_packed, K, Kpad, cout);
@@ -4112,6 +4155,7 @@ extern "C" int comic_cnn_backward_sched(const comic_cnn_op* ops, int n_ops, cons
                                         int64_t scratch_bytes, void* stream0, void* stream1, void* wgrad_stream) {
   COMIC_REQUIRE(ops && sched && buffers && grad_buffers && buf_channels && weights && grads && scratch,
                 "comic_cnn_backward_sched: null argument");
+  COMIC_REQUIRE(dtype != COMIC_F16, "comic_cnn_backward_sched: f16 plans have no backward (cnn_finetune runs on bf16, bf16x3 or fp32 plans)");
   if (dtype == COMIC_BF16)
     return cnn_backward_sched_impl<bf16_t>(ops, n_ops, sched, n_sched, buffers, grad_buffers, grad_buffers_alt, buf_channels,
                                            weights, grads, batch, scratch, scratch_bytes, (hipStream_t)stream0,
@@ -4129,6 +4173,10 @@ extern "C" int comic_cnn_backward_sched(const comic_cnn_op* ops, int n_ops, cons
 
 extern "C" int64_t comic_cnn_backward_scratch_bytes(const comic_cnn_op* ops, int n_ops, int batch, int dtype, int lanes) {
   if (!ops) return -1;
+  if (dtype != COMIC_BF16 && dtype != COMIC_F32) {
+    comic_set_error("comic_cnn_backward_scratch_bytes: dtype %d has no backward (bf16 or fp32 plans only)", dtype);
+    return -1;
+  }
   return backward_scratch_bytes(ops, n_ops, batch, dtype == COMIC_BF16 ? 2 : 4, lanes > 1);
 }
 
@@ -4164,6 +4212,7 @@ extern "C" int comic_cnn_pack_x3_weights(const float* const* masters, void* cons
 extern "C" int comic_cnn_pack_bwd_filters(const comic_cnn_op* ops, int n_ops, const comic_conv_grad* grads, int dtype,
                                           void* stream) {
   COMIC_REQUIRE(ops && grads, "comic_cnn_pack_bwd_filters: null argument");
+  COMIC_REQUIRE(dtype != COMIC_F16, "comic_cnn_pack_bwd_filters: f16 plans have no backward (cnn_finetune runs on bf16, bf16x3 or fp32 plans)");
   if (dtype == COMIC_BF16) return pack_bwd_filters_impl<bf16_t>(ops, n_ops, grads, (hipStream_t)stream);
   if (dtype == COMIC_F32) return pack_bwd_filters_impl<float>(ops, n_ops, grads, (hipStream_t)stream);
   COMIC_REQUIRE(false, "unknown dtype %d", dtype);
@@ -4176,6 +4225,7 @@ extern "C" int comic_cnn_backward(const comic_cnn_op* ops, int n_ops, void* cons
                                   int64_t scratch_bytes, void* stream, void* wgrad_stream) {
   COMIC_REQUIRE(ops && buffers && grad_buffers && buf_channels && weights && grads && scratch,
                 "comic_cnn_backward: null argument");
+  COMIC_REQUIRE(dtype != COMIC_F16, "comic_cnn_backward: f16 plans have no backward (cnn_finetune runs on bf16, bf16x3 or fp32 plans)");
   hipStream_t st = (hipStream_t)stream, st_w = (hipStream_t)wgrad_stream;
   if (dtype == COMIC_BF16)
     return cnn_backward_impl<bf16_t>(ops, n_ops, buffers, grad_buffers, buf_channels, weights, grads, batch, scratch,
@@ -4189,9 +4239,10 @@ extern "C" int comic_cnn_backward(const comic_cnn_op* ops, int n_ops, void* cons
 
 // fp32 master -> plan-dtype copy of a flat parameter block (the packed layouts are identical)
 namespace {
-__global__ void f32_to_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, long n) {
+template <typename HT>
+__global__ void f32_to_half_kernel(const float* __restrict__ in, HT* __restrict__ out, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = f32_to_bf16(in[i]);
+  if (i < n) out[i] = Half16<HT>::from_f32(in[i]);
 }
 __global__ void refold_bn_kernel(const float* __restrict__ beta, const float* __restrict__ mean,
                                  const float* __restrict__ scale, float* __restrict__ shift, long n) {
@@ -4200,14 +4251,19 @@ __global__ void refold_bn_kernel(const float* __restrict__ beta, const float* __
 }
 }  // namespace
 
-extern "C" int comic_cnn_refresh_weights(const float* master, void* plan_copy, int64_t n, const float* beta,
-                                         const float* mean, const float* scale, float* shift, int64_t channels,
-                                         void* stream) {
+extern "C" int comic_cnn_refresh_weights_dtype(const float* master, void* plan_copy, int64_t n, const float* beta,
+                                               const float* mean, const float* scale, float* shift, int64_t channels,
+                                               int dtype, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  COMIC_REQUIRE(dtype == COMIC_BF16 || dtype == COMIC_F16, "cnn_refresh_weights: the plan copy is bf16 or f16 (got dtype %d)", dtype);
   if (plan_copy && n > 0) {
     COMIC_REQUIRE(master, "cnn_refresh_weights: null master");
-    hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, master, (bf16_t*)plan_copy,
-                       (long)n);
+    if (dtype == COMIC_F16)
+      hipLaunchKernelGGL(f32_to_half_kernel<f16_t>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, master, (f16_t*)plan_copy,
+                         (long)n);
+    else
+      hipLaunchKernelGGL(f32_to_half_kernel<bf16_t>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, master, (bf16_t*)plan_copy,
+                         (long)n);
   }
   if (channels > 0) {
     COMIC_REQUIRE(beta && mean && scale && shift, "cnn_refresh_weights: null BN arrays");
@@ -4216,6 +4272,12 @@ extern "C" int comic_cnn_refresh_weights(const float* master, void* plan_copy, i
   }
   COMIC_LAUNCH_CHECK("cnn_refresh_weights");
   return 0;
+}
+
+extern "C" int comic_cnn_refresh_weights(const float* master, void* plan_copy, int64_t n, const float* beta,
+                                         const float* mean, const float* scale, float* shift, int64_t channels,
+                                         void* stream) {
+  return comic_cnn_refresh_weights_dtype(master, plan_copy, n, beta, mean, scale, shift, channels, COMIC_BF16, stream);
 }
 
 #ifdef COMIC_STAMPS

@@ -51,6 +51,10 @@ template <>
 struct Elem<bf16_t> {
   static constexpr int EPC = 8;
 };
+template <>
+struct Elem<f16_t> {
+  static constexpr int EPC = 8;
+};
 
 
 #ifdef COMIC_STAMPS
@@ -85,15 +89,16 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-// Epilogue shared by the bf16 conv kernels: y = relu(acc * scale[n] + shift[n]) for a wave's TN x TM
+// Epilogue shared by the 16-bit conv kernels: y = relu(acc * scale[n] + shift[n]) for a wave's TN x TM
 // 16x16 accumulator tiles.  Lane (mcol = lane & 15, nq = (lane >> 4) * 4) holds 4 consecutive output
 // channels n0..n0+3 of pixel mrow[j] (< 0: no such pixel).  Every scale / shift vector is loaded up
 // front and the arithmetic is branch-free, so the only vector-memory wait in here is the one for those
 // loads: with the loads inside the per-tile branches the compiler has to drain vmcnt(0) at the top of
 // every tile, i.e. each store waited for the previous store's round trip.
+// HT: the 16-bit storage format of the plan (bf16_t, f16_t); the COMIC_OP_X3 and MASK paths are bf16-plan only.
 // MASK: the launch is a backward-data conv fused with its producer's activation gradient (ConvArgs::mask_y).  A template
 // parameter, not a runtime branch: the extra registers of that path pushed every forward kernel into spills otherwise.
-template <int TN, int TM, bool MASK = false>
+template <typename HT, int TN, int TM, bool MASK = false>
 __device__ __forceinline__ void conv_store_tiles(const ConvArgs& a, f32x4_t (&acc)[TN][TM], const int nbase,
                                                  const int nq, const int (&mrow)[TM]) {
   float4 sc[TN], sh[TN];
@@ -189,7 +194,7 @@ __device__ __forceinline__ void conv_store_tiles(const ConvArgs& a, f32x4_t (&ac
     }
     return;
   }
-  // bf16, plain store, 16-byte aligned pixel rows: pairs of channel tiles are written as 16 B per lane.  A lane
+  // 16-bit, plain store, 16-byte aligned pixel rows: pairs of channel tiles are written as 16 B per lane.  A lane
   // holds channels [4q, 4q+4) of both tiles (q = lane >> 4); v_permlane16_swap exchanges the odd 16-lane rows of
   // tile i with the even rows of tile i+1, after which rows 0 / 2 hold channels [0,8) / [8,16) of tile i and rows
   // 1 / 3 the same of tile i+1: half the store instructions, 64 contiguous bytes per pixel instead of 4 x 8.
@@ -213,8 +218,8 @@ __device__ __forceinline__ void conv_store_tiles(const ConvArgs& a, f32x4_t (&ac
           asm("v_max_f32 %0, %1, %2" : "=v"(v1) : "v"(v1), "s"(lo));
           asm("v_max_f32 %0, %1, %2" : "=v"(v2) : "v"(v2), "s"(lo));
           asm("v_max_f32 %0, %1, %2" : "=v"(v3) : "v"(v3), "s"(lo));
-          pk[t][0] = pack_bf16x2(v0, v1);
-          pk[t][1] = pack_bf16x2(v2, v3);
+          pk[t][0] = Half16<HT>::pack(v0, v1);
+          pk[t][1] = Half16<HT>::pack(v2, v3);
         }
         const auto s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
         const auto s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
@@ -232,7 +237,7 @@ __device__ __forceinline__ void conv_store_tiles(const ConvArgs& a, f32x4_t (&ac
         asm("v_max_f32 %0, %1, %2" : "=v"(v1) : "v"(v1), "s"(lo));
         asm("v_max_f32 %0, %1, %2" : "=v"(v2) : "v"(v2), "s"(lo));
         asm("v_max_f32 %0, %1, %2" : "=v"(v3) : "v"(v3), "s"(lo));
-        if (nv[i] & mok) *(uint2*)(ypix + (i * 16 + nq) * 2) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+        if (nv[i] & mok) *(uint2*)(ypix + (i * 16 + nq) * 2) = make_uint2(Half16<HT>::pack(v0, v1), Half16<HT>::pack(v2, v3));
       }
     }
     return;
@@ -267,11 +272,11 @@ __device__ __forceinline__ void conv_store_tiles(const ConvArgs& a, f32x4_t (&ac
         if (a.accum) {
           if (ok) {
             const uint2 o = *yp;
-            v0 += __uint_as_float(o.x << 16); v1 += __uint_as_float(o.x & 0xFFFF0000u);
-            v2 += __uint_as_float(o.y << 16); v3 += __uint_as_float(o.y & 0xFFFF0000u);
+            v0 += Half16<HT>::lo(o.x); v1 += Half16<HT>::hi(o.x);
+            v2 += Half16<HT>::lo(o.y); v3 += Half16<HT>::hi(o.y);
           }
         }
-        if (ok) *yp = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+        if (ok) *yp = make_uint2(Half16<HT>::pack(v0, v1), Half16<HT>::pack(v2, v3));
       }
     }
   }

@@ -20,6 +20,7 @@ struct ComicImgArgs {
   int G, groups;            // images per workgroup, workgroups per member = ceil(B / G)
   int PXBp;                 // bytes per resident pixel (Cin * 2, padded to an odd multiple of 32)
   int KS32;                 // 32-deep k-steps per 16-channel tile in the packed weights (= Kpad / 32)
+  int f16;                  // 1: IEEE half activations / weights (COMIC_F16 plans), 0: bf16
 };
 
 // config id (>= 0) of the kernel instantiation that serves this shape, -1: not eligible
@@ -47,6 +48,7 @@ struct ComicChainArgs {
   ComicChainMember m[kChainMaxMembers];     // member 0: the longer chain
   int n_members;
   int B, H, W, Cin, PXBp;   // Cin = input channels of every conv = output channels of every conv but a chain's last (192)
+  int f16;                  // 1: IEEE half activations / weights (COMIC_F16 plans), 0: bf16
 };
 int comic_img_chain_supported(int H, int W, int Cin);
 int comic_img_chain_launch(const ComicChainArgs& a, hipStream_t st);

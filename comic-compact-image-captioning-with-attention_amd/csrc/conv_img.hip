@@ -74,7 +74,7 @@ __device__ __forceinline__ void img_pixel_state(int lane, int wm, int P, int H, 
 // The k loop of one convolution over the resident pixels: acc[i][j] = sum over (tap, channel step) of W-fragment x pixel
 // fragment, k order (kh, kw, c) as in conv_igemm_dma_body.  SYNC: a workgroup barrier between the first weight requests and
 // the first LDS read (the patch fill of conv_img_kernel ends there).
-template <int TM, int TN, int CS, int PD, bool SYNC>
+template <typename HT, int TM, int TN, int CS, int PD, bool SYNC>
 __device__ __forceinline__ void img_kloop(const unsigned char* smem, uint32_t zoff, const uint32_t (&pixaddr)[TM],
                                           const uint32_t (&mask)[TM], const bf16_t* wf, int Cout, int KS32, int KH, int KW,
                                           int PT, int PL, int W, int PXBp, int wn, int lane, f32x4_t (&acc)[TN][TM]) {
@@ -133,8 +133,8 @@ __device__ __forceinline__ void img_kloop(const unsigned char* smem, uint32_t zo
       for (int i = 0; i < TN; ++i)
 #pragma unroll
         for (int j = 0; j < TM; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wq[0][i]),
-                                                              __builtin_bit_cast(bf16x8_t, xf[j]), acc[i][j], 0, 0, 0);
+          acc[i][j] = Half16<HT>::mfma(__builtin_bit_cast(bf16x8_t, wq[0][i]),
+                                                              __builtin_bit_cast(bf16x8_t, xf[j]), acc[i][j]);
 #pragma unroll
       for (int d = 0; d < PD; ++d)
 #pragma unroll
@@ -148,7 +148,7 @@ __device__ __forceinline__ void img_kloop(const unsigned char* smem, uint32_t zo
   }
 }
 
-template <int TM, int TN, int WM, int WN, int CS, int PD = 2>
+template <typename HT, int TM, int TN, int WM, int WN, int CS, int PD = 2>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN <= 4 ? 2 : WM * WN <= 5 ? 3 : 1)) void conv_img_kernel(const ComicImgArgs a) {
   constexpr int NT = 64 * WM * WN;
   constexpr int CPP = CS * 4;            // 16-byte chunks per pixel (Cin = 32 * CS)
@@ -195,14 +195,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN <= 4 ? 2 : WM * WN <= 5 ? 3 
   int mrow[TM];
   img_pixel_state<TM>(lane, wm, P, a.H, a.W, PXBp, m.KH, m.KW, m.PT, m.PL, img0, pixaddr, mask, mrow);
   f32x4_t acc[TN][TM];
-  img_kloop<TM, TN, CS, PD, true>(smem, zoff, pixaddr, mask, m.wf, a.Cout, a.KS32, m.KH, m.KW, m.PT, m.PL, a.W, PXBp, wn, lane, acc);
+  img_kloop<HT, TM, TN, CS, PD, true>(smem, zoff, pixaddr, mask, m.wf, a.Cout, a.KS32, m.KH, m.KW, m.PT, m.PL, a.W, PXBp, wn, lane, acc);
 
   // ---- epilogue: BatchNorm + ReLU + store, shared with the other bf16 conv kernels ----------------------------------
   ConvArgs ca;
   ca.scale = m.scale; ca.shift = m.shift; ca.y = m.y; ca.y_cs = m.y_cs; ca.y_co = m.y_co; ca.Cout = a.Cout;
   ca.relu = m.relu; ca.out_f32 = m.out_f32; ca.accum = 0; ca.x3 = 0; ca.x3_src = 0;   // (x3 plans carry no fragment-order weights: never here)
   ca.mask_y = nullptr;     // (no fused activation gradient: a forward kernel)
-  conv_store_tiles<TN, TM>(ca, acc, wn * TN * 16, fg * 4, mrow);
+  conv_store_tiles<HT, TN, TM>(ca, acc, wn * TN * 16, fg * 4, mrow);
 }
 
 // ---- Branch chains of Mixed_6b-e (common/nets/inception_v3.py:262-345): 1x7 -> 7x1 and 7x1 -> 1x7 -> 7x1 -> 1x7 ------------
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN <= 4 ? 2 : WM * WN <= 5 ? 3 
 // chain of single launches.
 // TNI: 16-channel tiles per wave of the INNER convs (Cout = Cin: 2 at 128 channels, 3 at 160 -- ragged, as cfg 4 -- and
 // 192); the last conv of a chain has 192 output channels (three tiles per wave).
-template <int TM, int TNI, int CS, int PD = 2>
+template <typename HT, int TM, int TNI, int CS, int PD = 2>
 __global__ __launch_bounds__(256, 2) void conv_img_chain_kernel(const ComicChainArgs a) {
   constexpr int NT = 256, WN = 4;
   constexpr int CPP = CS * 4;
@@ -265,8 +265,8 @@ __global__ __launch_bounds__(256, 2) void conv_img_chain_kernel(const ComicChain
     const ComicChainConv& c = m.c[ci];
     img_pixel_state<TM>(lane, 0, P, a.H, a.W, PXBp, c.KH, c.KW, c.PT, c.PL, img0, pixaddr, mask, mrow);
     f32x4_t acc[TNI][TM];
-    img_kloop<TM, TNI, CS, PD, false>(smem, zoff, pixaddr, mask, c.wf, a.Cin, c.KS32, c.KH, c.KW, c.PT, c.PL, a.W, PXBp, wn, lane, acc);
-    // BatchNorm + ReLU + bf16 as conv_store_tiles computes them, written over the patch: lane (fr, fg) holds channels
+    img_kloop<HT, TM, TNI, CS, PD, false>(smem, zoff, pixaddr, mask, c.wf, a.Cin, c.KS32, c.KH, c.KW, c.PT, c.PL, a.W, PXBp, wn, lane, acc);
+    // BatchNorm + ReLU + 16-bit pack as conv_store_tiles computes them, written over the patch: lane (fr, fg) holds channels
     // [n0 + 4 fg, + 4) of pixel 16 j + fr
     float4 sc[TNI], sh[TNI];
     bool nv[TNI];
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void conv_img_chain_kernel(const ComicChain
         asm("v_max_f32 %0, %1, %2" : "=v"(v1) : "v"(v1), "s"(lo));
         asm("v_max_f32 %0, %1, %2" : "=v"(v2) : "v"(v2), "s"(lo));
         asm("v_max_f32 %0, %1, %2" : "=v"(v3) : "v"(v3), "s"(lo));
-        const uint2 pk = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+        const uint2 pk = make_uint2(Half16<HT>::pack(v0, v1), Half16<HT>::pack(v2, v3));
         if (nv[i]) *(uint2*)(prow + i * 32) = pk;
         // COMIC_OP_CHAIN_KEEP (trainable plans: the backward reads every conv's output): the same bits go to the conv's own
         // destination as well -- a store that nothing of this launch waits for
@@ -306,12 +306,12 @@ __global__ __launch_bounds__(256, 2) void conv_img_chain_kernel(const ComicChain
     const ComicChainConv& c = m.c[nc - 1];
     img_pixel_state<TM>(lane, 0, P, a.H, a.W, PXBp, c.KH, c.KW, c.PT, c.PL, img0, pixaddr, mask, mrow);
     f32x4_t acc[3][TM];
-    img_kloop<TM, 3, CS, PD, false>(smem, zoff, pixaddr, mask, c.wf, c.Cout, c.KS32, c.KH, c.KW, c.PT, c.PL, a.W, PXBp, wn, lane, acc);
+    img_kloop<HT, TM, 3, CS, PD, false>(smem, zoff, pixaddr, mask, c.wf, c.Cout, c.KS32, c.KH, c.KW, c.PT, c.PL, a.W, PXBp, wn, lane, acc);
     ConvArgs ca;
     ca.scale = c.scale; ca.shift = c.shift; ca.y = m.y; ca.y_cs = m.y_cs; ca.y_co = m.y_co; ca.Cout = c.Cout;
     ca.relu = c.relu; ca.out_f32 = m.out_f32; ca.accum = 0; ca.x3 = 0; ca.x3_src = 0;
     ca.mask_y = nullptr;
-    conv_store_tiles<3, TM>(ca, acc, wn * 3 * 16, fg * 4, mrow);
+    conv_store_tiles<HT, 3, TM>(ca, acc, wn * 3 * 16, fg * 4, mrow);
   }
 }
 
@@ -349,7 +349,7 @@ constexpr ImgCfg kCfg[] = {
 };
 constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
 
-template <int TM, int TN, int WM, int WN, int CS, int PD = 2>
+template <typename HT, int TM, int TN, int WM, int WN, int CS, int PD = 2>
 int launch_img(const ComicImgArgs& a, hipStream_t st) {
   const int lds = ((TM * WM * 16 * a.PXBp + 255) & ~255) + img_zero_bytes(CS);
   if (lds > 160 * 1024) {
@@ -359,32 +359,32 @@ int launch_img(const ComicImgArgs& a, hipStream_t st) {
   static PerDeviceOnce attr_once__;
   bool& attr_set = attr_once__.slot();   // hipFuncSetAttribute holds per device
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)conv_img_kernel<TM, TN, WM, WN, CS, PD>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)conv_img_kernel<HT, TM, TN, WM, WN, CS, PD>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024) != hipSuccess) {
       comic_set_error("conv_img: cannot reserve %d bytes of LDS", lds);
       return 1;
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((conv_img_kernel<TM, TN, WM, WN, CS, PD>), dim3(a.groups * a.n_members), dim3(64 * WM * WN), lds, st, a);
+  hipLaunchKernelGGL((conv_img_kernel<HT, TM, TN, WM, WN, CS, PD>), dim3(a.groups * a.n_members), dim3(64 * WM * WN), lds, st, a);
   return 0;
 }
 
-template <int TNI, int CS>
+template <typename HT, int TNI, int CS>
 int launch_chain(const ComicChainArgs& a, hipStream_t st) {
   constexpr int TM = 9;
   const int lds = ((TM * 16 * a.PXBp + 255) & ~255) + img_zero_bytes(CS);
   static PerDeviceOnce attr_once__;
   bool& attr_set = attr_once__.slot();
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)conv_img_chain_kernel<TM, TNI, CS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)conv_img_chain_kernel<HT, TM, TNI, CS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024) != hipSuccess) {
       comic_set_error("conv_img_chain: cannot reserve %d bytes of LDS", lds);
       return 1;
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((conv_img_chain_kernel<TM, TNI, CS>), dim3(a.B * a.n_members), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((conv_img_chain_kernel<HT, TM, TNI, CS>), dim3(a.B * a.n_members), dim3(256), lds, st, a);
   return 0;
 }
 
@@ -403,21 +403,28 @@ int comic_img_images_per_group(int cfg) {
 }
 
 
-int comic_img_launch(int cfg, const ComicImgArgs& a, hipStream_t st) {
+namespace {
+template <typename HT>
+int img_launch(int cfg, const ComicImgArgs& a, hipStream_t st) {
   switch (cfg) {
-    case 0: return launch_img<9, 3, 1, 4, 4>(a, st);
-    case 1: return launch_img<9, 3, 1, 4, 5>(a, st);
-    case 2: return launch_img<9, 3, 1, 4, 6>(a, st);
-    case 3: return launch_img<9, 2, 1, 4, 4>(a, st);
-    case 4: return launch_img<9, 3, 1, 4, 5>(a, st);      // 160 channels on the 192-channel geometry
-    case 5: return launch_img<10, 3, 4, 2, 2>(a, st);
-    case 6: return launch_img<10, 3, 4, 2, 3>(a, st);
-    case 7: return launch_img<5, 6, 2, 4, 12>(a, st);
-    case 8: return launch_img<5, 6, 2, 4, 14>(a, st);
+    case 0: return launch_img<HT, 9, 3, 1, 4, 4>(a, st);
+    case 1: return launch_img<HT, 9, 3, 1, 4, 5>(a, st);
+    case 2: return launch_img<HT, 9, 3, 1, 4, 6>(a, st);
+    case 3: return launch_img<HT, 9, 2, 1, 4, 4>(a, st);
+    case 4: return launch_img<HT, 9, 3, 1, 4, 5>(a, st);      // 160 channels on the 192-channel geometry
+    case 5: return launch_img<HT, 10, 3, 4, 2, 2>(a, st);
+    case 6: return launch_img<HT, 10, 3, 4, 2, 3>(a, st);
+    case 7: return launch_img<HT, 5, 6, 2, 4, 12>(a, st);
+    case 8: return launch_img<HT, 5, 6, 2, 4, 14>(a, st);
     default:
       comic_set_error("conv_img: unknown configuration %d", cfg);
       return 2;
   }
+}
+}  // namespace
+
+int comic_img_launch(int cfg, const ComicImgArgs& a, hipStream_t st) {
+  return a.f16 ? img_launch<f16_t>(cfg, a, st) : img_launch<bf16_t>(cfg, a, st);
 }
 
 // Chains of stride-1 SAME 7-tap convs over 12x12 maps with Cin = every inner Cout in {128, 160, 192} and 192 channels out of
@@ -431,10 +438,17 @@ int comic_img_chain_launch(const ComicChainArgs& a, hipStream_t st) {
     comic_set_error("conv_img_chain: unsupported shape (%dx%d, Cin %d, %d members)", a.H, a.W, a.Cin, a.n_members);
     return 2;
   }
+  if (a.f16) {
+    switch (a.Cin) {
+      case 128: return launch_chain<f16_t, 2, 4>(a, st);
+      case 160: return launch_chain<f16_t, 3, 5>(a, st);
+      default: return launch_chain<f16_t, 3, 6>(a, st);
+    }
+  }
   switch (a.Cin) {
-    case 128: return launch_chain<2, 4>(a, st);
-    case 160: return launch_chain<3, 5>(a, st);
-    default: return launch_chain<3, 6>(a, st);
+    case 128: return launch_chain<bf16_t, 2, 4>(a, st);
+    case 160: return launch_chain<bf16_t, 3, 5>(a, st);
+    default: return launch_chain<bf16_t, 3, 6>(a, st);
   }
 }
 

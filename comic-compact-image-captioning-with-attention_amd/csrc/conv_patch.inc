@@ -41,7 +41,7 @@ constexpr int kPatchMaxParts = 8;   // 1-KiB DMA pieces per patch row (host: pat
 // WM x WN waves: WM splits the pixels, WN the output channels; a wave owns TM x TN 16x16 tiles.
 // NSTAGE_ = kLoaderWaves + n (conv.hip): four extra waves share the patch fill and own the weight ring, the WM x WN
 // waves only read fragments and issue MFMAs after their share of the fill.
-template <int TM, int TN, int WM, int WN, int NSTAGE_>
+template <typename HT, int TM, int TN, int WM, int WN, int NSTAGE_>
 __device__ __forceinline__ void conv_patch_body(const ConvArgs& a, const int tile_m, const int block_n) {
   constexpr int NSTAGE = ring_stages(NSTAGE_);
   constexpr bool SPEC = NSTAGE_ >= kLoaderWaves;
@@ -250,8 +250,8 @@ __device__ __forceinline__ void conv_patch_body(const ConvArgs& a, const int til
     for (int i = 0; i < TN; ++i)
 #pragma unroll
       for (int j = 0; j < TM; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf0[i]),
-                                                            __builtin_bit_cast(bf16x8_t, xf0[j]), acc[i][j], 0, 0, 0);
+        acc[i][j] = Half16<HT>::mfma(__builtin_bit_cast(bf16x8_t, wf0[i]),
+                                                            __builtin_bit_cast(bf16x8_t, xf0[j]), acc[i][j]);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
@@ -259,26 +259,26 @@ __device__ __forceinline__ void conv_patch_body(const ConvArgs& a, const int til
     for (int i = 0; i < TN; ++i)
 #pragma unroll
       for (int j = 0; j < TM; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf1[i]),
-                                                            __builtin_bit_cast(bf16x8_t, xf1[j]), acc[i][j], 0, 0, 0);
+        acc[i][j] = Half16<HT>::mfma(__builtin_bit_cast(bf16x8_t, wf1[i]),
+                                                            __builtin_bit_cast(bf16x8_t, xf1[j]), acc[i][j]);
   }
 
   STAMP(4);
-  conv_store_tiles<TN, TM>(a, acc, bn0 + wn * TN * 16, fg * 4, mrow);
+  conv_store_tiles<HT, TN, TM>(a, acc, bn0 + wn * TN * 16, fg * 4, mrow);
   STAMP(5);
 }
 
-template <int TM, int TN, int WM, int WN, int NSTAGE>
+template <typename HT, int TM, int TN, int WM, int WN, int NSTAGE>
 __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_patch_kernel(ConvArgs a) {
   constexpr int BN = 16 * TN * WN;
   const int tiles_n = (a.Cout + BN - 1) / BN;
   const int l = xcd_tile_index(a.tiles_m * tiles_n);
   if (l < 0) return;
-  conv_patch_body<TM, TN, WM, WN, NSTAGE>(a, l / tiles_n, l % tiles_n);
+  conv_patch_body<HT, TM, TN, WM, WN, NSTAGE>(a, l / tiles_n, l % tiles_n);
 }
 
 // Grouped launch (the same-depth convs of an Inception block): flat workgroup id -> (member, tile).
-template <int TM, int TN, int WM, int WN, int NSTAGE>
+template <typename HT, int TM, int TN, int WM, int WN, int NSTAGE>
 __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_patch_grouped_kernel(const ConvArgs* __restrict__ args, int n, int total) {
   constexpr int BN = 16 * TN * WN;
   const int bid = blockIdx.x;
@@ -289,11 +289,11 @@ __global__ __launch_bounds__(dma_threads(WM, WN, NSTAGE)) void conv_patch_groupe
   const ConvArgs a = args[p];
   const int local = bid - a.blk0;
   if (a.member_kind == 1) {
-    pool_bn_relu_member(a, local);
+    pool_bn_relu_member<HT>(a, local);
     return;
   }
   const int tiles_n = (a.Cout + BN - 1) / BN;
-  conv_patch_body<TM, TN, WM, WN, NSTAGE>(a, local / tiles_n, local % tiles_n);
+  conv_patch_body<HT, TM, TN, WM, WN, NSTAGE>(a, local / tiles_n, local % tiles_n);
 }
 
 // Host side: tile geometry for a BM-pixel tile.  Returns false when the layer is not
@@ -361,7 +361,7 @@ static void apply_geometry(ConvArgs& b, const PatchGeo& g) {
   b.tiles_m = (int)((GR + g.TR - 1) / g.TR) * g.ncol;
 }
 
-template <int TM, int TN, int WM = 4, int WN = 1, int NSTAGE = 3>
+template <typename HT, int TM, int TN, int WM = 4, int WN = 1, int NSTAGE = 3>
 int launch_patch(const ConvArgs& a, hipStream_t st) {
   PatchGeo g;
   constexpr int BM = 16 * TM * WM, BN = 16 * TN * WN;
@@ -372,7 +372,7 @@ int launch_patch(const ConvArgs& a, hipStream_t st) {
   static PerDeviceOnce attr_once__;
   bool& attr_set = attr_once__.slot();   // hipFuncSetAttribute holds per device
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)conv_patch_kernel<TM, TN, WM, WN, NSTAGE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)conv_patch_kernel<HT, TM, TN, WM, WN, NSTAGE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024) != hipSuccess) {
       comic_set_error("conv: cannot reserve LDS for the patch kernel");
       return 1;
@@ -387,17 +387,17 @@ int launch_patch(const ConvArgs& a, hipStream_t st) {
     return 1;
   }
   const int lds = std::max(g.lds_bytes, a.min_lds);
-  hipLaunchKernelGGL((conv_patch_kernel<TM, TN, WM, WN, NSTAGE>), dim3((unsigned)((total + 7) / 8 * 8)),
+  hipLaunchKernelGGL((conv_patch_kernel<HT, TM, TN, WM, WN, NSTAGE>), dim3((unsigned)((total + 7) / 8 * 8)),
                      dim3(dma_threads(WM, WN, NSTAGE)), lds, st, b);
   return 0;
 }
 
-template <int TM, int TN, int WM = 4, int WN = 1, int NSTAGE = 3>
+template <typename HT, int TM, int TN, int WM = 4, int WN = 1, int NSTAGE = 3>
 int launch_patch_grouped(const ConvArgs* args_dev, int n, int total_blocks, int lds_bytes, hipStream_t st) {
   static PerDeviceOnce attr_once__;
   bool& attr_set = attr_once__.slot();   // hipFuncSetAttribute holds per device
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)conv_patch_grouped_kernel<TM, TN, WM, WN, NSTAGE>,
+    if (hipFuncSetAttribute((const void*)conv_patch_grouped_kernel<HT, TM, TN, WM, WN, NSTAGE>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
       comic_set_error("conv: cannot reserve LDS for the grouped patch kernel");
       return 1;
@@ -405,7 +405,7 @@ int launch_patch_grouped(const ConvArgs* args_dev, int n, int total_blocks, int 
     attr_set = true;
   }
   const int lds = lds_bytes;
-  hipLaunchKernelGGL((conv_patch_grouped_kernel<TM, TN, WM, WN, NSTAGE>), dim3((unsigned)total_blocks),
+  hipLaunchKernelGGL((conv_patch_grouped_kernel<HT, TM, TN, WM, WN, NSTAGE>), dim3((unsigned)total_blocks),
                      dim3(dma_threads(WM, WN, NSTAGE)), lds, st, args_dev, n, total_blocks);
   return 0;
 }
@@ -421,27 +421,28 @@ constexpr PatchTile kPatchTiles[19] = {{256, 64, 256}, {256, 32, 256}, {256, 96,
 constexpr int kPatchLoaderTile0 = 48;
 inline int patch_tile_index(int tile) { return tile >= kPatchLoaderTile0 ? 13 + (tile - kPatchLoaderTile0) : tile - 13; }
 
+template <typename HT>
 int launch_patch_grouped_tile(int tile, const ConvArgs* args_dev, int n, int total_blocks, int lds, hipStream_t st) {
   switch (tile) {
-    case 13: return launch_patch_grouped<4, 4>(args_dev, n, total_blocks, lds, st);
-    case 14: return launch_patch_grouped<4, 2>(args_dev, n, total_blocks, lds, st);
-    case 15: return launch_patch_grouped<4, 6>(args_dev, n, total_blocks, lds, st);
-    case 16: return launch_patch_grouped<2, 4>(args_dev, n, total_blocks, lds, st);
-    case 17: return launch_patch_grouped<2, 2>(args_dev, n, total_blocks, lds, st);
-    case 18: return launch_patch_grouped<2, 6>(args_dev, n, total_blocks, lds, st);
-    case 19: return launch_patch_grouped<4, 4, 4, 2>(args_dev, n, total_blocks, lds, st);
-    case 20: return launch_patch_grouped<4, 4, 4, 3>(args_dev, n, total_blocks, lds, st);
-    case 21: return launch_patch_grouped<4, 4, 8, 1>(args_dev, n, total_blocks, lds, st);
-    case 22: return launch_patch_grouped<4, 2, 4, 2>(args_dev, n, total_blocks, lds, st);
-    case 23: return launch_patch_grouped<4, 6, 4, 2>(args_dev, n, total_blocks, lds, st);
-    case 24: return launch_patch_grouped<2, 4, 4, 2>(args_dev, n, total_blocks, lds, st);
-    case 25: return launch_patch_grouped<2, 6, 4, 2>(args_dev, n, total_blocks, lds, st);
-    case 48: return launch_patch_grouped<4, 4, 4, 1, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
-    case 49: return launch_patch_grouped<4, 2, 4, 1, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
-    case 50: return launch_patch_grouped<4, 6, 4, 1, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
-    case 51: return launch_patch_grouped<2, 6, 4, 1, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
-    case 52: return launch_patch_grouped<4, 6, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
-    case 53: return launch_patch_grouped<4, 4, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
+    case 13: return launch_patch_grouped<HT, 4, 4>(args_dev, n, total_blocks, lds, st);
+    case 14: return launch_patch_grouped<HT, 4, 2>(args_dev, n, total_blocks, lds, st);
+    case 15: return launch_patch_grouped<HT, 4, 6>(args_dev, n, total_blocks, lds, st);
+    case 16: return launch_patch_grouped<HT, 2, 4>(args_dev, n, total_blocks, lds, st);
+    case 17: return launch_patch_grouped<HT, 2, 2>(args_dev, n, total_blocks, lds, st);
+    case 18: return launch_patch_grouped<HT, 2, 6>(args_dev, n, total_blocks, lds, st);
+    case 19: return launch_patch_grouped<HT, 4, 4, 4, 2>(args_dev, n, total_blocks, lds, st);
+    case 20: return launch_patch_grouped<HT, 4, 4, 4, 3>(args_dev, n, total_blocks, lds, st);
+    case 21: return launch_patch_grouped<HT, 4, 4, 8, 1>(args_dev, n, total_blocks, lds, st);
+    case 22: return launch_patch_grouped<HT, 4, 2, 4, 2>(args_dev, n, total_blocks, lds, st);
+    case 23: return launch_patch_grouped<HT, 4, 6, 4, 2>(args_dev, n, total_blocks, lds, st);
+    case 24: return launch_patch_grouped<HT, 2, 4, 4, 2>(args_dev, n, total_blocks, lds, st);
+    case 25: return launch_patch_grouped<HT, 2, 6, 4, 2>(args_dev, n, total_blocks, lds, st);
+    case 48: return launch_patch_grouped<HT, 4, 4, 4, 1, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
+    case 49: return launch_patch_grouped<HT, 4, 2, 4, 1, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
+    case 50: return launch_patch_grouped<HT, 4, 6, 4, 1, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
+    case 51: return launch_patch_grouped<HT, 2, 6, 4, 1, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
+    case 52: return launch_patch_grouped<HT, 4, 6, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
+    case 53: return launch_patch_grouped<HT, 4, 4, 2, 2, kLoaderWaves + 3>(args_dev, n, total_blocks, lds, st);
     default:
       comic_set_error("conv: unknown patch tile id %d", tile);
       return 2;

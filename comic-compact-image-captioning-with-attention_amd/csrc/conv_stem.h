@@ -17,6 +17,7 @@ struct ComicStemArgs {
   int Hi, Wi;
   const float* w0;        // Conv2d_1a filter, stem layout fp32 [27][32]
   const float *sc0, *sh0;
+  int f16;                // 1: IEEE half activations / weights (COMIC_F16 plans), 0: bf16
 };
 
 bool comic_stem_stream_supported(int H0, int W0);

@@ -56,7 +56,7 @@ constexpr int kImgRing = 16;             // FUSE1A: image rows resident in LDS (
 __device__ __forceinline__ float row_next1(float v) { return dpp_move<0x12F>(v, v); }
 __device__ __forceinline__ float row_next2(float v) { return dpp_move<0x12E>(v, v); }
 
-template <bool FUSE1A>
+template <typename HT, bool FUSE1A>
 __global__ __launch_bounds__(512) void conv_stem_stream_kernel(ComicStemArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* table = (float*)smem;                                   // sc1[32] sh1[32] sc2[64] sh2[64]
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(512) void conv_stem_stream_kernel(ComicStemArgs a) 
           acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0l[n], xh, acc0, 0, 0, 0);
           const float v0 = fmaxf(fmaf(acc0[0], sc0[n].x, sh0[n].x), 0.f), v1 = fmaxf(fmaf(acc0[1], sc0[n].y, sh0[n].y), 0.f);
           const float v2 = fmaxf(fmaf(acc0[2], sc0[n].z, sh0[n].z), 0.f), v3 = fmaxf(fmaf(acc0[3], sc0[n].w, sh0[n].w), 0.f);
-          if (x < a.W0) *(uint2*)(dst + x * kPxB + n * 32) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+          if (x < a.W0) *(uint2*)(dst + x * kPxB + n * 32) = make_uint2(Half16<HT>::pack(v0, v1), Half16<HT>::pack(v2, v3));
         }
       }
     };
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(512) void conv_stem_stream_kernel(ComicStemArgs a) 
               if (tap + 3 < 9) frags(tap + 3, xf[(tap + 3) & 3]);
 #pragma unroll
               for (int j = 0; j < 4; ++j)
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[tap], xf[tap & 3][j], acc[j], 0, 0, 0);
+                acc[j] = Half16<HT>::mfma(w1[tap], xf[tap & 3][j], acc[j]);
             }
             __builtin_amdgcn_s_setprio(0);
           }
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(512) void conv_stem_stream_kernel(ComicStemArgs a) 
             float v0 = fmaxf(fmaf(acc[j][0], sc1.x, sh1.x), 0.f), v1 = fmaxf(fmaf(acc[j][1], sc1.y, sh1.y), 0.f);
             float v2 = fmaxf(fmaf(acc[j][2], sc1.z, sh1.z), 0.f), v3 = fmaxf(fmaf(acc[j][3], sc1.w, sh1.w), 0.f);
             if (!real) v0 = v1 = v2 = v3 = 0.f;
-            if (x < W1) *(uint2*)(dst + (x + 1) * kPxB) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+            if (x < W1) *(uint2*)(dst + (x + 1) * kPxB) = make_uint2(Half16<HT>::pack(v0, v1), Half16<HT>::pack(v2, v3));
           }
         }
         if constexpr (FUSE1A) {
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(512) void conv_stem_stream_kernel(ComicStemArgs a) 
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[i][tap], xf[tap & 1][j], acc[i][j], 0, 0, 0);
+            acc[i][j] = Half16<HT>::mfma(w2[i][tap], xf[tap & 1][j], acc[i][j]);
       }
     };
     auto pool_row = [&](int r, f32x4_t (&acc)[2][4]) {
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(512) void conv_stem_stream_kernel(ComicStemArgs a) 
           const int jc = x >> 1;
           if ((fr & 1) == 0 && fr <= 12 && jc < a.Wp) {
             bf16_t* yp = a.y + ((size_t)((b * a.Hp + prow) * a.Wp + jc)) * a.y_cs + a.y_co + (2 * p + i) * 16 + fg * 4;
-            *(uint2*)yp = make_uint2(pack_bf16x2(o0, o1), pack_bf16x2(o2, o3));
+            *(uint2*)yp = make_uint2(Half16<HT>::pack(o0, o1), Half16<HT>::pack(o2, o3));
           }
         }
       }
@@ -445,7 +445,9 @@ bool comic_stem_stream_1a_supported(int Hi, int Wi) {
          kTableFloats * 4 + 2 * kRing * kRowB + kImgRing * Wi * 3 * 4 <= 160 * 1024;
 }
 
-int comic_stem_stream_launch(const ComicStemArgs& a_in, hipStream_t st) {
+namespace {
+template <typename HT>
+int stem_stream_launch(const ComicStemArgs& a_in, hipStream_t st) {
   ComicStemArgs a = a_in;
   if (!comic_stem_stream_supported(a.H0, a.W0) || (a.img && !comic_stem_stream_1a_supported(a.Hi, a.Wi))) {
     comic_set_error("conv_stem: unsupported map %dx%d", a.H0, a.W0);
@@ -455,9 +457,9 @@ int comic_stem_stream_launch(const ComicStemArgs& a_in, hipStream_t st) {
   static PerDeviceOnce attr_once__;
   bool& attr_set = attr_once__.slot();   // hipFuncSetAttribute holds per device
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)conv_stem_stream_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)conv_stem_stream_kernel<HT, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)conv_stem_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipFuncSetAttribute((const void*)conv_stem_stream_kernel<HT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024) != hipSuccess) {
       comic_set_error("conv_stem: cannot reserve %d bytes of LDS", lds);
       return 1;
@@ -475,8 +477,13 @@ int comic_stem_stream_launch(const ComicStemArgs& a_in, hipStream_t st) {
   a.n_tasks = a.B * a.parts;
   const int grid = std::min(a.n_tasks, cus);
   if (a.img)
-    hipLaunchKernelGGL(conv_stem_stream_kernel<true>, dim3(grid), dim3(512), lds, st, a);
+    hipLaunchKernelGGL((conv_stem_stream_kernel<HT, true>), dim3(grid), dim3(512), lds, st, a);
   else
-    hipLaunchKernelGGL(conv_stem_stream_kernel<false>, dim3(grid), dim3(512), lds, st, a);
+    hipLaunchKernelGGL((conv_stem_stream_kernel<HT, false>), dim3(grid), dim3(512), lds, st, a);
   return 0;
+}
+}  // namespace
+
+int comic_stem_stream_launch(const ComicStemArgs& a, hipStream_t st) {
+  return a.f16 ? stem_stream_launch<f16_t>(a, st) : stem_stream_launch<bf16_t>(a, st);
 }

@@ -16,6 +16,7 @@ struct ComicWsArgs {
   int Ho, Wo, M;         // output pixel grid (= H x W, or the pooled grid)
   int pooled;            // 1: an activation row is the 3x3 / stride-2 VALID max-pool window of x
   int n_members, n_tiles, tiles_m;
+  int f16;               // 1: IEEE half activations / weights (COMIC_F16 plans), 0: bf16
   ComicWsMember m[4];
 };
 

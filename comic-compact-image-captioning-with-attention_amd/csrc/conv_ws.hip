@@ -53,7 +53,7 @@ __device__ __forceinline__ uint32_t max_i16x2(uint32_t a, uint32_t b) {
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
 }
 
-template <int KS, int NT>
+template <typename HT, int KS, int NT>
 __global__ __launch_bounds__(512) void conv_ws_kernel(ComicWsArgs a) {
   constexpr int KT = (KS + 1) / 2;          // 64-deep k-tiles of the LDS image
   constexpr int ABYTES = KT * kWsRows * 128;
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ComicWsArgs a) {
       for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wreg[ks][i], xf[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = Half16<HT>::mfma(wreg[ks][i], xf[j], acc[i][j]);
     }
     // epilogue: lane holds channels fg*4 .. +3 of pixel (tile*64 + j*16 + fr) for each of its tiles
 #pragma unroll
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ComicWsArgs a) {
           if (a.m[p].out_f32)
             *(float4*)((float*)a.m[p].y + off) = make_float4(v0, v1, v2, v3);
           else
-            *(uint2*)((bf16_t*)a.m[p].y + off) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+            *(uint2*)((bf16_t*)a.m[p].y + off) = make_uint2(Half16<HT>::pack(v0, v1), Half16<HT>::pack(v2, v3));
         }
       }
     }
@@ -263,13 +263,13 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(ComicWsArgs a) {
   }
 }
 
-template <int KS, int NT>
+template <typename HT, int KS, int NT>
 int launch_ws(const ComicWsArgs& a, hipStream_t st) {
   constexpr int lds = kWsTableBytes + 2 * ((KS + 1) / 2) * kWsRows * 128;
   static PerDeviceOnce attr_once__;
   bool& attr_set = attr_once__.slot();   // hipFuncSetAttribute holds per device
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)conv_ws_kernel<KS, NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)conv_ws_kernel<HT, KS, NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024) != hipSuccess) {
       comic_set_error("conv_ws: cannot reserve %d bytes of LDS", lds);
       return 1;
@@ -279,7 +279,7 @@ int launch_ws(const ComicWsArgs& a, hipStream_t st) {
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const int grid = std::min(a.tiles_m, cus);
-  hipLaunchKernelGGL((conv_ws_kernel<KS, NT>), dim3(grid), dim3(512), lds, st, a);
+  hipLaunchKernelGGL((conv_ws_kernel<HT, KS, NT>), dim3(grid), dim3(512), lds, st, a);
   return 0;
 }
 
@@ -291,14 +291,21 @@ bool comic_ws_supported(int Cin, int n_tiles) {
   return (ks == 2 && nt <= 2) || ((ks == 6 || ks == 8 || ks == 9) && nt <= 4);
 }
 
+namespace {
+template <typename HT>
+int ws_launch(const ComicWsArgs& a, hipStream_t st) {
+  const int ks = a.Cin / 32;
+  if (ks == 2) return launch_ws<HT, 2, 2>(a, st);
+  if (ks == 6) return launch_ws<HT, 6, 4>(a, st);
+  if (ks == 8) return launch_ws<HT, 8, 4>(a, st);
+  return launch_ws<HT, 9, 4>(a, st);
+}
+}  // namespace
+
 int comic_ws_launch(const ComicWsArgs& a, hipStream_t st) {
-  const int ks = a.Cin / 32, nt = (a.n_tiles + 3) / 4;
   if (!comic_ws_supported(a.Cin, a.n_tiles)) {
     comic_set_error("conv_ws: unsupported shape (Cin %d, %d channel tiles)", a.Cin, a.n_tiles);
     return 2;
   }
-  if (ks == 2) return launch_ws<2, 2>(a, st);
-  if (ks == 6) return launch_ws<6, 4>(a, st);
-  if (ks == 8) return launch_ws<8, 4>(a, st);
-  return launch_ws<9, 4>(a, st);
+  return a.f16 ? ws_launch<f16_t>(a, st) : ws_launch<bf16_t>(a, st);
 }

@@ -91,7 +91,7 @@ class ModelBase(object):
             # config.cnn_autotune is False; the trainable CNN keeps the heuristic choice (its plan differs).
             H, W = self.plan.buffers[self.plan.input][:2]
             c = self._config
-            if (getattr(c, 'cnn_autotune', True) and dtype in ('bf16', 'bf16x3') and str(self.device).startswith('cuda')
+            if (getattr(c, 'cnn_autotune', True) and dtype in ('bf16', 'bf16x3', 'f16') and str(self.device).startswith('cuda')
                     and batch_size * H * W >= 16 * 224 * 224 and getattr(c, 'freeze_scopes', 'Model/encoder/cnn')):
                 log_path = getattr(c, 'log_path', None)
                 cache = os.path.join(log_path, 'conv_variants.json') if log_path and os.path.isdir(log_path) else None

@@ -729,7 +729,8 @@ def store_tune_cache(cache, key, tiles):
 
 class CnnEncoder:
     """Device-resident encoder: packed weights, folded BN, activation buffers, one native
-    forward call.  `dtype` 'bf16' (throughput path) or 'f32' (exact-fp32 MFMA, parity path)."""
+    forward call.  `dtype` 'bf16' (throughput path), 'f16' (the same kernels on IEEE half storage and the f16 matrix
+    cores: 3 more mantissa bits at bf16 speed; forward only) or 'f32' (exact-fp32 MFMA, parity path)."""
 
     def __init__(self, plan: CnnPlan, params: dict, batch: int, dtype='bf16', device='cuda:0', weights_from=None):
         import torch
@@ -739,15 +740,19 @@ class CnnEncoder:
         if dtype == 'bf16x3':              # the bf16 kernels over an x3 plan (CnnPlan(x3=True)): fp32-class accuracy
             assert getattr(plan, 'x3', False), "dtype 'bf16x3' needs a plan built with x3=True"
             dtype = 'bf16'
-        assert dtype in ('bf16', 'f32') and (dtype == 'bf16' or not getattr(plan, 'x3', False))
+        assert dtype in ('bf16', 'f16', 'f32'), dtype
+        if dtype == 'f16' and getattr(plan, 'x3', False):
+            raise ValueError("x3 plans run on the bf16 kernels ('bf16x3'); an f16 encoder takes a plan built with x3=False")
+        assert dtype == 'bf16' or not getattr(plan, 'x3', False)
+        self.half = dtype in ('bf16', 'f16')       # the 16-bit plans: same kernels, layouts and plan forms
         small = getattr(plan, 'small_batch_plan', None)
-        if small is not None and (batch < plan.CHAIN_MIN_BATCH or dtype != 'bf16'):
+        if small is not None and (batch < plan.CHAIN_MIN_BATCH or not self.half):
             plan = small          # same buffers, weights and end points; one launch per conv depth instead of fused chains
         self.plan, self.batch, self.dtype, self.device = plan, batch, dtype, device
-        self.dcode = 1 if dtype == 'bf16' else 0
-        if getattr(plan, 'fuse_pools', False) and dtype != 'bf16':
-            raise ValueError('fuse_pools plans run on the bf16 kernels only')
-        tdt = torch.bfloat16 if dtype == 'bf16' else torch.float32
+        self.dcode = {'f32': 0, 'bf16': 1, 'f16': 2}[dtype]    # COMIC_F32 / COMIC_BF16 / COMIC_F16
+        if getattr(plan, 'fuse_pools', False) and not self.half:
+            raise ValueError('fuse_pools plans run on the bf16 / f16 kernels only')
+        tdt = {'f32': torch.float32, 'bf16': torch.bfloat16, 'f16': torch.float16}[dtype]
         self._tdt = tdt
         st = L.stream_ptr()
         # fp32 masters in the packed kernel layout ([Cout][Kpad]; stem [K][Cout]) in ONE flat buffer, BN
@@ -783,10 +788,10 @@ class CnnEncoder:
                         n += cout_p * ((3 * kh * kw * cin_p + 63) // 64 * 64)
                 self._x3_off = offs
                 self.w_plan = torch.zeros(max(n, 64), dtype=tdt, device=device)
-            # bf16 plans: a second copy of the weights in MFMA-fragment order for the image-resident kernel
+            # 16-bit plans: a second copy of the weights in MFMA-fragment order for the image-resident kernel
             # (csrc/conv_img.hip), refreshed with the plan copy; table = {element offset, Cout, Kpad} per weight
             self.w_frag, self._frag_table = None, None
-            if self.dcode == 1 and self._x3_off is None:
+            if self.half and self._x3_off is None:
                 self.w_frag = torch.zeros(self.w_master.numel, dtype=tdt, device=device)
                 tab = []
                 for i, (prefix, kh, kw, cin, cout, stem) in enumerate(plan.weights):
@@ -821,7 +826,7 @@ class CnnEncoder:
             for k, v in o.items():
                 if k not in ('depth', 'branch', 'block_in'):
                     setattr(ops[i], k, v)
-            if self.dcode != 1:
+            if not self.half:
                 ops[i].group = 0               # the fp32 parity path launches every conv on its own
                 if o.get('tile') == L.CHAIN_TILE:
                     ops[i].tile = 0
@@ -891,13 +896,14 @@ class CnnEncoder:
     def refresh_weights(self):
         """Re-derive what the forward reads from the fp32 masters: the plan-dtype weight copy and
         shift = beta - mean*scale (after loading a checkpoint or an optimiser step)."""
-        plan_copy = self.w_plan.data_ptr() if (self.dcode == 1 and self._x3_off is None) else None
+        plan_copy = self.w_plan.data_ptr() if (self.half and self._x3_off is None) else None
         if self._x3_off is not None:
             self._pack_x3()
-        L.check(self.lib.comic_cnn_refresh_weights(self.w_master.data.data_ptr(), plan_copy, self.w_master.numel,
-                                                   self.beta.data.data_ptr(), self.mean.data.data_ptr(),
-                                                   self.scale.data.data_ptr(), self.shift.data.data_ptr(),
-                                                   self.beta.numel, L.stream_ptr()), 'cnn_refresh_weights')
+        L.check(self.lib.comic_cnn_refresh_weights_dtype(self.w_master.data.data_ptr(), plan_copy, self.w_master.numel,
+                                                         self.beta.data.data_ptr(), self.mean.data.data_ptr(),
+                                                         self.scale.data.data_ptr(), self.shift.data.data_ptr(),
+                                                         self.beta.numel, self.dcode if self.half else 1, L.stream_ptr()),
+                'cnn_refresh_weights')
         if self.w_frag is not None:
             L.check(self.lib.comic_cnn_pack_frag_weights(self.w_plan.data_ptr(), self.w_frag.data_ptr(),
                                                          self._frag_table.data_ptr(), self._frag_table.shape[0],
@@ -1019,6 +1025,9 @@ class CnnEncoder:
         if self._train is not None:
             return self._train
         torch, plan = self.torch, self.plan
+        if self.dtype == 'f16':
+            raise ValueError("f16 encoders are forward-only: cnn_finetune trains on 'bf16', 'bf16x3' or 'f32' "
+                             '(the activation gradients fall below the f16 normal range without loss scaling)')
         if plan.pool_after_projection:
             raise ValueError('cnn_finetune needs a plan built with pool_after_projection=False (a forward-only layout)')
         x3 = bool(getattr(plan, 'x3', False))
@@ -1312,7 +1321,7 @@ class CnnEncoder:
                                                     ('+fp' if getattr(p, 'fuse_pools', False) else '') +
                                                     ('+ch' if getattr(p, 'fuse_chains', False) else '') +
                                                     ('+x3' if getattr(p, 'x3', False) else ''),
-                                                  len(p.ops), self.polite_lds_kb)
+                                                  len(p.ops), self.polite_lds_kb) + (':f16' if self.dtype == 'f16' else '')
 
     def autotune(self, reps=5, verbose=False, cache=None):
         """Pick the fastest tile / pipeline-depth variant of the conv kernels for every conv of the plan
@@ -1320,7 +1329,7 @@ class CnnEncoder:
         are bit-identical across variants: the k order per accumulator does not depend on the tile.
         cache: path of a JSON file {plan key: [tile id per op]}: loaded when it holds this plan (no timing
         runs -- e.g. under a profiler), written after a tuning run."""
-        if self.dcode != 1:
+        if not self.half:
             return {}
         torch = self.torch
         st = L.stream_ptr()

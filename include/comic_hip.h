@@ -17,7 +17,8 @@
  *   - activations NHWC; conv weights packed [Cout][Kpad] with K = (kh, kw, cin)
  *     contiguous (see comic_pack_conv_weights); dense weights row-major [in][out]
  *     (TensorFlow layout, so checkpoints map 1:1).
- *   - dtype codes: COMIC_F32 = 0, COMIC_BF16 = 1.
+ *   - dtype codes: COMIC_F32 = 0, COMIC_BF16 = 1, COMIC_F16 = 2 (IEEE half storage on the f16
+ *     matrix cores; forward entry points only -- the backward ones refuse it).
  */
 #ifndef COMIC_HIP_H_
 #define COMIC_HIP_H_
@@ -31,6 +32,7 @@ extern "C" {
 
 #define COMIC_F32 0
 #define COMIC_BF16 1
+#define COMIC_F16 2
 #define COMIC_ABI_VERSION 1
 #define COMIC_CONV_TILES 61
 #define COMIC_WS_TILE 54     /* weight-stationary 1x1 group kernel (csrc/conv_ws.hip) */
@@ -302,6 +304,11 @@ int comic_cnn_pack_bwd_filters(const comic_cnn_op* ops, int n_ops, const comic_c
 int comic_cnn_refresh_weights(const float* master, void* plan_copy, int64_t n, const float* beta,
                               const float* mean, const float* scale, float* shift,
                               int64_t channels, void* stream);
+/* The same for a plan of any 16-bit dtype: the plan copy converted to `dtype` (COMIC_BF16 or COMIC_F16);
+ * comic_cnn_refresh_weights is this call with COMIC_BF16. */
+int comic_cnn_refresh_weights_dtype(const float* master, void* plan_copy, int64_t n, const float* beta,
+                                    const float* mean, const float* scale, float* shift,
+                                    int64_t channels, int dtype, void* stream);
 
 /* Single conv + folded BN + ReLU (slim.conv2d under inception_arg_scope). */
 int comic_conv2d_bn_relu(const comic_cnn_op* op, const void* x, int x_channels, void* y,

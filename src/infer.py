@@ -38,6 +38,9 @@ def create_parser():
       help='Split JPEG decode: C threads undo the entropy coding, the device does the pixels (bit-identical to PIL).')
     a('--loader_threads', type=int, default=None, help='Decode threads of the loader.')
     a('--loader_cache_gb', type=float, default=None, help='Coefficient cache of the split JPEG decoder, GB.')
+    a('--cnn_dtype', type=str, default=None, choices=['bf16', 'f16', 'f32', 'bf16x3'],
+      help='CNN plan of the inference run (default: the training run\'s).  Checkpoints hold fp32 variables, so any '
+           'run decodes on any plan, e.g. a bf16-trained model on f16.')
     return p
 
 

@@ -2,7 +2,7 @@
 """train.py -- same flags, mode chaining, run-directory naming and kwargs as the reference
 CLI (reference src/train.py:25-312), driving the MI355X-native path.
 
-Differences (all additive): `--cnn_dtype {bf16,f32,bf16x3}`, `--checkpoint_format {npz,tf}`; launched under
+Differences (all additive): `--cnn_dtype {bf16,f16,f32,bf16x3}`, `--checkpoint_format {npz,tf}`; launched under
 `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel (one process
 per GPU, RCCL gradient all-reduce); the slim checkpoint is not downloaded (no network):
 pass `--checkpoint_path` (an .npz with slim variable names) or train the CNN from random init.
@@ -71,9 +71,10 @@ def create_parser():
     a('--gpu', type=str, default='0', help='The gpu number.')
     a('--run', type=int, default=1, help='The run number.')
     # additions of this framework
-    a('--cnn_dtype', type=str, default='bf16', choices=['bf16', 'f32', 'bf16x3'],
-      help='CNN activation / MFMA input type.  bf16x3: hi/lo-split activations and filters on the bf16 matrix cores '
-           '(fp32-class accuracy, frozen-CNN modes).')
+    a('--cnn_dtype', type=str, default='bf16', choices=['bf16', 'f16', 'f32', 'bf16x3'],
+      help='CNN activation / MFMA input type.  f16: IEEE half activations and filters on the f16 matrix cores (bf16 '
+           'speed, about 7x closer to fp32; frozen-CNN modes only: decoder, scst, infer).  bf16x3: hi/lo-split '
+           'activations and filters on the bf16 matrix cores (fp32-class accuracy).')
     a('--checkpoint_format', type=str, default='npz', choices=['npz', 'tf'],
       help='Container of saved checkpoints: .npz or the TF checkpoint-V2 tensor bundle (both restore).')
     a('--log_root', type=str, default='', help='Root of the experiments directory (default: ../experiments).')
@@ -155,11 +156,20 @@ def build_kwargs(args):
     return kwargs, train_fn_name, overwrite
 
 
+def refuse_unsupported_dtype(train_mode, cnn_dtype):
+    """--cnn_dtype f16 runs the frozen CNN only (its backward would need loss scaling: the activation gradients of
+    cnn_finetune lie far below the f16 normal range).  Called before anything touches the GPU."""
+    if train_mode == 'cnn_finetune' and cnn_dtype == 'f16':
+        raise NotImplementedError('--cnn_dtype f16 is forward-only and cannot train the CNN: run --train_mode cnn_finetune '
+                                  'with --cnn_dtype bf16 or bf16x3 (decoder / scst runs and infer.py take f16)')
+
+
 def check_supported(kw):
     """Options of the reference that this hot path does not implement fail HERE instead of silently training a different
-    model.  Nothing is refused at present: --clip_gradient_norm (model_base.py:394-401) is per-variable tf.clip_by_norm
+    model.  Refused: --train_mode cnn_finetune with --cnn_dtype f16 (refuse_unsupported_dtype).  --clip_gradient_norm (model_base.py:394-401) is per-variable tf.clip_by_norm
     in front of the optimiser (optim.GradClip), --rnn_name LN_LSTM / GRU (model_base.py:622-629) run on the per-step
     launch chain."""
+    refuse_unsupported_dtype(kw.get('train_mode'), kw.get('cnn_dtype'))
     bad = []
     # --initialiser: `he` / `none` select TensorFlow's default initialiser in the reference (model_base.py:823-831:
     # every value but `xavier` returns None), which for these float variables is glorot_uniform == Xavier-uniform
@@ -170,6 +180,7 @@ def check_supported(kw):
 
 def main(argv=None):
     args = create_parser().parse_args(argv)
+    refuse_unsupported_dtype(args.train_mode, args.cnn_dtype)
     import torch
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
