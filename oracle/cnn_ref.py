@@ -18,7 +18,8 @@ end-point shapes at 299 (inception_v3_test.py:93-123) and the parameter count
 Layout: activations NHWC, weights HWIO (TF layout), all float32.  ``act_dtype='bf16'``
 emulates the product's bf16 storage: every conv input and every weight is rounded
 to bf16 (RNE) before an fp32-accumulated contraction, and every layer output is
-rounded to bf16 when stored.
+rounded to bf16 when stored.  ``act_dtype='f16'`` does the same with IEEE half (RNE through
+``np.float16``: subnormals kept, overflow to inf), the storage of the f16 plans.
 """
 from __future__ import annotations
 
@@ -43,8 +44,21 @@ def bf16_round(x: np.ndarray) -> np.ndarray:
     return y.view(np.float32)
 
 
+def f16_round(x: np.ndarray) -> np.ndarray:
+    """Round -> IEEE half (round-to-nearest-even, subnormals kept, |x| >= 65520 -> inf), returned in the input's float
+    dtype (float32 or float64)."""
+    x = np.asarray(x)
+    dt = x.dtype if x.dtype in (np.float32, np.float64) else np.float32
+    with np.errstate(over='ignore'):
+        return np.asarray(x, dt).astype(np.float16).astype(dt)
+
+
 def _q(x, act_dtype):
-    return bf16_round(x) if act_dtype == 'bf16' else x
+    if act_dtype == 'bf16':
+        return bf16_round(x)
+    if act_dtype == 'f16':
+        return f16_round(x)
+    return x
 
 
 # --------------------------------------------------------------------------- #
@@ -76,7 +90,7 @@ def conv2d(x, w, stride=1, padding='VALID'):
         x = np.pad(x, ((0, 0), (pt, pb), (pl, pr), (0, 0)))
     if kh == 1 and kw == 1 and stride == 1:
         return (x.reshape(-1, C) @ w.reshape(C, co)).reshape(B, Ho, Wo, co)
-    cols = np.empty((B, Ho, Wo, kh, kw, C), np.float32)
+    cols = np.empty((B, Ho, Wo, kh, kw, C), np.result_type(x.dtype, w.dtype, np.float32))   # float64 operands stay float64
     for i in range(kh):
         for j in range(kw):
             cols[:, :, :, i, j, :] = x[:, i:i + (Ho - 1) * stride + 1:stride,

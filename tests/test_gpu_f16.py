@@ -14,10 +14,19 @@ pytestmark = pytest.mark.gpu
 import comic_amd._lib as L
 from comic_amd import decoder as cdec, nets, trainer
 from oracle import cnn_ref
-from tests.gpu_util import DEV, assert_close, dev, rel_err, sync
+from tests.gpu_util import DEV, F32_RTOL, assert_close, dev, rel_err, sync
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F16_TOL = 5e-3           # priced worst case on the oracle: 2.3e-3
+F16_EMU_TOL = 2.5e-3     # the product plan against the f16-storage emulation of the oracle (measured 1.8e-3: see the test)
+# end points of the product plan (pool after projection, fused pools): where its rewrites act, and the blocks behind them
+PRODUCT_END_POINTS = ('MaxPool_3a_3x3', 'Conv2d_3b_1x1', 'Conv2d_4a_3x3', 'Mixed_5b', 'Mixed_5c', 'Mixed_5d', 'Mixed_6a',
+                      'Mixed_6c', 'Mixed_6e', 'Mixed_7a', 'Mixed_7b')
+
+
+def _product_plan(size, **kw):
+    """The frozen encoder's plan as the product builds it (model.py, bench.py)."""
+    return nets.CnnPlan('inception_v3', (size, size), pool_after_projection=True, fuse_pools=True, **kw)
 
 
 @pytest.fixture(scope='module')
@@ -269,3 +278,159 @@ def test_cli_chain_with_f16(tmp_path):
         assert caps
         data = json.load(open(caps[0]))
         assert len(data) == 4 and all(set(x) == {'image_id', 'caption'} for x in data)
+
+
+@pytest.mark.parametrize('size,B', [(224, 2), (224, 97), (299, 2)])
+def test_inception_v3_product_plan_f16(cnn_params, size, B):
+    """The f16 encoder on the plan train.py / infer.py --cnn_dtype f16 run (kind-9 stem stream, MaxPool_3a / 5a folded into
+    the 1x1 convs behind them, the pool branches as projection then kind-7 average + BN + ReLU, fused chains at B = 97):
+    every end point against the fp32 oracle at F16_TOL, and against the oracle's f16-storage emulation (act_dtype='f16')
+    at the tighter F16_EMU_TOL.  Measured against the emulation: at most 1.8e-3 over these end points (Mixed_6e at 224;
+    1.4e-3 or less at Mixed_7c and 4.8e-4 at the embedding; the emulation
+    rounds the image and the stem filter, which the device reads in fp32, and differs in the order of the rounding of
+    the pool branches).  B = 97: a permuted batch gives the permuted features bit for bit, the last partial pixel tile
+    included, so every image is held to the two compared with the oracle."""
+    params = cnn_params if size == 224 else cnn_ref.randomize_bn(cnn_ref.init_params(0, size), seed=1)
+    x = np.random.default_rng(70 + size + B).uniform(-1, 1, (B, size, size, 3)).astype(np.float32)
+    plan = _product_plan(size)
+    assert plan.ops[0]['kind'] == (9 if size % 4 == 0 else 1) and sum(1 for o in plan.ops if o['kind'] == 7) == 9   # kind 9: W % 4 == 0
+    # MaxPool_5a folded into the four 1x1s of Mixed_5b; MaxPool_3a into Conv2d_3b unless the kind-9 stem stream pools it
+    assert sum(1 for o in plan.ops if o.get('flags', 0) & L.OP_POOLED_SRC) == (4 if size % 4 == 0 else 5)
+    enc = nets.CnnEncoder(plan, params, B, 'f16', DEV)
+    im, fm = (t.clone() for t in enc.forward(dev(x)))
+    sync()
+    n = 2
+    net_ref, ep = cnn_ref.inception_v3(params, x[:n], act_dtype='f32')
+    net_emu, ep_emu = cnn_ref.inception_v3(params, x[:n], act_dtype='f16')
+    s = int(round(fm.shape[1] ** 0.5))
+    worst = {}
+    names = [k for k in PRODUCT_END_POINTS if k in plan.end_points]
+    assert len(names) == len(PRODUCT_END_POINTS) - (0 if size % 4 == 0 else 1)     # 299: MaxPool_3a is never materialised
+    for name in names:
+        got = enc.end_point(name)[:n].float().cpu().numpy()
+        assert_close(got, ep[name], F16_TOL, name + ' f16 product plan')
+        worst[name] = rel_err(got, ep_emu[name])
+    worst['Mixed_7c'] = rel_err(fm[:n].cpu().numpy().reshape(n, s, s, 2048), ep_emu['Mixed_7c'])
+    worst['embedding'] = rel_err(im[:n].cpu().numpy(), net_emu.reshape(n, -1))
+    assert_close(fm[:n].cpu().numpy().reshape(n, s, s, 2048), ep['Mixed_7c'], F16_TOL, 'Mixed_7c f16 product plan')
+    assert_close(im[:n].cpu().numpy(), net_ref.reshape(n, -1), F16_TOL, 'embedding f16 product plan')
+    print('product plan %d B=%d, deviation from the f16 emulation: %s' % (size, B, json.dumps({k: float('%.3g' % v) for k, v in worst.items()})))
+    assert max(worst.values()) <= F16_EMU_TOL, worst
+    if B == 97:
+        perm = np.random.default_rng(1).permutation(B)
+        im2, fm2 = enc.forward(dev(x[perm]))
+        sync()
+        assert torch.equal(fm2, fm[perm]) and torch.equal(im2, im[perm])
+
+
+def test_f16_fused_pools_weight_stationary_1x1(cnn_params):
+    """f16 counterpart of the bf16 weight-stationary test: the thin 1x1 groups of Mixed_5b-d forced onto tile 54, the
+    pooled-source 1x1s, the row-walking kind-7 kernel -- bit for bit against the plain forward-only plan with every conv on
+    im2col tile 3 (same k order per accumulator, exact max), and against the fp32 oracle."""
+    B = 3
+    x = np.random.default_rng(12).uniform(-1, 1, (B, 224, 224, 3)).astype(np.float32)
+    pa = nets.CnnPlan('inception_v3', (224, 224), pool_after_projection=True, fuse_chains=False)
+    pb = _product_plan(224, fuse_chains=True)
+    ea = nets.CnnEncoder(pa, cnn_params, B, 'f16', DEV)
+    eb = nets.CnnEncoder(pb, cnn_params, B, 'f16', DEV, weights_from=ea)
+    for i, o in enumerate(pa.ops):
+        if o['kind'] == 0:
+            ea._ops[i].tile = 3
+    n_ws = 0
+    for i, o in enumerate(pb.ops):
+        if o['kind'] == 0 and o['KH'] == 1 and o['Cin'] in (256, 288) and o['Ho'] == 25:
+            eb._ops[i].tile = L.WS_TILE
+            n_ws += 1
+    assert n_ws >= 6
+    for e, plan in ((ea, pa), (eb, pb)):
+        for i, o in enumerate(plan.ops):
+            if o['kind'] == 7:
+                e._ops[i].tile = 1
+    ea._build_group_args()
+    eb._build_group_args()
+    ima, fma = (t.clone() for t in ea.forward(dev(x)))
+    imb, fmb = eb.forward(dev(x))
+    sync()
+    net_ref, ep = cnn_ref.inception_v3(cnn_params, x[:2], act_dtype='f32')
+    for name in ('MaxPool_3a_3x3', 'Conv2d_3b_1x1', 'Mixed_5b', 'Mixed_5c', 'Mixed_5d', 'Mixed_6c', 'Mixed_7b'):
+        assert_close(eb.end_point(name)[:2].float().cpu().numpy(), ep[name], F16_TOL, name)
+        assert torch.equal(_bits(eb.end_point(name)), _bits(ea.end_point(name))), name
+    assert torch.equal(fma, fmb) and torch.equal(ima, imb)
+
+
+def test_f16_grouped_branch_launch_is_bit_identical():
+    """f16: comic_cnn_forward_grouped (one launch per depth of an Inception block) against the op-by-op executor, every
+    end point bit for bit at a ragged batch, eager and replayed from a graph."""
+    params = cnn_ref.randomize_bn(cnn_ref.init_params(0, 224), seed=2)
+    x = np.random.default_rng(7).uniform(-1, 1, (5, 224, 224, 3)).astype(np.float32)
+    single = nets.CnnEncoder(nets.CnnPlan('inception_v3', (224, 224), group_branches=False), params, 5, 'f16', DEV)
+    grouped = nets.CnnEncoder(nets.CnnPlan('inception_v3', (224, 224), group_branches=True), params, 5, 'f16', DEV)
+    assert grouped._group_args is not None and single._group_args is None
+    im0, fm0 = (t.clone() for t in single.forward(dev(x)))
+    im1, fm1 = grouped.forward(dev(x))
+    sync()
+    for name in single.plan.end_points:
+        assert torch.equal(_bits(single.end_point(name)), _bits(grouped.end_point(name))), name
+    assert torch.equal(fm0, fm1) and torch.equal(im0, im1)
+    for _ in range(2):
+        im2, fm2 = grouped.forward(dev(x), use_graph=True)
+    sync()
+    assert torch.equal(fm0, fm2) and torch.equal(im0, im2)
+
+
+def test_f16_walk_tiles_give_the_bits_of_the_one_tile_launch(cnn_params):
+    """f16: tile ids 56..61 (one workgroup per pixel tile walks over the out-channel tiles of every member of a shared-input
+    1x1 group) against the same groups on tile 44, the whole forward bit for bit."""
+    B = 3
+    x = np.random.default_rng(10).uniform(-1, 1, (B, 224, 224, 3)).astype(np.float32)
+    plan = nets.CnnPlan('inception_v3', (224, 224), pool_after_projection=True, fuse_chains=False)
+    enc = nets.CnnEncoder(plan, cnn_params, B, 'f16', DEV)
+    heads = [i for i, o in enumerate(plan.ops) if o['kind'] == 0 and o.get('group', 0) and o['KH'] == 1 and o['KW'] == 1 and o['depth'] == 0
+             and (i == 0 or plan.ops[i - 1].get('group', 0) != o['group'])]
+    assert len(heads) >= 9
+
+    def forward_with(tile):
+        for i in heads:
+            enc._ops[i].tile = tile
+        enc._build_group_args(); enc._drop_graphs()
+        im, fm = enc.forward(dev(x))
+        sync()
+        return im.clone(), fm.clone()
+    im0, fm0 = forward_with(44)
+    for tile in (56, 57, 58, 59, 60, 61):
+        im1, fm1 = forward_with(tile)
+        assert torch.equal(fm1, fm0) and torch.equal(im1, im0), 'walk tile %d differs' % tile
+
+
+def test_inception_v1_stem_wide_kernel_f16():
+    """Inception-V1's Conv2d_1a_7x7 (7x7 / 2 SAME, 3 -> 64) on an f16 plan runs on conv_stem_wide_kernel (16-bit plans only):
+    the stem's output against float64 on the fp32 image and filter, rounded once to f16, at the fp32 bar; the whole
+    forward against the fp32 oracle at F16_TOL; the direct stem kernel (tile 1) within the same fp32 bar."""
+    B = 3
+    params = cnn_ref.randomize_bn(cnn_ref.init_params_v1(0), seed=1)
+    x = np.random.default_rng(4).uniform(-1, 1, (B, 224, 224, 3)).astype(np.float32)
+    plan = nets.CnnPlan('inception_v1', (224, 224), 'Mixed_4f')
+    stem = [i for i, o in enumerate(plan.ops) if o['kind'] == 1]
+    assert len(stem) == 1 and (plan.ops[stem[0]]['KH'], plan.ops[stem[0]]['Cout']) == (7, 64) and not plan.ops[stem[0]].get('tile')
+    enc = nets.CnnEncoder(plan, params, B, 'f16', DEV)
+    im, fm = (t.clone() for t in enc.forward(dev(x)))
+    y = enc.end_point('Conv2d_1a_7x7').float().cpu().numpy()
+    sync()
+    name = [k for k in params if k.endswith('Conv2d_1a_7x7/weights')][0]
+    pre = name[:-len('weights')]
+    ref = cnn_ref.conv2d(x.astype(np.float64), params[name].astype(np.float64), 2, 'SAME')
+    ref = (ref - params[pre + 'BatchNorm/moving_mean']) / np.sqrt(params[pre + 'BatchNorm/moving_variance'].astype(np.float64)
+                                                                  + cnn_ref.BN_EPS) + params[pre + 'BatchNorm/beta']
+    ref = cnn_ref.f16_round(np.maximum(ref, 0))
+    assert_close(y[..., :64], ref, F32_RTOL, 'Conv2d_1a_7x7 f16 (wide stem kernel)', elementwise=True)
+    net_ref, ep = cnn_ref.inception_v1(params, x[:2], act_dtype='f32')
+    for n_ in ('MaxPool_2a_3x3', 'Conv2d_2c_3x3', 'Mixed_3c', 'Mixed_4e'):
+        got = enc.end_point(n_)[:2].float().cpu().numpy()
+        assert_close(got[..., :ep[n_].shape[-1]], ep[n_], F16_TOL, n_ + ' f16')
+    assert_close(fm[:2].cpu().numpy().reshape(2, 14, 14, 832), ep['Mixed_4f'], F16_TOL, 'Mixed_4f f16')
+    enc._ops[stem[0]].tile = 1
+    enc._drop_graphs()
+    enc.forward(dev(x))
+    sync()
+    assert_close(enc.end_point('Conv2d_1a_7x7').float().cpu().numpy()[..., :64], ref, F32_RTOL, 'Conv2d_1a_7x7 f16 (direct)',
+                 elementwise=True)

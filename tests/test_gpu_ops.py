@@ -193,13 +193,21 @@ def test_gemm_group_matches_numpy_and_is_reproducible(which):
 
 
 # ------------------------------------------------------------------------ conv / pool -----
-def _run_conv(x, w, beta, mean, var, stride, padding, dtype, dst_channels=None, dst_coff=0, relu=1, out_f32=0, tile=0):
+_TDT = {'f32': torch.float32, 'bf16': torch.bfloat16, 'f16': torch.float16}
+_CODE = {'f32': 0, 'bf16': 1, 'f16': 2}
+
+
+def _run_conv(x, w, beta, mean, var, stride, padding, dtype, dst_channels=None, dst_coff=0, relu=1, out_f32=0, tile=0,
+              flags=0):
     B, H, W, Cin = x.shape
     kh, kw, _, Cout = w.shape
-    Ho, pt, _ = cnn_ref.out_size(H, kh, stride, padding)
-    Wo, pl, _ = cnn_ref.out_size(W, kw, stride, padding)
-    tdt = torch.bfloat16 if dtype == 'bf16' else torch.float32
-    code = 1 if dtype == 'bf16' else 0
+    if flags & L.OP_POOLED_SRC:             # 1x1 conv behind a 3x3 / 2 VALID max-pool folded into its loads
+        Ho, Wo, pt, pl = (H - 3) // 2 + 1, (W - 3) // 2 + 1, 0, 0
+    else:
+        Ho, pt, _ = cnn_ref.out_size(H, kh, stride, padding)
+        Wo, pl, _ = cnn_ref.out_size(W, kw, stride, padding)
+    tdt = _TDT[dtype]
+    code = _CODE[dtype]
     stem = Cin <= 4
     xd = dev(x) if stem else dev(x).to(tdt)
     wd = dev(w)
@@ -217,7 +225,7 @@ def _run_conv(x, w, beta, mean, var, stride, padding, dtype, dst_channels=None, 
     y = torch.full((B, Ho, Wo, yc), -7.0, dtype=ydt, device=DEV)
     op = L.CnnOp(kind=1 if stem else 0, src=0, dst=1, src_coff=0, dst_coff=dst_coff, H=H, W=W, Cin=Cin, Cout=Cout,
                  KH=kh, KW=kw, SH=stride, SW=stride, PT=pt, PL=pl, Ho=Ho, Wo=Wo, weight=0, relu=relu, out_f32=out_f32,
-                 tile=tile)
+                 tile=tile, flags=flags)
     wt = L.ConvWeight(packed.data_ptr(), scale.data_ptr(), shift.data_ptr())
     L.check(lib().comic_conv2d_bn_relu(C.byref(op), xd.data_ptr(), Cin, y.data_ptr(), yc, C.byref(wt), B, code,
                                        stream()), 'conv')
@@ -226,12 +234,47 @@ def _run_conv(x, w, beta, mean, var, stride, padding, dtype, dst_channels=None, 
 
 
 def _ref_conv(x, w, beta, mean, var, stride, padding, dtype, relu=1, round_out=True):
+    """bf16: the bf16-emulating oracle (fp32 accumulate).  f16: float64 on the f16 operands the kernel reads (the
+    stem: the fp32 image and filter), BatchNorm in float64, ONE rounding of the output to f16 -- what is left between
+    kernel and reference is the kernel's fp32 accumulation and its single RNE store."""
+    if dtype == 'f16':
+        stem = x.shape[-1] <= 4
+        q = (lambda a: np.asarray(a, np.float64)) if stem else (lambda a: cnn_ref.f16_round(np.asarray(a, np.float64)))
+        y = cnn_ref.conv2d(q(x), q(w), stride, padding)
+        y = (y - mean.astype(np.float64)) / np.sqrt(var.astype(np.float64) + cnn_ref.BN_EPS) + beta.astype(np.float64)
+        if relu:
+            y = np.maximum(y, 0)
+        return cnn_ref.f16_round(y) if round_out else y
     q = cnn_ref.bf16_round if dtype == 'bf16' else (lambda a: a)
     y = cnn_ref.conv2d(q(x), q(w), stride, padding)
     y = cnn_ref.batch_norm_inference(y, beta, mean, var)
     if relu:
         y = np.maximum(y, 0)
     return q(y) if round_out else y
+
+
+def _assert_f16(got, ref, name):
+    """The f16 op bar: the north star's fp32 criterion (1e-3, max-norm AND element-wise) against the float64 reference.
+    The bar must discriminate: the reference rounded through bf16 instead fails it, so a kernel that rounds through
+    bf16 anywhere cannot pass.  (Outputs with fewer than 32 non-zero values -- the 1x1 map cases -- are exempt from that
+    second check: a handful of bf16 roundings can all land close enough by chance.)"""
+    assert_close(got, ref, F32_RTOL, name + ' f16', elementwise=True)
+    if np.count_nonzero(ref) < 32:
+        return
+    with pytest.raises(AssertionError):
+        assert_close(cnn_ref.bf16_round(np.asarray(ref, np.float32)), ref, F32_RTOL, name + ' bf16-rounded', elementwise=True)
+
+
+def _check(got, ref, dtype, name, tol_bf16=1e-2, tol_f32=1e-4):
+    if dtype == 'f16':
+        _assert_f16(got, ref, name)
+    else:
+        assert_close(got, ref, tol_f32 if dtype == 'f32' else tol_bf16, name)
+
+
+def _q_in(x, dtype):
+    """Activations as the plan stores them."""
+    return cnn_ref.bf16_round(x) if dtype == 'bf16' else cnn_ref.f16_round(x) if dtype == 'f16' else x
 
 
 CONV_CASES = [
@@ -245,7 +288,7 @@ CONV_CASES = [
     (9, 25, 25, 192, 48, (1, 1), 1, 'SAME'), (1, 1, 1, 32, 16, (1, 1), 1, 'SAME')]
 
 
-@pytest.mark.parametrize('dtype', ['f32', 'bf16'])
+@pytest.mark.parametrize('dtype', ['f32', 'bf16', 'f16'])
 @pytest.mark.parametrize('case', CONV_CASES)
 def test_conv_bn_relu(case, dtype):
     B, H, W, Cin, Cout, k, s, pad = case
@@ -255,34 +298,45 @@ def test_conv_bn_relu(case, dtype):
     beta = 0.2 * rng.standard_normal(Cout).astype(np.float32)
     mean = 0.2 * rng.standard_normal(Cout).astype(np.float32)
     var = rng.uniform(0.5, 1.5, Cout).astype(np.float32)
-    if dtype == 'bf16':
-        x = cnn_ref.bf16_round(x)
+    x = _q_in(x, dtype)
     ref = _ref_conv(x, w, beta, mean, var, s, pad, dtype)
     got = _run_conv(x, w, beta, mean, var, s, pad, dtype)
-    # bf16: one output ulp (2^-8) on top of accumulation-order noise
-    assert_close(got, ref, 1e-4 if dtype == 'f32' else 1e-2, 'conv %s' % (case,))
+    # bf16: one output ulp (2^-8) on top of accumulation-order noise; f16: the fp32 bar against float64
+    _check(got, ref, dtype, 'conv %s' % (case,))
     # concat slice: write at a channel offset of a wider buffer, neighbours untouched
     got2 = _run_conv(x, w, beta, mean, var, s, pad, dtype, dst_channels=Cout + 48, dst_coff=16)
     np.testing.assert_array_equal(got2[..., 16:16 + Cout], got)
     assert (got2[..., :16] == -7).all() and (got2[..., 16 + Cout:] == -7).all()
 
 
-@pytest.mark.parametrize('case', [CONV_CASES[i] for i in (1, 3, 5, 7, 8, 11, 12)])
+IM2COL_TILE_CASES = [CONV_CASES[i] for i in (1, 3, 5, 7, 8, 11, 12)]
+
+
+@pytest.mark.parametrize('case', IM2COL_TILE_CASES)
 def test_conv_im2col_tile_variants_identical_bits(case):
+    _im2col_tile_variants(case, 'bf16')
+
+
+@pytest.mark.parametrize('case', IM2COL_TILE_CASES)
+def test_conv_im2col_tile_variants_identical_bits_f16(case):
+    _im2col_tile_variants(case, 'f16')
+
+
+def _im2col_tile_variants(case, dtype):
     """Every im2col LDS-DMA variant (ids 1..12: tile shapes x pipeline depths; 26..47: wide tiles (35..47 with loader waves), 4 or 8 waves) is a
     different blocking of the same sums in the same k order: bit-identical outputs, ragged row / channel tiles
     included, and correct against the oracle."""
     B, H, W, Cin, Cout, k, s, pad = case
     rng = np.random.default_rng(B * 1000 + H * 7 + Cin + Cout + k[0] + 5)
-    x = cnn_ref.bf16_round(rng.standard_normal((B, H, W, Cin)).astype(np.float32))
+    x = _q_in(rng.standard_normal((B, H, W, Cin)).astype(np.float32), dtype)
     w = (rng.standard_normal((k[0], k[1], Cin, Cout)) / math.sqrt(k[0] * k[1] * Cin)).astype(np.float32)
     beta = 0.2 * rng.standard_normal(Cout).astype(np.float32)
     mean = 0.2 * rng.standard_normal(Cout).astype(np.float32)
     var = rng.uniform(0.5, 1.5, Cout).astype(np.float32)
-    base = _run_conv(x, w, beta, mean, var, s, pad, 'bf16', tile=3)
-    assert_close(base, _ref_conv(x, w, beta, mean, var, s, pad, 'bf16'), 1e-2, 'conv %s' % (case,))
+    base = _run_conv(x, w, beta, mean, var, s, pad, dtype, tile=3)
+    _check(base, _ref_conv(x, w, beta, mean, var, s, pad, dtype), dtype, 'conv %s' % (case,))
     for tile in list(range(1, 13)) + list(range(26, 48)):
-        got = _run_conv(x, w, beta, mean, var, s, pad, 'bf16', tile=tile)
+        got = _run_conv(x, w, beta, mean, var, s, pad, dtype, tile=tile)
         np.testing.assert_array_equal(got, base, err_msg='tile %d %s' % (tile, case))
 
 
@@ -300,30 +354,50 @@ PATCH_CASES = [
 @pytest.mark.parametrize('tile', list(range(13, 26)) + list(range(48, 54)))
 @pytest.mark.parametrize('case', PATCH_CASES)
 def test_conv_patch_variants(case, tile):
+    _patch_variant(case, tile, 'bf16')
+
+
+@pytest.mark.parametrize('tile', list(range(13, 26)) + list(range(48, 54)))
+@pytest.mark.parametrize('case', PATCH_CASES)
+def test_conv_patch_variants_f16(case, tile):
+    _patch_variant(case, tile, 'f16')
+
+
+def _patch_variant(case, tile, dtype):
     B, H, W, Cin, Cout, k, pad = case
     rng = np.random.default_rng(B * 1000 + H * 7 + Cin + Cout + k[0] + tile)
-    x = cnn_ref.bf16_round(rng.standard_normal((B, H, W, Cin)).astype(np.float32))
+    x = _q_in(rng.standard_normal((B, H, W, Cin)).astype(np.float32), dtype)
     w = (rng.standard_normal((k[0], k[1], Cin, Cout)) / math.sqrt(k[0] * k[1] * Cin)).astype(np.float32)
     beta = 0.2 * rng.standard_normal(Cout).astype(np.float32)
     mean = 0.2 * rng.standard_normal(Cout).astype(np.float32)
     var = rng.uniform(0.5, 1.5, Cout).astype(np.float32)
-    ref = _ref_conv(x, w, beta, mean, var, 1, pad, 'bf16')
+    ref = _ref_conv(x, w, beta, mean, var, 1, pad, dtype)
     try:
-        got = _run_conv(x, w, beta, mean, var, 1, pad, 'bf16', tile=tile)
+        got = _run_conv(x, w, beta, mean, var, 1, pad, dtype, tile=tile)
     except L.ComicHipError as e:
         assert 'not eligible' in str(e) and Cin >= 128      # the input window of a fat-Cin layer does not fit the LDS
         pytest.skip(str(e))
-    assert_close(got, ref, 1e-2, 'patch conv %s tile %d' % (case, tile))
+    _check(got, ref, dtype, 'patch conv %s tile %d' % (case, tile))
     # same operands and k order per accumulator as the im2col kernel: identical bits
-    np.testing.assert_array_equal(got, _run_conv(x, w, beta, mean, var, 1, pad, 'bf16', tile=3))
-    got2 = _run_conv(x, w, beta, mean, var, 1, pad, 'bf16', dst_channels=Cout + 48, dst_coff=16, tile=tile)
+    np.testing.assert_array_equal(got, _run_conv(x, w, beta, mean, var, 1, pad, dtype, tile=3))
+    got2 = _run_conv(x, w, beta, mean, var, 1, pad, dtype, dst_channels=Cout + 48, dst_coff=16, tile=tile)
     np.testing.assert_array_equal(got2[..., 16:16 + Cout], got)
     assert (got2[..., :16] == -7).all() and (got2[..., 16 + Cout:] == -7).all()
 
 
 def test_conv_patch_random_sweep():
+    _patch_random_sweep('bf16')
+
+
+def test_conv_patch_random_sweep_f16():
+    _patch_random_sweep('f16')
+
+
+def _patch_random_sweep(dtype):
     """Random stride-1 layer shapes, source / destination channel slices and batch sizes: every eligible
-    patch-resident variant gives the bits of the im2col kernel (same operands, same k order)."""
+    patch-resident variant gives the bits of the im2col kernel (same operands, same k order); f16: the first cases'
+    im2col results against float64 too."""
+    tdt = _TDT[dtype]
     rng = np.random.default_rng(2024)
     n_ok = 0
     for case in range(40):
@@ -337,25 +411,30 @@ def test_conv_patch_random_sweep():
         xc = Cin + int(rng.choice([0, 8, 64])); xo = int(rng.choice([0, 8])) if xc > Cin else 0
         yc = Cout + int(rng.choice([0, 16, 48])); yo = int(rng.choice([0, 4, 16])) if yc >= Cout + 16 else 0
         relu = int(rng.integers(2))
-        x = torch.randn(B, H, W, xc, device=DEV).to(torch.bfloat16)
+        x = torch.randn(B, H, W, xc, device=DEV).to(tdt)
         K = kh * kw * Cin
         wf = torch.randn(Cout, (K + 63) // 64 * 64, device=DEV) / K ** 0.5
         wf[:, K:] = 0
-        w = wf.to(torch.bfloat16).contiguous()
+        w = wf.to(tdt).contiguous()
         scale, shift = torch.rand(Cout, device=DEV) + 0.5, torch.randn(Cout, device=DEV) * 0.1
         wt = L.ConvWeight(w.data_ptr(), scale.data_ptr(), shift.data_ptr())
         ref = None
         for tile in [3] + list(range(13, 26)) + list(range(48, 54)):
-            y = torch.full((B, Ho, Wo, yc), -7.0, dtype=torch.bfloat16, device=DEV)
+            y = torch.full((B, Ho, Wo, yc), -7.0, dtype=tdt, device=DEV)
             op = L.CnnOp(kind=0, src=0, dst=1, src_coff=xo, dst_coff=yo, H=H, W=W, Cin=Cin, Cout=Cout, KH=kh, KW=kw, SH=1,
                          SW=1, PT=pt, PL=pl, Ho=Ho, Wo=Wo, weight=0, relu=relu, out_f32=0, tile=tile)
-            rc = lib().comic_conv2d_bn_relu(C.byref(op), x.data_ptr(), xc, y.data_ptr(), yc, C.byref(wt), B, 1, stream())
+            rc = lib().comic_conv2d_bn_relu(C.byref(op), x.data_ptr(), xc, y.data_ptr(), yc, C.byref(wt), B, _CODE[dtype],
+                                            stream())
             sync()
             if rc != 0:
                 assert tile != 3 and b'not eligible' in lib().comic_last_error()
                 continue
             if tile == 3:
                 ref = y
+                if dtype == 'f16' and case < 6:     # the im2col kernel itself against float64 on the same operands
+                    _assert_f16(y[..., yo:yo + Cout].float().cpu().numpy(),
+                                _ref_from_packed(x[..., xo:xo + Cin], w, kh, kw, Cin, Cout, scale, shift, 1, pad, relu),
+                                'sweep case %d' % case)
             else:
                 assert torch.equal(y, ref), (case, tile, B, H, W, Cin, Cout, kh, kw, pad, xc, xo, yc, yo)
                 n_ok += 1
@@ -370,52 +449,78 @@ IMG_CASES = [   # (H, W, Cin, Cout, taps): every shape csrc/conv_img.hip is inst
 
 
 def _frag_weights(w, Cout, Kpad):
-    """comic_cnn_pack_frag_weights on one [Cout][Kpad] bf16 record."""
+    """comic_cnn_pack_frag_weights on one [Cout][Kpad] 16-bit record."""
     out = torch.zeros_like(w)
     table = torch.tensor([[0, Cout, Kpad]], dtype=torch.int64, device=DEV)
     L.check(lib().comic_cnn_pack_frag_weights(w.data_ptr(), out.data_ptr(), table.data_ptr(), 1, w.numel(), stream()), 'pack')
     return out
 
 
+def _ref_from_packed(x, w, kh, kw, Cin, Cout, scale, shift, stride, padding, relu):
+    """float64 reference of a conv given as device tensors: 16-bit activations x [B][H][W][Cin], the packed filter
+    w [Cout][Kpad] (k = (tap row, tap column, channel)), the folded fp32 scale / shift; output rounded once to f16."""
+    K = kh * kw * Cin
+    xs = x.double().cpu().numpy()
+    ws = w.reshape(Cout, -1)[:, :K].double().cpu().numpy().reshape(Cout, kh, kw, Cin).transpose(1, 2, 3, 0)
+    y = cnn_ref.conv2d(xs, ws, stride, padding) * scale.double().cpu().numpy() + shift.double().cpu().numpy()
+    return cnn_ref.f16_round(np.maximum(y, 0) if relu else y)
+
+
 @pytest.mark.parametrize('case', IMG_CASES)
 def test_conv_image_resident_identical_bits(case):
+    _image_resident(case, 'bf16')
+
+
+@pytest.mark.parametrize('case', IMG_CASES)
+def test_conv_image_resident_identical_bits_f16(case):
+    _image_resident(case, 'f16')
+
+
+def _image_resident(case, dtype):
     """The image-resident kernel (tile id 55: whole images in the LDS without halo, out-of-image taps read a zero page,
     weights streamed in fragment order) against the im2col kernel: same operands, same k order per accumulator ->
     identical bits.  Batch sizes that leave the last workgroup with fewer images than it has room for, source and
-    destination channel slices, with and without ReLU; one launch with two members (a grouped launch's form) too."""
+    destination channel slices, with and without ReLU; one launch with two members (a grouped launch's form) too.
+    f16: the fragment-order pack of an f16 record, and the im2col result against float64 on the same operands."""
     H, W, Cin, Cout, (kh, kw) = case
+    tdt, code = _TDT[dtype], _CODE[dtype]
     rng = np.random.default_rng(H * 131 + Cin + Cout + 7 * kh + kw)
     K = kh * kw * Cin
     Kpad = (K + 63) // 64 * 64
     pt, pl = (kh - 1) // 2, (kw - 1) // 2
     for B, xc, xo, yc, yo, relu in ((1, Cin, 0, Cout, 0, 1), (5, Cin + 64, 8, Cout + 48, 16, 1), (13, Cin, 0, Cout + 16, 4, 0)):
-        x = torch.randn(B, H, W, xc, device=DEV).to(torch.bfloat16)
+        x = torch.randn(B, H, W, xc, device=DEV).to(tdt)
         wf = torch.randn(Cout, Kpad, device=DEV) / K ** 0.5
         wf[:, K:] = 0
-        w = wf.to(torch.bfloat16).contiguous()
+        w = wf.to(tdt).contiguous()
         frag = _frag_weights(w, Cout, Kpad)
         # the packing itself: lane l of step s of tile t holds W[16 t + (l & 15)][32 s + 8 (l >> 4) .. + 8]
         f = frag.view(Cout // 16, Kpad // 32, 64, 8)
         for t, s_, l in ((0, 0, 0), (Cout // 16 - 1, Kpad // 32 - 1, 63), (1, 3, 37)):
-            assert torch.equal(f[t, s_, l], w[16 * t + (l & 15), 32 * s_ + 8 * (l >> 4):32 * s_ + 8 * (l >> 4) + 8])
+            assert torch.equal(f[t, s_, l].view(torch.int16),
+                               w[16 * t + (l & 15), 32 * s_ + 8 * (l >> 4):32 * s_ + 8 * (l >> 4) + 8].view(torch.int16))
         scale, shift = torch.rand(Cout, device=DEV) + 0.5, torch.randn(Cout, device=DEV) * 0.1
         wt = L.ConvWeight(w.data_ptr(), scale.data_ptr(), shift.data_ptr(), frag.data_ptr())
         ys = {}
         for tile in (3, L.IMG_TILE):
-            y = torch.full((B, H, W, yc), -7.0, dtype=torch.bfloat16, device=DEV)
+            y = torch.full((B, H, W, yc), -7.0, dtype=tdt, device=DEV)
             op = L.CnnOp(kind=0, src=0, dst=1, src_coff=xo, dst_coff=yo, H=H, W=W, Cin=Cin, Cout=Cout, KH=kh, KW=kw, SH=1,
                          SW=1, PT=pt, PL=pl, Ho=H, Wo=W, weight=0, relu=relu, out_f32=0, tile=tile)
-            L.check(lib().comic_conv2d_bn_relu(C.byref(op), x.data_ptr(), xc, y.data_ptr(), yc, C.byref(wt), B, 1, stream()),
+            L.check(lib().comic_conv2d_bn_relu(C.byref(op), x.data_ptr(), xc, y.data_ptr(), yc, C.byref(wt), B, code, stream()),
                     'conv tile %d' % tile)
             sync()
             ys[tile] = y
-        assert torch.equal(ys[L.IMG_TILE], ys[3]), (case, B)
+        assert torch.equal(ys[L.IMG_TILE].view(torch.int16), ys[3].view(torch.int16)), (case, B)
         assert bool((ys[3][..., yo:yo + Cout].float().abs().max() > 0.1))
+        if dtype == 'f16' and B < 13:
+            _assert_f16(ys[L.IMG_TILE][..., yo:yo + Cout].float().cpu().numpy(),
+                        _ref_from_packed(x[..., xo:xo + Cin], w, kh, kw, Cin, Cout, scale, shift, 1, 'SAME', relu),
+                        'image-resident %s B=%d' % (case, B))
     # without fragment-order weights the id is refused, like a patch id on an ineligible layer
     wt0 = L.ConvWeight(w.data_ptr(), scale.data_ptr(), shift.data_ptr())
     op = L.CnnOp(kind=0, src=0, dst=1, H=H, W=W, Cin=Cin, Cout=Cout, KH=kh, KW=kw, SH=1, SW=1, PT=pt, PL=pl, Ho=H, Wo=W,
                  weight=0, relu=1, tile=L.IMG_TILE)
-    assert lib().comic_conv2d_bn_relu(C.byref(op), x.data_ptr(), xc, y.data_ptr(), yc, C.byref(wt0), B, 1, stream()) != 0
+    assert lib().comic_conv2d_bn_relu(C.byref(op), x.data_ptr(), xc, y.data_ptr(), yc, C.byref(wt0), B, code, stream()) != 0
     assert b'not eligible' in lib().comic_last_error()
 
 
@@ -442,21 +547,65 @@ def test_stem_conv(dtype):
     assert_close(got, cnn_ref.bf16_round(ref) if dtype == 'bf16' else ref, 1e-4 if dtype == 'f32' else 5e-3, 'stem')
 
 
-def _run_pool(x, kind, k, s, pad, dtype, dst_channels=None, dst_coff=0):
+# the three stem kernels: the 3x3x3 VALID MFMA form (Inception-V3 Conv2d_1a), the direct kernel (tile 1), and
+# conv_stem_wide_kernel at Inception-V1's Conv2d_1a_7x7 shape (7x7 / 2 SAME, 3 -> 64; 16-bit plans only)
+STEM_CASES = [((2, 37, 41, 3), (3, 3), 32, 2, 'VALID', 0), ((2, 37, 41, 3), (3, 3), 32, 2, 'VALID', 1),
+              ((1, 224, 224, 3), (7, 7), 64, 2, 'SAME', 0), ((2, 30, 36, 3), (7, 7), 64, 2, 'SAME', 1)]
+
+
+@pytest.mark.parametrize('case', STEM_CASES)
+def test_stem_conv_f16(case):
+    """f16 plans: the stem reads the fp32 image and fp32 filter, accumulates in fp32 and stores f16 once -- against
+    float64 with one rounding of the output, at the fp32 bar; the three stem kernels give the bits of each other where
+    two of them take the same layer."""
+    shape, (kh, kw), Cout, s, pad, tile = case
+    rng = np.random.default_rng(sum(shape) + Cout)
+    x = rng.uniform(-1, 1, shape).astype(np.float32)
+    w = (rng.standard_normal((kh, kw, 3, Cout)) / math.sqrt(kh * kw * 3)).astype(np.float32)
+    beta = 0.1 * rng.standard_normal(Cout).astype(np.float32)
+    mean = 0.1 * rng.standard_normal(Cout).astype(np.float32)
+    var = rng.uniform(0.5, 1.5, Cout).astype(np.float32)
+    got = _run_conv(x, w, beta, mean, var, s, pad, 'f16', tile=tile)
+    _assert_f16(got, _ref_conv(x, w, beta, mean, var, s, pad, 'f16'), 'stem %s tile %d' % (shape, tile))
+    if tile == 0:       # the direct kernel on the same layer: the same products in another order, within the bar
+        _assert_f16(_run_conv(x, w, beta, mean, var, s, pad, 'f16', tile=1), _ref_conv(x, w, beta, mean, var, s, pad, 'f16'),
+                    'stem direct %s' % (shape,))
+
+
+def _run_pool(x, kind, k, s, pad, dtype, dst_channels=None, dst_coff=0, tile=0):
     B, H, W, Cc = x.shape
     kh, kw = (k, k) if isinstance(k, int) else k
     Ho, pt, _ = cnn_ref.out_size(H, kh, s, pad)
     Wo, pl, _ = cnn_ref.out_size(W, kw, s, pad)
-    tdt = torch.bfloat16 if dtype == 'bf16' else torch.float32
+    tdt = _TDT[dtype]
     xd = dev(x).to(tdt)
     yc = dst_channels or Cc
     y = torch.full((B, Ho, Wo, yc), -7.0, dtype=torch.float32 if kind == 4 else tdt, device=DEV)
     op = L.CnnOp(kind=kind, src=0, dst=1, src_coff=0, dst_coff=dst_coff, H=H, W=W, Cin=Cc, Cout=Cc, KH=kh, KW=kw,
-                 SH=s, SW=s, PT=pt, PL=pl, Ho=Ho, Wo=Wo, weight=-1, relu=0, out_f32=int(kind == 4))
+                 SH=s, SW=s, PT=pt, PL=pl, Ho=Ho, Wo=Wo, weight=-1, relu=0, out_f32=int(kind == 4), tile=tile)
     L.check(lib().comic_conv2d_bn_relu(C.byref(op), xd.data_ptr(), Cc, y.data_ptr(), yc, None, B,
-                                       1 if dtype == 'bf16' else 0, stream()), 'pool')
+                                       _CODE[dtype], stream()), 'pool')
     sync()
     return y.float().cpu().numpy()
+
+
+def _run_pool_bn_relu(x, beta, mean, var, dtype, tile, relu=1, out_f32=0, dst_channels=None, dst_coff=0):
+    """Kind 7: 3x3 / 1 SAME average of an fp32 map (the raw 1x1 projection of a pool branch), then the folded BatchNorm
+    and ReLU, stored in the plan's 16-bit format (or fp32 with out_f32).  tile 1: the row-walking kernel
+    (pool_bn_relu_rows_kernel), tile 2: one thread per pixel (pool_bn_relu_kernel)."""
+    B, H, W, Cc = x.shape
+    scale = torch.empty(Cc, device=DEV); shift = torch.empty(Cc, device=DEV)
+    L.check(lib().comic_fold_bn(P(beta), P(mean), P(var), 1e-3, scale.data_ptr(), shift.data_ptr(), Cc, stream()))
+    xd = dev(x)
+    yc = dst_channels or Cc
+    y = torch.full((B, H, W, yc), -7.0, dtype=torch.float32 if out_f32 else _TDT[dtype], device=DEV)
+    op = L.CnnOp(kind=7, src=0, dst=1, src_coff=0, dst_coff=dst_coff, H=H, W=W, Cin=Cc, Cout=Cc, KH=3, KW=3, SH=1, SW=1,
+                 PT=1, PL=1, Ho=H, Wo=W, weight=0, relu=relu, out_f32=out_f32, src_f32=1, tile=tile)
+    wt = L.ConvWeight(None, scale.data_ptr(), shift.data_ptr())
+    L.check(lib().comic_conv2d_bn_relu(C.byref(op), xd.data_ptr(), Cc, y.data_ptr(), yc, C.byref(wt), B, _CODE[dtype],
+                                       stream()), 'pool+bn')
+    sync()
+    return y
 
 
 def test_device_image_preprocess_matches_numpy_pipeline():
@@ -482,16 +631,17 @@ def test_device_image_preprocess_matches_numpy_pipeline():
                                   preprocess_ref.preprocess_image(im, 256, 256, True, 0, 0))
 
 
-@pytest.mark.parametrize('dtype', ['f32', 'bf16'])
+@pytest.mark.parametrize('dtype', ['f32', 'bf16', 'f16'])
 def test_pools(dtype):
     rng = np.random.default_rng(1)
-    x = rng.standard_normal((3, 13, 11, 64)).astype(np.float32)
-    if dtype == 'bf16':
-        x = cnn_ref.bf16_round(x)
-    q = cnn_ref.bf16_round if dtype == 'bf16' else (lambda a: a)
+    x = _q_in(rng.standard_normal((3, 13, 11, 64)).astype(np.float32), dtype)
     np.testing.assert_array_equal(_run_pool(x, 2, 3, 2, 'VALID', dtype), cnn_ref.max_pool(x, 3, 2, 'VALID'))
     got = _run_pool(x, 3, 3, 1, 'SAME', dtype)
-    assert_close(got, q(cnn_ref.avg_pool(x, 3, 1, 'SAME')), 1e-6 if dtype == 'f32' else 5e-3, 'avgpool')
+    if dtype == 'f16':          # fp32 sum / count, one RNE store: against float64
+        _assert_f16(got, cnn_ref.f16_round(cnn_ref.avg_pool(x.astype(np.float64), 3, 1, 'SAME')), 'avgpool')
+    else:
+        q = cnn_ref.bf16_round if dtype == 'bf16' else (lambda a: a)
+        assert_close(got, q(cnn_ref.avg_pool(x, 3, 1, 'SAME')), 1e-6 if dtype == 'f32' else 5e-3, 'avgpool')
     got = _run_pool(x, 2, 3, 2, 'VALID', dtype, dst_channels=160, dst_coff=96)
     np.testing.assert_array_equal(got[..., 96:], cnn_ref.max_pool(x, 3, 2, 'VALID'))
     x5 = x[:, :5, :5, :]
@@ -499,6 +649,223 @@ def test_pools(dtype):
     assert_close(got, cnn_ref.avg_pool(x5, 5, 1, 'VALID'), 1e-5, 'global avgpool')
     got = _run_pool(x[:, :9, :9, :], 4, 8, 1, 'VALID', dtype)        # 9x9 map, 8x8 window -> 2x2
     assert_close(got, cnn_ref.avg_pool(x[:, :9, :9, :], 8, 1, 'VALID'), 1e-5, 'global avgpool 8x8')
+    if dtype != 'f32':
+        # the stride-1 3x3 SAME max-pool of Inception-V1: the row-walking kernel (tile 1) and the per-pixel one (tile 2)
+        want = cnn_ref.max_pool(x, 3, 1, 'SAME')
+        for tile in (1, 2):
+            np.testing.assert_array_equal(_run_pool(x, 2, 3, 1, 'SAME', dtype, tile=tile), want, err_msg='tile %d' % tile)
+
+
+@pytest.mark.parametrize('dtype', ['bf16', 'f16'])
+@pytest.mark.parametrize('shape', [(3, 13, 11, 64), (2, 25, 25, 96), (1, 5, 5, 32)])
+def test_pool_bn_relu(shape, dtype):
+    """Kind 7 on both kernels (row walk and per pixel): against float64 (average, BatchNorm, ReLU) with one rounding of
+    the output -- f16 at the fp32 bar, bf16 within one output ulp; the two kernels sum in different orders, so they
+    are each held to the reference; a destination channel slice leaves its neighbours untouched."""
+    B, H, W, Cc = shape
+    rng = np.random.default_rng(B * H + Cc)
+    x = (2 * rng.standard_normal(shape)).astype(np.float32)
+    beta = 0.2 * rng.standard_normal(Cc).astype(np.float32)
+    mean = 0.2 * rng.standard_normal(Cc).astype(np.float32)
+    var = rng.uniform(0.5, 1.5, Cc).astype(np.float32)
+    scale = 1.0 / np.sqrt(var.astype(np.float64) + cnn_ref.BN_EPS)
+    for relu in (1, 0):
+        y = cnn_ref.avg_pool(x.astype(np.float64), 3, 1, 'SAME')
+        y = (y - mean) * scale + beta
+        y = np.maximum(y, 0) if relu else y
+        for tile in (1, 2):
+            got = _run_pool_bn_relu(x, beta, mean, var, dtype, tile, relu=relu).float().cpu().numpy()
+            if dtype == 'f16':
+                _assert_f16(got, cnn_ref.f16_round(y), 'pool+bn %s tile %d' % (shape, tile))
+            else:
+                assert_close(got, cnn_ref.bf16_round(y.astype(np.float32)), 1e-2, 'pool+bn %s tile %d' % (shape, tile))
+    got = _run_pool_bn_relu(x, beta, mean, var, dtype, 1, dst_channels=Cc + 24, dst_coff=8).float().cpu().numpy()
+    assert (got[..., :8] == -7).all() and (got[..., 8 + Cc:] == -7).all()
+    np.testing.assert_array_equal(got[..., 8:8 + Cc], _run_pool_bn_relu(x, beta, mean, var, dtype, 1).float().cpu().numpy())
+
+
+@pytest.mark.parametrize('case', [(3, 25, 25, 288, 64, 0), (2, 25, 25, 192, 48, 0), (2, 21, 19, 64, 80, 0),
+                                  (3, 23, 23, 64, 80, L.OP_POOLED_SRC), (2, 13, 12, 192, 48, L.OP_POOLED_SRC),
+                                  (1, 13, 13, 192, 256, L.OP_POOLED_SRC)])
+def test_conv_weight_stationary_f16(case):
+    """Single 1x1 convs on the weight-stationary kernel (tile id 54, csrc/conv_ws.hip) on f16, plain and with
+    COMIC_OP_POOLED_SRC (the 3x3 / 2 VALID max-pool folded into the loads): against max-pool-then-conv in float64 at the
+    fp32 bar, and bit for bit against the im2col kernel on the same (pooled) operands."""
+    B, H, W, Cin, Cout, flags = case
+    rng = np.random.default_rng(B + H + W + Cin + Cout + flags)
+    x = cnn_ref.f16_round(rng.standard_normal((B, H, W, Cin)).astype(np.float32))
+    w = (rng.standard_normal((1, 1, Cin, Cout)) / math.sqrt(Cin)).astype(np.float32)
+    beta = 0.2 * rng.standard_normal(Cout).astype(np.float32)
+    mean = 0.2 * rng.standard_normal(Cout).astype(np.float32)
+    var = rng.uniform(0.5, 1.5, Cout).astype(np.float32)
+    xin = cnn_ref.max_pool(x, 3, 2, 'VALID') if flags else x          # exact in f16
+    ref = _ref_conv(xin, w, beta, mean, var, 1, 'SAME', 'f16')
+    got = _run_conv(x, w, beta, mean, var, 1, 'SAME', 'f16', tile=L.WS_TILE, flags=flags)
+    _assert_f16(got, ref, 'ws %s' % (case,))
+    np.testing.assert_array_equal(got, _run_conv(xin, w, beta, mean, var, 1, 'SAME', 'f16', tile=3))
+    got2 = _run_conv(x, w, beta, mean, var, 1, 'SAME', 'f16', tile=L.WS_TILE, flags=flags, dst_channels=Cout + 32, dst_coff=16)
+    np.testing.assert_array_equal(got2[..., 16:16 + Cout], got)
+    assert (got2[..., :16] == -7).all() and (got2[..., 16 + Cout:] == -7).all()
+
+
+# ---- the 16-bit store is IEEE conversion (RNE, subnormals, overflow to inf) ------------------------------------------
+def _range_bn(Cout, dtype):
+    """Per-channel (beta, mean, var) putting the outputs of a conv with O(1) products in four ranges (a quarter of the
+    channels each): f16 subnormals (scale 2^-19), around 1, just below 65504 (shift 65490) and past 65520 (shift 7e4).
+    relu is off, so each range holds both signs where the shift does not dominate."""
+    q = Cout // 4
+    scale = np.concatenate([np.full(q, 2.0 ** -19), np.ones(q), np.full(q, 4.0), np.ones(Cout - 3 * q)])
+    shift = np.concatenate([np.zeros(q), np.zeros(q), np.full(q, 65490.0), np.full(Cout - 3 * q, 7e4)])
+    var = (1.0 / scale ** 2 - cnn_ref.BN_EPS).astype(np.float32)
+    mean = np.zeros(Cout, np.float32)
+    return shift.astype(np.float32), mean, var
+
+
+def _store_cases():
+    # (name, B, H, W, Cin, Cout, (kh, kw), stride, padding, tile, flags)
+    return [('im2col', 2, 9, 9, 64, 64, (3, 3), 1, 'SAME', 3, 0), ('im2col wide', 2, 9, 9, 64, 64, (3, 3), 1, 'SAME', 26, 0),
+            ('patch', 2, 9, 9, 64, 64, (3, 3), 1, 'SAME', 13, 0), ('patch loader waves', 2, 9, 9, 64, 64, (3, 3), 1, 'SAME', 48, 0),
+            ('image-resident', 3, 12, 12, 128, 128, (1, 7), 1, 'SAME', L.IMG_TILE, 0),
+            ('weight-stationary', 2, 9, 9, 64, 64, (1, 1), 1, 'SAME', L.WS_TILE, 0),
+            ('weight-stationary pooled', 2, 11, 11, 64, 64, (1, 1), 1, 'SAME', L.WS_TILE, L.OP_POOLED_SRC),
+            ('stem mfma', 2, 17, 19, 3, 32, (3, 3), 2, 'VALID', 0, 0), ('stem direct', 2, 17, 19, 3, 32, (3, 3), 2, 'VALID', 1, 0),
+            ('stem wide', 1, 224, 224, 3, 64, (7, 7), 2, 'SAME', 0, 0)]
+
+
+def _conv_f32_and_16(case, dtype, x, w, beta, mean, var):
+    name, B, H, W, Cin, Cout, (kh, kw), s, pad, tile, flags = case
+    if tile == L.IMG_TILE:          # fragment-order weights: through the device-tensor path
+        K = kh * kw * Cin
+        Kpad = (K + 63) // 64 * 64
+        tdt, code = _TDT[dtype], _CODE[dtype]
+        wd = dev(w)
+        packed = torch.zeros(Cout * Kpad, dtype=tdt, device=DEV)
+        L.check(lib().comic_pack_conv_weights(wd.data_ptr(), packed.data_ptr(), kh, kw, Cin, Cout, code, stream()))
+        frag = _frag_weights(packed, Cout, Kpad)
+        scale = torch.empty(Cout, device=DEV); shift = torch.empty(Cout, device=DEV)
+        L.check(lib().comic_fold_bn(P(beta), P(mean), P(var), 1e-3, scale.data_ptr(), shift.data_ptr(), Cout, stream()))
+        wt = L.ConvWeight(packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), frag.data_ptr())
+        xd = dev(x).to(tdt)
+        outs = []
+        for out_f32 in (1, 0):
+            y = torch.full((B, H, W, Cout), -7.0, dtype=torch.float32 if out_f32 else tdt, device=DEV)
+            op = L.CnnOp(kind=0, src=0, dst=1, H=H, W=W, Cin=Cin, Cout=Cout, KH=kh, KW=kw, SH=1, SW=1, PT=(kh - 1) // 2,
+                         PL=(kw - 1) // 2, Ho=H, Wo=W, weight=0, relu=0, out_f32=out_f32, tile=tile)
+            L.check(lib().comic_conv2d_bn_relu(C.byref(op), xd.data_ptr(), Cin, y.data_ptr(), Cout, C.byref(wt), B, code,
+                                               stream()), name)
+            sync()
+            outs.append(y)
+        return outs
+    return [torch.from_numpy(_run_conv(x, w, beta, mean, var, s, pad, dtype, relu=0, out_f32=o, tile=tile, flags=flags))
+            for o in (1, 0)]
+
+
+@pytest.mark.parametrize('dtype', ['bf16', 'f16'])
+@pytest.mark.parametrize('case', _store_cases(), ids=lambda c: c[0].replace(' ', '_'))
+def test_conv_16bit_store_is_ieee_conversion(case, dtype):
+    """The same launch with out_f32 = 1 and with the 16-bit store: the work is the same, so the 16-bit output must be the
+    IEEE conversion of the fp32 one bit for bit -- RNE, subnormal outputs kept, overflow past 65520 to +-inf (what torch
+    does) -- over outputs in the f16 subnormal range, around 1, just below 65504 and past 65520."""
+    name, B, H, W, Cin, Cout, (kh, kw), s, pad, tile, flags = case
+    rng = np.random.default_rng(Cin * 7 + Cout + kh)
+    x = _q_in(rng.standard_normal((B, H, W, Cin)).astype(np.float32), dtype) if Cin > 4 else \
+        rng.uniform(-1, 1, (B, H, W, Cin)).astype(np.float32)
+    w = (rng.standard_normal((kh, kw, Cin, Cout)) * (8.0 / math.sqrt(kh * kw * Cin))).astype(np.float32)
+    beta, mean, var = _range_bn(Cout, dtype)
+    y32, y16 = _conv_f32_and_16(case, dtype, x, w, beta, mean, var)
+    y32 = torch.as_tensor(y32).float().cpu()
+    want = y32.half() if dtype == 'f16' else y32.bfloat16()
+    got = torch.as_tensor(y16).cpu().to(want.dtype)
+    assert torch.equal(got.view(torch.int16), want.view(torch.int16)), \
+        '%s: %d of %d values differ' % (name, int((got.view(torch.int16) != want.view(torch.int16)).sum()), got.numel())
+    if dtype == 'f16':          # the four ranges were all reached
+        a = y32.abs()
+        q = Cout // 4
+        assert ((a[..., :q] < 2.0 ** -14) & (a[..., :q] > 0)).float().mean() > 0.5
+        assert (want[..., 2 * q:3 * q].float() == 65504).any() and torch.isinf(want[..., 3 * q:].float()).all()
+        assert (want[..., 2 * q:3 * q].float() < 65504).any()
+
+
+@pytest.mark.parametrize('dtype', ['bf16', 'f16'])
+@pytest.mark.parametrize('tile', [1, 2])
+def test_pool_bn_relu_16bit_store_is_ieee_conversion(tile, dtype):
+    """Kind 7's 16-bit store against its own fp32 store, bit for bit, over the four output ranges."""
+    rng = np.random.default_rng(tile)
+    x = (8 * rng.standard_normal((2, 9, 11, 64))).astype(np.float32)
+    beta, mean, var = _range_bn(64, dtype)
+    y32 = _run_pool_bn_relu(x, beta, mean, var, dtype, tile, relu=0, out_f32=1).cpu()
+    y16 = _run_pool_bn_relu(x, beta, mean, var, dtype, tile, relu=0).cpu()
+    want = y32.half() if dtype == 'f16' else y32.bfloat16()
+    assert torch.equal(y16.view(torch.int16), want.view(torch.int16))
+
+
+def _f16_edge_vector():
+    from tests.test_oracle_cnn import F16_EDGES
+    rng = np.random.default_rng(0)
+    rand = np.concatenate([rng.standard_normal(4000), rng.standard_normal(2000) * 2.0 ** -17,
+                           rng.uniform(3e4, 7e4, 2000)])
+    # fp32 values on both sides of every f16 rounding boundary near the edges
+    mids = np.array([(2 * k + 1) * 2.0 ** -25 for k in range(8)] + [1 + 2.0 ** -11, 65504 + 8, 65504 + 16])
+    near = np.concatenate([np.nextafter(mids.astype(np.float32), np.float32(np.inf)),
+                           np.nextafter(mids.astype(np.float32), np.float32(-np.inf)), mids])
+    v = np.concatenate([F16_EDGES, -F16_EDGES, rand, -rand, near, -near]).astype(np.float32)
+    return np.concatenate([v, np.zeros(-len(v) % 64, np.float32)])
+
+
+def test_f16_weight_conversion_is_ieee():
+    """The two routes by which weights reach f16 -- comic_cnn_refresh_weights_dtype (the product's plan copy) and
+    comic_pack_conv_weights (code 2) -- against master.half(), bit for bit, over the edge classes of IEEE half."""
+    v = _f16_edge_vector()
+    n = v.size
+    master = dev(v)
+    want = master.cpu().half()
+    cout = 64
+    out = torch.zeros(n, dtype=torch.float16, device=DEV)
+    beta = torch.zeros(cout, device=DEV); mean = torch.zeros(cout, device=DEV)
+    scale = torch.ones(cout, device=DEV); shift = torch.empty(cout, device=DEV)
+    L.check(lib().comic_cnn_refresh_weights_dtype(master.data_ptr(), out.data_ptr(), n, beta.data_ptr(), mean.data_ptr(),
+                                                  scale.data_ptr(), shift.data_ptr(), cout, 2, stream()), 'refresh')
+    sync()
+    assert torch.equal(out.cpu().view(torch.int16), want.view(torch.int16)), \
+        'refresh: %d values differ' % int((out.cpu().view(torch.int16) != want.view(torch.int16)).sum())
+    # pack: HWIO [1][1][K][Cout] -> [Cout][Kpad], padding columns zero
+    K = n // cout
+    Kpad = (K + 63) // 64 * 64
+    packed = torch.full((cout, Kpad), 7.0, dtype=torch.float16, device=DEV)
+    L.check(lib().comic_pack_conv_weights(master.data_ptr(), packed.data_ptr(), 1, 1, K, cout, 2, stream()), 'pack')
+    sync()
+    wantp = want.reshape(K, cout).t().contiguous()
+    assert torch.equal(packed[:, :K].cpu().view(torch.int16), wantp.view(torch.int16))
+    assert not packed[:, K:].view(torch.int16).any()
+
+
+@pytest.mark.parametrize('which', ['inputs', 'weights'])
+def test_conv_f16_subnormal_operands(which):
+    """f16 operands in the subnormal range (|v| in [2^-24, 2^-14)) on the MFMA path: subnormal activations with weights
+    large enough that the products are normal, then the reverse -- against float64 on the same operands at the fp32 bar.
+    This measures whether v_mfma_f32_16x16x32_f16 on gfx950 keeps f16 subnormal A / B operands: it does (a flush would put
+    the result at the BatchNorm shift alone)."""
+    rng = np.random.default_rng(3 if which == 'inputs' else 4)
+    B, H, W, Cin, Cout = 2, 9, 9, 64, 64
+    sub = lambda shape: (np.sign(rng.standard_normal(shape)) * rng.uniform(2.0 ** -24, 2.0 ** -14, shape)).astype(np.float32)
+    if which == 'inputs':
+        x = cnn_ref.f16_round(sub((B, H, W, Cin)))
+        w = (rng.standard_normal((3, 3, Cin, Cout)) * 2.0 ** 12).astype(np.float32)
+    else:
+        x = cnn_ref.f16_round(rng.standard_normal((B, H, W, Cin)).astype(np.float32))
+        w = sub((3, 3, Cin, Cout))
+    x16 = cnn_ref.f16_round(x); w16 = cnn_ref.f16_round(w)
+    sub_share = np.mean((np.abs(x16 if which == 'inputs' else w16) < 2.0 ** -14) & ((x16 if which == 'inputs' else w16) != 0))
+    assert sub_share > 0.95
+    # scale the products back to O(1) through the BatchNorm (subnormal weights: var small)
+    ref_raw = cnn_ref.conv2d(x16.astype(np.float64), w16.astype(np.float64), 1, 'SAME')
+    amp = float(np.abs(ref_raw).max())
+    var = np.full(Cout, max((amp / 4.0) ** 2 - cnn_ref.BN_EPS, 0.0), np.float32)
+    beta = np.zeros(Cout, np.float32); mean = np.zeros(Cout, np.float32)
+    ref = _ref_conv(x16, w16, beta, mean, var, 1, 'SAME', 'f16', relu=0)
+    for tile in (3, 13, 26):
+        got = _run_conv(x16, w16, beta, mean, var, 1, 'SAME', 'f16', relu=0, tile=tile)
+        _assert_f16(got, ref, 'subnormal %s tile %d' % (which, tile))
 
 
 # ------------------------------------------------------------------------ decoder kernels --

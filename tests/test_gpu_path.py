@@ -86,7 +86,7 @@ def test_inception_v3_forward_224_bf16x3_meets_the_fp32_bar(cnn_params):
     assert_close(im_p.cpu().numpy(), net_ref.reshape(B, -1), F32_RTOL, 'im_embed bf16x3, pool after projection')
 
 
-@pytest.mark.parametrize('dtype,tol', [('f32', 1e-3), ('bf16', 3e-2)])
+@pytest.mark.parametrize('dtype,tol', [('f32', 1e-3), ('bf16', 3e-2), ('f16', 5e-3)])
 def test_inception_v3_pool_after_projection(cnn_params, dtype, tol):
     """Forward-only rewrite of the pool branches (1x1 projection first, then the 3x3 average with the
     BN + ReLU epilogue, kind 7): same end points as the reference order, against the oracle and against

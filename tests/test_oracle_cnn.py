@@ -1,6 +1,7 @@
 """InceptionV3 oracle vs the pins the reference's own tests hold (shapes, end-point
 names, parameter count) and vs an independent torch-CPU formulation.  CPU only."""
 import numpy as np
+import pytest
 import torch
 import torch.nn.functional as F
 
@@ -81,6 +82,48 @@ def test_bf16_round():
     r = cnn_ref.bf16_round(x)
     t = torch.tensor(x).to(torch.bfloat16).float().numpy()
     np.testing.assert_array_equal(r, t)
+
+
+# IEEE half edge classes: signed zeros, the smallest subnormal and ties between subnormals (to even), the smallest normal,
+# the largest finite value, the last value that rounds down to it and the first that overflows, values at and below half
+# the smallest subnormal (to zero), and ordinary ties in the normal range
+F16_EDGES = np.array([0.0, -0.0, 2.0 ** -24, -2.0 ** -24, 2.5 * 2.0 ** -24, 3.5 * 2.0 ** -24, -5.5 * 2.0 ** -24,
+                      1023.5 * 2.0 ** -24, 2.0 ** -14, -2.0 ** -14, (2.0 ** -14) * (1 - 2.0 ** -12), 65504.0, -65504.0,
+                      65519.99, 65520.0, -65520.0, 1e6, 2.0 ** -25, -2.0 ** -25, 2.0 ** -26, 1e-9,
+                      1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, 1.0, -3.1415927])
+
+
+@pytest.mark.parametrize('dt', [np.float32, np.float64])
+def test_f16_round_edges(dt):
+    """f16_round is IEEE RNE to half, bit for bit against numpy's and torch's conversions, across the range."""
+    x = F16_EDGES.astype(dt)
+    r = cnn_ref.f16_round(x)
+    assert r.dtype == dt
+    with np.errstate(over='ignore'):
+        want = x.astype(np.float16)
+    np.testing.assert_array_equal(r.astype(np.float16).view(np.uint16), want.view(np.uint16))
+    th = torch.from_numpy(x).half().view(torch.int16).numpy().view(np.uint16)
+    np.testing.assert_array_equal(r.astype(np.float16).view(np.uint16), th)
+    # the classes themselves, spelt out
+    got = dict(zip(F16_EDGES.tolist(), r.tolist()))
+    assert got[2.5 * 2.0 ** -24] == 2 * 2.0 ** -24 and got[3.5 * 2.0 ** -24] == 4 * 2.0 ** -24
+    assert got[65519.99] == 65504.0 and got[65520.0] == np.inf and got[-65520.0] == -np.inf
+    assert got[2.0 ** -25] == 0.0 and got[2.0 ** -26] == 0.0 and got[2.0 ** -24] == 2.0 ** -24
+    assert np.signbit(r[1]) and not np.signbit(r[0]) and np.signbit(r[F16_EDGES.tolist().index(-2.0 ** -25)])
+    assert got[1 + 2.0 ** -11] == 1.0 and got[1 + 3 * 2.0 ** -11] == 1 + 2 * 2.0 ** -10
+
+
+def test_f16_emulation_rounds_storage():
+    """act_dtype='f16': conv inputs, weights and stored outputs are IEEE half values."""
+    params = cnn_ref.randomize_bn(cnn_ref.init_params(0, 75))
+    x = np.random.default_rng(2).uniform(-1, 1, (1, 75, 75, 3)).astype(np.float32)
+    _, ep16 = cnn_ref.inception_v3(params, x, act_dtype='f16')
+    _, ep32 = cnn_ref.inception_v3(params, x, act_dtype='f32')
+    for name in ('Conv2d_1a_3x3', 'Mixed_5b', 'Mixed_6e'):
+        a = ep16[name]
+        np.testing.assert_array_equal(a, a.astype(np.float16).astype(np.float32))
+        assert not np.array_equal(a, ep32[name])
+        assert np.abs(a - ep32[name]).max() <= 1e-2 * np.abs(ep32[name]).max()
 
 
 def test_forward_small_image_finite_and_deterministic():
