@@ -171,6 +171,9 @@ _SIGS = {
     'comic_decoder_infer_workspace': (c_int64, [P, c_int, c_int]),
     'comic_decoder_train_step': (c_int, [P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P,
                                          P, P, P, P, P, c_int64, P]),
+    'comic_decoder_score_workspace': (c_int64, [P, c_int, c_int]),
+    'comic_decoder_score': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, c_int64, P]),
+    'comic_decoder_score_path': (c_int, []),
     'comic_decoder_greedy': (c_int, [P, P, P, P, c_int, c_int, P, P, P, P, P, c_int64, P]),
     'comic_decoder_sample': (c_int, [P, P, P, P, c_int, c_int, P, P, P, P, P, P, c_int64, P]),
     'comic_decoder_beam': (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int64, P]),

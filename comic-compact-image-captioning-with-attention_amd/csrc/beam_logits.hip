@@ -30,6 +30,7 @@
 
 #include <algorithm>
 
+#include "beam_pack.h"
 #include "conv_common.h"
 #include "lstm_prep.h"
 #include "lstm_stream_dev.h"
@@ -42,13 +43,6 @@
 
 namespace {
 
-#ifndef BL_VT
-#define BL_VT 7
-#endif
-// 16-column tiles per workgroup: 7 -> 112-column chunks, 229 workgroups at V = 25 599 (8 -> 200 of the 256 CUs)
-constexpr int kVT = BL_VT;
-constexpr int kChunkCols = 16 * kVT;    // vocabulary columns per workgroup
-constexpr int kQuarterBytes = 4 * kVT * 2 * 1024;     // four k-steps of kVT tiles x {hi, lo} x 1 KB
 constexpr int kBiasBytes = 512;
 
 struct BLVal {

@@ -76,6 +76,13 @@ int comic_beam_logits_step(const float* y, const void* y_frag_in, const void* wo
                            int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores,
                            int32_t* steps_executed, int t, int max_steps, int B, int W, int D, int V, int end_id,
                            const LstmPrepArgs* prep, hipStream_t st);
+// score_logits.hip
+bool comic_score_stream_supported(int D, int V);
+int64_t comic_score_logits_ws_bytes(int D, int V, long rows, int stream);
+float* comic_score_logits_buffer(void* ws);
+int comic_score_logits(const float* y, const float* W_o, const float* b_o, const int32_t* targets_bt, const float* wmask_bt,
+                       const int32_t* lens, const unsigned* err, int B, int T, int Tp, int D, int V, int stream,
+                       float* token_logp_tb, float* caption_logp, void* ws, int64_t ws_bytes, hipStream_t st);
 bool comic_lstm_stream_supported(int D, int E, int A, int R);
 int64_t comic_lstm_stream_kfrag_floats(int D, int Wd);
 int64_t comic_lstm_stream_xfrag_floats(int R, int Wd);
@@ -844,6 +851,8 @@ thread_local int g_greedy_path = 0;
 extern "C" int comic_decoder_greedy_path(void) { return g_greedy_path; }
 thread_local int g_beam_path = 0;
 extern "C" int comic_decoder_beam_path(void) { return g_beam_path; }
+thread_local int g_score_path = 0;
+extern "C" int comic_decoder_score_path(void) { return g_score_path; }
 
 extern "C" int64_t comic_decoder_train_workspace(const comic_decoder_desc* d, int B, int T) {
   if (!d) return -1;
@@ -888,21 +897,36 @@ extern "C" int64_t comic_decoder_train_workspace(const comic_decoder_desc* d, in
   return (int64_t)w.off;
 }
 
-extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic_decoder_params* p,
-                                        const comic_decoder_params* gr, const float* fm, const float* im_embed,
-                                        const int32_t* inputs_bt, const int32_t* targets_bt, const float* wmask_bt,
-                                        const float* coef_bt, const int32_t* lens, int B, int T, int Tp,
-                                        const float* mask_init_in, const float* mask_in, const float* mask_out,
-                                        const float* mask_alpha, float* logits_tb, int32_t* ids_tb, float* attn_hist,
-                                        float* loss_rows, float* map_loss, float* dfm, float* dim_embed,
-                                        void* workspace, int64_t workspace_bytes, void* stream) {
+// Scoring request of the teacher-forced executor (comic_decoder_score): the forward below with the masks absent, then the
+// per-token log-likelihoods (score_logits.hip) in place of the logits product, the loss and the backward.  The
+// backward-only blocks of the workspace are not taken (0 bytes); `size_out`: no launch at all, only the size of that layout.
+struct ScoreRequest {
+  float* token_logp_tb;     // [T][B]
+  float* caption_logp;      // [B]
+  int64_t* size_out;
+};
+
+static int teacher_forced_step(const comic_decoder_desc* d, const comic_decoder_params* p,
+                               const comic_decoder_params* gr, const float* fm, const float* im_embed,
+                               const int32_t* inputs_bt, const int32_t* targets_bt, const float* wmask_bt,
+                               const float* coef_bt, const int32_t* lens, int B, int T, int Tp,
+                               const float* mask_init_in, const float* mask_in, const float* mask_out,
+                               const float* mask_alpha, float* logits_tb, int32_t* ids_tb, float* attn_hist,
+                               float* loss_rows, float* map_loss, float* dfm, float* dim_embed,
+                               void* workspace, int64_t workspace_bytes, void* stream, const ScoreRequest* sc) {
   RC(check_desc(d));
   FlagScope flag_scope__(d);
-  COMIC_REQUIRE(p && gr && fm && im_embed && inputs_bt && targets_bt && wmask_bt && coef_bt && lens,
-                "train_step: null input");
-  COMIC_REQUIRE(logits_tb && ids_tb && attn_hist && loss_rows && map_loss && workspace, "train_step: null output");
+  const bool sizing = sc && sc->size_out;
+  if (!sc) {
+    COMIC_REQUIRE(p && gr && fm && im_embed && inputs_bt && targets_bt && wmask_bt && coef_bt && lens,
+                  "train_step: null input");
+    COMIC_REQUIRE(logits_tb && ids_tb && attn_hist && loss_rows && map_loss && workspace, "train_step: null output");
+  } else if (!sizing) {
+    COMIC_REQUIRE(p && fm && im_embed && inputs_bt && targets_bt && wmask_bt && lens, "score: null input");
+    COMIC_REQUIRE(sc->token_logp_tb && sc->caption_logp && workspace, "score: null output");
+  }
   COMIC_REQUIRE(B > 0 && T > 0 && Tp > 0 && Tp <= T, "train_step: bad B/T/Tp (%d %d %d)", B, T, Tp);
-  COMIC_REQUIRE(workspace_bytes >= comic_decoder_train_workspace(d, B, T), "train_step: workspace too small");
+  if (!sc) COMIC_REQUIRE(workspace_bytes >= comic_decoder_train_workspace(d, B, T), "train_step: workspace too small");
   COMIC_REQUIRE(d->keep_in >= 1.f || (mask_in && (d->init_method == 1 || mask_init_in)),
                 "train_step: input dropout enabled but no mask given");
   COMIC_REQUIRE(d->keep_out >= 1.f || mask_out, "train_step: output dropout enabled but no mask given");
@@ -911,13 +935,14 @@ extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic
   const int D = d->D, E = d->E, A = d->A, V = d->V, M = d->M, H = d->H, Cv = d->Cv, EA = E + A, Wd = E + A + D;
   const long TB = (long)T * B;
   const bool drop_in = d->keep_in < 1.f, drop_out = d->keep_out < 1.f, drop_al = d->keep_alpha < 1.f;
-  Bump w(workspace, (size_t)workspace_bytes);
+  const long bw = sc ? 0 : 1;                     // backward-only blocks: not taken when scoring
+  Bump w(sizing ? nullptr : workspace, sizing ? 0 : (size_t)workspace_bytes);
   float* keys = w.take<float>((long)B * M * D);
   float* values_buf = w.take<float>((long)B * M * D);
   InitBufs ib;
   ib.x = w.take<float>((long)B * EA); ib.xh = w.take<float>((long)B * EA);
   ib.g = w.take<float>((long)B * 4 * D); ib.gates = w.take<float>((long)B * 4 * D); ib.c_new = w.take<float>((long)B * D);
-  float* emb_all = w.take<float>(TB * E);
+  float* emb_all = w.take<float>(bw * TB * E);
   int32_t* in_tb = w.take<int32_t>(TB);
   float* xh_all = w.take<float>((TB + B) * Wd);
   float* g_tmp = w.take<float>((long)B * 4 * D);
@@ -932,48 +957,58 @@ extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic
   float* att_new = w.take<float>((long)B * D);
   float* att_all = w.take<float>((TB + B) * A);
   const int Vp = (V + 3) / 4 * 4;                 // d logits / W_o rows padded to 16 bytes: every product loads them 16 bytes at a time
-  float* dlogits = w.take<float>(TB * Vp);
-  float* wo_pad = w.take<float>((long)D * Vp);
-  float* dy_all = w.take<float>(TB * D);
-  float* dq_all = w.take<float>(TB * D);
-  float* dg_all = w.take<float>((TB + B) * 4 * D);
-  float* dxh = w.take<float>((long)B * Wd);
-  float* dc = w.take<float>((long)B * D);
-  float* dh = w.take<float>((long)B * D);
-  float* datt = w.take<float>((long)B * A);
-  float* datt_live = w.take<float>((long)B * A);
-  float* dctx = w.take<float>((long)B * Cv);
-  float* demb = w.take<float>(TB * E);
-  float* dkeys = w.take<float>((long)B * M * D);
-  float* dvalues_buf = w.take<float>((long)B * M * Cv);
-  float* pgrad = w.take<float>(TB * (3 * D + 1));   // one attention-parameter gradient row per (step, batch row)
-  float* dmap = w.take<float>(TB * M);
-  float* dx_init = w.take<float>((long)B * EA);
+  float* dlogits = w.take<float>(bw * TB * Vp);
+  float* wo_pad = w.take<float>(bw * D * Vp);
+  float* dy_all = w.take<float>(bw * TB * D);
+  float* dq_all = w.take<float>(bw * TB * D);
+  float* dg_all = w.take<float>(bw * (TB + B) * 4 * D);
+  float* dxh = w.take<float>(bw * B * Wd);
+  float* dc = w.take<float>(bw * B * D);
+  float* dh = w.take<float>(bw * B * D);
+  float* datt = w.take<float>(bw * B * A);
+  float* datt_live = w.take<float>(bw * B * A);
+  float* dctx = w.take<float>(bw * B * Cv);
+  float* demb = w.take<float>(bw * TB * E);
+  float* dkeys = w.take<float>(bw * B * M * D);
+  float* dvalues_buf = w.take<float>(bw * B * M * Cv);
+  float* pgrad = w.take<float>(bw * TB * (3 * D + 1));   // one attention-parameter gradient row per (step, batch row)
+  float* dmap = w.take<float>(bw * TB * M);
+  float* dx_init = w.take<float>(bw * B * EA);
   g_splitk_ws = w.take<char>(kSplitKBytes);
   void* splitk_ws_b = w.take<char>(kSplitKBytes);
   float* kpanel_f = w.take<float>(comic_lstm_panel_floats(D, Wd, 0));
-  float* kpanel_b = w.take<float>(comic_lstm_panel_floats(D, Wd, 1));
-  float* wq_panel = w.take<float>((long)D * D);
+  float* kpanel_b = w.take<float>(bw * comic_lstm_panel_floats(D, Wd, 1));
+  float* wq_panel = w.take<float>(bw * D * D);
   unsigned* persist_sync = w.take<unsigned>(kPersistSyncWords + kGroupTickets);
   unsigned* gg_tickets = persist_sync + kPersistSyncWords;
   const long TB16 = (long)T * ((B + 15) / 16) * 16;
   float* dq_part = w.take<float>(TB * 4 * D);
-  float* dg_blk = w.take<float>(TB16 * 4 * D);
-  float* dq_sum = w.take<float>(TB16 * D);
-  float* dstate = w.take<float>(TB * 2 * D);
-  float* pgrad4 = w.take<float>((long)4 * B * (3 * D + 1));
-  float* dotp = w.take<float>(TB * 64);
+  float* dg_blk = w.take<float>(bw * TB16 * 4 * D);
+  float* dq_sum = w.take<float>(bw * TB16 * D);
+  float* dstate = w.take<float>(bw * TB * 2 * D);
+  float* pgrad4 = w.take<float>(bw * 4 * B * (3 * D + 1));
+  float* dotp = w.take<float>(bw * TB * 64);
   float* statp = comic_persist_fwd_bigm(M, d->fm_projection == 2) ? w.take<float>(TB * 8 * M) : nullptr;
   const int cell = d->cell;
   float *lnx_all = nullptr, *lnr_all = nullptr, *lnpg = nullptr, *cell_tmp = nullptr, *xh2_all = nullptr, *gru_dxh = nullptr;
   if (cell == COMIC_CELL_LN_LSTM) {
     lnx_all = w.take<float>((TB + B) * 5 * D); lnr_all = w.take<float>((TB + B) * 8);
-    lnpg = w.take<float>((TB + B) * 10 * D); cell_tmp = w.take<float>(10L * D);
+    lnpg = w.take<float>(bw * (TB + B) * 10 * D); cell_tmp = w.take<float>(10L * D);
     ib.lnx = lnx_all + TB * 5 * D; ib.lnr = lnr_all + TB * 8;      // the init step's rows sit behind the time steps'
   } else if (cell == COMIC_CELL_GRU) {
-    xh2_all = w.take<float>(TB * Wd); gru_dxh = w.take<float>(2L * B * Wd); cell_tmp = w.take<float>(4L * D);
+    xh2_all = w.take<float>(TB * Wd); gru_dxh = w.take<float>(bw * 2 * B * Wd); cell_tmp = w.take<float>(4L * D);
   }
-  COMIC_REQUIRE(w.ok, "train_step: workspace overflow");
+  // scoring: the alignment history when the caller takes none, and the projection's scratch (no [T'][B][V] block on the
+  // streaming path: packed W_o and per-chunk partials)
+  const bool score_stream = sc && beam_logits_enabled() && comic_score_stream_supported(D, V);
+  const int64_t score_ws_bytes = sc ? comic_score_logits_ws_bytes(D, V, TB, score_stream) : 0;
+  if (sc && !attn_hist) attn_hist = w.take<float>(TB * H * M);
+  void* score_ws = w.take<char>((size_t)score_ws_bytes);
+  if (sizing) {
+    *sc->size_out = (int64_t)w.off;
+    return 0;
+  }
+  COMIC_REQUIRE(w.ok, sc ? "score: workspace too small" : "train_step: workspace overflow");
   RC(check_cell_params(d, p));
   // COMIC_DEC_PHASE_FWD / _BWD: the step in two calls over the same workspace -- everything up to the logits (no loss
   // coefficient enters it), then loss + backward.  The SCST step runs the first under the host's reward computation.
@@ -988,9 +1023,10 @@ extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic
   const bool persist = fused && persist_enabled() &&
                        comic_persist_fwd_supported(B, D, E, A, M, H, Cv, d->method, d->context_layer, ad.tied) &&
                        comic_persist_fits_device(B);
-  const bool persist_b = persist && persist_bwd_enabled() &&
+  const bool persist_b = !sc && persist && persist_bwd_enabled() &&
                          comic_persist_bwd_supported(B, D, E, A, M, H, Cv, d->method, d->prob, d->context_layer, ad.tied);
-  g_train_path = (persist ? 1 : 0) | (persist_b ? 2 : 0);
+  if (sc) g_score_path = (persist ? 1 : 0) | (score_stream ? 2 : 0);
+  else g_train_path = (persist ? 1 : 0) | (persist_b ? 2 : 0);
   // scratch of the split attention kernels (large memories: comic_attn_splits workgroups per batch row): the d q
   // partials of the persistent backward loop, free whenever the per-step kernels run ([Tp][B][4][D] >= 2 x [B][H][M])
   float* attn_ws = (!persist_b && comic_attn_splits(B, M) > 1 &&
@@ -1017,7 +1053,7 @@ extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic
     prologue_rides = group_gemm_enabled() && cell == COMIC_CELL_LSTM && fused;
     if (prologue_rides) {
       px.K = p->K; px.panel = kpanel_f; px.D = D; px.Wd = Wd; px.n_pack = comic_lstm_panel_floats(D, Wd, 0);
-      if (Vp != V) { px.W_o = p->W_o; px.wo_pad = wo_pad; px.V = V; px.Vp = Vp; px.n_pad = (long)D * Vp; }
+      if (Vp != V && !sc) { px.W_o = p->W_o; px.wo_pad = wo_pad; px.V = V; px.Vp = Vp; px.n_pad = (long)D * Vp; }
     }
     RC(comic_persist_prepare(pr, persist_sync, kPersistSyncWords + kGroupTickets, st, prologue_rides ? &px : nullptr));
   }
@@ -1038,9 +1074,9 @@ extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic
   if (do_fwd) {
   if (grp) {
     if (!persist) COMIC_REQUIRE(hipMemsetAsync(gg_tickets, 0, sizeof(unsigned) * kGroupTickets, st) == hipSuccess, "train_step: memset");
-    if (fused && !(prologue_rides && persist_b)) RC(comic_pack_lstm_panels(p->K, prologue_rides ? nullptr : kpanel_f, persist_b ? nullptr : kpanel_b, D, Wd, st));
-    if (fused_q && !persist_b) RC(comic_pack_wq_panel(p->W_q, wq_panel, D, st));
-    if (Vp != V && !prologue_rides) {
+    if (fused && !(prologue_rides && (persist_b || sc))) RC(comic_pack_lstm_panels(p->K, prologue_rides ? nullptr : kpanel_f, (persist_b || sc) ? nullptr : kpanel_b, D, Wd, st));
+    if (fused_q && !persist_b && !sc) RC(comic_pack_wq_panel(p->W_q, wq_panel, D, st));
+    if (Vp != V && !prologue_rides && !sc) {
       const long n = (long)D * Vp;
       hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, p->W_o, wo_pad, V, Vp, n);
       COMIC_LAUNCH_CHECK("pad W_o");
@@ -1069,8 +1105,8 @@ extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic
     hipStream_t sl = lane.lane();
     // weight panels of the fused step kernels (the persistent backward reads K and W_q in place): needed by the time
     // loop only, so they are packed on the side lane too
-    if (fused) RC(comic_pack_lstm_panels(p->K, kpanel_f, persist_b ? nullptr : kpanel_b, D, Wd, sl));
-    if (fused_q && !persist_b) RC(comic_pack_wq_panel(p->W_q, wq_panel, D, sl));
+    if (fused) RC(comic_pack_lstm_panels(p->K, kpanel_f, (persist_b || sc) ? nullptr : kpanel_b, D, Wd, sl));
+    if (fused_q && !persist_b && !sc) RC(comic_pack_wq_panel(p->W_q, wq_panel, D, sl));
     RC(rnn_init_fwd(d, p, im_embed, B, drop_in ? mask_init_in : nullptr, ib, cs, hs, sl));
     lane.main_ws();
     RC(memory_projections(d, p, fm, B, keys, values_buf, &values, st));
@@ -1162,6 +1198,14 @@ extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic
                          att_next, xh_n ? xh_n + E : nullptr, Wd, mask_n, EA, d->keep_in, B, A);
       COMIC_LAUNCH_CHECK("select_att");
     }
+  }
+  if (sc) {      // per-token log-likelihoods instead of logits / loss / backward; a timed-out loop turns them into NaN
+    if (!score_stream)
+      RC(gemm_big(y_all, p->W_o, comic_score_logits_buffer(score_ws), p->b_o, Tp * B, V, D, D, V, V, 0, 0, 0.f, st));
+    RC(comic_score_logits(y_all, p->W_o, p->b_o, targets_bt, wmask_bt, lens, persist ? persist_sync : nullptr, B, T, Tp, D, V,
+                          score_stream ? 1 : 0, sc->token_logp_tb, sc->caption_logp, score_ws, score_ws_bytes, st));
+    COMIC_LAUNCH_CHECK("score");
+    return 0;
   }
   // output projection for all executed steps, loss, d logits
   if (grp) {
@@ -1485,6 +1529,52 @@ extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic
   }
   COMIC_LAUNCH_CHECK("train_step");
   return 0;
+}
+
+extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic_decoder_params* p,
+                                        const comic_decoder_params* gr, const float* fm, const float* im_embed,
+                                        const int32_t* inputs_bt, const int32_t* targets_bt, const float* wmask_bt,
+                                        const float* coef_bt, const int32_t* lens, int B, int T, int Tp,
+                                        const float* mask_init_in, const float* mask_in, const float* mask_out,
+                                        const float* mask_alpha, float* logits_tb, int32_t* ids_tb, float* attn_hist,
+                                        float* loss_rows, float* map_loss, float* dfm, float* dim_embed,
+                                        void* workspace, int64_t workspace_bytes, void* stream) {
+  return teacher_forced_step(d, p, gr, fm, im_embed, inputs_bt, targets_bt, wmask_bt, coef_bt, lens, B, T, Tp, mask_init_in,
+                             mask_in, mask_out, mask_alpha, logits_tb, ids_tb, attn_hist, loss_rows, map_loss, dfm, dim_embed,
+                             workspace, workspace_bytes, stream, nullptr);
+}
+
+// Scoring: dropout off, both phases' flags and the fault injection of the training step cleared
+static comic_decoder_desc score_desc(const comic_decoder_desc* d) {
+  comic_decoder_desc s = *d;
+  s.keep_in = s.keep_out = s.keep_alpha = 1.f;
+  s.flags &= ~(uint32_t)(COMIC_DEC_PHASE_FWD | COMIC_DEC_PHASE_BWD | COMIC_DEC_INJECT_TIMEOUT);
+  return s;
+}
+
+extern "C" int64_t comic_decoder_score_workspace(const comic_decoder_desc* d, int B, int T) {
+  if (!d || B <= 0 || T <= 0) return -1;
+  const comic_decoder_desc s = score_desc(d);
+  int64_t n = 0;
+  ScoreRequest sc{nullptr, nullptr, &n};
+  if (teacher_forced_step(&s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, T, nullptr,
+                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                          nullptr, &sc))
+    return -1;
+  return n;
+}
+
+extern "C" int comic_decoder_score(const comic_decoder_desc* d, const comic_decoder_params* p, const float* fm,
+                                   const float* im_embed, const int32_t* inputs_bt, const int32_t* targets_bt,
+                                   const float* wmask_bt, const int32_t* lens, int B, int T, int Tp, float* token_logp_tb,
+                                   float* caption_logp, float* attn_hist, void* workspace, int64_t workspace_bytes,
+                                   void* stream) {
+  COMIC_REQUIRE(d, "score: null descriptor");
+  const comic_decoder_desc s = score_desc(d);
+  ScoreRequest sc{token_logp_tb, caption_logp, nullptr};
+  return teacher_forced_step(&s, p, nullptr, fm, im_embed, inputs_bt, targets_bt, wmask_bt, nullptr, lens, B, T, Tp, nullptr,
+                             nullptr, nullptr, nullptr, nullptr, nullptr, attn_hist, nullptr, nullptr, nullptr, nullptr, workspace,
+                             workspace_bytes, stream, &sc);
 }
 
 // columns of the W_o scratch: V rounded up to whole chunks of any of its packed forms (128, 112 or 64 columns)

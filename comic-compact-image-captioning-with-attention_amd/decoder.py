@@ -551,6 +551,98 @@ class Decoder:
         else:
             self._train_device(ctx, phase)
 
+    # ------------------------------------------------------------------ scoring --------
+    def _score_ctx(self, B, T, Tp, want_attention):
+        """Persistent device buffers (+ hipGraph) of one scoring shape: a context and staging slots of their own, so a
+        scoring call between two training steps of the same shape disturbs neither."""
+        key = (B, T, Tp, bool(want_attention))
+        ctxs = self.__dict__.setdefault('_score_ctxs', {})
+        ctx = ctxs.get(key)
+        if ctx is not None:
+            return ctx
+        torch, s, dev = self.torch, self.spec, self.device
+        from types import SimpleNamespace
+        ctx = SimpleNamespace(key=key, calls=0, graph=None)
+        f32 = dict(dtype=torch.float32, device=dev)
+        # ONE staging block per call: [inputs, targets int32 [B,T] | lens int32 [B] (+ pad) | wmask fp32 [B,T]]
+        n_i32 = 2 * B * T + B
+        o_f32 = 4 * ((n_i32 + 1) // 2 * 2)
+        nbytes = o_f32 + 4 * B * T
+
+        def views(buf):
+            return buf[:4 * n_i32].view(torch.int32), buf[o_f32:].view(torch.float32)
+        ctx.stage_dev = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        ctx.i32, ctx.f32 = views(ctx.stage_dev)
+        ctx.stage = []
+        for _ in range(2):      # pinned, used alternately (see _train_ctx)
+            buf = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+            i32, f32v = views(buf)
+            ctx.stage.append(SimpleNamespace(buf=buf, i32=i32, f32=f32v, copied=None))
+        ctx.fm = torch.empty((B, s.M, s.C), **f32)
+        ctx.im = torch.empty((B, s.Cg), **f32)
+        ctx.token_logp = torch.zeros((T, B), **f32)
+        ctx.logp = torch.zeros(B, **f32)
+        ctx.hist = torch.empty((Tp, B, s.H, s.M), **f32) if want_attention else None
+        ctx.desc = s.desc(False)
+        ctx.nbytes = self.lib.comic_decoder_score_workspace(C.byref(ctx.desc), B, T)
+        assert ctx.nbytes > 0, 'comic_decoder_score_workspace failed'
+        ctx.ws = torch.empty(int(ctx.nbytes), dtype=torch.uint8, device=dev)
+        ctxs[key] = ctx
+        return ctx
+
+    def _score_device(self, ctx):
+        """Device-only part of a scoring call (no host sync, no host memcpy): capturable."""
+        B, T, Tp, _ = ctx.key
+        BT = B * T
+        ptab = self.params.table()
+        ctx.desc.flags = L.decoder_flags_from_env()
+        L.check(self.lib.comic_decoder_score(
+            C.byref(ctx.desc), C.byref(ptab), ctx.fm.data_ptr(), ctx.im.data_ptr(), ctx.i32.data_ptr(),
+            ctx.i32.data_ptr() + 4 * BT, ctx.f32.data_ptr(), ctx.i32.data_ptr() + 8 * BT, B, T, Tp,
+            ctx.token_logp.data_ptr(), ctx.logp.data_ptr(), L.ptr(ctx.hist), ctx.ws.data_ptr(), ctx.nbytes,
+            L.stream_ptr()), 'decoder_score')
+
+    def score(self, fm, im_embed, captions, want_attention=False, use_graph=False):
+        """Teacher-forced log-likelihoods of given captions, forward only (comic_decoder_score): no dropout, no gradient,
+        no logits tensor at a large vocabulary.  `captions` [B,L] int (PAD = -1), processed as in train_step.
+        use_graph: replay from a hipGraph captured per (B, T, T') shape (the second call with a shape captures it).
+        Returns dict(token_log_probs [B,T] (0 at padding), log_prob [B] (their float32 sum in t order), lengths [B],
+        attn_maps [B,H,T',M] or None): device views of persistent buffers, valid until the next call with the shape."""
+        torch, s = self.torch, self.spec
+        inputs, targets, wmask, lens = process_inputs(captions, s.token_type)
+        B, T = inputs.shape
+        Tp = int(lens.max())
+        assert Tp > 0, 'score: every caption is empty'
+        ctx = self._score_ctx(B, T, Tp, want_attention)
+        BT = B * T
+        slot = ctx.stage[ctx.calls % 2]
+        if slot.copied is not None:
+            slot.copied.synchronize()
+        ih, fh = slot.i32.numpy(), slot.f32.numpy()
+        ih[:BT] = inputs.reshape(-1); ih[BT:2 * BT] = targets.reshape(-1); ih[2 * BT:] = lens
+        fh[:BT] = wmask.reshape(-1)
+        ctx.stage_dev.copy_(slot.buf, non_blocking=True)
+        if slot.copied is None:
+            slot.copied = torch.cuda.Event()
+        slot.copied.record(torch.cuda.current_stream())
+        assert fm.shape == (B, s.M, s.C) and im_embed.shape == (B, s.Cg), (fm.shape, im_embed.shape)
+        assert fm.dtype == torch.float32 and im_embed.dtype == torch.float32
+        ctx.fm.copy_(fm)
+        ctx.im.copy_(im_embed)
+        if use_graph and ctx.graph is None and ctx.calls >= 1:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode='thread_local'):
+                self._score_device(ctx)
+            ctx.graph = g
+        if use_graph and ctx.graph is not None:
+            ctx.graph.replay()
+        else:
+            self._score_device(ctx)
+        ctx.calls += 1
+        ctx.wmask = ctx.f32[:BT]
+        return dict(token_log_probs=ctx.token_logp.t(), log_prob=ctx.logp, lengths=torch.from_numpy(lens.copy()),
+                    attn_maps=ctx.hist.permute(1, 2, 0, 3) if ctx.hist is not None else None, Tp=Tp, wmask=ctx.wmask)
+
     # ------------------------------------------------------------------ decoding -------
     def max_iterations(self, infer_max_length, vocab_len):
         """model_base.py:708-714."""

@@ -490,11 +490,23 @@ class CaptionModel(ModelBase):
         self.last = res
         return res['loss']
 
-    def run_eval_step(self, batch=None):
+    def score_captions(self, images, captions):
+        """log p(caption | image) of given captions: encoder forward, then Decoder.score (forward only, no logits tensor at
+        a large vocabulary).  `captions` [B,L] token ids as the input pipeline delivers them (PAD = -1).
+        -> dict(token_log_probs [B,T], log_prob [B], lengths [B], attn_maps None) (see Decoder.score)."""
+        im_embed, fm = self._encode(images)
+        return self.decoder.score(fm, im_embed, np.asarray(captions))
+
+    def run_eval_step(self, batch=None, forward_only=False):
         """== sess.run(m_valid.dec_log_ppl) (train_fn.py:328-330): loss only, dropout off.
-        The fused step also produces gradients; they are simply not applied."""
+        The fused step also produces gradients; they are simply not applied.
+        forward_only: the same number, -sum(token log-probs) / (sum(mask) + 1e-12) (model_base.py:337-341), from the scoring
+        path (Decoder.score: no backward, no weight gradients, no logits tensor), reduced on the device."""
         images, captions = batch if batch is not None else next(self.batch_ops)
         im_embed, fm = self._encode(images)
+        if forward_only:
+            res = self.decoder.score(fm, im_embed, np.asarray(captions), use_graph=True)
+            return -res['log_prob'].sum() / (res['wmask'].sum() + 1e-12)
         res = self.decoder.train_step(fm, im_embed, np.asarray(captions), training=False, use_graph=True)
         return res['loss']
 

@@ -624,6 +624,31 @@ int comic_decoder_greedy_path(void);
  * comic_beam_step's kernel + the all-finished launch. */
 int comic_decoder_beam_path(void);
 
+/* Caption scoring: log p(caption | image) of given captions, forward only -- the teacher-forced half of
+ * rnn_decoder_training (common/ops_rnn.py:183-243) and the per-token terms of the sequence loss (_train_caption_model,
+ * src/model_base.py:325-347: sparse softmax cross-entropy times the caption mask) WITHOUT their reduction to one number.
+ * The forward (memory projections, rnn init, time loop) is the code of comic_decoder_train_step with the dropout masks
+ * absent; no gradient table is taken, nothing is filled for a backward, and the workspace holds none of the backward's
+ * blocks (comic_decoder_score_workspace < comic_decoder_train_workspace).  Same cells, alignment methods, probability
+ * functions, projection modes and COMIC_DEC_* switches as the training step (the keeps and the phase / fault-injection
+ * flags of the descriptor are ignored).
+ *   inputs as comic_decoder_train_step: fm [B,M,C], im_embed [B,Cg], inputs_bt / targets_bt [B,T] int32, wmask_bt [B,T],
+ *   lens [B] int32 (device), Tp = max(lens) (host).
+ * Outputs: token_logp_tb [T,B] = wmask * (logit[target] - logsumexp(y W_o + b_o)), exactly 0 where wmask == 0 or
+ *   t >= lens[b]; caption_logp [B] = the float32 sum of a caption's tokens in t order; attn_hist [Tp,B,H,M] or NULL.
+ * Deterministic: partial results are combined in a fixed order, no atomics.  If a bounded wait of the persistent forward
+ * loop expires, every output is NaN. */
+int64_t comic_decoder_score_workspace(const comic_decoder_desc* d, int B, int T);
+int comic_decoder_score(const comic_decoder_desc* d, const comic_decoder_params* p, const float* fm, const float* im_embed,
+                        const int32_t* inputs_bt, const int32_t* targets_bt, const float* wmask_bt, const int32_t* lens,
+                        int B, int T, int Tp, float* token_logp_tb /*[T,B]*/, float* caption_logp /*[B]*/,
+                        float* attn_hist /*[Tp,B,H,M] or NULL*/, void* workspace, int64_t workspace_bytes, void* stream);
+/* Paths of the LAST comic_decoder_score of this thread, a bit mask: bit 0 = forward loop as one persistent launch
+ * (csrc/decoder_persist.hip, the conditions of comic_decoder_train_path bit 0); bit 1 = streaming projection over the
+ * packed W_o (csrc/score_logits.hip: D % 128 == 0, V >= 4096, COMIC_DEC_NO_BEAM_LOGITS clear) -- no logits in memory --
+ * instead of the GEMM into workspace + one wave per row. */
+int comic_decoder_score_path(void);   /* bit 0: forward loop persistent; bit 1: streaming projection (no logits in memory) */
+
 /* Greedy decode (rnn_decoder_search, ops_rnn.py:115-180): runs `max_steps` steps on the
  * device without host sync; ids [max_steps,B], attn [max_steps,B,H,M]; finished-at step per
  * row in first_eos [B] (max_steps when no EOS).  The host trims to the executed length. */
