@@ -845,8 +845,6 @@ int infer_step_fused(const comic_decoder_desc* d, const comic_decoder_params* p,
 
 thread_local int g_train_path = 0;
 extern "C" int comic_decoder_train_path(void) { return g_train_path; }
-// fault injection for the tests of the end-of-step gate: the next comic_decoder_train_step that runs a persistent loop
-// behaves as if one of its bounded waits had expired (one shot)
 thread_local int g_greedy_path = 0;
 extern "C" int comic_decoder_greedy_path(void) { return g_greedy_path; }
 thread_local int g_beam_path = 0;
@@ -854,662 +852,688 @@ extern "C" int comic_decoder_beam_path(void) { return g_beam_path; }
 thread_local int g_score_path = 0;
 extern "C" int comic_decoder_score_path(void) { return g_score_path; }
 
-extern "C" int64_t comic_decoder_train_workspace(const comic_decoder_desc* d, int B, int T) {
-  if (!d) return -1;
-  Bump w(nullptr, 0);
-  const long D = d->D, E = d->E, A = d->A, V = d->V, M = d->M, H = d->H, Cv = d->Cv, Wd = E + A + D;
-  const long TB = (long)T * B;
-  w.take<float>(B * M * D); w.take<float>(B * M * D);              // keys, values
-  w.take<float>(B * (E + A)); w.take<float>(B * (E + A));          // init x, xh
-  w.take<float>(B * 4 * D); w.take<float>(B * 4 * D); w.take<float>(B * D);  // init g, gates, c_new
-  w.take<float>(TB * E); w.take<int32_t>(TB);                      // emb_all, ids_tb
-  w.take<float>((TB + B) * Wd); w.take<float>(B * 4 * D);          // xh_all (+ the init step's operand rows), g_tmp
-  w.take<float>(TB * 4 * D);                                       // gates_act
-  w.take<float>((TB + B) * D); w.take<float>((TB + B) * D);        // cs, hs
-  w.take<float>(TB * D); w.take<float>(TB * D); w.take<float>(TB * D);  // c_new, y, q
-  w.take<float>(TB * H * M);                                       // alpha
-  w.take<float>(TB * Cv); w.take<float>(B * D); w.take<float>((TB + B) * A);  // ctx, att_new, att
-  w.take<float>(TB * ((V + 3) / 4 * 4));                           // dlogits (rows padded to a multiple of 4 columns)
-  w.take<float>(D * ((V + 3) / 4 * 4));                            // W_o with padded rows (grouped GEMM launches)
-  w.take<float>(TB * D); w.take<float>(TB * D); w.take<float>((TB + B) * 4 * D);    // dy_all, dq_all, dg_all (+ the init step's rows)
-  w.take<float>(B * Wd); w.take<float>(B * D); w.take<float>(B * D);          // dxh, dc, dh
-  w.take<float>(B * A); w.take<float>(B * A); w.take<float>(B * Cv);          // datt, datt_live, dctx
-  w.take<float>(TB * E); w.take<float>(B * M * D); w.take<float>(B * M * Cv); // demb, dkeys, dvalues
-  w.take<float>(TB * (3 * D + 1)); w.take<float>(TB * M);                      // pgrad rows, dmap
-  w.take<float>(B * (E + A));                                                  // dx_init
-  w.take<char>(kSplitKBytes);                                                  // split-K partials
-  w.take<char>(kSplitKBytes);                                                  // ... of the second gradient lane
-  w.take<float>(comic_lstm_panel_floats((int)D, (int)Wd, 0));                  // LSTM kernel panels (fused step)
-  w.take<float>(comic_lstm_panel_floats((int)D, (int)Wd, 1));
-  w.take<float>(D * D);                                                        // W_q panel
-  w.take<unsigned>(kPersistSyncWords + kGroupTickets);                         // persistent loops: error word; grouped GEMM: tile tickets
-  w.take<float>(TB * 4 * D); w.take<float>((long)T * ((B + 15) / 16) * 16 * 4 * D);  // persistent backward: d q partials, d gates (blocked)
-  w.take<float>((long)T * ((B + 15) / 16) * 16 * D);                                  // summed d q (blocked)
-  w.take<float>(TB * 2 * D);                                                   // d att | d h
-  w.take<float>(4 * B * (3 * D + 1));                                          // its parameter-gradient rows
-  w.take<float>(TB * 64);                                                      // ... per-head dot products of the row quarters (M > 28)
-  if (comic_persist_fwd_bigm((int)M, d->fm_projection == 2)) w.take<float>(TB * 8 * M);   // forward loop, channel-quarter form: LayerNorm sums of the quarters
-  if (d->cell == COMIC_CELL_LN_LSTM) {           // normalised rows, 1/std and LayerNorm gradient rows of every step + the init step
-    w.take<float>((TB + B) * 5 * D); w.take<float>((TB + B) * 8); w.take<float>((TB + B) * 10 * D); w.take<float>(10 * D);
-  } else if (d->cell == COMIC_CELL_GRU) {        // [x ; att ; r*h] of every step, the two d-operand products of a step, bias sums
-    w.take<float>(TB * Wd); w.take<float>(2 * B * Wd); w.take<float>(4 * D);
-  }
-  return (int64_t)w.off;
-}
+namespace {
 
-// Scoring request of the teacher-forced executor (comic_decoder_score): the forward below with the masks absent, then the
-// per-token log-likelihoods (score_logits.hip) in place of the logits product, the loss and the backward.  The
-// backward-only blocks of the workspace are not taken (0 bytes); `size_out`: no launch at all, only the size of that layout.
-struct ScoreRequest {
-  float* token_logp_tb;     // [T][B]
-  float* caption_logp;      // [B]
-  int64_t* size_out;
+// ---- workspace of the teacher-forced step (training and scoring) ---------------------------------------------------------
+// TrainLayout::carve is the ONE definition of the blocks, their order and their sizes: comic_decoder_train_workspace and
+// comic_decoder_score_workspace run it over a null base, the step over the caller's buffer.  What a launch assumes about
+// where blocks sit relative to each other is an accessor below: the step does no pointer arithmetic across blocks itself.
+enum TfMode { TF_TRAIN, TF_SCORE };           // TF_SCORE: the backward-only blocks (x bw) are not taken (0 bytes)
+struct TrainLayout {
+  long B = 0, TB = 0, D = 0, A = 0, M = 0, H = 0, Wd = 0;
+  size_t bytes = 0;           // what carve took; ok: it fitted the caller's buffer
+  bool ok = false;
+  InitBufs ib;
+  int32_t* in_tb;
+  float *keys, *values_buf;
+  float *emb_all, *xh_all, *g_tmp, *gates_all, *cs, *hs, *cnew_all, *y_all, *q_all, *alpha_all, *ctx_all, *att_new, *att_all;
+  float *dlogits, *wo_pad, *dy_all, *dq_all, *dg_all, *dxh, *dc, *dh, *datt, *datt_live, *dctx, *demb, *dkeys, *dvalues_buf;
+  float *pgrad, *dmap, *dx_init, *kpanel_f, *kpanel_b, *wq_panel, *dq_part, *dg_blk, *dq_sum, *dstate, *pgrad4, *dotp, *statp;
+  float *lnx_all = nullptr, *lnr_all = nullptr, *lnpg = nullptr, *cell_tmp = nullptr, *xh2_all = nullptr, *gru_dxh = nullptr;
+  void *splitk_a, *splitk_b;                  // split-K partials of the main stream / of the second gradient lane
+  unsigned* persist_sync;
+  // scoring (latched flags: FlagScope): the alignment history when the caller takes none, and the projection's scratch (no
+  // [T'][B][V] block on the streaming path: packed W_o and per-chunk partials)
+  bool score_stream = false;
+  float* attn_hist_own = nullptr;
+  void* score_ws;
+  int64_t score_ws_bytes = 0;
+
+  void carve(const comic_decoder_desc* d, int B_, int T, TfMode mode, bool own_attn_hist, void* base, size_t cap) {
+    Bump w(base, cap);
+    B = B_; D = d->D; A = d->A; M = d->M; H = d->H; Wd = d->E + d->A + d->D; TB = (long)T * B;
+    const long E = d->E, V = d->V, Cv = d->Cv, EA = E + A;
+    const long bw = mode == TF_SCORE ? 0 : 1;
+    keys = w.take<float>(B * M * D); values_buf = w.take<float>(B * M * D);
+    ib.x = w.take<float>(B * EA); ib.xh = w.take<float>(B * EA);
+    ib.g = w.take<float>(B * 4 * D); ib.gates = w.take<float>(B * 4 * D); ib.c_new = w.take<float>(B * D);
+    emb_all = w.take<float>(bw * TB * E); in_tb = w.take<int32_t>(TB);
+    xh_all = w.take<float>((TB + B) * Wd);                  // (+ the init step's operand rows: xh_init)
+    g_tmp = w.take<float>(B * 4 * D); gates_all = w.take<float>(TB * 4 * D);
+    cs = w.take<float>((TB + B) * D); hs = w.take<float>((TB + B) * D);
+    cnew_all = w.take<float>(TB * D); y_all = w.take<float>(TB * D); q_all = w.take<float>(TB * D);
+    alpha_all = w.take<float>(TB * H * M); ctx_all = w.take<float>(TB * Cv);
+    att_new = w.take<float>(B * D); att_all = w.take<float>((TB + B) * A);
+    const long Vp = (V + 3) / 4 * 4;                        // d logits / W_o rows padded to 16 bytes: every product loads them 16 bytes at a time
+    dlogits = w.take<float>(bw * TB * Vp); wo_pad = w.take<float>(bw * D * Vp);
+    dy_all = w.take<float>(bw * TB * D); dq_all = w.take<float>(bw * TB * D);
+    dg_all = w.take<float>(bw * (TB + B) * 4 * D);          // (+ the init step's rows: dg_init)
+    dxh = w.take<float>(bw * B * Wd);
+    dc = w.take<float>(bw * B * D); dh = w.take<float>(bw * B * D); datt = w.take<float>(bw * B * A);   // consecutive: state_grads()
+    datt_live = w.take<float>(bw * B * A); dctx = w.take<float>(bw * B * Cv); demb = w.take<float>(bw * TB * E);
+    dkeys = w.take<float>(bw * B * M * D); dvalues_buf = w.take<float>(bw * B * M * Cv);
+    pgrad = w.take<float>(bw * TB * (3 * D + 1));           // one attention-parameter gradient row per (step, batch row)
+    dmap = w.take<float>(bw * TB * M); dx_init = w.take<float>(bw * B * EA);
+    splitk_a = w.take<char>(kSplitKBytes); splitk_b = w.take<char>(kSplitKBytes);       // consecutive: gg_slab()
+    kpanel_f = w.take<float>(comic_lstm_panel_floats((int)D, (int)Wd, 0));          // LSTM kernel panels (fused step)
+    kpanel_b = w.take<float>(bw * comic_lstm_panel_floats((int)D, (int)Wd, 1)); wq_panel = w.take<float>(bw * D * D);
+    persist_sync = w.take<unsigned>(kPersistSyncWords + kGroupTickets);     // persistent loops' sync words | gg_tickets()
+    const long TB16 = (long)T * ((B + 15) / 16) * 16;
+    dq_part = w.take<float>(TB * 4 * D);                    // persistent backward: d q partials; per-step kernels: attn_scratch()
+    dg_blk = w.take<float>(bw * TB16 * 4 * D); dq_sum = w.take<float>(bw * TB16 * D);      // ... d gates, summed d q (blocked)
+    dstate = w.take<float>(bw * TB * 2 * D);                // ... d att | d h
+    pgrad4 = w.take<float>(bw * 4 * B * (3 * D + 1));       // ... its parameter-gradient rows
+    dotp = w.take<float>(bw * TB * 64);                     // ... per-head dot products of the row quarters (M > 28)
+    // forward loop, channel-quarter form: LayerNorm sums of the quarters
+    statp = comic_persist_fwd_bigm((int)M, d->fm_projection == 2) ? w.take<float>(TB * 8 * M) : nullptr;
+    if (d->cell == COMIC_CELL_LN_LSTM) {      // normalised rows, 1/std and LayerNorm gradient rows of every step + the init step
+      lnx_all = w.take<float>((TB + B) * 5 * D); lnr_all = w.take<float>((TB + B) * 8);
+      lnpg = w.take<float>(bw * (TB + B) * 10 * D); cell_tmp = w.take<float>(10 * D);
+      ib.lnx = lnx_all + TB * 5 * D; ib.lnr = lnr_all + TB * 8;      // the init step's rows sit behind the time steps'
+    } else if (d->cell == COMIC_CELL_GRU) {   // [x ; att ; r*h] of every step, the two d-operand products of a step, bias sums
+      xh2_all = w.take<float>(TB * Wd); gru_dxh = w.take<float>(bw * 2 * B * Wd); cell_tmp = w.take<float>(4 * D);
+    }
+    score_stream = mode == TF_SCORE && beam_logits_enabled() && comic_score_stream_supported((int)D, (int)V);
+    score_ws_bytes = mode == TF_SCORE ? comic_score_logits_ws_bytes((int)D, (int)V, TB, score_stream) : 0;
+    if (mode == TF_SCORE && own_attn_hist) attn_hist_own = w.take<float>(TB * H * M);
+    score_ws = w.take<char>((size_t)score_ws_bytes);
+    bytes = w.off; ok = w.ok;
+  }
+
+  // row block Tp of xh_all / dg_all: the rnn init step's operand rows [drop(x_init) ; 0] and its d gates (grouped path)
+  float* xh_init(int Tp) const { return xh_all + Tp * B * Wd; }
+  float* dg_init(int Tp) const { return dg_all + Tp * B * 4 * D; }
+  // dc | dh | datt are zeroed by ONE fill: consecutive blocks (the span includes their alignment padding)
+  float* state_grads() const { return dc; }
+  long state_grads_floats() const { return (long)((datt + B * A) - dc); }
+  // scratch slab of the grouped launches: both lanes' split-K blocks, consecutive
+  void* gg_slab() const { return splitk_a; }
+  int64_t gg_slab_cap() const { return 2 * kSplitKBytes; }
+  // tile tickets of the grouped launches: kGroupTickets words behind the persistent loops' sync words, zeroed with them by
+  // comic_persist_prepare (sync_words() words) and left zero by every launch; the last one is the loss launch's
+  int sync_words() const { return kPersistSyncWords + kGroupTickets; }
+  unsigned* gg_tickets() const { return persist_sync + kPersistSyncWords; }
+  unsigned* loss_ticket() const { return gg_tickets() + kGroupTickets - 1; }
+  // scratch of the split attention kernels (large memories: comic_attn_splits workgroups per batch row; 2 x [B][H][M] +
+  // comic_attn_bwd_scratch): the d q partials of the persistent backward loop, free whenever the per-step kernels run
+  float* attn_scratch(bool persist_b) const {
+    return (!persist_b && comic_attn_splits((int)B, (int)M) > 1 &&
+            TB * 4 * D >= B * H * M + comic_attn_bwd_scratch((int)B, (int)H, (int)M, (int)D)) ? dq_part : nullptr;
+  }
+  float* attn_scratch_bwd(float* scratch) const { return scratch ? scratch + B * H * M : nullptr; }
+  // partial sums of the map loss: dxh [B][Wd], free until the backward loop (the step checks that they fit)
+  float* maploss_partials() const { return dxh; }
+  long maploss_partials_cap() const { return B * Wd; }
+  // column-summed [v | ln_g | ln_b | tau] row (lane form): g_tmp [B][4D], free after the loops, >= 3D + 1 floats at any B
+  float* pgrad_sum() const { return g_tmp; }
 };
 
-static int teacher_forced_step(const comic_decoder_desc* d, const comic_decoder_params* p,
-                               const comic_decoder_params* gr, const float* fm, const float* im_embed,
-                               const int32_t* inputs_bt, const int32_t* targets_bt, const float* wmask_bt,
-                               const float* coef_bt, const int32_t* lens, int B, int T, int Tp,
-                               const float* mask_init_in, const float* mask_in, const float* mask_out,
-                               const float* mask_alpha, float* logits_tb, int32_t* ids_tb, float* attn_hist,
-                               float* loss_rows, float* map_loss, float* dfm, float* dim_embed,
-                               void* workspace, int64_t workspace_bytes, void* stream, const ScoreRequest* sc) {
-  RC(check_desc(d));
-  FlagScope flag_scope__(d);
-  const bool sizing = sc && sc->size_out;
-  if (!sc) {
-    COMIC_REQUIRE(p && gr && fm && im_embed && inputs_bt && targets_bt && wmask_bt && coef_bt && lens,
-                  "train_step: null input");
-    COMIC_REQUIRE(logits_tb && ids_tb && attn_hist && loss_rows && map_loss && workspace, "train_step: null output");
-  } else if (!sizing) {
-    COMIC_REQUIRE(p && fm && im_embed && inputs_bt && targets_bt && wmask_bt && lens, "score: null input");
-    COMIC_REQUIRE(sc->token_logp_tb && sc->caption_logp && workspace, "score: null output");
+// Caller's side of one teacher-forced call: what comic_decoder_train_step / comic_decoder_score were handed.  Scoring
+// (score set): the forward with the masks absent, then the per-token log-likelihoods (score_logits.hip) in place of
+// the logits product, the loss and the backward.
+struct StepIO {
+  const float *fm, *im_embed, *wmask_bt, *coef_bt, *mask_init_in, *mask_in, *mask_out, *mask_alpha;
+  const int32_t *inputs_bt, *targets_bt, *lens;
+  int B, T, Tp;
+  float *logits_tb, *attn_hist, *loss_rows, *map_loss, *dfm, *dim_embed;
+  int32_t* ids_tb;
+  bool score;
+  float *token_logp_tb, *caption_logp;        // [T][B], [B]: scoring
+  void* workspace;
+  int64_t workspace_bytes;
+};
+
+// The decisions of one call, taken once after validation
+struct StepPlan {
+  bool score, score_stream, use_map, drop_in;
+  bool do_fwd, do_bwd;        // COMIC_DEC_PHASE_FWD / _BWD: the step in two calls over one workspace (to the logits | loss + backward)
+  bool fused, fused_q;        // fused step kernels (decoder_fused.hip); ... of the backward's query half too
+  bool persist, persist_b;    // the time loops as persistent launches (decoder_persist.hip, decoder_persist_bwd.hip)
+  bool grp;                   // the products outside the time loops as grouped launches (gemm_group.hip)
+  bool prologue_rides;        // the forward panel of the LSTM kernel and the padded W_o ride on comic_persist_prepare
+  int attn_bwd_mode, Vp, ldl; // comic_attn_bwd_ex's pgrad_overwrite; padded vocabulary; row stride of d logits
+  const float *wo_g, *values; // W_o with rows of ldl floats; the attention's values (keys when tied, fm without a projection)
+  const float *m_init, *m_in, *m_out, *m_alpha;               // dropout masks: null when that dropout is off
+  float *attn_hist, *attn_ws, *dvalues;
+  comic_attn_desc ad;
+  SideLane* lane;
+};
+
+// The pointers of time step t: the one place of the t * B * ... offsets, of "null when that dropout is off" and of "the next
+// step's operand row, or null at the last step"
+struct StepView {
+  float *xh, *xh_next_att, *xh_next_h, *gates, *cnew, *y, *q, *alpha, *hist, *ctx, *c_next, *h_next, *att_next;
+  const float *c_prev, *h_prev, *att_prev, *mask_in, *mask_att_next, *mask_out, *mask_alpha, *dmap;
+  float *lnx, *lnr, *xh2, *lnpg;              // LN_LSTM / GRU rows (null for the other cells)
+  float *dq, *dy, *dg, *demb, *pgrad;         // backward
+};
+
+struct TeacherForcedStep {
+  const comic_decoder_desc* d;
+  const comic_decoder_params *p, *gr;
+  const StepIO& io;
+  hipStream_t st;
+  TrainLayout L{};
+  StepPlan pl{};
+  int B = 0, T = 0, Tp = 0, D = 0, E = 0, A = 0, V = 0, M = 0, H = 0, Cv = 0, EA = 0, Wd = 0, cell = 0;
+  float* dx_im = nullptr;     // gradient w.r.t. (im_embed * W_init), n_init columns: set by the weight-gradient phase
+  int n_init = 0;
+
+  StepView view(int t) const {
+    const size_t r = (size_t)t * B;             // first row of the step in the time-major blocks
+    const bool last = t + 1 >= Tp;
+    StepView v{};
+    float* xh_n = last ? nullptr : L.xh_all + (r + B) * Wd;
+    v.xh = L.xh_all + r * Wd; v.xh_next_att = xh_n ? xh_n + E : nullptr; v.xh_next_h = xh_n ? xh_n + EA : nullptr;
+    v.gates = L.gates_all + r * 4 * D; v.cnew = L.cnew_all + r * D; v.y = L.y_all + r * D; v.q = L.q_all + r * D;
+    v.alpha = L.alpha_all + r * H * M; v.hist = pl.attn_hist + r * H * M; v.ctx = L.ctx_all + r * Cv;
+    v.c_prev = L.cs + r * D; v.h_prev = L.hs + r * D; v.att_prev = L.att_all + r * A;
+    v.c_next = L.cs + (r + B) * D; v.h_next = L.hs + (r + B) * D; v.att_next = L.att_all + (r + B) * A;
+    v.mask_in = pl.m_in ? pl.m_in + r * EA : nullptr; v.mask_att_next = (pl.m_in && !last) ? pl.m_in + (r + B) * EA + E : nullptr;
+    v.mask_out = pl.m_out ? pl.m_out + r * D : nullptr; v.mask_alpha = pl.m_alpha ? pl.m_alpha + r * H * M : nullptr;
+    v.lnx = L.lnx_all ? L.lnx_all + r * 5 * D : nullptr; v.lnr = L.lnr_all ? L.lnr_all + r * 8 : nullptr;
+    v.xh2 = L.xh2_all ? L.xh2_all + r * Wd : nullptr;
+    if (pl.score) return v;
+    v.lnpg = L.lnpg ? L.lnpg + r * 10 * D : nullptr; v.dmap = pl.use_map ? L.dmap + r * M : nullptr;
+    v.dq = L.dq_all + r * D; v.dy = L.dy_all + r * D; v.dg = L.dg_all + r * 4 * D; v.demb = L.demb + r * E;
+    v.pgrad = L.pgrad + r * (3 * D + 1);
+    return v;
   }
-  COMIC_REQUIRE(B > 0 && T > 0 && Tp > 0 && Tp <= T, "train_step: bad B/T/Tp (%d %d %d)", B, T, Tp);
-  if (!sc) COMIC_REQUIRE(workspace_bytes >= comic_decoder_train_workspace(d, B, T), "train_step: workspace too small");
-  COMIC_REQUIRE(d->keep_in >= 1.f || (mask_in && (d->init_method == 1 || mask_init_in)),
-                "train_step: input dropout enabled but no mask given");
-  COMIC_REQUIRE(d->keep_out >= 1.f || mask_out, "train_step: output dropout enabled but no mask given");
-  COMIC_REQUIRE(d->keep_alpha >= 1.f || mask_alpha, "train_step: attention dropout enabled but no mask given");
-  hipStream_t st = (hipStream_t)stream;
-  const int D = d->D, E = d->E, A = d->A, V = d->V, M = d->M, H = d->H, Cv = d->Cv, EA = E + A, Wd = E + A + D;
-  const long TB = (long)T * B;
-  const bool drop_in = d->keep_in < 1.f, drop_out = d->keep_out < 1.f, drop_al = d->keep_alpha < 1.f;
-  const long bw = sc ? 0 : 1;                     // backward-only blocks: not taken when scoring
-  Bump w(sizing ? nullptr : workspace, sizing ? 0 : (size_t)workspace_bytes);
-  float* keys = w.take<float>((long)B * M * D);
-  float* values_buf = w.take<float>((long)B * M * D);
-  InitBufs ib;
-  ib.x = w.take<float>((long)B * EA); ib.xh = w.take<float>((long)B * EA);
-  ib.g = w.take<float>((long)B * 4 * D); ib.gates = w.take<float>((long)B * 4 * D); ib.c_new = w.take<float>((long)B * D);
-  float* emb_all = w.take<float>(bw * TB * E);
-  int32_t* in_tb = w.take<int32_t>(TB);
-  float* xh_all = w.take<float>((TB + B) * Wd);
-  float* g_tmp = w.take<float>((long)B * 4 * D);
-  float* gates_all = w.take<float>(TB * 4 * D);
-  float* cs = w.take<float>((TB + B) * D);
-  float* hs = w.take<float>((TB + B) * D);
-  float* cnew_all = w.take<float>(TB * D);
-  float* y_all = w.take<float>(TB * D);
-  float* q_all = w.take<float>(TB * D);
-  float* alpha_all = w.take<float>(TB * H * M);
-  float* ctx_all = w.take<float>(TB * Cv);
-  float* att_new = w.take<float>((long)B * D);
-  float* att_all = w.take<float>((TB + B) * A);
-  const int Vp = (V + 3) / 4 * 4;                 // d logits / W_o rows padded to 16 bytes: every product loads them 16 bytes at a time
-  float* dlogits = w.take<float>(bw * TB * Vp);
-  float* wo_pad = w.take<float>(bw * D * Vp);
-  float* dy_all = w.take<float>(bw * TB * D);
-  float* dq_all = w.take<float>(bw * TB * D);
-  float* dg_all = w.take<float>(bw * (TB + B) * 4 * D);
-  float* dxh = w.take<float>(bw * B * Wd);
-  float* dc = w.take<float>(bw * B * D);
-  float* dh = w.take<float>(bw * B * D);
-  float* datt = w.take<float>(bw * B * A);
-  float* datt_live = w.take<float>(bw * B * A);
-  float* dctx = w.take<float>(bw * B * Cv);
-  float* demb = w.take<float>(bw * TB * E);
-  float* dkeys = w.take<float>(bw * B * M * D);
-  float* dvalues_buf = w.take<float>(bw * B * M * Cv);
-  float* pgrad = w.take<float>(bw * TB * (3 * D + 1));   // one attention-parameter gradient row per (step, batch row)
-  float* dmap = w.take<float>(bw * TB * M);
-  float* dx_init = w.take<float>(bw * B * EA);
-  g_splitk_ws = w.take<char>(kSplitKBytes);
-  void* splitk_ws_b = w.take<char>(kSplitKBytes);
-  float* kpanel_f = w.take<float>(comic_lstm_panel_floats(D, Wd, 0));
-  float* kpanel_b = w.take<float>(bw * comic_lstm_panel_floats(D, Wd, 1));
-  float* wq_panel = w.take<float>(bw * D * D);
-  unsigned* persist_sync = w.take<unsigned>(kPersistSyncWords + kGroupTickets);
-  unsigned* gg_tickets = persist_sync + kPersistSyncWords;
-  const long TB16 = (long)T * ((B + 15) / 16) * 16;
-  float* dq_part = w.take<float>(TB * 4 * D);
-  float* dg_blk = w.take<float>(bw * TB16 * 4 * D);
-  float* dq_sum = w.take<float>(bw * TB16 * D);
-  float* dstate = w.take<float>(bw * TB * 2 * D);
-  float* pgrad4 = w.take<float>(bw * 4 * B * (3 * D + 1));
-  float* dotp = w.take<float>(bw * TB * 64);
-  float* statp = comic_persist_fwd_bigm(M, d->fm_projection == 2) ? w.take<float>(TB * 8 * M) : nullptr;
-  const int cell = d->cell;
-  float *lnx_all = nullptr, *lnr_all = nullptr, *lnpg = nullptr, *cell_tmp = nullptr, *xh2_all = nullptr, *gru_dxh = nullptr;
-  if (cell == COMIC_CELL_LN_LSTM) {
-    lnx_all = w.take<float>((TB + B) * 5 * D); lnr_all = w.take<float>((TB + B) * 8);
-    lnpg = w.take<float>(bw * (TB + B) * 10 * D); cell_tmp = w.take<float>(10L * D);
-    ib.lnx = lnx_all + TB * 5 * D; ib.lnr = lnr_all + TB * 8;      // the init step's rows sit behind the time steps'
-  } else if (cell == COMIC_CELL_GRU) {
-    xh2_all = w.take<float>(TB * Wd); gru_dxh = w.take<float>(bw * 2 * B * Wd); cell_tmp = w.take<float>(4L * D);
-  }
-  // scoring: the alignment history when the caller takes none, and the projection's scratch (no [T'][B][V] block on the
-  // streaming path: packed W_o and per-chunk partials)
-  const bool score_stream = sc && beam_logits_enabled() && comic_score_stream_supported(D, V);
-  const int64_t score_ws_bytes = sc ? comic_score_logits_ws_bytes(D, V, TB, score_stream) : 0;
-  if (sc && !attn_hist) attn_hist = w.take<float>(TB * H * M);
-  void* score_ws = w.take<char>((size_t)score_ws_bytes);
-  if (sizing) {
-    *sc->size_out = (int64_t)w.off;
+
+  // ---- validation, workspace, plan ---------------------------------------------------------------------------------------
+  int validate_and_plan() {
+    const bool sc = io.score;
+    if (!sc) {
+      COMIC_REQUIRE(p && gr && io.fm && io.im_embed && io.inputs_bt && io.targets_bt && io.wmask_bt && io.coef_bt && io.lens,
+                    "train_step: null input");
+      COMIC_REQUIRE(io.logits_tb && io.ids_tb && io.attn_hist && io.loss_rows && io.map_loss && io.workspace,
+                    "train_step: null output");
+    } else {
+      COMIC_REQUIRE(p && io.fm && io.im_embed && io.inputs_bt && io.targets_bt && io.wmask_bt && io.lens, "score: null input");
+      COMIC_REQUIRE(io.token_logp_tb && io.caption_logp && io.workspace, "score: null output");
+    }
+    B = io.B; T = io.T; Tp = io.Tp;
+    COMIC_REQUIRE(B > 0 && T > 0 && Tp > 0 && Tp <= T, "train_step: bad B/T/Tp (%d %d %d)", B, T, Tp);
+    if (!sc) COMIC_REQUIRE(io.workspace_bytes >= comic_decoder_train_workspace(d, B, T), "train_step: workspace too small");
+    COMIC_REQUIRE(d->keep_in >= 1.f || (io.mask_in && (d->init_method == 1 || io.mask_init_in)),
+                  "train_step: input dropout enabled but no mask given");
+    COMIC_REQUIRE(d->keep_out >= 1.f || io.mask_out, "train_step: output dropout enabled but no mask given");
+    COMIC_REQUIRE(d->keep_alpha >= 1.f || io.mask_alpha, "train_step: attention dropout enabled but no mask given");
+    D = d->D; E = d->E; A = d->A; V = d->V; M = d->M; H = d->H; Cv = d->Cv; EA = E + A; Wd = E + A + D; cell = d->cell;
+    L.carve(d, B, T, sc ? TF_SCORE : TF_TRAIN, !io.attn_hist, io.workspace, (size_t)io.workspace_bytes);
+    g_splitk_ws = L.splitk_a;
+    COMIC_REQUIRE(L.ok, sc ? "score: workspace too small" : "train_step: workspace overflow");
+    RC(check_cell_params(d, p));
+    pl.score = sc;
+    pl.do_fwd = !(d->flags & COMIC_DEC_PHASE_BWD); pl.do_bwd = !(d->flags & COMIC_DEC_PHASE_FWD);
+    COMIC_REQUIRE(pl.do_fwd || pl.do_bwd, "train_step: both phase flags set");
+    pl.ad = attn_desc(d, B);
+    pl.values = d->fm_projection == 2 ? L.keys : d->fm_projection == 1 ? L.values_buf : io.fm;   // (= what memory_projections reports)
+    pl.drop_in = d->keep_in < 1.f;
+    pl.m_init = pl.drop_in ? io.mask_init_in : nullptr; pl.m_in = pl.drop_in ? io.mask_in : nullptr;
+    pl.m_out = d->keep_out < 1.f ? io.mask_out : nullptr; pl.m_alpha = d->keep_alpha < 1.f ? io.mask_alpha : nullptr;
+    pl.attn_hist = io.attn_hist ? io.attn_hist : L.attn_hist_own;
+    pl.score_stream = L.score_stream;
+    pl.fused = fused_step_enabled() && comic_fused_step_supported(D, Wd);
+    pl.fused_q = pl.fused && D % 16 == 0;
+    pl.persist = pl.fused && persist_enabled() &&
+                 comic_persist_fwd_supported(B, D, E, A, M, H, Cv, d->method, d->context_layer, pl.ad.tied) &&
+                 comic_persist_fits_device(B);
+    pl.persist_b = !sc && pl.persist && persist_bwd_enabled() &&
+                   comic_persist_bwd_supported(B, D, E, A, M, H, Cv, d->method, d->prob, d->context_layer, pl.ad.tied);
+    if (sc) g_score_path = (pl.persist ? 1 : 0) | (pl.score_stream ? 2 : 0);
+    else g_train_path = (pl.persist ? 1 : 0) | (pl.persist_b ? 2 : 0);
+    pl.attn_ws = L.attn_scratch(pl.persist_b);
+    pl.prologue_rides = pl.persist && pl.do_fwd && group_gemm_enabled() && cell == COMIC_CELL_LSTM && pl.fused;
+    // grp: the rnn init step then keeps its operand rows and its d gates in row block Tp of xh_all / dg_all, so that d K and
+    // d b are ONE product over (Tp + 1) * B rows.  (Products with a short reduction -- a handful of rows in all -- keep the
+    // separate launches, whose small shapes run the exact-fp32 kernels: gemm_big's rule)
+    pl.grp = group_gemm_enabled() && cell == COMIC_CELL_LSTM && (long)Tp * B >= 64 && (long)B * M >= 64 && B >= 16;
+    pl.Vp = (V + 3) / 4 * 4;
+    pl.ldl = pl.grp ? pl.Vp : V;
+    pl.wo_g = (pl.grp && pl.Vp != V) ? L.wo_pad : p->W_o;
+    pl.lane = pl.grp ? nullptr : side_lane();
+    pl.use_map = d->map_loss_scale > 0.f;
+    pl.dvalues = d->fm_projection != 2 ? L.dvalues_buf : L.dkeys;
+    // softmax attention: the backward kernel runs as two workgroups per batch row (half of the memory rows each), whose
+    // d q / parameter-gradient contributions are added into zero-filled rows (comic_attn_bwd_ex, pgrad_overwrite 2)
+    pl.attn_bwd_mode = (d->prob == 0 && split_attn_bwd_enabled()) ? 2 : 1;
     return 0;
   }
-  COMIC_REQUIRE(w.ok, sc ? "score: workspace too small" : "train_step: workspace overflow");
-  RC(check_cell_params(d, p));
-  // COMIC_DEC_PHASE_FWD / _BWD: the step in two calls over the same workspace -- everything up to the logits (no loss
-  // coefficient enters it), then loss + backward.  The SCST step runs the first under the host's reward computation.
-  const bool do_fwd = !(d->flags & COMIC_DEC_PHASE_BWD), do_bwd = !(d->flags & COMIC_DEC_PHASE_FWD);
-  COMIC_REQUIRE(do_fwd || do_bwd, "train_step: both phase flags set");
 
-  const comic_attn_desc ad = attn_desc(d, B);
-  const float* values = d->fm_projection == 2 ? keys : d->fm_projection == 1 ? values_buf : fm;   // (= what memory_projections reports)
-  const bool fused = fused_step_enabled() && comic_fused_step_supported(D, Wd);
-  const bool fused_q = fused && D % 16 == 0;
-  // the time loops as persistent launches (decoder_persist.hip, decoder_persist_bwd.hip) when the shape allows it
-  const bool persist = fused && persist_enabled() &&
-                       comic_persist_fwd_supported(B, D, E, A, M, H, Cv, d->method, d->context_layer, ad.tied) &&
-                       comic_persist_fits_device(B);
-  const bool persist_b = !sc && persist && persist_bwd_enabled() &&
-                         comic_persist_bwd_supported(B, D, E, A, M, H, Cv, d->method, d->prob, d->context_layer, ad.tied);
-  if (sc) g_score_path = (persist ? 1 : 0) | (score_stream ? 2 : 0);
-  else g_train_path = (persist ? 1 : 0) | (persist_b ? 2 : 0);
-  // scratch of the split attention kernels (large memories: comic_attn_splits workgroups per batch row): the d q
-  // partials of the persistent backward loop, free whenever the per-step kernels run ([Tp][B][4][D] >= 2 x [B][H][M])
-  float* attn_ws = (!persist_b && comic_attn_splits(B, M) > 1 &&
-                    TB * 4 * D >= (long)B * H * M + comic_attn_bwd_scratch(B, H, M, D)) ? dq_part : nullptr;
-  bool prologue_rides = false;
-  if (persist && do_fwd) {   // every hand-off buffer of the step starts as "not written yet"; the error word as zero
+  // ---- persistent loops: every hand-off buffer of the step starts as "not written yet", the sync words and tickets as zero
+  int prologue() {
     ComicPersistRanges pr{};
     const long n16 = (long)Tp * ((B + 15) / 16) * 16 * D;
-    pr.p[0] = xh_all; pr.n[0] = (long)Tp * B * Wd;
-    pr.p[1] = y_all; pr.n[1] = (long)Tp * B * D;
-    pr.p[2] = q_all; pr.n[2] = (long)Tp * B * D;
-    if (statp) {                       // the quarters' partial LayerNorm sums (decoder_persist.hip, BIGM): [Tp][B][4][M/2][4]
-      pr.p[8] = statp; pr.n[8] = (long)Tp * B * 8 * M;
+    pr.p[0] = L.xh_all; pr.n[0] = (long)Tp * B * Wd;
+    pr.p[1] = L.y_all; pr.n[1] = (long)Tp * B * D;
+    pr.p[2] = L.q_all; pr.n[2] = (long)Tp * B * D;
+    if (L.statp) {                     // the quarters' partial LayerNorm sums (decoder_persist.hip, BIGM): [Tp][B][4][M/2][4]
+      pr.p[8] = L.statp; pr.n[8] = (long)Tp * B * 8 * M;
     }
-    if (persist_b) {
-      pr.p[3] = dq_part; pr.n[3] = (long)Tp * B * 4 * D;
-      pr.p[4] = dg_blk; pr.n[4] = 4 * n16;
-      pr.p[5] = dstate; pr.n[5] = (long)Tp * B * 2 * D;
-      pr.p[6] = dq_sum; pr.n[6] = n16;
-      pr.p[7] = dotp; pr.n[7] = (long)Tp * B * 64;
+    if (pl.persist_b) {
+      pr.p[3] = L.dq_part; pr.n[3] = (long)Tp * B * 4 * D;
+      pr.p[4] = L.dg_blk; pr.n[4] = 4 * n16;
+      pr.p[5] = L.dstate; pr.n[5] = (long)Tp * B * 2 * D;
+      pr.p[6] = L.dq_sum; pr.n[6] = n16;
+      pr.p[7] = L.dotp; pr.n[7] = (long)Tp * B * 64;
     }
-    // grouped path: the forward panel of the LSTM kernel and the padded W_o ride on the same launch
     ComicPrologueExtra px{};
-    prologue_rides = group_gemm_enabled() && cell == COMIC_CELL_LSTM && fused;
-    if (prologue_rides) {
-      px.K = p->K; px.panel = kpanel_f; px.D = D; px.Wd = Wd; px.n_pack = comic_lstm_panel_floats(D, Wd, 0);
-      if (Vp != V && !sc) { px.W_o = p->W_o; px.wo_pad = wo_pad; px.V = V; px.Vp = Vp; px.n_pad = (long)D * Vp; }
+    if (pl.prologue_rides) {
+      px.K = p->K; px.panel = L.kpanel_f; px.D = D; px.Wd = Wd; px.n_pack = comic_lstm_panel_floats(D, Wd, 0);
+      if (pl.Vp != V && !pl.score) { px.W_o = p->W_o; px.wo_pad = L.wo_pad; px.V = V; px.Vp = pl.Vp; px.n_pad = (long)D * pl.Vp; }
     }
-    RC(comic_persist_prepare(pr, persist_sync, kPersistSyncWords + kGroupTickets, st, prologue_rides ? &px : nullptr));
+    return comic_persist_prepare(pr, L.persist_sync, L.sync_words(), st, pl.prologue_rides ? &px : nullptr);
   }
-  // ------------------------------------------------------------------ forward ------------
-  // grp: the products outside the time loops as grouped launches (gemm_group.hip).  The rnn init step then keeps its
-  // operand rows [drop(x_init) ; 0] and its d gates in row block Tp of xh_all / dg_all, so that d K and d b are ONE
-  // product over (Tp + 1) * B rows.
-  // (products with a short reduction -- a handful of rows in all -- keep the separate launches, whose small shapes run the
-  // exact-fp32 kernels: gemm_big's rule)
-  const bool grp = group_gemm_enabled() && cell == COMIC_CELL_LSTM && (long)Tp * B >= 64 && (long)B * M >= 64 && B >= 16;
-  const int ldl = grp ? Vp : V;                                // row stride of d logits
-  const float* wo_g = (grp && Vp != V) ? wo_pad : p->W_o;      // W_o with rows of ldl floats
-  float* xh_init = xh_all + (size_t)Tp * B * Wd;
-  float* dg_init = dg_all + (size_t)Tp * B * 4 * D;
-  void* const gg_slab = g_splitk_ws;                 // both lanes' split-K blocks: consecutive in the workspace
-  const int64_t gg_slab_cap = 2 * kSplitKBytes;
-  SideLane* L = grp ? nullptr : side_lane();
-  if (do_fwd) {
-  if (grp) {
-    if (!persist) COMIC_REQUIRE(hipMemsetAsync(gg_tickets, 0, sizeof(unsigned) * kGroupTickets, st) == hipSuccess, "train_step: memset");
-    if (fused && !(prologue_rides && (persist_b || sc))) RC(comic_pack_lstm_panels(p->K, prologue_rides ? nullptr : kpanel_f, (persist_b || sc) ? nullptr : kpanel_b, D, Wd, st));
-    if (fused_q && !persist_b && !sc) RC(comic_pack_wq_panel(p->W_q, wq_panel, D, st));
-    if (Vp != V && !prologue_rides && !sc) {
-      const long n = (long)D * Vp;
-      hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, p->W_o, wo_pad, V, Vp, n);
+
+  // ---- forward set-up: weight panels, memory projections, rnn init -- as grouped launches ...
+  int forward_setup_grouped() {
+    const bool no_bwd_panels = pl.persist_b || pl.score;    // the persistent backward reads K and W_q in place
+    if (!pl.persist)
+      COMIC_REQUIRE(hipMemsetAsync(L.gg_tickets(), 0, sizeof(unsigned) * kGroupTickets, st) == hipSuccess, "train_step: memset");
+    if (pl.fused && !(pl.prologue_rides && no_bwd_panels))
+      RC(comic_pack_lstm_panels(p->K, pl.prologue_rides ? nullptr : L.kpanel_f, no_bwd_panels ? nullptr : L.kpanel_b, D, Wd, st));
+    if (pl.fused_q && !no_bwd_panels) RC(comic_pack_wq_panel(p->W_q, L.wq_panel, D, st));
+    if (pl.Vp != V && !pl.prologue_rides && !pl.score) {
+      const long n = (long)D * pl.Vp;
+      hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, p->W_o, L.wo_pad, V, pl.Vp, n);
       COMIC_LAUNCH_CHECK("pad W_o");
     }
     GemmGroupRun g1;
-    g1.add(COMIC_GG_NN, fm, p->W_m, keys, B * M, D, d->C, d->C, D, D);
-    if (d->fm_projection == 1) g1.add(COMIC_GG_NN, fm, p->W_v, values_buf, B * M, D, d->C, d->C, D, D);
+    g1.add(COMIC_GG_NN, io.fm, p->W_m, L.keys, B * M, D, d->C, d->C, D, D);
+    if (d->fm_projection == 1) g1.add(COMIC_GG_NN, io.fm, p->W_v, L.values_buf, B * M, D, d->C, d->C, D, D);
     if (d->init_method == 1) {
-      g1.add(COMIC_GG_NN, im_embed, p->W_init, hs, B, D, d->Cg, d->Cg, D, D);
+      g1.add(COMIC_GG_NN, io.im_embed, p->W_init, L.hs, B, D, d->Cg, d->Cg, D, D);
     } else {
-      ComicGemmProb* q = g1.add(COMIC_GG_NN, im_embed, p->W_init, xh_init, B, EA, d->Cg, d->Cg, EA, Wd);
-      if (drop_in) { q->mask = mask_init_in; q->ld_mask = EA; q->keep = d->keep_in; }
+      ComicGemmProb* q = g1.add(COMIC_GG_NN, io.im_embed, p->W_init, L.xh_init(Tp), B, EA, d->Cg, d->Cg, EA, Wd);
+      if (pl.drop_in) { q->mask = io.mask_init_in; q->ld_mask = EA; q->keep = d->keep_in; }
     }
-    RC(g1.run(gg_slab, gg_slab_cap, gg_tickets, st));
-    if (d->init_method == 1) {
-      RC(fill(cs, 0.f, (long)B * D, st));
-    } else {
-      // zero initial state: only the first E+A rows of the cell's kernel contribute
-      GemmGroupRun g2;
-      g2.add(COMIC_GG_NN, xh_init, p->K, ib.g, B, 4 * D, EA, Wd, 4 * D, 4 * D)->bias = p->b;
-      RC(g2.run(gg_slab, gg_slab_cap, gg_tickets, st));      // (the cell itself: inside the operand-row launch below)
-    }
-  } else {
-    LaneScope lane(L, st, splitk_ws_b);
+    RC(g1.run(L.gg_slab(), L.gg_slab_cap(), L.gg_tickets(), st));
+    if (d->init_method == 1) return fill(L.cs, 0.f, (long)B * D, st);
+    // zero initial state: only the first E+A rows of the cell's kernel contribute
+    GemmGroupRun g2;
+    g2.add(COMIC_GG_NN, L.xh_init(Tp), p->K, L.ib.g, B, 4 * D, EA, Wd, 4 * D, 4 * D)->bias = p->b;
+    return g2.run(L.gg_slab(), L.gg_slab_cap(), L.gg_tickets(), st);      // (the cell itself: inside the operand-row launch)
+  }
+  // ... or on two lanes: the panels (needed by the time loop only) and the rnn init on the side lane
+  int forward_setup_lanes() {
+    const bool no_bwd_panels = pl.persist_b || pl.score;
+    LaneScope lane(pl.lane, st, L.splitk_b);
     RC(lane.rc);
     hipStream_t sl = lane.lane();
-    // weight panels of the fused step kernels (the persistent backward reads K and W_q in place): needed by the time
-    // loop only, so they are packed on the side lane too
-    if (fused) RC(comic_pack_lstm_panels(p->K, kpanel_f, (persist_b || sc) ? nullptr : kpanel_b, D, Wd, sl));
-    if (fused_q && !persist_b && !sc) RC(comic_pack_wq_panel(p->W_q, wq_panel, D, sl));
-    RC(rnn_init_fwd(d, p, im_embed, B, drop_in ? mask_init_in : nullptr, ib, cs, hs, sl));
+    if (pl.fused) RC(comic_pack_lstm_panels(p->K, L.kpanel_f, no_bwd_panels ? nullptr : L.kpanel_b, D, Wd, sl));
+    if (pl.fused_q && !no_bwd_panels) RC(comic_pack_wq_panel(p->W_q, L.wq_panel, D, sl));
+    RC(rnn_init_fwd(d, p, io.im_embed, B, pl.m_init, L.ib, L.cs, L.hs, sl));
     lane.main_ws();
-    RC(memory_projections(d, p, fm, B, keys, values_buf, &values, st));
-    RC(lane.join());
+    const float* values = nullptr;
+    RC(memory_projections(d, p, io.fm, B, L.keys, L.values_buf, &values, st));
+    return lane.join();
   }
-  // operand rows before the loop: the x part of every step (embedding lookup + input dropout, hoisted) and step 0's
-  // att part (zero: dropout of 0 is 0) and h part (h0)
-  {
-    const bool zi = grp && d->init_method != 1;
+
+  // operand rows before the loop: the x part of every step (embedding lookup + input dropout, hoisted) and step 0's att part
+  // (zero: dropout of 0 is 0) and h part (h0); grouped path: the init step's cell from its zero state too
+  int operand_rows() {
+    const bool zi = pl.grp && d->init_method != 1;
     const long n = (long)Tp * B * E + (long)B * A + (long)B * D * (zi ? 2 : 1);
-    hipLaunchKernelGGL(embed_step0_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, p->emb, inputs_bt, in_tb,
-                       drop_in ? mask_in : nullptr, d->keep_in, xh_all, att_all, hs, Tp, B, T, E, A, D, V,
-                       zi ? xh_init : (float*)nullptr, zi ? ib.g : (const float*)nullptr, ib.gates, ib.c_new, cs, hs);
+    hipLaunchKernelGGL(embed_step0_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, p->emb, io.inputs_bt, L.in_tb,
+                       pl.m_in, d->keep_in, L.xh_all, L.att_all, L.hs, Tp, B, T, E, A, D, V,
+                       zi ? L.xh_init(Tp) : (float*)nullptr, zi ? L.ib.g : (const float*)nullptr, L.ib.gates, L.ib.c_new, L.cs,
+                       L.hs);
     COMIC_LAUNCH_CHECK("embed_step0");
+    return 0;
   }
-  if (persist) {
+
+  // a persistent launch serves up to four 16-row groups of the batch (256 CUs)
+  template <typename Args>
+  int launch_groups(Args& a, int (*launch)(const Args&, hipStream_t)) {
+    const int n_grp = (B + 15) / 16;
+    for (a.grp0 = 0; a.grp0 < n_grp; a.grp0 += 4) {
+      a.n_groups = std::min(4, n_grp - a.grp0);
+      RC(launch(a, st));
+    }
+    return 0;
+  }
+
+  // ---- forward time loop, as persistent launches ...
+  int forward_persistent() {
     ComicPersistFwdArgs pa{};
-    pa.K_panel = kpanel_f; pa.bias = p->b; pa.W_q = p->W_q; pa.keys = keys; pa.values = values;
-    pa.ln_g = p->ln_g; pa.ln_b = p->ln_b; pa.v = p->v; pa.tau = p->tau; pa.lens = lens;
-    pa.mask_in = drop_in ? mask_in : nullptr; pa.mask_out = drop_out ? mask_out : nullptr;
-    pa.mask_alpha = drop_al ? mask_alpha : nullptr;
+    pa.K_panel = L.kpanel_f; pa.bias = p->b; pa.W_q = p->W_q; pa.keys = L.keys; pa.values = pl.values;
+    pa.ln_g = p->ln_g; pa.ln_b = p->ln_b; pa.v = p->v; pa.tau = p->tau; pa.lens = io.lens;
+    pa.mask_in = pl.m_in; pa.mask_out = pl.m_out; pa.mask_alpha = pl.m_alpha;
     pa.keep_in = d->keep_in; pa.keep_out = d->keep_out; pa.keep_alpha = d->keep_alpha;
-    pa.xh_all = xh_all; pa.gates_all = gates_all; pa.cnew_all = cnew_all; pa.y_all = y_all; pa.q_all = q_all;
-    pa.cs = cs; pa.hs = hs; pa.att_all = att_all; pa.alpha_all = alpha_all; pa.attn_hist = attn_hist;
-    pa.ctx_all = ctx_all; pa.sync = persist_sync;
-    pa.statp = statp;
+    pa.xh_all = L.xh_all; pa.gates_all = L.gates_all; pa.cnew_all = L.cnew_all; pa.y_all = L.y_all; pa.q_all = L.q_all;
+    pa.cs = L.cs; pa.hs = L.hs; pa.att_all = L.att_all; pa.alpha_all = L.alpha_all; pa.attn_hist = pl.attn_hist;
+    pa.ctx_all = L.ctx_all; pa.sync = L.persist_sync;
+    pa.statp = L.statp;
     pa.B = B; pa.D = D; pa.E = E; pa.Wd = Wd; pa.M = M; pa.H = H; pa.Tp = Tp;
-    pa.method = d->method; pa.prob = d->prob; pa.tied = ad.tied;
-    const int n_grp = (B + 15) / 16;                     // a launch serves up to four 16-row groups (256 CUs)
-    for (int g0 = 0; g0 < n_grp; g0 += 4) {
-      pa.grp0 = g0;
-      pa.n_groups = std::min(4, n_grp - g0);
-      RC(comic_persist_fwd_launch(pa, st));
-    }
+    pa.method = d->method; pa.prob = d->prob; pa.tied = pl.ad.tied;
+    return launch_groups(pa, comic_persist_fwd_launch);
   }
-  for (int t = 0; t < (persist ? 0 : Tp); ++t) {
-    float* xh_t = xh_all + (size_t)t * B * Wd;
-    float* xh_n = (t + 1 < Tp) ? xh_all + (size_t)(t + 1) * B * Wd : nullptr;
-    const float* c_prev = cs + (size_t)t * B * D;
-    const float* h_prev = hs + (size_t)t * B * D;
-    const float* att_prev = att_all + (size_t)t * B * A;
-    float* att_next = att_all + (size_t)(t + 1) * B * A;
-    const float* mask_n = (drop_in && xh_n) ? mask_in + (size_t)(t + 1) * B * EA + E : nullptr;
-    int S1 = 1, S2 = 1;
+
+  // the recurrent cell of step t in its per-step forms: the fused LSTM step, or a split-K product + the cell's kernel(s)
+  int cell_fwd(const StepView& v, int t) {
     float* part = (float*)g_splitk_ws;
-    float* y_t = y_all + (size_t)t * B * D;
-    if (fused) {
-      RC(comic_lstm_step_fused(xh_t, Wd, kpanel_f, p->b, c_prev, h_prev, gates_all + (size_t)t * B * 4 * D,
-                               cnew_all + (size_t)t * B * D, y_t, drop_out ? mask_out + (size_t)t * B * D : nullptr,
-                               d->keep_out, lens, t, cs + (size_t)(t + 1) * B * D, hs + (size_t)(t + 1) * B * D,
-                               xh_n ? xh_n + EA : nullptr, Wd, B, D, Wd, st));
-    } else if (cell == COMIC_CELL_LN_LSTM) {
-      RC(comic_gemm_f32_partial(xh_t, p->K, B, 4 * D, Wd, Wd, 4 * D, 0, part, kSplitKBytes, &S1, st));
-      RC(comic_ln_lstm_fwd(part, S1, p->cell_ln, c_prev, h_prev, gates_all + (size_t)t * B * 4 * D,
-                           lnx_all + (size_t)t * B * 5 * D, lnr_all + (size_t)t * B * 8, cnew_all + (size_t)t * B * D, y_t,
-                           drop_out ? mask_out + (size_t)t * B * D : nullptr, d->keep_out, lens, t,
-                           cs + (size_t)(t + 1) * B * D, hs + (size_t)(t + 1) * B * D, B, D, xh_n ? xh_n + EA : nullptr, Wd, st));
-    } else if (cell == COMIC_CELL_GRU) {         // gates_all[t]: r | u | candidate | -
-      float* ga = gates_all + (size_t)t * B * 4 * D;
-      float* xh2_t = xh2_all + (size_t)t * B * Wd;
-      RC(comic_gemm_f32_partial(xh_t, p->K, B, 2 * D, Wd, Wd, 2 * D, 0, part, kSplitKBytes, &S1, st));
-      RC(comic_gru_gates_fwd(part, S1, p->b, h_prev, xh_t, Wd, ga, 4 * D, xh2_t, Wd, B, D, EA, st));
-      RC(comic_gemm_f32_partial(xh2_t, p->K_c, B, D, Wd, Wd, D, 0, part, kSplitKBytes, &S1, st));
-      RC(comic_gru_out_fwd(part, S1, p->b_c, ga, 4 * D, h_prev, ga + 2 * D, 4 * D, y_t,
-                           drop_out ? mask_out + (size_t)t * B * D : nullptr, d->keep_out, lens, t,
-                           hs + (size_t)(t + 1) * B * D, xh_n ? xh_n + EA : nullptr, Wd, B, D, st));
-    } else {
-      RC(comic_gemm_f32_partial(xh_t, p->K, B, 4 * D, Wd, Wd, 4 * D, 0, part, kSplitKBytes, &S1, st));
-      RC(comic_lstm_gates_fwd_ex(part, c_prev, h_prev, gates_all + (size_t)t * B * 4 * D,
-                                 cnew_all + (size_t)t * B * D, y_t,
-                                 drop_out ? mask_out + (size_t)t * B * D : nullptr, d->keep_out, lens, t,
-                                 cs + (size_t)(t + 1) * B * D, hs + (size_t)(t + 1) * B * D, B, D,
-                                 xh_n ? xh_n + EA : nullptr, Wd, S1, p->b, st));
+    int S = 1;
+    if (pl.fused)
+      return comic_lstm_step_fused(v.xh, Wd, L.kpanel_f, p->b, v.c_prev, v.h_prev, v.gates, v.cnew, v.y, v.mask_out, d->keep_out,
+                                   io.lens, t, v.c_next, v.h_next, v.xh_next_h, Wd, B, D, Wd, st);
+    if (cell == COMIC_CELL_GRU) {                // gates_all[t]: r | u | candidate | -
+      RC(comic_gemm_f32_partial(v.xh, p->K, B, 2 * D, Wd, Wd, 2 * D, 0, part, kSplitKBytes, &S, st));
+      RC(comic_gru_gates_fwd(part, S, p->b, v.h_prev, v.xh, Wd, v.gates, 4 * D, v.xh2, Wd, B, D, EA, st));
+      RC(comic_gemm_f32_partial(v.xh2, p->K_c, B, D, Wd, Wd, D, 0, part, kSplitKBytes, &S, st));
+      return comic_gru_out_fwd(part, S, p->b_c, v.gates, 4 * D, v.h_prev, v.gates + 2 * D, 4 * D, v.y, v.mask_out, d->keep_out,
+                               io.lens, t, v.h_next, v.xh_next_h, Wd, B, D, st);
     }
-    float* q_t = q_all + (size_t)t * B * D;
-    RC(comic_gemm_f32_partial(y_t, p->W_q, B, D, D, D, D, 0, part, kSplitKBytes, &S2, st));
-    float* ctx_t = ctx_all + (size_t)t * B * Cv;
-    const float* mal = drop_al ? mask_alpha + (size_t)t * B * H * M : nullptr;
-    if (!d->context_layer) {
-      RC(comic_attn_fwd_ex(&ad, keys, values, part, p->ln_g, p->ln_b, p->v, p->tau, mal, d->keep_alpha,
-                           alpha_all + (size_t)t * B * H * M, attn_hist + (size_t)t * B * H * M, ctx_t, lens, t,
-                           att_prev, att_next, xh_n ? xh_n + E : nullptr, Wd, mask_n, EA, d->keep_in, S2, q_t, attn_ws, st));
-    } else {
-      RC(comic_attn_fwd_ex(&ad, keys, values, part, p->ln_g, p->ln_b, p->v, p->tau, mal, d->keep_alpha,
-                           alpha_all + (size_t)t * B * H * M, attn_hist + (size_t)t * B * H * M, ctx_t, nullptr, 0,
-                           nullptr, nullptr, nullptr, 0, nullptr, 0, 1.f, S2, q_t, attn_ws, st));
-      RC(gemm(ctx_t, p->W_a, att_new, nullptr, B, D, Cv, Cv, D, D, 0, 0, 0.f, st));
-      hipLaunchKernelGGL(select_att_kernel, dim3(cdiv(B * A, 256)), dim3(256), 0, st, att_prev, att_new, lens, t,
-                         att_next, xh_n ? xh_n + E : nullptr, Wd, mask_n, EA, d->keep_in, B, A);
-      COMIC_LAUNCH_CHECK("select_att");
-    }
+    RC(comic_gemm_f32_partial(v.xh, p->K, B, 4 * D, Wd, Wd, 4 * D, 0, part, kSplitKBytes, &S, st));
+    if (cell == COMIC_CELL_LN_LSTM)
+      return comic_ln_lstm_fwd(part, S, p->cell_ln, v.c_prev, v.h_prev, v.gates, v.lnx, v.lnr, v.cnew, v.y, v.mask_out,
+                               d->keep_out, io.lens, t, v.c_next, v.h_next, B, D, v.xh_next_h, Wd, st);
+    return comic_lstm_gates_fwd_ex(part, v.c_prev, v.h_prev, v.gates, v.cnew, v.y, v.mask_out, d->keep_out, io.lens, t, v.c_next,
+                                   v.h_next, B, D, v.xh_next_h, Wd, S, p->b, st);
   }
-  if (sc) {      // per-token log-likelihoods instead of logits / loss / backward; a timed-out loop turns them into NaN
-    if (!score_stream)
-      RC(gemm_big(y_all, p->W_o, comic_score_logits_buffer(score_ws), p->b_o, Tp * B, V, D, D, V, V, 0, 0, 0.f, st));
-    RC(comic_score_logits(y_all, p->W_o, p->b_o, targets_bt, wmask_bt, lens, persist ? persist_sync : nullptr, B, T, Tp, D, V,
-                          score_stream ? 1 : 0, sc->token_logp_tb, sc->caption_logp, score_ws, score_ws_bytes, st));
+  // ... or per step: cell, query product (split-K partials), attention (+ the context layer)
+  int forward_steps() {
+    float* part = (float*)g_splitk_ws;
+    for (int t = 0; t < Tp; ++t) {
+      const StepView v = view(t);
+      int S2 = 1;
+      RC(cell_fwd(v, t));
+      RC(comic_gemm_f32_partial(v.y, p->W_q, B, D, D, D, D, 0, part, kSplitKBytes, &S2, st));
+      if (!d->context_layer) {
+        RC(comic_attn_fwd_ex(&pl.ad, L.keys, pl.values, part, p->ln_g, p->ln_b, p->v, p->tau, v.mask_alpha, d->keep_alpha, v.alpha,
+                             v.hist, v.ctx, io.lens, t, v.att_prev, v.att_next, v.xh_next_att, Wd, v.mask_att_next, EA,
+                             d->keep_in, S2, v.q, pl.attn_ws, st));
+      } else {
+        RC(comic_attn_fwd_ex(&pl.ad, L.keys, pl.values, part, p->ln_g, p->ln_b, p->v, p->tau, v.mask_alpha, d->keep_alpha, v.alpha,
+                             v.hist, v.ctx, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, 1.f, S2, v.q, pl.attn_ws, st));
+        RC(gemm(v.ctx, p->W_a, L.att_new, nullptr, B, D, Cv, Cv, D, D, 0, 0, 0.f, st));
+        hipLaunchKernelGGL(select_att_kernel, dim3(cdiv(B * A, 256)), dim3(256), 0, st, v.att_prev, (const float*)L.att_new,
+                           io.lens, t, v.att_next, v.xh_next_att, Wd, v.mask_att_next, EA, d->keep_in, B, A);
+        COMIC_LAUNCH_CHECK("select_att");
+      }
+    }
+    return 0;
+  }
+
+  // ---- scoring tail: per-token log-likelihoods instead of logits / loss / backward; a timed-out loop turns them into NaN
+  int score_tail() {
+    if (!pl.score_stream)
+      RC(gemm_big(L.y_all, p->W_o, comic_score_logits_buffer(L.score_ws), p->b_o, Tp * B, V, D, D, V, V, 0, 0, 0.f, st));
+    RC(comic_score_logits(L.y_all, p->W_o, p->b_o, io.targets_bt, io.wmask_bt, io.lens, pl.persist ? L.persist_sync : nullptr, B,
+                          T, Tp, D, V, pl.score_stream ? 1 : 0, io.token_logp_tb, io.caption_logp, L.score_ws, L.score_ws_bytes,
+                          st));
     COMIC_LAUNCH_CHECK("score");
     return 0;
   }
-  // output projection for all executed steps, loss, d logits
-  if (grp) {
+
+  // ---- output projection for all executed steps
+  int logits() {
+    if (!pl.grp) return gemm_big(L.y_all, p->W_o, io.logits_tb, p->b_o, Tp * B, V, D, D, V, V, 0, 0, 0.f, st);
     GemmGroupRun go;
-    go.add(COMIC_GG_NN, y_all, wo_g, logits_tb, Tp * B, V, D, D, ldl, V)->bias = p->b_o;
-    RC(go.run(gg_slab, gg_slab_cap, gg_tickets, st));
-  } else {
-    RC(gemm_big(y_all, p->W_o, logits_tb, p->b_o, Tp * B, V, D, D, V, V, 0, 0, 0.f, st));
-  }
-  }   // do_fwd
-  if (!do_bwd) {
-    COMIC_LAUNCH_CHECK("train_step (forward phase)");
-    return 0;
-  }
-  if (grp) {       // sequence loss + attention-map loss: one launch (d logits rows are ldl floats apart)
-    const int nparts = (int)cdiv64((long)Tp * B * M, 256);
-    COMIC_REQUIRE(nparts <= B * Wd, "train_step: map-loss scratch too small");
-    RC(comic_xent_maploss(logits_tb, targets_bt, coef_bt, wmask_bt, lens, loss_rows, dlogits, ldl, ids_tb, Tp, T, B, V, attn_hist,
-                          dmap, dxh /* free until the backward loop */, map_loss, gg_tickets + kGroupTickets - 1, H, M,
-                          d->map_loss_scale, st));
-  } else {
-    RC(comic_xent_ex(logits_tb, targets_bt, coef_bt, wmask_bt, lens, loss_rows, dlogits, ids_tb, Tp, T, B, V, st));
-  }
-  for (int t = Tp; t < T; ++t) {  // ops_rnn.py:235-241: pad by copying the last executed step
-    (void)hipMemcpyAsync(logits_tb + (size_t)t * B * V, logits_tb + (size_t)(Tp - 1) * B * V, sizeof(float) * B * V,
-                         hipMemcpyDeviceToDevice, st);
-    (void)hipMemcpyAsync(ids_tb + (size_t)t * B, ids_tb + (size_t)(Tp - 1) * B, sizeof(int32_t) * B,
-                         hipMemcpyDeviceToDevice, st);
-    RC(fill(loss_rows + (size_t)t * B, 0.f, B, st));
-  }
-  if (!grp) {
-    const long n = (long)Tp * B * M;
-    const int nparts = (int)cdiv64(n, 256);
-    float* partial = dxh;  // free until the backward loop; needs nparts floats
-    COMIC_REQUIRE(nparts <= B * Wd, "train_step: map-loss scratch too small");
-    hipLaunchKernelGGL(maploss_part_kernel, dim3(nparts), dim3(256), 0, st, attn_hist, dmap, partial, Tp, B, H, M,
-                       d->map_loss_scale);
-    hipLaunchKernelGGL(maploss_final_kernel, dim3(1), dim3(256), 0, st, partial, nparts, n, d->map_loss_scale,
-                       map_loss);
-    COMIC_LAUNCH_CHECK("maploss");
+    go.add(COMIC_GG_NN, L.y_all, pl.wo_g, io.logits_tb, Tp * B, V, D, D, pl.ldl, V)->bias = p->b_o;
+    return go.run(L.gg_slab(), L.gg_slab_cap(), L.gg_tickets(), st);
   }
 
-  // ------------------------------------------------------------------ backward -----------
-  const bool use_map = d->map_loss_scale > 0.f;
-  const bool sep_values = d->fm_projection != 2;
-  float* dvalues = sep_values ? dvalues_buf : dkeys;
-  if (!persist_b) {
-    RC(fill(dkeys, 0.f, (long)B * M * D, st));
-    if (sep_values) RC(fill(dvalues_buf, 0.f, (long)B * M * Cv, st));
-    RC(fill(dc, 0.f, (long)((datt + (long)B * A) - dc), st));    // dc | dh | datt: consecutive workspace blocks
+  // ---- sequence loss + d logits, attention-map loss, padding of the steps past Tp
+  int loss_and_padding() {
+    const long n = (long)Tp * B * M;
+    const int nparts = (int)cdiv64(n, 256);               // partial sums of the map loss
+    if (pl.grp) {       // both losses in one launch (d logits rows are ldl floats apart)
+      COMIC_REQUIRE(nparts <= L.maploss_partials_cap(), "train_step: map-loss scratch too small");
+      RC(comic_xent_maploss(io.logits_tb, io.targets_bt, io.coef_bt, io.wmask_bt, io.lens, io.loss_rows, L.dlogits, pl.ldl,
+                            io.ids_tb, Tp, T, B, V, pl.attn_hist, L.dmap, L.maploss_partials(), io.map_loss, L.loss_ticket(), H, M,
+                            d->map_loss_scale, st));
+    } else {
+      RC(comic_xent_ex(io.logits_tb, io.targets_bt, io.coef_bt, io.wmask_bt, io.lens, io.loss_rows, L.dlogits, io.ids_tb, Tp, T, B,
+                       V, st));
+    }
+    for (int t = Tp; t < T; ++t) {  // ops_rnn.py:235-241: pad by copying the last executed step
+      (void)hipMemcpyAsync(io.logits_tb + (size_t)t * B * V, io.logits_tb + (size_t)(Tp - 1) * B * V, sizeof(float) * B * V,
+                           hipMemcpyDeviceToDevice, st);
+      (void)hipMemcpyAsync(io.ids_tb + (size_t)t * B, io.ids_tb + (size_t)(Tp - 1) * B, sizeof(int32_t) * B,
+                           hipMemcpyDeviceToDevice, st);
+      RC(fill(io.loss_rows + (size_t)t * B, 0.f, B, st));
+    }
+    if (!pl.grp) {
+      float* partial = L.maploss_partials();
+      COMIC_REQUIRE(nparts <= L.maploss_partials_cap(), "train_step: map-loss scratch too small");
+      hipLaunchKernelGGL(maploss_part_kernel, dim3(nparts), dim3(256), 0, st, (const float*)pl.attn_hist, L.dmap, partial, Tp, B,
+                         H, M, d->map_loss_scale);
+      hipLaunchKernelGGL(maploss_final_kernel, dim3(1), dim3(256), 0, st, (const float*)partial, nparts, n, d->map_loss_scale,
+                         io.map_loss);
+      COMIC_LAUNCH_CHECK("maploss");
+    }
+    return 0;
   }
-  // dy_all = dlogits * W_o^T (d W_o, d b_o: after the loop, on the gradient lanes)
-  if (grp) {
-    GemmGroupRun gy;
-    gy.add(COMIC_GG_NT, dlogits, wo_g, dy_all, Tp * B, D, ldl, ldl, ldl, D);     // (K = padded columns: zeros on both sides)
-    RC(gy.run(gg_slab, gg_slab_cap, gg_tickets, st));
-  } else {
-    RC(gemm_big(dlogits, p->W_o, dy_all, nullptr, Tp * B, D, V, V, V, D, 0, 1, 0.f, st));
+
+  // ---- backward: zero-fills of the per-step form, dy_all = dlogits * W_o^T (d W_o, d b_o: with the weight gradients)
+  int backward_prepare() {
+    if (!pl.persist_b) {
+      RC(fill(L.dkeys, 0.f, (long)B * M * D, st));
+      if (d->fm_projection != 2) RC(fill(L.dvalues_buf, 0.f, (long)B * M * Cv, st));
+      RC(fill(L.state_grads(), 0.f, L.state_grads_floats(), st));
+    }
+    if (pl.grp) {
+      GemmGroupRun gy;
+      gy.add(COMIC_GG_NT, L.dlogits, pl.wo_g, L.dy_all, Tp * B, D, pl.ldl, pl.ldl, pl.ldl, D);     // (K = padded columns: zeros on both sides)
+      RC(gy.run(L.gg_slab(), L.gg_slab_cap(), L.gg_tickets(), st));
+    } else {
+      RC(gemm_big(L.dlogits, p->W_o, L.dy_all, nullptr, Tp * B, D, V, V, V, D, 0, 1, 0.f, st));
+    }
+    if (d->context_layer) RC(fill(gr->W_a, 0.f, (long)Cv * D, st));
+    return 0;
   }
-  if (d->context_layer) RC(fill(gr->W_a, 0.f, (long)Cv * D, st));
-  // softmax attention: the backward kernel runs as two workgroups per batch row (half of the memory rows each), whose
-  // d q / parameter-gradient contributions are added into zero-filled rows (comic_attn_bwd_ex, pgrad_overwrite 2)
-  const int attn_bwd_mode = (d->prob == 0 && split_attn_bwd_enabled()) ? 2 : 1;
-  if (persist_b) {
+
+  // ---- backward time loop, as persistent launches ...
+  int backward_persistent() {
     // M > 64: the loop ADDS its rows' d keys into memory step by step (one writer per address, in step order)
     const bool own_rows = (d->flags & COMIC_DEC_BWD_OWN_ROWS) != 0;
-    if (M > 64 || own_rows) RC(fill(dkeys, 0.f, (long)B * M * D, st));
+    if (M > 64 || own_rows) RC(fill(L.dkeys, 0.f, (long)B * M * D, st));
     ComicPersistBwdArgs pb{};
     pb.own_rows = own_rows ? 1 : 0;
-    pb.K = p->K; pb.W_q = p->W_q; pb.keys = keys;
-    pb.ln_g = p->ln_g; pb.ln_b = p->ln_b; pb.v = p->v; pb.tau = p->tau; pb.lens = lens;
-    pb.mask_in = drop_in ? mask_in : nullptr; pb.mask_out = drop_out ? mask_out : nullptr;
-    pb.mask_alpha = drop_al ? mask_alpha : nullptr;
+    pb.K = p->K; pb.W_q = p->W_q; pb.keys = L.keys;
+    pb.ln_g = p->ln_g; pb.ln_b = p->ln_b; pb.v = p->v; pb.tau = p->tau; pb.lens = io.lens;
+    pb.mask_in = pl.m_in; pb.mask_out = pl.m_out; pb.mask_alpha = pl.m_alpha;
     pb.keep_in = d->keep_in; pb.keep_out = d->keep_out; pb.keep_alpha = d->keep_alpha;
-    pb.q_all = q_all; pb.alpha_all = alpha_all; pb.gates_all = gates_all; pb.cs = cs; pb.cnew_all = cnew_all;
-    pb.dy_all = dy_all; pb.dmap = use_map ? dmap : nullptr;
-    pb.dq_part = dq_part; pb.dq_sum = dq_sum; pb.dg_blk = dg_blk; pb.dg_all = dg_all; pb.dstate = dstate;
-    pb.dotp = dotp;
-    pb.dq_all = dq_all; pb.dc = dc; pb.dh = dh; pb.dkeys = dkeys; pb.pgrad = pgrad4; pb.sync = persist_sync;
+    pb.q_all = L.q_all; pb.alpha_all = L.alpha_all; pb.gates_all = L.gates_all; pb.cs = L.cs; pb.cnew_all = L.cnew_all;
+    pb.dy_all = L.dy_all; pb.dmap = pl.use_map ? L.dmap : nullptr;
+    pb.dq_part = L.dq_part; pb.dq_sum = L.dq_sum; pb.dg_blk = L.dg_blk; pb.dg_all = L.dg_all; pb.dstate = L.dstate;
+    pb.dotp = L.dotp;
+    pb.dq_all = L.dq_all; pb.dc = L.dc; pb.dh = L.dh; pb.dkeys = L.dkeys; pb.pgrad = L.pgrad4; pb.sync = L.persist_sync;
     pb.B = B; pb.E = E; pb.M = M; pb.H = H; pb.Tp = Tp; pb.method = d->method;
-    const int n_grp = (B + 15) / 16;
-    for (int g0 = 0; g0 < n_grp; g0 += 4) {
-      pb.grp0 = g0;
-      pb.n_groups = std::min(4, n_grp - g0);
-      RC(comic_persist_bwd_launch(pb, st));
-    }
-  } else if (attn_bwd_mode == 2) {
-    RC(fill(dq_all, 0.f, (long)Tp * B * D, st));
-    RC(fill(pgrad, 0.f, (long)Tp * B * (3 * D + 1), st));
+    return launch_groups(pb, comic_persist_bwd_launch);
   }
-  for (int t = persist_b ? -1 : Tp - 1; t >= 0; --t) {
-    const float* ctx_t = ctx_all + (size_t)t * B * Cv;
-    float* dq_t = dq_all + (size_t)t * B * D;
-    const float* mal = drop_al ? mask_alpha + (size_t)t * B * H * M : nullptr;
-    int carry;
-    if (!d->context_layer) {
-      // attn_bwd masks d(att state) by "live" itself; input_bwd keeps the finished rows' share
-      RC(comic_attn_bwd_ex(&ad, keys, values, q_all + (size_t)t * B * D, p->ln_g, p->ln_b, p->v, p->tau,
-                           alpha_all + (size_t)t * B * H * M, mal, d->keep_alpha, datt,
-                           use_map ? dmap + (size_t)t * B * M : nullptr, dq_t, dkeys, dvalues,
-                           pgrad + (size_t)t * B * (3 * D + 1), lens, t, st, attn_bwd_mode, attn_ws,
-                           attn_ws ? attn_ws + (size_t)B * H * M : nullptr));
-      carry = 1;
-    } else {
-      hipLaunchKernelGGL(split_live_kernel, dim3(cdiv(B * A, 256)), dim3(256), 0, st, datt, datt_live, lens, t, B, A);
+
+  // d (attention state after step t) -> d q, d keys / values, parameter-gradient row; `carry` for the operand backward
+  int attention_bwd(const StepView& v, int t, int* carry) {
+    const bool cl = d->context_layer;
+    *carry = cl ? 0 : 1;
+    if (cl) {                   // the live rows' d(att state) through the context layer -> d ctx
+      hipLaunchKernelGGL(split_live_kernel, dim3(cdiv(B * A, 256)), dim3(256), 0, st, L.datt, L.datt_live, io.lens, t, B, A);
       COMIC_LAUNCH_CHECK("split_live");
-      RC(gemm(ctx_t, datt_live, gr->W_a, nullptr, Cv, D, B, Cv, D, D, 1, 0, 1.f, st));
-      RC(gemm(datt_live, p->W_a, dctx, nullptr, B, Cv, D, D, D, Cv, 0, 1, 0.f, st));
-      RC(comic_attn_bwd_ex(&ad, keys, values, q_all + (size_t)t * B * D, p->ln_g, p->ln_b, p->v, p->tau,
-                           alpha_all + (size_t)t * B * H * M, mal, d->keep_alpha, dctx,
-                           use_map ? dmap + (size_t)t * B * M : nullptr, dq_t, dkeys, dvalues,
-                           pgrad + (size_t)t * B * (3 * D + 1), nullptr, 0, st, attn_bwd_mode, attn_ws,
-                           attn_ws ? attn_ws + (size_t)B * H * M : nullptr));
-      carry = 0;
-    }
-    float* dy_t = dy_all + (size_t)t * B * D;
-    float* part = (float*)g_splitk_ws;
-    int S3 = 1, S4 = 1;
-    float* dg_t = dg_all + (size_t)t * B * 4 * D;
-    if (fused_q) {
-      RC(comic_lstm_grad_fused(dq_t, wq_panel, gates_all + (size_t)t * B * 4 * D, cs + (size_t)t * B * D,
-                               cnew_all + (size_t)t * B * D, dy_t, drop_out ? mask_out + (size_t)t * B * D : nullptr,
-                               d->keep_out, lens, t, dc, dh, dg_t, B, D, st));
-    } else if (cell == COMIC_CELL_LN_LSTM) {
-      RC(comic_gemm_f32_partial(dq_t, p->W_q, B, D, D, D, D, 1, part, kSplitKBytes, &S3, st));
-      RC(comic_ln_lstm_bwd(gates_all + (size_t)t * B * 4 * D, lnx_all + (size_t)t * B * 5 * D, lnr_all + (size_t)t * B * 8,
-                           p->cell_ln, cs + (size_t)t * B * D, cnew_all + (size_t)t * B * D, dy_t, part, S3,
-                           drop_out ? mask_out + (size_t)t * B * D : nullptr, d->keep_out, lens, t, dc, dh, dg_t,
-                           lnpg + (size_t)t * B * 10 * D, B, D, st));
-    } else if (cell == COMIC_CELL_GRU) {         // dg_t: d r_pre | d u_pre | d candidate_pre | -
-      const float* ga = gates_all + (size_t)t * B * 4 * D;
-      const float* h_prev = hs + (size_t)t * B * D;
-      float* slice1 = gru_dxh + (size_t)B * Wd;
-      RC(comic_gemm_f32_partial(dq_t, p->W_q, B, D, D, D, D, 1, part, kSplitKBytes, &S3, st));
-      RC(comic_gru_bwd1(dy_t, part, S3, drop_out ? mask_out + (size_t)t * B * D : nullptr, d->keep_out, lens, t, dh, ga, 4 * D,
-                        ga + 2 * D, 4 * D, h_prev, dg_t, 4 * D, B, D, st));
-      RC(gemm(dg_t + 2 * D, p->K_c, slice1, nullptr, B, Wd, D, 4 * D, D, Wd, 0, 1, 0.f, st));
-      RC(comic_gru_bwd2(slice1, Wd, ga, 4 * D, h_prev, dg_t, 4 * D, B, D, EA, st));
-      RC(gemm(dg_t, p->K, gru_dxh, nullptr, B, Wd, 2 * D, 4 * D, 2 * D, Wd, 0, 1, 0.f, st));
-      hipLaunchKernelGGL(input_bwd_kernel, dim3(cdiv(B * Wd, 256)), dim3(256), 0, st, gru_dxh,
-                         drop_in ? mask_in + (size_t)t * B * EA : nullptr, d->keep_in, demb + (size_t)t * B * E,
-                         datt, dh, lens, t, carry, B, E, A, D, 2);
-      COMIC_LAUNCH_CHECK("input_bwd");
-      continue;
-    } else {
-      RC(comic_gemm_f32_partial(dq_t, p->W_q, B, D, D, D, D, 1, part, kSplitKBytes, &S3, st));
-      RC(comic_lstm_gates_bwd_ex(gates_all + (size_t)t * B * 4 * D, cs + (size_t)t * B * D,
-                                 cnew_all + (size_t)t * B * D, dy_t, part, S3,
-                                 drop_out ? mask_out + (size_t)t * B * D : nullptr, d->keep_out, lens, t, dc, dh,
-                                 dg_t, B, D, st));
-    }
-    if (fused) {
-      RC(comic_input_grad_fused(dg_t, kpanel_b, drop_in ? mask_in + (size_t)t * B * EA : nullptr, d->keep_in,
-                                demb + (size_t)t * B * E, datt, dh, lens, t, carry, B, E, A, D, st));
-    } else {
-      RC(comic_gemm_f32_partial(dg_t, p->K, B, Wd, 4 * D, 4 * D, 4 * D, 1, part, kSplitKBytes, &S4, st));
-      hipLaunchKernelGGL(input_bwd_kernel, dim3(cdiv(B * Wd, 256)), dim3(256), 0, st, part,
-                         drop_in ? mask_in + (size_t)t * B * EA : nullptr, d->keep_in, demb + (size_t)t * B * E,
-                         datt, dh, lens, t, carry, B, E, A, D, S4);
-      COMIC_LAUNCH_CHECK("input_bwd");
-    }
+      RC(gemm(v.ctx, L.datt_live, gr->W_a, nullptr, Cv, D, B, Cv, D, D, 1, 0, 1.f, st));
+      RC(gemm(L.datt_live, p->W_a, L.dctx, nullptr, B, Cv, D, D, D, Cv, 0, 1, 0.f, st));
+    }                           // else: attn_bwd masks d(att state) by "live" itself; input_bwd keeps the finished rows' share
+    return comic_attn_bwd_ex(&pl.ad, L.keys, pl.values, v.q, p->ln_g, p->ln_b, p->v, p->tau, v.alpha, v.mask_alpha, d->keep_alpha,
+                             cl ? L.dctx : L.datt, v.dmap, v.dq, L.dkeys, pl.dvalues, v.pgrad, cl ? nullptr : io.lens, cl ? 0 : t, st,
+                             pl.attn_bwd_mode, pl.attn_ws, L.attn_scratch_bwd(pl.attn_ws));
   }
-  // ---- gradients that do not feed the recurrence ---------------------------------------------------------------------
-  float* dx_im = nullptr;  // gradient w.r.t. (im_embed * W_init)
-  int n_init = 0;
-  if (grp) {
-    // ONE grouped launch: every weight gradient, the bias sums, the embedding third of d gates * K^T, d x_init
+  // ... or per step: attention backward, the cell's gates, d operand row -> d emb, d att, d h
+  int backward_steps() {
+    if (pl.attn_bwd_mode == 2) {
+      RC(fill(L.dq_all, 0.f, (long)Tp * B * D, st));
+      RC(fill(L.pgrad, 0.f, (long)Tp * B * (3 * D + 1), st));
+    }
+    float* part = (float*)g_splitk_ws;
+    for (int t = Tp - 1; t >= 0; --t) {
+      const StepView v = view(t);
+      int carry, S3 = 1, S4 = 1;
+      const float* dxh_t = part;                 // d operand row(s) of the step: S4 slices
+      RC(attention_bwd(v, t, &carry));
+      if (pl.fused_q) {
+        RC(comic_lstm_grad_fused(v.dq, L.wq_panel, v.gates, v.c_prev, v.cnew, v.dy, v.mask_out, d->keep_out, io.lens, t, L.dc,
+                                 L.dh, v.dg, B, D, st));
+      } else {
+        RC(comic_gemm_f32_partial(v.dq, p->W_q, B, D, D, D, D, 1, part, kSplitKBytes, &S3, st));
+        if (cell == COMIC_CELL_LN_LSTM) {
+          RC(comic_ln_lstm_bwd(v.gates, v.lnx, v.lnr, p->cell_ln, v.c_prev, v.cnew, v.dy, part, S3, v.mask_out, d->keep_out,
+                               io.lens, t, L.dc, L.dh, v.dg, v.lnpg, B, D, st));
+        } else if (cell == COMIC_CELL_GRU) {       // dg_t: d r_pre | d u_pre | d candidate_pre | -
+          float* slice1 = L.gru_dxh + (size_t)B * Wd;
+          RC(comic_gru_bwd1(v.dy, part, S3, v.mask_out, d->keep_out, io.lens, t, L.dh, v.gates, 4 * D, v.gates + 2 * D, 4 * D,
+                            v.h_prev, v.dg, 4 * D, B, D, st));
+          RC(gemm(v.dg + 2 * D, p->K_c, slice1, nullptr, B, Wd, D, 4 * D, D, Wd, 0, 1, 0.f, st));
+          RC(comic_gru_bwd2(slice1, Wd, v.gates, 4 * D, v.h_prev, v.dg, 4 * D, B, D, EA, st));
+          RC(gemm(v.dg, p->K, L.gru_dxh, nullptr, B, Wd, 2 * D, 4 * D, 2 * D, Wd, 0, 1, 0.f, st));
+          dxh_t = L.gru_dxh;                       // the two products are the two "split-K" slices input_bwd adds
+          S4 = 2;
+        } else {
+          RC(comic_lstm_gates_bwd_ex(v.gates, v.c_prev, v.cnew, v.dy, part, S3, v.mask_out, d->keep_out, io.lens, t, L.dc, L.dh,
+                                     v.dg, B, D, st));
+        }
+      }
+      if (pl.fused) {
+        RC(comic_input_grad_fused(v.dg, L.kpanel_b, v.mask_in, d->keep_in, v.demb, L.datt, L.dh, io.lens, t, carry, B, E, A, D, st));
+        continue;
+      }
+      if (cell != COMIC_CELL_GRU) RC(comic_gemm_f32_partial(v.dg, p->K, B, Wd, 4 * D, 4 * D, 4 * D, 1, part, kSplitKBytes, &S4, st));
+      hipLaunchKernelGGL(input_bwd_kernel, dim3(cdiv(B * Wd, 256)), dim3(256), 0, st, dxh_t, v.mask_in, d->keep_in, v.demb, L.datt,
+                         L.dh, io.lens, t, carry, B, E, A, D, S4);
+      COMIC_LAUNCH_CHECK("input_bwd");
+    }
+    return 0;
+  }
+
+  // ---- gradients that do not feed the recurrence, as ONE grouped launch: every weight gradient, the bias sums, the embedding
+  // third of d gates * K^T, d x_init (and a second launch for what depends on d x_init / accumulates into dfm)
+  int weight_grads_grouped() {
     const bool init_step = d->init_method != 1;
     const int rows_k = (Tp + (init_step ? 1 : 0)) * B;            // rows of the LSTM operand / d gates matrices
+    float* dg_init = L.dg_init(Tp);
     if (init_step)                                               // d gates of the init step -> row block Tp of dg_all
-      RC(comic_lstm_gates_bwd(ib.gates, nullptr, ib.c_new, nullptr, nullptr, 1.f, nullptr, 0, dc, dh, dg_init, B, D, (void*)st));
+      RC(comic_lstm_gates_bwd(L.ib.gates, nullptr, L.ib.c_new, nullptr, nullptr, 1.f, nullptr, 0, L.dc, L.dh, dg_init, B, D, (void*)st));
     GemmGroupRun g1, g2;
-    g1.add(COMIC_GG_TN, xh_all, dg_all, gr->K, Wd, 4 * D, rows_k, Wd, 4 * D, 4 * D);
-    g1.add(COMIC_GG_TN, fm, dkeys, gr->W_m, d->C, D, B * M, d->C, D, D);
-    if (d->fm_projection == 1) g1.add(COMIC_GG_TN, fm, dvalues_buf, gr->W_v, d->C, D, B * M, d->C, D, D);
-    if (persist_b) {   // the embedding third of d gates * K^T, all steps at once, and its input dropout
-      ComicGemmProb* q = g1.add(COMIC_GG_NT, dg_all, p->K, demb, Tp * B, E, 4 * D, 4 * D, 4 * D, E);
-      if (drop_in) { q->mask = mask_in; q->ld_mask = EA; q->keep = d->keep_in; }
+    g1.add(COMIC_GG_TN, L.xh_all, L.dg_all, gr->K, Wd, 4 * D, rows_k, Wd, 4 * D, 4 * D);
+    g1.add(COMIC_GG_TN, io.fm, L.dkeys, gr->W_m, d->C, D, B * M, d->C, D, D);
+    if (d->fm_projection == 1) g1.add(COMIC_GG_TN, io.fm, L.dvalues_buf, gr->W_v, d->C, D, B * M, d->C, D, D);
+    if (pl.persist_b) {   // the embedding third of d gates * K^T, all steps at once, and its input dropout
+      ComicGemmProb* q = g1.add(COMIC_GG_NT, L.dg_all, p->K, L.demb, Tp * B, E, 4 * D, 4 * D, 4 * D, E);
+      if (pl.drop_in) { q->mask = io.mask_in; q->ld_mask = EA; q->keep = d->keep_in; }
     }
-    g1.add(COMIC_GG_TN, y_all, dq_all, gr->W_q, D, D, Tp * B, D, D, D);
-    g1.add(COMIC_GG_TN, y_all, dlogits, gr->W_o, D, V, Tp * B, D, ldl, V);
-    if (dfm) g1.add(COMIC_GG_NT, dkeys, p->W_m, dfm, B * M, d->C, D, D, D, d->C);
-    g1.add_colsum(dg_all, gr->b, 4 * D, rows_k, 4 * D);
-    g1.add_colsum(dlogits, gr->b_o, V, Tp * B, ldl);
+    g1.add(COMIC_GG_TN, L.y_all, L.dq_all, gr->W_q, D, D, Tp * B, D, D, D);
+    g1.add(COMIC_GG_TN, L.y_all, L.dlogits, gr->W_o, D, V, Tp * B, D, pl.ldl, V);
+    if (io.dfm) g1.add(COMIC_GG_NT, L.dkeys, p->W_m, io.dfm, B * M, d->C, D, D, D, d->C);
+    g1.add_colsum(L.dg_all, gr->b, 4 * D, rows_k, 4 * D);
+    g1.add_colsum(L.dlogits, gr->b_o, V, Tp * B, pl.ldl);
     if (d->method == 0) {      // pgrad rows are [v | ln_g | ln_b | tau]: column sums over the rows
-      const float* pg = persist_b ? pgrad4 : pgrad;
-      const int pr = persist_b ? 4 * B : Tp * B, ldp = 3 * D + 1;
+      const float* pg = pl.persist_b ? L.pgrad4 : L.pgrad;
+      const int pr = pl.persist_b ? 4 * B : Tp * B, ldp = 3 * D + 1;
       g1.add_colsum(pg, gr->v, D, pr, ldp);
       g1.add_colsum(pg + D, gr->ln_g, D, pr, ldp);
       g1.add_colsum(pg + 2 * D, gr->ln_b, D, pr, ldp);
       g1.add_colsum(pg + 3 * D, gr->tau, 1, pr, ldp);
     }
+    GemmGroupRun& gi = init_step ? g2 : g1;                       // d W_init (d im_embed) waits for d x_init of the first launch
     if (init_step) {
-      ComicGemmProb* q = g1.add(COMIC_GG_NT, dg_init, p->K, dx_init, B, EA, 4 * D, 4 * D, 4 * D, EA);
-      if (drop_in) { q->mask = mask_init_in; q->ld_mask = EA; q->keep = d->keep_in; }
-      dx_im = dx_init;
-      n_init = EA;
-      g2.add(COMIC_GG_TN, im_embed, dx_im, gr->W_init, d->Cg, n_init, B, d->Cg, n_init, n_init);
-      if (dim_embed) g2.add(COMIC_GG_NT, dx_im, p->W_init, dim_embed, B, d->Cg, n_init, n_init, n_init, d->Cg);
-    } else {
-      dx_im = dh;
-      n_init = D;
-      g1.add(COMIC_GG_TN, im_embed, dx_im, gr->W_init, d->Cg, n_init, B, d->Cg, n_init, n_init);
-      if (dim_embed) g1.add(COMIC_GG_NT, dx_im, p->W_init, dim_embed, B, d->Cg, n_init, n_init, n_init, d->Cg);
+      ComicGemmProb* q = g1.add(COMIC_GG_NT, dg_init, p->K, L.dx_init, B, EA, 4 * D, 4 * D, 4 * D, EA);
+      if (pl.drop_in) { q->mask = io.mask_init_in; q->ld_mask = EA; q->keep = d->keep_in; }
     }
-    if (d->fm_projection == 1 && dfm) {
-      ComicGemmProb* q = g2.add(COMIC_GG_NT, dvalues_buf, p->W_v, dfm, B * M, d->C, D, D, D, d->C);
+    dx_im = init_step ? L.dx_init : L.dh;
+    n_init = init_step ? EA : D;
+    gi.add(COMIC_GG_TN, io.im_embed, dx_im, gr->W_init, d->Cg, n_init, B, d->Cg, n_init, n_init);
+    if (io.dim_embed) gi.add(COMIC_GG_NT, dx_im, p->W_init, io.dim_embed, B, d->Cg, n_init, n_init, n_init, d->Cg);
+    if (d->fm_projection == 1 && io.dfm) {
+      ComicGemmProb* q = g2.add(COMIC_GG_NT, L.dvalues_buf, p->W_v, io.dfm, B * M, d->C, D, D, D, d->C);
       q->beta = 1.f;
     }
-    RC(g1.run(gg_slab, gg_slab_cap, gg_tickets, st));
-    RC(comic_embed_bwd_set(in_tb, demb, gr->emb, Tp * B, E, V, st));
-    RC(g2.run(gg_slab, gg_slab_cap, gg_tickets, st));
-    if (d->fm_projection == 0 && dfm) RC(comic_axpy(dfm, dvalues_buf, 1.f, (int64_t)B * M * Cv, (void*)st));
-  } else {
-  // ---- gradients that do not feed the recurrence, on two lanes (side_lane) ------------------------------------------
-  LaneScope glane(L, st, splitk_ws_b);
-  RC(glane.rc);
-  hipStream_t sb = glane.lane();
-  // lane B: output projection, embedding, query layer, memory projections, attention parameters
-  RC(gemm_big(y_all, dlogits, gr->W_o, nullptr, D, V, Tp * B, D, V, V, 1, 0, 0.f, sb));
-  if (persist_b) {   // the embedding third of d gates * K^T, all steps at once, and its input dropout
-    RC(gemm_big(dg_all, p->K, demb, nullptr, Tp * B, E, 4 * D, 4 * D, 4 * D, E, 0, 1, 0.f, sb));
-    if (drop_in) RC(comic_dropout_rows(demb, mask_in, d->keep_in, (long)Tp * B, E, EA, sb));
+    RC(g1.run(L.gg_slab(), L.gg_slab_cap(), L.gg_tickets(), st));
+    RC(comic_embed_bwd_set(L.in_tb, L.demb, gr->emb, Tp * B, E, V, st));
+    RC(g2.run(L.gg_slab(), L.gg_slab_cap(), L.gg_tickets(), st));
+    if (d->fm_projection == 0 && io.dfm) RC(comic_axpy(io.dfm, L.dvalues_buf, 1.f, (int64_t)B * M * Cv, (void*)st));
+    return 0;
   }
-  RC(fill(gr->emb, 0.f, (long)V * E, sb));
-  RC(comic_embed_bwd(in_tb, demb, gr->emb, Tp * B, E, V, (void*)sb));
-  RC(gemm_big(y_all, dq_all, gr->W_q, nullptr, D, D, Tp * B, D, D, D, 1, 0, 0.f, sb));
-  RC(gemm_big(fm, dkeys, gr->W_m, nullptr, d->C, D, B * M, d->C, D, D, 1, 0, 0.f, sb));
-  if (dfm) RC(gemm_big(dkeys, p->W_m, dfm, nullptr, B * M, d->C, D, D, D, d->C, 0, 1, 0.f, sb));
-  if (d->fm_projection == 1) {
-    RC(gemm_big(fm, dvalues_buf, gr->W_v, nullptr, d->C, D, B * M, d->C, D, D, 1, 0, 0.f, sb));
-    if (dfm) RC(gemm_big(dvalues_buf, p->W_v, dfm, nullptr, B * M, d->C, D, D, D, d->C, 0, 1, 1.f, sb));
-  } else if (d->fm_projection == 0 && dfm) {
-    RC(comic_axpy(dfm, dvalues_buf, 1.f, (int64_t)B * M * Cv, (void*)sb));
+  // ---- ... or on two lanes (side_lane).  Lane B: output projection, embedding, query layer, memory projections, attention
+  // parameters; lane A (the caller's stream): output bias, cell kernel(s) and bias(es), then the rnn init
+  int weight_grads_lanes() {
+    LaneScope glane(pl.lane, st, L.splitk_b);
+    RC(glane.rc);
+    hipStream_t sb = glane.lane();
+    RC(gemm_big(L.y_all, L.dlogits, gr->W_o, nullptr, D, V, Tp * B, D, V, V, 1, 0, 0.f, sb));
+    if (pl.persist_b) {   // the embedding third of d gates * K^T, all steps at once, and its input dropout
+      RC(gemm_big(L.dg_all, p->K, L.demb, nullptr, Tp * B, E, 4 * D, 4 * D, 4 * D, E, 0, 1, 0.f, sb));
+      if (pl.drop_in) RC(comic_dropout_rows(L.demb, io.mask_in, d->keep_in, (long)Tp * B, E, EA, sb));
+    }
+    RC(fill(gr->emb, 0.f, (long)V * E, sb));
+    RC(comic_embed_bwd(L.in_tb, L.demb, gr->emb, Tp * B, E, V, (void*)sb));
+    RC(gemm_big(L.y_all, L.dq_all, gr->W_q, nullptr, D, D, Tp * B, D, D, D, 1, 0, 0.f, sb));
+    RC(gemm_big(io.fm, L.dkeys, gr->W_m, nullptr, d->C, D, B * M, d->C, D, D, 1, 0, 0.f, sb));
+    if (io.dfm) RC(gemm_big(L.dkeys, p->W_m, io.dfm, nullptr, B * M, d->C, D, D, D, d->C, 0, 1, 0.f, sb));
+    if (d->fm_projection == 1) {
+      RC(gemm_big(io.fm, L.dvalues_buf, gr->W_v, nullptr, d->C, D, B * M, d->C, D, D, 1, 0, 0.f, sb));
+      if (io.dfm) RC(gemm_big(L.dvalues_buf, p->W_v, io.dfm, nullptr, B * M, d->C, D, D, D, d->C, 0, 1, 1.f, sb));
+    } else if (d->fm_projection == 0 && io.dfm) {
+      RC(comic_axpy(io.dfm, L.dvalues_buf, 1.f, (int64_t)B * M * Cv, (void*)sb));
+    }
+    if (d->method == 0) {        // pgrad rows are [v | ln_g | ln_b | tau]: column sums over the batch, then scatter
+      float* tmp = L.pgrad_sum();
+      RC(comic_colsum_ws(pl.persist_b ? L.pgrad4 : L.pgrad, tmp, pl.persist_b ? 4 * B : Tp * B, 3 * D + 1, 0.f, (float*)g_splitk_ws, sb));
+      hipLaunchKernelGGL(scatter_pgrad_kernel, dim3(cdiv(D, 256)), dim3(256), 0, sb, (const float*)tmp, gr->v, gr->ln_g, gr->ln_b,
+                         gr->tau, D);
+    }
+    glane.main_ws();
+    RC(comic_colsum_ws(L.dlogits, gr->b_o, Tp * B, V, 0.f, (float*)g_splitk_ws, st));
+    if (cell == COMIC_CELL_GRU) {
+      RC(gemm_big(L.xh_all, L.dg_all, gr->K, nullptr, Wd, 2 * D, Tp * B, Wd, 4 * D, 2 * D, 1, 0, 0.f, st));
+      RC(gemm_big(L.xh2_all, L.dg_all + 2 * D, gr->K_c, nullptr, Wd, D, Tp * B, Wd, 4 * D, D, 1, 0, 0.f, st));
+      RC(comic_colsum_ws(L.dg_all, L.cell_tmp, Tp * B, 4 * D, 0.f, (float*)g_splitk_ws, st));
+      COMIC_REQUIRE(hipMemcpyAsync(gr->b, L.cell_tmp, sizeof(float) * 2 * D, hipMemcpyDeviceToDevice, st) == hipSuccess &&
+                        hipMemcpyAsync(gr->b_c, L.cell_tmp + 2 * D, sizeof(float) * D, hipMemcpyDeviceToDevice, st) == hipSuccess,
+                    "train_step: bias gradient copy");
+    } else {
+      RC(gemm_big(L.xh_all, L.dg_all, gr->K, nullptr, Wd, 4 * D, Tp * B, Wd, 4 * D, 4 * D, 1, 0, 0.f, st));
+      if (cell == COMIC_CELL_LSTM) RC(comic_colsum_ws(L.dg_all, gr->b, Tp * B, 4 * D, 0.f, (float*)g_splitk_ws, st));
+    }
+    RC(init_step_bwd());
+    if (cell == COMIC_CELL_LN_LSTM) {           // LayerNorm gains / shifts: column sums of the per-row gradient rows
+      const int rows = Tp * B + (d->init_method == 1 ? 0 : B);      // (the init step wrote its rows behind step Tp - 1's)
+      RC(comic_colsum_ws(L.lnpg, L.cell_tmp, rows, 10 * D, 0.f, (float*)g_splitk_ws, st));
+      RC(comic_ln_lstm_scatter(L.cell_tmp, gr->cell_ln, D, 0.f, st));
+    }
+    RC(gemm_big(io.im_embed, dx_im, gr->W_init, nullptr, d->Cg, n_init, B, d->Cg, n_init, n_init, 1, 0, 0.f, st));
+    if (io.dim_embed) RC(gemm(dx_im, p->W_init, io.dim_embed, nullptr, B, d->Cg, n_init, n_init, n_init, d->Cg, 0, 1, 0.f, st));
+    return glane.join();
   }
-  if (d->method == 0) {
-    // pgrad rows are [v | ln_g | ln_b | tau]: column sums over the batch, then scatter (g_tmp [B][4D] is free after
-    // the loops and holds 3D + 1 floats at any batch size)
-    float* tmp = g_tmp;
-    if (persist_b) RC(comic_colsum_ws(pgrad4, tmp, 4 * B, 3 * D + 1, 0.f, (float*)g_splitk_ws, sb));
-    else RC(comic_colsum_ws(pgrad, tmp, Tp * B, 3 * D + 1, 0.f, (float*)g_splitk_ws, sb));
-    hipLaunchKernelGGL(scatter_pgrad_kernel, dim3(cdiv(D, 256)), dim3(256), 0, sb, tmp, gr->v, gr->ln_g, gr->ln_b, gr->tau, D);
-  }
-  glane.main_ws();
-  // lane A: output bias, LSTM kernel and bias, then the rnn init (which accumulates into both)
-  RC(comic_colsum_ws(dlogits, gr->b_o, Tp * B, V, 0.f, (float*)g_splitk_ws, st));
-  if (cell == COMIC_CELL_GRU) {
-    RC(gemm_big(xh_all, dg_all, gr->K, nullptr, Wd, 2 * D, Tp * B, Wd, 4 * D, 2 * D, 1, 0, 0.f, st));
-    RC(gemm_big(xh2_all, dg_all + 2 * D, gr->K_c, nullptr, Wd, D, Tp * B, Wd, 4 * D, D, 1, 0, 0.f, st));
-    RC(comic_colsum_ws(dg_all, cell_tmp, Tp * B, 4 * D, 0.f, (float*)g_splitk_ws, st));
-    COMIC_REQUIRE(hipMemcpyAsync(gr->b, cell_tmp, sizeof(float) * 2 * D, hipMemcpyDeviceToDevice, st) == hipSuccess &&
-                      hipMemcpyAsync(gr->b_c, cell_tmp + 2 * D, sizeof(float) * D, hipMemcpyDeviceToDevice, st) == hipSuccess,
-                  "train_step: bias gradient copy");
-  } else {
-    RC(gemm_big(xh_all, dg_all, gr->K, nullptr, Wd, 4 * D, Tp * B, Wd, 4 * D, 4 * D, 1, 0, 0.f, st));
-    if (cell == COMIC_CELL_LSTM) RC(comic_colsum_ws(dg_all, gr->b, Tp * B, 4 * D, 0.f, (float*)g_splitk_ws, st));
-  }
-  if (d->init_method == 1) {
-    dx_im = dh;
+
+  // The rnn init step's backward (lane form; it accumulates into the cell's weight gradients): each cell's own launches
+  // leave the init step's d pre-activations in ib.g, one tail turns them into d x_init = drop'(ib.g * K^T) [B][E+A]
+  int init_step_bwd() {
+    const InitBufs& ib = L.ib;
+    dx_im = L.dh;
     n_init = D;
-  } else if (cell == COMIC_CELL_LN_LSTM) {
-    RC(comic_ln_lstm_bwd(ib.gates, ib.lnx, ib.lnr, p->cell_ln, nullptr, ib.c_new, nullptr, nullptr, 0, nullptr, 1.f, nullptr, 0,
-                         dc, dh, ib.g, lnpg + (size_t)Tp * B * 10 * D, B, D, st));
-    RC(gemm(ib.xh, ib.g, gr->K, nullptr, EA, 4 * D, B, EA, 4 * D, 4 * D, 1, 0, 1.f, st));
-    RC(gemm(ib.g, p->K, dx_init, nullptr, B, EA, 4 * D, 4 * D, 4 * D, EA, 0, 1, 0.f, st));
-    if (drop_in) RC(comic_dropout_apply(dx_init, mask_init_in, d->keep_in, dx_init, (int64_t)B * EA, (void*)st));
-    dx_im = dx_init;
+    if (d->init_method == 1) return 0;
+    if (cell == COMIC_CELL_LN_LSTM) {
+      RC(comic_ln_lstm_bwd(ib.gates, ib.lnx, ib.lnr, p->cell_ln, nullptr, ib.c_new, nullptr, nullptr, 0, nullptr, 1.f, nullptr, 0,
+                           L.dc, L.dh, ib.g, L.lnpg + (size_t)Tp * B * 10 * D, B, D, st));
+      RC(gemm(ib.xh, ib.g, gr->K, nullptr, EA, 4 * D, B, EA, 4 * D, 4 * D, 1, 0, 1.f, st));
+    } else if (cell == COMIC_CELL_GRU) {        // zero state: d r_pre = 0
+      RC(fill(ib.g, 0.f, (long)B * 4 * D, st));
+      RC(comic_gru_bwd1(nullptr, nullptr, 0, nullptr, 1.f, nullptr, 0, L.dh, ib.gates, 4 * D, ib.gates + 2 * D, 4 * D, nullptr,
+                        ib.g, 4 * D, B, D, st));
+      RC(gemm(ib.xh, ib.g, gr->K, nullptr, EA, 2 * D, B, EA, 4 * D, 2 * D, 1, 0, 1.f, st));
+      RC(gemm(ib.xh, ib.g + 2 * D, gr->K_c, nullptr, EA, D, B, EA, 4 * D, D, 1, 0, 1.f, st));
+      RC(comic_colsum(ib.g, L.cell_tmp, B, 4 * D, 0.f, (void*)st));
+      RC(comic_axpy(gr->b, L.cell_tmp, 1.f, 2 * D, (void*)st));
+      RC(comic_axpy(gr->b_c, L.cell_tmp + 2 * D, 1.f, D, (void*)st));
+    } else {
+      RC(comic_lstm_gates_bwd(ib.gates, nullptr, ib.c_new, nullptr, nullptr, 1.f, nullptr, 0, L.dc, L.dh, ib.g, B, D, (void*)st));
+      RC(gemm(ib.xh, ib.g, gr->K, nullptr, EA, 4 * D, B, EA, 4 * D, 4 * D, 1, 0, 1.f, st));
+      RC(comic_colsum(ib.g, gr->b, B, 4 * D, 1.f, (void*)st));
+    }
+    if (cell == COMIC_CELL_GRU) {               // the gates' and the candidate's kernels
+      RC(gemm(ib.g, p->K, L.dx_init, nullptr, B, EA, 2 * D, 4 * D, 2 * D, EA, 0, 1, 0.f, st));
+      RC(gemm(ib.g + 2 * D, p->K_c, L.dx_init, nullptr, B, EA, D, 4 * D, D, EA, 0, 1, 1.f, st));
+    } else {
+      RC(gemm(ib.g, p->K, L.dx_init, nullptr, B, EA, 4 * D, 4 * D, 4 * D, EA, 0, 1, 0.f, st));
+    }
+    if (pl.drop_in) RC(comic_dropout_apply(L.dx_init, io.mask_init_in, d->keep_in, L.dx_init, (int64_t)B * EA, (void*)st));
+    dx_im = L.dx_init;
     n_init = EA;
-  } else if (cell == COMIC_CELL_GRU) {        // zero state: d r_pre = 0
-    RC(fill(ib.g, 0.f, (long)B * 4 * D, st));
-    RC(comic_gru_bwd1(nullptr, nullptr, 0, nullptr, 1.f, nullptr, 0, dh, ib.gates, 4 * D, ib.gates + 2 * D, 4 * D, nullptr,
-                      ib.g, 4 * D, B, D, st));
-    RC(gemm(ib.xh, ib.g, gr->K, nullptr, EA, 2 * D, B, EA, 4 * D, 2 * D, 1, 0, 1.f, st));
-    RC(gemm(ib.xh, ib.g + 2 * D, gr->K_c, nullptr, EA, D, B, EA, 4 * D, D, 1, 0, 1.f, st));
-    RC(comic_colsum(ib.g, cell_tmp, B, 4 * D, 0.f, (void*)st));
-    RC(comic_axpy(gr->b, cell_tmp, 1.f, 2 * D, (void*)st));
-    RC(comic_axpy(gr->b_c, cell_tmp + 2 * D, 1.f, D, (void*)st));
-    RC(gemm(ib.g, p->K, dx_init, nullptr, B, EA, 2 * D, 4 * D, 2 * D, EA, 0, 1, 0.f, st));
-    RC(gemm(ib.g + 2 * D, p->K_c, dx_init, nullptr, B, EA, D, 4 * D, D, EA, 0, 1, 1.f, st));
-    if (drop_in) RC(comic_dropout_apply(dx_init, mask_init_in, d->keep_in, dx_init, (int64_t)B * EA, (void*)st));
-    dx_im = dx_init;
-    n_init = EA;
-  } else {
-    RC(comic_lstm_gates_bwd(ib.gates, nullptr, ib.c_new, nullptr, nullptr, 1.f, nullptr, 0, dc, dh, ib.g, B, D,
-                            (void*)st));
-    RC(gemm(ib.xh, ib.g, gr->K, nullptr, EA, 4 * D, B, EA, 4 * D, 4 * D, 1, 0, 1.f, st));
-    RC(comic_colsum(ib.g, gr->b, B, 4 * D, 1.f, (void*)st));
-    RC(gemm(ib.g, p->K, dx_init, nullptr, B, EA, 4 * D, 4 * D, 4 * D, EA, 0, 1, 0.f, st));
-    if (drop_in) RC(comic_dropout_apply(dx_init, mask_init_in, d->keep_in, dx_init, (int64_t)B * EA, (void*)st));
-    dx_im = dx_init;
-    n_init = EA;
+    return 0;
   }
-  if (cell == COMIC_CELL_LN_LSTM) {           // LayerNorm gains / shifts: column sums of the per-row gradient rows
-    const int rows = Tp * B + (d->init_method == 1 ? 0 : B);      // (the init step wrote its rows behind step Tp - 1's)
-    RC(comic_colsum_ws(lnpg, cell_tmp, rows, 10 * D, 0.f, (float*)g_splitk_ws, st));
-    RC(comic_ln_lstm_scatter(cell_tmp, gr->cell_ln, D, 0.f, st));
-  }
-  RC(gemm_big(im_embed, dx_im, gr->W_init, nullptr, d->Cg, n_init, B, d->Cg, n_init, n_init, 1, 0, 0.f, st));
-  if (dim_embed) RC(gemm(dx_im, p->W_init, dim_embed, nullptr, B, d->Cg, n_init, n_init, n_init, d->Cg, 0, 1, 0.f, st));
-  RC(glane.join());
-  }
-  if (persist) {
-    // a persistent loop that timed out leaves garbage everywhere: NaN losses and zero gradients (no host check needed
-    // for the optimiser step that follows to be harmless; the host raises at its next look at the loss)
+
+  // ---- end-of-step gate: a persistent loop that timed out leaves garbage everywhere -- NaN losses and zero gradients (no
+  // host check needed for the optimiser step that follows to be harmless; the host raises at its next look at the loss)
+  int gate() {
     ComicGateRanges gr_{};
     int k = 0;
     auto add = [&](float* ptr, long n) {
@@ -1522,13 +1546,61 @@ static int teacher_forced_step(const comic_decoder_desc* d, const comic_decoder_
     if (d->method == 0) { add(gr->v, D); add(gr->ln_g, D); add(gr->ln_b, D); add(gr->tau, 1); }
     if (d->context_layer) add(gr->W_a, (long)Cv * D);
     add(gr->W_o, (long)D * V); add(gr->b_o, V); add(gr->emb, (long)V * E);
-    add(dfm, (long)B * M * d->C); add(dim_embed, (long)B * d->Cg);
-    if (d->flags & COMIC_DEC_INJECT_TIMEOUT)     // fault injection of THIS call: raise the loops' error word by hand
-      COMIC_REQUIRE(hipMemsetAsync(persist_sync, 0xFF, sizeof(unsigned), st) == hipSuccess, "train_step: memset");
-    RC(comic_persist_gate(persist_sync, loss_rows, map_loss, gr_, gr->status, p->status, st));
+    add(io.dfm, (long)B * M * d->C); add(io.dim_embed, (long)B * d->Cg);
+    // COMIC_DEC_INJECT_TIMEOUT, fault injection for the tests of this gate: THIS call behaves as if one of its loops' bounded
+    // waits had expired (the error word raised by hand)
+    if (d->flags & COMIC_DEC_INJECT_TIMEOUT)
+      COMIC_REQUIRE(hipMemsetAsync(L.persist_sync, 0xFF, sizeof(unsigned), st) == hipSuccess, "train_step: memset");
+    return comic_persist_gate(L.persist_sync, io.loss_rows, io.map_loss, gr_, gr->status, p->status, st);
   }
-  COMIC_LAUNCH_CHECK("train_step");
-  return 0;
+
+  int run() {
+    RC(validate_and_plan());
+    if (pl.persist && pl.do_fwd) RC(prologue());
+    if (pl.do_fwd) {
+      RC(pl.grp ? forward_setup_grouped() : forward_setup_lanes());
+      RC(operand_rows());
+      RC(pl.persist ? forward_persistent() : forward_steps());
+      if (pl.score) return score_tail();
+      RC(logits());
+    }
+    if (!pl.do_bwd) {
+      COMIC_LAUNCH_CHECK("train_step (forward phase)");
+      return 0;
+    }
+    RC(loss_and_padding());
+    RC(backward_prepare());
+    RC(pl.persist_b ? backward_persistent() : backward_steps());
+    RC(pl.grp ? weight_grads_grouped() : weight_grads_lanes());
+    if (pl.persist) RC(gate());
+    COMIC_LAUNCH_CHECK("train_step");
+    return 0;
+  }
+};
+
+int teacher_forced_step(const comic_decoder_desc* d, const comic_decoder_params* p, const comic_decoder_params* gr,
+                        const StepIO& io, void* stream) {
+  RC(check_desc(d));
+  FlagScope flag_scope__(d);
+  TeacherForcedStep step{d, p, gr, io, (hipStream_t)stream};
+  return step.run();
+}
+
+// Scoring: dropout off, both phases' flags and the fault injection of the training step cleared
+comic_decoder_desc score_desc(const comic_decoder_desc* d) {
+  comic_decoder_desc s = *d;
+  s.keep_in = s.keep_out = s.keep_alpha = 1.f;
+  s.flags &= ~(uint32_t)(COMIC_DEC_PHASE_FWD | COMIC_DEC_PHASE_BWD | COMIC_DEC_INJECT_TIMEOUT);
+  return s;
+}
+
+}  // namespace
+
+extern "C" int64_t comic_decoder_train_workspace(const comic_decoder_desc* d, int B, int T) {
+  if (!d) return -1;
+  TrainLayout L;
+  L.carve(d, B, T, TF_TRAIN, false, nullptr, 0);
+  return (int64_t)L.bytes;
 }
 
 extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic_decoder_params* p,
@@ -1539,29 +1611,25 @@ extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic
                                         const float* mask_alpha, float* logits_tb, int32_t* ids_tb, float* attn_hist,
                                         float* loss_rows, float* map_loss, float* dfm, float* dim_embed,
                                         void* workspace, int64_t workspace_bytes, void* stream) {
-  return teacher_forced_step(d, p, gr, fm, im_embed, inputs_bt, targets_bt, wmask_bt, coef_bt, lens, B, T, Tp, mask_init_in,
-                             mask_in, mask_out, mask_alpha, logits_tb, ids_tb, attn_hist, loss_rows, map_loss, dfm, dim_embed,
-                             workspace, workspace_bytes, stream, nullptr);
+  StepIO io{};
+  io.fm = fm; io.im_embed = im_embed; io.inputs_bt = inputs_bt; io.targets_bt = targets_bt; io.wmask_bt = wmask_bt;
+  io.coef_bt = coef_bt; io.lens = lens; io.B = B; io.T = T; io.Tp = Tp;
+  io.mask_init_in = mask_init_in; io.mask_in = mask_in; io.mask_out = mask_out; io.mask_alpha = mask_alpha;
+  io.logits_tb = logits_tb; io.ids_tb = ids_tb; io.attn_hist = attn_hist; io.loss_rows = loss_rows; io.map_loss = map_loss;
+  io.dfm = dfm; io.dim_embed = dim_embed; io.workspace = workspace; io.workspace_bytes = workspace_bytes;
+  return teacher_forced_step(d, p, gr, io, stream);
 }
 
-// Scoring: dropout off, both phases' flags and the fault injection of the training step cleared
-static comic_decoder_desc score_desc(const comic_decoder_desc* d) {
-  comic_decoder_desc s = *d;
-  s.keep_in = s.keep_out = s.keep_alpha = 1.f;
-  s.flags &= ~(uint32_t)(COMIC_DEC_PHASE_FWD | COMIC_DEC_PHASE_BWD | COMIC_DEC_INJECT_TIMEOUT);
-  return s;
-}
-
+// the scoring layout (the caller takes no alignment history: the workspace holds it), with the flags that select the
+// projection's form latched as in the call itself
 extern "C" int64_t comic_decoder_score_workspace(const comic_decoder_desc* d, int B, int T) {
   if (!d || B <= 0 || T <= 0) return -1;
   const comic_decoder_desc s = score_desc(d);
-  int64_t n = 0;
-  ScoreRequest sc{nullptr, nullptr, &n};
-  if (teacher_forced_step(&s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, T, nullptr,
-                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                          nullptr, &sc))
-    return -1;
-  return n;
+  if (check_desc(&s)) return -1;
+  FlagScope flag_scope__(&s);
+  TrainLayout L;
+  L.carve(&s, B, T, TF_SCORE, true, nullptr, 0);
+  return (int64_t)L.bytes;
 }
 
 extern "C" int comic_decoder_score(const comic_decoder_desc* d, const comic_decoder_params* p, const float* fm,
@@ -1571,48 +1639,20 @@ extern "C" int comic_decoder_score(const comic_decoder_desc* d, const comic_deco
                                    void* stream) {
   COMIC_REQUIRE(d, "score: null descriptor");
   const comic_decoder_desc s = score_desc(d);
-  ScoreRequest sc{token_logp_tb, caption_logp, nullptr};
-  return teacher_forced_step(&s, p, nullptr, fm, im_embed, inputs_bt, targets_bt, wmask_bt, nullptr, lens, B, T, Tp, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, nullptr, attn_hist, nullptr, nullptr, nullptr, nullptr, workspace,
-                             workspace_bytes, stream, &sc);
+  StepIO io{};
+  io.fm = fm; io.im_embed = im_embed; io.inputs_bt = inputs_bt; io.targets_bt = targets_bt; io.wmask_bt = wmask_bt;
+  io.lens = lens; io.B = B; io.T = T; io.Tp = Tp; io.attn_hist = attn_hist;
+  io.score = true; io.token_logp_tb = token_logp_tb; io.caption_logp = caption_logp; io.workspace = workspace; io.workspace_bytes = workspace_bytes;
+  return teacher_forced_step(&s, p, nullptr, io, stream);
 }
 
 // columns of the W_o scratch: V rounded up to whole chunks of any of its packed forms (128, 112 or 64 columns)
 static inline long wo_pad_cols(long V) { return (V + 127) / 128 * 128 + 128; }
 constexpr int kBeamCntSteps = 4096;       // decode steps the in-kernel completion counters of the beam step cover
 
-extern "C" int64_t comic_decoder_infer_workspace(const comic_decoder_desc* d, int rows, int max_steps) {
-  if (!d) return -1;
-  Bump w(nullptr, 0);
-  const long D = d->D, E = d->E, A = d->A, V = d->V, M = d->M, H = d->H, Cv = d->Cv, Wd = E + A + D, R = rows;
-  w.take<float>(R * M * d->C); w.take<float>(R * d->Cg);           // tiled fm, im_embed
-  w.take<float>(R * M * D); w.take<float>(R * M * D);              // keys, values
-  w.take<float>(R * (E + A)); w.take<float>(R * (E + A)); w.take<float>(R * 4 * D); w.take<float>(R * 4 * D);
-  w.take<float>(R * D);                                            // init bufs
-  w.take<float>(R * Wd); w.take<float>(R * 4 * D); w.take<float>(R * D); w.take<float>(R * D);  // xh,g,y,q
-  w.take<float>(R * H * M); w.take<float>(R * Cv);                 // alpha, ctx
-  for (int i = 0; i < 4; ++i) w.take<float>(R * D);                // c,h ping-pong
-  w.take<float>(R * D);                                            // att2 (context layer)
-  for (int i = 0; i < 2; ++i) w.take<float>(R * A);                // att ping-pong
-  w.take<float>(R * E); w.take<float>(R * V);                      // x, logits
-  w.take<int32_t>(R); w.take<float>(R); w.take<int32_t>(R);        // ids, log_probs, parents
-  w.take<float>(R * (2 * D + A));                                  // gather temp
-  w.take<char>(kSplitKBytes);                                      // split-K partials
-  w.take<float>(comic_lstm_panel_floats(d->D, d->E + d->A + d->D, 0));  // LSTM kernel panel (fused step)
-  w.take<float>((D + 1) * wo_pad_cols(V));                         // W_o with 16-byte aligned rows / packed hi-lo fragments + bias
-  w.take<float>(comic_lstm_stream_kfrag_floats(d->D, (int)Wd)); w.take<float>(comic_lstm_stream_xfrag_floats(rows, (int)Wd));  // streaming LSTM step
-  w.take<float>(comic_stream_gemm_wfrag_floats(d->D, d->D)); w.take<float>(comic_lstm_stream_xfrag_floats(rows, d->D));     // ... W_q, y fragments
-  w.take<unsigned long long>(kBeamCntSteps);                       // beam search: per-step completion counters
-  if (d->cell == COMIC_CELL_GRU) w.take<float>(R * Wd);            // GRU: [x ; att ; r*h]
-  if (rows <= 64) {                                                // persistent greedy loop: hand-off buffers of all steps
-    const long S = std::max(1, max_steps);
-    w.take<float>(S * R * Wd); w.take<float>(S * R * D); w.take<float>(S * R * D); w.take<float>(S * R * 132);
-    w.take<unsigned>(kPersistSyncWords);
-  }
-  return (int64_t)w.off;
-}
-
 namespace {
+// Workspace of the decode loops.  carve_infer is the ONE definition of its blocks: comic_decoder_infer_workspace runs it over a
+// null base, greedy / sampling / beam search over the caller's buffer.
 struct InferBufs {
   float *fm_t, *im_t, *keys, *values_buf;
   InitBufs ib;
@@ -1622,9 +1662,12 @@ struct InferBufs {
   int32_t *ids, *parents;
   float *p_xh = nullptr, *p_y = nullptr, *p_q = nullptr, *p_argp = nullptr;   // persistent greedy loop (rows <= 64)
   unsigned* p_sync = nullptr;
+  void* splitk;              // split-K partials (the executor points g_splitk_ws at it)
+  size_t bytes;
   bool ok;
 };
-InferBufs carve_infer(const comic_decoder_desc* d, int rows, void* ws, int64_t bytes, int max_steps = 0) {
+// max_steps > 0: the hand-off buffers of the persistent greedy loop (rows <= 64), [max_steps] rows each, behind everything else
+InferBufs carve_infer(const comic_decoder_desc* d, int rows, void* ws, int64_t bytes, int max_steps) {
   Bump w(ws, (size_t)bytes);
   const long D = d->D, E = d->E, A = d->A, V = d->V, M = d->M, H = d->H, Cv = d->Cv, Wd = E + A + D, R = rows;
   InferBufs b;
@@ -1641,9 +1684,9 @@ InferBufs carve_infer(const comic_decoder_desc* d, int rows, void* ws, int64_t b
   b.x = w.take<float>(R * E); b.logits = w.take<float>(R * V);
   b.ids = w.take<int32_t>(R); b.log_probs = w.take<float>(R); b.parents = w.take<int32_t>(R);
   b.gtmp = w.take<float>(R * (2 * D + A));
-  g_splitk_ws = w.take<char>(kSplitKBytes);
+  b.splitk = w.take<char>(kSplitKBytes);
   b.kpanel = w.take<float>(comic_lstm_panel_floats(d->D, d->E + d->A + d->D, 0));
-  b.wo_pad = w.take<float>((D + 1) * wo_pad_cols(V));
+  b.wo_pad = w.take<float>((D + 1) * wo_pad_cols(V));      // W_o with 16-byte aligned rows / packed hi-lo fragments + bias
   b.kfrag = w.take<float>(comic_lstm_stream_kfrag_floats(d->D, (int)Wd)); b.xfrag = w.take<float>(comic_lstm_stream_xfrag_floats(rows, (int)Wd));
   b.wqfrag = w.take<float>(comic_stream_gemm_wfrag_floats(d->D, d->D)); b.yfrag = w.take<float>(comic_lstm_stream_xfrag_floats(rows, d->D));
   b.beam_cnt = w.take<unsigned long long>(kBeamCntSteps);
@@ -1654,6 +1697,7 @@ InferBufs carve_infer(const comic_decoder_desc* d, int rows, void* ws, int64_t b
     b.p_argp = w.take<float>(S * R * 132);
     b.p_sync = w.take<unsigned>(kPersistSyncWords);
   }
+  b.bytes = w.off;
   b.ok = w.ok;
   return b;
 }
@@ -1676,6 +1720,13 @@ const float* aligned_w_o(const comic_decoder_desc* d, const comic_decoder_params
 }
 }  // namespace
 
+// The size covers the greedy loop's hand-off buffers whenever rows <= 64, for one step at the least: beam search asks with
+// the same entry and carves without them (max_steps 0), its blocks sit in front of them.
+extern "C" int64_t comic_decoder_infer_workspace(const comic_decoder_desc* d, int rows, int max_steps) {
+  if (!d) return -1;
+  return (int64_t)carve_infer(d, rows, nullptr, 0, std::max(1, max_steps)).bytes;
+}
+
 int comic_argmax_rows_noise(const float* x, const float* noise, int32_t* idx, int rows, int V, hipStream_t st);
 
 // greedy (gumbel_tb null) or sampled (gumbel_tb [max_steps][B][V]: ids = argmax(logits + noise)) decode loop
@@ -1691,6 +1742,7 @@ static int decoder_search(const comic_decoder_desc* d, const comic_decoder_param
   hipStream_t st = (hipStream_t)stream;
   InferBufs ws = carve_infer(d, B, workspace, workspace_bytes, max_steps);
   COMIC_REQUIRE(ws.ok, "greedy: workspace overflow");
+  g_splitk_ws = ws.splitk;
   const int D = d->D, E = d->E, A = d->A, V = d->V, M = d->M, H = d->H, Cv = d->Cv;
   const comic_attn_desc ad = attn_desc(d, B);
   const float* values = nullptr;
@@ -1777,7 +1829,6 @@ static int decoder_search(const comic_decoder_desc* d, const comic_decoder_param
                        d->end_id, B, steps_done, max_steps);
     COMIC_LAUNCH_CHECK("eos_track");
   }
-  (void)Cv; (void)M;
   return 0;
 }
 
@@ -1857,8 +1908,9 @@ extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decod
   const int R = B * W;
   COMIC_REQUIRE(workspace_bytes >= comic_decoder_infer_workspace(d, R, max_steps), "beam: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  InferBufs ws = carve_infer(d, R, workspace, workspace_bytes);
+  InferBufs ws = carve_infer(d, R, workspace, workspace_bytes, 0);
   COMIC_REQUIRE(ws.ok, "beam: workspace overflow");
+  g_splitk_ws = ws.splitk;
   const int D = d->D, E = d->E, A = d->A, V = d->V, M = d->M, H = d->H;
   // tile_batch BEFORE keys are computed (model_base.py:127-131).  The beams of an entry attend to the same memory: the
   // fused step's attention kernel reads row b / W of keys / values held ONCE per entry (same values as the tiled copy's)
