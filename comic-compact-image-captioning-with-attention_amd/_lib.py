@@ -177,6 +177,11 @@ _SIGS = {
     'comic_decoder_greedy': (c_int, [P, P, P, P, c_int, c_int, P, P, P, P, P, c_int64, P]),
     'comic_decoder_sample': (c_int, [P, P, P, P, c_int, c_int, P, P, P, P, P, P, c_int64, P]),
     'comic_decoder_beam': (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int64, P]),
+    'comic_beam_step_ensemble_workspace': (c_int64, [c_int, c_int, c_int, c_int]),
+    'comic_beam_step_ensemble': (c_int, [P, P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, c_int64, P]),
+    'comic_beam_step_ensemble_path': (c_int, []),
+    'comic_decoder_beam_ensemble_workspace': (c_int64, [P, c_int, c_int, c_int]),
+    'comic_decoder_beam_ensemble': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int64, P]),
     'comic_scorer_create': (c_void_p, [c_char_p, P, c_int64, c_double]),
     'comic_scorer_destroy': (None, [c_void_p]),
     'comic_scorer_score': (c_int, [c_void_p, P, c_int, P, P, P, P, c_int]),

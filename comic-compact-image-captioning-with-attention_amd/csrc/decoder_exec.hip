@@ -2095,3 +2095,187 @@ extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decod
   }
   return 0;
 }
+
+// ---- ensemble beam search: several members, one beam ------------------------------------------------------------------------
+// rnn_decoder_beam_search (ops_rnn.py:49-112) over the MEAN of the members' step distributions.  An executor of its own
+// beside comic_decoder_beam: that loop picks one of three fused projection + top-k launches per shape, each of which owns a
+// single member's W_o; here every member runs its own wrapper step on its own InferBufs, writes its logits into one slab,
+// and one ensemble step (beam_ensemble.hip) ranks the candidates for all of them.  Members follow the SAME ids / parents.
+int comic_ens_gather_state(const float* c, const float* h, const float* att, const int32_t* parent, float* c_out,
+                           float* h_out, float* att_out, int R, int W, int D, int A, hipStream_t st);
+
+namespace {
+constexpr int kEnsMembers = 8;
+// Workspace of the ensemble loop: the members' InferBufs one after another, then the shared blocks.  carve_ens is the ONE
+// definition: comic_decoder_beam_ensemble_workspace runs it over a null base.
+struct EnsBufs {
+  InferBufs m[kEnsMembers];
+  float* alpha[kEnsMembers];       // one step's [R][H][M] alignments of a member whose history nobody asked for
+  float *logits, *log_probs;       // [n][R][V] slab, [R]
+  int32_t* ids;                    // [R] start ids
+  void* step_ws;
+  int64_t step_bytes;
+  size_t bytes;
+  bool ok;
+};
+// bytes of the ensemble step's workspace for any split of `rows` into batch x beam: (2 n + 2) * rows * chunks words, chunks <= 32
+int64_t ens_step_ws_bound(int n, int rows) { return ((int64_t)(2 * n + 2) * rows * 32) * 4 + 1024; }
+EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64_t bytes) {
+  EnsBufs e{};
+  size_t off = 0;
+  e.ok = true;
+  for (int m = 0; m < n; ++m) {
+    const int64_t left = std::max<int64_t>(0, bytes - (int64_t)off);
+    e.m[m] = carve_infer(&descs[m], R, ws ? (char*)ws + off : nullptr, left, 0);
+    e.ok = e.ok && e.m[m].ok;
+    off += e.m[m].bytes;
+  }
+  Bump w(ws ? (char*)ws + off : nullptr, (size_t)std::max<int64_t>(0, bytes - (int64_t)off));
+  for (int m = 0; m < n; ++m) e.alpha[m] = w.take<float>((size_t)R * descs[m].H * descs[m].M);
+  e.logits = w.take<float>((size_t)n * R * descs[0].V);
+  e.log_probs = w.take<float>(R);
+  e.ids = w.take<int32_t>(R);
+  e.step_bytes = ens_step_ws_bound(n, R);
+  e.step_ws = w.take<char>((size_t)e.step_bytes);
+  e.ok = e.ok && w.ok;
+  e.bytes = off + w.off;
+  return e;
+}
+struct EnsMember {
+  bool fused = false, stream_lstm = false;
+  int mem_div = 1, ld_wo = 0, cur = 0;
+  comic_attn_desc ad{};
+  const float* values = nullptr;
+  const float* w_o = nullptr;
+  StreamBufs sm{};
+};
+}  // namespace
+
+extern "C" int64_t comic_decoder_beam_ensemble_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                         int max_steps) {
+  (void)max_steps;
+  if (!descs || n_models < 1 || n_models > kEnsMembers || rows <= 0) return -1;
+  for (int m = 0; m < n_models; ++m)
+    if (descs[m].D <= 0 || descs[m].V <= 0 || descs[m].M <= 0 || descs[m].H <= 0) return -1;
+  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0).bytes;
+}
+
+extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                           const float* const* fms, const float* const* im_embeds, const float* weights,
+                                           int n_models, int B, int W, int max_steps, int32_t* step_ids, int32_t* parent_ids,
+                                           float* scores, int64_t* lengths, int32_t* finished, float* const* attn_hists,
+                                           int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream) {
+  COMIC_REQUIRE(descs && params && fms && im_embeds && weights && step_ids && parent_ids && scores && lengths && finished &&
+                    steps_executed && workspace,
+                "beam_ensemble: null pointer");
+  COMIC_REQUIRE(n_models >= 1 && n_models <= kEnsMembers, "beam_ensemble: 1 to %d members (got %d)", kEnsMembers, n_models);
+  COMIC_REQUIRE(B > 0 && W > 0 && W <= 64 && max_steps > 0, "beam_ensemble: bad shape");
+  const int n = n_models, R = B * W, V = descs[0].V;
+  for (int m = 0; m < n; ++m) {
+    RC(check_desc(&descs[m]));
+    RC(check_cell_params(&descs[m], &params[m]));
+    COMIC_REQUIRE(fms[m] && im_embeds[m], "beam_ensemble: member %d has no features", m);
+    COMIC_REQUIRE(descs[m].V == V && descs[m].start_id == descs[0].start_id && descs[m].end_id == descs[0].end_id,
+                  "beam_ensemble: member %d differs from member 0 in V / start_id / end_id", m);
+  }
+  COMIC_REQUIRE(W <= V && (long)W * V < (1L << 31), "beam_ensemble: beam*V too large or beam > V");
+  hipStream_t st = (hipStream_t)stream;
+  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes);
+  COMIC_REQUIRE(L.ok && (int64_t)L.bytes <= workspace_bytes, "beam_ensemble: workspace too small");
+  g_splitk_ws = L.m[0].splitk;               // members run back to back on the one stream: one split-K scratch serves all
+  const float lpw = descs[0].length_penalty_weight;
+  EnsMember mem[kEnsMembers];
+  for (int m = 0; m < n; ++m) {
+    const comic_decoder_desc* d = &descs[m];
+    const comic_decoder_params* p = &params[m];
+    FlagScope flag_scope__(d);
+    InferBufs& ws = L.m[m];
+    EnsMember& e = mem[m];
+    const int D = d->D, E = d->E, A = d->A, M = d->M;
+    e.fused = fused_step_enabled() && comic_fused_step_supported(D, E + A + D);
+    e.mem_div = e.fused ? W : 1;              // fused attention reads keys / values held once per entry (see comic_decoder_beam)
+    {
+      const long n1 = (long)R * M * d->C, n2 = (long)R * d->Cg;
+      if (e.mem_div == 1)
+        hipLaunchKernelGGL(tile_rows_kernel, dim3((unsigned)cdiv64(n1, 256)), dim3(256), 0, st, fms[m], ws.fm_t, n1, W,
+                           M * d->C);
+      hipLaunchKernelGGL(tile_rows_kernel, dim3((unsigned)cdiv64(n2, 256)), dim3(256), 0, st, im_embeds[m], ws.im_t, n2, W,
+                         d->Cg);
+      COMIC_LAUNCH_CHECK("tile_rows");
+    }
+    e.ad = attn_desc(d, R);
+    if (e.mem_div == 1) RC(memory_projections(d, p, ws.fm_t, R, ws.keys, ws.values_buf, &e.values, st));
+    else RC(memory_projections(d, p, fms[m], B, ws.keys, ws.values_buf, &e.values, st));
+    RC(rnn_init_fwd(d, p, ws.im_t, R, nullptr, ws.ib, ws.c[0], ws.h[0], st));
+    RC(fill(ws.att[0], 0.f, (long)R * A, st));
+    e.stream_lstm = e.fused && lstm_stream_enabled() && comic_lstm_stream_supported(D, E, A, R) &&
+                    comic_lstm_stream_part_bytes(D, E + A + D, R) <= kSplitKBytes;
+    e.sm = StreamBufs{ws.kfrag, ws.xfrag, ws.yfrag, nullptr};
+    if (e.stream_lstm) {
+      RC(comic_lstm_stream_pack(p->K, ws.kfrag, D, E + A + D, st));
+      if (comic_stream_gemm_supported(D, D, R) && comic_stream_gemm_part_bytes(D, D, R) <= kSplitKBytes) {
+        RC(comic_stream_gemm_pack(p->W_q, ws.wqfrag, D, D, st));
+        e.sm.wqfrag = ws.wqfrag;
+      }
+    } else if (e.fused) RC(comic_pack_lstm_panels(p->K, ws.kpanel, nullptr, D, E + A + D, st));
+    e.w_o = aligned_w_o(d, p, ws.wo_pad, &e.ld_wo, st);
+  }
+  hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, L.log_probs, finished, lengths, R, W);
+  hipLaunchKernelGGL(fill_i32_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, L.ids, descs[0].start_id, (long)R);
+  hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(64), 0, st, steps_executed, max_steps, 1L);
+  COMIC_LAUNCH_CHECK("beam_ensemble init");
+  struct StopScope {          // whatever way this call returns, no later launch sees the flag
+    ~StopScope() { g_comic_stop = ComicStop(); }
+  } stop_scope;
+  for (int t = 0; t < max_steps; ++t) {
+    // the launches of step t return at once when the loop ended at an earlier step (common.h, ComicStop).  Members on
+    // the per-step launch chain keep running on their last state; what they index through (ids: clamped by the embedding
+    // kernel, parents: comic_ens_gather_state) tolerates the unwritten rows of a skipped step.
+    g_comic_stop.p = steps_executed;
+    g_comic_stop.t = t;
+    int32_t* word = step_ids + (size_t)t * R;
+    int32_t* parent = parent_ids + (size_t)t * R;
+    const int32_t* ids_in = t == 0 ? L.ids : step_ids + (size_t)(t - 1) * R;
+    const int32_t* par_in = t == 0 ? nullptr : parent_ids + (size_t)(t - 1) * R;
+    for (int m = 0; m < n; ++m) {
+      const comic_decoder_desc* d = &descs[m];
+      const comic_decoder_params* p = &params[m];
+      FlagScope flag_scope__(d);
+      InferBufs& ws = L.m[m];
+      EnsMember& e = mem[m];
+      const int D = d->D, E = d->E, A = d->A;
+      float* hist = (attn_hists && attn_hists[m]) ? attn_hists[m] + (size_t)t * R * d->H * d->M : L.alpha[m];
+      float* lg = L.logits + (size_t)m * R * V;
+      StepBufs sb = ws.sb;
+      if (e.fused) {
+        // raw step outputs ping-pong in c/h/att[]; the next step's operand prep gathers them through the shared parents
+        const int cur = e.cur, nxt = cur ^ 1;
+        sb.c2 = ws.c[nxt];
+        sb.h2 = ws.h[nxt];
+        if (!d->context_layer) sb.ctx = ws.att[nxt];
+        else sb.att2 = ws.att[nxt];
+        e.sm.skip_prep = 0;
+        e.sm.wo_part = nullptr;
+        StreamBufs* smp = e.stream_lstm ? &e.sm : nullptr;
+        RC(infer_step_lstm(d, p, ws.kpanel, ids_in, par_in, W, ws.c[cur], ws.h[cur], ws.att[cur], sb, ws.gtmp, R, st, smp));
+        RC(infer_step_attend(d, p, e.ad, ws.keys, e.values, sb, hist, R, st, smp, e.mem_div));
+        e.cur = nxt;
+      } else {
+        sb.c2 = ws.gtmp;
+        sb.h2 = ws.gtmp + (size_t)R * D;
+        float* att_new = ws.gtmp + (size_t)2 * R * D;
+        if (!d->context_layer) sb.ctx = att_new;
+        else sb.att2 = att_new;
+        if (t > 0) RC(comic_ens_gather_state(sb.c2, sb.h2, att_new, par_in, ws.c[0], ws.h[0], ws.att[0], R, W, D, A, st));
+        RC(comic_embed_fwd(p->emb, ids_in, ws.x, R, E, V, (void*)st));
+        RC(infer_step(d, p, e.ad, ws.keys, e.values, ws.x, ws.c[0], ws.h[0], ws.att[0], sb, hist, R, st));
+      }
+      RC(gemm_big(sb.y, e.w_o, lg, p->b_o, R, V, D, D, e.ld_wo, V, 0, 0, 0.f, st));
+    }
+    RC(comic_beam_step_ensemble(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R, B,
+                                W, V, descs[0].end_id, lpw, L.step_ws, L.step_bytes, (void*)st));
+    hipLaunchKernelGGL(all_finished_kernel, dim3(1), dim3(256), 0, st, finished, steps_executed, t, R, max_steps);
+    COMIC_LAUNCH_CHECK("all_finished");
+  }
+  return 0;
+}

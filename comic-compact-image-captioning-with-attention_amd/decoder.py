@@ -887,3 +887,114 @@ def gather_tree_from_array(t, parent_ids, sequence_length, _unused_end=None):
     sorted_ids = np.where(mask, sorted_ids, beam_ids)
     src = np.asarray(t).reshape(T, B, W, -1)
     return src[np.arange(T)[:, None, None], np.arange(B)[None, :, None], sorted_ids].reshape(np.asarray(t).shape)
+
+
+def check_ensemble(specs, weights=None):
+    """Validation of an ensemble on the host (no GPU call): 1 to 8 members that agree in vocabulary size, token type and
+    start / end ids; weights (default uniform) one per member, >= 0, summing to 1 within 1e-6.  -> the weights as a list."""
+    n = len(specs)
+    if not 1 <= n <= 8:
+        raise ValueError('an ensemble has 1 to 8 members, got %d' % n)
+    for k, s in enumerate(specs[1:], 1):
+        for f in ('V', 'token_type', 'start_id', 'end_id'):
+            if getattr(s, f) != getattr(specs[0], f):
+                raise ValueError('ensemble member %d differs from member 0 in %s: %r against %r'
+                                 % (k, f, getattr(s, f), getattr(specs[0], f)))
+    if weights is None:
+        return [1.0 / n] * n
+    w = [float(x) for x in weights]
+    if len(w) != n:
+        raise ValueError('%d ensemble weights for %d members' % (len(w), n))
+    if any(not (x >= 0.0) or math.isinf(x) for x in w):
+        raise ValueError('ensemble weights must be finite and >= 0: %r' % (w,))
+    if abs(sum(w) - 1.0) > 1e-6:
+        raise ValueError('ensemble weights must sum to 1 (got %r)' % (sum(w),))
+    return w
+
+
+class EnsembleDecoder:
+    """Several decoders, one beam: beam search whose step distribution is the weighted mean of the members' word
+    distributions (comic_decoder_beam_ensemble; extends rnn_decoder_beam_search, ops_rnn.py:49-112).  Members may differ
+    in geometry, cell and attention; they share the vocabulary."""
+
+    def __init__(self, decoders, weights=None):
+        decoders = list(decoders)
+        self.weights = check_ensemble([d.spec for d in decoders], weights)      # raises before anything touches the GPU
+        self.decoders = decoders
+        self.spec = decoders[0].spec
+        self.torch, self.lib, self.device = decoders[0].torch, decoders[0].lib, decoders[0].device
+        self._ctxs = {}
+
+    def _ctx(self, B, W, max_steps, lpw, feats):
+        """Persistent buffers (+ a hipGraph of the whole loop, captured on the second call with the shape), as
+        Decoder._infer_ctx."""
+        torch, n = self.torch, len(self.decoders)
+        key = (B, W, max_steps, float(lpw))
+        ctx = self._ctxs.get(key)
+        if ctx is None:
+            ctx = type('EnsembleCtx', (), {})()
+            R = B * W
+            i32 = dict(dtype=torch.int32, device=self.device)
+            f32 = dict(dtype=torch.float32, device=self.device)
+            specs = [d.spec for d in self.decoders]
+            ctx.fm = [torch.empty((B, s.M, s.C), **f32) for s in specs]
+            ctx.im = [torch.empty((B, s.Cg), **f32) for s in specs]
+            ctx.hist = torch.empty((max_steps, R, specs[0].H * specs[0].M), **f32)      # member 0's alignments
+            # rows past the executed steps are never written (device-side early exit): poisoned, as Decoder._infer_ctx
+            ctx.step_ids = torch.full((max_steps, B, W), 0x7f7f7f7f, **i32)
+            ctx.parent_ids = torch.full((max_steps, B, W), 0x7f7f7f7f, **i32)
+            ctx.scores = torch.empty((max_steps, B, W), **f32)
+            ctx.lengths = torch.empty((B, W), dtype=torch.int64, device=self.device)
+            ctx.finished = torch.empty((B, W), **i32)
+            ctx.steps = torch.empty(1, **i32)
+            ctx.descs = (L.DecoderDesc * n)(*[s.desc(False) for s in specs])
+            ctx.descs[0].length_penalty_weight = float(lpw)
+            ctx.ptabs = (L.DecoderParams * n)(*[d.params.table() for d in self.decoders])
+            ctx.fm_ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ctx.fm])
+            ctx.im_ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ctx.im])
+            ctx.hist_ptrs = (C.c_void_p * n)(*([ctx.hist.data_ptr()] + [None] * (n - 1)))
+            ctx.wts = (C.c_float * n)(*self.weights)
+            ctx.nbytes = int(self.lib.comic_decoder_beam_ensemble_workspace(ctx.descs, n, R, max_steps))
+            assert ctx.nbytes > 0, 'comic_decoder_beam_ensemble_workspace failed'
+            ctx.ws = torch.empty(ctx.nbytes, dtype=torch.uint8, device=self.device)
+            ctx.graph, ctx.calls = None, 0
+            self._ctxs[key] = ctx
+        for k, (fm, im) in enumerate(feats):
+            ctx.fm[k].copy_(fm.reshape(ctx.fm[k].shape))
+            ctx.im[k].copy_(im.reshape(ctx.im[k].shape))
+        return ctx
+
+    def beam_search(self, fms, im_embeds, beam, max_steps, want_attention=False, use_graph=True, length_penalty_weight=0.0):
+        """fms / im_embeds: one device tensor (every member reads the same features) or a sequence with one per member.
+        Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's."""
+        torch, n = self.torch, len(self.decoders)
+        if torch.is_tensor(fms):
+            fms = [fms] * n
+        if torch.is_tensor(im_embeds):
+            im_embeds = [im_embeds] * n
+        assert len(fms) == n and len(im_embeds) == n
+        B, W = int(fms[0].shape[0]), int(beam)
+        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)))
+
+        def launch():
+            flags = L.decoder_flags_from_env()
+            for k in range(n):
+                ctx.descs[k].flags = flags
+            L.check(self.lib.comic_decoder_beam_ensemble(
+                ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps, ctx.step_ids.data_ptr(),
+                ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(), ctx.finished.data_ptr(),
+                ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes, L.stream_ptr()), 'decoder_beam_ensemble')
+        Decoder._run_infer(self, ctx, launch, use_graph)
+        s = self.spec
+        T = int(ctx.steps.item())
+        max_len = ctx.lengths.max(dim=1).values.to(torch.int32).contiguous()
+        pred = torch.empty((T, B, W), dtype=torch.int32, device=self.device)
+        L.check(self.lib.comic_gather_tree(ctx.step_ids[:T].data_ptr(), ctx.parent_ids[:T].data_ptr(), max_len.data_ptr(),
+                                           pred.data_ptr(), T, B, W, s.end_id, L.stream_ptr()), 'gather_tree')
+        par = ctx.parent_ids[:T].cpu().numpy()
+        ln = ctx.lengths.cpu().numpy()
+        out = dict(predicted_ids=pred.cpu().numpy(), scores=ctx.scores[:T].cpu().numpy(),
+                   step_ids=ctx.step_ids[:T].cpu().numpy(), parent_ids=par, lengths=ln)
+        if want_attention:
+            out['attn_hist'] = gather_tree_from_array(ctx.hist[:T].cpu().numpy(), par, ln, s.end_id)
+        return out

@@ -33,15 +33,57 @@ def run_inference(config, curr_ckpt_path, device='cuda:0'):
         inputs_man.close()
 
 
-def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, device):
+def ensemble_name(ckpt_nums):
+    """Tag of an ensemble's output files: captions___ens_<n1>+<n2>+....json"""
+    return 'ens_' + '+'.join(str(n) for n in ckpt_nums)
+
+
+def run_inference_ensemble(config, ckpt_paths, weights=None, device='cuda:0'):
+    """The checkpoints decode TOGETHER: one beam search over the weighted mean of the members' word distributions
+    (model.CaptionEnsemble).  Writes captions___ens_<n1>+<n2>+....json and a line in infer_speed.txt."""
+    nums = [P_CKPT.findall(os.path.split(p)[1])[0] for p in ckpt_paths]
+    mdl.reset_default_graph()
+    inputs_man = inputs.InputManager(config, is_inference=True)
+    try:
+        return _inference_loop(inputs_man, list(ckpt_paths), None, None, ensemble_name(nums), device, weights=weights)
+    finally:
+        inputs_man.close()
+        mdl.reset_default_graph()
+
+
+def _build_ensemble(c, inputs_man, ckpt_paths, weights, device):
+    members = []
+    for k, path in enumerate(ckpt_paths):
+        mdl.reset_default_graph()
+        c.checkpoint_path = path
+        m = mdl.CaptionModel(c, mode='infer', batch_ops=inputs_man.batch_infer if k == 0 else None, reuse=False,
+                             name='inference (member %d)' % k, device=device)
+        m.restore_model()
+        members.append(mdl.CaptionEnsemble.detach(m))
+    return mdl.CaptionEnsemble(members, weights)
+
+
+def _ensemble_batches(ens):
+    while True:
+        try:
+            yield ens.infer()
+        except StopIteration:
+            return
+
+
+def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, device, weights=None):
     inputs_man.enable_device_preprocess(device)
     c = inputs_man.config
     batch_size = c.batch_size_infer
-    c.checkpoint_path = curr_ckpt_path
     c.resume_training = False
-    m_infer = mdl.CaptionModel(c, mode='infer', batch_ops=inputs_man.batch_infer, reuse=False, name='inference',
-                               device=device)
-    m_infer.restore_model()
+    ensemble = isinstance(curr_ckpt_path, list)
+    if ensemble:
+        m_infer = _build_ensemble(c, inputs_man, curr_ckpt_path, weights, device)
+    else:
+        c.checkpoint_path = curr_ckpt_path
+        m_infer = mdl.CaptionModel(c, mode='infer', batch_ops=inputs_man.batch_infer, reuse=False, name='inference',
+                                   device=device)
+        m_infer.restore_model()
     filenames = inputs_man.filenames_infer
     num_batches = int(c.split_sizes['infer'] / batch_size)
     raw_outputs = dict(captions={}, attention={}, image_ids={}, beam_size=c.infer_beam_size,
@@ -52,7 +94,10 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
     start_time = time.time()
     captions = []
     # captions alone (no --save_attention_maps): the decode loops of two batches are in flight (CaptionModel.infer_pipelined)
-    batches = m_infer.infer_pipelined(want_attention=bool(getattr(c, 'save_attention_maps', False)))
+    if ensemble:
+        batches = _ensemble_batches(m_infer)
+    else:
+        batches = m_infer.infer_pipelined(want_attention=bool(getattr(c, 'save_attention_maps', False)))
     for step in range(num_batches):
         word_ids, attn_maps = next(batches)
         captions = id_to_caption(word_ids, c)

@@ -760,3 +760,67 @@ class CaptionModel_SCST(ModelBase):
                                       use_graph=True, phase='bwd')
         self.dp.exchange_and_step(self.opt, self.decoder.grads, lr)
         return res['loss']
+
+
+class CaptionEnsemble(object):
+    """Several `CaptionModel(mode='infer')` members decoding together: one beam search over the weighted mean of their
+    word distributions (decoder.EnsembleDecoder).  A member built after `reset_default_graph()` owns its variables; pass
+    each through `CaptionEnsemble.detach(model)` before the next one is built (the module-level share is cleared then).
+    When the members' CNN variables are bit-equal -- checkpoints of one decoder-mode run, whose CNN is frozen -- the encoder
+    runs once per batch and its feature map feeds every member; otherwise each member encodes."""
+
+    @staticmethod
+    def detach(model):
+        """Give `model` its own copy of the construction share, so that building the next member leaves it alone."""
+        model._share = dict(model._share)
+        return model
+
+    def __init__(self, models, weights=None):
+        models = list(models)
+        assert all(m.mode == 'infer' for m in models), 'CaptionEnsemble is built over mode="infer" members'
+        self.models = models
+        self.decoder = cdec.EnsembleDecoder([m.decoder for m in models], weights)
+        self._config = models[0]._config
+        self.torch, self.device = models[0].torch, models[0].device
+        self.shared_encoder = all(self._same_cnn(models[0], m) for m in models[1:])
+        self.infer_output = None
+
+    @staticmethod
+    def _same_cnn(a, b):
+        torch = a.torch
+        ea, eb = (next(iter(m._share['encoders'].values())) for m in (a, b))
+        if ea is eb:
+            return True
+        if a.plan.param_shapes() != b.plan.param_shapes() or ea.dtype != eb.dtype:
+            return False
+        return all(x.data.shape == y.data.shape and bool(torch.equal(x.data, y.data))
+                   for x, y in ((ea.w_master, eb.w_master), (ea.scale, eb.scale), (ea.shift, eb.shift)))
+
+    def _features(self, images):
+        m0 = self.models[0]
+        if not self.torch.is_tensor(images):
+            images = self.torch.from_numpy(np.ascontiguousarray(images, np.float32)).to(self.device)
+        if self.shared_encoder:
+            net, fm = m0._encoder_for(int(images.shape[0])).forward(images, use_graph=True)
+            return [(m._embed(net), fm) for m in self.models]
+        return [m._encode(images) for m in self.models]
+
+    def infer(self, batch=None):
+        """-> [dec_preds (B,T), attention_maps (B,H,T,M) of member 0], as CaptionModel.infer; without `batch` the images
+        come from member 0's input pipeline."""
+        c = self._config
+        if batch is None:
+            batch = next(self.models[0].batch_ops)
+        images = batch[0] if isinstance(batch, (tuple, list)) else batch
+        feats = self._features(images)
+        spec = self.decoder.spec
+        iters = self.models[0].decoder.max_iterations(c.infer_max_length, len(c.wtoi))
+        W = c.infer_beam_size
+        assert W > 1, 'the ensemble decodes by beam search: infer_beam_size must be at least 2'
+        r = self.decoder.beam_search([f[1] for f in feats], [f[0] for f in feats], W, iters, want_attention=True,
+                                     length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0))
+        pred = r['predicted_ids']                                  # (T, B, W)
+        T = pred.shape[0]
+        hist = r['attn_hist'].reshape(T, -1, W, spec.H, spec.M)[:, :, 0]
+        self.infer_output = [pred[:, :, 0].T.copy(), hist.transpose(1, 2, 0, 3)]
+        return self.infer_output

@@ -474,6 +474,21 @@ int64_t comic_beam_step_dense_workspace(int B, int W, int D, int V);
 int comic_beam_step_dense(const float* y, const float* W_o, const float* b_o, float* log_probs, int32_t* finished,
                           int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int D,
                           int V, int end_id, void* workspace, int64_t workspace_bytes, void* stream);
+/* Ensemble beam step (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112, to several members): comic_beam_step on
+ * lp[v] = log sum_m weights[m] * softmax(logits_m[b,w,:])[v], formed as A + log sum_m weights[m] * exp(a_m - A) with a_m
+ * member m's log-softmax and A its maximum over the members of weight > 0 (members in order 0, 1, ...; a member of weight 0
+ * is not read).  logits [n_models][B*W][V] (device), weights [n_models] (HOST: they travel as kernel arguments),
+ * 1 <= n_models <= 8, W <= 64, W <= V, W*V < 2^31.  State arrays, total order, _mask_probs and the length penalty
+ * (length_penalty_weight, 0 = none) as comic_beam_step / comic_decoder_beam.  With length_penalty_weight == 0,
+ * W*V >= 8192 and a vocabulary of at least 2048 words the step runs split over several workgroups per entry when
+ * `workspace` holds comic_beam_step_ensemble_workspace bytes (null / smaller: one workgroup per entry, same result);
+ * comic_beam_step_ensemble_path() is 1 when the LAST call of this thread ran the split form. */
+int64_t comic_beam_step_ensemble_workspace(int n_models, int B, int W, int V);
+int comic_beam_step_ensemble(const float* logits, const float* weights, int n_models, float* log_probs, int32_t* finished,
+                             int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int V,
+                             int end_id, float length_penalty_weight, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+int comic_beam_step_ensemble_path(void);
 /* out[r,:] = in[(r/W)*W + parent[r], :]   (state re-ordering by parent beam) */
 int comic_gather_rows(const float* in, const int32_t* parent, float* out, int rows, int W, int cols,
                       void* stream);
@@ -679,6 +694,21 @@ int comic_decoder_beam(const comic_decoder_desc* d, const comic_decoder_params* 
                        int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
                        float* attn_hist, int32_t* steps_executed, void* workspace,
                        int64_t workspace_bytes, void* stream);
+
+/* Ensemble beam search (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112): ONE beam whose step distribution is
+ * the weighted mean of n_models members' distributions (comic_beam_step_ensemble).  descs / params: arrays of n_models
+ * entries; fms / im_embeds / attn_hists: HOST arrays of n_models device pointers (member m's fm [B,M_m,C_m], im_embed
+ * [B,Cg_m], attn_hist [max_steps, B*W, H_m*M_m] or NULL when its alignments are not wanted; attn_hists itself may be
+ * NULL); weights [n_models] on the host.  Members may differ in D, E, H, M, C, cell and attention method and must agree
+ * in V, start_id and end_id; length_penalty_weight is descs[0]'s.  Every member runs its own wrapper step on the shared
+ * ids / parents of the step before; outputs, early exit through steps_executed and the untouched rows past it as
+ * comic_decoder_beam.  workspace: comic_decoder_beam_ensemble_workspace(descs, n_models, B*W, max_steps) bytes. */
+int64_t comic_decoder_beam_ensemble_workspace(const comic_decoder_desc* descs, int n_models, int rows, int max_steps);
+int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                const float* const* fms, const float* const* im_embeds, const float* weights,
+                                int n_models, int B, int W, int max_steps, int32_t* step_ids, int32_t* parent_ids,
+                                float* scores, int64_t* lengths, int32_t* finished, float* const* attn_hists,
+                                int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SCST reward scorer (host, multi-threaded)  common/scst/scorers.py:43-171      */

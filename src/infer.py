@@ -41,6 +41,11 @@ def create_parser():
     a('--cnn_dtype', type=str, default=None, choices=['bf16', 'f16', 'f32', 'bf16x3'],
       help='CNN plan of the inference run (default: the training run\'s).  Checkpoints hold fp32 variables, so any '
            'run decodes on any plan, e.g. a bf16-trained model on f16.')
+    a('--infer_ensemble', action='store_true', default=None,
+      help='Decode the checkpoints of --infer_checkpoints TOGETHER: one beam search over the mean of their word '
+           'distributions; writes captions___ens_<n1>+<n2>+....json.')
+    a('--infer_ensemble_weights', type=str, default=None,
+      help='Comma-separated weights of the ensemble members (>= 0, summing to 1; default uniform).')
     return p
 
 
@@ -78,6 +83,8 @@ def main(argv=None):
     import torch
     torch.cuda.set_device(int(str(c.gpu).split(',')[0]))
     scores_combined = {}
+    if getattr(c, 'infer_ensemble', None):
+        return run_ensemble(c, ckpt_prefix)
     for ckpt_num in c.infer_checkpoints:
         path = pjoin(c.infer_checkpoints_dir, ckpt_prefix + ckpt_num)
         path = path + '.npz' if os.path.isfile(path + '.npz') else path       # else: TF bundle prefix
@@ -93,6 +100,36 @@ def main(argv=None):
             print('INFO: annotation file `{}` not found: captions are written, metric scores skipped.'.format(ann))
         infer.evaluate_model(config=c, curr_ckpt_path=path, scores_combined=scores_combined, evaluate_captions=evaluator)
         print('\n')
+
+
+def run_ensemble(c, ckpt_prefix):
+    """--infer_ensemble: the listed checkpoints as one ensemble; metric scores through the same hand-off."""
+    from comic_amd import infer_fn as infer
+    paths = []
+    for ckpt_num in c.infer_checkpoints:
+        path = pjoin(c.infer_checkpoints_dir, ckpt_prefix + ckpt_num)
+        paths.append(path + '.npz' if os.path.isfile(path + '.npz') else path)
+    weights = None
+    if getattr(c, 'infer_ensemble_weights', None):
+        weights = [float(w) for w in str(c.infer_ensemble_weights).split(',')]
+    tag = infer.ensemble_name(c.infer_checkpoints)
+    coco_json = pjoin(c.infer_save_path, 'captions___{}.json'.format(tag))
+    if c.run_inference:
+        if os.path.isfile(coco_json):
+            print('INFO: Found caption file `{}`. Skipping inference.'.format(os.path.basename(coco_json)))
+        else:
+            infer.run_inference_ensemble(c, paths, weights)
+    ann = c.annotations_file if os.path.isabs(c.annotations_file) else pjoin(c.dataset_dir, 'captions', c.annotations_file)
+    if c.get_metric_score and os.path.isfile(ann):
+        from comic_amd import coco_eval
+        results = coco_eval.evaluate_captions(ann, coco_json)
+        metrics = [m for m in ['Bleu_1', 'Bleu_2', 'Bleu_3', 'Bleu_4', 'METEOR', 'ROUGE_L', 'CIDEr', 'SPICE'] if m in results]
+        with open(pjoin(c.infer_save_path, 'metric_scores.txt'), 'a', newline='') as f:
+            f.write('===================================\r\n%s\r\nBeam size: %d\r\n===================================\r\n'
+                    % (tag, c.infer_beam_size))
+            f.write('\r\n'.join('{}: {:1.3f}'.format(m, results[m]) for m in metrics) + '\r\n\r\n\r\n')
+    elif c.get_metric_score:
+        print('INFO: annotation file `{}` not found: captions are written, metric scores skipped.'.format(ann))
 
 
 if __name__ == '__main__':
