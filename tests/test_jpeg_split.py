@@ -447,7 +447,20 @@ def test_split_loader_batches_are_bit_identical_to_the_thread_decode(tmp_path):
     Image.fromarray(_photo(120, 90, seed=9)).save(png)
     paths.append(png)
     pre = inputs.DevicePreprocessor('cuda:0', 224, 224)
-    jpool = inputs.JpegSplitPool(4, slot_elems=200000, max_batch=16)       # room for about half of the files: the rest -> PIL
+    # a staging slot holds max_batch x slot_elems 16-bit units of PACKED coefficients: sized here for half of what the files
+    # need, so the batch overflows it and the files that end their decode last -> PIL (which ones is a matter of thread timing)
+    jl, n = L.load_jpeg(), len(paths)
+    room = np.zeros(8 << 20, np.uint16)
+    infos, status = np.zeros(n, L.JPEG_INFO_DTYPE), np.full(n, 99, np.int32)
+    cpool = jl.comic_jpeg_pool_create(2)
+    h = jl.comic_jpeg_pool_submit_packed(cpool, (C.c_char_p * n)(*[os.fsencode(p) for p in paths]), n, infos.ctypes.data,
+                                         status.ctypes.data, room.ctypes.data, room.size)
+    need, samples = C.c_int64(), C.c_int64()
+    assert h and jl.comic_jpeg_pool_wait(cpool, h, 60.0, C.byref(need), C.byref(samples)) == 0
+    jl.comic_jpeg_pool_destroy(cpool)
+    assert int((status == 0).sum()) == 10 and L.JPEG_TOO_SMALL not in status.tolist() and 100_000 < need.value < room.size
+    jpool = inputs.JpegSplitPool(4, slot_elems=need.value // 2 // 16 // 8 * 8, max_batch=16)      # (whole multiples of 8: kept as is)
+    assert need.value // 4 < jpool.max_batch * jpool.slot_elems <= need.value // 2
     pre.enable_split(jpool, 3)
     params = [(bool(i % 2), (i * 7) % 33, (i * 5) % 33) for i in range(len(paths))]
     ref = pre(list(map(inputs.decode_image, paths)), params).cpu()
@@ -455,6 +468,8 @@ def test_split_loader_batches_are_bit_identical_to_the_thread_decode(tmp_path):
     for packed in inflight:
         got = pre.finish(packed).cpu()
         assert torch.equal(got, ref)
+        codes = packed.slot[3]['status'][:n].tolist()      # (the slot is not handed out again before the next pack)
+        assert L.JPEG_TOO_SMALL in codes and L.JPEG_OK in codes, codes
     torch.cuda.synchronize()
     pre._reap()
     assert pre._free_coef.qsize() == 3                     # every staging slot came back
