@@ -1,0 +1,519 @@
+// One beam-search step on a slab of logits: log-softmax, finished masking, top-k over beam * V, length / finished
+// bookkeeping.  Restates [TF-1.9] _beam_search_step as used by common/ops_rnn.py:49-112:
+//   log_softmax -> _mask_probs (finished rows: float32.min, 0 at EOS) -> total = log_probs[:, :, None] + step
+//   -> top_k(beam) over the flattened beam * V axis -> word = idx % V, parent = idx / V.
+// Candidates are ranked under one total order, value descending and flat index w * V + v ascending, within a chunk, across
+// chunks and across beams.  With a length penalty (lpw != 0, _get_scores) they are ranked by
+// total / ((5 + length) / 6)^lpw with length = the beam's + 1 unless the beam is finished or the candidate is EOS; the beam
+// state keeps the unpenalised total, the step's `scores` output the penalised one.
+//
+// How a candidate's step log-probability lp[v] is formed is a policy, known at compile time:
+//   OneMember ... lp[v] = (logits[v] - max) - log sum exp(logits - max)                       the row's log-softmax
+//   Ensemble  ... a_m[v] = member m's log-softmax as above, A = max over the members with weight > 0 of a_m[v],
+//                 lp[v] = A + log sum_m wt_m * exp(a_m[v] - A), members in order 0, 1, ...: the log of the weighted mean
+//                 of the members' distributions.  A member with weight 0 is never read: it contributes exactly 0 to the
+//                 sum, and leaving it out of A as well keeps a zero-weight member with a far larger a_m from pushing every
+//                 term that counts into underflow.  With one member of weight 1 and finite logits the sum is exp(0) = 1
+//                 and lp = a_0 to the bit.  (OneMember is NOT this with n = 1: a_0 - A is NaN at a -inf logit, a weight
+//                 other than 1 adds log wt, and the single path would pay an expf / logf per candidate.)
+// The policy also owns the row constants a workgroup keeps in LDS: [64] per beam for one member, [kEnsMax * 64] for several.
+//
+// Two forms, one copy of each kernel, instantiated per policy:
+//   beam_step_kernel ........ one workgroup per batch entry: any V, length penalty included
+//   beam_stats_kernel ....... per (chunk, beam, entry, member): max and sum exp(x - max) of the chunk
+//   beam_chunk_topk_kernel .. per (entry, chunk): every row's constants from the partials (combined in chunk order, so each
+//                             workgroup of an entry gets the same bits), lp of its slice of all W beams, its own top-W
+//   beam_merge_kernel ....... per entry: top-W of the chunks' candidates + bookkeeping (no policy: candidates carry totals)
+// The global top-W under a total order is the top-W of the union of the per-chunk top-W lists.  No kernel waits on another
+// workgroup; the three launches of the split form are ordered by the stream.  (Word tokens: V = 25 599, beam 3 -> 76 797
+// candidates per entry; one workgroup per entry leaves the GPU empty and scans them 2 + W times.)
+#include <float.h>
+
+#include <algorithm>
+
+#include "beam_select.h"
+
+// executor-internal: chunks per entry of the split form, and the bytes of its workspace for n members
+// (2 * n * B * W * chunks floats of partials + B * chunks * W (float + int32) candidates)
+int comic_beam_step_chunks(int B, int V) {
+  const int chunks = std::max(1, std::min(32, 1024 / std::max(1, B)));
+  return std::min(chunks, std::max(1, V / 1024));
+}
+int64_t comic_beam_step_split_bytes(int n, int B, int W, int chunks) {
+  return ((int64_t)2 * n * B * W * chunks + (int64_t)2 * B * chunks * W) * 4 + 1024;
+}
+
+namespace {
+
+struct OneMember {
+  static constexpr const char* kName = "beam_step";
+  static constexpr const char* kSplitName = "beam_step (split)";
+  struct Rows {
+    float mx[64], logsum[64];
+    float lp[64];
+    int fin[64];
+  };
+  __device__ __forceinline__ int members() const { return 1; }
+  __device__ __forceinline__ void begin(Rows&) const {}
+  __device__ __forceinline__ float weight(int) const { return 1.f; }
+  __device__ __forceinline__ bool live(const Rows&, int) const { return true; }
+  __device__ __forceinline__ float step_lp(const float* __restrict__ lg, size_t, int f, int w, const Rows& s) const {
+    return (lg[f] - s.mx[w]) - s.logsum[w];
+  }
+};
+
+struct Ensemble {
+  static constexpr const char* kName = "beam_step_ensemble";
+  static constexpr const char* kSplitName = "beam_step_ensemble (split)";
+  int n;
+  float w[kEnsMax];
+  // Row constants of the entry: member m, beam w at [m * 64 + w]
+  struct Rows {
+    float mx[kEnsMax * 64], logsum[kEnsMax * 64];
+    float wt[kEnsMax];
+    float lp[64];
+    int fin[64];
+  };
+  __device__ __forceinline__ int members() const { return n; }
+  __device__ __forceinline__ void begin(Rows& s) const {       // the weights, visible to the workgroup on return
+    if (threadIdx.x < kEnsMax) s.wt[threadIdx.x] = (int)threadIdx.x < n ? w[threadIdx.x] : 0.f;
+    __syncthreads();
+  }
+  __device__ __forceinline__ float weight(int m) const {       // (a select chain: no dynamic index into the arguments)
+    float wt = 0.f;
+#pragma unroll
+    for (int k = 0; k < kEnsMax; ++k)
+      if (k == m) wt = w[k];
+    return wt;
+  }
+  __device__ __forceinline__ bool live(const Rows& s, int m) const { return s.wt[m] > 0.f; }
+  // member m's logits are mstride floats behind member 0's
+  __device__ __forceinline__ float step_lp(const float* __restrict__ lg, size_t mstride, int f, int w, const Rows& s) const {
+    float a[kEnsMax];
+    float A = -INFINITY;
+#pragma unroll
+    for (int m = 0; m < kEnsMax; ++m) {
+      a[m] = -INFINITY;
+      if (m < n && s.wt[m] > 0.f) {
+        a[m] = (lg[m * mstride + f] - s.mx[m * 64 + w]) - s.logsum[m * 64 + w];
+        A = fmaxf(A, a[m]);
+      }
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int m = 0; m < kEnsMax; ++m)
+      if (m < n && s.wt[m] > 0.f) sum += s.wt[m] * expf(a[m] - A);      // member order 0, 1, ...
+    return A + logf(sum);
+  }
+};
+
+// unpenalised total of candidate (beam w, word v), flat index f, of the entry whose member-0 logits start at lg:
+// _mask_probs for a finished beam
+template <class P>
+__device__ __forceinline__ float cand_total(const P& pol, const float* __restrict__ lg, size_t mstride, int f, int w, int v,
+                                            int end_id, const typename P::Rows& s) {
+  const float step = s.fin[w] ? ((v == end_id) ? 0.f : -FLT_MAX) : pol.step_lp(lg, mstride, f, w, s);   // dtype.min
+  return s.lp[w] + step;
+}
+
+// all-(-inf) / all-NaN corner of a selection round: the lowest untaken flat index (matches a stable sort)
+__device__ __forceinline__ int lowest_untaken(const int* sel, int r) {
+  int f = 0;
+  bool again = true;
+  while (again) {
+    again = false;
+    for (int q = 0; q < r; ++q)
+      if (sel[q] == f) {
+        ++f;
+        again = true;
+      }
+  }
+  return f;
+}
+
+// the W chosen flat indices of an entry -> its outputs and new state; `total` is the unpenalised total of slot tid
+__device__ __forceinline__ void write_beam(int o, int f, float score, float total, const int* fin, const long long* len, int V,
+                                           int end_id, float* __restrict__ log_probs, int32_t* __restrict__ finished,
+                                           int64_t* __restrict__ lengths, int32_t* __restrict__ word_ids,
+                                           int32_t* __restrict__ parent_ids, float* __restrict__ scores) {
+  const int parent = f / V, word = f - parent * V;
+  const int prev_fin = fin[parent];
+  word_ids[o] = word;
+  parent_ids[o] = parent;
+  scores[o] = score;
+  log_probs[o] = total;
+  finished[o] = (prev_fin || word == end_id) ? 1 : 0;
+  lengths[o] = len[parent] + (prev_fin ? 0 : 1);
+}
+
+// ---- one workgroup per batch entry -----------------------------------------------------------------------------------
+template <class P>
+__global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict__ logits, P pol, float* __restrict__ log_probs,
+                                                        int32_t* __restrict__ finished, int64_t* __restrict__ lengths,
+                                                        int32_t* __restrict__ word_ids, int32_t* __restrict__ parent_ids,
+                                                        float* __restrict__ scores, int B, int W, int V, int end_id,
+                                                        float lpw, const int32_t* __restrict__ stop, int stop_t) {
+  __shared__ ValIdx sh[256];
+  __shared__ typename P::Rows s;
+  __shared__ int s_sel[64];
+  __shared__ float s_selv[64];
+  __shared__ long long s_len[64];
+  if (comic_stopped(stop, stop_t)) return;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t mstride = (size_t)B * W * V;
+  const float* lg = logits + (size_t)b * W * V;
+  // the entry's beam state (W <= 64): loaded first, in flight behind the passes over the logits
+  float lp_w = 0.f;
+  int fin_w = 0;
+  long long len_w = 0;
+  if (tid < W) {
+    lp_w = log_probs[b * W + tid];
+    fin_w = finished[b * W + tid];
+    len_w = lengths[b * W + tid];
+  }
+  pol.begin(s);
+  // log-softmax constants per (member, beam): one wave per row
+  for (int p = wave; p < pol.members() * W; p += 4) {
+    const int m = pol.members() > 1 ? p / W : 0, w = p - m * W;
+    if (!pol.live(s, m)) continue;
+    const float* row = lg + m * mstride + (size_t)w * V;
+    float mx = -INFINITY;
+    for (int v = lane; v < V; v += 64) mx = fmaxf(mx, row[v]);
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int v = lane; v < V; v += 64) sum += expf(row[v] - mx);
+    sum = wave_sum(sum);
+    if (lane == 0) {
+      s.mx[m * 64 + w] = mx;
+      s.logsum[m * 64 + w] = logf(sum);
+    }
+  }
+  if (tid < W) {
+    s.lp[tid] = lp_w;
+    s.fin[tid] = fin_w;
+    s_len[tid] = len_w;
+  }
+  __syncthreads();
+  const int total = W * V;
+  for (int r = 0; r < W; ++r) {
+    float bv = -INFINITY;
+    int bi = kNone;
+    for (int f = tid; f < total; f += 256) {
+      bool taken = false;
+      for (int q = 0; q < r; ++q) taken |= (s_sel[q] == f);
+      if (taken) continue;
+      const int w = f / V, v = f - w * V;
+      float tot = cand_total(pol, lg, mstride, f, w, v, end_id, s);
+      if (lpw != 0.f) {
+        const long long len = s_len[w] + ((s.fin[w] || v == end_id) ? 0 : 1);
+        tot = tot / powf((5.f + (float)len) / 6.f, lpw);
+      }
+      if (better(tot, f, bv, bi)) {
+        bv = tot;
+        bi = f;
+      }
+    }
+    const ValIdx best = block_argmax(bv, bi, sh);
+    if (tid == 0) {
+      s_sel[r] = best.i == kNone ? lowest_untaken(s_sel, r) : best.i;
+      s_selv[r] = best.v;
+    }
+    __syncthreads();
+  }
+  if (tid < W) {
+    const int f = s_sel[tid], parent = f / V, word = f - parent * V;
+    // the state carries the unpenalised total log probability of the chosen candidate
+    const float state = lpw != 0.f ? cand_total(pol, lg, mstride, f, parent, word, end_id, s) : s_selv[tid];
+    write_beam(b * W + tid, f, s_selv[tid], state, s.fin, s_len, V, end_id, log_probs, finished, lengths, word_ids, parent_ids,
+               scores);
+  }
+}
+
+// ---- large vocabularies: the step split over `chunks` workgroups per entry ------------------------------------------------
+// partials at [((m * B + b) * W + w) * chunks + c]
+template <class P>
+__global__ __launch_bounds__(256) void beam_stats_kernel(const float* __restrict__ logits, P pol, float* __restrict__ pmax,
+                                                         float* __restrict__ psum, int B, int W, int V, int chunks,
+                                                         const int32_t* __restrict__ stop, int stop_t) {
+  if (comic_stopped(stop, stop_t)) return;
+  __shared__ float sh[4];
+  const int c = blockIdx.x, w = blockIdx.y, m = pol.members() > 1 ? blockIdx.z / B : 0, b = blockIdx.z - m * B;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (!(pol.weight(m) > 0.f)) return;         // (uniform over the workgroup) a zero-weight member is never read
+  const int per = (V + chunks - 1) / chunks, v0 = c * per, v1 = min(V, v0 + per);
+  const size_t rowi = ((size_t)m * B + b) * W + w;
+  const float* row = logits + rowi * V;
+  float mx = -INFINITY;
+  for (int v = v0 + tid; v < v1; v += 256) mx = fmaxf(mx, row[v]);
+  mx = wave_max(mx);
+  if (lane == 0) sh[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+  __syncthreads();
+  float sum = 0.f;
+  for (int v = v0 + tid; v < v1; v += 256) sum += expf(row[v] - mx);
+  sum = wave_sum(sum);
+  if (lane == 0) sh[wave] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    pmax[rowi * chunks + c] = mx;
+    psum[rowi * chunks + c] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  }
+}
+
+// KLOCAL > 0: a thread's share of the W * nv candidates (column v0 + tid + 256 * k of every beam) fits in KLOCAL registers.
+// It is formed ONCE, with all loads in flight together, and the W selection rounds run on the register copy (the
+// rescanning form pays an L2 round trip per element and round: 31 -> 9 us at W = 3, V = 25 599).  0: the rescanning form.
+// The launcher picks the capacity (16 / 40 / 0).
+template <class P, int KLOCAL>
+__global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __restrict__ logits, P pol,
+                                                              const float* __restrict__ log_probs,
+                                                              const int32_t* __restrict__ finished,
+                                                              const float* __restrict__ pmax, const float* __restrict__ psum,
+                                                              float* __restrict__ cand_v, int32_t* __restrict__ cand_i, int B,
+                                                              int W, int V, int chunks, int end_id,
+                                                              const int32_t* __restrict__ stop, int stop_t) {
+  __shared__ ValIdx sh[256];
+  __shared__ typename P::Rows s;
+  __shared__ int s_sel[64];
+  if (comic_stopped(stop, stop_t)) return;
+  const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t mstride = (size_t)B * W * V;
+  const float* lg = logits + (size_t)b * W * V;
+  // the entry's beam state (W <= 64): loaded first, in flight behind the partials
+  float lp_w = 0.f;
+  int fin_w = 0;
+  if (tid < W) {
+    lp_w = log_probs[b * W + tid];
+    fin_w = finished[b * W + tid];
+  }
+  pol.begin(s);
+  // row constants from the per-chunk partials: one wave per (member, beam), one lane per chunk (chunks <= 32), partials
+  // combined in chunk order so that every workgroup of the entry gets the same bits
+  for (int p = wave; p < pol.members() * W; p += 4) {
+    const int m = pol.members() > 1 ? p / W : 0, w = p - m * W;
+    if (!pol.live(s, m)) continue;
+    const size_t o = (((size_t)m * B + b) * W + w) * chunks;
+    const float pm = lane < chunks ? pmax[o + lane] : -INFINITY;
+    const float ps = lane < chunks ? psum[o + lane] : 0.f;
+    const float mx = wave_max(pm);
+    const float term = lane < chunks ? ps * expf(pm - mx) : 0.f;
+    float sum = 0.f;
+    for (int k = 0; k < chunks; ++k) sum += __shfl(term, k, 64);      // fixed order: chunk 0, 1, ...
+    if (lane == 0) {
+      s.mx[m * 64 + w] = mx;
+      s.logsum[m * 64 + w] = logf(sum);
+    }
+  }
+  if (tid < W) {
+    s.lp[tid] = lp_w;
+    s.fin[tid] = fin_w;
+  }
+  __syncthreads();
+  const int per = (V + chunks - 1) / chunks, v0 = c * per, v1 = min(V, v0 + per), nv = max(0, v1 - v0);
+  const size_t out = ((size_t)b * chunks + c) * W;
+  constexpr int kLocal = KLOCAL > 0 ? KLOCAL : 1;
+  const int kper = (nv + 255) >> 8;                 // columns per thread and beam
+  if (KLOCAL > 0 && W * kper <= kLocal) {
+    __shared__ ValIdx sh8[8];
+    float tv[kLocal];
+    int ti[kLocal];
+    int w = 0, k = 0;                               // (beam, column slot) of register slot e: scalar counters
+#pragma unroll
+    for (int e = 0; e < kLocal; ++e) {
+      tv[e] = -INFINITY;
+      ti[e] = kNone;
+      const int v = v0 + tid + 256 * k;
+      if (w < W && v < v1) {
+        const int f = w * V + v;
+        tv[e] = cand_total(pol, lg, mstride, f, w, v, end_id, s);
+        ti[e] = f;
+      }
+      if (++k == kper) {
+        k = 0;
+        ++w;
+      }
+    }
+    for (int r = 0; r < W; ++r) {
+      float bv = -INFINITY;
+      int bi = kNone;
+#pragma unroll
+      for (int e = 0; e < kLocal; ++e)
+        if (ti[e] != kNone && better(tv[e], ti[e], bv, bi)) {
+          bv = tv[e];
+          bi = ti[e];
+        }
+      const ValIdx best = block_argmax_1b(bv, bi, sh8, r & 1);
+#pragma unroll
+      for (int e = 0; e < kLocal; ++e)
+        if (ti[e] == best.i) ti[e] = kNone;         // taken (flat indices are unique; kNone marks "none")
+      if (tid == 0) {
+        cand_v[out + r] = best.v;
+        cand_i[out + r] = best.i;
+      }
+    }
+    return;
+  }
+  const int total = W * nv;
+  for (int r = 0; r < W; ++r) {
+    float bv = -INFINITY;
+    int bi = kNone;
+    for (int j = tid; j < total; j += 256) {
+      const int w = j / nv, v = v0 + (j - w * nv);
+      const int f = w * V + v;
+      bool taken = false;
+      for (int q = 0; q < r; ++q) taken |= (s_sel[q] == f);
+      if (taken) continue;
+      const float tot = cand_total(pol, lg, mstride, f, w, v, end_id, s);
+      if (better(tot, f, bv, bi)) {
+        bv = tot;
+        bi = f;
+      }
+    }
+    const ValIdx best = block_argmax(bv, bi, sh);
+    if (tid == 0) {
+      s_sel[r] = best.i;                            // kNone when the chunk has fewer than r + 1 candidates
+      cand_v[out + r] = best.v;
+      cand_i[out + r] = best.i;
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict__ cand_v, const int32_t* __restrict__ cand_i,
+                                                         float* __restrict__ log_probs, int32_t* __restrict__ finished,
+                                                         int64_t* __restrict__ lengths, int32_t* __restrict__ word_ids,
+                                                         int32_t* __restrict__ parent_ids, float* __restrict__ scores, int W,
+                                                         int V, int chunks, int end_id, const int32_t* __restrict__ stop,
+                                                         int stop_t) {
+  __shared__ ValIdx sh[256];
+  __shared__ int s_fin[64], s_sel[64];
+  __shared__ float s_selv[64];
+  __shared__ long long s_len[64];
+  if (comic_stopped(stop, stop_t)) return;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (tid < W) {                       // (W <= 64)
+    s_fin[tid] = finished[b * W + tid];
+    s_len[tid] = lengths[b * W + tid];
+  }
+  __syncthreads();
+  const int n = chunks * W;
+  const float* cv = cand_v + (size_t)b * n;
+  const int32_t* ci = cand_i + (size_t)b * n;
+  for (int r = 0; r < W; ++r) {
+    float bv = -INFINITY;
+    int bi = kNone;
+    for (int j = tid; j < n; j += 256) {
+      const int f = ci[j];
+      if (f == kNone) continue;
+      bool taken = false;
+      for (int q = 0; q < r; ++q) taken |= (s_sel[q] == f);
+      if (taken) continue;
+      if (better(cv[j], f, bv, bi)) {
+        bv = cv[j];
+        bi = f;
+      }
+    }
+    const ValIdx best = block_argmax(bv, bi, sh);
+    if (tid == 0) {
+      s_sel[r] = best.i == kNone ? lowest_untaken(s_sel, r) : best.i;
+      s_selv[r] = best.v;
+    }
+    __syncthreads();
+  }
+  if (tid < W)
+    write_beam(b * W + tid, s_sel[tid], s_selv[tid], s_selv[tid], s_fin, s_len, V, end_id, log_probs, finished, lengths,
+               word_ids, parent_ids, scores);
+}
+
+thread_local int g_ens_step_path = 0;
+
+// The ONE launcher: one workgroup per entry, or -- without a length penalty (it ranks by score, not by log probability),
+// with enough candidates, at least two chunks and a workspace that holds the partials -- the split form.
+template <class P>
+int beam_step_launch(const P& pol, int n, const float* logits, float* log_probs, int32_t* finished, int64_t* lengths,
+                     int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int V, int end_id, float lpw, void* ws,
+                     int64_t ws_bytes, hipStream_t st, int* path) {
+  const int chunks = comic_beam_step_chunks(B, V);
+  const bool split = lpw == 0.f && (long)W * V >= 8192 && chunks >= 2 && ws &&
+                     ws_bytes >= comic_beam_step_split_bytes(n, B, W, chunks);
+  if (path) *path = split ? 1 : 0;
+  if (!split) {
+    hipLaunchKernelGGL(beam_step_kernel<P>, dim3(B), dim3(256), 0, st, logits, pol, log_probs, finished, lengths, word_ids,
+                       parent_ids, scores, B, W, V, end_id, lpw, g_comic_stop.p, g_comic_stop.t);
+    COMIC_LAUNCH_CHECK(P::kName);
+    return 0;
+  }
+  float* pmax = (float*)ws;
+  float* psum = pmax + (size_t)n * B * W * chunks;
+  float* cand_v = psum + (size_t)n * B * W * chunks;
+  int32_t* cand_i = (int32_t*)(cand_v + (size_t)B * chunks * W);
+  hipLaunchKernelGGL(beam_stats_kernel<P>, dim3(chunks, W, n * B), dim3(256), 0, st, logits, pol, pmax, psum, B, W, V, chunks,
+                     g_comic_stop.p, g_comic_stop.t);
+  {
+    const int per = (V + chunks - 1) / chunks, kper = (per + 255) / 256;
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(chunks, B), dim3(256), 0, st, logits, pol, (const float*)log_probs,
+                         (const int32_t*)finished, (const float*)pmax, (const float*)psum, cand_v, cand_i, B, W, V, chunks,
+                         end_id, g_comic_stop.p, g_comic_stop.t);
+    };
+    if (W * kper <= 16) launch(beam_chunk_topk_kernel<P, 16>);
+    else if (W * kper <= 40) launch(beam_chunk_topk_kernel<P, 40>);
+    else launch(beam_chunk_topk_kernel<P, 0>);
+  }
+  hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, st, (const float*)cand_v, (const int32_t*)cand_i, log_probs,
+                     finished, lengths, word_ids, parent_ids, scores, W, V, chunks, end_id, g_comic_stop.p, g_comic_stop.t);
+  COMIC_LAUNCH_CHECK(P::kSplitName);
+  return 0;
+}
+
+}  // namespace
+
+// executor-internal: the single-member step with BeamSearchDecoder's length penalty (length_penalty_weight; 0 = none) and
+// a workspace (may be null) for the split form
+int comic_beam_step_ws(const float* logits, float* log_probs, int32_t* finished, int64_t* lengths, int32_t* word_ids,
+                       int32_t* parent_ids, float* scores, int B, int W, int V, int end_id, float lpw, void* ws,
+                       int64_t ws_bytes, hipStream_t st) {
+  COMIC_REQUIRE(logits && log_probs && finished && lengths && word_ids && parent_ids && scores,
+                "beam_step: null pointer");
+  COMIC_REQUIRE(W >= 1 && W <= 64, "beam_step: beam width must be in [1,64] (got %d)", W);
+  COMIC_REQUIRE((long)W * V < (1L << 31) && W <= V, "beam_step: beam*V too large or beam > V");
+  return beam_step_launch(OneMember{}, 1, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V, end_id,
+                          lpw, ws, ws_bytes, st, nullptr);
+}
+extern "C" int comic_beam_step(const float* logits, float* log_probs, int32_t* finished, int64_t* lengths,
+                               int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int V, int end_id,
+                               void* stream) {
+  return comic_beam_step_ws(logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V, end_id, 0.f, nullptr,
+                            0, (hipStream_t)stream);
+}
+
+extern "C" int comic_beam_step_ensemble_path(void) { return g_ens_step_path; }
+
+extern "C" int64_t comic_beam_step_ensemble_workspace(int n_models, int B, int W, int V) {
+  if (n_models < 1 || n_models > kEnsMax || B <= 0 || W <= 0 || V <= 0) return -1;
+  return comic_beam_step_split_bytes(n_models, B, W, comic_beam_step_chunks(B, V));
+}
+
+extern "C" int comic_beam_step_ensemble(const float* logits, const float* weights, int n_models, float* log_probs,
+                                        int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids,
+                                        float* scores, int B, int W, int V, int end_id, float length_penalty_weight,
+                                        void* workspace, int64_t workspace_bytes, void* stream) {
+  COMIC_REQUIRE(logits && weights && log_probs && finished && lengths && word_ids && parent_ids && scores,
+                "beam_step_ensemble: null pointer");
+  COMIC_REQUIRE(n_models >= 1 && n_models <= kEnsMax, "beam_step_ensemble: 1 to %d members (got %d)", kEnsMax, n_models);
+  COMIC_REQUIRE(B > 0 && W >= 1 && W <= 64, "beam_step_ensemble: beam width must be in [1,64] (got %d)", W);
+  COMIC_REQUIRE(V > 0 && W <= V && (long)W * V < (1L << 31), "beam_step_ensemble: beam*V too large or beam > V");
+  COMIC_REQUIRE((long)n_models * B <= 65535, "beam_step_ensemble: members * batch too large");
+  Ensemble pol{};
+  pol.n = n_models;
+  float wsum = 0.f;
+  for (int m = 0; m < n_models; ++m) {
+    COMIC_REQUIRE(weights[m] >= 0.f && weights[m] <= FLT_MAX, "beam_step_ensemble: weight %d is negative or not finite", m);
+    pol.w[m] = weights[m];
+    wsum += weights[m];
+  }
+  COMIC_REQUIRE(wsum > 0.f, "beam_step_ensemble: every weight is zero");
+  return beam_step_launch(pol, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V, end_id,
+                          length_penalty_weight, workspace, workspace_bytes, (hipStream_t)stream, &g_ens_step_path);
+}

@@ -24,6 +24,9 @@ struct ComicStop {
 extern thread_local ComicStop g_comic_stop;
 __device__ __forceinline__ bool comic_stopped(const int32_t* p, int t) { return p && p[0] <= t; }
 
+// most members of an ensemble beam search (beam_step.hip's row constants and the executor's member arrays are sized by it)
+constexpr int kEnsMax = 8;
+
 #define COMIC_LAUNCH_CHECK(name)                                               \
   do {                                                                         \
     hipError_t e__ = hipGetLastError();                                        \

@@ -66,7 +66,7 @@ int comic_embed_bwd_set(const int32_t* ids, const float* dout, float* dtable, in
 int comic_gemm_bf16x3_impl(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int lda,
                            int ldb, int ldc, int trans_a, int trans_b, float alpha, float beta, void* ws,
                            int64_t ws_bytes, hipStream_t st);
-// decode.hip
+// beam_logits.hip
 bool comic_beam_logits_supported(int D, int V, int R, int W);
 int64_t comic_beam_logits_pack_bytes(int D, int V);
 int64_t comic_beam_logits_partial_floats(int D, int V, int R, int W, int max_steps);
@@ -114,11 +114,14 @@ int comic_beam_step_small(const float* logits, const float* bias, int S, int ld,
                           int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B,
                           int W, int V, int end_id, void* cnt, int32_t* steps_executed, int t, int max_steps,
                           const LstmPrepArgs* prep, hipStream_t st);
-int comic_beam_step_lp(const float* logits, float* log_probs, int32_t* finished, int64_t* lengths, int32_t* word_ids,
-                       int32_t* parent_ids, float* scores, int B, int W, int V, int end_id, float lpw, hipStream_t st);
+// beam_step.hip
 int comic_beam_step_ws(const float* logits, float* log_probs, int32_t* finished, int64_t* lengths, int32_t* word_ids,
-                       int32_t* parent_ids, float* scores, int B, int W, int V, int end_id, void* ws, int64_t ws_bytes,
-                       hipStream_t st);
+                       int32_t* parent_ids, float* scores, int B, int W, int V, int end_id, float lpw, void* ws,
+                       int64_t ws_bytes, hipStream_t st);
+int64_t comic_beam_step_split_bytes(int n, int B, int W, int chunks);
+// decode.hip
+int comic_ens_gather_state(const float* c, const float* h, const float* att, const int32_t* parent, float* c_out,
+                           float* h_out, float* att_out, int R, int W, int D, int A, hipStream_t st);
 // decoder_fused.hip
 int comic_fused_step_supported(int D, int Wd);
 long comic_lstm_panel_floats(int D, int Wd, int mode);
@@ -1890,8 +1893,65 @@ extern "C" int comic_beam_step_dense(const float* y, const float* W_o, const flo
     return comic_beam_step_small(region, nullptr, 1, V, 0, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V,
                                  end_id, cnt, steps, 0, 1, nullptr, st);
   }
-  return comic_beam_step_ws(region, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V, end_id, splitk,
+  return comic_beam_step_ws(region, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V, end_id, 0.f, splitk,
                             kSplitKBytes, st);
+}
+
+// ---- beam search: what a single decoder and every member of an ensemble share ---------------------------------------------
+struct BeamMember {
+  bool fused = false, stream_lstm = false;
+  int mem_div = 1, ld_wo = 0, cur = 0;
+  comic_attn_desc ad{};
+  const float* values = nullptr;
+  const float* w_o = nullptr;      // (with ld_wo) set by the loop that projects with the GEMM
+  StreamBufs sm{};
+};
+// The member's state before step 0: tiled inputs, keys / values, initial c / h / attention, and its LSTM weights packed for
+// the step kernel its shape selects.
+static int beam_member_begin(const comic_decoder_desc* d, const comic_decoder_params* p, const float* fm, const float* im_embed,
+                             int B, int W, InferBufs& ws, hipStream_t st, BeamMember& e) {
+  const int R = B * W, D = d->D, E = d->E, A = d->A, M = d->M;
+  // tile_batch BEFORE keys are computed (model_base.py:127-131).  The beams of an entry attend to the same memory: the
+  // fused step's attention kernel reads row b / W of keys / values held ONCE per entry (same values as the tiled copy's)
+  e.fused = fused_step_enabled() && comic_fused_step_supported(D, E + A + D);
+  e.mem_div = e.fused ? W : 1;
+  {
+    const long n1 = (long)R * M * d->C, n2 = (long)R * d->Cg;
+    if (e.mem_div == 1)
+      hipLaunchKernelGGL(tile_rows_kernel, dim3((unsigned)cdiv64(n1, 256)), dim3(256), 0, st, fm, ws.fm_t, n1, W,
+                         M * d->C);
+    hipLaunchKernelGGL(tile_rows_kernel, dim3((unsigned)cdiv64(n2, 256)), dim3(256), 0, st, im_embed, ws.im_t, n2, W,
+                       d->Cg);
+    COMIC_LAUNCH_CHECK("tile_rows");
+  }
+  e.ad = attn_desc(d, R);
+  if (e.mem_div == 1) RC(memory_projections(d, p, ws.fm_t, R, ws.keys, ws.values_buf, &e.values, st));
+  else RC(memory_projections(d, p, fm, B, ws.keys, ws.values_buf, &e.values, st));
+  RC(rnn_init_fwd(d, p, ws.im_t, R, nullptr, ws.ib, ws.c[0], ws.h[0], st));
+  RC(fill(ws.att[0], 0.f, (long)R * A, st));
+  e.stream_lstm = e.fused && lstm_stream_enabled() && comic_lstm_stream_supported(D, E, A, R) &&
+                  comic_lstm_stream_part_bytes(D, E + A + D, R) <= kSplitKBytes;
+  e.sm = StreamBufs{ws.kfrag, ws.xfrag, ws.yfrag, nullptr};
+  if (e.stream_lstm) {
+    RC(comic_lstm_stream_pack(p->K, ws.kfrag, D, E + A + D, st));
+    if (comic_stream_gemm_supported(D, D, R) && comic_stream_gemm_part_bytes(D, D, R) <= kSplitKBytes) {
+      RC(comic_stream_gemm_pack(p->W_q, ws.wqfrag, D, D, st));
+      e.sm.wqfrag = ws.wqfrag;
+    }
+  } else if (e.fused) RC(comic_pack_lstm_panels(p->K, ws.kpanel, nullptr, D, E + A + D, st));
+  return 0;
+}
+// Where a step writes: fused, the raw outputs ping-pong into c / h / att[nxt] and the NEXT step's operand prep gathers them
+// through the parents chosen in between (no gather / copy / embedding kernels); unfused, they land in gtmp and the loop
+// re-orders them itself.  *att_new is the step's new attention state in either form.
+static StepBufs beam_step_bufs(const comic_decoder_desc* d, const InferBufs& ws, bool fused, int nxt, int R, float** att_new) {
+  StepBufs sb = ws.sb;
+  sb.c2 = fused ? ws.c[nxt] : ws.gtmp;
+  sb.h2 = fused ? ws.h[nxt] : ws.gtmp + (size_t)R * d->D;
+  *att_new = fused ? ws.att[nxt] : ws.gtmp + (size_t)2 * R * d->D;
+  if (!d->context_layer) sb.ctx = *att_new;
+  else sb.att2 = *att_new;
+  return sb;
 }
 
 extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decoder_params* p, const float* fm,
@@ -1912,40 +1972,15 @@ extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decod
   COMIC_REQUIRE(ws.ok, "beam: workspace overflow");
   g_splitk_ws = ws.splitk;
   const int D = d->D, E = d->E, A = d->A, V = d->V, M = d->M, H = d->H;
-  // tile_batch BEFORE keys are computed (model_base.py:127-131).  The beams of an entry attend to the same memory: the
-  // fused step's attention kernel reads row b / W of keys / values held ONCE per entry (same values as the tiled copy's)
-  const bool fused = fused_step_enabled() && comic_fused_step_supported(D, E + A + D);
-  const int mem_div = fused ? W : 1;
-  {
-    const long n1 = (long)R * M * d->C, n2 = (long)R * d->Cg;
-    if (mem_div == 1)
-      hipLaunchKernelGGL(tile_rows_kernel, dim3((unsigned)cdiv64(n1, 256)), dim3(256), 0, st, fm, ws.fm_t, n1, W,
-                         M * d->C);
-    hipLaunchKernelGGL(tile_rows_kernel, dim3((unsigned)cdiv64(n2, 256)), dim3(256), 0, st, im_embed, ws.im_t, n2, W,
-                       d->Cg);
-    COMIC_LAUNCH_CHECK("tile_rows");
-  }
-  const comic_attn_desc ad = attn_desc(d, R);
-  const float* values = nullptr;
-  if (mem_div == 1) RC(memory_projections(d, p, ws.fm_t, R, ws.keys, ws.values_buf, &values, st));
-  else RC(memory_projections(d, p, fm, B, ws.keys, ws.values_buf, &values, st));
-  RC(rnn_init_fwd(d, p, ws.im_t, R, nullptr, ws.ib, ws.c[0], ws.h[0], st));
-  RC(fill(ws.att[0], 0.f, (long)R * A, st));
   // initial beam state: log_probs [0,-inf,...], finished [0,1,...], lengths 0
   hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, ws.log_probs, finished, lengths, R, W);
   hipLaunchKernelGGL(fill_i32_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, ws.ids, d->start_id, (long)R);
   hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(64), 0, st, steps_executed, max_steps, 1L);
   COMIC_LAUNCH_CHECK("beam init");
-  const bool stream_lstm = fused && lstm_stream_enabled() && comic_lstm_stream_supported(D, E, A, R) &&
-                           comic_lstm_stream_part_bytes(D, E + A + D, R) <= kSplitKBytes;
-  StreamBufs sm{ws.kfrag, ws.xfrag, ws.yfrag, nullptr};
-  if (stream_lstm) {
-    RC(comic_lstm_stream_pack(p->K, ws.kfrag, D, E + A + D, st));
-    if (comic_stream_gemm_supported(D, D, R) && comic_stream_gemm_part_bytes(D, D, R) <= kSplitKBytes) {
-      RC(comic_stream_gemm_pack(p->W_q, ws.wqfrag, D, D, st));
-      sm.wqfrag = ws.wqfrag;
-    }
-  } else if (fused) RC(comic_pack_lstm_panels(p->K, ws.kpanel, nullptr, D, E + A + D, st));
+  BeamMember mem;
+  RC(beam_member_begin(d, p, fm, im_embed, B, W, ws, st, mem));
+  const bool fused = mem.fused, stream_lstm = mem.stream_lstm;
+  StreamBufs& sm = mem.sm;
   // large vocabularies: projection + per-chunk top-k as one streaming launch over a packed W_o (beam_logits.hip)
   // (a length penalty ranks by score, not by log probability: its step runs the one-workgroup-per-entry kernel)
   const float lpw = d->length_penalty_weight;
@@ -1959,8 +1994,6 @@ extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decod
   const bool stream_wo = small_step && stream_lstm && comic_stream_gemm_supported(D, V, R) &&
                          comic_stream_gemm_part_bytes(D, V, R) <= kSplitKBytes &&
                          comic_stream_gemm_wfrag_floats(D, V) <= (int64_t)(D + 1) * wo_pad_cols(V);
-  int ld_wo = V;
-  const float* w_o = nullptr;
   if (stream_logits) {
     RC(comic_beam_pack_wo(p->W_o, p->b_o, V, ws.wo_pad, D, V, st));
     RC(comic_beam_logits_begin(ws.logits, B, W, V, max_steps, st));
@@ -1973,7 +2006,7 @@ extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decod
       sm.wo_N = V;
     }
   } else {
-    w_o = aligned_w_o(d, p, ws.wo_pad, &ld_wo, st);
+    mem.w_o = aligned_w_o(d, p, ws.wo_pad, &mem.ld_wo, st);
   }
   if (small_step) RC(comic_beam_counters_zero(ws.beam_cnt, max_steps, st));
   g_beam_path = (stream_logits ? 1 : 0) | (stream_lstm ? 2 : 0) | (small_step ? 4 : 0);
@@ -1992,14 +2025,12 @@ extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decod
     int32_t* word = step_ids + (size_t)t * R;
     int32_t* parent = parent_ids + (size_t)t * R;
     const int nxt = cur ^ 1;
+    float* att_new;
+    StepBufs sb = beam_step_bufs(d, ws, fused, nxt, R, &att_new);
     if (fused) {
-      // raw step outputs ping-pong in c/h/att[]; the NEXT step's operand prep gathers them through the
-      // parents chosen here (no gather / copy / embedding kernels in between)
-      StepBufs sb = ws.sb;
-      sb.c2 = ws.c[nxt];
-      sb.h2 = ws.h[nxt];
-      if (!d->context_layer) sb.ctx = ws.att[nxt];
-      else sb.att2 = ws.att[nxt];
+      // (with the streaming LSTM step the merge / the small step also gathers the next step's operand rows: raw c / h /
+      // attention outputs of this step through the parents it has just chosen)
+      const LstmPrepArgs prep{p->emb, att_new, sb.h2, sb.c2, (uint4*)ws.xfrag, ws.gtmp, E, A, D, V, (E + A + D + 31) / 32};
       const int32_t* ids_in = t == 0 ? ws.ids : step_ids + (size_t)(t - 1) * R;
       const int32_t* par_in = t == 0 ? nullptr : parent_ids + (size_t)(t - 1) * R;
       sm.skip_prep = (stream_lstm && (stream_logits || small_step) && t > 0) ? 1 : 0;
@@ -2012,32 +2043,23 @@ extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decod
       if (stream_logits && stream_lstm && sm.wqfrag) {
         // projection launch first, with the query projection's workgroups riding on the CUs its chunks leave idle; the
         // attention step (which needs q) and the merge (which gathers the attention output) follow
-        const float* att_new = d->context_layer ? sb.att2 : sb.ctx;
-        LstmPrepArgs prep{p->emb, att_new, sb.h2, sb.c2, (uint4*)ws.xfrag, ws.gtmp, E, A, D, V, (E + A + D + 31) / 32};
         int n_q = 0, q_lds = 0;
         const LstmStreamArgs qa = comic_stream_gemm_args(ws.yfrag, ws.wqfrag, (float*)g_splitk_ws, R, D, D, &sm.q_S, &n_q, &q_lds,
                                                          std::max(8, 256 - comic_beam_logits_chunks(V)));
         RC(comic_beam_logits_launch(sb.y, ws.yfrag, ws.wo_pad, ws.logits, max_steps, B, W, D, V, &qa, n_q, q_lds, st));
-        RC(infer_step_attend(d, p, ad, ws.keys, values, sb, attn_hist + (size_t)t * R * H * M, R, st, smp, mem_div));
+        RC(infer_step_attend(d, p, mem.ad, ws.keys, mem.values, sb, attn_hist + (size_t)t * R * H * M, R, st, smp, mem.mem_div));
         RC(comic_beam_merge_launch(ws.logits, ws.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
                                    steps_executed, t, max_steps, B, W, V, d->end_id, &prep, st));
         cur = nxt;
         continue;
       }
-      RC(infer_step_attend(d, p, ad, ws.keys, values, sb, attn_hist + (size_t)t * R * H * M, R, st, smp, mem_div));
+      RC(infer_step_attend(d, p, mem.ad, ws.keys, mem.values, sb, attn_hist + (size_t)t * R * H * M, R, st, smp, mem.mem_div));
       if (stream_logits) {
-        // (with the streaming LSTM step the merge also gathers the next step's operand rows: raw c / h / attention
-        // outputs of this step through the parents it has just chosen)
-        const float* att_new = d->context_layer ? sb.att2 : sb.ctx;
-        LstmPrepArgs prep{p->emb, att_new, sb.h2, sb.c2, (uint4*)ws.xfrag, ws.gtmp, E, A, D, V, (E + A + D + 31) / 32};
         RC(comic_beam_logits_step(sb.y, stream_lstm ? ws.yfrag : nullptr, ws.wo_pad, ws.logits, ws.log_probs, finished, lengths, word, parent,
                                   scores + (size_t)t * R, steps_executed, t, max_steps, B, W, D, V, d->end_id,
                                   stream_lstm ? &prep : nullptr, st));
       } else if (small_step) {
-        // small vocabulary: the entry's whole step in one workgroup, which also keeps steps_executed and (with the
-        // streaming LSTM step) gathers the next step's operand rows
-        const float* att_new = d->context_layer ? sb.att2 : sb.ctx;
-        LstmPrepArgs prep{p->emb, att_new, sb.h2, sb.c2, (uint4*)ws.xfrag, ws.gtmp, E, A, D, V, (E + A + D + 31) / 32};
+        // small vocabulary: the entry's whole step in one workgroup, which also keeps steps_executed
         if (stream_wo) {     // vocabulary projection through the streaming kernel: K-slice partials, summed by the step kernel
           int S = sm.wo_S;
           const int ldp = (V + 63) / 64 * 64;
@@ -2050,39 +2072,25 @@ extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decod
                                    word, parent, scores + (size_t)t * R, B, W, V, d->end_id, ws.beam_cnt + t, steps_executed,
                                    t, max_steps, &prep, st));
         } else {
-          RC(gemm_big(sb.y, w_o, ws.logits, p->b_o, R, V, D, D, ld_wo, V, 0, 0, 0.f, st));
+          RC(gemm_big(sb.y, mem.w_o, ws.logits, p->b_o, R, V, D, D, mem.ld_wo, V, 0, 0, 0.f, st));
           RC(comic_beam_step_small(ws.logits, nullptr, 1, V, 0, ws.log_probs, finished, lengths, word, parent,
                                    scores + (size_t)t * R, B, W, V, d->end_id, ws.beam_cnt + t, steps_executed, t, max_steps,
                                    stream_lstm ? &prep : nullptr, st));
         }
       } else {
-        RC(gemm_big(sb.y, w_o, ws.logits, p->b_o, R, V, D, D, ld_wo, V, 0, 0, 0.f, st));
-        if (lpw != 0.f)
-          RC(comic_beam_step_lp(ws.logits, ws.log_probs, finished, lengths, word, parent, scores + (size_t)t * R, B, W, V,
-                                d->end_id, lpw, st));
-        else
-          RC(comic_beam_step_ws(ws.logits, ws.log_probs, finished, lengths, word, parent, scores + (size_t)t * R, B, W, V,
-                                d->end_id, g_splitk_ws, kSplitKBytes, st));
+        RC(gemm_big(sb.y, mem.w_o, ws.logits, p->b_o, R, V, D, D, mem.ld_wo, V, 0, 0, 0.f, st));
+        RC(comic_beam_step_ws(ws.logits, ws.log_probs, finished, lengths, word, parent, scores + (size_t)t * R, B, W, V,
+                              d->end_id, lpw, g_splitk_ws, kSplitKBytes, st));
       }
     } else {
       if (t > 0) (void)hipMemcpyAsync(ws.ids, step_ids + (size_t)(t - 1) * R, sizeof(int32_t) * R,
                                       hipMemcpyDeviceToDevice, st);
       RC(comic_embed_fwd(p->emb, ws.ids, ws.x, R, E, V, (void*)st));
-      StepBufs sb = ws.sb;
-      sb.c2 = ws.gtmp;
-      sb.h2 = ws.gtmp + (size_t)R * D;
-      float* att_new = ws.gtmp + (size_t)2 * R * D;
-      if (!d->context_layer) sb.ctx = att_new;
-      else sb.att2 = att_new;
-      RC(infer_step(d, p, ad, ws.keys, values, ws.x, ws.c[cur], ws.h[cur], ws.att[cur], sb,
+      RC(infer_step(d, p, mem.ad, ws.keys, mem.values, ws.x, ws.c[cur], ws.h[cur], ws.att[cur], sb,
                     attn_hist + (size_t)t * R * H * M, R, st));
-      RC(gemm_big(sb.y, w_o, ws.logits, p->b_o, R, V, D, D, ld_wo, V, 0, 0, 0.f, st));
-      if (lpw != 0.f)
-        RC(comic_beam_step_lp(ws.logits, ws.log_probs, finished, lengths, word, parent, scores + (size_t)t * R, B, W, V,
-                              d->end_id, lpw, st));
-      else
-        RC(comic_beam_step_ws(ws.logits, ws.log_probs, finished, lengths, word, parent, scores + (size_t)t * R, B, W, V,
-                              d->end_id, g_splitk_ws, kSplitKBytes, st));
+      RC(gemm_big(sb.y, mem.w_o, ws.logits, p->b_o, R, V, D, D, mem.ld_wo, V, 0, 0, 0.f, st));
+      RC(comic_beam_step_ws(ws.logits, ws.log_probs, finished, lengths, word, parent, scores + (size_t)t * R, B, W, V,
+                            d->end_id, lpw, g_splitk_ws, kSplitKBytes, st));
       RC(comic_gather_rows(sb.c2, parent, ws.c[nxt], R, W, D, (void*)st));
       RC(comic_gather_rows(sb.h2, parent, ws.h[nxt], R, W, D, (void*)st));
       RC(comic_gather_rows(att_new, parent, ws.att[nxt], R, W, A, (void*)st));
@@ -2100,17 +2108,13 @@ extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decod
 // rnn_decoder_beam_search (ops_rnn.py:49-112) over the MEAN of the members' step distributions.  An executor of its own
 // beside comic_decoder_beam: that loop picks one of three fused projection + top-k launches per shape, each of which owns a
 // single member's W_o; here every member runs its own wrapper step on its own InferBufs, writes its logits into one slab,
-// and one ensemble step (beam_ensemble.hip) ranks the candidates for all of them.  Members follow the SAME ids / parents.
-int comic_ens_gather_state(const float* c, const float* h, const float* att, const int32_t* parent, float* c_out,
-                           float* h_out, float* att_out, int R, int W, int D, int A, hipStream_t st);
-
+// and one ensemble step (beam_step.hip) ranks the candidates for all of them.  Members follow the SAME ids / parents.
 namespace {
-constexpr int kEnsMembers = 8;
 // Workspace of the ensemble loop: the members' InferBufs one after another, then the shared blocks.  carve_ens is the ONE
 // definition: comic_decoder_beam_ensemble_workspace runs it over a null base.
 struct EnsBufs {
-  InferBufs m[kEnsMembers];
-  float* alpha[kEnsMembers];       // one step's [R][H][M] alignments of a member whose history nobody asked for
+  InferBufs m[kEnsMax];
+  float* alpha[kEnsMax];       // one step's [R][H][M] alignments of a member whose history nobody asked for
   float *logits, *log_probs;       // [n][R][V] slab, [R]
   int32_t* ids;                    // [R] start ids
   void* step_ws;
@@ -2119,7 +2123,7 @@ struct EnsBufs {
   bool ok;
 };
 // bytes of the ensemble step's workspace for any split of `rows` into batch x beam: (2 n + 2) * rows * chunks words, chunks <= 32
-int64_t ens_step_ws_bound(int n, int rows) { return ((int64_t)(2 * n + 2) * rows * 32) * 4 + 1024; }
+int64_t ens_step_ws_bound(int n, int rows) { return comic_beam_step_split_bytes(n, rows, 1, 32); }
 EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64_t bytes) {
   EnsBufs e{};
   size_t off = 0;
@@ -2141,20 +2145,12 @@ EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64
   e.bytes = off + w.off;
   return e;
 }
-struct EnsMember {
-  bool fused = false, stream_lstm = false;
-  int mem_div = 1, ld_wo = 0, cur = 0;
-  comic_attn_desc ad{};
-  const float* values = nullptr;
-  const float* w_o = nullptr;
-  StreamBufs sm{};
-};
 }  // namespace
 
 extern "C" int64_t comic_decoder_beam_ensemble_workspace(const comic_decoder_desc* descs, int n_models, int rows,
                                                          int max_steps) {
   (void)max_steps;
-  if (!descs || n_models < 1 || n_models > kEnsMembers || rows <= 0) return -1;
+  if (!descs || n_models < 1 || n_models > kEnsMax || rows <= 0) return -1;
   for (int m = 0; m < n_models; ++m)
     if (descs[m].D <= 0 || descs[m].V <= 0 || descs[m].M <= 0 || descs[m].H <= 0) return -1;
   return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0).bytes;
@@ -2168,7 +2164,7 @@ extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, cons
   COMIC_REQUIRE(descs && params && fms && im_embeds && weights && step_ids && parent_ids && scores && lengths && finished &&
                     steps_executed && workspace,
                 "beam_ensemble: null pointer");
-  COMIC_REQUIRE(n_models >= 1 && n_models <= kEnsMembers, "beam_ensemble: 1 to %d members (got %d)", kEnsMembers, n_models);
+  COMIC_REQUIRE(n_models >= 1 && n_models <= kEnsMax, "beam_ensemble: 1 to %d members (got %d)", kEnsMax, n_models);
   COMIC_REQUIRE(B > 0 && W > 0 && W <= 64 && max_steps > 0, "beam_ensemble: bad shape");
   const int n = n_models, R = B * W, V = descs[0].V;
   for (int m = 0; m < n; ++m) {
@@ -2184,40 +2180,14 @@ extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, cons
   COMIC_REQUIRE(L.ok && (int64_t)L.bytes <= workspace_bytes, "beam_ensemble: workspace too small");
   g_splitk_ws = L.m[0].splitk;               // members run back to back on the one stream: one split-K scratch serves all
   const float lpw = descs[0].length_penalty_weight;
-  EnsMember mem[kEnsMembers];
+  BeamMember mem[kEnsMax];
   for (int m = 0; m < n; ++m) {
     const comic_decoder_desc* d = &descs[m];
     const comic_decoder_params* p = &params[m];
     FlagScope flag_scope__(d);
     InferBufs& ws = L.m[m];
-    EnsMember& e = mem[m];
-    const int D = d->D, E = d->E, A = d->A, M = d->M;
-    e.fused = fused_step_enabled() && comic_fused_step_supported(D, E + A + D);
-    e.mem_div = e.fused ? W : 1;              // fused attention reads keys / values held once per entry (see comic_decoder_beam)
-    {
-      const long n1 = (long)R * M * d->C, n2 = (long)R * d->Cg;
-      if (e.mem_div == 1)
-        hipLaunchKernelGGL(tile_rows_kernel, dim3((unsigned)cdiv64(n1, 256)), dim3(256), 0, st, fms[m], ws.fm_t, n1, W,
-                           M * d->C);
-      hipLaunchKernelGGL(tile_rows_kernel, dim3((unsigned)cdiv64(n2, 256)), dim3(256), 0, st, im_embeds[m], ws.im_t, n2, W,
-                         d->Cg);
-      COMIC_LAUNCH_CHECK("tile_rows");
-    }
-    e.ad = attn_desc(d, R);
-    if (e.mem_div == 1) RC(memory_projections(d, p, ws.fm_t, R, ws.keys, ws.values_buf, &e.values, st));
-    else RC(memory_projections(d, p, fms[m], B, ws.keys, ws.values_buf, &e.values, st));
-    RC(rnn_init_fwd(d, p, ws.im_t, R, nullptr, ws.ib, ws.c[0], ws.h[0], st));
-    RC(fill(ws.att[0], 0.f, (long)R * A, st));
-    e.stream_lstm = e.fused && lstm_stream_enabled() && comic_lstm_stream_supported(D, E, A, R) &&
-                    comic_lstm_stream_part_bytes(D, E + A + D, R) <= kSplitKBytes;
-    e.sm = StreamBufs{ws.kfrag, ws.xfrag, ws.yfrag, nullptr};
-    if (e.stream_lstm) {
-      RC(comic_lstm_stream_pack(p->K, ws.kfrag, D, E + A + D, st));
-      if (comic_stream_gemm_supported(D, D, R) && comic_stream_gemm_part_bytes(D, D, R) <= kSplitKBytes) {
-        RC(comic_stream_gemm_pack(p->W_q, ws.wqfrag, D, D, st));
-        e.sm.wqfrag = ws.wqfrag;
-      }
-    } else if (e.fused) RC(comic_pack_lstm_panels(p->K, ws.kpanel, nullptr, D, E + A + D, st));
+    BeamMember& e = mem[m];
+    RC(beam_member_begin(d, p, fms[m], im_embeds[m], B, W, ws, st, e));
     e.w_o = aligned_w_o(d, p, ws.wo_pad, &e.ld_wo, st);
   }
   hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, L.log_probs, finished, lengths, R, W);
@@ -2242,18 +2212,14 @@ extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, cons
       const comic_decoder_params* p = &params[m];
       FlagScope flag_scope__(d);
       InferBufs& ws = L.m[m];
-      EnsMember& e = mem[m];
+      BeamMember& e = mem[m];
       const int D = d->D, E = d->E, A = d->A;
       float* hist = (attn_hists && attn_hists[m]) ? attn_hists[m] + (size_t)t * R * d->H * d->M : L.alpha[m];
       float* lg = L.logits + (size_t)m * R * V;
-      StepBufs sb = ws.sb;
+      const int cur = e.cur, nxt = cur ^ 1;
+      float* att_new;
+      StepBufs sb = beam_step_bufs(d, ws, e.fused, nxt, R, &att_new);
       if (e.fused) {
-        // raw step outputs ping-pong in c/h/att[]; the next step's operand prep gathers them through the shared parents
-        const int cur = e.cur, nxt = cur ^ 1;
-        sb.c2 = ws.c[nxt];
-        sb.h2 = ws.h[nxt];
-        if (!d->context_layer) sb.ctx = ws.att[nxt];
-        else sb.att2 = ws.att[nxt];
         e.sm.skip_prep = 0;
         e.sm.wo_part = nullptr;
         StreamBufs* smp = e.stream_lstm ? &e.sm : nullptr;
@@ -2261,11 +2227,6 @@ extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, cons
         RC(infer_step_attend(d, p, e.ad, ws.keys, e.values, sb, hist, R, st, smp, e.mem_div));
         e.cur = nxt;
       } else {
-        sb.c2 = ws.gtmp;
-        sb.h2 = ws.gtmp + (size_t)R * D;
-        float* att_new = ws.gtmp + (size_t)2 * R * D;
-        if (!d->context_layer) sb.ctx = att_new;
-        else sb.att2 = att_new;
         if (t > 0) RC(comic_ens_gather_state(sb.c2, sb.h2, att_new, par_in, ws.c[0], ws.h[0], ws.att[0], R, W, D, A, st));
         RC(comic_embed_fwd(p->emb, ids_in, ws.x, R, E, V, (void*)st));
         RC(infer_step(d, p, e.ad, ws.keys, e.values, ws.x, ws.c[0], ws.h[0], ws.att[0], sb, hist, R, st));

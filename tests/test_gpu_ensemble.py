@@ -78,6 +78,8 @@ def ref_select(lp, log_probs, finished, lengths, end_id, lpw):
 # (n, B, W, V): smallest case; radix vocabulary; split form with V not divisible by its 8 chunks; maximum member count
 SHAPES = [(1, 2, 3, 17), (3, 3, 3, 258), (2, 2, 5, 9001), (8, 1, 2, 300)]
 STEP_CASES = [(s, state, lpw) for s in SHAPES for state in ('init', 'mid') for lpw in (0.0, 0.7)]
+# the rescanning form of the split step: 8 chunks of 1126 columns, 5 per thread x 9 beams = 45 > 40 register slots
+STEP_CASES.append(((2, 2, 9, 9001), 'mid', 0.0))
 STEP_SEED = 0             # checked on the CPU: the float64 reference of every case meets the rank gap at twice the bar
 
 
@@ -103,7 +105,7 @@ def step_case(shape, state, lpw, seed=None):
     return dict(logits=logits, wts=wts, end_id=end_id, log_probs=log_probs, finished=finished, lengths=lengths, ref=ref)
 
 
-def run_step(logits, wts, log_probs, finished, lengths, end_id, lpw):
+def run_step(logits, wts, log_probs, finished, lengths, end_id, lpw, workspace=True):
     lib = L.load()
     n, B, W, V = logits.shape
     d_lg, d_lp, d_fin, d_len = dev(logits), dev(log_probs), dev(finished), dev(lengths)
@@ -113,10 +115,11 @@ def run_step(logits, wts, log_probs, finished, lengths, end_id, lpw):
     nbytes = int(lib.comic_beam_step_ensemble_workspace(n, B, W, V))
     assert nbytes > 0
     ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    ws_ptr, ws_bytes = (ws.data_ptr(), nbytes) if workspace else (None, 0)
     wt = (C.c_float * n)(*[float(w) for w in wts])
     L.check(lib.comic_beam_step_ensemble(d_lg.data_ptr(), wt, n, d_lp.data_ptr(), d_fin.data_ptr(), d_len.data_ptr(),
                                          word.data_ptr(), parent.data_ptr(), scores.data_ptr(), B, W, V, end_id, float(lpw),
-                                         ws.data_ptr(), nbytes, stream()), 'beam_step_ensemble')
+                                         ws_ptr, ws_bytes, stream()), 'beam_step_ensemble')
     sync()
     return dict(word=word.cpu().numpy(), parent=parent.cpu().numpy(), scores=scores.cpu().numpy(),
                 log_probs=d_lp.cpu().numpy(), finished=d_fin.cpu().numpy(), lengths=d_len.cpu().numpy(),
@@ -136,6 +139,25 @@ def test_ensemble_step_matches_float64(shape, state, lpw):
         np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
     assert_close(got['scores'], ref['scores'], F32_RTOL, 'scores')
     assert_close(got['log_probs'], ref['log_probs'], F32_RTOL, 'new log_probs')
+
+
+@pytest.mark.parametrize('state', ['init', 'mid'])
+def test_one_member_of_weight_1_is_comic_beam_step(state):
+    """n = 1, weights [1.0], no workspace against comic_beam_step: the logits are finite, so the ensemble's
+    a + logf(1 * expf(0)) is a exactly and the outputs and the new state are equal to the bit."""
+    c = step_case((1, 3, 3, 258), state, 0.0)
+    ens = run_step(c['logits'], [1.0], c['log_probs'], c['finished'], c['lengths'], c['end_id'], 0.0, workspace=False)
+    B, W, V = c['logits'].shape[1:]
+    d_lg, d_lp, d_fin, d_len = dev(c['logits'][0]), dev(c['log_probs']), dev(c['finished']), dev(c['lengths'])
+    word = torch.full((B, W), -1, dtype=torch.int32, device=DEV)
+    parent = torch.full((B, W), -1, dtype=torch.int32, device=DEV)
+    scores = torch.zeros((B, W), dtype=torch.float32, device=DEV)
+    L.check(L.load().comic_beam_step(d_lg.data_ptr(), d_lp.data_ptr(), d_fin.data_ptr(), d_len.data_ptr(), word.data_ptr(),
+                                     parent.data_ptr(), scores.data_ptr(), B, W, V, c['end_id'], stream()), 'beam_step')
+    sync()
+    one = dict(word=word, parent=parent, scores=scores, log_probs=d_lp, finished=d_fin, lengths=d_len)
+    for k, v in one.items():
+        np.testing.assert_array_equal(ens[k], v.cpu().numpy(), err_msg=k)
 
 
 @pytest.mark.parametrize('shape', [(2, 3, 3, 258), (2, 2, 5, 9001)])

@@ -1137,7 +1137,11 @@ def test_beam_step_vs_oracle_step():
     assert word.cpu().numpy()[0, 0] == 5 and word.cpu().numpy()[0, 1] == 9
 
 
-@pytest.mark.parametrize('B,W,V,D', [(4, 3, 258, 128), (5, 8, 9000, 128), (6, 3, 8962, 256), (3, 5, 1000, 64), (4, 3, 2500, 96)])
+# the last three: GEMM + the single-member split step (D = 96, 1024 < V < 4096, W * V >= 8192), one case per form of its chunk
+# top-W: 3 chunks of 1034 columns, 5 per thread x 3 beams = 15 register slots (capacity 16); 2 chunks of 1250, 5 x 5 = 25
+# (capacity 40); 5 x 9 = 45 (the rescanning form)
+@pytest.mark.parametrize('B,W,V,D', [(4, 3, 258, 128), (5, 8, 9000, 128), (6, 3, 8962, 256), (3, 5, 1000, 64), (4, 3, 2500, 96),
+                                     (4, 3, 3100, 96), (4, 5, 2500, 96), (4, 9, 2500, 96)])
 def test_beam_step_dense_vs_oracle_step(B, W, V, D):
     """One beam step from the decoder outputs through the kernels the decode loop uses for the shape (streaming projection
     + chunk top-k + merge; register-resident small step; GEMM + comic_beam_step) against the [TF-1.9] step restated in
