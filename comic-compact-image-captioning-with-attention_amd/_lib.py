@@ -90,6 +90,11 @@ class DecoderParams(C.Structure):
     _fields_ = [(n, c_void_p) for n in PARAM_NAMES]
 
 
+class BeamConstraints(C.Structure):  # struct comic_beam_constraints
+    _fields_ = [(n, c_int32) for n in ('min_length', 'no_repeat_ngram', 'ngram_stride', 'n_suppress')] + [
+        ('suppress', c_int32 * 32)]
+
+
 class GemmProb(C.Structure):         # struct comic_gemm_prob
     _fields_ = [(n, c_void_p) for n in ('A', 'B', 'C', 'bias', 'mask')] + [(n, c_int32) for n in (
         'M', 'N', 'K', 'lda', 'ldb', 'ldc', 'ld_mask')] + [(n, c_float) for n in ('alpha', 'beta', 'keep')] + [
@@ -182,6 +187,12 @@ _SIGS = {
     'comic_beam_step_ensemble_path': (c_int, []),
     'comic_decoder_beam_ensemble_workspace': (c_int64, [P, c_int, c_int, c_int]),
     'comic_decoder_beam_ensemble': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int64, P]),
+    'comic_beam_bans': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    'comic_beam_step_constrained': (c_int, [P, P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, c_int, P,
+                                            c_int64, P]),
+    'comic_decoder_beam_constrained_workspace': (c_int64, [P, c_int, c_int, c_int]),
+    'comic_decoder_beam_constrained': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, c_int64,
+                                               P]),
     'comic_scorer_create': (c_void_p, [c_char_p, P, c_int64, c_double]),
     'comic_scorer_destroy': (None, [c_void_p]),
     'comic_scorer_score': (c_int, [c_void_p, P, c_int, P, P, P, P, c_int]),

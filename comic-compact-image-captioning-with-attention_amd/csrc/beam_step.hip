@@ -18,6 +18,13 @@
 //                 other than 1 adds log wt, and the single path would pay an expf / logf per candidate.)
 // The policy also owns the row constants a workgroup keeps in LDS: [64] per beam for one member, [kEnsMax * 64] for several.
 //
+// Which candidates a live beam may not emit is a second, orthogonal policy (constrained beam search):
+//   NoBans ... none: the code of the step as it always was
+//   Bans ..... bit v of row (b, w) of `bits` [B*W][words] (beam_bans.hip builds it before the step) bans candidate (w, v):
+//              its step log-probability is -inf.  Applied AFTER the log-softmax -- the normaliser counts banned tokens,
+//              so survivors keep their scores -- and to live beams only (_mask_probs is untouched).  One L2-resident word
+//              load and a bit test per candidate, however many tokens are banned.
+//
 // Two forms, one copy of each kernel, instantiated per policy:
 //   beam_step_kernel ........ one workgroup per batch entry: any V, length penalty included
 //   beam_stats_kernel ....... per (chunk, beam, entry, member): max and sum exp(x - max) of the chunk
@@ -107,12 +114,25 @@ struct Ensemble {
   }
 };
 
-// unpenalised total of candidate (beam w, word v), flat index f, of the entry whose member-0 logits start at lg:
-// _mask_probs for a finished beam
-template <class P>
-__device__ __forceinline__ float cand_total(const P& pol, const float* __restrict__ lg, size_t mstride, int f, int w, int v,
-                                            int end_id, const typename P::Rows& s) {
-  const float step = s.fin[w] ? ((v == end_id) ? 0.f : -FLT_MAX) : pol.step_lp(lg, mstride, f, w, s);   // dtype.min
+struct NoBans {
+  __device__ __forceinline__ NoBans entry(int, int) const { return NoBans{}; }
+  __device__ __forceinline__ bool hit(int, int) const { return false; }
+};
+struct Bans {
+  const uint32_t* bits;      // [B * W][words]
+  int words;
+  // the masks of entry b's W beams
+  __device__ __forceinline__ Bans entry(int b, int W) const { return Bans{bits + (size_t)b * W * words, words}; }
+  __device__ __forceinline__ bool hit(int w, int v) const { return (bits[(size_t)w * words + (v >> 5)] >> (v & 31)) & 1u; }
+};
+
+// unpenalised total of candidate (beam w, word v), flat index f, of the entry whose member-0 logits start at lg and whose
+// bans are bn: _mask_probs for a finished beam, -inf for a banned candidate of a live one
+template <class P, class Bn>
+__device__ __forceinline__ float cand_total(const P& pol, const Bn& bn, const float* __restrict__ lg, size_t mstride, int f,
+                                            int w, int v, int end_id, const typename P::Rows& s) {
+  const float step = s.fin[w] ? ((v == end_id) ? 0.f : -FLT_MAX)                                         // dtype.min
+                              : (bn.hit(w, v) ? -INFINITY : pol.step_lp(lg, mstride, f, w, s));
   return s.lp[w] + step;
 }
 
@@ -147,8 +167,8 @@ __device__ __forceinline__ void write_beam(int o, int f, float score, float tota
 }
 
 // ---- one workgroup per batch entry -----------------------------------------------------------------------------------
-template <class P>
-__global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict__ logits, P pol, float* __restrict__ log_probs,
+template <class P, class Bn>
+__global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict__ logits, P pol, Bn bans, float* __restrict__ log_probs,
                                                         int32_t* __restrict__ finished, int64_t* __restrict__ lengths,
                                                         int32_t* __restrict__ word_ids, int32_t* __restrict__ parent_ids,
                                                         float* __restrict__ scores, int B, int W, int V, int end_id,
@@ -162,6 +182,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t mstride = (size_t)B * W * V;
   const float* lg = logits + (size_t)b * W * V;
+  const Bn bn = bans.entry(b, W);
   // the entry's beam state (W <= 64): loaded first, in flight behind the passes over the logits
   float lp_w = 0.f;
   int fin_w = 0;
@@ -203,7 +224,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
       for (int q = 0; q < r; ++q) taken |= (s_sel[q] == f);
       if (taken) continue;
       const int w = f / V, v = f - w * V;
-      float tot = cand_total(pol, lg, mstride, f, w, v, end_id, s);
+      float tot = cand_total(pol, bn, lg, mstride, f, w, v, end_id, s);
       if (lpw != 0.f) {
         const long long len = s_len[w] + ((s.fin[w] || v == end_id) ? 0 : 1);
         tot = tot / powf((5.f + (float)len) / 6.f, lpw);
@@ -223,7 +244,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
   if (tid < W) {
     const int f = s_sel[tid], parent = f / V, word = f - parent * V;
     // the state carries the unpenalised total log probability of the chosen candidate
-    const float state = lpw != 0.f ? cand_total(pol, lg, mstride, f, parent, word, end_id, s) : s_selv[tid];
+    const float state = lpw != 0.f ? cand_total(pol, bn, lg, mstride, f, parent, word, end_id, s) : s_selv[tid];
     write_beam(b * W + tid, f, s_selv[tid], state, s.fin, s_len, V, end_id, log_probs, finished, lengths, word_ids, parent_ids,
                scores);
   }
@@ -265,8 +286,8 @@ __global__ __launch_bounds__(256) void beam_stats_kernel(const float* __restrict
 // It is formed ONCE, with all loads in flight together, and the W selection rounds run on the register copy (the
 // rescanning form pays an L2 round trip per element and round: 31 -> 9 us at W = 3, V = 25 599).  0: the rescanning form.
 // The launcher picks the capacity (16 / 40 / 0).
-template <class P, int KLOCAL>
-__global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __restrict__ logits, P pol,
+template <class P, class Bn, int KLOCAL>
+__global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __restrict__ logits, P pol, Bn bans,
                                                               const float* __restrict__ log_probs,
                                                               const int32_t* __restrict__ finished,
                                                               const float* __restrict__ pmax, const float* __restrict__ psum,
@@ -280,6 +301,7 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
   const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t mstride = (size_t)B * W * V;
   const float* lg = logits + (size_t)b * W * V;
+  const Bn bn = bans.entry(b, W);
   // the entry's beam state (W <= 64): loaded first, in flight behind the partials
   float lp_w = 0.f;
   int fin_w = 0;
@@ -326,7 +348,7 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
       const int v = v0 + tid + 256 * k;
       if (w < W && v < v1) {
         const int f = w * V + v;
-        tv[e] = cand_total(pol, lg, mstride, f, w, v, end_id, s);
+        tv[e] = cand_total(pol, bn, lg, mstride, f, w, v, end_id, s);
         ti[e] = f;
       }
       if (++k == kper) {
@@ -364,7 +386,7 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
       bool taken = false;
       for (int q = 0; q < r; ++q) taken |= (s_sel[q] == f);
       if (taken) continue;
-      const float tot = cand_total(pol, lg, mstride, f, w, v, end_id, s);
+      const float tot = cand_total(pol, bn, lg, mstride, f, w, v, end_id, s);
       if (better(tot, f, bv, bi)) {
         bv = tot;
         bi = f;
@@ -430,8 +452,8 @@ thread_local int g_ens_step_path = 0;
 
 // The ONE launcher: one workgroup per entry, or -- without a length penalty (it ranks by score, not by log probability),
 // with enough candidates, at least two chunks and a workspace that holds the partials -- the split form.
-template <class P>
-int beam_step_launch(const P& pol, int n, const float* logits, float* log_probs, int32_t* finished, int64_t* lengths,
+template <class P, class Bn>
+int beam_step_launch(const P& pol, const Bn& bans, int n, const float* logits, float* log_probs, int32_t* finished, int64_t* lengths,
                      int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int V, int end_id, float lpw, void* ws,
                      int64_t ws_bytes, hipStream_t st, int* path) {
   const int chunks = comic_beam_step_chunks(B, V);
@@ -439,7 +461,7 @@ int beam_step_launch(const P& pol, int n, const float* logits, float* log_probs,
                      ws_bytes >= comic_beam_step_split_bytes(n, B, W, chunks);
   if (path) *path = split ? 1 : 0;
   if (!split) {
-    hipLaunchKernelGGL(beam_step_kernel<P>, dim3(B), dim3(256), 0, st, logits, pol, log_probs, finished, lengths, word_ids,
+    hipLaunchKernelGGL((beam_step_kernel<P, Bn>), dim3(B), dim3(256), 0, st, logits, pol, bans, log_probs, finished, lengths, word_ids,
                        parent_ids, scores, B, W, V, end_id, lpw, g_comic_stop.p, g_comic_stop.t);
     COMIC_LAUNCH_CHECK(P::kName);
     return 0;
@@ -453,13 +475,13 @@ int beam_step_launch(const P& pol, int n, const float* logits, float* log_probs,
   {
     const int per = (V + chunks - 1) / chunks, kper = (per + 255) / 256;
     auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(chunks, B), dim3(256), 0, st, logits, pol, (const float*)log_probs,
+      hipLaunchKernelGGL(kern, dim3(chunks, B), dim3(256), 0, st, logits, pol, bans, (const float*)log_probs,
                          (const int32_t*)finished, (const float*)pmax, (const float*)psum, cand_v, cand_i, B, W, V, chunks,
                          end_id, g_comic_stop.p, g_comic_stop.t);
     };
-    if (W * kper <= 16) launch(beam_chunk_topk_kernel<P, 16>);
-    else if (W * kper <= 40) launch(beam_chunk_topk_kernel<P, 40>);
-    else launch(beam_chunk_topk_kernel<P, 0>);
+    if (W * kper <= 16) launch(beam_chunk_topk_kernel<P, Bn, 16>);
+    else if (W * kper <= 40) launch(beam_chunk_topk_kernel<P, Bn, 40>);
+    else launch(beam_chunk_topk_kernel<P, Bn, 0>);
   }
   hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, st, (const float*)cand_v, (const int32_t*)cand_i, log_probs,
                      finished, lengths, word_ids, parent_ids, scores, W, V, chunks, end_id, g_comic_stop.p, g_comic_stop.t);
@@ -478,7 +500,7 @@ int comic_beam_step_ws(const float* logits, float* log_probs, int32_t* finished,
                 "beam_step: null pointer");
   COMIC_REQUIRE(W >= 1 && W <= 64, "beam_step: beam width must be in [1,64] (got %d)", W);
   COMIC_REQUIRE((long)W * V < (1L << 31) && W <= V, "beam_step: beam*V too large or beam > V");
-  return beam_step_launch(OneMember{}, 1, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V, end_id,
+  return beam_step_launch(OneMember{}, NoBans{}, 1, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V, end_id,
                           lpw, ws, ws_bytes, st, nullptr);
 }
 extern "C" int comic_beam_step(const float* logits, float* log_probs, int32_t* finished, int64_t* lengths,
@@ -495,25 +517,49 @@ extern "C" int64_t comic_beam_step_ensemble_workspace(int n_models, int B, int W
   return comic_beam_step_split_bytes(n_models, B, W, comic_beam_step_chunks(B, V));
 }
 
-extern "C" int comic_beam_step_ensemble(const float* logits, const float* weights, int n_models, float* log_probs,
-                                        int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids,
-                                        float* scores, int B, int W, int V, int end_id, float length_penalty_weight,
-                                        void* workspace, int64_t workspace_bytes, void* stream) {
+// the ensemble step's argument checks and launch; bits null: no bans (the code of comic_beam_step_ensemble as it was)
+static int ens_step(const char* who, const float* logits, const float* weights, int n_models, float* log_probs,
+                    int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W,
+                    int V, int end_id, float length_penalty_weight, const uint32_t* bits, int words, void* workspace,
+                    int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(logits && weights && log_probs && finished && lengths && word_ids && parent_ids && scores,
-                "beam_step_ensemble: null pointer");
-  COMIC_REQUIRE(n_models >= 1 && n_models <= kEnsMax, "beam_step_ensemble: 1 to %d members (got %d)", kEnsMax, n_models);
-  COMIC_REQUIRE(B > 0 && W >= 1 && W <= 64, "beam_step_ensemble: beam width must be in [1,64] (got %d)", W);
-  COMIC_REQUIRE(V > 0 && W <= V && (long)W * V < (1L << 31), "beam_step_ensemble: beam*V too large or beam > V");
-  COMIC_REQUIRE((long)n_models * B <= 65535, "beam_step_ensemble: members * batch too large");
+                "%s: null pointer", who);
+  COMIC_REQUIRE(n_models >= 1 && n_models <= kEnsMax, "%s: 1 to %d members (got %d)", who, kEnsMax, n_models);
+  COMIC_REQUIRE(B > 0 && W >= 1 && W <= 64, "%s: beam width must be in [1,64] (got %d)", who, W);
+  COMIC_REQUIRE(V > 0 && W <= V && (long)W * V < (1L << 31), "%s: beam*V too large or beam > V", who);
+  COMIC_REQUIRE((long)n_models * B <= 65535, "%s: members * batch too large", who);
   Ensemble pol{};
   pol.n = n_models;
   float wsum = 0.f;
   for (int m = 0; m < n_models; ++m) {
-    COMIC_REQUIRE(weights[m] >= 0.f && weights[m] <= FLT_MAX, "beam_step_ensemble: weight %d is negative or not finite", m);
+    COMIC_REQUIRE(weights[m] >= 0.f && weights[m] <= FLT_MAX, "%s: weight %d is negative or not finite", who, m);
     pol.w[m] = weights[m];
     wsum += weights[m];
   }
-  COMIC_REQUIRE(wsum > 0.f, "beam_step_ensemble: every weight is zero");
-  return beam_step_launch(pol, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V, end_id,
-                          length_penalty_weight, workspace, workspace_bytes, (hipStream_t)stream, &g_ens_step_path);
+  COMIC_REQUIRE(wsum > 0.f, "%s: every weight is zero", who);
+  if (bits)
+    return beam_step_launch(pol, Bans{bits, words}, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids, scores,
+                            B, W, V, end_id, length_penalty_weight, workspace, workspace_bytes, (hipStream_t)stream,
+                            &g_ens_step_path);
+  return beam_step_launch(pol, NoBans{}, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V,
+                          end_id, length_penalty_weight, workspace, workspace_bytes, (hipStream_t)stream, &g_ens_step_path);
+}
+
+extern "C" int comic_beam_step_ensemble(const float* logits, const float* weights, int n_models, float* log_probs,
+                                        int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids,
+                                        float* scores, int B, int W, int V, int end_id, float length_penalty_weight,
+                                        void* workspace, int64_t workspace_bytes, void* stream) {
+  return ens_step("beam_step_ensemble", logits, weights, n_models, log_probs, finished, lengths, word_ids, parent_ids, scores,
+                  B, W, V, end_id, length_penalty_weight, nullptr, 0, workspace, workspace_bytes, stream);
+}
+
+extern "C" int comic_beam_step_constrained(const float* logits, const float* weights, int n_models, float* log_probs,
+                                           int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids,
+                                           float* scores, int B, int W, int V, int end_id, float length_penalty_weight,
+                                           const uint32_t* bits, int words, void* workspace, int64_t workspace_bytes,
+                                           void* stream) {
+  COMIC_REQUIRE(bits, "beam_step_constrained: null ban mask");
+  COMIC_REQUIRE(V > 0 && words == (V + 31) / 32, "beam_step_constrained: %d mask words for a vocabulary of %d", words, V);
+  return ens_step("beam_step_constrained", logits, weights, n_models, log_probs, finished, lengths, word_ids, parent_ids,
+                  scores, B, W, V, end_id, length_penalty_weight, bits, words, workspace, workspace_bytes, stream);
 }

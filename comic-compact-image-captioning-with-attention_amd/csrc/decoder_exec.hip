@@ -119,6 +119,12 @@ int comic_beam_step_ws(const float* logits, float* log_probs, int32_t* finished,
                        int32_t* parent_ids, float* scores, int B, int W, int V, int end_id, float lpw, void* ws,
                        int64_t ws_bytes, hipStream_t st);
 int64_t comic_beam_step_split_bytes(int n, int B, int W, int chunks);
+// beam_bans.hip
+int comic_beam_constraints_check(const comic_beam_constraints* c, const char* who, int W, int V, int end_id, int max_steps,
+                                 bool whole);
+int comic_beam_bans_launch(const int32_t* prev_words, const int32_t* prev_parents, const int32_t* finished,
+                           const int64_t* lengths, int32_t* hist, uint32_t* bits, int t, int B, int W, int V, int max_steps,
+                           int end_id, const comic_beam_constraints* c, hipStream_t st);
 // decode.hip
 int comic_ens_gather_state(const float* c, const float* h, const float* att, const int32_t* parent, float* c_out,
                            float* h_out, float* att_out, int R, int W, int D, int A, hipStream_t st);
@@ -2111,7 +2117,8 @@ extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decod
 // and one ensemble step (beam_step.hip) ranks the candidates for all of them.  Members follow the SAME ids / parents.
 namespace {
 // Workspace of the ensemble loop: the members' InferBufs one after another, then the shared blocks.  carve_ens is the ONE
-// definition: comic_decoder_beam_ensemble_workspace runs it over a null base.
+// definition: comic_decoder_beam_ensemble_workspace runs it over a null base.  A constrained loop (ban_steps > 0) adds the
+// ban masks and the two history buffers of beam_bans.hip.
 struct EnsBufs {
   InferBufs m[kEnsMax];
   float* alpha[kEnsMax];       // one step's [R][H][M] alignments of a member whose history nobody asked for
@@ -2119,12 +2126,14 @@ struct EnsBufs {
   int32_t* ids;                    // [R] start ids
   void* step_ws;
   int64_t step_bytes;
+  uint32_t* bits;                  // [R][ceil(V / 32)] ban masks (constrained only)
+  int32_t* ban_hist;               // [2][R][max_steps] token histories in beam order (constrained only)
   size_t bytes;
   bool ok;
 };
 // bytes of the ensemble step's workspace for any split of `rows` into batch x beam: (2 n + 2) * rows * chunks words, chunks <= 32
 int64_t ens_step_ws_bound(int n, int rows) { return comic_beam_step_split_bytes(n, rows, 1, 32); }
-EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64_t bytes) {
+EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64_t bytes, int ban_steps = 0) {
   EnsBufs e{};
   size_t off = 0;
   e.ok = true;
@@ -2141,6 +2150,10 @@ EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64
   e.ids = w.take<int32_t>(R);
   e.step_bytes = ens_step_ws_bound(n, R);
   e.step_ws = w.take<char>((size_t)e.step_bytes);
+  if (ban_steps > 0) {
+    e.bits = w.take<uint32_t>((size_t)R * ((descs[0].V + 31) / 32));
+    e.ban_hist = w.take<int32_t>((size_t)2 * R * ban_steps);
+  }
   e.ok = e.ok && w.ok;
   e.bytes = off + w.off;
   return e;
@@ -2155,12 +2168,19 @@ extern "C" int64_t comic_decoder_beam_ensemble_workspace(const comic_decoder_des
     if (descs[m].D <= 0 || descs[m].V <= 0 || descs[m].M <= 0 || descs[m].H <= 0) return -1;
   return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0).bytes;
 }
+extern "C" int64_t comic_decoder_beam_constrained_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                            int max_steps) {
+  if (max_steps <= 0 || comic_decoder_beam_ensemble_workspace(descs, n_models, rows, max_steps) < 0) return -1;
+  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0, max_steps).bytes;
+}
 
-extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, const comic_decoder_params* params,
-                                           const float* const* fms, const float* const* im_embeds, const float* weights,
-                                           int n_models, int B, int W, int max_steps, int32_t* step_ids, int32_t* parent_ids,
-                                           float* scores, int64_t* lengths, int32_t* finished, float* const* attn_hists,
-                                           int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream) {
+// The ONE ensemble loop.  cons null: comic_decoder_beam_ensemble, launch for launch as it always was; else every step
+// builds the beams' ban masks first (beam_bans.hip) and ranks through them (the Bans policy of beam_step.hip).
+static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decoder_params* params, const float* const* fms,
+                             const float* const* im_embeds, const float* weights, int n_models, int B, int W, int max_steps,
+                             int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
+                             float* const* attn_hists, int32_t* steps_executed, const comic_beam_constraints* cons,
+                             void* workspace, int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(descs && params && fms && im_embeds && weights && step_ids && parent_ids && scores && lengths && finished &&
                     steps_executed && workspace,
                 "beam_ensemble: null pointer");
@@ -2175,8 +2195,9 @@ extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, cons
                   "beam_ensemble: member %d differs from member 0 in V / start_id / end_id", m);
   }
   COMIC_REQUIRE(W <= V && (long)W * V < (1L << 31), "beam_ensemble: beam*V too large or beam > V");
+  if (cons) RC(comic_beam_constraints_check(cons, "beam_constrained", W, V, descs[0].end_id, max_steps, true));
   hipStream_t st = (hipStream_t)stream;
-  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes);
+  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, cons ? max_steps : 0);
   COMIC_REQUIRE(L.ok && (int64_t)L.bytes <= workspace_bytes, "beam_ensemble: workspace too small");
   g_splitk_ws = L.m[0].splitk;               // members run back to back on the one stream: one split-K scratch serves all
   const float lpw = descs[0].length_penalty_weight;
@@ -2233,10 +2254,39 @@ extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, cons
       }
       RC(gemm_big(sb.y, e.w_o, lg, p->b_o, R, V, D, D, e.ld_wo, V, 0, 0, 0.f, st));
     }
-    RC(comic_beam_step_ensemble(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R, B,
-                                W, V, descs[0].end_id, lpw, L.step_ws, L.step_bytes, (void*)st));
+    if (cons) {
+      RC(comic_beam_bans_launch(t == 0 ? nullptr : (const int32_t*)ids_in, par_in, finished, lengths, L.ban_hist, L.bits, t, B,
+                                W, V, max_steps, descs[0].end_id, cons, st));
+      RC(comic_beam_step_constrained(L.logits, weights, n, L.log_probs, finished, lengths, word, parent,
+                                     scores + (size_t)t * R, B, W, V, descs[0].end_id, lpw, L.bits, (V + 31) / 32, L.step_ws,
+                                     L.step_bytes, (void*)st));
+    } else {
+      RC(comic_beam_step_ensemble(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
+                                  B, W, V, descs[0].end_id, lpw, L.step_ws, L.step_bytes, (void*)st));
+    }
     hipLaunchKernelGGL(all_finished_kernel, dim3(1), dim3(256), 0, st, finished, steps_executed, t, R, max_steps);
     COMIC_LAUNCH_CHECK("all_finished");
   }
   return 0;
+}
+
+extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                           const float* const* fms, const float* const* im_embeds, const float* weights,
+                                           int n_models, int B, int W, int max_steps, int32_t* step_ids, int32_t* parent_ids,
+                                           float* scores, int64_t* lengths, int32_t* finished, float* const* attn_hists,
+                                           int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream) {
+  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
+                           lengths, finished, attn_hists, steps_executed, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int comic_decoder_beam_constrained(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                              const float* const* fms, const float* const* im_embeds, const float* weights,
+                                              int n_models, int B, int W, int max_steps,
+                                              const comic_beam_constraints* constraints, int32_t* step_ids,
+                                              int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
+                                              float* const* attn_hists, int32_t* steps_executed, void* workspace,
+                                              int64_t workspace_bytes, void* stream) {
+  COMIC_REQUIRE(constraints, "beam_constrained: null constraints");
+  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
+                           lengths, finished, attn_hists, steps_executed, constraints, workspace, workspace_bytes, stream);
 }

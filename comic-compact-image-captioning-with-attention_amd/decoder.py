@@ -250,6 +250,105 @@ class FlatParams:
         return int(sum(int(np.prod(s)) if len(s) else 1 for s in self.shapes.values()))
 
 
+class BeamConstraints:
+    """What a beam may emit (comic_beam_constraints; extends rnn_decoder_beam_search, ops_rnn.py:49-112), in TOKENS:
+    min_length: no <EOS> before that many tokens; no_repeat_ngram = n: no n-gram twice (0: off), with windows that start at
+    multiples of ngram_stride (n % ngram_stride == 0; the radix word length makes the windows whole words); suppress: up to
+    32 token ids that are never emitted.  Immutable and hashable: decode contexts are keyed by it."""
+    MAX_SUPPRESS = 32
+    MAX_WORDS = 2048                 # mask words of a row: V <= 65 536
+
+    def __init__(self, min_length=0, no_repeat_ngram=0, ngram_stride=1, suppress=()):
+        self.min_length, self.no_repeat_ngram, self.ngram_stride = int(min_length), int(no_repeat_ngram), int(ngram_stride)
+        self.suppress = tuple(int(x) for x in suppress)
+
+    def key(self):
+        return (self.min_length, self.no_repeat_ngram, self.ngram_stride, self.suppress)
+
+    def __eq__(self, other):
+        return isinstance(other, BeamConstraints) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'BeamConstraints(min_length=%d, no_repeat_ngram=%d, ngram_stride=%d, suppress=%r)' % self.key()
+
+    @property
+    def active(self):
+        return bool(self.min_length > 0 or self.no_repeat_ngram > 0 or self.suppress)
+
+    def check(self, spec, beam, max_steps):
+        """The rules of the C side, on the host before any GPU call; raises ValueError naming the field."""
+        V = int(spec.V)
+        if self.min_length < 0:
+            raise ValueError('min_length must be >= 0, got %d' % self.min_length)
+        if self.no_repeat_ngram < 0:
+            raise ValueError('no_repeat_ngram must be >= 0, got %d' % self.no_repeat_ngram)
+        if self.ngram_stride < 1:
+            raise ValueError('ngram_stride must be >= 1, got %d' % self.ngram_stride)
+        if self.no_repeat_ngram % self.ngram_stride:
+            raise ValueError('no_repeat_ngram %d is no multiple of ngram_stride %d' % (self.no_repeat_ngram, self.ngram_stride))
+        if len(self.suppress) > self.MAX_SUPPRESS:
+            raise ValueError('suppress holds %d ids, at most %d' % (len(self.suppress), self.MAX_SUPPRESS))
+        for v in self.suppress:
+            if not 0 <= v < V:
+                raise ValueError('suppress: id %d is outside the vocabulary of %d' % (v, V))
+            if v == spec.end_id:
+                raise ValueError('suppress: end_id %d cannot be suppressed' % v)
+        if self.min_length >= max_steps:
+            raise ValueError('min_length %d is not below max_steps %d' % (self.min_length, max_steps))
+        if (V + 31) // 32 > self.MAX_WORDS:
+            raise ValueError('V = %d: constraints need a vocabulary of at most %d' % (V, 32 * self.MAX_WORDS))
+        need = int(beam) + len(self.suppress) + 1 + int(max_steps)
+        if V < need:
+            raise ValueError('V = %d is too small: beam %d + %d suppress + 1 + max_steps %d = %d candidates are needed'
+                             % (V, beam, len(self.suppress), max_steps, need))
+
+    def c_struct(self):
+        c = L.BeamConstraints()
+        c.min_length, c.no_repeat_ngram, c.ngram_stride = self.min_length, self.no_repeat_ngram, self.ngram_stride
+        c.n_suppress = len(self.suppress)
+        for k, v in enumerate(self.suppress):
+            c.suppress[k] = v
+        return c
+
+
+def constraints_from_config(c):
+    """The BeamConstraints a configuration asks for, or None when it asks for none.  infer_min_length and
+    infer_no_repeat_ngram count WORDS for `word` and `radix` tokens -- a radix word is len(number_to_base(len(wtoi),
+    radix_base)) tokens, so both are multiplied by that length and the n-gram windows are aligned to it -- and characters
+    for `char` tokens.  infer_suppress_words (a sequence or a comma-separated string) maps through wtoi; with radix tokens
+    a word is not a token and the field is refused."""
+    m, n, sup = (getattr(c, k, None) for k in ('infer_min_length', 'infer_no_repeat_ngram', 'infer_suppress_words'))
+    if isinstance(sup, str):
+        sup = [w for w in sup.split(',') if w]
+    if not m and not n and not sup:
+        return None
+    m, n, stride = int(m or 0), int(n or 0), 1
+    if c.token_type == 'radix':
+        if sup:
+            raise ValueError('infer_suppress_words: a word is not a token with radix tokens, words cannot be suppressed')
+        stride = len(number_to_base(len(c.wtoi), c.radix_base))
+        m, n = m * stride, n * stride
+    ids = []
+    for w in sup or ():
+        if w not in c.wtoi:
+            raise ValueError('infer_suppress_words: `%s` is not in the vocabulary' % (w,))
+        ids.append(int(c.wtoi[w]))
+    return BeamConstraints(min_length=m, no_repeat_ngram=n, ngram_stride=stride, suppress=ids)
+
+
+def constraints_dir_suffix(c):
+    """'_min{m}_ngram{n}_sup{k}' when the configuration sets any constraint field (in its own units), else ''."""
+    m, n, sup = (getattr(c, k, None) for k in ('infer_min_length', 'infer_no_repeat_ngram', 'infer_suppress_words'))
+    if m is None and n is None and sup is None:
+        return ''
+    if isinstance(sup, str):
+        sup = [w for w in sup.split(',') if w]
+    return '_min%d_ngram%d_sup%d' % (int(m or 0), int(n or 0), len(sup or ()))
+
+
 def process_inputs(captions, token_type):
     """ModelBase._process_inputs (model_base.py:501-528) on the host.
     -> inputs [B,T] int32, targets [B,T] int32, masks [B,T] fp32, lens [B] int32."""
@@ -815,12 +914,22 @@ class Decoder:
             return ctx.pred_host[:int(ctx.steps_host[0])].numpy().copy()
         return fetch
 
-    def beam_search(self, fm, im_embed, beam, max_steps, want_attention=True, use_graph=True, length_penalty_weight=0.0):
+    def beam_search(self, fm, im_embed, beam, max_steps, want_attention=True, use_graph=True, length_penalty_weight=0.0,
+                    constraints=None):
         """rnn_decoder_beam_search (ops_rnn.py:49-112).  Returns predicted_ids [T,B,W] (after
         gather_tree), scores [T,B,W] (with length_penalty_weight != 0: the penalised scores the beams were ranked by,
         BeamSearchDecoder's `scores` output), the raw step/parent ids and, unless want_attention=False, the
         beam-sorted alignment history [T,B*W,H*M] (numpy; BeamSearchDecoderMultiHead,
-        ops_rnn.py:807-845 -- host post-processing that only visualisation needs)."""
+        ops_rnn.py:807-845 -- host post-processing that only visualisation needs).
+        constraints: a BeamConstraints; active ones decode as a one-member ensemble through the constrained executor
+        (comic_decoder_beam_constrained), None / inactive ones change nothing."""
+        if constraints is not None and constraints.active:
+            constraints.check(self.spec, beam, max_steps)
+            ens = self.__dict__.get('_self_ensemble')
+            if ens is None:
+                ens = self._self_ensemble = EnsembleDecoder([self])
+            return ens.beam_search(fm, im_embed, beam, max_steps, want_attention=want_attention, use_graph=use_graph,
+                                   length_penalty_weight=length_penalty_weight, constraints=constraints)
         torch, s = self.torch, self.spec
         B, W = fm.shape[0], beam
         # (a non-zero length penalty is another captured graph: the weight is baked into the step kernel's arguments)
@@ -925,11 +1034,11 @@ class EnsembleDecoder:
         self.torch, self.lib, self.device = decoders[0].torch, decoders[0].lib, decoders[0].device
         self._ctxs = {}
 
-    def _ctx(self, B, W, max_steps, lpw, feats):
+    def _ctx(self, B, W, max_steps, lpw, feats, cons=None):
         """Persistent buffers (+ a hipGraph of the whole loop, captured on the second call with the shape), as
-        Decoder._infer_ctx."""
+        Decoder._infer_ctx.  cons: active BeamConstraints (they are baked into the captured launches) or None."""
         torch, n = self.torch, len(self.decoders)
-        key = (B, W, max_steps, float(lpw))
+        key = (B, W, max_steps, float(lpw)) if cons is None else (B, W, max_steps, float(lpw), cons.key())
         ctx = self._ctxs.get(key)
         if ctx is None:
             ctx = type('EnsembleCtx', (), {})()
@@ -954,8 +1063,11 @@ class EnsembleDecoder:
             ctx.im_ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ctx.im])
             ctx.hist_ptrs = (C.c_void_p * n)(*([ctx.hist.data_ptr()] + [None] * (n - 1)))
             ctx.wts = (C.c_float * n)(*self.weights)
-            ctx.nbytes = int(self.lib.comic_decoder_beam_ensemble_workspace(ctx.descs, n, R, max_steps))
-            assert ctx.nbytes > 0, 'comic_decoder_beam_ensemble_workspace failed'
+            ctx.cons = cons.c_struct() if cons is not None else None
+            ws_fn = self.lib.comic_decoder_beam_ensemble_workspace if cons is None else \
+                self.lib.comic_decoder_beam_constrained_workspace
+            ctx.nbytes = int(ws_fn(ctx.descs, n, R, max_steps))
+            assert ctx.nbytes > 0, 'the ensemble workspace query failed'
             ctx.ws = torch.empty(ctx.nbytes, dtype=torch.uint8, device=self.device)
             ctx.graph, ctx.calls = None, 0
             self._ctxs[key] = ctx
@@ -964,22 +1076,34 @@ class EnsembleDecoder:
             ctx.im[k].copy_(im.reshape(ctx.im[k].shape))
         return ctx
 
-    def beam_search(self, fms, im_embeds, beam, max_steps, want_attention=False, use_graph=True, length_penalty_weight=0.0):
+    def beam_search(self, fms, im_embeds, beam, max_steps, want_attention=False, use_graph=True, length_penalty_weight=0.0,
+                    constraints=None):
         """fms / im_embeds: one device tensor (every member reads the same features) or a sequence with one per member.
-        Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's."""
+        Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's.  constraints: a
+        BeamConstraints; active ones run comic_decoder_beam_constrained, None / inactive ones today's entry point."""
         torch, n = self.torch, len(self.decoders)
+        cons = constraints if constraints is not None and constraints.active else None
+        if cons is not None:
+            cons.check(self.spec, beam, max_steps)
         if torch.is_tensor(fms):
             fms = [fms] * n
         if torch.is_tensor(im_embeds):
             im_embeds = [im_embeds] * n
         assert len(fms) == n and len(im_embeds) == n
         B, W = int(fms[0].shape[0]), int(beam)
-        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)))
+        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)), cons)
 
         def launch():
             flags = L.decoder_flags_from_env()
             for k in range(n):
                 ctx.descs[k].flags = flags
+            if ctx.cons is not None:
+                L.check(self.lib.comic_decoder_beam_constrained(
+                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps, C.byref(ctx.cons),
+                    ctx.step_ids.data_ptr(), ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(),
+                    ctx.finished.data_ptr(), ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
+                    L.stream_ptr()), 'decoder_beam_constrained')
+                return
             L.check(self.lib.comic_decoder_beam_ensemble(
                 ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps, ctx.step_ids.data_ptr(),
                 ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(), ctx.finished.data_ptr(),

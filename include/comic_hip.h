@@ -489,6 +489,34 @@ int comic_beam_step_ensemble(const float* logits, const float* weights, int n_mo
                              int end_id, float length_penalty_weight, void* workspace, int64_t workspace_bytes,
                              void* stream);
 int comic_beam_step_ensemble_path(void);
+/* Constrained beam search (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112): what a live beam may not emit.
+ * At step t a live beam with history h[0..L-1] (L == t; the start token is not part of it) bans candidate v when
+ *   v is one of suppress[0..n_suppress-1], or
+ *   v == end_id and lengths[beam] < min_length, or
+ *   n = no_repeat_ngram > 0, L + 1 >= n, (L + 1) % ngram_stride == 0 and some window start i with i % ngram_stride == 0,
+ *   i + n - 1 <= L - 1 and h[i..i+n-2] == h[L-n+1..L-1] has h[i+n-1] == v.
+ * A banned candidate's step log-probability is -inf, applied after the log-softmax; finished beams ban nothing.
+ * no_repeat_ngram % ngram_stride == 0, n_suppress <= 32, ids in [0,V), end_id not suppressed. */
+typedef struct comic_beam_constraints {
+  int32_t min_length, no_repeat_ngram, ngram_stride, n_suppress;
+  int32_t suppress[32];
+} comic_beam_constraints;
+/* One step of the ban bookkeeping as a raw operator (common/ops_rnn.py:49-112; csrc/beam_bans.hip), to run BEFORE step t
+ * on the state step t - 1 left: prev_words / prev_parents [B*W] are step t - 1's word_ids / parent_ids (null at t == 0),
+ * finished [B*W], lengths [B*W] (int64).  hist [2][B*W][max_steps] (int32) holds the beams' token histories in beam
+ * order: buffer (t-1)&1 is read, row (b,w) of buffer t&1 becomes row (b, parent) of it plus the word (t tokens).
+ * bits [B*W][ceil(V/32)] receives the masks: bit v of a row set = banned; all zero for a finished row and at positions
+ * >= V.  Parents are clamped to [0,W) and tokens to [0,V) before they index anything.  V <= 65 536. */
+int comic_beam_bans(const int32_t* prev_words, const int32_t* prev_parents, const int32_t* finished, const int64_t* lengths,
+                    int32_t* hist, uint32_t* bits, int t, int B, int W, int V, int max_steps, int end_id,
+                    const comic_beam_constraints* constraints, void* stream);
+/* comic_beam_step_ensemble (common/ops_rnn.py:49-112) under a ban mask: bits [B*W][words], words == ceil(V/32), as
+ * comic_beam_bans writes it.  Every live beam must keep at least W candidates that are not banned.  An all-zero mask gives
+ * comic_beam_step_ensemble's result to the bit; workspace, split form and comic_beam_step_ensemble_path() as there. */
+int comic_beam_step_constrained(const float* logits, const float* weights, int n_models, float* log_probs,
+                                int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores,
+                                int B, int W, int V, int end_id, float length_penalty_weight, const uint32_t* bits, int words,
+                                void* workspace, int64_t workspace_bytes, void* stream);
 /* out[r,:] = in[(r/W)*W + parent[r], :]   (state re-ordering by parent beam) */
 int comic_gather_rows(const float* in, const int32_t* parent, float* out, int rows, int W, int cols,
                       void* stream);
@@ -709,6 +737,20 @@ int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, const comic_dec
                                 int n_models, int B, int W, int max_steps, int32_t* step_ids, int32_t* parent_ids,
                                 float* scores, int64_t* lengths, int32_t* finished, float* const* attn_hists,
                                 int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Constrained beam search (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112): comic_decoder_beam_ensemble -- the
+ * same loop; a single decoder is n_models == 1 with weight 1 -- whose every step first builds the beams' ban masks
+ * (comic_beam_bans) and then ranks through them (comic_beam_step_constrained).  Besides the rules of the struct:
+ * min_length < max_steps, V <= 65 536 and V >= W + n_suppress + 1 + max_steps, so that a live beam always keeps W
+ * candidates and a banned token is never selected.  Everything else, outputs included, as comic_decoder_beam_ensemble.
+ * workspace: comic_decoder_beam_constrained_workspace(descs, n_models, B*W, max_steps) bytes. */
+int64_t comic_decoder_beam_constrained_workspace(const comic_decoder_desc* descs, int n_models, int rows, int max_steps);
+int comic_decoder_beam_constrained(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                   const float* const* fms, const float* const* im_embeds, const float* weights,
+                                   int n_models, int B, int W, int max_steps, const comic_beam_constraints* constraints,
+                                   int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths,
+                                   int32_t* finished, float* const* attn_hists, int32_t* steps_executed, void* workspace,
+                                   int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SCST reward scorer (host, multi-threaded)  common/scst/scorers.py:43-171      */

@@ -46,6 +46,12 @@ def create_parser():
            'distributions; writes captions___ens_<n1>+<n2>+....json.')
     a('--infer_ensemble_weights', type=str, default=None,
       help='Comma-separated weights of the ensemble members (>= 0, summing to 1; default uniform).')
+    a('--infer_min_length', type=int, default=None,
+      help='Beam search: no caption ends before this many words (characters with char tokens).')
+    a('--infer_no_repeat_ngram', type=int, default=None,
+      help='Beam search: no n-gram of this many words (characters with char tokens) occurs twice in a caption.')
+    a('--infer_suppress_words', type=str, default=None,
+      help='Beam search: comma-separated words that are never emitted, e.g. `<UNK>` (word and char tokens only).')
     return p
 
 
@@ -74,6 +80,9 @@ def main(argv=None):
     save_name = 'beam_{}_lpen_{}'.format(c.infer_beam_size, c.infer_length_penalty_weight)
     save_name = {'test': 'infer_test_', 'valid': 'infer_valid_', 'coco_test': 'infer_cocoTest_',
                  'coco_valid': 'infer_cocoValid_'}[c.infer_set] + save_name
+    # constrained captions get a directory of their own: they never overwrite the unconstrained ones
+    from comic_amd.decoder import constraints_dir_suffix
+    save_name += constraints_dir_suffix(c)
     c.infer_save_path = pjoin(c.infer_checkpoints_dir, save_name)
     if os.path.exists(c.infer_save_path):
         print('\nINFO: `eval_log_path` already exists.')
