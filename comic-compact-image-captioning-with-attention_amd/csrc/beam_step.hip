@@ -25,14 +25,44 @@
 //              so survivors keep their scores -- and to live beams only (_mask_probs is untouched).  One L2-resident word
 //              load and a bit test per candidate, however many tokens are banned.
 //
+// How the W slots of an entry share the candidates is a third, orthogonal policy (diverse beam search, Vijayakumar et al.
+// 2016, with the Hamming diversity):
+//   NoGroups ... one beam of width W: the code of the step as it always was
+//   Groups ..... G groups (1 <= G <= W, W % G == 0, Wg = W / G) and diversity = lambda, a finite float >= 0.  Group g owns
+//                the slots [g * Wg, (g + 1) * Wg) of an entry.  total[w][v] = log_probs[w] + step[w][v] and score[w][v]
+//                (total, or total / ((5 + len) / 6)^lpw) are exactly the plain step's, _mask_probs and bans included.  The
+//                groups are processed in order g = 0, 1, ..., G - 1:
+//                  count[v]   = the number of slots q < g * Wg of the entry whose word chosen AT THIS STEP is v
+//                  rank[w][v] = score[w][v] - lambda * count[v] for a live beam w and v != end_id, else score[w][v]
+//                               (a finished beam and <EOS> are never penalised: otherwise the first group to end a caption
+//                               would push every later group to run on); the product float(lambda) * float(count) is
+//                               formed in fp32 and subtracted once
+//                  select       the group's Wg best among ITS OWN Wg * V candidates, rank descending and entry-wide flat
+//                               index f = w * V + v ascending (w the entry-wide slot); in the all-(-inf) / NaN corner the
+//                               lowest untaken flat index of the group's range
+//                  write        slot g * Wg + r: word = f % V, parent = f / V (an entry-wide slot, always inside the
+//                               group), scores = the rank, log_probs (the state) = the UNPENALISED total, finished and
+//                               lengths as ever
+//                Parents being entry-wide slots, gather_tree, the state gathers, the attention histories and the ban
+//                histories work unchanged.  The initial state has the first slot of each group live (beam_init_kernel
+//                with Wg for W).  G == 1 is the plain step; lambda == 0 is G independent beams of width Wg; group 0 is
+//                always beam search of width Wg.  The penalty is per TOKEN at the same position (with radix tokens: not
+//                per word).  A candidate finds its count by one bit test in an LDS mask of the penalised words (hashed by
+//                v mod 32 768, so any V fits) and walks the list of at most 63 words only on a hit.
+//
 // Two forms, one copy of each kernel, instantiated per policy:
 //   beam_step_kernel ........ one workgroup per batch entry: any V, length penalty included
 //   beam_stats_kernel ....... per (chunk, beam, entry, member): max and sum exp(x - max) of the chunk
 //   beam_chunk_topk_kernel .. per (entry, chunk): every row's constants from the partials (combined in chunk order, so each
 //                             workgroup of an entry gets the same bits), lp of its slice of all W beams, its own top-W
-//   beam_merge_kernel ....... per entry: top-W of the chunks' candidates + bookkeeping (no policy: candidates carry totals)
+//   beam_merge_kernel ....... per entry: top-W of the chunks' candidates + bookkeeping (candidates carry totals; under
+//                             Groups their ranks, and the unpenalised totals beside them)
 // The global top-W under a total order is the top-W of the union of the per-chunk top-W lists.  No kernel waits on another
-// workgroup; the three launches of the split form are ordered by the stream.  (Word tokens: V = 25 599, beam 3 -> 76 797
+// workgroup; the three launches of the split form are ordered by the stream.  Under Groups the one-workgroup form loops
+// over the groups inside the kernel (the words chosen so far stay in LDS); the split form runs the statistics once and
+// then, per group, one chunk top-k launch over that group's beams and one merge that writes that group's slots -- 1 + 2 G
+// launches, ordered by the stream -- and group g's chunk kernel reads the words of the groups before it from the step's
+// own word_ids rows, where the earlier merges wrote them.  (Word tokens: V = 25 599, beam 3 -> 76 797
 // candidates per entry; one workgroup per entry leaves the GPU empty and scans them 2 + W times.)
 #include <float.h>
 
@@ -126,6 +156,63 @@ struct Bans {
   __device__ __forceinline__ bool hit(int w, int v) const { return (bits[(size_t)w * words + (v >> 5)] >> (v & 31)) & 1u; }
 };
 
+constexpr int kPenWords = 1024;      // LDS mask of the penalised words: bit (v mod 32 768)
+struct NoGroups {
+  static constexpr bool kActive = false;
+  struct Pen {};
+  __host__ __device__ __forceinline__ int groups() const { return 1; }
+  __device__ __forceinline__ int group() const { return 0; }
+  NoGroups at(int, float*, const int32_t*) const { return NoGroups{}; }
+  __device__ __forceinline__ int chosen(int) const { return 0; }
+  __device__ __forceinline__ void clear(Pen&) const {}
+  __device__ __forceinline__ void add(Pen&, int, int) const {}
+  __device__ __forceinline__ float rank(const Pen&, int, float score, bool, int, int) const { return score; }
+  __device__ __forceinline__ void total(size_t, float) const {}
+  __device__ __forceinline__ float total_of(size_t, const ValIdx& best) const { return best.v; }
+};
+struct Groups {
+  static constexpr bool kActive = true;
+  int G;
+  float lambda;
+  int g;               // split form: the group this launch serves
+  float* cand_t;       // split form: the candidates' unpenalised totals, beside cand_v (their ranks)
+  const int32_t* words;  // split form: the step's word_ids output, whose slots before the group are already written
+  struct Pen {
+    uint32_t mask[kPenWords];
+    int word[64];
+  };
+  __host__ __device__ __forceinline__ int groups() const { return G; }
+  __device__ __forceinline__ int group() const { return g; }
+  // host: the policy of group g's launches of the split form
+  Groups at(int group, float* totals, const int32_t* word_ids) const { return Groups{G, lambda, group, totals, word_ids}; }
+  __device__ __forceinline__ int chosen(int row) const { return words[row]; }
+  // (every thread; the caller's barrier makes it visible)
+  __device__ __forceinline__ void clear(Pen& p) const {
+    for (int k = threadIdx.x; k < kPenWords; k += blockDim.x) p.mask[k] = 0u;
+  }
+  // slot q of the entry chose `word` at this step
+  __device__ __forceinline__ void add(Pen& p, int q, int word) const {
+    p.word[q] = word;
+    atomicOr(&p.mask[(word & (32 * kPenWords - 1)) >> 5], 1u << (word & 31));
+  }
+  // split form: the unpenalised total of candidate o of the chunk lists
+  __device__ __forceinline__ void total(size_t o, float t) const { cand_t[o] = t; }
+  // merge: the total of the round's winner, candidate o (none: the round's -inf)
+  __device__ __forceinline__ float total_of(size_t o, const ValIdx& best) const { return best.i == kNone ? best.v : cand_t[o]; }
+  // the rank of a candidate with `score`, npen slots before its group
+  __device__ __forceinline__ float rank(const Pen& p, int npen, float score, bool live, int v, int end_id) const {
+    if (!live || v == end_id || !((p.mask[(v & (32 * kPenWords - 1)) >> 5] >> (v & 31)) & 1u)) return score;
+    int count = 0;
+    for (int q = 0; q < npen; ++q) count += (p.word[q] == v) ? 1 : 0;
+    if (count == 0) return score;
+    {
+#pragma clang fp contract(off)
+      const float pen = lambda * (float)count;
+      return score - pen;
+    }
+  }
+};
+
 // unpenalised total of candidate (beam w, word v), flat index f, of the entry whose member-0 logits start at lg and whose
 // bans are bn: _mask_probs for a finished beam, -inf for a banned candidate of a live one
 template <class P, class Bn>
@@ -136,9 +223,18 @@ __device__ __forceinline__ float cand_total(const P& pol, const Bn& bn, const fl
   return s.lp[w] + step;
 }
 
-// all-(-inf) / all-NaN corner of a selection round: the lowest untaken flat index (matches a stable sort)
-__device__ __forceinline__ int lowest_untaken(const int* sel, int r) {
-  int f = 0;
+// (Groups, split form) the unpenalised total of a chunk's chosen candidate f, -inf for "none"
+template <class P, class Bn>
+__device__ __forceinline__ float chunk_total(const P& pol, const Bn& bn, const float* __restrict__ lg, size_t mstride, int f,
+                                             int V, int end_id, const typename P::Rows& s) {
+  if (f == kNone) return -INFINITY;
+  const int w = f / V;
+  return cand_total(pol, bn, lg, mstride, f, w, f - w * V, end_id, s);
+}
+
+// all-(-inf) / all-NaN corner of a selection round: the lowest untaken flat index from `first` on (matches a stable sort)
+__device__ __forceinline__ int lowest_untaken(const int* sel, int r, int first = 0) {
+  int f = first;
   bool again = true;
   while (again) {
     again = false;
@@ -167,22 +263,24 @@ __device__ __forceinline__ void write_beam(int o, int f, float score, float tota
 }
 
 // ---- one workgroup per batch entry -----------------------------------------------------------------------------------
-template <class P, class Bn>
+template <class P, class Bn, class Gr>
 __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict__ logits, P pol, Bn bans, float* __restrict__ log_probs,
                                                         int32_t* __restrict__ finished, int64_t* __restrict__ lengths,
                                                         int32_t* __restrict__ word_ids, int32_t* __restrict__ parent_ids,
                                                         float* __restrict__ scores, int B, int W, int V, int end_id,
-                                                        float lpw, const int32_t* __restrict__ stop, int stop_t) {
+                                                        float lpw, const int32_t* __restrict__ stop, int stop_t, Gr gr) {
   __shared__ ValIdx sh[256];
   __shared__ typename P::Rows s;
   __shared__ int s_sel[64];
   __shared__ float s_selv[64];
   __shared__ long long s_len[64];
+  __shared__ typename Gr::Pen pen;
   if (comic_stopped(stop, stop_t)) return;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t mstride = (size_t)B * W * V;
   const float* lg = logits + (size_t)b * W * V;
   const Bn bn = bans.entry(b, W);
+  gr.clear(pen);
   // the entry's beam state (W <= 64): loaded first, in flight behind the passes over the logits
   float lp_w = 0.f;
   int fin_w = 0;
@@ -215,36 +313,46 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
     s_len[tid] = len_w;
   }
   __syncthreads();
-  const int total = W * V;
-  for (int r = 0; r < W; ++r) {
-    float bv = -INFINITY;
-    int bi = kNone;
-    for (int f = tid; f < total; f += 256) {
-      bool taken = false;
-      for (int q = 0; q < r; ++q) taken |= (s_sel[q] == f);
-      if (taken) continue;
-      const int w = f / V, v = f - w * V;
-      float tot = cand_total(pol, bn, lg, mstride, f, w, v, end_id, s);
-      if (lpw != 0.f) {
-        const long long len = s_len[w] + ((s.fin[w] || v == end_id) ? 0 : 1);
-        tot = tot / powf((5.f + (float)len) / 6.f, lpw);
-      }
-      if (better(tot, f, bv, bi)) {
-        bv = tot;
-        bi = f;
-      }
+  // group g selects its Wg slots among the candidates of its own Wg beams (NoGroups: one group, the W beams)
+  const int Wg = Gr::kActive ? W / gr.groups() : W, total = Wg * V;
+  int g = 0;
+  do {
+    const int w0 = Gr::kActive ? g * Wg : 0, f0 = w0 * V;
+    if (Gr::kActive && g > 0) {                     // the words of the group before: penalised from here on
+      if (tid >= w0 - Wg && tid < w0) gr.add(pen, tid, s_sel[tid] % V);
+      __syncthreads();
     }
-    const ValIdx best = block_argmax(bv, bi, sh);
-    if (tid == 0) {
-      s_sel[r] = best.i == kNone ? lowest_untaken(s_sel, r) : best.i;
-      s_selv[r] = best.v;
+    for (int r = 0; r < Wg; ++r) {
+      float bv = -INFINITY;
+      int bi = kNone;
+      for (int f = f0 + tid; f < f0 + total; f += 256) {
+        bool taken = false;
+        for (int q = 0; q < r; ++q) taken |= (s_sel[w0 + q] == f);
+        if (taken) continue;
+        const int w = f / V, v = f - w * V;
+        float tot = cand_total(pol, bn, lg, mstride, f, w, v, end_id, s);
+        if (lpw != 0.f) {
+          const long long len = s_len[w] + ((s.fin[w] || v == end_id) ? 0 : 1);
+          tot = tot / powf((5.f + (float)len) / 6.f, lpw);
+        }
+        if (Gr::kActive) tot = gr.rank(pen, w0, tot, !s.fin[w], v, end_id);
+        if (better(tot, f, bv, bi)) {
+          bv = tot;
+          bi = f;
+        }
+      }
+      const ValIdx best = block_argmax(bv, bi, sh);
+      if (tid == 0) {
+        s_sel[w0 + r] = best.i == kNone ? lowest_untaken(s_sel + w0, r, f0) : best.i;
+        s_selv[w0 + r] = best.v;
+      }
+      __syncthreads();
     }
-    __syncthreads();
-  }
+  } while (Gr::kActive && ++g < gr.groups());
   if (tid < W) {
     const int f = s_sel[tid], parent = f / V, word = f - parent * V;
     // the state carries the unpenalised total log probability of the chosen candidate
-    const float state = lpw != 0.f ? cand_total(pol, bn, lg, mstride, f, parent, word, end_id, s) : s_selv[tid];
+    const float state = (Gr::kActive || lpw != 0.f) ? cand_total(pol, bn, lg, mstride, f, parent, word, end_id, s) : s_selv[tid];
     write_beam(b * W + tid, f, s_selv[tid], state, s.fin, s_len, V, end_id, log_probs, finished, lengths, word_ids, parent_ids,
                scores);
   }
@@ -285,23 +393,32 @@ __global__ __launch_bounds__(256) void beam_stats_kernel(const float* __restrict
 // KLOCAL > 0: a thread's share of the W * nv candidates (column v0 + tid + 256 * k of every beam) fits in KLOCAL registers.
 // It is formed ONCE, with all loads in flight together, and the W selection rounds run on the register copy (the
 // rescanning form pays an L2 round trip per element and round: 31 -> 9 us at W = 3, V = 25 599).  0: the rescanning form.
-// The launcher picks the capacity (16 / 40 / 0).
-template <class P, class Bn, int KLOCAL>
+// The launcher picks the capacity (16 / 40 / 0).  Under Groups a launch serves group gr.group(): its Wg beams, its top-Wg,
+// the words of the slots before the group read from the step's word_ids (the earlier groups' merges wrote them).  The
+// group policy is the LAST argument of every kernel: the others keep their places.
+template <class P, class Bn, class Gr, int KLOCAL>
 __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __restrict__ logits, P pol, Bn bans,
                                                               const float* __restrict__ log_probs,
                                                               const int32_t* __restrict__ finished,
                                                               const float* __restrict__ pmax, const float* __restrict__ psum,
                                                               float* __restrict__ cand_v, int32_t* __restrict__ cand_i, int B,
                                                               int W, int V, int chunks, int end_id,
-                                                              const int32_t* __restrict__ stop, int stop_t) {
+                                                              const int32_t* __restrict__ stop, int stop_t, Gr gr) {
   __shared__ ValIdx sh[256];
   __shared__ typename P::Rows s;
   __shared__ int s_sel[64];
+  __shared__ typename Gr::Pen pen;
   if (comic_stopped(stop, stop_t)) return;
   const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t mstride = (size_t)B * W * V;
   const float* lg = logits + (size_t)b * W * V;
   const Bn bn = bans.entry(b, W);
+  const int Wg = W / gr.groups(), w0 = gr.group() * Wg;       // this launch's beams: [w0, w0 + Wg)
+  if (Gr::kActive) {
+    gr.clear(pen);
+    __syncthreads();
+    if (tid < w0) gr.add(pen, tid, gr.chosen(b * W + tid));   // (visible behind the barrier below)
+  }
   // the entry's beam state (W <= 64): loaded first, in flight behind the partials
   float lp_w = 0.f;
   int fin_w = 0;
@@ -333,22 +450,22 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
   }
   __syncthreads();
   const int per = (V + chunks - 1) / chunks, v0 = c * per, v1 = min(V, v0 + per), nv = max(0, v1 - v0);
-  const size_t out = ((size_t)b * chunks + c) * W;
+  const size_t out = ((size_t)b * chunks + c) * Wg;
   constexpr int kLocal = KLOCAL > 0 ? KLOCAL : 1;
   const int kper = (nv + 255) >> 8;                 // columns per thread and beam
-  if (KLOCAL > 0 && W * kper <= kLocal) {
+  if (KLOCAL > 0 && Wg * kper <= kLocal) {
     __shared__ ValIdx sh8[8];
     float tv[kLocal];
     int ti[kLocal];
-    int w = 0, k = 0;                               // (beam, column slot) of register slot e: scalar counters
+    int w = w0, k = 0;                              // (beam, column slot) of register slot e: scalar counters
 #pragma unroll
     for (int e = 0; e < kLocal; ++e) {
       tv[e] = -INFINITY;
       ti[e] = kNone;
       const int v = v0 + tid + 256 * k;
-      if (w < W && v < v1) {
+      if (w < w0 + Wg && v < v1) {
         const int f = w * V + v;
-        tv[e] = cand_total(pol, bn, lg, mstride, f, w, v, end_id, s);
+        tv[e] = gr.rank(pen, w0, cand_total(pol, bn, lg, mstride, f, w, v, end_id, s), !s.fin[w], v, end_id);
         ti[e] = f;
       }
       if (++k == kper) {
@@ -356,7 +473,8 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
         ++w;
       }
     }
-    for (int r = 0; r < W; ++r) {
+    int mine = kNone;                               // (Groups) thread r keeps round r's winner
+    for (int r = 0; r < Wg; ++r) {
       float bv = -INFINITY;
       int bi = kNone;
 #pragma unroll
@@ -373,20 +491,22 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
         cand_v[out + r] = best.v;
         cand_i[out + r] = best.i;
       }
+      if (Gr::kActive && tid == r) mine = best.i;
     }
+    if (Gr::kActive && tid < Wg) gr.total(out + tid, chunk_total(pol, bn, lg, mstride, mine, V, end_id, s));
     return;
   }
-  const int total = W * nv;
-  for (int r = 0; r < W; ++r) {
+  const int total = Wg * nv;
+  for (int r = 0; r < Wg; ++r) {
     float bv = -INFINITY;
     int bi = kNone;
     for (int j = tid; j < total; j += 256) {
-      const int w = j / nv, v = v0 + (j - w * nv);
+      const int wl = j / nv, w = w0 + wl, v = v0 + (j - wl * nv);
       const int f = w * V + v;
       bool taken = false;
       for (int q = 0; q < r; ++q) taken |= (s_sel[q] == f);
       if (taken) continue;
-      const float tot = cand_total(pol, bn, lg, mstride, f, w, v, end_id, s);
+      const float tot = gr.rank(pen, w0, cand_total(pol, bn, lg, mstride, f, w, v, end_id, s), !s.fin[w], v, end_id);
       if (better(tot, f, bv, bi)) {
         bv = tot;
         bi = f;
@@ -400,17 +520,22 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
     }
     __syncthreads();
   }
+  if (Gr::kActive && tid < Wg) gr.total(out + tid, chunk_total(pol, bn, lg, mstride, s_sel[tid], V, end_id, s));
 }
 
+// Under Groups a launch merges group gr.group()'s lists (Wg per chunk, ranked) into that group's slots; the state takes
+// the chosen candidate's unpenalised total from gr.cand_t.
+template <class Gr>
 __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict__ cand_v, const int32_t* __restrict__ cand_i,
                                                          float* __restrict__ log_probs, int32_t* __restrict__ finished,
                                                          int64_t* __restrict__ lengths, int32_t* __restrict__ word_ids,
                                                          int32_t* __restrict__ parent_ids, float* __restrict__ scores, int W,
                                                          int V, int chunks, int end_id, const int32_t* __restrict__ stop,
-                                                         int stop_t) {
+                                                         int stop_t, Gr gr) {
   __shared__ ValIdx sh[256];
   __shared__ int s_fin[64], s_sel[64];
   __shared__ float s_selv[64];
+  __shared__ float s_selt[Gr::kActive ? 64 : 1];
   __shared__ long long s_len[64];
   if (comic_stopped(stop, stop_t)) return;
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -419,12 +544,13 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
     s_len[tid] = lengths[b * W + tid];
   }
   __syncthreads();
-  const int n = chunks * W;
+  const int Wg = W / gr.groups(), w0 = gr.group() * Wg;
+  const int n = chunks * Wg;
   const float* cv = cand_v + (size_t)b * n;
   const int32_t* ci = cand_i + (size_t)b * n;
-  for (int r = 0; r < W; ++r) {
+  for (int r = 0; r < Wg; ++r) {
     float bv = -INFINITY;
-    int bi = kNone;
+    int bi = kNone, bj = 0;
     for (int j = tid; j < n; j += 256) {
       const int f = ci[j];
       if (f == kNone) continue;
@@ -434,26 +560,31 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
       if (better(cv[j], f, bv, bi)) {
         bv = cv[j];
         bi = f;
+        bj = j;
       }
     }
     const ValIdx best = block_argmax(bv, bi, sh);
     if (tid == 0) {
-      s_sel[r] = best.i == kNone ? lowest_untaken(s_sel, r) : best.i;
+      s_sel[r] = best.i == kNone ? lowest_untaken(s_sel, r, w0 * V) : best.i;
       s_selv[r] = best.v;
     }
+    // (flat indices are unique: one thread holds the winner)
+    if (Gr::kActive && (best.i == kNone ? tid == 0 : bi == best.i)) s_selt[r] = gr.total_of((size_t)b * n + bj, best);
     __syncthreads();
   }
-  if (tid < W)
-    write_beam(b * W + tid, s_sel[tid], s_selv[tid], s_selv[tid], s_fin, s_len, V, end_id, log_probs, finished, lengths,
-               word_ids, parent_ids, scores);
+  if (tid < Wg)
+    write_beam(b * W + w0 + tid, s_sel[tid], s_selv[tid], Gr::kActive ? s_selt[tid] : s_selv[tid], s_fin, s_len, V, end_id,
+               log_probs, finished, lengths, word_ids, parent_ids, scores);
 }
 
 thread_local int g_ens_step_path = 0;
 
 // The ONE launcher: one workgroup per entry, or -- without a length penalty (it ranks by score, not by log probability),
-// with enough candidates, at least two chunks and a workspace that holds the partials -- the split form.
-template <class P, class Bn>
-int beam_step_launch(const P& pol, const Bn& bans, int n, const float* logits, float* log_probs, int32_t* finished, int64_t* lengths,
+// with enough candidates, at least two chunks and a workspace that holds the partials -- the split form.  Under Groups
+// the split form is the statistics once, then a chunk top-k and a merge per group; the eligibility rule is the same, on
+// the entry-wide W * V, and the register-resident chunk form is chosen on Wg * kper.
+template <class P, class Bn, class Gr>
+int beam_step_launch(const P& pol, const Bn& bans, Gr gr, int n, const float* logits, float* log_probs, int32_t* finished, int64_t* lengths,
                      int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int V, int end_id, float lpw, void* ws,
                      int64_t ws_bytes, hipStream_t st, int* path) {
   const int chunks = comic_beam_step_chunks(B, V);
@@ -461,8 +592,8 @@ int beam_step_launch(const P& pol, const Bn& bans, int n, const float* logits, f
                      ws_bytes >= comic_beam_step_split_bytes(n, B, W, chunks);
   if (path) *path = split ? 1 : 0;
   if (!split) {
-    hipLaunchKernelGGL((beam_step_kernel<P, Bn>), dim3(B), dim3(256), 0, st, logits, pol, bans, log_probs, finished, lengths, word_ids,
-                       parent_ids, scores, B, W, V, end_id, lpw, g_comic_stop.p, g_comic_stop.t);
+    hipLaunchKernelGGL((beam_step_kernel<P, Bn, Gr>), dim3(B), dim3(256), 0, st, logits, pol, bans, log_probs, finished, lengths, word_ids,
+                       parent_ids, scores, B, W, V, end_id, lpw, g_comic_stop.p, g_comic_stop.t, gr);
     COMIC_LAUNCH_CHECK(P::kName);
     return 0;
   }
@@ -472,19 +603,23 @@ int beam_step_launch(const P& pol, const Bn& bans, int n, const float* logits, f
   int32_t* cand_i = (int32_t*)(cand_v + (size_t)B * chunks * W);
   hipLaunchKernelGGL(beam_stats_kernel<P>, dim3(chunks, W, n * B), dim3(256), 0, st, logits, pol, pmax, psum, B, W, V, chunks,
                      g_comic_stop.p, g_comic_stop.t);
-  {
+  // (Groups: the lists are Wg <= W / 2 per chunk, so the totals fit behind the ranks inside cand_v's W per chunk)
+  const int Wg = W / gr.groups();
+  for (int g = 0; g < gr.groups(); ++g) {
+    const Gr gg = gr.at(g, cand_v + (size_t)B * chunks * Wg, word_ids);
     const int per = (V + chunks - 1) / chunks, kper = (per + 255) / 256;
     auto launch = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3(chunks, B), dim3(256), 0, st, logits, pol, bans, (const float*)log_probs,
                          (const int32_t*)finished, (const float*)pmax, (const float*)psum, cand_v, cand_i, B, W, V, chunks,
-                         end_id, g_comic_stop.p, g_comic_stop.t);
+                         end_id, g_comic_stop.p, g_comic_stop.t, gg);
     };
-    if (W * kper <= 16) launch(beam_chunk_topk_kernel<P, Bn, 16>);
-    else if (W * kper <= 40) launch(beam_chunk_topk_kernel<P, Bn, 40>);
-    else launch(beam_chunk_topk_kernel<P, Bn, 0>);
+    if (Wg * kper <= 16) launch(beam_chunk_topk_kernel<P, Bn, Gr, 16>);
+    else if (Wg * kper <= 40) launch(beam_chunk_topk_kernel<P, Bn, Gr, 40>);
+    else launch(beam_chunk_topk_kernel<P, Bn, Gr, 0>);
+    hipLaunchKernelGGL(beam_merge_kernel<Gr>, dim3(B), dim3(256), 0, st, (const float*)cand_v, (const int32_t*)cand_i,
+                       log_probs, finished, lengths, word_ids, parent_ids, scores, W, V, chunks, end_id, g_comic_stop.p,
+                       g_comic_stop.t, gg);
   }
-  hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, st, (const float*)cand_v, (const int32_t*)cand_i, log_probs,
-                     finished, lengths, word_ids, parent_ids, scores, W, V, chunks, end_id, g_comic_stop.p, g_comic_stop.t);
   COMIC_LAUNCH_CHECK(P::kSplitName);
   return 0;
 }
@@ -500,7 +635,7 @@ int comic_beam_step_ws(const float* logits, float* log_probs, int32_t* finished,
                 "beam_step: null pointer");
   COMIC_REQUIRE(W >= 1 && W <= 64, "beam_step: beam width must be in [1,64] (got %d)", W);
   COMIC_REQUIRE((long)W * V < (1L << 31) && W <= V, "beam_step: beam*V too large or beam > V");
-  return beam_step_launch(OneMember{}, NoBans{}, 1, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V, end_id,
+  return beam_step_launch(OneMember{}, NoBans{}, NoGroups{}, 1, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V, end_id,
                           lpw, ws, ws_bytes, st, nullptr);
 }
 extern "C" int comic_beam_step(const float* logits, float* log_probs, int32_t* finished, int64_t* lengths,
@@ -517,11 +652,12 @@ extern "C" int64_t comic_beam_step_ensemble_workspace(int n_models, int B, int W
   return comic_beam_step_split_bytes(n_models, B, W, comic_beam_step_chunks(B, V));
 }
 
-// the ensemble step's argument checks and launch; bits null: no bans (the code of comic_beam_step_ensemble as it was)
+// the ensemble step's argument checks and launch; bits null: no bans (the code of comic_beam_step_ensemble as it was);
+// grp null or one group: no groups (G == 1 IS the plain step: the same instantiation, the same launches)
 static int ens_step(const char* who, const float* logits, const float* weights, int n_models, float* log_probs,
                     int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W,
-                    int V, int end_id, float length_penalty_weight, const uint32_t* bits, int words, void* workspace,
-                    int64_t workspace_bytes, void* stream) {
+                    int V, int end_id, float length_penalty_weight, const uint32_t* bits, int words,
+                    const comic_beam_groups* grp, void* workspace, int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(logits && weights && log_probs && finished && lengths && word_ids && parent_ids && scores,
                 "%s: null pointer", who);
   COMIC_REQUIRE(n_models >= 1 && n_models <= kEnsMax, "%s: 1 to %d members (got %d)", who, kEnsMax, n_models);
@@ -537,11 +673,21 @@ static int ens_step(const char* who, const float* logits, const float* weights, 
     wsum += weights[m];
   }
   COMIC_REQUIRE(wsum > 0.f, "%s: every weight is zero", who);
+  if (grp && grp->groups > 1) {
+    const Groups gr{grp->groups, grp->diversity, 0, nullptr, nullptr};
+    if (bits)
+      return beam_step_launch(pol, Bans{bits, words}, gr, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids,
+                              scores, B, W, V, end_id, length_penalty_weight, workspace, workspace_bytes, (hipStream_t)stream,
+                              &g_ens_step_path);
+    return beam_step_launch(pol, NoBans{}, gr, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B,
+                            W, V, end_id, length_penalty_weight, workspace, workspace_bytes, (hipStream_t)stream,
+                            &g_ens_step_path);
+  }
   if (bits)
-    return beam_step_launch(pol, Bans{bits, words}, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids, scores,
+    return beam_step_launch(pol, Bans{bits, words}, NoGroups{}, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids, scores,
                             B, W, V, end_id, length_penalty_weight, workspace, workspace_bytes, (hipStream_t)stream,
                             &g_ens_step_path);
-  return beam_step_launch(pol, NoBans{}, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V,
+  return beam_step_launch(pol, NoBans{}, NoGroups{}, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V,
                           end_id, length_penalty_weight, workspace, workspace_bytes, (hipStream_t)stream, &g_ens_step_path);
 }
 
@@ -550,7 +696,7 @@ extern "C" int comic_beam_step_ensemble(const float* logits, const float* weight
                                         float* scores, int B, int W, int V, int end_id, float length_penalty_weight,
                                         void* workspace, int64_t workspace_bytes, void* stream) {
   return ens_step("beam_step_ensemble", logits, weights, n_models, log_probs, finished, lengths, word_ids, parent_ids, scores,
-                  B, W, V, end_id, length_penalty_weight, nullptr, 0, workspace, workspace_bytes, stream);
+                  B, W, V, end_id, length_penalty_weight, nullptr, 0, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int comic_beam_step_constrained(const float* logits, const float* weights, int n_models, float* log_probs,
@@ -561,5 +707,28 @@ extern "C" int comic_beam_step_constrained(const float* logits, const float* wei
   COMIC_REQUIRE(bits, "beam_step_constrained: null ban mask");
   COMIC_REQUIRE(V > 0 && words == (V + 31) / 32, "beam_step_constrained: %d mask words for a vocabulary of %d", words, V);
   return ens_step("beam_step_constrained", logits, weights, n_models, log_probs, finished, lengths, word_ids, parent_ids,
-                  scores, B, W, V, end_id, length_penalty_weight, bits, words, workspace, workspace_bytes, stream);
+                  scores, B, W, V, end_id, length_penalty_weight, bits, words, nullptr, workspace, workspace_bytes, stream);
+}
+
+// executor-internal (decoder_exec.hip checks a loop's groups once, in front of its first launch)
+int comic_beam_groups_check(const comic_beam_groups* g, const char* who, int W, int V) {
+  COMIC_REQUIRE(g, "%s: null groups", who);
+  COMIC_REQUIRE(g->groups >= 1, "%s: groups must be at least 1 (got %d)", who, g->groups);
+  COMIC_REQUIRE(g->groups <= W, "%s: groups %d exceeds the beam width %d", who, g->groups, W);
+  COMIC_REQUIRE(W % g->groups == 0, "%s: groups %d does not divide the beam width %d", who, g->groups, W);
+  COMIC_REQUIRE(g->diversity >= 0.f && g->diversity <= FLT_MAX, "%s: diversity is negative or not finite", who);
+  COMIC_REQUIRE(W / g->groups <= V, "%s: groups: a group's width %d exceeds V = %d", who, W / g->groups, V);
+  return 0;
+}
+
+extern "C" int comic_beam_step_diverse(const float* logits, const float* weights, int n_models, float* log_probs,
+                                       int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids,
+                                       float* scores, int B, int W, int V, int end_id, float length_penalty_weight,
+                                       const uint32_t* bits, int words, const comic_beam_groups* groups, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+  COMIC_REQUIRE(W >= 1 && W <= 64 && V > 0, "beam_step_diverse: beam width must be in [1,64] (got %d)", W);
+  if (int rc = comic_beam_groups_check(groups, "beam_step_diverse", W, V)) return rc;
+  COMIC_REQUIRE(!bits || words == (V + 31) / 32, "beam_step_diverse: %d mask words for a vocabulary of %d", words, V);
+  return ens_step("beam_step_diverse", logits, weights, n_models, log_probs, finished, lengths, word_ids, parent_ids, scores,
+                  B, W, V, end_id, length_penalty_weight, bits, words, groups, workspace, workspace_bytes, stream);
 }

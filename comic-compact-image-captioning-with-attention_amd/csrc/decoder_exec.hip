@@ -119,6 +119,7 @@ int comic_beam_step_ws(const float* logits, float* log_probs, int32_t* finished,
                        int32_t* parent_ids, float* scores, int B, int W, int V, int end_id, float lpw, void* ws,
                        int64_t ws_bytes, hipStream_t st);
 int64_t comic_beam_step_split_bytes(int n, int B, int W, int chunks);
+int comic_beam_groups_check(const comic_beam_groups* g, const char* who, int W, int V);
 // beam_bans.hip
 int comic_beam_constraints_check(const comic_beam_constraints* c, const char* who, int W, int V, int end_id, int max_steps,
                                  bool whole);
@@ -2175,12 +2176,13 @@ extern "C" int64_t comic_decoder_beam_constrained_workspace(const comic_decoder_
 }
 
 // The ONE ensemble loop.  cons null: comic_decoder_beam_ensemble, launch for launch as it always was; else every step
-// builds the beams' ban masks first (beam_bans.hip) and ranks through them (the Bans policy of beam_step.hip).
+// builds the beams' ban masks first (beam_bans.hip) and ranks through them (the Bans policy of beam_step.hip).  grp null:
+// one beam of width W; else the first slot of every group starts live and every step ranks under the Groups policy.
 static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decoder_params* params, const float* const* fms,
                              const float* const* im_embeds, const float* weights, int n_models, int B, int W, int max_steps,
                              int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
                              float* const* attn_hists, int32_t* steps_executed, const comic_beam_constraints* cons,
-                             void* workspace, int64_t workspace_bytes, void* stream) {
+                             const comic_beam_groups* grp, void* workspace, int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(descs && params && fms && im_embeds && weights && step_ids && parent_ids && scores && lengths && finished &&
                     steps_executed && workspace,
                 "beam_ensemble: null pointer");
@@ -2196,6 +2198,7 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
   }
   COMIC_REQUIRE(W <= V && (long)W * V < (1L << 31), "beam_ensemble: beam*V too large or beam > V");
   if (cons) RC(comic_beam_constraints_check(cons, "beam_constrained", W, V, descs[0].end_id, max_steps, true));
+  if (grp) RC(comic_beam_groups_check(grp, "beam_diverse", W, V));
   hipStream_t st = (hipStream_t)stream;
   EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, cons ? max_steps : 0);
   COMIC_REQUIRE(L.ok && (int64_t)L.bytes <= workspace_bytes, "beam_ensemble: workspace too small");
@@ -2211,7 +2214,9 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
     RC(beam_member_begin(d, p, fms[m], im_embeds[m], B, W, ws, st, e));
     e.w_o = aligned_w_o(d, p, ws.wo_pad, &e.ld_wo, st);
   }
-  hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, L.log_probs, finished, lengths, R, W);
+  // (groups: row i starts live when i % Wg == 0, the first slot of its group)
+  hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, L.log_probs, finished, lengths, R,
+                     grp ? W / grp->groups : W);
   hipLaunchKernelGGL(fill_i32_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, L.ids, descs[0].start_id, (long)R);
   hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(64), 0, st, steps_executed, max_steps, 1L);
   COMIC_LAUNCH_CHECK("beam_ensemble init");
@@ -2254,9 +2259,14 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
       }
       RC(gemm_big(sb.y, e.w_o, lg, p->b_o, R, V, D, D, e.ld_wo, V, 0, 0, 0.f, st));
     }
-    if (cons) {
+    if (cons)
       RC(comic_beam_bans_launch(t == 0 ? nullptr : (const int32_t*)ids_in, par_in, finished, lengths, L.ban_hist, L.bits, t, B,
                                 W, V, max_steps, descs[0].end_id, cons, st));
+    if (grp) {
+      RC(comic_beam_step_diverse(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
+                                 B, W, V, descs[0].end_id, lpw, cons ? L.bits : nullptr, (V + 31) / 32, grp, L.step_ws,
+                                 L.step_bytes, (void*)st));
+    } else if (cons) {
       RC(comic_beam_step_constrained(L.logits, weights, n, L.log_probs, finished, lengths, word, parent,
                                      scores + (size_t)t * R, B, W, V, descs[0].end_id, lpw, L.bits, (V + 31) / 32, L.step_ws,
                                      L.step_bytes, (void*)st));
@@ -2276,7 +2286,7 @@ extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, cons
                                            float* scores, int64_t* lengths, int32_t* finished, float* const* attn_hists,
                                            int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream) {
   return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
-                           lengths, finished, attn_hists, steps_executed, nullptr, workspace, workspace_bytes, stream);
+                           lengths, finished, attn_hists, steps_executed, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int comic_decoder_beam_constrained(const comic_decoder_desc* descs, const comic_decoder_params* params,
@@ -2288,5 +2298,25 @@ extern "C" int comic_decoder_beam_constrained(const comic_decoder_desc* descs, c
                                               int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(constraints, "beam_constrained: null constraints");
   return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
-                           lengths, finished, attn_hists, steps_executed, constraints, workspace, workspace_bytes, stream);
+                           lengths, finished, attn_hists, steps_executed, constraints, nullptr, workspace, workspace_bytes,
+                           stream);
+}
+
+extern "C" int64_t comic_decoder_beam_diverse_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                        int max_steps, int constrained) {
+  return constrained ? comic_decoder_beam_constrained_workspace(descs, n_models, rows, max_steps)
+                     : comic_decoder_beam_ensemble_workspace(descs, n_models, rows, max_steps);
+}
+
+extern "C" int comic_decoder_beam_diverse(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                          const float* const* fms, const float* const* im_embeds, const float* weights,
+                                          int n_models, int B, int W, int max_steps,
+                                          const comic_beam_constraints* constraints, const comic_beam_groups* groups,
+                                          int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths,
+                                          int32_t* finished, float* const* attn_hists, int32_t* steps_executed,
+                                          void* workspace, int64_t workspace_bytes, void* stream) {
+  COMIC_REQUIRE(groups, "beam_diverse: null groups");
+  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
+                           lengths, finished, attn_hists, steps_executed, constraints, groups, workspace, workspace_bytes,
+                           stream);
 }

@@ -349,6 +349,89 @@ def constraints_dir_suffix(c):
     return '_min%d_ngram%d_sup%d' % (int(m or 0), int(n or 0), len(sup or ()))
 
 
+class BeamGroups:
+    """Diverse beam search (comic_beam_groups; Vijayakumar et al. 2016 with the Hamming diversity; extends
+    rnn_decoder_beam_search, ops_rnn.py:49-112): the beam is split into `groups` groups of beam / groups slots, decided in
+    order at every step; a later group ranks a candidate token by its score minus `diversity` times the number of slots of
+    the earlier groups that chose that token at this step.  <EOS> and finished beams are never penalised; the beam state
+    keeps the unpenalised log-probability.  Group 0 is plain beam search of width beam / groups.  The penalty is per TOKEN
+    at the same position: with radix tokens it is not per word.  Immutable and hashable: decode contexts are keyed by it."""
+
+    def __init__(self, groups=1, diversity=0.0):
+        self.groups, self.diversity = int(groups), float(diversity)
+
+    def key(self):
+        return (self.groups, self.diversity)
+
+    def __eq__(self, other):
+        return isinstance(other, BeamGroups) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'BeamGroups(groups=%d, diversity=%r)' % self.key()
+
+    @property
+    def active(self):
+        return self.groups > 1
+
+    def check(self, beam, V=None):
+        """The rules of the C side, on the host before any GPU call; raises ValueError naming the field."""
+        beam = int(beam)
+        if self.groups < 1:
+            raise ValueError('groups must be >= 1, got %d' % self.groups)
+        if self.groups > beam:
+            raise ValueError('groups %d exceeds the beam width %d' % (self.groups, beam))
+        if beam % self.groups:
+            raise ValueError('groups %d does not divide the beam width %d' % (self.groups, beam))
+        if not (self.diversity >= 0.0) or math.isinf(self.diversity):
+            raise ValueError('diversity must be finite and >= 0, got %r' % self.diversity)
+        if V is not None and beam // self.groups > int(V):
+            raise ValueError('groups: a group of %d slots exceeds the vocabulary of %d' % (beam // self.groups, V))
+
+    def c_struct(self):
+        g = L.BeamGroups()
+        g.groups, g.diversity = self.groups, self.diversity
+        return g
+
+    def final_log_probs(self, scores, step_ids, lengths, end_id, lpw=0.0):
+        """The beams' unpenalised total log-probabilities [B,W] after the last executed step, recovered on the host from
+        that step's `scores` row (the ranks) and words: rank + diversity * count where the last word was penalised,
+        times the length penalty's divisor.  Exact wherever no penalty applied (every finished caption without a length
+        penalty); to fp32 rounding elsewhere."""
+        sc, words = np.asarray(scores[-1], np.float32), np.asarray(step_ids[-1])
+        B, W = words.shape
+        Wg = W // self.groups
+        count = np.zeros((B, W), np.float32)
+        for w in range(Wg, W):
+            before = words[:, :(w // Wg) * Wg]
+            count[:, w] = (before == words[:, w:w + 1]).sum(axis=1)
+        count[words == end_id] = 0
+        out = sc + np.float32(self.diversity) * count
+        if lpw:
+            out = out * (((5.0 + np.asarray(lengths, np.float32)) / 6.0) ** np.float32(lpw))
+        return out.astype(np.float32)
+
+
+def groups_from_config(c):
+    """The BeamGroups a configuration asks for (infer_beam_groups, infer_diversity), or None when it sets neither."""
+    g, d = getattr(c, 'infer_beam_groups', None), getattr(c, 'infer_diversity', None)
+    if g is None and d is None:
+        return None
+    grp = BeamGroups(groups=1 if g is None else g, diversity=0.0 if d is None else d)
+    grp.check(c.infer_beam_size)
+    return grp
+
+
+def groups_dir_suffix(c):
+    """'_grp{G}_div{diversity:g}' when the configuration sets a group field, else ''."""
+    g, d = getattr(c, 'infer_beam_groups', None), getattr(c, 'infer_diversity', None)
+    if g is None and d is None:
+        return ''
+    return '_grp%d_div%g' % (int(1 if g is None else g), float(0.0 if d is None else d))
+
+
 def process_inputs(captions, token_type):
     """ModelBase._process_inputs (model_base.py:501-528) on the host.
     -> inputs [B,T] int32, targets [B,T] int32, masks [B,T] fp32, lens [B] int32."""
@@ -915,21 +998,30 @@ class Decoder:
         return fetch
 
     def beam_search(self, fm, im_embed, beam, max_steps, want_attention=True, use_graph=True, length_penalty_weight=0.0,
-                    constraints=None):
+                    constraints=None, groups=None):
         """rnn_decoder_beam_search (ops_rnn.py:49-112).  Returns predicted_ids [T,B,W] (after
         gather_tree), scores [T,B,W] (with length_penalty_weight != 0: the penalised scores the beams were ranked by,
         BeamSearchDecoder's `scores` output), the raw step/parent ids and, unless want_attention=False, the
         beam-sorted alignment history [T,B*W,H*M] (numpy; BeamSearchDecoderMultiHead,
         ops_rnn.py:807-845 -- host post-processing that only visualisation needs).
         constraints: a BeamConstraints; active ones decode as a one-member ensemble through the constrained executor
-        (comic_decoder_beam_constrained), None / inactive ones change nothing."""
-        if constraints is not None and constraints.active:
-            constraints.check(self.spec, beam, max_steps)
+        (comic_decoder_beam_constrained), None / inactive ones change nothing.
+        groups: a BeamGroups (diverse beam search); an active one (groups > 1) decodes the same way through
+        comic_decoder_beam_diverse, alone or with constraints: slot g * (beam / groups) of predicted_ids and scores is
+        group g's best caption, and the result carries `log_probs` [B,W] (BeamGroups.final_log_probs).  None / inactive:
+        today's path.  The result's `groups` holds the number of groups (1 without)."""
+        constrained = constraints is not None and constraints.active
+        grouped = groups is not None and groups.active
+        if groups is not None:
+            groups.check(beam, self.spec.V)
+        if constrained or grouped:
+            if constrained:
+                constraints.check(self.spec, beam, max_steps)
             ens = self.__dict__.get('_self_ensemble')
             if ens is None:
                 ens = self._self_ensemble = EnsembleDecoder([self])
             return ens.beam_search(fm, im_embed, beam, max_steps, want_attention=want_attention, use_graph=use_graph,
-                                   length_penalty_weight=length_penalty_weight, constraints=constraints)
+                                   length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups)
         torch, s = self.torch, self.spec
         B, W = fm.shape[0], beam
         # (a non-zero length penalty is another captured graph: the weight is baked into the step kernel's arguments)
@@ -955,7 +1047,7 @@ class Decoder:
         par = ctx.parent_ids[:T].cpu().numpy()
         ln = ctx.lengths.cpu().numpy()
         out = dict(predicted_ids=pred.cpu().numpy(), scores=ctx.scores[:T].cpu().numpy(),
-                   step_ids=ctx.step_ids[:T].cpu().numpy(), parent_ids=par, lengths=ln)
+                   step_ids=ctx.step_ids[:T].cpu().numpy(), parent_ids=par, lengths=ln, groups=1)
         if want_attention:
             out['attn_hist'] = gather_tree_from_array(ctx.hist[:T].cpu().numpy(), par, ln, s.end_id)
         return out
@@ -1034,11 +1126,14 @@ class EnsembleDecoder:
         self.torch, self.lib, self.device = decoders[0].torch, decoders[0].lib, decoders[0].device
         self._ctxs = {}
 
-    def _ctx(self, B, W, max_steps, lpw, feats, cons=None):
+    def _ctx(self, B, W, max_steps, lpw, feats, cons=None, grp=None):
         """Persistent buffers (+ a hipGraph of the whole loop, captured on the second call with the shape), as
-        Decoder._infer_ctx.  cons: active BeamConstraints (they are baked into the captured launches) or None."""
+        Decoder._infer_ctx.  cons: active BeamConstraints (they are baked into the captured launches) or None; grp: active
+        BeamGroups (baked in likewise) or None."""
         torch, n = self.torch, len(self.decoders)
         key = (B, W, max_steps, float(lpw)) if cons is None else (B, W, max_steps, float(lpw), cons.key())
+        if grp is not None:
+            key = (B, W, max_steps, float(lpw), cons.key() if cons is not None else None, grp.key())
         ctx = self._ctxs.get(key)
         if ctx is None:
             ctx = type('EnsembleCtx', (), {})()
@@ -1064,9 +1159,14 @@ class EnsembleDecoder:
             ctx.hist_ptrs = (C.c_void_p * n)(*([ctx.hist.data_ptr()] + [None] * (n - 1)))
             ctx.wts = (C.c_float * n)(*self.weights)
             ctx.cons = cons.c_struct() if cons is not None else None
+            ctx.grp = grp.c_struct() if grp is not None else None
             ws_fn = self.lib.comic_decoder_beam_ensemble_workspace if cons is None else \
                 self.lib.comic_decoder_beam_constrained_workspace
-            ctx.nbytes = int(ws_fn(ctx.descs, n, R, max_steps))
+            if grp is not None:
+                ctx.nbytes = int(self.lib.comic_decoder_beam_diverse_workspace(ctx.descs, n, R, max_steps,
+                                                                               0 if cons is None else 1))
+            else:
+                ctx.nbytes = int(ws_fn(ctx.descs, n, R, max_steps))
             assert ctx.nbytes > 0, 'the ensemble workspace query failed'
             ctx.ws = torch.empty(ctx.nbytes, dtype=torch.uint8, device=self.device)
             ctx.graph, ctx.calls = None, 0
@@ -1077,12 +1177,17 @@ class EnsembleDecoder:
         return ctx
 
     def beam_search(self, fms, im_embeds, beam, max_steps, want_attention=False, use_graph=True, length_penalty_weight=0.0,
-                    constraints=None):
+                    constraints=None, groups=None):
         """fms / im_embeds: one device tensor (every member reads the same features) or a sequence with one per member.
         Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's.  constraints: a
-        BeamConstraints; active ones run comic_decoder_beam_constrained, None / inactive ones today's entry point."""
+        BeamConstraints; active ones run comic_decoder_beam_constrained, None / inactive ones today's entry point.
+        groups: a BeamGroups; an active one runs comic_decoder_beam_diverse (with the constraints, if any), as
+        Decoder.beam_search describes; None / inactive: today's entry points."""
         torch, n = self.torch, len(self.decoders)
         cons = constraints if constraints is not None and constraints.active else None
+        if groups is not None:
+            groups.check(beam, self.spec.V)
+        grp = groups if groups is not None and groups.active else None
         if cons is not None:
             cons.check(self.spec, beam, max_steps)
         if torch.is_tensor(fms):
@@ -1091,12 +1196,20 @@ class EnsembleDecoder:
             im_embeds = [im_embeds] * n
         assert len(fms) == n and len(im_embeds) == n
         B, W = int(fms[0].shape[0]), int(beam)
-        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)), cons)
+        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)), cons, grp)
 
         def launch():
             flags = L.decoder_flags_from_env()
             for k in range(n):
                 ctx.descs[k].flags = flags
+            if ctx.grp is not None:
+                L.check(self.lib.comic_decoder_beam_diverse(
+                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps,
+                    C.byref(ctx.cons) if ctx.cons is not None else None, C.byref(ctx.grp), ctx.step_ids.data_ptr(),
+                    ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(), ctx.finished.data_ptr(),
+                    ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes, L.stream_ptr()),
+                    'decoder_beam_diverse')
+                return
             if ctx.cons is not None:
                 L.check(self.lib.comic_decoder_beam_constrained(
                     ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps, C.byref(ctx.cons),
@@ -1118,7 +1231,10 @@ class EnsembleDecoder:
         par = ctx.parent_ids[:T].cpu().numpy()
         ln = ctx.lengths.cpu().numpy()
         out = dict(predicted_ids=pred.cpu().numpy(), scores=ctx.scores[:T].cpu().numpy(),
-                   step_ids=ctx.step_ids[:T].cpu().numpy(), parent_ids=par, lengths=ln)
+                   step_ids=ctx.step_ids[:T].cpu().numpy(), parent_ids=par, lengths=ln, groups=1)
+        if grp is not None:
+            out['groups'] = grp.groups
+            out['log_probs'] = grp.final_log_probs(out['scores'], out['step_ids'], ln, s.end_id, length_penalty_weight)
         if want_attention:
             out['attn_hist'] = gather_tree_from_array(ctx.hist[:T].cpu().numpy(), par, ln, s.end_id)
         return out

@@ -90,6 +90,7 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
                        max_caption_length=c.infer_max_length, checkpoint_path=curr_ckpt_path,
                        checkpoint_number=ckpt_num)
     coco_json = []
+    groups_json = []                # diverse beam search: the group-best captions of every image
     print('INFO: Graph constructed. Starting inference.')
     start_time = time.time()
     captions = []
@@ -101,6 +102,12 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
     for step in range(num_batches):
         word_ids, attn_maps = next(batches)
         captions = id_to_caption(word_ids, c)
+        # with beam groups word_ids is group 0's best (the caption beam search of width beam / groups gives, so metrics
+        # stay comparable); every group's best goes to caption_groups___N.json
+        grp = getattr(m_infer, 'group_output', None)
+        if grp is not None:
+            G = grp['ids'].shape[1]
+            grp_caps = [id_to_caption(grp['ids'][:, g], c) for g in range(G)]
         for i, f in enumerate(filenames[step * batch_size:(step + 1) * batch_size]):
             image_id = f.replace('.jpg', '')
             if '@' in image_id:
@@ -115,6 +122,10 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
             raw_outputs['attention'][f] = attn_maps[i] if attn_maps is not None else None
             raw_outputs['image_ids'][f] = image_id
             coco_json.append(dict(image_id=image_id, caption=str(captions[i])))
+            if grp is not None:
+                groups_json.append(dict(image_id=image_id, captions=[
+                    dict(group=g, caption=str(grp_caps[g][i]), score=float(grp['scores'][i, g]),
+                         log_prob=float(grp['log_probs'][i, g])) for g in range(G)]))
     print('\nExample captions:\n{}\n'.format('\n'.join(captions[:3])))
     t = time.time() - start_time
     assert len(filenames) == len(list(set(filenames)))
@@ -124,6 +135,9 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
             pickle.dump(raw_outputs, f, 2)
     with open(pjoin(c.infer_save_path, 'captions___{}.json'.format(ckpt_num)), 'w') as f:
         json.dump(coco_json, f)
+    if groups_json:
+        with open(pjoin(c.infer_save_path, 'caption_groups___{}.json'.format(ckpt_num)), 'w') as f:
+            json.dump(groups_json, f)
     speed_file = pjoin(c.infer_save_path, 'infer_speed.txt')
     if not os.path.isfile(speed_file):
         out = ['Using GPU #: {}'.format(c.gpu), 'Inference batch size: {}'.format(c.batch_size_infer),

@@ -351,29 +351,38 @@ class ModelBase(object):
 
     # ---- decode (model_base.py:692-757, :272-314) ----------------------------------------
     def _decode(self, images, beam_size, max_length, top_beam=True, want_attention=True, length_penalty_weight=0.0,
-                constraints=None):
+                constraints=None, groups=None):
         im_embed, fm = self._encode(images)
         return self._decode_features(im_embed, fm, beam_size, max_length, top_beam, want_attention, length_penalty_weight,
-                                     constraints)
+                                     constraints, groups)
 
     def _decode_features(self, im_embed, fm, beam_size, max_length, top_beam=True, want_attention=True,
-                         length_penalty_weight=0.0, constraints=None):
+                         length_penalty_weight=0.0, constraints=None, groups=None):
         """constraints: decoder.BeamConstraints in TOKENS (decoder.constraints_from_config translates a configuration's
-        words); beam search only."""
+        words); beam search only.  groups: decoder.BeamGroups; an active one decodes by diverse beam search: the top beam is
+        group 0's best (the caption of beam search of width beam / groups), and self.group_output holds the group-best
+        captions of the batch (group_best), None otherwise."""
         c = self._config
         iters = self.decoder.max_iterations(max_length, len(c.wtoi))
         constrained = constraints is not None and constraints.active
+        grouped = groups is not None and groups.active
+        self.group_output = None
         if constrained and beam_size <= 1:
             raise ValueError('beam constraints need beam search: infer_beam_size must be at least 2')
+        if grouped and beam_size <= 1:
+            raise ValueError('beam groups need beam search: infer_beam_size must be at least 2')
         if beam_size > 1:
-            if not want_attention and not length_penalty_weight and not constrained:
+            if not want_attention and not length_penalty_weight and not constrained and not grouped:
                 # captions alone: the ids come back through pinned memory behind one event (no stream drain per array)
                 r = {'predicted_ids': self.decoder.beam_search_ids(fm, im_embed, beam_size, iters)()}
             else:
                 r = self.decoder.beam_search(fm, im_embed, beam_size, iters, want_attention=want_attention,
-                                             length_penalty_weight=length_penalty_weight, constraints=constraints)
+                                             length_penalty_weight=length_penalty_weight, constraints=constraints,
+                                             groups=groups)
             pred = r['predicted_ids']                                  # (T, B, W)
             T = pred.shape[0]
+            if grouped:
+                self.group_output = group_best(r)
             attn = None
             if want_attention:
                 hist = r['attn_hist'].reshape(T, -1, beam_size, self.spec.H, self.spec.M)[:, :, 0]
@@ -389,6 +398,15 @@ class ModelBase(object):
             return ids, amap.cpu().numpy()
         ids, amap, _ = self.decoder.greedy(fm, im_embed, iters)
         return ids, amap.cpu().numpy()
+
+
+def group_best(r):
+    """The group-best captions of a grouped Decoder.beam_search result: ids (B, G, T), their final `scores` (B, G) and
+    their unpenalised log-probabilities (B, G), in group order (slot g * W / G is group g's best)."""
+    W = r['predicted_ids'].shape[2]
+    Wg = W // int(r['groups'])
+    return dict(ids=r['predicted_ids'][:, :, ::Wg].transpose(1, 2, 0).copy(), scores=r['scores'][-1][:, ::Wg].copy(),
+                log_probs=r['log_probs'][:, ::Wg].copy())
 
 
 class CaptionModel(ModelBase):
@@ -517,10 +535,11 @@ class CaptionModel(ModelBase):
         res = self.decoder.train_step(fm, im_embed, np.asarray(captions), training=False, use_graph=True)
         return res['loss']
 
-    def infer(self, batch=None, constraints=None):
+    def infer(self, batch=None, constraints=None, groups=None):
         """== sess.run(m_infer.infer_output) -> [dec_preds (B,T), attention_maps (B,H,T,M)].
         constraints: decoder.BeamConstraints; None reads the configuration (infer_min_length, infer_no_repeat_ngram,
-        infer_suppress_words).
+        infer_suppress_words).  groups: decoder.BeamGroups; None reads the configuration (infer_beam_groups,
+        infer_diversity).  With active groups dec_preds is group 0's best and self.group_output holds every group's.
         Batches drawn from the input pipeline are decoded with the encoder forward of the NEXT group of batches already
         running on a second stream (the decode steps are small launches that leave most of the GPU idle;
         config.pipeline_encoder, default on; config.pipeline_encoder_group batches per forward, 0 = auto).  Same
@@ -536,13 +555,15 @@ class CaptionModel(ModelBase):
             im_embed, fm = feats
         if constraints is None:
             constraints = cdec.constraints_from_config(c)
+        if groups is None:
+            groups = cdec.groups_from_config(c)
         ids, attn = self._decode_features(im_embed, fm, c.infer_beam_size, c.infer_max_length, top_beam=True,
                                           length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
-                                          constraints=constraints)
+                                          constraints=constraints, groups=groups)
         self.infer_output = [ids, attn]
         return self.infer_output
 
-    def infer_pipelined(self, want_attention=True, constraints=None):
+    def infer_pipelined(self, want_attention=True, constraints=None, groups=None):
         """Generator over the batches of the input pipeline -> [dec_preds (B,T), attention_maps or None] in input order, with
         the decode loops of THREE batches in flight (COMIC_INFER_IN_FLIGHT; one stream and one buffer set of the decoder each:
         Decoder.beam_search_ids(slot=)).
@@ -550,13 +571,16 @@ class CaptionModel(ModelBase):
         kernels of a second, independent batch fill those holes: 2.29 -> 1.64 ms per batch of 50 at beam 3 on the word
         baseline (tools/beam_time.py TWO=1), the same ids; three in flight +6 % over two (24.5k against 23.1k captions/s on one
         box; four and five lose: 23.9k, 19.3k -- each loop streams the 52 MB vocabulary projection per step).  Only the captions-only beam search runs this way (no attention
-        maps, no length penalty, no beam constraints: what `infer.py` writes unless --save_attention_maps); everything else
-        yields infer().  constraints: as infer()."""
+        maps, no length penalty, no beam constraints, no beam groups: what `infer.py` writes unless --save_attention_maps);
+        everything else yields infer().  constraints, groups: as infer()."""
         c, torch = self._config, self.torch
         lp = getattr(c, 'infer_length_penalty_weight', 0.0)
         if constraints is None:
             constraints = cdec.constraints_from_config(c)
         constrained = constraints is not None and constraints.active
+        if groups is None:
+            groups = cdec.groups_from_config(c)
+        constrained = constrained or (groups is not None and groups.active)     # (either keeps to the one-loop path)
         NL = max(1, min(5, int(os.environ.get('COMIC_INFER_IN_FLIGHT', '3'))))      # decode loops in flight (3: measured best of 1-5)
         if want_attention or lp or constrained or c.infer_beam_size <= 1 or not str(self.device).startswith('cuda'):
             NL = 1
@@ -567,7 +591,7 @@ class CaptionModel(ModelBase):
                     return
                 ids, attn = self._decode_features(feats[0], feats[1], c.infer_beam_size, c.infer_max_length, top_beam=True,
                                                   want_attention=want_attention, length_penalty_weight=lp,
-                                                  constraints=constraints)
+                                                  constraints=constraints, groups=groups)
                 yield [ids, attn]
         iters = self.decoder.max_iterations(c.infer_max_length, len(c.wtoi))
         lanes = [streams.lane(torch, self.device, 'infer%d' % k) for k in range(NL)]
@@ -822,12 +846,14 @@ class CaptionEnsemble(object):
             return [(m._embed(net), fm) for m in self.models]
         return [m._encode(images) for m in self.models]
 
-    def infer(self, batch=None, constraints=None):
+    def infer(self, batch=None, constraints=None, groups=None):
         """-> [dec_preds (B,T), attention_maps (B,H,T,M) of member 0], as CaptionModel.infer; without `batch` the images
-        come from member 0's input pipeline.  constraints: as CaptionModel.infer."""
+        come from member 0's input pipeline.  constraints, groups: as CaptionModel.infer."""
         c = self._config
         if constraints is None:
             constraints = cdec.constraints_from_config(c)
+        if groups is None:
+            groups = cdec.groups_from_config(c)
         if batch is None:
             batch = next(self.models[0].batch_ops)
         images = batch[0] if isinstance(batch, (tuple, list)) else batch
@@ -838,9 +864,10 @@ class CaptionEnsemble(object):
         assert W > 1, 'the ensemble decodes by beam search: infer_beam_size must be at least 2'
         r = self.decoder.beam_search([f[1] for f in feats], [f[0] for f in feats], W, iters, want_attention=True,
                                      length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
-                                     constraints=constraints)
+                                     constraints=constraints, groups=groups)
         pred = r['predicted_ids']                                  # (T, B, W)
         T = pred.shape[0]
+        self.group_output = group_best(r) if r['groups'] > 1 else None
         hist = r['attn_hist'].reshape(T, -1, W, spec.H, spec.M)[:, :, 0]
         self.infer_output = [pred[:, :, 0].T.copy(), hist.transpose(1, 2, 0, 3)]
         return self.infer_output

@@ -517,6 +517,35 @@ int comic_beam_step_constrained(const float* logits, const float* weights, int n
                                 int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores,
                                 int B, int W, int V, int end_id, float length_penalty_weight, const uint32_t* bits, int words,
                                 void* workspace, int64_t workspace_bytes, void* stream);
+/* Diverse beam search (Vijayakumar et al. 2016, Hamming diversity; extends rnn_decoder_beam_search,
+ * common/ops_rnn.py:49-112): the W slots of an entry form `groups` = G groups of Wg = W / G, group g owning the slots
+ * [g*Wg, (g+1)*Wg); diversity = lambda.  total[w][v] = log_probs[w] + step[w][v] and score[w][v] (total, or with a length
+ * penalty total / ((5 + len) / 6)^lpw) are the plain step's, _mask_probs for finished beams and -inf for banned
+ * candidates included.  The groups are processed in order g = 0 .. G-1:
+ *   count[v]   = the number of slots q < g*Wg of the entry whose word chosen at this step is v;
+ *   rank[w][v] = score[w][v] - lambda * count[v] for a live beam w and v != end_id, score[w][v] otherwise (a finished
+ *                beam and <EOS> are never penalised); the product is float(lambda) * float(count), subtracted once;
+ *   the group selects its Wg best among its own Wg * V candidates, rank descending, then entry-wide flat index
+ *   f = w*V + v ascending (all -inf / NaN: the lowest untaken flat index of the group's range);
+ *   slot g*Wg + r gets word = f % V, parent = f / V (an entry-wide slot, always inside the group), scores = the rank,
+ *   log_probs (the state) = the UNPENALISED total, finished and lengths as ever.
+ * The initial state has the first slot of every group live with log-probability 0.  G == 1 is the plain step to the bit;
+ * lambda == 0 gives G identical beams of width Wg; group 0 is always beam search of width Wg.  The penalty is per token at
+ * the same position (radix tokens: not per word).
+ * Limits: 1 <= groups <= W, W % groups == 0, diversity finite and >= 0, Wg <= V. */
+typedef struct comic_beam_groups {
+  int32_t groups;
+  float diversity;
+} comic_beam_groups;
+/* comic_beam_step_ensemble / comic_beam_step_constrained (common/ops_rnn.py:49-112) under groups, as a raw operator.
+ * bits may be NULL: no bans, and `words` is ignored; else bits [B*W][words], words == ceil(V/32).  groups must not be
+ * NULL.  One workgroup per entry loops over the groups; the split form (same eligibility rule, on the entry-wide W * V)
+ * is the statistics once and a chunk top-k + a merge per group: 1 + 2 G launches ordered by the stream.
+ * comic_beam_step_ensemble_workspace bytes suffice; comic_beam_step_ensemble_path() reports the form. */
+int comic_beam_step_diverse(const float* logits, const float* weights, int n_models, float* log_probs, int32_t* finished,
+                            int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int V,
+                            int end_id, float length_penalty_weight, const uint32_t* bits, int words,
+                            const comic_beam_groups* groups, void* workspace, int64_t workspace_bytes, void* stream);
 /* out[r,:] = in[(r/W)*W + parent[r], :]   (state re-ordering by parent beam) */
 int comic_gather_rows(const float* in, const int32_t* parent, float* out, int rows, int W, int cols,
                       void* stream);
@@ -751,6 +780,23 @@ int comic_decoder_beam_constrained(const comic_decoder_desc* descs, const comic_
                                    int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths,
                                    int32_t* finished, float* const* attn_hists, int32_t* steps_executed, void* workspace,
                                    int64_t workspace_bytes, void* stream);
+
+/* Diverse beam search (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112): comic_decoder_beam_ensemble /
+ * comic_decoder_beam_constrained -- the same loop; a single decoder is n_models == 1 with weight 1 -- whose beams start
+ * with the first slot of every group live and whose every step ranks under `groups` (comic_beam_step_diverse, the rule
+ * at comic_beam_groups).  constraints may be NULL; given, their rules hold unchanged (V >= W + n_suppress + 1 +
+ * max_steps, ...).  groups must not be NULL: 1 <= groups <= W, W % groups == 0, diversity finite and >= 0, W / groups <= V.
+ * Slot g * (W / groups) of the outputs is group g's best.  Everything else as comic_decoder_beam_ensemble.
+ * workspace: comic_decoder_beam_diverse_workspace(descs, n_models, B*W, max_steps, constrained) bytes, constrained != 0
+ * when constraints are given (the constrained layout), else the ensemble's. */
+int64_t comic_decoder_beam_diverse_workspace(const comic_decoder_desc* descs, int n_models, int rows, int max_steps,
+                                             int constrained);
+int comic_decoder_beam_diverse(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                               const float* const* fms, const float* const* im_embeds, const float* weights, int n_models,
+                               int B, int W, int max_steps, const comic_beam_constraints* constraints,
+                               const comic_beam_groups* groups, int32_t* step_ids, int32_t* parent_ids, float* scores,
+                               int64_t* lengths, int32_t* finished, float* const* attn_hists, int32_t* steps_executed,
+                               void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SCST reward scorer (host, multi-threaded)  common/scst/scorers.py:43-171      */

@@ -52,6 +52,11 @@ def create_parser():
       help='Beam search: no n-gram of this many words (characters with char tokens) occurs twice in a caption.')
     a('--infer_suppress_words', type=str, default=None,
       help='Beam search: comma-separated words that are never emitted, e.g. `<UNK>` (word and char tokens only).')
+    a('--infer_beam_groups', type=int, default=None,
+      help='Diverse beam search: split the beam into this many groups (infer_beam_size must be a multiple); also writes '
+           'caption_groups___N.json with the best caption of every group.')
+    a('--infer_diversity', type=float, default=None,
+      help='Diverse beam search: the Hamming diversity penalty a later group pays per earlier pick of the same token.')
     return p
 
 
@@ -80,9 +85,10 @@ def main(argv=None):
     save_name = 'beam_{}_lpen_{}'.format(c.infer_beam_size, c.infer_length_penalty_weight)
     save_name = {'test': 'infer_test_', 'valid': 'infer_valid_', 'coco_test': 'infer_cocoTest_',
                  'coco_valid': 'infer_cocoValid_'}[c.infer_set] + save_name
-    # constrained captions get a directory of their own: they never overwrite the unconstrained ones
-    from comic_amd.decoder import constraints_dir_suffix
-    save_name += constraints_dir_suffix(c)
+    # constrained and grouped captions get a directory of their own: they never overwrite the plain ones
+    from comic_amd.decoder import constraints_dir_suffix, groups_dir_suffix, groups_from_config
+    groups_from_config(c)           # (refuses groups that do not divide infer_beam_size before anything is loaded)
+    save_name += constraints_dir_suffix(c) + groups_dir_suffix(c)
     c.infer_save_path = pjoin(c.infer_checkpoints_dir, save_name)
     if os.path.exists(c.infer_save_path):
         print('\nINFO: `eval_log_path` already exists.')
