@@ -99,6 +99,10 @@ class BeamGroups(C.Structure):       # struct comic_beam_groups
     _fields_ = [('groups', c_int32), ('diversity', c_float)]
 
 
+class BeamSampling(C.Structure):     # struct comic_beam_sampling
+    _fields_ = [('temperature', c_float), ('seed_dev', c_void_p)]
+
+
 class GemmProb(C.Structure):         # struct comic_gemm_prob
     _fields_ = [(n, c_void_p) for n in ('A', 'B', 'C', 'bias', 'mask')] + [(n, c_int32) for n in (
         'M', 'N', 'K', 'lda', 'ldb', 'ldc', 'ld_mask')] + [(n, c_float) for n in ('alpha', 'beta', 'keep')] + [
@@ -201,6 +205,13 @@ _SIGS = {
                                         c_int64, P]),
     'comic_decoder_beam_diverse_workspace': (c_int64, [P, c_int, c_int, c_int, c_int]),
     'comic_decoder_beam_diverse': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, c_int64,
+                                           P]),
+    'comic_beam_sample_noise': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
+    'comic_beam_step_sampled_workspace': (c_int64, [c_int, c_int, c_int, c_int]),
+    'comic_beam_step_sampled': (c_int, [P, P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P,
+                                        c_int64, P]),
+    'comic_decoder_beam_sampled_workspace': (c_int64, [P, c_int, c_int, c_int, c_int]),
+    'comic_decoder_beam_sampled': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, c_int64,
                                            P]),
     'comic_scorer_create': (c_void_p, [c_char_p, P, c_int64, c_double]),
     'comic_scorer_destroy': (None, [c_void_p]),

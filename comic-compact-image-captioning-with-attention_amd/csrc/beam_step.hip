@@ -49,6 +49,26 @@
 //                always beam search of width Wg.  The penalty is per TOKEN at the same position (with radix tokens: not
 //                per word).  A candidate finds its count by one bit test in an LDS mask of the penalised words (hashed by
 //                v mod 32 768, so any V fits) and walks the list of at most 63 words only on a hit.
+//   Samples .... W independent chains (sampling n = W captions per image): every slot of an entry is live from the start
+//                (beam_init_kernel with width 1) and takes, at step t, the best of ITS OWN V candidates under
+//                  rank[v] = lp[v] * inv_temp + g(b, w, t, v)      for a live slot; -inf (a ban) stays -inf
+//                lowest v on ties, the lowest flat index of its row in the all-(-inf) / NaN corner.  lp[v] is the policy's
+//                step_lp exactly as above, inv_temp = 1.0f / temperature formed once on the host, and g Gumbel noise from
+//                a counter-based generator that nobody stores (splitmix.h; seed_dev = uint64[2] = {seed, image_base} in
+//                device memory, read at run time so a captured graph replays with a new seed):
+//                  k1 = splitmix64(splitmix64(seed) ^ (image_base + b))
+//                  k2 = splitmix64(k1 ^ ((uint64(w) << 32) | uint64(t)))      once per (slot, step), kept in LDS
+//                  r  = splitmix64(k2 ^ uint64(v)),  k = r >> 41,  u = (2k + 1) * 2^-24  (exact, never 0 or 1)
+//                  g  = -logf(-logf(u))                                       the accurate logf; g in [-2.82, 16.64]
+//                A finished slot sees no noise: _mask_probs makes it emit <EOS> and its log-probability carries over.
+//                word = v, parent = w (the slot itself), log_probs (the state) = old state + lp[v] and scores = the same
+//                value: the model's UNPERTURBED, UNTEMPERED log p(caption so far | image), which at a temperature != 1 is
+//                not the log-probability under the tempered distribution.  The perturbed rank is never returned.  No
+//                length penalty, no groups.  To the launches it is ONE group of all W slots whose selection round r is
+//                restricted to slot r (kPerSlot): the one-workgroup form loops over the slots, the split form is the
+//                statistics, one chunk launch (every slot's best per chunk, the unperturbed total beside it) and one
+//                merge -- 3 launches whatever W is.  The lists hold W candidates per chunk, so the totals need a block
+//                of their own in the workspace: comic_beam_step_sampled_workspace.
 //
 // Two forms, one copy of each kernel, instantiated per policy:
 //   beam_step_kernel ........ one workgroup per batch entry: any V, length penalty included
@@ -69,6 +89,7 @@
 #include <algorithm>
 
 #include "beam_select.h"
+#include "splitmix.h"
 
 // executor-internal: chunks per entry of the split form, and the bytes of its workspace for n members
 // (2 * n * B * W * chunks floats of partials + B * chunks * W (float + int32) candidates)
@@ -159,19 +180,21 @@ struct Bans {
 constexpr int kPenWords = 1024;      // LDS mask of the penalised words: bit (v mod 32 768)
 struct NoGroups {
   static constexpr bool kActive = false;
+  static constexpr bool kPerSlot = false;
   struct Pen {};
   __host__ __device__ __forceinline__ int groups() const { return 1; }
   __device__ __forceinline__ int group() const { return 0; }
   NoGroups at(int, float*, const int32_t*) const { return NoGroups{}; }
   __device__ __forceinline__ int chosen(int) const { return 0; }
-  __device__ __forceinline__ void clear(Pen&) const {}
+  __device__ __forceinline__ void clear(Pen&, int, int) const {}
   __device__ __forceinline__ void add(Pen&, int, int) const {}
-  __device__ __forceinline__ float rank(const Pen&, int, float score, bool, int, int) const { return score; }
+  __device__ __forceinline__ float rank(const Pen&, int, float score, float, bool, int, int, int) const { return score; }
   __device__ __forceinline__ void total(size_t, float) const {}
   __device__ __forceinline__ float total_of(size_t, const ValIdx& best) const { return best.v; }
 };
 struct Groups {
   static constexpr bool kActive = true;
+  static constexpr bool kPerSlot = false;
   int G;
   float lambda;
   int g;               // split form: the group this launch serves
@@ -187,7 +210,7 @@ struct Groups {
   Groups at(int group, float* totals, const int32_t* word_ids) const { return Groups{G, lambda, group, totals, word_ids}; }
   __device__ __forceinline__ int chosen(int row) const { return words[row]; }
   // (every thread; the caller's barrier makes it visible)
-  __device__ __forceinline__ void clear(Pen& p) const {
+  __device__ __forceinline__ void clear(Pen& p, int, int) const {
     for (int k = threadIdx.x; k < kPenWords; k += blockDim.x) p.mask[k] = 0u;
   }
   // slot q of the entry chose `word` at this step
@@ -199,8 +222,8 @@ struct Groups {
   __device__ __forceinline__ void total(size_t o, float t) const { cand_t[o] = t; }
   // merge: the total of the round's winner, candidate o (none: the round's -inf)
   __device__ __forceinline__ float total_of(size_t o, const ValIdx& best) const { return best.i == kNone ? best.v : cand_t[o]; }
-  // the rank of a candidate with `score`, npen slots before its group
-  __device__ __forceinline__ float rank(const Pen& p, int npen, float score, bool live, int v, int end_id) const {
+  // the rank of candidate v of slot w with `score` (its step log-probability `step`), npen slots before its group
+  __device__ __forceinline__ float rank(const Pen& p, int npen, float score, float, bool live, int, int v, int end_id) const {
     if (!live || v == end_id || !((p.mask[(v & (32 * kPenWords - 1)) >> 5] >> (v & 31)) & 1u)) return score;
     int count = 0;
     for (int q = 0; q < npen; ++q) count += (p.word[q] == v) ? 1 : 0;
@@ -213,14 +236,65 @@ struct Groups {
   }
 };
 
-// unpenalised total of candidate (beam w, word v), flat index f, of the entry whose member-0 logits start at lg and whose
-// bans are bn: _mask_probs for a finished beam, -inf for a banned candidate of a live one
+// The generator of the Samples policy (the contract: include/comic_hip.h, comic_beam_sampling).  seed = {seed, image_base}.
+__device__ __forceinline__ uint64_t sample_k2(const uint64_t* __restrict__ seed, int b, int w, int t) {
+  const uint64_t k1 = splitmix64(splitmix64(seed[0]) ^ (seed[1] + (uint64_t)b));
+  return splitmix64(k1 ^ (((uint64_t)w << 32) | (uint64_t)(uint32_t)t));
+}
+__device__ __forceinline__ int sample_k(uint64_t k2, int v) { return (int)(splitmix64(k2 ^ (uint64_t)v) >> 41); }
+// u = (2k + 1) * 2^-24 is exact in fp32 and never 0 or 1; the accurate logf (the native approximation loses g near u -> 1)
+__device__ __forceinline__ float sample_gumbel(int k) {
+  const float u = (float)(2 * k + 1) * (1.0f / 16777216.0f);
+  return -logf(-logf(u));
+}
+// W independent chains: every slot takes the best of ITS OWN V candidates under rank = lp * inv_temp + Gumbel noise.  One
+// "group" of all W slots as far as the launches go (groups() == 1: the statistics, one chunk launch, one merge); kPerSlot
+// restricts selection round r to slot r in every kernel.  The candidates carry their unperturbed totals as under Groups.
+struct Samples {
+  static constexpr bool kActive = true;
+  static constexpr bool kPerSlot = true;
+  const uint64_t* seed;  // device: {seed, image_base}, read at run time
+  float inv_temp;
+  int t;                 // the step
+  float* cand_t;         // split form: the candidates' unperturbed totals, beside cand_v (their ranks)
+  struct Pen {
+    uint64_t k2[64];     // the key of (entry, slot w, step): formed once per workgroup
+  };
+  __host__ __device__ __forceinline__ int groups() const { return 1; }
+  __device__ __forceinline__ int group() const { return 0; }
+  Samples at(int, float* totals, const int32_t*) const { return Samples{seed, inv_temp, t, totals}; }
+  __device__ __forceinline__ int chosen(int) const { return 0; }
+  // (the caller's barrier makes it visible)
+  __device__ __forceinline__ void clear(Pen& p, int b, int W) const {
+    if ((int)threadIdx.x < W) p.k2[threadIdx.x] = sample_k2(seed, b, threadIdx.x, t);
+  }
+  __device__ __forceinline__ void add(Pen&, int, int) const {}
+  __device__ __forceinline__ void total(size_t o, float tot) const { cand_t[o] = tot; }
+  __device__ __forceinline__ float total_of(size_t o, const ValIdx& best) const { return best.i == kNone ? best.v : cand_t[o]; }
+  // a finished slot sees no noise; -inf (a banned candidate) stays -inf
+  __device__ __forceinline__ float rank(const Pen& p, int, float score, float step, bool live, int w, int v, int) const {
+    if (!live) return score;
+    const float g = sample_gumbel(sample_k(p.k2[w], v));
+    {
+#pragma clang fp contract(off)
+      const float scaled = step * inv_temp;
+      return scaled + g;
+    }
+  }
+};
+
+// step log-probability / unpenalised total of candidate (beam w, word v), flat index f, of the entry whose member-0 logits
+// start at lg and whose bans are bn: _mask_probs for a finished beam, -inf for a banned candidate of a live one
+template <class P, class Bn>
+__device__ __forceinline__ float cand_step(const P& pol, const Bn& bn, const float* __restrict__ lg, size_t mstride, int f,
+                                           int w, int v, int end_id, const typename P::Rows& s) {
+  return s.fin[w] ? ((v == end_id) ? 0.f : -FLT_MAX)                                                     // dtype.min
+                  : (bn.hit(w, v) ? -INFINITY : pol.step_lp(lg, mstride, f, w, s));
+}
 template <class P, class Bn>
 __device__ __forceinline__ float cand_total(const P& pol, const Bn& bn, const float* __restrict__ lg, size_t mstride, int f,
                                             int w, int v, int end_id, const typename P::Rows& s) {
-  const float step = s.fin[w] ? ((v == end_id) ? 0.f : -FLT_MAX)                                         // dtype.min
-                              : (bn.hit(w, v) ? -INFINITY : pol.step_lp(lg, mstride, f, w, s));
-  return s.lp[w] + step;
+  return s.lp[w] + cand_step(pol, bn, lg, mstride, f, w, v, end_id, s);
 }
 
 // (Groups, split form) the unpenalised total of a chunk's chosen candidate f, -inf for "none"
@@ -280,7 +354,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
   const size_t mstride = (size_t)B * W * V;
   const float* lg = logits + (size_t)b * W * V;
   const Bn bn = bans.entry(b, W);
-  gr.clear(pen);
+  gr.clear(pen, b, W);
   // the entry's beam state (W <= 64): loaded first, in flight behind the passes over the logits
   float lp_w = 0.f;
   int fin_w = 0;
@@ -313,7 +387,8 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
     s_len[tid] = len_w;
   }
   __syncthreads();
-  // group g selects its Wg slots among the candidates of its own Wg beams (NoGroups: one group, the W beams)
+  // group g selects its Wg slots among the candidates of its own Wg beams (NoGroups: one group, the W beams; Samples: one
+  // group whose round r is slot r's best among its own V candidates)
   const int Wg = Gr::kActive ? W / gr.groups() : W, total = Wg * V;
   int g = 0;
   do {
@@ -325,17 +400,19 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
     for (int r = 0; r < Wg; ++r) {
       float bv = -INFINITY;
       int bi = kNone;
-      for (int f = f0 + tid; f < f0 + total; f += 256) {
+      const int fa = Gr::kPerSlot ? r * V : f0, fb = Gr::kPerSlot ? fa + V : f0 + total;
+      for (int f = fa + tid; f < fb; f += 256) {
         bool taken = false;
-        for (int q = 0; q < r; ++q) taken |= (s_sel[w0 + q] == f);
+        for (int q = 0; q < (Gr::kPerSlot ? 0 : r); ++q) taken |= (s_sel[w0 + q] == f);
         if (taken) continue;
         const int w = f / V, v = f - w * V;
-        float tot = cand_total(pol, bn, lg, mstride, f, w, v, end_id, s);
+        const float step = cand_step(pol, bn, lg, mstride, f, w, v, end_id, s);
+        float tot = s.lp[w] + step;
         if (lpw != 0.f) {
           const long long len = s_len[w] + ((s.fin[w] || v == end_id) ? 0 : 1);
           tot = tot / powf((5.f + (float)len) / 6.f, lpw);
         }
-        if (Gr::kActive) tot = gr.rank(pen, w0, tot, !s.fin[w], v, end_id);
+        if (Gr::kActive) tot = gr.rank(pen, w0, tot, step, !s.fin[w], w, v, end_id);
         if (better(tot, f, bv, bi)) {
           bv = tot;
           bi = f;
@@ -343,7 +420,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
       }
       const ValIdx best = block_argmax(bv, bi, sh);
       if (tid == 0) {
-        s_sel[w0 + r] = best.i == kNone ? lowest_untaken(s_sel + w0, r, f0) : best.i;
+        s_sel[w0 + r] = best.i != kNone ? best.i : Gr::kPerSlot ? r * V : lowest_untaken(s_sel + w0, r, f0);
         s_selv[w0 + r] = best.v;
       }
       __syncthreads();
@@ -353,8 +430,9 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
     const int f = s_sel[tid], parent = f / V, word = f - parent * V;
     // the state carries the unpenalised total log probability of the chosen candidate
     const float state = (Gr::kActive || lpw != 0.f) ? cand_total(pol, bn, lg, mstride, f, parent, word, end_id, s) : s_selv[tid];
-    write_beam(b * W + tid, f, s_selv[tid], state, s.fin, s_len, V, end_id, log_probs, finished, lengths, word_ids, parent_ids,
-               scores);
+    // (Samples: the perturbed rank is never returned; scores is the state)
+    write_beam(b * W + tid, f, Gr::kPerSlot ? state : s_selv[tid], state, s.fin, s_len, V, end_id, log_probs, finished, lengths,
+               word_ids, parent_ids, scores);
   }
 }
 
@@ -415,7 +493,7 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
   const Bn bn = bans.entry(b, W);
   const int Wg = W / gr.groups(), w0 = gr.group() * Wg;       // this launch's beams: [w0, w0 + Wg)
   if (Gr::kActive) {
-    gr.clear(pen);
+    gr.clear(pen, b, W);
     __syncthreads();
     if (tid < w0) gr.add(pen, tid, gr.chosen(b * W + tid));   // (visible behind the barrier below)
   }
@@ -465,7 +543,8 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
       const int v = v0 + tid + 256 * k;
       if (w < w0 + Wg && v < v1) {
         const int f = w * V + v;
-        tv[e] = gr.rank(pen, w0, cand_total(pol, bn, lg, mstride, f, w, v, end_id, s), !s.fin[w], v, end_id);
+        const float step = cand_step(pol, bn, lg, mstride, f, w, v, end_id, s);
+        tv[e] = gr.rank(pen, w0, s.lp[w] + step, step, !s.fin[w], w, v, end_id);
         ti[e] = f;
       }
       if (++k == kper) {
@@ -477,16 +556,24 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
     for (int r = 0; r < Wg; ++r) {
       float bv = -INFINITY;
       int bi = kNone;
+      int ws = 0, ks = 0;                           // (Samples) the slot of register slot e: round r takes slot r's best
 #pragma unroll
-      for (int e = 0; e < kLocal; ++e)
-        if (ti[e] != kNone && better(tv[e], ti[e], bv, bi)) {
+      for (int e = 0; e < kLocal; ++e) {
+        if ((!Gr::kPerSlot || ws == r) && ti[e] != kNone && better(tv[e], ti[e], bv, bi)) {
           bv = tv[e];
           bi = ti[e];
         }
+        if (Gr::kPerSlot && ++ks == kper) {
+          ks = 0;
+          ++ws;
+        }
+      }
       const ValIdx best = block_argmax_1b(bv, bi, sh8, r & 1);
+      if (!Gr::kPerSlot) {
 #pragma unroll
-      for (int e = 0; e < kLocal; ++e)
-        if (ti[e] == best.i) ti[e] = kNone;         // taken (flat indices are unique; kNone marks "none")
+        for (int e = 0; e < kLocal; ++e)
+          if (ti[e] == best.i) ti[e] = kNone;       // taken (flat indices are unique; kNone marks "none")
+      }
       if (tid == 0) {
         cand_v[out + r] = best.v;
         cand_i[out + r] = best.i;
@@ -496,17 +583,18 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
     if (Gr::kActive && tid < Wg) gr.total(out + tid, chunk_total(pol, bn, lg, mstride, mine, V, end_id, s));
     return;
   }
-  const int total = Wg * nv;
+  const int total = Gr::kPerSlot ? nv : Wg * nv;    // (Samples: round r scans slot r's columns)
   for (int r = 0; r < Wg; ++r) {
     float bv = -INFINITY;
     int bi = kNone;
     for (int j = tid; j < total; j += 256) {
-      const int wl = j / nv, w = w0 + wl, v = v0 + (j - wl * nv);
+      const int wl = Gr::kPerSlot ? r : j / nv, w = w0 + wl, v = v0 + (Gr::kPerSlot ? j : j - wl * nv);
       const int f = w * V + v;
       bool taken = false;
-      for (int q = 0; q < r; ++q) taken |= (s_sel[q] == f);
+      for (int q = 0; q < (Gr::kPerSlot ? 0 : r); ++q) taken |= (s_sel[q] == f);
       if (taken) continue;
-      const float tot = gr.rank(pen, w0, cand_total(pol, bn, lg, mstride, f, w, v, end_id, s), !s.fin[w], v, end_id);
+      const float step = cand_step(pol, bn, lg, mstride, f, w, v, end_id, s);
+      const float tot = gr.rank(pen, w0, s.lp[w] + step, step, !s.fin[w], w, v, end_id);
       if (better(tot, f, bv, bi)) {
         bv = tot;
         bi = f;
@@ -548,6 +636,24 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
   const int n = chunks * Wg;
   const float* cv = cand_v + (size_t)b * n;
   const int32_t* ci = cand_i + (size_t)b * n;
+  if (Gr::kPerSlot) {                  // slot tid's best over the chunks' lists (one candidate per chunk and slot)
+    if (tid < W) {
+      float bv = -INFINITY;
+      int bi = kNone, bj = 0;
+      for (int c = 0; c < chunks; ++c) {
+        const int j = c * W + tid, f = ci[j];
+        if (f != kNone && better(cv[j], f, bv, bi)) {
+          bv = cv[j];
+          bi = f;
+          bj = j;
+        }
+      }
+      const float tot = gr.total_of((size_t)b * n + bj, ValIdx{bv, bi});
+      write_beam(b * W + tid, bi == kNone ? tid * V : bi, tot, tot, s_fin, s_len, V, end_id, log_probs, finished, lengths,
+                 word_ids, parent_ids, scores);
+    }
+    return;
+  }
   for (int r = 0; r < Wg; ++r) {
     float bv = -INFINITY;
     int bi = kNone, bj = 0;
@@ -589,7 +695,7 @@ int beam_step_launch(const P& pol, const Bn& bans, Gr gr, int n, const float* lo
                      int64_t ws_bytes, hipStream_t st, int* path) {
   const int chunks = comic_beam_step_chunks(B, V);
   const bool split = lpw == 0.f && (long)W * V >= 8192 && chunks >= 2 && ws &&
-                     ws_bytes >= comic_beam_step_split_bytes(n, B, W, chunks);
+                     ws_bytes >= comic_beam_step_split_bytes(n, B, W, chunks) + (Gr::kPerSlot ? (int64_t)B * chunks * W * 4 : 0);
   if (path) *path = split ? 1 : 0;
   if (!split) {
     hipLaunchKernelGGL((beam_step_kernel<P, Bn, Gr>), dim3(B), dim3(256), 0, st, logits, pol, bans, log_probs, finished, lengths, word_ids,
@@ -600,7 +706,8 @@ int beam_step_launch(const P& pol, const Bn& bans, Gr gr, int n, const float* lo
   float* pmax = (float*)ws;
   float* psum = pmax + (size_t)n * B * W * chunks;
   float* cand_v = psum + (size_t)n * B * W * chunks;
-  int32_t* cand_i = (int32_t*)(cand_v + (size_t)B * chunks * W);
+  // (Samples: W candidates per chunk, so their totals take a block of their own between the ranks and the indices)
+  int32_t* cand_i = (int32_t*)(cand_v + (size_t)B * chunks * W * (Gr::kPerSlot ? 2 : 1));
   hipLaunchKernelGGL(beam_stats_kernel<P>, dim3(chunks, W, n * B), dim3(256), 0, st, logits, pol, pmax, psum, B, W, V, chunks,
                      g_comic_stop.p, g_comic_stop.t);
   // (Groups: the lists are Wg <= W / 2 per chunk, so the totals fit behind the ranks inside cand_v's W per chunk)
@@ -653,11 +760,13 @@ extern "C" int64_t comic_beam_step_ensemble_workspace(int n_models, int B, int W
 }
 
 // the ensemble step's argument checks and launch; bits null: no bans (the code of comic_beam_step_ensemble as it was);
-// grp null or one group: no groups (G == 1 IS the plain step: the same instantiation, the same launches)
+// grp null or one group: no groups (G == 1 IS the plain step: the same instantiation, the same launches); smp: the Samples
+// policy of a sampled step (then grp is null and the penalty weight 0)
 static int ens_step(const char* who, const float* logits, const float* weights, int n_models, float* log_probs,
                     int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W,
                     int V, int end_id, float length_penalty_weight, const uint32_t* bits, int words,
-                    const comic_beam_groups* grp, void* workspace, int64_t workspace_bytes, void* stream) {
+                    const comic_beam_groups* grp, void* workspace, int64_t workspace_bytes, void* stream,
+                    const Samples* smp = nullptr) {
   COMIC_REQUIRE(logits && weights && log_probs && finished && lengths && word_ids && parent_ids && scores,
                 "%s: null pointer", who);
   COMIC_REQUIRE(n_models >= 1 && n_models <= kEnsMax, "%s: 1 to %d members (got %d)", who, kEnsMax, n_models);
@@ -673,6 +782,13 @@ static int ens_step(const char* who, const float* logits, const float* weights, 
     wsum += weights[m];
   }
   COMIC_REQUIRE(wsum > 0.f, "%s: every weight is zero", who);
+  if (smp) {
+    if (bits)
+      return beam_step_launch(pol, Bans{bits, words}, *smp, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids,
+                              scores, B, W, V, end_id, 0.f, workspace, workspace_bytes, (hipStream_t)stream, &g_ens_step_path);
+    return beam_step_launch(pol, NoBans{}, *smp, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, B,
+                            W, V, end_id, 0.f, workspace, workspace_bytes, (hipStream_t)stream, &g_ens_step_path);
+  }
   if (grp && grp->groups > 1) {
     const Groups gr{grp->groups, grp->diversity, 0, nullptr, nullptr};
     if (bits)
@@ -731,4 +847,60 @@ extern "C" int comic_beam_step_diverse(const float* logits, const float* weights
   COMIC_REQUIRE(!bits || words == (V + 31) / 32, "beam_step_diverse: %d mask words for a vocabulary of %d", words, V);
   return ens_step("beam_step_diverse", logits, weights, n_models, log_probs, finished, lengths, word_ids, parent_ids, scores,
                   B, W, V, end_id, length_penalty_weight, bits, words, groups, workspace, workspace_bytes, stream);
+}
+
+// ---- sampling inside the step ------------------------------------------------------------------------------------------
+namespace {
+__global__ __launch_bounds__(256) void beam_sample_noise_kernel(const uint64_t* __restrict__ seed, int W, int t, int V, long n,
+                                                                int32_t* __restrict__ k_out, float* __restrict__ g_out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int row = (int)(i / V), v = (int)(i - (long)row * V), b = row / W, w = row - b * W;
+  const int k = sample_k(sample_k2(seed, b, w, t), v);
+  if (k_out) k_out[i] = k;
+  if (g_out) g_out[i] = sample_gumbel(k);
+}
+}  // namespace
+
+// executor-internal (decoder_exec.hip checks a loop's sampling once, in front of its first launch)
+int comic_beam_sampling_check(const comic_beam_sampling* s, const char* who, float lpw, int W) {
+  COMIC_REQUIRE(s, "%s: null sampling", who);
+  COMIC_REQUIRE(s->seed_dev, "%s: null seed_dev", who);
+  COMIC_REQUIRE(s->temperature > 0.f && s->temperature <= FLT_MAX, "%s: temperature must be finite and > 0", who);
+  COMIC_REQUIRE(1.0f / s->temperature <= FLT_MAX, "%s: the reciprocal of the temperature is not finite", who);
+  COMIC_REQUIRE(lpw == 0.f, "%s: a length penalty does not combine with sampling", who);
+  COMIC_REQUIRE(W >= 1 && W <= 64, "%s: the number of samples must be in [1,64] (got %d)", who, W);
+  return 0;
+}
+
+extern "C" int comic_beam_sample_noise(const uint64_t* seed_dev, int B, int W, int t, int V, int32_t* k_out, float* g_out,
+                                       void* stream) {
+  COMIC_REQUIRE(seed_dev, "beam_sample_noise: null seed_dev");
+  COMIC_REQUIRE(k_out || g_out, "beam_sample_noise: no output");
+  COMIC_REQUIRE(B > 0 && W >= 1 && W <= 64 && V > 0 && t >= 0, "beam_sample_noise: bad shape");
+  const long n = (long)B * W * V;
+  COMIC_REQUIRE(n < (1L << 31), "beam_sample_noise: B*W*V too large");
+  hipLaunchKernelGGL(beam_sample_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed_dev, W,
+                     t, V, n, k_out, g_out);
+  COMIC_LAUNCH_CHECK("beam_sample_noise");
+  return 0;
+}
+
+extern "C" int64_t comic_beam_step_sampled_workspace(int n_models, int B, int W, int V) {
+  if (n_models < 1 || n_models > kEnsMax || B <= 0 || W <= 0 || V <= 0) return -1;
+  const int chunks = comic_beam_step_chunks(B, V);
+  return comic_beam_step_split_bytes(n_models, B, W, chunks) + (int64_t)B * chunks * W * 4;
+}
+
+extern "C" int comic_beam_step_sampled(const float* logits, const float* weights, int n_models, float* log_probs,
+                                       int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids,
+                                       float* scores, int B, int W, int V, int end_id, const uint32_t* bits, int words,
+                                       const comic_beam_sampling* sampling, int t, void* workspace, int64_t workspace_bytes,
+                                       void* stream) {
+  if (int rc = comic_beam_sampling_check(sampling, "beam_step_sampled", 0.f, W)) return rc;
+  COMIC_REQUIRE(t >= 0, "beam_step_sampled: negative step %d", t);
+  COMIC_REQUIRE(!bits || (V > 0 && words == (V + 31) / 32), "beam_step_sampled: %d mask words for a vocabulary of %d", words, V);
+  const Samples smp{sampling->seed_dev, 1.0f / sampling->temperature, t, nullptr};
+  return ens_step("beam_step_sampled", logits, weights, n_models, log_probs, finished, lengths, word_ids, parent_ids, scores,
+                  B, W, V, end_id, 0.f, bits, words, nullptr, workspace, workspace_bytes, stream, &smp);
 }

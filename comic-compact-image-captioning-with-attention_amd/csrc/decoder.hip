@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "decoder_math.h"
+#include "splitmix.h"
 
 namespace {
 
@@ -158,12 +159,6 @@ __global__ void dropout_apply_kernel(const float* __restrict__ x, const float* _
   y[i] = mask ? (x[i] / keep) * mask[i] : x[i];
 }
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 __global__ void dropout_mask_kernel(float* __restrict__ mask, long n, float keep, uint64_t seed,
                                     const uint64_t* __restrict__ seed_dev, uint64_t offset) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

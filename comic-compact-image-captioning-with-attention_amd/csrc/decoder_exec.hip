@@ -120,6 +120,7 @@ int comic_beam_step_ws(const float* logits, float* log_probs, int32_t* finished,
                        int64_t ws_bytes, hipStream_t st);
 int64_t comic_beam_step_split_bytes(int n, int B, int W, int chunks);
 int comic_beam_groups_check(const comic_beam_groups* g, const char* who, int W, int V);
+int comic_beam_sampling_check(const comic_beam_sampling* s, const char* who, float lpw, int W);
 // beam_bans.hip
 int comic_beam_constraints_check(const comic_beam_constraints* c, const char* who, int W, int V, int end_id, int max_steps,
                                  bool whole);
@@ -2134,7 +2135,9 @@ struct EnsBufs {
 };
 // bytes of the ensemble step's workspace for any split of `rows` into batch x beam: (2 n + 2) * rows * chunks words, chunks <= 32
 int64_t ens_step_ws_bound(int n, int rows) { return comic_beam_step_split_bytes(n, rows, 1, 32); }
-EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64_t bytes, int ban_steps = 0) {
+// sampled: the step's lists carry every slot's total too (comic_beam_step_sampled_workspace): rows * chunks words more
+EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64_t bytes, int ban_steps = 0,
+                  bool sampled = false) {
   EnsBufs e{};
   size_t off = 0;
   e.ok = true;
@@ -2149,7 +2152,7 @@ EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64
   e.logits = w.take<float>((size_t)n * R * descs[0].V);
   e.log_probs = w.take<float>(R);
   e.ids = w.take<int32_t>(R);
-  e.step_bytes = ens_step_ws_bound(n, R);
+  e.step_bytes = ens_step_ws_bound(n, R) + (sampled ? (int64_t)R * 32 * 4 : 0);
   e.step_ws = w.take<char>((size_t)e.step_bytes);
   if (ban_steps > 0) {
     e.bits = w.take<uint32_t>((size_t)R * ((descs[0].V + 31) / 32));
@@ -2177,12 +2180,14 @@ extern "C" int64_t comic_decoder_beam_constrained_workspace(const comic_decoder_
 
 // The ONE ensemble loop.  cons null: comic_decoder_beam_ensemble, launch for launch as it always was; else every step
 // builds the beams' ban masks first (beam_bans.hip) and ranks through them (the Bans policy of beam_step.hip).  grp null:
-// one beam of width W; else the first slot of every group starts live and every step ranks under the Groups policy.
+// one beam of width W; else the first slot of every group starts live and every step ranks under the Groups policy.  smp
+// null: no sampling; else (grp is null) every slot starts live and step t ranks under the Samples policy.
 static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decoder_params* params, const float* const* fms,
                              const float* const* im_embeds, const float* weights, int n_models, int B, int W, int max_steps,
                              int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
                              float* const* attn_hists, int32_t* steps_executed, const comic_beam_constraints* cons,
-                             const comic_beam_groups* grp, void* workspace, int64_t workspace_bytes, void* stream) {
+                             const comic_beam_groups* grp, const comic_beam_sampling* smp, void* workspace,
+                             int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(descs && params && fms && im_embeds && weights && step_ids && parent_ids && scores && lengths && finished &&
                     steps_executed && workspace,
                 "beam_ensemble: null pointer");
@@ -2199,8 +2204,9 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
   COMIC_REQUIRE(W <= V && (long)W * V < (1L << 31), "beam_ensemble: beam*V too large or beam > V");
   if (cons) RC(comic_beam_constraints_check(cons, "beam_constrained", W, V, descs[0].end_id, max_steps, true));
   if (grp) RC(comic_beam_groups_check(grp, "beam_diverse", W, V));
+  if (smp) RC(comic_beam_sampling_check(smp, "beam_sampled", descs[0].length_penalty_weight, W));
   hipStream_t st = (hipStream_t)stream;
-  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, cons ? max_steps : 0);
+  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, cons ? max_steps : 0, smp != nullptr);
   COMIC_REQUIRE(L.ok && (int64_t)L.bytes <= workspace_bytes, "beam_ensemble: workspace too small");
   g_splitk_ws = L.m[0].splitk;               // members run back to back on the one stream: one split-K scratch serves all
   const float lpw = descs[0].length_penalty_weight;
@@ -2214,9 +2220,9 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
     RC(beam_member_begin(d, p, fms[m], im_embeds[m], B, W, ws, st, e));
     e.w_o = aligned_w_o(d, p, ws.wo_pad, &e.ld_wo, st);
   }
-  // (groups: row i starts live when i % Wg == 0, the first slot of its group)
+  // (groups: row i starts live when i % Wg == 0, the first slot of its group; sampling: every row)
   hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, L.log_probs, finished, lengths, R,
-                     grp ? W / grp->groups : W);
+                     smp ? 1 : grp ? W / grp->groups : W);
   hipLaunchKernelGGL(fill_i32_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, L.ids, descs[0].start_id, (long)R);
   hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(64), 0, st, steps_executed, max_steps, 1L);
   COMIC_LAUNCH_CHECK("beam_ensemble init");
@@ -2262,7 +2268,11 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
     if (cons)
       RC(comic_beam_bans_launch(t == 0 ? nullptr : (const int32_t*)ids_in, par_in, finished, lengths, L.ban_hist, L.bits, t, B,
                                 W, V, max_steps, descs[0].end_id, cons, st));
-    if (grp) {
+    if (smp) {
+      RC(comic_beam_step_sampled(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
+                                 B, W, V, descs[0].end_id, cons ? L.bits : nullptr, (V + 31) / 32, smp, t, L.step_ws,
+                                 L.step_bytes, (void*)st));
+    } else if (grp) {
       RC(comic_beam_step_diverse(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
                                  B, W, V, descs[0].end_id, lpw, cons ? L.bits : nullptr, (V + 31) / 32, grp, L.step_ws,
                                  L.step_bytes, (void*)st));
@@ -2286,7 +2296,8 @@ extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, cons
                                            float* scores, int64_t* lengths, int32_t* finished, float* const* attn_hists,
                                            int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream) {
   return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
-                           lengths, finished, attn_hists, steps_executed, nullptr, nullptr, workspace, workspace_bytes, stream);
+                           lengths, finished, attn_hists, steps_executed, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+                           stream);
 }
 
 extern "C" int comic_decoder_beam_constrained(const comic_decoder_desc* descs, const comic_decoder_params* params,
@@ -2298,8 +2309,8 @@ extern "C" int comic_decoder_beam_constrained(const comic_decoder_desc* descs, c
                                               int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(constraints, "beam_constrained: null constraints");
   return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
-                           lengths, finished, attn_hists, steps_executed, constraints, nullptr, workspace, workspace_bytes,
-                           stream);
+                           lengths, finished, attn_hists, steps_executed, constraints, nullptr, nullptr, workspace,
+                           workspace_bytes, stream);
 }
 
 extern "C" int64_t comic_decoder_beam_diverse_workspace(const comic_decoder_desc* descs, int n_models, int rows,
@@ -2317,6 +2328,25 @@ extern "C" int comic_decoder_beam_diverse(const comic_decoder_desc* descs, const
                                           void* workspace, int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(groups, "beam_diverse: null groups");
   return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
-                           lengths, finished, attn_hists, steps_executed, constraints, groups, workspace, workspace_bytes,
-                           stream);
+                           lengths, finished, attn_hists, steps_executed, constraints, groups, nullptr, workspace,
+                           workspace_bytes, stream);
+}
+
+extern "C" int64_t comic_decoder_beam_sampled_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                        int max_steps, int constrained) {
+  if (comic_decoder_beam_diverse_workspace(descs, n_models, rows, max_steps, constrained) < 0) return -1;
+  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0, constrained ? max_steps : 0, true).bytes;
+}
+
+extern "C" int comic_decoder_beam_sampled(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                          const float* const* fms, const float* const* im_embeds, const float* weights,
+                                          int n_models, int B, int W, int max_steps,
+                                          const comic_beam_constraints* constraints, const comic_beam_sampling* sampling,
+                                          int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths,
+                                          int32_t* finished, float* const* attn_hists, int32_t* steps_executed,
+                                          void* workspace, int64_t workspace_bytes, void* stream) {
+  COMIC_REQUIRE(sampling, "beam_sampled: null sampling");
+  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
+                           lengths, finished, attn_hists, steps_executed, constraints, nullptr, sampling, workspace,
+                           workspace_bytes, stream);
 }

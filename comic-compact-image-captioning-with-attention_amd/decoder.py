@@ -432,6 +432,90 @@ def groups_dir_suffix(c):
     return '_grp%d_div%g' % (int(1 if g is None else g), float(0.0 if d is None else d))
 
 
+class BeamSampling:
+    """Sampling inside the beam step (comic_beam_sampling; extends rnn_decoder_beam_search, ops_rnn.py:49-112): the `beam`
+    slots of an image are `beam` independent chains, each drawn from the step distribution at `temperature` by the
+    Gumbel-max rule, with noise from a counter-based generator keyed by (seed, the image's index in the run, slot, step,
+    token).  The beam state is the chain's log p(caption | image) under the model: unperturbed and untempered.  The
+    temperature is part of a decode context's key (it is baked into the captured graph); the seed is not: it lives in a
+    device tensor that is written in front of every launch or replay.  enabled=False is the inactive value."""
+
+    def __init__(self, temperature=1.0, seed=0, enabled=True):
+        self.temperature, self.seed, self.enabled = float(temperature), int(seed), bool(enabled)
+
+    def key(self):
+        return (self.temperature, self.seed, self.enabled)
+
+    def __eq__(self, other):
+        return isinstance(other, BeamSampling) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'BeamSampling(temperature=%r, seed=%d%s)' % (self.temperature, self.seed, '' if self.enabled else ', enabled=False')
+
+    @property
+    def active(self):
+        return self.enabled
+
+    def ctx_key(self):
+        """What a decode context is keyed by: the temperature as the fp32 value the kernels see; not the seed."""
+        return ('sample', float(np.float32(self.temperature)))
+
+    def check(self, beam, length_penalty_weight=0.0, groups=None):
+        """The rules of the C side, on the host before any GPU call; raises ValueError naming the field."""
+        with np.errstate(all='ignore'):
+            t = np.float32(self.temperature)
+            inv = np.float32(1.0) / t
+        if not (np.isfinite(t) and t > 0):
+            raise ValueError('temperature must be finite and > 0, got %r' % self.temperature)
+        if not np.isfinite(inv):
+            raise ValueError('temperature %r has no finite fp32 reciprocal' % self.temperature)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError('seed must be in [0, 2^64), got %d' % self.seed)
+        if not self.enabled:
+            return
+        if not 1 <= int(beam) <= 64:
+            raise ValueError('sampling: the number of samples (beam) must be in [1,64], got %d' % int(beam))
+        if length_penalty_weight:
+            raise ValueError('sampling does not combine with a length penalty (length_penalty_weight=%r)'
+                             % length_penalty_weight)
+        if groups is not None and groups.groups > 1:
+            raise ValueError('sampling does not combine with beam groups (groups=%d)' % groups.groups)
+
+    def c_struct(self, seed_dev):
+        """seed_dev: the address of the device uint64[2] {seed, image_base}."""
+        g = L.BeamSampling()
+        g.temperature, g.seed_dev = self.temperature, seed_dev
+        return g
+
+    def seed_words(self, image_base=0):
+        """{seed, image_base} as the int64 view of the device's uint64[2]."""
+        if not 0 <= int(image_base) < 2 ** 64:
+            raise ValueError('image_base must be in [0, 2^64), got %d' % int(image_base))
+        return np.array([self.seed, int(image_base)], np.uint64).view(np.int64)
+
+
+def sampling_from_config(c):
+    """The BeamSampling a configuration asks for (infer_sample, infer_temperature, infer_sample_seed), or None when it
+    sets none of them; inactive unless infer_sample is set."""
+    on, t, seed = (getattr(c, k, None) for k in ('infer_sample', 'infer_temperature', 'infer_sample_seed'))
+    if not on and t is None and seed is None:
+        return None
+    smp = BeamSampling(temperature=1.0 if t is None else t, seed=0 if seed is None else seed, enabled=bool(on))
+    smp.check(c.infer_beam_size, getattr(c, 'infer_length_penalty_weight', 0.0) or 0.0, groups_from_config(c))
+    return smp
+
+
+def sampling_dir_suffix(c):
+    """'_smp_t{temperature:g}_s{seed}' when the configuration sets infer_sample, else ''."""
+    if not getattr(c, 'infer_sample', None):
+        return ''
+    t, seed = getattr(c, 'infer_temperature', None), getattr(c, 'infer_sample_seed', None)
+    return '_smp_t%g_s%d' % (float(1.0 if t is None else t), int(0 if seed is None else seed))
+
+
 def process_inputs(captions, token_type):
     """ModelBase._process_inputs (model_base.py:501-528) on the host.
     -> inputs [B,T] int32, targets [B,T] int32, masks [B,T] fp32, lens [B] int32."""
@@ -998,7 +1082,7 @@ class Decoder:
         return fetch
 
     def beam_search(self, fm, im_embed, beam, max_steps, want_attention=True, use_graph=True, length_penalty_weight=0.0,
-                    constraints=None, groups=None):
+                    constraints=None, groups=None, sampling=None, image_base=0):
         """rnn_decoder_beam_search (ops_rnn.py:49-112).  Returns predicted_ids [T,B,W] (after
         gather_tree), scores [T,B,W] (with length_penalty_weight != 0: the penalised scores the beams were ranked by,
         BeamSearchDecoder's `scores` output), the raw step/parent ids and, unless want_attention=False, the
@@ -1009,19 +1093,28 @@ class Decoder:
         groups: a BeamGroups (diverse beam search); an active one (groups > 1) decodes the same way through
         comic_decoder_beam_diverse, alone or with constraints: slot g * (beam / groups) of predicted_ids and scores is
         group g's best caption, and the result carries `log_probs` [B,W] (BeamGroups.final_log_probs).  None / inactive:
-        today's path.  The result's `groups` holds the number of groups (1 without)."""
+        today's path.  The result's `groups` holds the number of groups (1 without).
+        sampling: a BeamSampling; an active one draws `beam` samples per image through comic_decoder_beam_sampled, alone or
+        with constraints (not with more than one group or a length penalty: ValueError): slot w of predicted_ids is sample
+        w, `scores` the chains' running log p(caption | image) and `log_probs` [B,beam] the final ones; image_base is the
+        index in the run of the batch's first image (the noise of an image does not depend on its batch).  None /
+        inactive: today's path."""
         constrained = constraints is not None and constraints.active
         grouped = groups is not None and groups.active
+        sampled = sampling is not None and sampling.active
         if groups is not None:
             groups.check(beam, self.spec.V)
-        if constrained or grouped:
+        if sampling is not None:
+            sampling.check(beam, length_penalty_weight, groups)
+        if constrained or grouped or sampled:
             if constrained:
                 constraints.check(self.spec, beam, max_steps)
             ens = self.__dict__.get('_self_ensemble')
             if ens is None:
                 ens = self._self_ensemble = EnsembleDecoder([self])
             return ens.beam_search(fm, im_embed, beam, max_steps, want_attention=want_attention, use_graph=use_graph,
-                                   length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups)
+                                   length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
+                                   sampling=sampling, image_base=image_base)
         torch, s = self.torch, self.spec
         B, W = fm.shape[0], beam
         # (a non-zero length penalty is another captured graph: the weight is baked into the step kernel's arguments)
@@ -1126,14 +1219,17 @@ class EnsembleDecoder:
         self.torch, self.lib, self.device = decoders[0].torch, decoders[0].lib, decoders[0].device
         self._ctxs = {}
 
-    def _ctx(self, B, W, max_steps, lpw, feats, cons=None, grp=None):
+    def _ctx(self, B, W, max_steps, lpw, feats, cons=None, grp=None, smp=None):
         """Persistent buffers (+ a hipGraph of the whole loop, captured on the second call with the shape), as
         Decoder._infer_ctx.  cons: active BeamConstraints (they are baked into the captured launches) or None; grp: active
-        BeamGroups (baked in likewise) or None."""
+        BeamGroups (baked in likewise) or None; smp: active BeamSampling or None -- its temperature is baked in and part
+        of the key, its seed words are not: they live in ctx.seed, which beam_search writes in front of every launch."""
         torch, n = self.torch, len(self.decoders)
         key = (B, W, max_steps, float(lpw)) if cons is None else (B, W, max_steps, float(lpw), cons.key())
         if grp is not None:
             key = (B, W, max_steps, float(lpw), cons.key() if cons is not None else None, grp.key())
+        if smp is not None:
+            key = (B, W, max_steps, float(lpw), cons.key() if cons is not None else None, None, smp.ctx_key())
         ctx = self._ctxs.get(key)
         if ctx is None:
             ctx = type('EnsembleCtx', (), {})()
@@ -1160,9 +1256,16 @@ class EnsembleDecoder:
             ctx.wts = (C.c_float * n)(*self.weights)
             ctx.cons = cons.c_struct() if cons is not None else None
             ctx.grp = grp.c_struct() if grp is not None else None
+            ctx.smp = None
+            if smp is not None:
+                ctx.seed = torch.zeros(2, dtype=torch.int64, device=self.device)       # uint64[2]: {seed, image_base}
+                ctx.smp = smp.c_struct(ctx.seed.data_ptr())
             ws_fn = self.lib.comic_decoder_beam_ensemble_workspace if cons is None else \
                 self.lib.comic_decoder_beam_constrained_workspace
-            if grp is not None:
+            if smp is not None:
+                ctx.nbytes = int(self.lib.comic_decoder_beam_sampled_workspace(ctx.descs, n, R, max_steps,
+                                                                               0 if cons is None else 1))
+            elif grp is not None:
                 ctx.nbytes = int(self.lib.comic_decoder_beam_diverse_workspace(ctx.descs, n, R, max_steps,
                                                                                0 if cons is None else 1))
             else:
@@ -1177,17 +1280,22 @@ class EnsembleDecoder:
         return ctx
 
     def beam_search(self, fms, im_embeds, beam, max_steps, want_attention=False, use_graph=True, length_penalty_weight=0.0,
-                    constraints=None, groups=None):
+                    constraints=None, groups=None, sampling=None, image_base=0):
         """fms / im_embeds: one device tensor (every member reads the same features) or a sequence with one per member.
         Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's.  constraints: a
         BeamConstraints; active ones run comic_decoder_beam_constrained, None / inactive ones today's entry point.
         groups: a BeamGroups; an active one runs comic_decoder_beam_diverse (with the constraints, if any), as
-        Decoder.beam_search describes; None / inactive: today's entry points."""
+        Decoder.beam_search describes; None / inactive: today's entry points.
+        sampling, image_base: a BeamSampling; an active one runs comic_decoder_beam_sampled (with the constraints, if any),
+        as Decoder.beam_search describes; None / inactive: today's entry points."""
         torch, n = self.torch, len(self.decoders)
         cons = constraints if constraints is not None and constraints.active else None
         if groups is not None:
             groups.check(beam, self.spec.V)
         grp = groups if groups is not None and groups.active else None
+        if sampling is not None:
+            sampling.check(beam, length_penalty_weight, groups)
+        smp = sampling if sampling is not None and sampling.active else None
         if cons is not None:
             cons.check(self.spec, beam, max_steps)
         if torch.is_tensor(fms):
@@ -1196,12 +1304,22 @@ class EnsembleDecoder:
             im_embeds = [im_embeds] * n
         assert len(fms) == n and len(im_embeds) == n
         B, W = int(fms[0].shape[0]), int(beam)
-        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)), cons, grp)
+        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)), cons, grp, smp)
+        if smp is not None:                 # on the stream, in front of the launch or the replay that reads them
+            ctx.seed.copy_(torch.from_numpy(smp.seed_words(image_base)))
 
         def launch():
             flags = L.decoder_flags_from_env()
             for k in range(n):
                 ctx.descs[k].flags = flags
+            if ctx.smp is not None:
+                L.check(self.lib.comic_decoder_beam_sampled(
+                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps,
+                    C.byref(ctx.cons) if ctx.cons is not None else None, C.byref(ctx.smp), ctx.step_ids.data_ptr(),
+                    ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(), ctx.finished.data_ptr(),
+                    ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes, L.stream_ptr()),
+                    'decoder_beam_sampled')
+                return
             if ctx.grp is not None:
                 L.check(self.lib.comic_decoder_beam_diverse(
                     ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps,
@@ -1235,6 +1353,8 @@ class EnsembleDecoder:
         if grp is not None:
             out['groups'] = grp.groups
             out['log_probs'] = grp.final_log_probs(out['scores'], out['step_ids'], ln, s.end_id, length_penalty_weight)
+        if smp is not None:                 # the state after the last executed step: a finished chain's carries over
+            out['log_probs'] = out['scores'][-1].copy()
         if want_attention:
             out['attn_hist'] = gather_tree_from_array(ctx.hist[:T].cpu().numpy(), par, ln, s.end_id)
         return out

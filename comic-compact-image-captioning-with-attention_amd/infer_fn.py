@@ -91,6 +91,7 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
                        checkpoint_number=ckpt_num)
     coco_json = []
     groups_json = []                # diverse beam search: the group-best captions of every image
+    samples_json = []               # sampling: every sample of every image, with its log-probability
     print('INFO: Graph constructed. Starting inference.')
     start_time = time.time()
     captions = []
@@ -101,13 +102,18 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
         batches = m_infer.infer_pipelined(want_attention=bool(getattr(c, 'save_attention_maps', False)))
     for step in range(num_batches):
         word_ids, attn_maps = next(batches)
-        captions = id_to_caption(word_ids, c)
+        smp = getattr(m_infer, 'sample_output', None)
+        captions = id_to_caption(word_ids, c, skip_unmapped=smp is not None)
         # with beam groups word_ids is group 0's best (the caption beam search of width beam / groups gives, so metrics
         # stay comparable); every group's best goes to caption_groups___N.json
         grp = getattr(m_infer, 'group_output', None)
         if grp is not None:
             G = grp['ids'].shape[1]
             grp_caps = [id_to_caption(grp['ids'][:, g], c) for g in range(G)]
+        # with sampling word_ids is, per image, the sample of highest log-probability; every sample goes to
+        # caption_samples___N.json
+        if smp is not None:
+            smp_caps = [id_to_caption(smp['ids'][:, k], c, skip_unmapped=True) for k in range(smp['ids'].shape[1])]
         for i, f in enumerate(filenames[step * batch_size:(step + 1) * batch_size]):
             image_id = f.replace('.jpg', '')
             if '@' in image_id:
@@ -126,6 +132,10 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
                 groups_json.append(dict(image_id=image_id, captions=[
                     dict(group=g, caption=str(grp_caps[g][i]), score=float(grp['scores'][i, g]),
                          log_prob=float(grp['log_probs'][i, g])) for g in range(G)]))
+            if smp is not None:
+                samples_json.append(dict(image_id=image_id, captions=[
+                    dict(sample=k, caption=str(smp_caps[k][i]), log_prob=float(smp['log_probs'][i, k]))
+                    for k in range(len(smp_caps))]))
     print('\nExample captions:\n{}\n'.format('\n'.join(captions[:3])))
     t = time.time() - start_time
     assert len(filenames) == len(list(set(filenames)))
@@ -138,6 +148,9 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
     if groups_json:
         with open(pjoin(c.infer_save_path, 'caption_groups___{}.json'.format(ckpt_num)), 'w') as f:
             json.dump(groups_json, f)
+    if samples_json:
+        with open(pjoin(c.infer_save_path, 'caption_samples___{}.json'.format(ckpt_num)), 'w') as f:
+            json.dump(samples_json, f)
     speed_file = pjoin(c.infer_save_path, 'infer_speed.txt')
     if not os.path.isfile(speed_file):
         out = ['Using GPU #: {}'.format(c.gpu), 'Inference batch size: {}'.format(c.batch_size_infer),

@@ -351,22 +351,42 @@ class ModelBase(object):
 
     # ---- decode (model_base.py:692-757, :272-314) ----------------------------------------
     def _decode(self, images, beam_size, max_length, top_beam=True, want_attention=True, length_penalty_weight=0.0,
-                constraints=None, groups=None):
+                constraints=None, groups=None, sampling=None, image_base=0):
         im_embed, fm = self._encode(images)
         return self._decode_features(im_embed, fm, beam_size, max_length, top_beam, want_attention, length_penalty_weight,
-                                     constraints, groups)
+                                     constraints, groups, sampling, image_base)
 
     def _decode_features(self, im_embed, fm, beam_size, max_length, top_beam=True, want_attention=True,
-                         length_penalty_weight=0.0, constraints=None, groups=None):
+                         length_penalty_weight=0.0, constraints=None, groups=None, sampling=None, image_base=0):
         """constraints: decoder.BeamConstraints in TOKENS (decoder.constraints_from_config translates a configuration's
         words); beam search only.  groups: decoder.BeamGroups; an active one decodes by diverse beam search: the top beam is
         group 0's best (the caption of beam search of width beam / groups), and self.group_output holds the group-best
-        captions of the batch (group_best), None otherwise."""
+        captions of the batch (group_best), None otherwise.  sampling: decoder.BeamSampling; an active one draws beam_size
+        samples per image (image_base: the number of images decoded before this batch in the run): the top beam is, per
+        image, the sample of highest log-probability (lowest slot on ties), and self.sample_output holds every sample
+        (sample_set), None otherwise."""
         c = self._config
         iters = self.decoder.max_iterations(max_length, len(c.wtoi))
         constrained = constraints is not None and constraints.active
         grouped = groups is not None and groups.active
+        sampled = sampling is not None and sampling.active
         self.group_output = None
+        self.sample_output = None
+        if sampled:
+            sampling.check(beam_size, length_penalty_weight, groups)
+            r = self.decoder.beam_search(fm, im_embed, beam_size, iters, want_attention=want_attention,
+                                         constraints=constraints, sampling=sampling, image_base=image_base)
+            self.sample_output = sample_set(r)
+            pred = r['predicted_ids']                                  # (T, B, n)
+            T, B = pred.shape[:2]
+            best = np.argmax(r['log_probs'], axis=1)                   # (the lowest slot on ties)
+            attn = None
+            if want_attention:
+                hist = r['attn_hist'].reshape(T, B, beam_size, self.spec.H, self.spec.M)
+                attn = hist[:, np.arange(B), best].transpose(1, 2, 0, 3)      # (B, H, T, M) of the chosen sample
+            if top_beam:
+                return pred[:, np.arange(B), best].T.copy(), attn
+            return pred.transpose(2, 1, 0).copy(), attn
         if constrained and beam_size <= 1:
             raise ValueError('beam constraints need beam search: infer_beam_size must be at least 2')
         if grouped and beam_size <= 1:
@@ -407,6 +427,13 @@ def group_best(r):
     Wg = W // int(r['groups'])
     return dict(ids=r['predicted_ids'][:, :, ::Wg].transpose(1, 2, 0).copy(), scores=r['scores'][-1][:, ::Wg].copy(),
                 log_probs=r['log_probs'][:, ::Wg].copy())
+
+
+def sample_set(r):
+    """Every sample of a sampled Decoder.beam_search result: ids (B, n, T), their log-probabilities (B, n) under the model
+    (unperturbed, untempered) and their lengths (B, n), in slot order."""
+    return dict(ids=r['predicted_ids'].transpose(1, 2, 0).copy(), log_probs=np.asarray(r['log_probs']).copy(),
+                lengths=np.asarray(r['lengths']).copy())
 
 
 class CaptionModel(ModelBase):
@@ -535,11 +562,22 @@ class CaptionModel(ModelBase):
         res = self.decoder.train_step(fm, im_embed, np.asarray(captions), training=False, use_graph=True)
         return res['loss']
 
-    def infer(self, batch=None, constraints=None, groups=None):
+    def _image_base(self, sampling, B):
+        """The number of images decoded before this batch of B in the run (the noise of a sampled decode is keyed by it)."""
+        if sampling is None or not sampling.active:
+            return 0
+        base = self.__dict__.get('_images_sampled', 0)
+        self._images_sampled = base + int(B)
+        return base
+
+    def infer(self, batch=None, constraints=None, groups=None, sampling=None):
         """== sess.run(m_infer.infer_output) -> [dec_preds (B,T), attention_maps (B,H,T,M)].
         constraints: decoder.BeamConstraints; None reads the configuration (infer_min_length, infer_no_repeat_ngram,
         infer_suppress_words).  groups: decoder.BeamGroups; None reads the configuration (infer_beam_groups,
         infer_diversity).  With active groups dec_preds is group 0's best and self.group_output holds every group's.
+        sampling: decoder.BeamSampling; None reads the configuration (infer_sample, infer_temperature, infer_sample_seed).
+        With active sampling infer_beam_size is the number of samples per image, dec_preds is per image the sample of
+        highest log-probability and self.sample_output = dict(ids (B,n,T), log_probs (B,n), lengths (B,n)).
         Batches drawn from the input pipeline are decoded with the encoder forward of the NEXT group of batches already
         running on a second stream (the decode steps are small launches that leave most of the GPU idle;
         config.pipeline_encoder, default on; config.pipeline_encoder_group batches per forward, 0 = auto).  Same
@@ -557,13 +595,16 @@ class CaptionModel(ModelBase):
             constraints = cdec.constraints_from_config(c)
         if groups is None:
             groups = cdec.groups_from_config(c)
+        if sampling is None:
+            sampling = cdec.sampling_from_config(c)
         ids, attn = self._decode_features(im_embed, fm, c.infer_beam_size, c.infer_max_length, top_beam=True,
                                           length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
-                                          constraints=constraints, groups=groups)
+                                          constraints=constraints, groups=groups, sampling=sampling,
+                                          image_base=self._image_base(sampling, fm.shape[0]))
         self.infer_output = [ids, attn]
         return self.infer_output
 
-    def infer_pipelined(self, want_attention=True, constraints=None, groups=None):
+    def infer_pipelined(self, want_attention=True, constraints=None, groups=None, sampling=None):
         """Generator over the batches of the input pipeline -> [dec_preds (B,T), attention_maps or None] in input order, with
         the decode loops of THREE batches in flight (COMIC_INFER_IN_FLIGHT; one stream and one buffer set of the decoder each:
         Decoder.beam_search_ids(slot=)).
@@ -572,7 +613,7 @@ class CaptionModel(ModelBase):
         baseline (tools/beam_time.py TWO=1), the same ids; three in flight +6 % over two (24.5k against 23.1k captions/s on one
         box; four and five lose: 23.9k, 19.3k -- each loop streams the 52 MB vocabulary projection per step).  Only the captions-only beam search runs this way (no attention
         maps, no length penalty, no beam constraints, no beam groups: what `infer.py` writes unless --save_attention_maps);
-        everything else yields infer().  constraints, groups: as infer()."""
+        everything else yields infer().  constraints, groups, sampling: as infer()."""
         c, torch = self._config, self.torch
         lp = getattr(c, 'infer_length_penalty_weight', 0.0)
         if constraints is None:
@@ -581,6 +622,9 @@ class CaptionModel(ModelBase):
         if groups is None:
             groups = cdec.groups_from_config(c)
         constrained = constrained or (groups is not None and groups.active)     # (either keeps to the one-loop path)
+        if sampling is None:
+            sampling = cdec.sampling_from_config(c)
+        constrained = constrained or (sampling is not None and sampling.active)  # (so does sampling)
         NL = max(1, min(5, int(os.environ.get('COMIC_INFER_IN_FLIGHT', '3'))))      # decode loops in flight (3: measured best of 1-5)
         if want_attention or lp or constrained or c.infer_beam_size <= 1 or not str(self.device).startswith('cuda'):
             NL = 1
@@ -591,7 +635,8 @@ class CaptionModel(ModelBase):
                     return
                 ids, attn = self._decode_features(feats[0], feats[1], c.infer_beam_size, c.infer_max_length, top_beam=True,
                                                   want_attention=want_attention, length_penalty_weight=lp,
-                                                  constraints=constraints, groups=groups)
+                                                  constraints=constraints, groups=groups, sampling=sampling,
+                                                  image_base=self._image_base(sampling, feats[1].shape[0]))
                 yield [ids, attn]
         iters = self.decoder.max_iterations(c.infer_max_length, len(c.wtoi))
         lanes = [streams.lane(torch, self.device, 'infer%d' % k) for k in range(NL)]
@@ -846,14 +891,17 @@ class CaptionEnsemble(object):
             return [(m._embed(net), fm) for m in self.models]
         return [m._encode(images) for m in self.models]
 
-    def infer(self, batch=None, constraints=None, groups=None):
+    def infer(self, batch=None, constraints=None, groups=None, sampling=None):
         """-> [dec_preds (B,T), attention_maps (B,H,T,M) of member 0], as CaptionModel.infer; without `batch` the images
-        come from member 0's input pipeline.  constraints, groups: as CaptionModel.infer."""
+        come from member 0's input pipeline.  constraints, groups, sampling: as CaptionModel.infer."""
         c = self._config
         if constraints is None:
             constraints = cdec.constraints_from_config(c)
         if groups is None:
             groups = cdec.groups_from_config(c)
+        if sampling is None:
+            sampling = cdec.sampling_from_config(c)
+        sampled = sampling is not None and sampling.active
         if batch is None:
             batch = next(self.models[0].batch_ops)
         images = batch[0] if isinstance(batch, (tuple, list)) else batch
@@ -861,13 +909,20 @@ class CaptionEnsemble(object):
         spec = self.decoder.spec
         iters = self.models[0].decoder.max_iterations(c.infer_max_length, len(c.wtoi))
         W = c.infer_beam_size
-        assert W > 1, 'the ensemble decodes by beam search: infer_beam_size must be at least 2'
+        assert W > 1 or sampled, 'the ensemble decodes by beam search: infer_beam_size must be at least 2'
+        base = 0
+        if sampled:
+            base = self.__dict__.get('_images_sampled', 0)
+            self._images_sampled = base + int(feats[0][1].shape[0])
         r = self.decoder.beam_search([f[1] for f in feats], [f[0] for f in feats], W, iters, want_attention=True,
                                      length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
-                                     constraints=constraints, groups=groups)
+                                     constraints=constraints, groups=groups, sampling=sampling, image_base=base)
         pred = r['predicted_ids']                                  # (T, B, W)
-        T = pred.shape[0]
+        T, B = pred.shape[:2]
         self.group_output = group_best(r) if r['groups'] > 1 else None
-        hist = r['attn_hist'].reshape(T, -1, W, spec.H, spec.M)[:, :, 0]
-        self.infer_output = [pred[:, :, 0].T.copy(), hist.transpose(1, 2, 0, 3)]
+        self.sample_output = sample_set(r) if sampled else None
+        # (sampling: per image the sample of highest log-probability, the lowest slot on ties; else the top beam)
+        best = np.argmax(r['log_probs'], axis=1) if sampled else np.zeros(B, np.int64)
+        hist = r['attn_hist'].reshape(T, B, W, spec.H, spec.M)[:, np.arange(B), best]
+        self.infer_output = [pred[:, np.arange(B), best].T.copy(), hist.transpose(1, 2, 0, 3)]
         return self.infer_output

@@ -48,10 +48,12 @@ def _word_array(config):
     return cache[2]
 
 
-def id_to_caption(ids, config):
+def id_to_caption(ids, config, skip_unmapped=False):
     """ids [N,T] -> list of N strings.  Radix: keep ids in [0, base), drop one trailing id
     when the count is not a multiple of the word length, decode base-N groups, skip word ids
-    >= vocab; word/char: drop negatives and <EOS>."""
+    >= vocab; word/char: drop negatives and <EOS>.  skip_unmapped (radix): the one word id below len(itow) that the table
+    lacks (len - 1: '-1' is <PAD>) is skipped like the ids >= vocab instead of raising -- sampled digits can spell it,
+    beam search practically never does."""
     ids = np.asarray(ids)
     captions = []
     if config.token_type == 'radix':
@@ -68,6 +70,8 @@ def id_to_caption(ids, config):
             except AttributeError:
                 pass
         words_of = cache[1]
+        if skip_unmapped and vocab_size > 0 and words_of[vocab_size - 1] is None:
+            vocab_size -= 1                                   # (after word_len and the table were formed from the full size)
         def lookup(wids):
             words = [words_of[w] for w in wids]
             if None in words:                             # the dict lookup of the reference raises here

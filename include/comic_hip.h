@@ -546,6 +546,47 @@ int comic_beam_step_diverse(const float* logits, const float* weights, int n_mod
                             int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int V,
                             int end_id, float length_penalty_weight, const uint32_t* bits, int words,
                             const comic_beam_groups* groups, void* workspace, int64_t workspace_bytes, void* stream);
+/* Sampling inside the beam step (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112): the W slots of an entry
+ * (1 <= W <= 64) are W independent chains, each drawn from the step distribution at a temperature by the Gumbel-max rule
+ * with noise from a counter-based generator -- nothing is stored.  All W slots start live with log-probability 0; a
+ * slot's parent is always the slot itself, so gather_tree, the state gathers and the ban / attention histories work
+ * unchanged.
+ *   Generator: seed_dev (DEVICE memory, read by the kernels at run time: a captured graph replays with new values) =
+ *   uint64[2] = {seed, image_base}.  For entry b, slot w, step t, candidate v, with splitmix64 of csrc/splitmix.h:
+ *     k1 = splitmix64(splitmix64(seed) ^ (image_base + b))
+ *     k2 = splitmix64(k1 ^ ((uint64(w) << 32) | uint64(t)))
+ *     r  = splitmix64(k2 ^ uint64(v));  k = r >> 41 (23 bits);  u = (2k + 1) * 2^-24 (exact in fp32, never 0, never 1)
+ *     g  = -logf(-logf(u))   with the accurate logf; g in [-2.82, 16.64]
+ *   The noise depends on the image's index in the run (image_base + b), not on the batch it happens to be in.
+ *   Rank: lp[v] is the step log-probability of the plain step (the ensemble mean; -inf for a banned candidate of a live
+ *   slot).  A live slot ranks rank[v] = lp[v] * inv_temp + g(b, w, t, v), inv_temp = 1.0f / temperature formed once on
+ *   the host in fp32 (-inf stays -inf), and takes the best rank among its own V candidates, lowest v on ties (all -inf /
+ *   NaN: the lowest flat index of its row).  A finished slot sees no noise: _mask_probs makes it emit <EOS>, its length
+ *   freezes, its log-probability carries over.
+ *   Outputs: word_ids = v, parent_ids = w, the state log_probs = old state + lp[v], scores = the same value; finished and
+ *   lengths as ever.  The state is the model's UNPERTURBED, UNTEMPERED log-probability log p(caption so far | image):
+ *   with temperature != 1 it is not the log-probability under the tempered distribution.  The perturbed rank is never
+ *   returned.
+ * Limits: temperature finite and > 0 with a finite fp32 reciprocal; no length penalty, no beam groups. */
+typedef struct comic_beam_sampling {
+  float temperature;
+  const uint64_t* seed_dev;
+} comic_beam_sampling;
+/* The generator above as a raw operator (common/ops_rnn.py:49-112 has no counterpart; test aid): k_out / g_out
+ * [B*W][V] (device) receive k and g of step t for every (entry, slot, candidate).  Either output may be NULL. */
+int comic_beam_sample_noise(const uint64_t* seed_dev, int B, int W, int t, int V, int32_t* k_out, float* g_out,
+                            void* stream);
+/* comic_beam_step_ensemble / comic_beam_step_constrained (common/ops_rnn.py:49-112) under sampling, as a raw operator:
+ * step t of the rule at comic_beam_sampling.  bits may be NULL: no bans, and `words` is ignored; else bits [B*W][words],
+ * words == ceil(V/32).  One workgroup per entry loops over the slots; the split form (same eligibility rule, on the
+ * entry-wide W * V, when `workspace` holds comic_beam_step_sampled_workspace bytes -- more than the ensemble step's: every
+ * slot's candidates carry their unperturbed totals) is the statistics, ONE chunk launch that forms every slot's best per
+ * chunk and ONE merge: 3 launches whatever W is.  comic_beam_step_ensemble_path() reports the form. */
+int64_t comic_beam_step_sampled_workspace(int n_models, int B, int W, int V);
+int comic_beam_step_sampled(const float* logits, const float* weights, int n_models, float* log_probs, int32_t* finished,
+                            int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int V,
+                            int end_id, const uint32_t* bits, int words, const comic_beam_sampling* sampling, int t,
+                            void* workspace, int64_t workspace_bytes, void* stream);
 /* out[r,:] = in[(r/W)*W + parent[r], :]   (state re-ordering by parent beam) */
 int comic_gather_rows(const float* in, const int32_t* parent, float* out, int rows, int W, int cols,
                       void* stream);
@@ -795,6 +836,23 @@ int comic_decoder_beam_diverse(const comic_decoder_desc* descs, const comic_deco
                                const float* const* fms, const float* const* im_embeds, const float* weights, int n_models,
                                int B, int W, int max_steps, const comic_beam_constraints* constraints,
                                const comic_beam_groups* groups, int32_t* step_ids, int32_t* parent_ids, float* scores,
+                               int64_t* lengths, int32_t* finished, float* const* attn_hists, int32_t* steps_executed,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Sampled decode (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112): comic_decoder_beam_ensemble /
+ * comic_decoder_beam_constrained -- the same loop; a single decoder is n_models == 1 with weight 1 -- whose W slots all
+ * start live with log-probability 0 and whose step t ranks under `sampling` (comic_beam_step_sampled, the rule at
+ * comic_beam_sampling): W samples per image, `scores` [max_steps][B][W] the chains' running log p(caption | image),
+ * parent_ids the slot itself.  constraints may be NULL; given, their rules hold unchanged.  sampling and its seed_dev
+ * must not be NULL; descs[0].length_penalty_weight must be 0.  Everything else as comic_decoder_beam_ensemble.
+ * workspace: comic_decoder_beam_sampled_workspace(descs, n_models, B*W, max_steps, constrained) bytes, constrained != 0
+ * when constraints are given. */
+int64_t comic_decoder_beam_sampled_workspace(const comic_decoder_desc* descs, int n_models, int rows, int max_steps,
+                                             int constrained);
+int comic_decoder_beam_sampled(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                               const float* const* fms, const float* const* im_embeds, const float* weights, int n_models,
+                               int B, int W, int max_steps, const comic_beam_constraints* constraints,
+                               const comic_beam_sampling* sampling, int32_t* step_ids, int32_t* parent_ids, float* scores,
                                int64_t* lengths, int32_t* finished, float* const* attn_hists, int32_t* steps_executed,
                                void* workspace, int64_t workspace_bytes, void* stream);
 

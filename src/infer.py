@@ -57,6 +57,11 @@ def create_parser():
            'caption_groups___N.json with the best caption of every group.')
     a('--infer_diversity', type=float, default=None,
       help='Diverse beam search: the Hamming diversity penalty a later group pays per earlier pick of the same token.')
+    a('--infer_sample', action='store_true', default=None,
+      help='Sample --infer_beam_size captions per image instead of beam search; captions___N.json keeps, per image, the '
+           'sample of highest log-probability, caption_samples___N.json every sample with its log-probability.')
+    a('--infer_temperature', type=float, default=None, help='Sampling: the temperature of the word distribution (default 1).')
+    a('--infer_sample_seed', type=int, default=None, help='Sampling: the seed of the noise generator (default 0).')
     return p
 
 
@@ -85,10 +90,12 @@ def main(argv=None):
     save_name = 'beam_{}_lpen_{}'.format(c.infer_beam_size, c.infer_length_penalty_weight)
     save_name = {'test': 'infer_test_', 'valid': 'infer_valid_', 'coco_test': 'infer_cocoTest_',
                  'coco_valid': 'infer_cocoValid_'}[c.infer_set] + save_name
-    # constrained and grouped captions get a directory of their own: they never overwrite the plain ones
-    from comic_amd.decoder import constraints_dir_suffix, groups_dir_suffix, groups_from_config
+    # constrained, grouped and sampled captions get a directory of their own: they never overwrite the plain ones
+    from comic_amd.decoder import (constraints_dir_suffix, groups_dir_suffix, groups_from_config, sampling_dir_suffix,
+                                   sampling_from_config)
     groups_from_config(c)           # (refuses groups that do not divide infer_beam_size before anything is loaded)
-    save_name += constraints_dir_suffix(c) + groups_dir_suffix(c)
+    sampling_from_config(c)         # (refuses sampling with more than one group or a length penalty likewise)
+    save_name += constraints_dir_suffix(c) + groups_dir_suffix(c) + sampling_dir_suffix(c)
     c.infer_save_path = pjoin(c.infer_checkpoints_dir, save_name)
     if os.path.exists(c.infer_save_path):
         print('\nINFO: `eval_log_path` already exists.')
