@@ -213,6 +213,29 @@ _SIGS = {
     'comic_decoder_beam_sampled_workspace': (c_int64, [P, c_int, c_int, c_int, c_int]),
     'comic_decoder_beam_sampled': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, c_int64,
                                            P]),
+    # op-level entries of the executor-only kernel forms (tests only; the argument lists are csrc/exec_entries.h's)
+    'comic_attn_splits': (c_int, [c_int, c_int]),
+    'comic_attn_bwd_scratch': (C.c_long, [c_int, c_int, c_int, c_int]),
+    'comic_cell_ln_stride': (c_int, [c_int]),
+    'comic_gemm_f32_partial': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int64, P, P]),
+    'comic_op_attn_fwd': (c_int, [P] * 9 + [c_float, P, P, P, P, c_int, P, P, P, c_int, P, c_int, c_float, c_int, P, P,
+                                  c_int, P]),
+    'comic_op_attn_bwd': (c_int, [P] * 10 + [c_float, P, P, P, P, P, P, P, c_int, c_int, P, P, P]),
+    'comic_op_xent': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    'comic_op_xent_maploss': (c_int, [P, P, P, P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int,
+                                      c_int, c_float, P]),
+    'comic_op_lstm_gates_fwd': (c_int, [P, P, P, P, P, P, P, c_float, P, c_int, P, P, c_int, c_int, P, c_int, c_int, P, P]),
+    'comic_op_lstm_gates_bwd': (c_int, [P, P, P, P, P, c_int, P, c_float, P, c_int, P, P, P, c_int, c_int, P]),
+    'comic_op_colsum_ws': (c_int, [P, P, c_int, c_int, c_float, P, P]),
+    'comic_op_ln_lstm_fwd': (c_int, [P, c_int, P, P, P, P, P, P, P, P, P, c_float, P, c_int, P, P, c_int, c_int, P, c_int,
+                                     P]),
+    'comic_op_ln_lstm_bwd': (c_int, [P, P, P, P, P, P, P, P, c_int, P, c_float, P, c_int, P, P, P, P, c_int, c_int, P]),
+    'comic_op_ln_lstm_scatter': (c_int, [P, P, c_int, c_float, P]),
+    'comic_op_gru_gates_fwd': (c_int, [P, c_int, P, P, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P]),
+    'comic_op_gru_out_fwd': (c_int, [P, c_int, P, P, c_int, P, P, c_int, P, P, c_float, P, c_int, P, P, c_int, c_int, c_int,
+                                     P]),
+    'comic_op_gru_bwd1': (c_int, [P, P, c_int, P, c_float, P, c_int, P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, P]),
+    'comic_op_gru_bwd2': (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
     'comic_scorer_create': (c_void_p, [c_char_p, P, c_int64, c_double]),
     'comic_scorer_destroy': (None, [c_void_p]),
     'comic_scorer_score': (c_int, [c_void_p, P, c_int, P, P, P, P, c_int]),

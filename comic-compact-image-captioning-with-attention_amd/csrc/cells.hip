@@ -12,6 +12,7 @@
 //            tanh([x, r*h] W_c + b_c), new_h = u*h + (1-u)*cand; the state is h alone.
 // Oracle: oracle/decoder_ref.py ln_lstm_cell / gru_cell / _cell_backward.
 #include "decoder_math.h"
+#include "exec_entries.h"
 
 namespace {
 

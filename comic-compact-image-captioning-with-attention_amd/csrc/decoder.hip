@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "decoder_math.h"
+#include "exec_entries.h"
 #include "splitmix.h"
 
 namespace {
@@ -734,8 +735,9 @@ __global__ __launch_bounds__(kAttnThreads) void attn_bwd_kernel(AttnArgs a) {
   // contributions, added atomically into zero-filled buffers: with exactly two addends the result does not depend
   // on their order.
   // gridDim.y > 2 (large memories): phase A ran as attn_bwd_scores_kernel (a.ws_s / a.ws_d hold s and d alpha_d of ALL
-  // rows); the S contributions to d q and to the parameter-gradient row are added atomically (for S > 2 the sum of
-  // the partials depends on their arrival order in the last bits: the step is no longer bit-reproducible there)
+  // rows); the S contributions to d q and to the parameter-gradient row go to partial rows (a.ws_parts) that
+  // attn_bwd_reduce_kernel adds in a fixed order: no float atomics, the step stays bit-reproducible
+  // (tests/test_gpu_exec_ops.py launches both split forms twice and compares the bits)
   const bool split = gridDim.y >= 2;
   const int S_ = (int)gridDim.y, per_ = (M + S_ - 1) / S_;
   const int m0 = split ? (int)blockIdx.y * per_ : 0;
@@ -1413,7 +1415,6 @@ int comic_lstm_gates_bwd_ex(const float* gates_act, const float* c_prev, const f
   return 0;
 }
 
-int comic_attn_splits(int B, int M);
 // executor-internal forms (fused state plumbing); the public ops pass no extras
 int comic_attn_fwd_ex(const comic_attn_desc* d, const float* keys, const float* values, const float* q,
                       const float* ln_g, const float* ln_b, const float* v, const float* tau, const float* mask_alpha,
@@ -1433,7 +1434,10 @@ int comic_attn_fwd_ex(const comic_attn_desc* d, const float* keys, const float* 
   a.mem_div = mem_div;
   a.stop = g_comic_stop.p; a.stop_t = g_comic_stop.t;
   const size_t lds = (size_t)d->H * d->M * sizeof(float);
-  const int S = scores_ws ? comic_attn_splits(d->B, d->M) : 1;
+  int S = scores_ws ? comic_attn_splits(d->B, d->M) : 1;
+  // attn_ctx_kernel gives a channel of the workgroup's share to one thread: a share wider than the workgroup (Cv = 4096
+  // at S = 2) would leave context channels unwritten -- the one-workgroup form loops over the channels instead
+  if (S > 1 && cdiv(d->Cv, S) > kAttnThreads) S = 1;
   if (S > 1) {        // large memory: S workgroups per batch row, scores and probability / context as two launches
     a.ws_s = scores_ws;
     int rc = attn_dispatch(d->D, [&](auto epl) {

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "exec_entries.h"
 #include "gemm_x3_dev.h"
 
 namespace {
@@ -454,7 +455,8 @@ void launch(const GemmArgs& a, int ta, int tb, hipStream_t st) {
 // Skinny product left as split-K partials: ws receives [S][M][N] (ld = N) raw partial sums and
 // *S_out their count; the consumer kernel adds them up (saves a reduce launch per GEMM).
 int comic_gemm_f32_partial(const float* A, const float* B, int M, int N, int K, int lda, int ldb, int trans_b,
-                           void* ws, int64_t ws_bytes, int* S_out, hipStream_t st) {
+                           void* ws, int64_t ws_bytes, int* S_out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
   COMIC_REQUIRE(A && B && ws && S_out, "gemm_partial: null pointer");
   COMIC_REQUIRE(M > 0 && N > 0 && K > 0 && lda >= K && ldb >= (trans_b ? K : N), "gemm_partial: bad shape");
   const int KB = (K + 15) / 16, NB = cdiv(N, 64), MB = cdiv(M, 64);

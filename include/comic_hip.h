@@ -857,6 +857,83 @@ int comic_decoder_beam_sampled(const comic_decoder_desc* descs, const comic_deco
                                void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Op-level entries of the executor-only kernel forms                        */
+/* ------------------------------------------------------------------------- */
+/* The public ops above reach the decoder kernels with every executor-only argument null, 0 or 1.  The executors
+ * (training, greedy / beam decode, sampling, scoring) launch the forms below; each entry forwards its arguments to the
+ * internal entry the executors call and does nothing else, so one form can be compared with a reference on its own
+ * operands.  No product code calls them; the arguments are those of the kernels (csrc/decoder.hip, csrc/cells.hip,
+ * csrc/gemm.hip), in short:
+ *   comic_attn_splits(B, M)      workgroups per batch row of the split attention forms (1: one-workgroup form);
+ *   comic_attn_bwd_scratch       floats behind ws_d for the split backward (d alpha_d [B][H][M] + the partial rows);
+ *   comic_op_attn_fwd            lens/t/att_prev -> att_next = finished ? att_prev : ctx; xh_next[b*xh_ld + c] =
+ *                                drop(att_next) under mask_next / keep_in; q_parts > 1: q is [q_parts][B][D] split-K
+ *                                partials, summed in slice order (also to q_out); scores_ws ([B][H][M] floats) enables
+ *                                the split form when comic_attn_splits > 1; mem_div = W > 1: keys / values are held once
+ *                                per B / W entries;
+ *   comic_op_attn_bwd            pgrad_overwrite 0 adds this step's parameter-gradient row, 1 stores it, 2 is the split
+ *                                form (dq and the pgrad rows zero-filled by the caller; softmax only): two workgroups
+ *                                per row, or with ws_s ([B][H][M]) and ws_d (comic_attn_bwd_scratch floats) and
+ *                                comic_attn_splits > 2 the partial-rows form with a fixed-order reduce;
+ *   comic_op_xent / _maploss     t_rows <= t_stride time steps; d logits rows of ld_dl >= V floats (padding zeroed); the
+ *                                map loss mean((1 - sum_h hist)^2) * scale with its gradient dmap (may be NULL) in the
+ *                                same launch; partial: ceil(t_rows*B*M / 256) floats; *ticket zero before and after;
+ *   comic_op_lstm_gates_*        g is [S][B][4D] split-K partials + bias; dy_part [S][B][D]; xh_next row stride xh_ld;
+ *   comic_op_colsum_ws           two-stage column sum from 256 rows on (ws: 64*cols floats; NULL: comic_colsum);
+ *   comic_gemm_f32_partial       ws receives [*S_out][M][N] raw split-K partial products of A[M,K] * op(B);
+ *   comic_cell_ln_stride(D)      floats between the ten LayerNorm vectors of comic_decoder_params::cell_ln;
+ *   comic_op_ln_lstm_* / _gru_*  the element-wise / row-wise halves of an LN_LSTM / GRU step (csrc/cells.hip). */
+int comic_attn_splits(int B, int M);
+long comic_attn_bwd_scratch(int B, int H, int M, int D);
+int comic_cell_ln_stride(int D);
+int comic_gemm_f32_partial(const float* A, const float* B, int M, int N, int K, int lda, int ldb, int trans_b, void* ws,
+                           int64_t ws_bytes, int* S_out, void* stream);
+int comic_op_attn_fwd(const comic_attn_desc* d, const float* keys, const float* values, const float* q, const float* ln_g,
+                      const float* ln_b, const float* v, const float* tau, const float* mask_alpha, float keep_alpha,
+                      float* alpha, float* alpha_d, float* ctx, const int32_t* lens, int t, const float* att_prev,
+                      float* att_next, float* xh_next, int xh_ld, const float* mask_next, int mask_ld, float keep_in,
+                      int q_parts, float* q_out, float* scores_ws, int mem_div, void* stream);
+int comic_op_attn_bwd(const comic_attn_desc* d, const float* keys, const float* values, const float* q, const float* ln_g,
+                      const float* ln_b, const float* v, const float* tau, const float* alpha, const float* mask_alpha,
+                      float keep_alpha, const float* dctx, const float* dmap, float* dq, float* dkeys, float* dvalues,
+                      float* pgrad, const int32_t* lens, int t, int pgrad_overwrite, float* ws_s, float* ws_d,
+                      void* stream);
+int comic_op_xent(float* logits, const int32_t* targets_bt, const float* coef_bt, const float* wmask_bt,
+                  const int32_t* lens, float* loss_rows, float* dlogits, int32_t* ids_tb, int t_rows, int t_stride, int B,
+                  int V, void* stream);
+int comic_op_xent_maploss(float* logits, const int32_t* targets_bt, const float* coef_bt, const float* wmask_bt,
+                          const int32_t* lens, float* loss_rows, float* dlogits, int ld_dl, int32_t* ids_tb, int t_rows,
+                          int t_stride, int B, int V, const float* hist, float* dmap, float* partial, float* map_loss,
+                          uint32_t* ticket, int H, int M, float scale, void* stream);
+int comic_op_lstm_gates_fwd(const float* g, const float* c_prev, const float* h_prev, float* gates_act, float* c_new,
+                            float* y, const float* mask_out, float keep_out, const int32_t* lens, int t, float* c_state,
+                            float* h_state, int B, int D, float* xh_next, int xh_ld, int S, const float* bias,
+                            void* stream);
+int comic_op_lstm_gates_bwd(const float* gates_act, const float* c_prev, const float* c_new, const float* dy,
+                            const float* dy_part, int S, const float* mask_out, float keep_out, const int32_t* lens, int t,
+                            float* dc_state, float* dh_state, float* dg, int B, int D, void* stream);
+int comic_op_colsum_ws(const float* in, float* out, int rows, int cols, float beta, float* ws, void* stream);
+int comic_op_ln_lstm_fwd(const float* g, int S, const float* ln, const float* c_prev, const float* h_prev,
+                         float* gates_act, float* xhat, float* rstd, float* c_new, float* y, const float* mask_out,
+                         float keep_out, const int32_t* lens, int t, float* c_state, float* h_state, int B, int D,
+                         float* xh_next, int xh_ld, void* stream);
+int comic_op_ln_lstm_bwd(const float* gates_act, const float* xhat, const float* rstd, const float* ln,
+                         const float* c_prev, const float* c_new, const float* dy, const float* dy_part, int S,
+                         const float* mask_out, float keep_out, const int32_t* lens, int t, float* dc, float* dh, float* dg,
+                         float* pgrad, int B, int D, void* stream);
+int comic_op_ln_lstm_scatter(const float* sums, float* cell_ln_grad, int D, float beta, void* stream);
+int comic_op_gru_gates_fwd(const float* g1, int S, const float* bias, const float* h_prev, const float* xh, int xh_ld,
+                           float* ru, int ld_ru, float* xh2, int xh2_ld, int B, int D, int EA, void* stream);
+int comic_op_gru_out_fwd(const float* g2, int S, const float* bias, const float* ru, int ld_ru, const float* h_prev,
+                         float* cand, int ld_cand, float* y, const float* mask_out, float keep_out, const int32_t* lens,
+                         int t, float* h_state, float* xh_next, int xh_ld, int B, int D, void* stream);
+int comic_op_gru_bwd1(const float* dy, const float* dy_part, int S, const float* mask_out, float keep_out,
+                      const int32_t* lens, int t, float* dh_state, const float* ru, int ld_ru, const float* cand,
+                      int ld_cand, const float* h_prev, float* dpre, int ld_dpre, int B, int D, void* stream);
+int comic_op_gru_bwd2(float* dxh2, int ld, const float* ru, int ld_ru, const float* h_prev, float* dpre, int ld_dpre, int B,
+                      int D, int EA, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* SCST reward scorer (host, multi-threaded)  common/scst/scorers.py:43-171      */
 /* ------------------------------------------------------------------------- */
 typedef struct comic_scorer comic_scorer;

@@ -1,6 +1,9 @@
 """Op-level parity: every HIP kernel behind the C-ABI vs the CPU oracle on the same seeded
 inputs.  Tolerances: fp32 1e-3 relative (max-norm), bf16 storage 2e-2 vs a bf16-emulating
-oracle (inputs/weights rounded to bf16, fp32 accumulate), indices bit-exact."""
+oracle (inputs/weights rounded to bf16, fp32 accumulate), indices bit-exact.
+The decoder ops here run with every executor-only argument null, 0 or 1; the forms the executors launch (split
+attention, fused epilogue, shared memories, split backward, fused losses, LN_LSTM / GRU cells, split-K partials) are in
+tests/test_gpu_exec_ops.py."""
 import ctypes as C
 import math
 
