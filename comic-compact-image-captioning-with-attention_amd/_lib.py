@@ -103,6 +103,10 @@ class BeamSampling(C.Structure):     # struct comic_beam_sampling
     _fields_ = [('temperature', c_float), ('seed_dev', c_void_p)]
 
 
+class BeamTruncation(C.Structure):   # struct comic_beam_truncation
+    _fields_ = [('top_k', c_int32), ('top_p', c_float)]
+
+
 class GemmProb(C.Structure):         # struct comic_gemm_prob
     _fields_ = [(n, c_void_p) for n in ('A', 'B', 'C', 'bias', 'mask')] + [(n, c_int32) for n in (
         'M', 'N', 'K', 'lda', 'ldb', 'ldc', 'ld_mask')] + [(n, c_float) for n in ('alpha', 'beta', 'keep')] + [
@@ -213,6 +217,11 @@ _SIGS = {
     'comic_decoder_beam_sampled_workspace': (c_int64, [P, c_int, c_int, c_int, c_int]),
     'comic_decoder_beam_sampled': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, c_int64,
                                            P]),
+    'comic_beam_truncate_workspace': (c_int64, [c_int, c_int, c_int, c_int]),
+    'comic_beam_truncate': (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_float, P, c_int, P, c_int64, P]),
+    'comic_decoder_beam_truncated_workspace': (c_int64, [P, c_int, c_int, c_int, c_int]),
+    'comic_decoder_beam_truncated': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P,
+                                             c_int64, P]),
     # op-level entries of the executor-only kernel forms (tests only; the argument lists are csrc/exec_entries.h's)
     'comic_attn_splits': (c_int, [c_int, c_int]),
     'comic_attn_bwd_scratch': (C.c_long, [c_int, c_int, c_int, c_int]),

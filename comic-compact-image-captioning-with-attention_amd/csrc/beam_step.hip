@@ -17,6 +17,7 @@
 //                 and lp = a_0 to the bit.  (OneMember is NOT this with n = 1: a_0 - A is NaN at a -inf logit, a weight
 //                 other than 1 adds log wt, and the single path would pay an expf / logf per candidate.)
 // The policy also owns the row constants a workgroup keeps in LDS: [64] per beam for one member, [kEnsMax * 64] for several.
+// (The two structs live in beam_policy.h: beam_truncate.hip forms lp[v] with the same code.)
 //
 // Which candidates a live beam may not emit is a second, orthogonal policy (constrained beam search):
 //   NoBans ... none: the code of the step as it always was
@@ -88,6 +89,7 @@
 
 #include <algorithm>
 
+#include "beam_policy.h"
 #include "beam_select.h"
 #include "splitmix.h"
 
@@ -102,68 +104,6 @@ int64_t comic_beam_step_split_bytes(int n, int B, int W, int chunks) {
 }
 
 namespace {
-
-struct OneMember {
-  static constexpr const char* kName = "beam_step";
-  static constexpr const char* kSplitName = "beam_step (split)";
-  struct Rows {
-    float mx[64], logsum[64];
-    float lp[64];
-    int fin[64];
-  };
-  __device__ __forceinline__ int members() const { return 1; }
-  __device__ __forceinline__ void begin(Rows&) const {}
-  __device__ __forceinline__ float weight(int) const { return 1.f; }
-  __device__ __forceinline__ bool live(const Rows&, int) const { return true; }
-  __device__ __forceinline__ float step_lp(const float* __restrict__ lg, size_t, int f, int w, const Rows& s) const {
-    return (lg[f] - s.mx[w]) - s.logsum[w];
-  }
-};
-
-struct Ensemble {
-  static constexpr const char* kName = "beam_step_ensemble";
-  static constexpr const char* kSplitName = "beam_step_ensemble (split)";
-  int n;
-  float w[kEnsMax];
-  // Row constants of the entry: member m, beam w at [m * 64 + w]
-  struct Rows {
-    float mx[kEnsMax * 64], logsum[kEnsMax * 64];
-    float wt[kEnsMax];
-    float lp[64];
-    int fin[64];
-  };
-  __device__ __forceinline__ int members() const { return n; }
-  __device__ __forceinline__ void begin(Rows& s) const {       // the weights, visible to the workgroup on return
-    if (threadIdx.x < kEnsMax) s.wt[threadIdx.x] = (int)threadIdx.x < n ? w[threadIdx.x] : 0.f;
-    __syncthreads();
-  }
-  __device__ __forceinline__ float weight(int m) const {       // (a select chain: no dynamic index into the arguments)
-    float wt = 0.f;
-#pragma unroll
-    for (int k = 0; k < kEnsMax; ++k)
-      if (k == m) wt = w[k];
-    return wt;
-  }
-  __device__ __forceinline__ bool live(const Rows& s, int m) const { return s.wt[m] > 0.f; }
-  // member m's logits are mstride floats behind member 0's
-  __device__ __forceinline__ float step_lp(const float* __restrict__ lg, size_t mstride, int f, int w, const Rows& s) const {
-    float a[kEnsMax];
-    float A = -INFINITY;
-#pragma unroll
-    for (int m = 0; m < kEnsMax; ++m) {
-      a[m] = -INFINITY;
-      if (m < n && s.wt[m] > 0.f) {
-        a[m] = (lg[m * mstride + f] - s.mx[m * 64 + w]) - s.logsum[m * 64 + w];
-        A = fmaxf(A, a[m]);
-      }
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int m = 0; m < kEnsMax; ++m)
-      if (m < n && s.wt[m] > 0.f) sum += s.wt[m] * expf(a[m] - A);      // member order 0, 1, ...
-    return A + logf(sum);
-  }
-};
 
 struct NoBans {
   __device__ __forceinline__ NoBans entry(int, int) const { return NoBans{}; }
@@ -774,14 +714,7 @@ static int ens_step(const char* who, const float* logits, const float* weights, 
   COMIC_REQUIRE(V > 0 && W <= V && (long)W * V < (1L << 31), "%s: beam*V too large or beam > V", who);
   COMIC_REQUIRE((long)n_models * B <= 65535, "%s: members * batch too large", who);
   Ensemble pol{};
-  pol.n = n_models;
-  float wsum = 0.f;
-  for (int m = 0; m < n_models; ++m) {
-    COMIC_REQUIRE(weights[m] >= 0.f && weights[m] <= FLT_MAX, "%s: weight %d is negative or not finite", who, m);
-    pol.w[m] = weights[m];
-    wsum += weights[m];
-  }
-  COMIC_REQUIRE(wsum > 0.f, "%s: every weight is zero", who);
+  if (int rc = comic_ensemble_policy(who, weights, n_models, &pol)) return rc;
   if (smp) {
     if (bits)
       return beam_step_launch(pol, Bans{bits, words}, *smp, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids,

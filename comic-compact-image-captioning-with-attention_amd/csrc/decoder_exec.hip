@@ -90,6 +90,8 @@ int comic_beam_step_ws(const float* logits, float* log_probs, int32_t* finished,
 int64_t comic_beam_step_split_bytes(int n, int B, int W, int chunks);
 int comic_beam_groups_check(const comic_beam_groups* g, const char* who, int W, int V);
 int comic_beam_sampling_check(const comic_beam_sampling* s, const char* who, float lpw, int W);
+// beam_truncate.hip
+int comic_beam_truncation_check(const comic_beam_truncation* tr, const char* who, int V, bool whole);
 // beam_bans.hip
 int comic_beam_constraints_check(const comic_beam_constraints* c, const char* who, int W, int V, int end_id, int max_steps,
                                  bool whole);
@@ -2075,16 +2077,19 @@ struct EnsBufs {
   int32_t* ids;                    // [R] start ids
   void* step_ws;
   int64_t step_bytes;
-  uint32_t* bits;                  // [R][ceil(V / 32)] ban masks (constrained only)
+  uint32_t* bits;                  // [R][ceil(V / 32)] ban masks (constrained or truncated only)
   int32_t* ban_hist;               // [2][R][max_steps] token histories in beam order (constrained only)
+  void* trunc_ws;                  // comic_beam_truncate's scratch rows (truncated only; none while a row fits in LDS)
+  int64_t trunc_bytes;
   size_t bytes;
   bool ok;
 };
 // bytes of the ensemble step's workspace for any split of `rows` into batch x beam: (2 n + 2) * rows * chunks words, chunks <= 32
 int64_t ens_step_ws_bound(int n, int rows) { return comic_beam_step_split_bytes(n, rows, 1, 32); }
 // sampled: the step's lists carry every slot's total too (comic_beam_step_sampled_workspace): rows * chunks words more
+// truncated: the masks even without constraints, and the truncation's scratch rows
 EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64_t bytes, int ban_steps = 0,
-                  bool sampled = false) {
+                  bool sampled = false, bool truncated = false) {
   EnsBufs e{};
   size_t off = 0;
   e.ok = true;
@@ -2104,6 +2109,11 @@ EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64
   if (ban_steps > 0) {
     e.bits = w.take<uint32_t>((size_t)R * ((descs[0].V + 31) / 32));
     e.ban_hist = w.take<int32_t>((size_t)2 * R * ban_steps);
+  }
+  if (truncated) {
+    if (ban_steps <= 0) e.bits = w.take<uint32_t>((size_t)R * ((descs[0].V + 31) / 32));
+    e.trunc_bytes = std::max<int64_t>(0, comic_beam_truncate_workspace(n, R, 1, descs[0].V));
+    if (e.trunc_bytes > 0) e.trunc_ws = w.take<char>((size_t)e.trunc_bytes);
   }
   e.ok = e.ok && w.ok;
   e.bytes = off + w.off;
@@ -2128,13 +2138,14 @@ extern "C" int64_t comic_decoder_beam_constrained_workspace(const comic_decoder_
 // The ONE ensemble loop.  cons null: comic_decoder_beam_ensemble, launch for launch as it always was; else every step
 // builds the beams' ban masks first (beam_bans.hip) and ranks through them (the Bans policy of beam_step.hip).  grp null:
 // one beam of width W; else the first slot of every group starts live and every step ranks under the Groups policy.  smp
-// null: no sampling; else (grp is null) every slot starts live and step t ranks under the Samples policy.
+// null: no sampling; else (grp is null) every slot starts live and step t ranks under the Samples policy.  trc null: no
+// truncation; else (smp is not null) every step narrows the mask by top-k / top-p (beam_truncate.hip) before it ranks.
 static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decoder_params* params, const float* const* fms,
                              const float* const* im_embeds, const float* weights, int n_models, int B, int W, int max_steps,
                              int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
                              float* const* attn_hists, int32_t* steps_executed, const comic_beam_constraints* cons,
                              const comic_beam_groups* grp, const comic_beam_sampling* smp, void* workspace,
-                             int64_t workspace_bytes, void* stream) {
+                             int64_t workspace_bytes, void* stream, const comic_beam_truncation* trc = nullptr) {
   COMIC_REQUIRE(descs && params && fms && im_embeds && weights && step_ids && parent_ids && scores && lengths && finished &&
                     steps_executed && workspace,
                 "beam_ensemble: null pointer");
@@ -2151,9 +2162,10 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
   COMIC_REQUIRE(W <= V && (long)W * V < (1L << 31), "beam_ensemble: beam*V too large or beam > V");
   if (cons) RC(comic_beam_constraints_check(cons, "beam_constrained", W, V, descs[0].end_id, max_steps, true));
   if (grp) RC(comic_beam_groups_check(grp, "beam_diverse", W, V));
-  if (smp) RC(comic_beam_sampling_check(smp, "beam_sampled", descs[0].length_penalty_weight, W));
+  if (smp) RC(comic_beam_sampling_check(smp, trc ? "beam_truncated" : "beam_sampled", descs[0].length_penalty_weight, W));
+  if (trc) RC(comic_beam_truncation_check(trc, "beam_truncated", V, true));
   hipStream_t st = (hipStream_t)stream;
-  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, cons ? max_steps : 0, smp != nullptr);
+  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, cons ? max_steps : 0, smp != nullptr, trc != nullptr);
   COMIC_REQUIRE(L.ok && (int64_t)L.bytes <= workspace_bytes, "beam_ensemble: workspace too small");
   g_splitk_ws = L.m[0].splitk;               // members run back to back on the one stream: one split-K scratch serves all
   const float lpw = descs[0].length_penalty_weight;
@@ -2215,9 +2227,12 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
     if (cons)
       RC(comic_beam_bans_launch(t == 0 ? nullptr : (const int32_t*)ids_in, par_in, finished, lengths, L.ban_hist, L.bits, t, B,
                                 W, V, max_steps, descs[0].end_id, cons, st));
+    if (trc)
+      RC(comic_beam_truncate(L.logits, weights, n, finished, L.bits, (V + 31) / 32, B, W, V, smp->temperature, trc,
+                             cons ? 1 : 0, L.trunc_ws, L.trunc_bytes, (void*)st));
     if (smp) {
       RC(comic_beam_step_sampled(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
-                                 B, W, V, descs[0].end_id, cons ? L.bits : nullptr, (V + 31) / 32, smp, t, L.step_ws,
+                                 B, W, V, descs[0].end_id, (cons || trc) ? L.bits : nullptr, (V + 31) / 32, smp, t, L.step_ws,
                                  L.step_bytes, (void*)st));
     } else if (grp) {
       RC(comic_beam_step_diverse(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
@@ -2296,4 +2311,26 @@ extern "C" int comic_decoder_beam_sampled(const comic_decoder_desc* descs, const
   return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
                            lengths, finished, attn_hists, steps_executed, constraints, nullptr, sampling, workspace,
                            workspace_bytes, stream);
+}
+
+extern "C" int64_t comic_decoder_beam_truncated_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                          int max_steps, int constrained) {
+  if (comic_decoder_beam_sampled_workspace(descs, n_models, rows, max_steps, constrained) < 0) return -1;
+  if (comic_beam_truncate_workspace(n_models, rows, 1, descs[0].V) < 0) return -1;
+  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0, constrained ? max_steps : 0, true, true).bytes;
+}
+
+extern "C" int comic_decoder_beam_truncated(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                            const float* const* fms, const float* const* im_embeds, const float* weights,
+                                            int n_models, int B, int W, int max_steps,
+                                            const comic_beam_constraints* constraints, const comic_beam_sampling* sampling,
+                                            const comic_beam_truncation* truncation, int32_t* step_ids, int32_t* parent_ids,
+                                            float* scores, int64_t* lengths, int32_t* finished, float* const* attn_hists,
+                                            int32_t* steps_executed, void* workspace, int64_t workspace_bytes,
+                                            void* stream) {
+  COMIC_REQUIRE(sampling, "beam_truncated: null sampling");
+  COMIC_REQUIRE(truncation, "beam_truncated: null truncation");
+  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
+                           lengths, finished, attn_hists, steps_executed, constraints, nullptr, sampling, workspace,
+                           workspace_bytes, stream, truncation);
 }

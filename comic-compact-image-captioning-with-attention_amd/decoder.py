@@ -516,6 +516,82 @@ def sampling_dir_suffix(c):
     return '_smp_t%g_s%d' % (float(1.0 if t is None else t), int(0 if seed is None else seed))
 
 
+class BeamTruncation:
+    """Top-k and nucleus (top-p) truncation of the sampled step (comic_beam_truncation; extends rnn_decoder_beam_search,
+    ops_rnn.py:49-112): a live slot draws from the `top_k` likeliest tokens of the tempered step distribution only
+    (0 = off; ties by lowest id), and of those from the smallest set of likeliest tokens whose probability, renormalised
+    over them, reaches `top_p` (>= 1 = off; tokens tied at the boundary all stay) -- the temperature -> top-k -> top-p
+    order.  Constraints are applied first: a banned token counts neither in k nor in the mass.  The log-probabilities a
+    decode returns stay the model's own unperturbed, untempered, UNTRUNCATED log p(caption | image), which Decoder.score
+    reproduces; they are not the log-probability under the truncated distribution.  Both values are baked into a
+    captured graph, so both are part of a decode context's key.  BeamTruncation() is the inactive value."""
+
+    def __init__(self, top_k=0, top_p=1.0):
+        self.top_k, self.top_p = int(top_k), float(top_p)
+
+    def key(self):
+        return (self.top_k, self.top_p)
+
+    def __eq__(self, other):
+        return isinstance(other, BeamTruncation) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'BeamTruncation(top_k=%d, top_p=%r)' % self.key()
+
+    @property
+    def active(self):
+        return self.top_k >= 1 or self.top_p < 1.0
+
+    def ctx_key(self):
+        """What a decode context is keyed by: top_k, and top_p as the fp32 value the kernel sees."""
+        return ('truncate', self.top_k, float(np.float32(self.top_p)))
+
+    def check(self, sampling=None):
+        """The rules of the C side, on the host before any GPU call; raises ValueError naming the field.  An active
+        truncation needs an active BeamSampling."""
+        if self.top_k < 0:
+            raise ValueError('top_k must be >= 0, got %d' % self.top_k)
+        if not self.top_p > 0.0:
+            raise ValueError('top_p must be > 0 and not NaN, got %r' % self.top_p)
+        if self.active and (sampling is None or not sampling.active):
+            raise ValueError('truncation (top_k / top_p) applies to sampling only: it needs an active BeamSampling')
+
+    def c_struct(self):
+        g = L.BeamTruncation()
+        g.top_k, g.top_p = self.top_k, self.top_p
+        return g
+
+
+def truncation_from_config(c):
+    """The BeamTruncation a configuration asks for (infer_top_k, infer_top_p), or None when it sets neither; either of
+    them without infer_sample is a ValueError."""
+    k, p = getattr(c, 'infer_top_k', None), getattr(c, 'infer_top_p', None)
+    if k is None and p is None:
+        return None
+    if not getattr(c, 'infer_sample', None):
+        raise ValueError('infer_top_k / infer_top_p apply to sampling only: set infer_sample')
+    trc = BeamTruncation(top_k=0 if k is None else k, top_p=1.0 if p is None else p)
+    trc.check(sampling_from_config(c))
+    return trc
+
+
+def truncation_dir_suffix(c):
+    """'_k{top_k}_p{top_p:g}' when the configuration samples under a truncation -- a stage that is off is left out:
+    '_k40', '_p0.9' -- else ''."""
+    if not getattr(c, 'infer_sample', None):
+        return ''
+    k, p = getattr(c, 'infer_top_k', None), getattr(c, 'infer_top_p', None)
+    out = ''
+    if k is not None and int(k) >= 1:
+        out += '_k%d' % int(k)
+    if p is not None and float(p) < 1.0:
+        out += '_p%g' % float(p)
+    return out
+
+
 def process_inputs(captions, token_type):
     """ModelBase._process_inputs (model_base.py:501-528) on the host.
     -> inputs [B,T] int32, targets [B,T] int32, masks [B,T] fp32, lens [B] int32."""
@@ -1082,7 +1158,7 @@ class Decoder:
         return fetch
 
     def beam_search(self, fm, im_embed, beam, max_steps, want_attention=True, use_graph=True, length_penalty_weight=0.0,
-                    constraints=None, groups=None, sampling=None, image_base=0):
+                    constraints=None, groups=None, sampling=None, image_base=0, truncation=None):
         """rnn_decoder_beam_search (ops_rnn.py:49-112).  Returns predicted_ids [T,B,W] (after
         gather_tree), scores [T,B,W] (with length_penalty_weight != 0: the penalised scores the beams were ranked by,
         BeamSearchDecoder's `scores` output), the raw step/parent ids and, unless want_attention=False, the
@@ -1098,7 +1174,13 @@ class Decoder:
         with constraints (not with more than one group or a length penalty: ValueError): slot w of predicted_ids is sample
         w, `scores` the chains' running log p(caption | image) and `log_probs` [B,beam] the final ones; image_base is the
         index in the run of the batch's first image (the noise of an image does not depend on its batch).  None /
-        inactive: today's path."""
+        inactive: today's path.
+        truncation: a BeamTruncation; an active one (with active sampling: ValueError otherwise) restricts every draw to the
+        top_k likeliest tokens and / or the top_p nucleus through comic_decoder_beam_truncated.  `scores` / `log_probs` stay
+        the model's own unperturbed, untempered, UNTRUNCATED log p(caption | image) -- Decoder.score reproduces them -- not
+        the log-probability under the truncated distribution.  None / inactive: today's path, call for call."""
+        if truncation is not None:
+            truncation.check(sampling)
         constrained = constraints is not None and constraints.active
         grouped = groups is not None and groups.active
         sampled = sampling is not None and sampling.active
@@ -1114,7 +1196,7 @@ class Decoder:
                 ens = self._self_ensemble = EnsembleDecoder([self])
             return ens.beam_search(fm, im_embed, beam, max_steps, want_attention=want_attention, use_graph=use_graph,
                                    length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
-                                   sampling=sampling, image_base=image_base)
+                                   sampling=sampling, image_base=image_base, truncation=truncation)
         torch, s = self.torch, self.spec
         B, W = fm.shape[0], beam
         # (a non-zero length penalty is another captured graph: the weight is baked into the step kernel's arguments)
@@ -1219,17 +1301,20 @@ class EnsembleDecoder:
         self.torch, self.lib, self.device = decoders[0].torch, decoders[0].lib, decoders[0].device
         self._ctxs = {}
 
-    def _ctx(self, B, W, max_steps, lpw, feats, cons=None, grp=None, smp=None):
+    def _ctx(self, B, W, max_steps, lpw, feats, cons=None, grp=None, smp=None, trc=None):
         """Persistent buffers (+ a hipGraph of the whole loop, captured on the second call with the shape), as
         Decoder._infer_ctx.  cons: active BeamConstraints (they are baked into the captured launches) or None; grp: active
         BeamGroups (baked in likewise) or None; smp: active BeamSampling or None -- its temperature is baked in and part
-        of the key, its seed words are not: they live in ctx.seed, which beam_search writes in front of every launch."""
+        of the key, its seed words are not: they live in ctx.seed, which beam_search writes in front of every launch;
+        trc: active BeamTruncation (with smp) or None -- baked in, part of the key."""
         torch, n = self.torch, len(self.decoders)
         key = (B, W, max_steps, float(lpw)) if cons is None else (B, W, max_steps, float(lpw), cons.key())
         if grp is not None:
             key = (B, W, max_steps, float(lpw), cons.key() if cons is not None else None, grp.key())
         if smp is not None:
             key = (B, W, max_steps, float(lpw), cons.key() if cons is not None else None, None, smp.ctx_key())
+            if trc is not None:
+                key = key + (trc.ctx_key(),)
         ctx = self._ctxs.get(key)
         if ctx is None:
             ctx = type('EnsembleCtx', (), {})()
@@ -1260,9 +1345,13 @@ class EnsembleDecoder:
             if smp is not None:
                 ctx.seed = torch.zeros(2, dtype=torch.int64, device=self.device)       # uint64[2]: {seed, image_base}
                 ctx.smp = smp.c_struct(ctx.seed.data_ptr())
+            ctx.trc = trc.c_struct() if trc is not None else None
             ws_fn = self.lib.comic_decoder_beam_ensemble_workspace if cons is None else \
                 self.lib.comic_decoder_beam_constrained_workspace
-            if smp is not None:
+            if trc is not None:
+                ctx.nbytes = int(self.lib.comic_decoder_beam_truncated_workspace(ctx.descs, n, R, max_steps,
+                                                                                 0 if cons is None else 1))
+            elif smp is not None:
                 ctx.nbytes = int(self.lib.comic_decoder_beam_sampled_workspace(ctx.descs, n, R, max_steps,
                                                                                0 if cons is None else 1))
             elif grp is not None:
@@ -1280,14 +1369,16 @@ class EnsembleDecoder:
         return ctx
 
     def beam_search(self, fms, im_embeds, beam, max_steps, want_attention=False, use_graph=True, length_penalty_weight=0.0,
-                    constraints=None, groups=None, sampling=None, image_base=0):
+                    constraints=None, groups=None, sampling=None, image_base=0, truncation=None):
         """fms / im_embeds: one device tensor (every member reads the same features) or a sequence with one per member.
         Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's.  constraints: a
         BeamConstraints; active ones run comic_decoder_beam_constrained, None / inactive ones today's entry point.
         groups: a BeamGroups; an active one runs comic_decoder_beam_diverse (with the constraints, if any), as
         Decoder.beam_search describes; None / inactive: today's entry points.
         sampling, image_base: a BeamSampling; an active one runs comic_decoder_beam_sampled (with the constraints, if any),
-        as Decoder.beam_search describes; None / inactive: today's entry points."""
+        as Decoder.beam_search describes; None / inactive: today's entry points.
+        truncation: a BeamTruncation; an active one (sampling only) runs comic_decoder_beam_truncated; the log-probabilities
+        stay the untruncated ones, as Decoder.beam_search describes; None / inactive: today's entry points, call for call."""
         torch, n = self.torch, len(self.decoders)
         cons = constraints if constraints is not None and constraints.active else None
         if groups is not None:
@@ -1296,6 +1387,9 @@ class EnsembleDecoder:
         if sampling is not None:
             sampling.check(beam, length_penalty_weight, groups)
         smp = sampling if sampling is not None and sampling.active else None
+        if truncation is not None:
+            truncation.check(sampling)
+        trc = truncation if truncation is not None and truncation.active else None
         if cons is not None:
             cons.check(self.spec, beam, max_steps)
         if torch.is_tensor(fms):
@@ -1304,7 +1398,7 @@ class EnsembleDecoder:
             im_embeds = [im_embeds] * n
         assert len(fms) == n and len(im_embeds) == n
         B, W = int(fms[0].shape[0]), int(beam)
-        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)), cons, grp, smp)
+        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)), cons, grp, smp, trc)
         if smp is not None:                 # on the stream, in front of the launch or the replay that reads them
             ctx.seed.copy_(torch.from_numpy(smp.seed_words(image_base)))
 
@@ -1312,6 +1406,14 @@ class EnsembleDecoder:
             flags = L.decoder_flags_from_env()
             for k in range(n):
                 ctx.descs[k].flags = flags
+            if ctx.trc is not None:
+                L.check(self.lib.comic_decoder_beam_truncated(
+                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps,
+                    C.byref(ctx.cons) if ctx.cons is not None else None, C.byref(ctx.smp), C.byref(ctx.trc),
+                    ctx.step_ids.data_ptr(), ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(),
+                    ctx.finished.data_ptr(), ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
+                    L.stream_ptr()), 'decoder_beam_truncated')
+                return
             if ctx.smp is not None:
                 L.check(self.lib.comic_decoder_beam_sampled(
                     ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps,

@@ -351,20 +351,23 @@ class ModelBase(object):
 
     # ---- decode (model_base.py:692-757, :272-314) ----------------------------------------
     def _decode(self, images, beam_size, max_length, top_beam=True, want_attention=True, length_penalty_weight=0.0,
-                constraints=None, groups=None, sampling=None, image_base=0):
+                constraints=None, groups=None, sampling=None, image_base=0, truncation=None):
         im_embed, fm = self._encode(images)
         return self._decode_features(im_embed, fm, beam_size, max_length, top_beam, want_attention, length_penalty_weight,
-                                     constraints, groups, sampling, image_base)
+                                     constraints, groups, sampling, image_base, truncation)
 
     def _decode_features(self, im_embed, fm, beam_size, max_length, top_beam=True, want_attention=True,
-                         length_penalty_weight=0.0, constraints=None, groups=None, sampling=None, image_base=0):
+                         length_penalty_weight=0.0, constraints=None, groups=None, sampling=None, image_base=0,
+                         truncation=None):
         """constraints: decoder.BeamConstraints in TOKENS (decoder.constraints_from_config translates a configuration's
         words); beam search only.  groups: decoder.BeamGroups; an active one decodes by diverse beam search: the top beam is
         group 0's best (the caption of beam search of width beam / groups), and self.group_output holds the group-best
         captions of the batch (group_best), None otherwise.  sampling: decoder.BeamSampling; an active one draws beam_size
         samples per image (image_base: the number of images decoded before this batch in the run): the top beam is, per
         image, the sample of highest log-probability (lowest slot on ties), and self.sample_output holds every sample
-        (sample_set), None otherwise."""
+        (sample_set), None otherwise.  truncation: decoder.BeamTruncation; an active one restricts every draw to the top_k
+        likeliest tokens and / or the top_p nucleus (sampling only: ValueError otherwise); the log-probabilities stay the
+        model's own, untruncated."""
         c = self._config
         iters = self.decoder.max_iterations(max_length, len(c.wtoi))
         constrained = constraints is not None and constraints.active
@@ -372,10 +375,13 @@ class ModelBase(object):
         sampled = sampling is not None and sampling.active
         self.group_output = None
         self.sample_output = None
+        if truncation is not None:
+            truncation.check(sampling)
         if sampled:
             sampling.check(beam_size, length_penalty_weight, groups)
             r = self.decoder.beam_search(fm, im_embed, beam_size, iters, want_attention=want_attention,
-                                         constraints=constraints, sampling=sampling, image_base=image_base)
+                                         constraints=constraints, sampling=sampling, image_base=image_base,
+                                         truncation=truncation)
             self.sample_output = sample_set(r)
             pred = r['predicted_ids']                                  # (T, B, n)
             T, B = pred.shape[:2]
@@ -570,7 +576,7 @@ class CaptionModel(ModelBase):
         self._images_sampled = base + int(B)
         return base
 
-    def infer(self, batch=None, constraints=None, groups=None, sampling=None):
+    def infer(self, batch=None, constraints=None, groups=None, sampling=None, truncation=None):
         """== sess.run(m_infer.infer_output) -> [dec_preds (B,T), attention_maps (B,H,T,M)].
         constraints: decoder.BeamConstraints; None reads the configuration (infer_min_length, infer_no_repeat_ngram,
         infer_suppress_words).  groups: decoder.BeamGroups; None reads the configuration (infer_beam_groups,
@@ -578,6 +584,7 @@ class CaptionModel(ModelBase):
         sampling: decoder.BeamSampling; None reads the configuration (infer_sample, infer_temperature, infer_sample_seed).
         With active sampling infer_beam_size is the number of samples per image, dec_preds is per image the sample of
         highest log-probability and self.sample_output = dict(ids (B,n,T), log_probs (B,n), lengths (B,n)).
+        truncation: decoder.BeamTruncation; None reads the configuration (infer_top_k, infer_top_p); sampling only.
         Batches drawn from the input pipeline are decoded with the encoder forward of the NEXT group of batches already
         running on a second stream (the decode steps are small launches that leave most of the GPU idle;
         config.pipeline_encoder, default on; config.pipeline_encoder_group batches per forward, 0 = auto).  Same
@@ -597,14 +604,16 @@ class CaptionModel(ModelBase):
             groups = cdec.groups_from_config(c)
         if sampling is None:
             sampling = cdec.sampling_from_config(c)
+        if truncation is None:
+            truncation = cdec.truncation_from_config(c)
         ids, attn = self._decode_features(im_embed, fm, c.infer_beam_size, c.infer_max_length, top_beam=True,
                                           length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
                                           constraints=constraints, groups=groups, sampling=sampling,
-                                          image_base=self._image_base(sampling, fm.shape[0]))
+                                          image_base=self._image_base(sampling, fm.shape[0]), truncation=truncation)
         self.infer_output = [ids, attn]
         return self.infer_output
 
-    def infer_pipelined(self, want_attention=True, constraints=None, groups=None, sampling=None):
+    def infer_pipelined(self, want_attention=True, constraints=None, groups=None, sampling=None, truncation=None):
         """Generator over the batches of the input pipeline -> [dec_preds (B,T), attention_maps or None] in input order, with
         the decode loops of THREE batches in flight (COMIC_INFER_IN_FLIGHT; one stream and one buffer set of the decoder each:
         Decoder.beam_search_ids(slot=)).
@@ -613,7 +622,7 @@ class CaptionModel(ModelBase):
         baseline (tools/beam_time.py TWO=1), the same ids; three in flight +6 % over two (24.5k against 23.1k captions/s on one
         box; four and five lose: 23.9k, 19.3k -- each loop streams the 52 MB vocabulary projection per step).  Only the captions-only beam search runs this way (no attention
         maps, no length penalty, no beam constraints, no beam groups: what `infer.py` writes unless --save_attention_maps);
-        everything else yields infer().  constraints, groups, sampling: as infer()."""
+        everything else yields infer().  constraints, groups, sampling, truncation: as infer()."""
         c, torch = self._config, self.torch
         lp = getattr(c, 'infer_length_penalty_weight', 0.0)
         if constraints is None:
@@ -625,6 +634,10 @@ class CaptionModel(ModelBase):
         if sampling is None:
             sampling = cdec.sampling_from_config(c)
         constrained = constrained or (sampling is not None and sampling.active)  # (so does sampling)
+        if truncation is None:
+            truncation = cdec.truncation_from_config(c)
+        if truncation is not None:
+            truncation.check(sampling)
         NL = max(1, min(5, int(os.environ.get('COMIC_INFER_IN_FLIGHT', '3'))))      # decode loops in flight (3: measured best of 1-5)
         if want_attention or lp or constrained or c.infer_beam_size <= 1 or not str(self.device).startswith('cuda'):
             NL = 1
@@ -636,7 +649,8 @@ class CaptionModel(ModelBase):
                 ids, attn = self._decode_features(feats[0], feats[1], c.infer_beam_size, c.infer_max_length, top_beam=True,
                                                   want_attention=want_attention, length_penalty_weight=lp,
                                                   constraints=constraints, groups=groups, sampling=sampling,
-                                                  image_base=self._image_base(sampling, feats[1].shape[0]))
+                                                  image_base=self._image_base(sampling, feats[1].shape[0]),
+                                                  truncation=truncation)
                 yield [ids, attn]
         iters = self.decoder.max_iterations(c.infer_max_length, len(c.wtoi))
         lanes = [streams.lane(torch, self.device, 'infer%d' % k) for k in range(NL)]
@@ -891,9 +905,9 @@ class CaptionEnsemble(object):
             return [(m._embed(net), fm) for m in self.models]
         return [m._encode(images) for m in self.models]
 
-    def infer(self, batch=None, constraints=None, groups=None, sampling=None):
+    def infer(self, batch=None, constraints=None, groups=None, sampling=None, truncation=None):
         """-> [dec_preds (B,T), attention_maps (B,H,T,M) of member 0], as CaptionModel.infer; without `batch` the images
-        come from member 0's input pipeline.  constraints, groups, sampling: as CaptionModel.infer."""
+        come from member 0's input pipeline.  constraints, groups, sampling, truncation: as CaptionModel.infer."""
         c = self._config
         if constraints is None:
             constraints = cdec.constraints_from_config(c)
@@ -901,6 +915,8 @@ class CaptionEnsemble(object):
             groups = cdec.groups_from_config(c)
         if sampling is None:
             sampling = cdec.sampling_from_config(c)
+        if truncation is None:
+            truncation = cdec.truncation_from_config(c)
         sampled = sampling is not None and sampling.active
         if batch is None:
             batch = next(self.models[0].batch_ops)
@@ -916,7 +932,8 @@ class CaptionEnsemble(object):
             self._images_sampled = base + int(feats[0][1].shape[0])
         r = self.decoder.beam_search([f[1] for f in feats], [f[0] for f in feats], W, iters, want_attention=True,
                                      length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
-                                     constraints=constraints, groups=groups, sampling=sampling, image_base=base)
+                                     constraints=constraints, groups=groups, sampling=sampling, image_base=base,
+                                     truncation=truncation)
         pred = r['predicted_ids']                                  # (T, B, W)
         T, B = pred.shape[:2]
         self.group_output = group_best(r) if r['groups'] > 1 else None

@@ -587,6 +587,41 @@ int comic_beam_step_sampled(const float* logits, const float* weights, int n_mod
                             int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int V,
                             int end_id, const uint32_t* bits, int words, const comic_beam_sampling* sampling, int t,
                             void* workspace, int64_t workspace_bytes, void* stream);
+/* Top-k and nucleus (top-p) truncation of the sampled step (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112):
+ * which candidates a live slot may draw from.  Applied to a live slot (b, w) at step t AFTER the ban mask of the
+ * constraints (if any) has been built and BEFORE the sampled step ranks; its result is ban bits in the same mask.
+ *   Inputs: lp[v] is the step log-probability of the plain step (the ensemble mean, the very code the step ranks by);
+ *   a[v] = lp[v] * inv_temp in fp32, inv_temp = 1.0f / temperature formed once on the host as for comic_beam_sampling;
+ *   the allowed set A is the tokens whose ban bit is clear (no constraints: all V tokens).
+ *   Top-k (top_k >= 1; 0 = off): K = the top_k largest a over A, equal values resolved by lowest v.  top_k >= |A|: the
+ *   stage does nothing and K = A.
+ *   Top-p (0 < top_p < 1; top_p >= 1 = off): m = max_K a, e[v] = exp(a[v] - m), Z = sum_K e; tau is the largest value
+ *   among a[K] such that sum_{u in K, a[u] >= tau} e[u] >= top_p * Z (a product, never a division); v in K is kept iff
+ *   a[v] >= tau: all candidates tied at the boundary value are kept.  The nucleus is taken on the distribution
+ *   renormalised over K: the temperature -> top-k -> top-p order.  The masses are summed exactly, as the fixed-point
+ *   integers floor(e * 2^40) (csrc/beam_truncate.hip), so the mask does not depend on how the waves interleave.
+ *   Mask: every token of a live row that is not kept gets its ban bit set; bits already set stay set; the best allowed
+ *   candidate is always kept.  A row whose m is not finite (all banned, or a NaN) is left as it came.  A finished row is
+ *   not touched: _mask_probs makes it emit <EOS> as ever.
+ *   Nothing else changes: the sampled step ranks lp[v] * inv_temp + g over the survivors; word_ids, the state log_probs
+ *   and scores stay the model's own UNPERTURBED, UNTEMPERED, UNTRUNCATED log p(caption so far | image) -- not the
+ *   log-probability under the truncated distribution.
+ * Limits: top_k >= 0; top_p > 0 and not NaN; not both stages off; V <= 65 536; sampling only (no beam search, no groups). */
+typedef struct comic_beam_truncation {
+  int32_t top_k;
+  float top_p;
+} comic_beam_truncation;
+/* One step of the rule above as a raw operator (common/ops_rnn.py:49-112 has no counterpart; csrc/beam_truncate.hip).
+ * logits [n_models][B*W][V] (device), weights [n_models] (HOST) as comic_beam_step_ensemble; finished [B*W];
+ * bits [B*W][words], words == ceil(V/32).  has_bans != 0: bits holds the constraints' mask (comic_beam_bans) and is
+ * updated in place; has_bans == 0: its incoming content is ignored and every word of every row is written (a finished
+ * row, and a row left as it came, as zeros).  Bits at positions >= V stay / become zero.  As a raw operator a top_k that
+ * reaches V is accepted (it changes nothing).  workspace: comic_beam_truncate_workspace bytes (0 while a row's keys fit
+ * in LDS, V <= 32 768; else a scratch row per slot), may be NULL when that is 0. */
+int64_t comic_beam_truncate_workspace(int n_models, int B, int W, int V);
+int comic_beam_truncate(const float* logits, const float* weights, int n_models, const int32_t* finished, uint32_t* bits,
+                        int words, int B, int W, int V, float temperature, const comic_beam_truncation* truncation,
+                        int has_bans, void* workspace, int64_t workspace_bytes, void* stream);
 /* out[r,:] = in[(r/W)*W + parent[r], :]   (state re-ordering by parent beam) */
 int comic_gather_rows(const float* in, const int32_t* parent, float* out, int rows, int W, int cols,
                       void* stream);
@@ -855,6 +890,22 @@ int comic_decoder_beam_sampled(const comic_decoder_desc* descs, const comic_deco
                                const comic_beam_sampling* sampling, int32_t* step_ids, int32_t* parent_ids, float* scores,
                                int64_t* lengths, int32_t* finished, float* const* attn_hists, int32_t* steps_executed,
                                void* workspace, int64_t workspace_bytes, void* stream);
+/* Sampled decode under a truncation (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112):
+ * comic_decoder_beam_sampled -- the same loop -- with one more launch per step, between the ban bookkeeping and the
+ * sampled step: comic_beam_truncate under sampling->temperature, on the constraints' mask when there are constraints,
+ * else on a mask of its own.  The sampled step then ranks through that mask.  `scores` stay the chains' running
+ * UNTRUNCATED log p(caption | image).  truncation must not be NULL and must do something: refused are top_k < 0,
+ * top_p NaN or <= 0, both stages off (top_k == 0 or >= V, with top_p >= 1) and V > 65 536.  Everything else as
+ * comic_decoder_beam_sampled.  workspace: comic_decoder_beam_truncated_workspace bytes. */
+int64_t comic_decoder_beam_truncated_workspace(const comic_decoder_desc* descs, int n_models, int rows, int max_steps,
+                                               int constrained);
+int comic_decoder_beam_truncated(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                 const float* const* fms, const float* const* im_embeds, const float* weights, int n_models,
+                                 int B, int W, int max_steps, const comic_beam_constraints* constraints,
+                                 const comic_beam_sampling* sampling, const comic_beam_truncation* truncation,
+                                 int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
+                                 float* const* attn_hists, int32_t* steps_executed, void* workspace,
+                                 int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Op-level entries of the executor-only kernel forms                        */

@@ -62,6 +62,11 @@ def create_parser():
            'sample of highest log-probability, caption_samples___N.json every sample with its log-probability.')
     a('--infer_temperature', type=float, default=None, help='Sampling: the temperature of the word distribution (default 1).')
     a('--infer_sample_seed', type=int, default=None, help='Sampling: the seed of the noise generator (default 0).')
+    a('--infer_top_k', type=int, default=None,
+      help='Sampling: draw every token from the k likeliest only (0 = off; needs --infer_sample).')
+    a('--infer_top_p', type=float, default=None,
+      help='Sampling: draw every token from the smallest set of likeliest tokens whose probability reaches p (the nucleus; '
+           'after --infer_top_k; 1 = off; needs --infer_sample).')
     return p
 
 
@@ -92,10 +97,11 @@ def main(argv=None):
                  'coco_valid': 'infer_cocoValid_'}[c.infer_set] + save_name
     # constrained, grouped and sampled captions get a directory of their own: they never overwrite the plain ones
     from comic_amd.decoder import (constraints_dir_suffix, groups_dir_suffix, groups_from_config, sampling_dir_suffix,
-                                   sampling_from_config)
+                                   sampling_from_config, truncation_dir_suffix, truncation_from_config)
     groups_from_config(c)           # (refuses groups that do not divide infer_beam_size before anything is loaded)
     sampling_from_config(c)         # (refuses sampling with more than one group or a length penalty likewise)
-    save_name += constraints_dir_suffix(c) + groups_dir_suffix(c) + sampling_dir_suffix(c)
+    truncation_from_config(c)       # (refuses --infer_top_k / --infer_top_p without --infer_sample likewise)
+    save_name += constraints_dir_suffix(c) + groups_dir_suffix(c) + sampling_dir_suffix(c) + truncation_dir_suffix(c)
     c.infer_save_path = pjoin(c.infer_checkpoints_dir, save_name)
     if os.path.exists(c.infer_save_path):
         print('\nINFO: `eval_log_path` already exists.')
