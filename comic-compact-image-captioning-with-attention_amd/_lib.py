@@ -99,6 +99,10 @@ class BeamGroups(C.Structure):       # struct comic_beam_groups
     _fields_ = [('groups', c_int32), ('diversity', c_float)]
 
 
+class BeamRequired(C.Structure):     # struct comic_beam_required
+    _fields_ = [('n_words', c_int32), ('stride', c_int32)]
+
+
 class BeamSampling(C.Structure):     # struct comic_beam_sampling
     _fields_ = [('temperature', c_float), ('seed_dev', c_void_p)]
 
@@ -210,6 +214,14 @@ _SIGS = {
     'comic_decoder_beam_diverse_workspace': (c_int64, [P, c_int, c_int, c_int, c_int]),
     'comic_decoder_beam_diverse': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, c_int64,
                                            P]),
+    'comic_beam_required_table': (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'comic_beam_required_init': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    'comic_beam_step_required_workspace': (c_int64, [c_int, c_int, c_int, c_int]),
+    'comic_beam_step_required': (c_int, [P, P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, c_int, P, P,
+                                         c_int, P, c_int64, P]),
+    'comic_decoder_beam_required_workspace': (c_int64, [P, c_int, c_int, c_int, c_int]),
+    'comic_decoder_beam_required': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                            c_int64, P]),
     'comic_beam_sample_noise': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
     'comic_beam_step_sampled_workspace': (c_int64, [c_int, c_int, c_int, c_int]),
     'comic_beam_step_sampled': (c_int, [P, P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P,

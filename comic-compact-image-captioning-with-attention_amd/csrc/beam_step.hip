@@ -71,6 +71,10 @@
 //                merge -- 3 launches whatever W is.  The lists hold W candidates per chunk, so the totals need a block
 //                of their own in the workspace: comic_beam_step_sampled_workspace.
 //
+// Beam search with required words splits the W slots into banks by constraint progress.  A bank's parents are any of the W
+// slots, so it is no member of the slot above (whose launches update a group's state in place) but a pair of kernels of
+// its own further down ("banks by constraint progress"), built from the same step_lp, cand_step, order and write_beam.
+//
 // Two forms, one copy of each kernel, instantiated per policy:
 //   beam_step_kernel ........ one workgroup per batch entry: any V, length penalty included
 //   beam_stats_kernel ....... per (chunk, beam, entry, member): max and sum exp(x - max) of the chunk
@@ -276,36 +280,12 @@ __device__ __forceinline__ void write_beam(int o, int f, float score, float tota
   lengths[o] = len[parent] + (prev_fin ? 0 : 1);
 }
 
-// ---- one workgroup per batch entry -----------------------------------------------------------------------------------
-template <class P, class Bn, class Gr>
-__global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict__ logits, P pol, Bn bans, float* __restrict__ log_probs,
-                                                        int32_t* __restrict__ finished, int64_t* __restrict__ lengths,
-                                                        int32_t* __restrict__ word_ids, int32_t* __restrict__ parent_ids,
-                                                        float* __restrict__ scores, int B, int W, int V, int end_id,
-                                                        float lpw, const int32_t* __restrict__ stop, int stop_t, Gr gr) {
-  __shared__ ValIdx sh[256];
-  __shared__ typename P::Rows s;
-  __shared__ int s_sel[64];
-  __shared__ float s_selv[64];
-  __shared__ long long s_len[64];
-  __shared__ typename Gr::Pen pen;
-  if (comic_stopped(stop, stop_t)) return;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const size_t mstride = (size_t)B * W * V;
-  const float* lg = logits + (size_t)b * W * V;
-  const Bn bn = bans.entry(b, W);
-  gr.clear(pen, b, W);
-  // the entry's beam state (W <= 64): loaded first, in flight behind the passes over the logits
-  float lp_w = 0.f;
-  int fin_w = 0;
-  long long len_w = 0;
-  if (tid < W) {
-    lp_w = log_probs[b * W + tid];
-    fin_w = finished[b * W + tid];
-    len_w = lengths[b * W + tid];
-  }
-  pol.begin(s);
-  // log-softmax constants per (member, beam): one wave per row
+// The row constants of an entry's W beams (every member), into the workgroup's LDS rows; the caller's barrier makes them
+// visible.  From the logits: one wave per (member, beam) row, max and log sum exp(x - max) over the V logits.
+template <class P>
+__device__ __forceinline__ void rows_from_logits(const P& pol, typename P::Rows& s, const float* __restrict__ lg, size_t mstride,
+                                                 int W, int V) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int p = wave; p < pol.members() * W; p += 4) {
     const int m = pol.members() > 1 ? p / W : 0, w = p - m * W;
     if (!pol.live(s, m)) continue;
@@ -321,6 +301,60 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
       s.logsum[m * 64 + w] = logf(sum);
     }
   }
+}
+// From the per-chunk partials of beam_stats_kernel: one wave per (member, beam), one lane per chunk (chunks <= 32), partials
+// combined in chunk order so that every workgroup of the entry gets the same bits
+template <class P>
+__device__ __forceinline__ void rows_from_partials(const P& pol, typename P::Rows& s, const float* __restrict__ pmax,
+                                                   const float* __restrict__ psum, int B, int b, int W, int chunks) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int p = wave; p < pol.members() * W; p += 4) {
+    const int m = pol.members() > 1 ? p / W : 0, w = p - m * W;
+    if (!pol.live(s, m)) continue;
+    const size_t o = (((size_t)m * B + b) * W + w) * chunks;
+    const float pm = lane < chunks ? pmax[o + lane] : -INFINITY;
+    const float ps = lane < chunks ? psum[o + lane] : 0.f;
+    const float mx = wave_max(pm);
+    const float term = lane < chunks ? ps * expf(pm - mx) : 0.f;
+    float sum = 0.f;
+    for (int k = 0; k < chunks; ++k) sum += __shfl(term, k, 64);      // fixed order: chunk 0, 1, ...
+    if (lane == 0) {
+      s.mx[m * 64 + w] = mx;
+      s.logsum[m * 64 + w] = logf(sum);
+    }
+  }
+}
+
+// ---- one workgroup per batch entry -----------------------------------------------------------------------------------
+template <class P, class Bn, class Gr>
+__global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict__ logits, P pol, Bn bans, float* __restrict__ log_probs,
+                                                        int32_t* __restrict__ finished, int64_t* __restrict__ lengths,
+                                                        int32_t* __restrict__ word_ids, int32_t* __restrict__ parent_ids,
+                                                        float* __restrict__ scores, int B, int W, int V, int end_id,
+                                                        float lpw, const int32_t* __restrict__ stop, int stop_t, Gr gr) {
+  __shared__ ValIdx sh[256];
+  __shared__ typename P::Rows s;
+  __shared__ int s_sel[64];
+  __shared__ float s_selv[64];
+  __shared__ long long s_len[64];
+  __shared__ typename Gr::Pen pen;
+  if (comic_stopped(stop, stop_t)) return;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const size_t mstride = (size_t)B * W * V;
+  const float* lg = logits + (size_t)b * W * V;
+  const Bn bn = bans.entry(b, W);
+  gr.clear(pen, b, W);
+  // the entry's beam state (W <= 64): loaded first, in flight behind the passes over the logits
+  float lp_w = 0.f;
+  int fin_w = 0;
+  long long len_w = 0;
+  if (tid < W) {
+    lp_w = log_probs[b * W + tid];
+    fin_w = finished[b * W + tid];
+    len_w = lengths[b * W + tid];
+  }
+  pol.begin(s);
+  rows_from_logits(pol, s, lg, mstride, W, V);
   if (tid < W) {
     s.lp[tid] = lp_w;
     s.fin[tid] = fin_w;
@@ -427,7 +461,7 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
   __shared__ int s_sel[64];
   __shared__ typename Gr::Pen pen;
   if (comic_stopped(stop, stop_t)) return;
-  const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const size_t mstride = (size_t)B * W * V;
   const float* lg = logits + (size_t)b * W * V;
   const Bn bn = bans.entry(b, W);
@@ -445,23 +479,7 @@ __global__ __launch_bounds__(256) void beam_chunk_topk_kernel(const float* __res
     fin_w = finished[b * W + tid];
   }
   pol.begin(s);
-  // row constants from the per-chunk partials: one wave per (member, beam), one lane per chunk (chunks <= 32), partials
-  // combined in chunk order so that every workgroup of the entry gets the same bits
-  for (int p = wave; p < pol.members() * W; p += 4) {
-    const int m = pol.members() > 1 ? p / W : 0, w = p - m * W;
-    if (!pol.live(s, m)) continue;
-    const size_t o = (((size_t)m * B + b) * W + w) * chunks;
-    const float pm = lane < chunks ? pmax[o + lane] : -INFINITY;
-    const float ps = lane < chunks ? psum[o + lane] : 0.f;
-    const float mx = wave_max(pm);
-    const float term = lane < chunks ? ps * expf(pm - mx) : 0.f;
-    float sum = 0.f;
-    for (int k = 0; k < chunks; ++k) sum += __shfl(term, k, 64);      // fixed order: chunk 0, 1, ...
-    if (lane == 0) {
-      s.mx[m * 64 + w] = mx;
-      s.logsum[m * 64 + w] = logf(sum);
-    }
-  }
+  rows_from_partials(pol, s, pmax, psum, B, b, W, chunks);
   if (tid < W) {
     s.lp[tid] = lp_w;
     s.fin[tid] = fin_w;
@@ -621,6 +639,355 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
   if (tid < Wg)
     write_beam(b * W + w0 + tid, s_sel[tid], s_selv[tid], Gr::kActive ? s_selt[tid] : s_selv[tid], s_fin, s_len, V, end_id,
                log_probs, finished, lengths, word_ids, parent_ids, scores);
+}
+
+// ---- banks by constraint progress (required words; the rule: include/comic_hip.h, comic_beam_required) ---------------------
+// The W slots of an entry are `banks` banks of Wb = W / banks.  A candidate (w, v) has a destination bank: a finished
+// parent's own bank w / Wb; a live parent's base[w], or the dest of the first of its at most four specials that names v
+// (the per-step table of beam_required.hip).  Bank c takes its Wb best among the candidates of ALL W parents whose
+// destination is c and whose total is finite, under the order of every other step (score descending, flat index ascending),
+// and a slot for which none is left becomes a dead slot.  step_lp, cand_step, the order and write_beam are those of the
+// other steps, so a candidate's score has the same bits here.  Two forms, as the other policies:
+//   beam_step_banks_kernel .. one workgroup per entry: any V, length penalty included
+//   split ................... beam_stats_kernel once, then per bank beam_bank_chunk_kernel (per (chunk, entry): the rows
+//                             whose base is the bank in full minus their specials, of every other live row only the specials
+//                             that lead into the bank) and beam_bank_merge_kernel: 1 + 2 banks launches ordered by the
+//                             stream.  A bank's parents are any of the W slots, so no launch may see the state a bank
+//                             before it wrote: bank 0's chunk launch copies the entry's state into the workspace, and every
+//                             later launch of the step reads that copy.
+constexpr int kSpecials = 4;
+struct BankRows {          // the entry's rows of the per-step table: 2 KB of specials + the bases
+  int base[64];
+  int tok[64 * kSpecials], dst[64 * kSpecials];
+};
+// (every thread; the caller's barrier makes it visible)  A token outside [0, V) is an unused special.
+__device__ __forceinline__ void bank_rows_load(BankRows& t, const int32_t* __restrict__ base, const int32_t* __restrict__ special,
+                                               int b, int W, int V) {
+  for (int i = threadIdx.x; i < W * kSpecials; i += blockDim.x) {
+    const size_t o = ((size_t)b * W * kSpecials + i) * 2;
+    const int tok = special[o];
+    t.tok[i] = (tok >= 0 && tok < V) ? tok : -1;
+    t.dst[i] = special[o + 1];
+  }
+  if ((int)threadIdx.x < W) t.base[threadIdx.x] = base[b * W + threadIdx.x];
+}
+// the destination of candidate v of the LIVE row w
+__device__ __forceinline__ int bank_dest(const BankRows& t, int w, int v) {
+  int d = t.base[w];
+#pragma unroll
+  for (int k = kSpecials - 1; k >= 0; --k)
+    if (t.tok[w * kSpecials + k] == v) d = t.dst[w * kSpecials + k];       // (the first special that names v decides)
+  return d;
+}
+// special k of row w is in use and the first of its row to name its token
+__device__ __forceinline__ bool bank_special_first(const BankRows& t, int w, int k) {
+  const int tok = t.tok[w * kSpecials + k];
+  bool first = tok >= 0;
+  for (int q = 0; q < k; ++q) first = first && t.tok[w * kSpecials + q] != tok;
+  return first;
+}
+// row w is scanned in full for bank c (Wb slots per bank)
+__device__ __forceinline__ bool bank_full_row(const BankRows& t, const int* fin, int w, int Wb, int c) {
+  return fin[w] ? (w / Wb == c) : (t.base[w] == c);
+}
+// a slot no eligible candidate is left for
+__device__ __forceinline__ void write_dead(int o, int slot, long long len, int end_id, float* __restrict__ log_probs,
+                                           int32_t* __restrict__ finished, int64_t* __restrict__ lengths,
+                                           int32_t* __restrict__ word_ids, int32_t* __restrict__ parent_ids,
+                                           float* __restrict__ scores) {
+  word_ids[o] = end_id;
+  parent_ids[o] = slot;
+  scores[o] = -INFINITY;
+  log_probs[o] = -INFINITY;
+  finished[o] = 1;
+  lengths[o] = len;
+}
+
+template <class P, class Bn>
+__global__ __launch_bounds__(256) void beam_step_banks_kernel(const float* __restrict__ logits, P pol, Bn bans, float* __restrict__ log_probs,
+                                                              int32_t* __restrict__ finished, int64_t* __restrict__ lengths,
+                                                              int32_t* __restrict__ word_ids, int32_t* __restrict__ parent_ids,
+                                                              float* __restrict__ scores, const int32_t* __restrict__ base,
+                                                              const int32_t* __restrict__ special, int B, int W, int V, int end_id,
+                                                              float lpw, int banks, const int32_t* __restrict__ stop, int stop_t) {
+  __shared__ ValIdx sh[256];
+  __shared__ typename P::Rows s;
+  __shared__ BankRows tb;
+  __shared__ int s_sel[64];
+  __shared__ float s_selv[64];
+  __shared__ long long s_len[64];
+  if (comic_stopped(stop, stop_t)) return;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const size_t mstride = (size_t)B * W * V;
+  const float* lg = logits + (size_t)b * W * V;
+  const Bn bn = bans.entry(b, W);
+  float lp_w = 0.f;
+  int fin_w = 0;
+  long long len_w = 0;
+  if (tid < W) {
+    lp_w = log_probs[b * W + tid];
+    fin_w = finished[b * W + tid];
+    len_w = lengths[b * W + tid];
+  }
+  pol.begin(s);
+  rows_from_logits(pol, s, lg, mstride, W, V);
+  bank_rows_load(tb, base, special, b, W, V);
+  if (tid < W) {
+    s.lp[tid] = lp_w;
+    s.fin[tid] = fin_w;
+    s_len[tid] = len_w;
+  }
+  __syncthreads();
+  const int Wb = W / banks;
+  for (int c = 0; c < banks; ++c) {
+    const int* taken_sel = s_sel + c * Wb;
+    for (int r = 0; r < Wb; ++r) {
+      float bv = -INFINITY;
+      int bi = kNone;
+      auto consider = [&](int w, int v) {
+        const int f = w * V + v;
+        bool taken = false;
+        for (int q = 0; q < r; ++q) taken |= (taken_sel[q] == f);
+        if (taken) return;
+        float tot = s.lp[w] + cand_step(pol, bn, lg, mstride, f, w, v, end_id, s);
+        if (!(tot > -INFINITY)) return;                 // -inf or NaN: not eligible
+        if (lpw != 0.f) {
+          const long long len = s_len[w] + ((s.fin[w] || v == end_id) ? 0 : 1);
+          tot = tot / powf((5.f + (float)len) / 6.f, lpw);
+        }
+        if (better(tot, f, bv, bi)) {
+          bv = tot;
+          bi = f;
+        }
+      };
+      for (int w = 0; w < W; ++w) {
+        const bool fin = s.fin[w] != 0;
+        if (bank_full_row(tb, s.fin, w, Wb, c)) {
+          for (int v = tid; v < V; v += 256)
+            if (fin || bank_dest(tb, w, v) == c) consider(w, v);
+        } else if (!fin && tid < kSpecials) {
+          if (tb.dst[w * kSpecials + tid] == c && bank_special_first(tb, w, tid)) consider(w, tb.tok[w * kSpecials + tid]);
+        }
+      }
+      const ValIdx best = block_argmax(bv, bi, sh);
+      if (tid == 0) {
+        s_sel[c * Wb + r] = best.i;                     // kNone: a dead slot
+        s_selv[c * Wb + r] = best.v;
+      }
+      __syncthreads();
+    }
+  }
+  if (tid < W) {
+    const int f = s_sel[tid];
+    if (f == kNone) {
+      write_dead(b * W + tid, tid, s_len[tid], end_id, log_probs, finished, lengths, word_ids, parent_ids, scores);
+    } else {
+      const int parent = f / V, word = f - parent * V;
+      const float state = lpw != 0.f ? cand_total(pol, bn, lg, mstride, f, parent, word, end_id, s) : s_selv[tid];
+      write_beam(b * W + tid, f, s_selv[tid], state, s.fin, s_len, V, end_id, log_probs, finished, lengths, word_ids, parent_ids,
+                 scores);
+    }
+  }
+}
+
+// Bank c's chunk launch (no length penalty: the score is the total).  A thread's share of the full rows' columns
+// (nfull * kper values) is formed once in registers when it fits in KLOCAL, as beam_chunk_topk_kernel does; else every
+// round rescans.  The at most 4 W specials of the other live rows are one candidate per thread.
+template <class P, class Bn, int KLOCAL>
+__global__ __launch_bounds__(256) void beam_bank_chunk_kernel(const float* __restrict__ logits, P pol, Bn bans,
+                                                              const float* __restrict__ src_lp, const int32_t* __restrict__ src_fin,
+                                                              const int64_t* __restrict__ src_len, float* __restrict__ snap_lp,
+                                                              int32_t* __restrict__ snap_fin, int64_t* __restrict__ snap_len,
+                                                              const int32_t* __restrict__ base, const int32_t* __restrict__ special,
+                                                              const float* __restrict__ pmax, const float* __restrict__ psum,
+                                                              float* __restrict__ cand_v, int32_t* __restrict__ cand_i, int B,
+                                                              int W, int V, int chunks, int end_id, int banks, int c,
+                                                              const int32_t* __restrict__ stop, int stop_t) {
+  __shared__ ValIdx sh[256];
+  __shared__ ValIdx sh8[8];
+  __shared__ typename P::Rows s;
+  __shared__ BankRows tb;
+  __shared__ int s_sel[64];
+  __shared__ int s_full[64];
+  __shared__ int s_nfull;
+  if (comic_stopped(stop, stop_t)) return;
+  const int ch = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const size_t mstride = (size_t)B * W * V;
+  const float* lg = logits + (size_t)b * W * V;
+  const Bn bn = bans.entry(b, W);
+  float lp_w = 0.f;
+  int fin_w = 0;
+  if (tid < W) {
+    lp_w = src_lp[b * W + tid];
+    fin_w = src_fin[b * W + tid];
+    if (snap_lp && ch == 0) {                           // bank 0: the state every later launch of the step reads
+      snap_lp[b * W + tid] = lp_w;
+      snap_fin[b * W + tid] = fin_w;
+      snap_len[b * W + tid] = src_len[b * W + tid];
+    }
+  }
+  pol.begin(s);
+  rows_from_partials(pol, s, pmax, psum, B, b, W, chunks);
+  bank_rows_load(tb, base, special, b, W, V);
+  if (tid < W) {
+    s.lp[tid] = lp_w;
+    s.fin[tid] = fin_w;
+  }
+  __syncthreads();
+  const int Wb = W / banks;
+  if (tid == 0) {
+    int n = 0;
+    for (int w = 0; w < W; ++w)
+      if (bank_full_row(tb, s.fin, w, Wb, c)) s_full[n++] = w;
+    s_nfull = n;
+  }
+  __syncthreads();
+  const int nfull = s_nfull;
+  const int per = (V + chunks - 1) / chunks, v0 = ch * per, v1 = min(V, v0 + per), nv = max(0, v1 - v0);
+  const size_t out = ((size_t)b * chunks + ch) * Wb;
+  // total of candidate (w, v), kNone when it is not eligible for the bank
+  auto eligible = [&](int w, int v, float& tot) {
+    if (!s.fin[w] && bank_dest(tb, w, v) != c) return kNone;
+    const int f = w * V + v;
+    tot = cand_total(pol, bn, lg, mstride, f, w, v, end_id, s);
+    return tot > -INFINITY ? f : kNone;                 // -inf or NaN: not eligible
+  };
+  // the special this thread owns: special tid % 4 of row tid / 4, when its row is not scanned in full
+  float sv = -INFINITY;
+  int si = kNone;
+  if (tid < W * kSpecials) {
+    const int w = tid / kSpecials, k = tid - w * kSpecials;
+    if (!s.fin[w] && tb.base[w] != c && tb.dst[tid] == c && bank_special_first(tb, w, k)) {
+      const int v = tb.tok[tid];
+      if (v >= v0 && v < v1) si = eligible(w, v, sv);
+      if (si == kNone) sv = -INFINITY;
+    }
+  }
+  const int kper = (nv + 255) >> 8;                     // columns per thread and row
+  if (nfull * kper <= KLOCAL) {
+    float tv[KLOCAL];
+    int ti[KLOCAL];
+    int li = 0, k = 0;
+#pragma unroll
+    for (int e = 0; e < KLOCAL; ++e) {
+      tv[e] = -INFINITY;
+      ti[e] = kNone;
+      const int v = v0 + tid + 256 * k;
+      if (li < nfull && v < v1) {
+        ti[e] = eligible(s_full[li], v, tv[e]);
+        if (ti[e] == kNone) tv[e] = -INFINITY;
+      }
+      if (++k == kper) {
+        k = 0;
+        ++li;
+      }
+    }
+    for (int r = 0; r < Wb; ++r) {
+      float bv = si != kNone ? sv : -INFINITY;
+      int bi = si;
+#pragma unroll
+      for (int e = 0; e < KLOCAL; ++e)
+        if (ti[e] != kNone && better(tv[e], ti[e], bv, bi)) {
+          bv = tv[e];
+          bi = ti[e];
+        }
+      const ValIdx best = block_argmax_1b(bv, bi, sh8, r & 1);
+#pragma unroll
+      for (int e = 0; e < KLOCAL; ++e)
+        if (ti[e] == best.i) ti[e] = kNone;             // taken (flat indices are unique; kNone marks "none")
+      if (si == best.i) si = kNone;
+      if (tid == 0) {
+        cand_v[out + r] = best.v;
+        cand_i[out + r] = best.i;
+      }
+    }
+    return;
+  }
+  const int total = nfull * nv;
+  for (int r = 0; r < Wb; ++r) {
+    float bv = -INFINITY;
+    int bi = kNone;
+    if (si != kNone) {
+      bool taken = false;
+      for (int q = 0; q < r; ++q) taken |= (s_sel[q] == si);
+      if (!taken) {
+        bv = sv;
+        bi = si;
+      }
+    }
+    for (int j = tid; j < total; j += 256) {
+      const int li = j / nv, w = s_full[li], v = v0 + (j - li * nv);
+      const int f = w * V + v;
+      bool taken = false;
+      for (int q = 0; q < r; ++q) taken |= (s_sel[q] == f);
+      if (taken) continue;
+      float tot;
+      if (eligible(w, v, tot) != kNone && better(tot, f, bv, bi)) {
+        bv = tot;
+        bi = f;
+      }
+    }
+    const ValIdx best = block_argmax(bv, bi, sh);
+    if (tid == 0) {
+      s_sel[r] = best.i;                                // kNone when the chunk has fewer than r + 1 candidates
+      cand_v[out + r] = best.v;
+      cand_i[out + r] = best.i;
+    }
+    __syncthreads();
+  }
+}
+
+// Bank c's merge: the Wb best of the chunks' lists into the bank's slots, on the state copy of the step's first launch.
+__global__ __launch_bounds__(256) void beam_bank_merge_kernel(const float* __restrict__ cand_v, const int32_t* __restrict__ cand_i,
+                                                              const int32_t* __restrict__ snap_fin,
+                                                              const int64_t* __restrict__ snap_len, float* __restrict__ log_probs,
+                                                              int32_t* __restrict__ finished, int64_t* __restrict__ lengths,
+                                                              int32_t* __restrict__ word_ids, int32_t* __restrict__ parent_ids,
+                                                              float* __restrict__ scores, int W, int V, int chunks, int end_id,
+                                                              int banks, int c, const int32_t* __restrict__ stop, int stop_t) {
+  __shared__ ValIdx sh[256];
+  __shared__ int s_fin[64], s_sel[64];
+  __shared__ float s_selv[64];
+  __shared__ long long s_len[64];
+  if (comic_stopped(stop, stop_t)) return;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (tid < W) {                       // (W <= 64)
+    s_fin[tid] = snap_fin[b * W + tid];
+    s_len[tid] = snap_len[b * W + tid];
+  }
+  __syncthreads();
+  const int Wb = W / banks, n = chunks * Wb;
+  const float* cv = cand_v + (size_t)b * n;
+  const int32_t* ci = cand_i + (size_t)b * n;
+  for (int r = 0; r < Wb; ++r) {
+    float bv = -INFINITY;
+    int bi = kNone;
+    for (int j = tid; j < n; j += 256) {
+      const int f = ci[j];
+      if (f == kNone) continue;
+      bool taken = false;
+      for (int q = 0; q < r; ++q) taken |= (s_sel[q] == f);
+      if (taken) continue;
+      if (better(cv[j], f, bv, bi)) {
+        bv = cv[j];
+        bi = f;
+      }
+    }
+    const ValIdx best = block_argmax(bv, bi, sh);
+    if (tid == 0) {
+      s_sel[r] = best.i;                                // kNone: a dead slot
+      s_selv[r] = best.v;
+    }
+    __syncthreads();
+  }
+  if (tid < Wb) {
+    const int slot = c * Wb + tid, o = b * W + slot;
+    if (s_sel[tid] == kNone)
+      write_dead(o, slot, s_len[slot], end_id, log_probs, finished, lengths, word_ids, parent_ids, scores);
+    else
+      write_beam(o, s_sel[tid], s_selv[tid], s_selv[tid], s_fin, s_len, V, end_id, log_probs, finished, lengths, word_ids,
+                 parent_ids, scores);
+  }
 }
 
 thread_local int g_ens_step_path = 0;
@@ -836,4 +1203,92 @@ extern "C" int comic_beam_step_sampled(const float* logits, const float* weights
   const Samples smp{sampling->seed_dev, 1.0f / sampling->temperature, t, nullptr};
   return ens_step("beam_step_sampled", logits, weights, n_models, log_probs, finished, lengths, word_ids, parent_ids, scores,
                   B, W, V, end_id, 0.f, bits, words, nullptr, workspace, workspace_bytes, stream, &smp);
+}
+
+// ---- banks by constraint progress: the launcher and the raw operator ---------------------------------------------------------
+// executor-internal: the bytes of the banked step's workspace -- the split form's, then the state copy [B * W] of
+// (int64 length, float log-probability, int32 finished)
+int64_t comic_beam_step_required_bytes(int n, int B, int W, int chunks) {
+  return ((comic_beam_step_split_bytes(n, B, W, chunks) + 15) & ~(int64_t)15) + (int64_t)B * W * 16;
+}
+
+namespace {
+template <class P, class Bn>
+int beam_step_banks_launch(const P& pol, const Bn& bans, int n, const float* logits, float* log_probs, int32_t* finished,
+                           int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, const int32_t* base,
+                           const int32_t* special, int banks, int B, int W, int V, int end_id, float lpw, void* ws,
+                           int64_t ws_bytes, hipStream_t st, int* path) {
+  const int chunks = comic_beam_step_chunks(B, V);
+  const bool split = lpw == 0.f && (long)W * V >= 8192 && chunks >= 2 && ws &&
+                     ws_bytes >= comic_beam_step_required_bytes(n, B, W, chunks);
+  if (path) *path = split ? 1 : 0;
+  if (!split) {
+    hipLaunchKernelGGL((beam_step_banks_kernel<P, Bn>), dim3(B), dim3(256), 0, st, logits, pol, bans, log_probs, finished, lengths,
+                       word_ids, parent_ids, scores, base, special, B, W, V, end_id, lpw, banks, g_comic_stop.p, g_comic_stop.t);
+    COMIC_LAUNCH_CHECK("beam_step_required");
+    return 0;
+  }
+  float* pmax = (float*)ws;
+  float* psum = pmax + (size_t)n * B * W * chunks;
+  float* cand_v = psum + (size_t)n * B * W * chunks;
+  int32_t* cand_i = (int32_t*)(cand_v + (size_t)B * chunks * W);
+  char* snap = (char*)ws + ((comic_beam_step_split_bytes(n, B, W, chunks) + 15) & ~(int64_t)15);
+  int64_t* snap_len = (int64_t*)snap;
+  float* snap_lp = (float*)(snap_len + (size_t)B * W);
+  int32_t* snap_fin = (int32_t*)(snap_lp + (size_t)B * W);
+  hipLaunchKernelGGL(beam_stats_kernel<P>, dim3(chunks, W, n * B), dim3(256), 0, st, logits, pol, pmax, psum, B, W, V, chunks,
+                     g_comic_stop.p, g_comic_stop.t);
+  const int per = (V + chunks - 1) / chunks, kper = (per + 255) / 256;
+  for (int c = 0; c < banks; ++c) {
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(chunks, B), dim3(256), 0, st, logits, pol, bans,
+                         c == 0 ? (const float*)log_probs : (const float*)snap_lp,
+                         c == 0 ? (const int32_t*)finished : (const int32_t*)snap_fin,
+                         c == 0 ? (const int64_t*)lengths : (const int64_t*)snap_len, c == 0 ? snap_lp : (float*)nullptr,
+                         c == 0 ? snap_fin : (int32_t*)nullptr, c == 0 ? snap_len : (int64_t*)nullptr, base, special,
+                         (const float*)pmax, (const float*)psum, cand_v, cand_i, B, W, V, chunks, end_id, banks, c,
+                         g_comic_stop.p, g_comic_stop.t);
+    };
+    // (the capacity by the most rows a bank can scan in full, W; a bank with more than fit rescans)
+    if (W * kper <= 16) launch(beam_bank_chunk_kernel<P, Bn, 16>);
+    else launch(beam_bank_chunk_kernel<P, Bn, 40>);
+    hipLaunchKernelGGL(beam_bank_merge_kernel, dim3(B), dim3(256), 0, st, (const float*)cand_v, (const int32_t*)cand_i,
+                       (const int32_t*)snap_fin, (const int64_t*)snap_len, log_probs, finished, lengths, word_ids, parent_ids,
+                       scores, W, V, chunks, end_id, banks, c, g_comic_stop.p, g_comic_stop.t);
+  }
+  COMIC_LAUNCH_CHECK("beam_step_required (split)");
+  return 0;
+}
+}  // namespace
+
+extern "C" int64_t comic_beam_step_required_workspace(int n_models, int B, int W, int V) {
+  if (n_models < 1 || n_models > kEnsMax || B <= 0 || W <= 0 || V <= 0) return -1;
+  return comic_beam_step_required_bytes(n_models, B, W, comic_beam_step_chunks(B, V));
+}
+
+extern "C" int comic_beam_step_required(const float* logits, const float* weights, int n_models, float* log_probs,
+                                        int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids,
+                                        float* scores, int B, int W, int V, int end_id, float length_penalty_weight,
+                                        const uint32_t* bits, int words, const int32_t* base, const int32_t* special, int banks,
+                                        void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "beam_step_required";
+  COMIC_REQUIRE(logits && weights && log_probs && finished && lengths && word_ids && parent_ids && scores && base && special,
+                "%s: null pointer", who);
+  COMIC_REQUIRE(n_models >= 1 && n_models <= kEnsMax, "%s: 1 to %d members (got %d)", who, kEnsMax, n_models);
+  COMIC_REQUIRE(B > 0 && W >= 1 && W <= 64, "%s: beam width must be in [1,64] (got %d)", who, W);
+  COMIC_REQUIRE(V > 0 && W <= V && (long)W * V < (1L << 31), "%s: beam*V too large or beam > V", who);
+  COMIC_REQUIRE((long)n_models * B <= 65535, "%s: members * batch too large", who);
+  COMIC_REQUIRE(end_id >= 0 && end_id < V, "%s: end_id %d outside the vocabulary", who, end_id);
+  COMIC_REQUIRE(banks >= 2 && banks <= 17, "%s: banks must be in [2,17] (got %d)", who, banks);
+  COMIC_REQUIRE(W % banks == 0, "%s: banks %d does not divide the beam width %d", who, banks, W);
+  COMIC_REQUIRE(!bits || words == (V + 31) / 32, "%s: %d mask words for a vocabulary of %d", who, words, V);
+  Ensemble pol{};
+  if (int rc = comic_ensemble_policy(who, weights, n_models, &pol)) return rc;
+  if (bits)
+    return beam_step_banks_launch(pol, Bans{bits, words}, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids,
+                                  scores, base, special, banks, B, W, V, end_id, length_penalty_weight, workspace,
+                                  workspace_bytes, (hipStream_t)stream, &g_ens_step_path);
+  return beam_step_banks_launch(pol, NoBans{}, n_models, logits, log_probs, finished, lengths, word_ids, parent_ids, scores, base,
+                                special, banks, B, W, V, end_id, length_penalty_weight, workspace, workspace_bytes,
+                                (hipStream_t)stream, &g_ens_step_path);
 }

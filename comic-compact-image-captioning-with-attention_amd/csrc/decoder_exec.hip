@@ -90,6 +90,7 @@ int comic_beam_step_ws(const float* logits, float* log_probs, int32_t* finished,
 int64_t comic_beam_step_split_bytes(int n, int B, int W, int chunks);
 int comic_beam_groups_check(const comic_beam_groups* g, const char* who, int W, int V);
 int comic_beam_sampling_check(const comic_beam_sampling* s, const char* who, float lpw, int W);
+int64_t comic_beam_step_required_bytes(int n, int B, int W, int chunks);
 // beam_truncate.hip
 int comic_beam_truncation_check(const comic_beam_truncation* tr, const char* who, int V, bool whole);
 // beam_bans.hip
@@ -98,6 +99,14 @@ int comic_beam_constraints_check(const comic_beam_constraints* c, const char* wh
 int comic_beam_bans_launch(const int32_t* prev_words, const int32_t* prev_parents, const int32_t* finished,
                            const int64_t* lengths, int32_t* hist, uint32_t* bits, int t, int B, int W, int V, int max_steps,
                            int end_id, const comic_beam_constraints* c, hipStream_t st);
+// beam_required.hip
+int comic_beam_required_check(const comic_beam_required* q, const char* who, int W, int V, int end_id, int max_steps,
+                              const comic_beam_constraints* cons);
+int comic_beam_required_launch(const int32_t* prev_words, const int32_t* prev_parents, const int32_t* req, int32_t* hist,
+                               int32_t* base, int32_t* special, const comic_beam_required* q, int t, int B, int W, int V,
+                               int max_steps, int write_hist, hipStream_t st);
+int comic_beam_required_init_launch(const int32_t* req, float* log_probs, int32_t* finished, int64_t* lengths, int B, int W,
+                                    const comic_beam_required* q, hipStream_t st);
 // decode.hip
 int comic_ens_gather_state(const float* c, const float* h, const float* att, const int32_t* parent, float* c_out,
                            float* h_out, float* att_out, int R, int W, int D, int A, hipStream_t st);
@@ -2081,6 +2090,7 @@ struct EnsBufs {
   int32_t* ban_hist;               // [2][R][max_steps] token histories in beam order (constrained only)
   void* trunc_ws;                  // comic_beam_truncate's scratch rows (truncated only; none while a row fits in LDS)
   int64_t trunc_bytes;
+  int32_t *req_base, *req_special; // [R], [R][4][2]: the per-step table of beam_required.hip (required words only)
   size_t bytes;
   bool ok;
 };
@@ -2088,8 +2098,10 @@ struct EnsBufs {
 int64_t ens_step_ws_bound(int n, int rows) { return comic_beam_step_split_bytes(n, rows, 1, 32); }
 // sampled: the step's lists carry every slot's total too (comic_beam_step_sampled_workspace): rows * chunks words more
 // truncated: the masks even without constraints, and the truncation's scratch rows
+// required words (req_steps > 0): the banked step's state copy, the per-step table, and the histories unless the
+// constraints keep them already
 EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64_t bytes, int ban_steps = 0,
-                  bool sampled = false, bool truncated = false) {
+                  bool sampled = false, bool truncated = false, int req_steps = 0) {
   EnsBufs e{};
   size_t off = 0;
   e.ok = true;
@@ -2105,6 +2117,7 @@ EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64
   e.log_probs = w.take<float>(R);
   e.ids = w.take<int32_t>(R);
   e.step_bytes = ens_step_ws_bound(n, R) + (sampled ? (int64_t)R * 32 * 4 : 0);
+  if (req_steps > 0) e.step_bytes = comic_beam_step_required_bytes(n, R, 1, 32);
   e.step_ws = w.take<char>((size_t)e.step_bytes);
   if (ban_steps > 0) {
     e.bits = w.take<uint32_t>((size_t)R * ((descs[0].V + 31) / 32));
@@ -2114,6 +2127,11 @@ EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64
     if (ban_steps <= 0) e.bits = w.take<uint32_t>((size_t)R * ((descs[0].V + 31) / 32));
     e.trunc_bytes = std::max<int64_t>(0, comic_beam_truncate_workspace(n, R, 1, descs[0].V));
     if (e.trunc_bytes > 0) e.trunc_ws = w.take<char>((size_t)e.trunc_bytes);
+  }
+  if (req_steps > 0) {
+    e.req_base = w.take<int32_t>(R);
+    e.req_special = w.take<int32_t>((size_t)R * 8);
+    if (ban_steps <= 0) e.ban_hist = w.take<int32_t>((size_t)2 * R * req_steps);
   }
   e.ok = e.ok && w.ok;
   e.bytes = off + w.off;
@@ -2145,7 +2163,8 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
                              int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
                              float* const* attn_hists, int32_t* steps_executed, const comic_beam_constraints* cons,
                              const comic_beam_groups* grp, const comic_beam_sampling* smp, void* workspace,
-                             int64_t workspace_bytes, void* stream, const comic_beam_truncation* trc = nullptr) {
+                             int64_t workspace_bytes, void* stream, const comic_beam_truncation* trc = nullptr,
+                             const comic_beam_required* rqd = nullptr, const int32_t* req = nullptr) {
   COMIC_REQUIRE(descs && params && fms && im_embeds && weights && step_ids && parent_ids && scores && lengths && finished &&
                     steps_executed && workspace,
                 "beam_ensemble: null pointer");
@@ -2164,8 +2183,10 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
   if (grp) RC(comic_beam_groups_check(grp, "beam_diverse", W, V));
   if (smp) RC(comic_beam_sampling_check(smp, trc ? "beam_truncated" : "beam_sampled", descs[0].length_penalty_weight, W));
   if (trc) RC(comic_beam_truncation_check(trc, "beam_truncated", V, true));
+  if (rqd) RC(comic_beam_required_check(rqd, "beam_required", W, V, descs[0].end_id, max_steps, cons));
   hipStream_t st = (hipStream_t)stream;
-  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, cons ? max_steps : 0, smp != nullptr, trc != nullptr);
+  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, cons ? max_steps : 0, smp != nullptr, trc != nullptr,
+                        rqd ? max_steps : 0);
   COMIC_REQUIRE(L.ok && (int64_t)L.bytes <= workspace_bytes, "beam_ensemble: workspace too small");
   g_splitk_ws = L.m[0].splitk;               // members run back to back on the one stream: one split-K scratch serves all
   const float lpw = descs[0].length_penalty_weight;
@@ -2179,9 +2200,13 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
     RC(beam_member_begin(d, p, fms[m], im_embeds[m], B, W, ws, st, e));
     e.w_o = aligned_w_o(d, p, ws.wo_pad, &e.ld_wo, st);
   }
-  // (groups: row i starts live when i % Wg == 0, the first slot of its group; sampling: every row)
-  hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, L.log_probs, finished, lengths, R,
-                     smp ? 1 : grp ? W / grp->groups : W);
+  // (groups: row i starts live when i % Wg == 0, the first slot of its group; sampling: every row; required words: the
+  // first slot of the bank that the entry's padding rows select)
+  if (rqd)
+    RC(comic_beam_required_init_launch(req, L.log_probs, finished, lengths, B, W, rqd, st));
+  else
+    hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, L.log_probs, finished, lengths, R,
+                       smp ? 1 : grp ? W / grp->groups : W);
   hipLaunchKernelGGL(fill_i32_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, L.ids, descs[0].start_id, (long)R);
   hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(64), 0, st, steps_executed, max_steps, 1L);
   COMIC_LAUNCH_CHECK("beam_ensemble init");
@@ -2230,7 +2255,14 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
     if (trc)
       RC(comic_beam_truncate(L.logits, weights, n, finished, L.bits, (V + 31) / 32, B, W, V, smp->temperature, trc,
                              cons ? 1 : 0, L.trunc_ws, L.trunc_bytes, (void*)st));
-    if (smp) {
+    if (rqd) {
+      // (with constraints the ban launch above has advanced the ONE pair of histories; this launch only reads them)
+      RC(comic_beam_required_launch(t == 0 ? nullptr : (const int32_t*)ids_in, par_in, req, L.ban_hist, L.req_base,
+                                    L.req_special, rqd, t, B, W, V, max_steps, cons ? 0 : 1, st));
+      RC(comic_beam_step_required(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
+                                  B, W, V, descs[0].end_id, lpw, cons ? L.bits : nullptr, (V + 31) / 32, L.req_base,
+                                  L.req_special, rqd->n_words * rqd->stride + 1, L.step_ws, L.step_bytes, (void*)st));
+    } else if (smp) {
       RC(comic_beam_step_sampled(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
                                  B, W, V, descs[0].end_id, (cons || trc) ? L.bits : nullptr, (V + 31) / 32, smp, t, L.step_ws,
                                  L.step_bytes, (void*)st));
@@ -2333,4 +2365,28 @@ extern "C" int comic_decoder_beam_truncated(const comic_decoder_desc* descs, con
   return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
                            lengths, finished, attn_hists, steps_executed, constraints, nullptr, sampling, workspace,
                            workspace_bytes, stream, truncation);
+}
+
+extern "C" int64_t comic_decoder_beam_required_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                         int max_steps, int constrained) {
+  if (max_steps <= 0 || comic_decoder_beam_ensemble_workspace(descs, n_models, rows, max_steps) < 0) return -1;
+  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0, constrained ? max_steps : 0, false, false, max_steps).bytes;
+}
+
+extern "C" int comic_decoder_beam_required(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                           const float* const* fms, const float* const* im_embeds, const float* weights,
+                                           int n_models, int B, int W, int max_steps,
+                                           const comic_beam_constraints* constraints, const comic_beam_groups* groups,
+                                           const comic_beam_sampling* sampling, const comic_beam_required* required,
+                                           const int32_t* req, int32_t* step_ids, int32_t* parent_ids, float* scores,
+                                           int64_t* lengths, int32_t* finished, float* const* attn_hists,
+                                           int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream) {
+  COMIC_REQUIRE(required, "beam_required: null required");
+  COMIC_REQUIRE(req, "beam_required: null req table");
+  COMIC_REQUIRE(!groups || groups->groups <= 1, "beam_required: groups = %d does not combine with required words",
+                groups ? groups->groups : 0);
+  COMIC_REQUIRE(!sampling, "beam_required: sampling does not combine with required words");
+  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
+                           lengths, finished, attn_hists, steps_executed, constraints, nullptr, nullptr, workspace,
+                           workspace_bytes, stream, nullptr, required, req);
 }

@@ -12,7 +12,9 @@ is a single fused kernel and the data-parallel gradient exchange is a single all
 from __future__ import annotations
 
 import ctypes as C
+import json
 import math
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -430,6 +432,177 @@ def groups_dir_suffix(c):
     if g is None and d is None:
         return ''
     return '_grp%d_div%g' % (int(1 if g is None else g), float(0.0 if d is None else d))
+
+
+class BeamRequired:
+    """Beam search with required words (comic_beam_required; Anderson et al. 2017, the bank form of Post & Vilar 2018;
+    extends rnn_decoder_beam_search, ops_rnn.py:49-112).  ids: int32 [B, C, S], -1 padded: row (b, q) is the S tokens of
+    required word q of image b (S = 1 for word tokens, the radix word length for radix tokens), or all -1.  The beam is
+    split into C*S + 1 banks by how much of the set a hypothesis has produced; slot c * (beam / banks) of a result is bank
+    c's best, and the caption is the best of the highest bank that holds a finished-scoring hypothesis.  Hashable by
+    (C, S) only: the table lives in device memory and is written in front of every launch or replay, so decode contexts
+    and captured graphs are shared across tables."""
+    MAX_WORDS, MAX_STRIDE = 4, 4
+
+    def __init__(self, ids):
+        self.ids = np.ascontiguousarray(np.asarray(ids, np.int32))
+        if self.ids.ndim != 3:
+            raise ValueError('required: ids must be [B, n_words, stride], got shape %r' % (self.ids.shape,))
+        self.n_words, self.stride = int(self.ids.shape[1]), int(self.ids.shape[2])
+
+    def key(self):
+        return (self.n_words, self.stride)
+
+    def __eq__(self, other):
+        return isinstance(other, BeamRequired) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'BeamRequired(n_words=%d, stride=%d, images=%d)' % (self.n_words, self.stride, self.ids.shape[0])
+
+    @property
+    def active(self):
+        return True
+
+    @property
+    def banks(self):
+        return self.n_words * self.stride + 1
+
+    def ctx_key(self):
+        return ('required',) + self.key()
+
+    def check(self, spec, beam, batch=None, max_steps=None, constraints=None, groups=None, sampling=None):
+        """The rules of the C side and of the table, on the host before any GPU call; raises ValueError naming the field."""
+        V, beam = int(spec.V), int(beam)
+        if not 1 <= self.n_words <= self.MAX_WORDS:
+            raise ValueError('required: n_words must be in [1,%d], got %d' % (self.MAX_WORDS, self.n_words))
+        if not 1 <= self.stride <= self.MAX_STRIDE:
+            raise ValueError('required: stride must be in [1,%d], got %d' % (self.MAX_STRIDE, self.stride))
+        if beam % self.banks or not 1 <= beam <= 64:
+            raise ValueError('required: %d banks (n_words %d * stride %d + 1) do not divide the beam width %d'
+                             % (self.banks, self.n_words, self.stride, beam))
+        if batch is not None and self.ids.shape[0] != int(batch):
+            raise ValueError('required: the table holds %d images, the batch %d' % (self.ids.shape[0], int(batch)))
+        if V > 65536:
+            raise ValueError('required: V = %d exceeds 65536' % V)
+        pad = self.ids[:, :, 0] < 0
+        if ((self.ids < 0) != pad[:, :, None]).any():
+            raise ValueError('required: a word is -1 in all of its tokens or in none')
+        if (self.ids >= V).any():
+            raise ValueError('required: token %d is outside the vocabulary of %d' % (int(self.ids.max()), V))
+        if (self.ids == spec.end_id).any():
+            raise ValueError('required: end_id %d cannot be required' % spec.end_id)
+        if groups is not None and groups.groups > 1:
+            raise ValueError('required words do not combine with beam groups (groups=%d)' % groups.groups)
+        if sampling is not None and sampling.active:
+            raise ValueError('required words do not combine with sampling')
+        if constraints is not None and constraints.active and max_steps is not None:
+            need = beam + len(constraints.suppress) + 1 + int(max_steps) + self.MAX_WORDS
+            if V < need:
+                raise ValueError('V = %d is too small: beam %d + %d suppress + 1 + max_steps %d + %d required = %d candidates '
+                                 'are needed' % (V, beam, len(constraints.suppress), max_steps, self.MAX_WORDS, need))
+
+    def c_struct(self):
+        r = L.BeamRequired()
+        r.n_words, r.stride = self.n_words, self.stride
+        return r
+
+    def result(self, last_scores):
+        """(best_slot [B], met [B]) from the last executed step's scores [B, W]: the first slot of the highest bank whose
+        first slot has a finite score, and the number of required words (padding included) that bank stands for."""
+        sc = np.asarray(last_scores)
+        Wb = sc.shape[1] // self.banks
+        ok = np.isfinite(sc[:, ::Wb])                                            # [B, banks]
+        bank = np.where(ok.any(axis=1), self.banks - 1 - np.argmax(ok[:, ::-1], axis=1), 0)
+        return (bank * Wb).astype(np.int64), (bank // self.stride).astype(np.int64)
+
+
+def required_image_key(filename):
+    """The key of an image in --infer_require_file besides its file name: the image_id infer_fn derives from the name
+    (the COCO number, or the base name without `.jpg` for names that hold an `@`), as a string; None when it has none."""
+    import re
+    image_id = filename.replace('.jpg', '')
+    if '@' in image_id:
+        return os.path.basename(image_id)
+    found = re.findall(r'(?<=_)\d+', image_id)
+    return str(int(found[0])) if found else None
+
+
+def required_from_config(c, filenames=None):
+    """The required words a configuration asks for (infer_require_file, infer_require_words), or None when it names no
+    file.  The file is JSON: image file name (with or without its directory) or image_id -> list of words.  Words map
+    through wtoi for `word` tokens and through the radix encoding for `radix` tokens (`char` tokens are refused); words
+    outside the vocabulary, <GO> / <EOS> / <PAD>, repeats and words beyond C = infer_require_words (default: the longest list
+    in the file, at most 4) are dropped and reported.  infer_beam_size must be a multiple of C*S + 1.
+    filenames None: the checks alone -> dict(n_words, stride, banks).  Else -> dict(n_words, stride, banks, required (a
+    BeamRequired over all the images, in order), words, dropped (lists of words per image)); one summary line is printed."""
+    path = getattr(c, 'infer_require_file', None)
+    if not path:
+        return None
+    if c.token_type == 'char':
+        raise ValueError('infer_require_file: required words need `word` or `radix` tokens, not `char`')
+    with open(path) as f:
+        table = json.load(f)
+    if not isinstance(table, dict) or not all(isinstance(v, list) for v in table.values()):
+        raise ValueError('infer_require_file: %s must hold a JSON object of image -> list of words' % path)
+    C_ = getattr(c, 'infer_require_words', None)
+    if C_ is None:
+        C_ = max(1, min(BeamRequired.MAX_WORDS, max([len(v) for v in table.values()] or [1])))
+    C_ = int(C_)
+    if not 1 <= C_ <= BeamRequired.MAX_WORDS:
+        raise ValueError('infer_require_words must be in [1,%d], got %d' % (BeamRequired.MAX_WORDS, C_))
+    wtoi = getattr(c, 'wtoi', None)
+    if wtoi is None:                  # before the input manager has read the vocabulary: the same file
+        with open(os.path.join(c.dataset_dir, 'captions', c.dataset_file_pattern.format('wtoi')) + '.json') as f:
+            wtoi = json.load(f)
+    S = len(number_to_base(len(wtoi), c.radix_base)) if c.token_type == 'radix' else 1
+    if S > BeamRequired.MAX_STRIDE:
+        raise ValueError('infer_require_file: a radix word of %d tokens exceeds %d' % (S, BeamRequired.MAX_STRIDE))
+    banks = C_ * S + 1
+    if int(c.infer_beam_size) % banks:
+        raise ValueError('infer_beam_size %d is no multiple of %d (infer_require_words %d * %d tokens per word + 1 banks)'
+                         % (int(c.infer_beam_size), banks, C_, S))
+    out = dict(n_words=C_, stride=S, banks=banks)
+    if filenames is None:
+        return out
+    if c.token_type == 'radix':
+        from .ops import build_radix_wtoi
+        enc = build_radix_wtoi(wtoi, c.radix_base)
+    else:
+        enc = {w: [int(i)] for w, i in wtoi.items()}
+    ids = np.full((len(filenames), C_, S), -1, np.int32)
+    words, dropped = [], []
+    for k, f in enumerate(filenames):
+        asked = None
+        for key in (f, os.path.basename(f), required_image_key(f)):
+            if key is not None and key in table:
+                asked = table[key]
+                break
+        keep, drop = [], []
+        for w in asked or []:
+            w = str(w)
+            if w in ('<GO>', '<EOS>', '<PAD>') or w not in enc or w in keep or len(keep) == C_:
+                drop.append(w)
+            else:
+                ids[k, len(keep)] = enc[w]
+                keep.append(w)
+        words.append(keep)
+        dropped.append(drop)
+    print('INFO: required words: %d of %d images name words; %d words kept, %d dropped (outside the vocabulary, repeated '
+          'or beyond %d per image)' % (sum(1 for w in words if w), len(filenames), sum(len(w) for w in words),
+                                       sum(len(d) for d in dropped), C_))
+    out.update(required=BeamRequired(ids), words=words, dropped=dropped)
+    return out
+
+
+def required_dir_suffix(c):
+    """'_req{C}_{stem of the file}' when the configuration names infer_require_file, else ''."""
+    path = getattr(c, 'infer_require_file', None)
+    if not path:
+        return ''
+    return '_req%d_%s' % (required_from_config(c)['n_words'], os.path.splitext(os.path.basename(path))[0])
 
 
 class BeamSampling:
@@ -1158,7 +1331,7 @@ class Decoder:
         return fetch
 
     def beam_search(self, fm, im_embed, beam, max_steps, want_attention=True, use_graph=True, length_penalty_weight=0.0,
-                    constraints=None, groups=None, sampling=None, image_base=0, truncation=None):
+                    constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None):
         """rnn_decoder_beam_search (ops_rnn.py:49-112).  Returns predicted_ids [T,B,W] (after
         gather_tree), scores [T,B,W] (with length_penalty_weight != 0: the penalised scores the beams were ranked by,
         BeamSearchDecoder's `scores` output), the raw step/parent ids and, unless want_attention=False, the
@@ -1178,9 +1351,16 @@ class Decoder:
         truncation: a BeamTruncation; an active one (with active sampling: ValueError otherwise) restricts every draw to the
         top_k likeliest tokens and / or the top_p nucleus through comic_decoder_beam_truncated.  `scores` / `log_probs` stay
         the model's own unperturbed, untempered, UNTRUNCATED log p(caption | image) -- Decoder.score reproduces them -- not
-        the log-probability under the truncated distribution.  None / inactive: today's path, call for call."""
+        the log-probability under the truncated distribution.  None / inactive: today's path, call for call.
+        required: a BeamRequired (one row of words per image); decodes through comic_decoder_beam_required, alone or with
+        constraints and a length penalty (not with groups or sampling: ValueError).  Slot c * (beam / banks) of
+        predicted_ids and scores is bank c's best; the result gains `banks`, `best_slot` [B] (the caption's slot: the
+        highest bank that holds a hypothesis) and `met` [B] (the required words that bank stands for, padding included),
+        and `log_probs` [B,W], the final unpenalised log-probabilities.  None: today's path."""
         if truncation is not None:
             truncation.check(sampling)
+        if required is not None:
+            required.check(self.spec, beam, fm.shape[0], max_steps, constraints, groups, sampling)
         constrained = constraints is not None and constraints.active
         grouped = groups is not None and groups.active
         sampled = sampling is not None and sampling.active
@@ -1188,7 +1368,7 @@ class Decoder:
             groups.check(beam, self.spec.V)
         if sampling is not None:
             sampling.check(beam, length_penalty_weight, groups)
-        if constrained or grouped or sampled:
+        if constrained or grouped or sampled or required is not None:
             if constrained:
                 constraints.check(self.spec, beam, max_steps)
             ens = self.__dict__.get('_self_ensemble')
@@ -1196,7 +1376,7 @@ class Decoder:
                 ens = self._self_ensemble = EnsembleDecoder([self])
             return ens.beam_search(fm, im_embed, beam, max_steps, want_attention=want_attention, use_graph=use_graph,
                                    length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
-                                   sampling=sampling, image_base=image_base, truncation=truncation)
+                                   sampling=sampling, image_base=image_base, truncation=truncation, required=required)
         torch, s = self.torch, self.spec
         B, W = fm.shape[0], beam
         # (a non-zero length penalty is another captured graph: the weight is baked into the step kernel's arguments)
@@ -1301,12 +1481,14 @@ class EnsembleDecoder:
         self.torch, self.lib, self.device = decoders[0].torch, decoders[0].lib, decoders[0].device
         self._ctxs = {}
 
-    def _ctx(self, B, W, max_steps, lpw, feats, cons=None, grp=None, smp=None, trc=None):
+    def _ctx(self, B, W, max_steps, lpw, feats, cons=None, grp=None, smp=None, trc=None, rqd=None):
         """Persistent buffers (+ a hipGraph of the whole loop, captured on the second call with the shape), as
         Decoder._infer_ctx.  cons: active BeamConstraints (they are baked into the captured launches) or None; grp: active
         BeamGroups (baked in likewise) or None; smp: active BeamSampling or None -- its temperature is baked in and part
         of the key, its seed words are not: they live in ctx.seed, which beam_search writes in front of every launch;
-        trc: active BeamTruncation (with smp) or None -- baked in, part of the key."""
+        trc: active BeamTruncation (with smp) or None -- baked in, part of the key; rqd: BeamRequired or None -- its
+        (n_words, stride) are baked in and part of the key, its table is not: it lives in ctx.req, which beam_search
+        writes in front of every launch."""
         torch, n = self.torch, len(self.decoders)
         key = (B, W, max_steps, float(lpw)) if cons is None else (B, W, max_steps, float(lpw), cons.key())
         if grp is not None:
@@ -1315,6 +1497,8 @@ class EnsembleDecoder:
             key = (B, W, max_steps, float(lpw), cons.key() if cons is not None else None, None, smp.ctx_key())
             if trc is not None:
                 key = key + (trc.ctx_key(),)
+        if rqd is not None:
+            key = (B, W, max_steps, float(lpw), cons.key() if cons is not None else None, None, rqd.ctx_key())
         ctx = self._ctxs.get(key)
         if ctx is None:
             ctx = type('EnsembleCtx', (), {})()
@@ -1346,9 +1530,16 @@ class EnsembleDecoder:
                 ctx.seed = torch.zeros(2, dtype=torch.int64, device=self.device)       # uint64[2]: {seed, image_base}
                 ctx.smp = smp.c_struct(ctx.seed.data_ptr())
             ctx.trc = trc.c_struct() if trc is not None else None
+            ctx.rqd = None
+            if rqd is not None:
+                ctx.req = torch.full((B, rqd.n_words, rqd.stride), -1, **i32)
+                ctx.rqd = rqd.c_struct()
             ws_fn = self.lib.comic_decoder_beam_ensemble_workspace if cons is None else \
                 self.lib.comic_decoder_beam_constrained_workspace
-            if trc is not None:
+            if rqd is not None:
+                ctx.nbytes = int(self.lib.comic_decoder_beam_required_workspace(ctx.descs, n, R, max_steps,
+                                                                                0 if cons is None else 1))
+            elif trc is not None:
                 ctx.nbytes = int(self.lib.comic_decoder_beam_truncated_workspace(ctx.descs, n, R, max_steps,
                                                                                  0 if cons is None else 1))
             elif smp is not None:
@@ -1369,7 +1560,7 @@ class EnsembleDecoder:
         return ctx
 
     def beam_search(self, fms, im_embeds, beam, max_steps, want_attention=False, use_graph=True, length_penalty_weight=0.0,
-                    constraints=None, groups=None, sampling=None, image_base=0, truncation=None):
+                    constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None):
         """fms / im_embeds: one device tensor (every member reads the same features) or a sequence with one per member.
         Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's.  constraints: a
         BeamConstraints; active ones run comic_decoder_beam_constrained, None / inactive ones today's entry point.
@@ -1378,8 +1569,13 @@ class EnsembleDecoder:
         sampling, image_base: a BeamSampling; an active one runs comic_decoder_beam_sampled (with the constraints, if any),
         as Decoder.beam_search describes; None / inactive: today's entry points.
         truncation: a BeamTruncation; an active one (sampling only) runs comic_decoder_beam_truncated; the log-probabilities
-        stay the untruncated ones, as Decoder.beam_search describes; None / inactive: today's entry points, call for call."""
+        stay the untruncated ones, as Decoder.beam_search describes; None / inactive: today's entry points, call for call.
+        required: a BeamRequired; runs comic_decoder_beam_required (with the constraints, if any), as Decoder.beam_search
+        describes; None: today's entry points."""
         torch, n = self.torch, len(self.decoders)
+        if required is not None:
+            B0 = int((fms if torch.is_tensor(fms) else fms[0]).shape[0])
+            required.check(self.spec, beam, B0, max_steps, constraints, groups, sampling)
         cons = constraints if constraints is not None and constraints.active else None
         if groups is not None:
             groups.check(beam, self.spec.V)
@@ -1398,7 +1594,9 @@ class EnsembleDecoder:
             im_embeds = [im_embeds] * n
         assert len(fms) == n and len(im_embeds) == n
         B, W = int(fms[0].shape[0]), int(beam)
-        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)), cons, grp, smp, trc)
+        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)), cons, grp, smp, trc, required)
+        if required is not None:            # on the stream, in front of the launch or the replay that reads it
+            ctx.req.copy_(torch.from_numpy(required.ids))
         if smp is not None:                 # on the stream, in front of the launch or the replay that reads them
             ctx.seed.copy_(torch.from_numpy(smp.seed_words(image_base)))
 
@@ -1406,6 +1604,14 @@ class EnsembleDecoder:
             flags = L.decoder_flags_from_env()
             for k in range(n):
                 ctx.descs[k].flags = flags
+            if ctx.rqd is not None:
+                L.check(self.lib.comic_decoder_beam_required(
+                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps,
+                    C.byref(ctx.cons) if ctx.cons is not None else None, None, None, C.byref(ctx.rqd), ctx.req.data_ptr(),
+                    ctx.step_ids.data_ptr(), ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(),
+                    ctx.finished.data_ptr(), ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
+                    L.stream_ptr()), 'decoder_beam_required')
+                return
             if ctx.trc is not None:
                 L.check(self.lib.comic_decoder_beam_truncated(
                     ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps,
@@ -1457,6 +1663,12 @@ class EnsembleDecoder:
             out['log_probs'] = grp.final_log_probs(out['scores'], out['step_ids'], ln, s.end_id, length_penalty_weight)
         if smp is not None:                 # the state after the last executed step: a finished chain's carries over
             out['log_probs'] = out['scores'][-1].copy()
+        if required is not None:            # the unpenalised totals: the last scores times the length penalty's divisor
+            lp = out['scores'][-1].copy()
+            if length_penalty_weight:
+                lp = (lp * (((5.0 + ln.astype(np.float32)) / 6.0) ** np.float32(length_penalty_weight))).astype(np.float32)
+            out['log_probs'], out['banks'] = lp, required.banks
+            out['best_slot'], out['met'] = required.result(out['scores'][-1])
         if want_attention:
             out['attn_hist'] = gather_tree_from_array(ctx.hist[:T].cpu().numpy(), par, ln, s.end_id)
         return out

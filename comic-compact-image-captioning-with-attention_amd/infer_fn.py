@@ -13,7 +13,9 @@ import pickle
 import re
 import time
 
-from . import inputs, model as mdl
+import numpy as np
+
+from . import decoder as cdec, inputs, model as mdl
 from .ops import id_to_caption, base_n_to_dec as _baseN_arr_to_dec  # noqa: F401  (re-exported)
 
 pjoin = os.path.join
@@ -85,6 +87,10 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
                                    device=device)
         m_infer.restore_model()
     filenames = inputs_man.filenames_infer
+    # required words (--infer_require_file): the table of the whole run, in input order; the model slices it per batch
+    req = cdec.required_from_config(c, filenames)
+    if req is not None:
+        m_infer.required_table = req['required']
     num_batches = int(c.split_sizes['infer'] / batch_size)
     raw_outputs = dict(captions={}, attention={}, image_ids={}, beam_size=c.infer_beam_size,
                        max_caption_length=c.infer_max_length, checkpoint_path=curr_ckpt_path,
@@ -92,6 +98,7 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
     coco_json = []
     groups_json = []                # diverse beam search: the group-best captions of every image
     samples_json = []               # sampling: every sample of every image, with its log-probability
+    required_json = []              # required words: per image the words, met, and every non-empty bank's best caption
     print('INFO: Graph constructed. Starting inference.')
     start_time = time.time()
     captions = []
@@ -114,6 +121,11 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
         # caption_samples___N.json
         if smp is not None:
             smp_caps = [id_to_caption(smp['ids'][:, k], c, skip_unmapped=True) for k in range(smp['ids'].shape[1])]
+        # with required words word_ids is, per image, the best caption of the highest bank that holds one; every non-empty
+        # bank's best goes to caption_required___N.json
+        rqo = getattr(m_infer, 'required_output', None)
+        if rqo is not None:
+            rq_caps = [id_to_caption(rqo['ids'][:, k], c) for k in range(rqo['ids'].shape[1])]
         for i, f in enumerate(filenames[step * batch_size:(step + 1) * batch_size]):
             image_id = f.replace('.jpg', '')
             if '@' in image_id:
@@ -132,6 +144,14 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
                 groups_json.append(dict(image_id=image_id, captions=[
                     dict(group=g, caption=str(grp_caps[g][i]), score=float(grp['scores'][i, g]),
                          log_prob=float(grp['log_probs'][i, g])) for g in range(G)]))
+            if rqo is not None:
+                n_img = step * batch_size + i
+                required_json.append(dict(
+                    image_id=image_id, required=req['words'][n_img], dropped=req['dropped'][n_img], met=int(rqo['met'][i]),
+                    bank=int(rqo['bank'][i]), captions=[
+                        dict(bank=k, caption=str(rq_caps[k][i]), score=float(rqo['scores'][i, k]),
+                             log_prob=float(rqo['log_probs'][i, k]))
+                        for k in range(len(rq_caps)) if np.isfinite(rqo['scores'][i, k])]))
             if smp is not None:
                 samples_json.append(dict(image_id=image_id, captions=[
                     dict(sample=k, caption=str(smp_caps[k][i]), log_prob=float(smp['log_probs'][i, k]))
@@ -148,6 +168,9 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
     if groups_json:
         with open(pjoin(c.infer_save_path, 'caption_groups___{}.json'.format(ckpt_num)), 'w') as f:
             json.dump(groups_json, f)
+    if required_json:
+        with open(pjoin(c.infer_save_path, 'caption_required___{}.json'.format(ckpt_num)), 'w') as f:
+            json.dump(required_json, f)
     if samples_json:
         with open(pjoin(c.infer_save_path, 'caption_samples___{}.json'.format(ckpt_num)), 'w') as f:
             json.dump(samples_json, f)

@@ -351,14 +351,14 @@ class ModelBase(object):
 
     # ---- decode (model_base.py:692-757, :272-314) ----------------------------------------
     def _decode(self, images, beam_size, max_length, top_beam=True, want_attention=True, length_penalty_weight=0.0,
-                constraints=None, groups=None, sampling=None, image_base=0, truncation=None):
+                constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None):
         im_embed, fm = self._encode(images)
         return self._decode_features(im_embed, fm, beam_size, max_length, top_beam, want_attention, length_penalty_weight,
-                                     constraints, groups, sampling, image_base, truncation)
+                                     constraints, groups, sampling, image_base, truncation, required)
 
     def _decode_features(self, im_embed, fm, beam_size, max_length, top_beam=True, want_attention=True,
                          length_penalty_weight=0.0, constraints=None, groups=None, sampling=None, image_base=0,
-                         truncation=None):
+                         truncation=None, required=None):
         """constraints: decoder.BeamConstraints in TOKENS (decoder.constraints_from_config translates a configuration's
         words); beam search only.  groups: decoder.BeamGroups; an active one decodes by diverse beam search: the top beam is
         group 0's best (the caption of beam search of width beam / groups), and self.group_output holds the group-best
@@ -367,9 +367,27 @@ class ModelBase(object):
         image, the sample of highest log-probability (lowest slot on ties), and self.sample_output holds every sample
         (sample_set), None otherwise.  truncation: decoder.BeamTruncation; an active one restricts every draw to the top_k
         likeliest tokens and / or the top_p nucleus (sampling only: ValueError otherwise); the log-probabilities stay the
-        model's own, untruncated."""
+        model's own, untruncated.  required: decoder.BeamRequired with the batch's rows; decodes by banks of constraint progress:
+        the top beam is, per image, the best caption of the highest bank that holds one, and self.required_output holds
+        every bank's best (bank_best), None otherwise."""
         c = self._config
         iters = self.decoder.max_iterations(max_length, len(c.wtoi))
+        self.required_output = None
+        if required is not None:
+            r = self.decoder.beam_search(fm, im_embed, beam_size, iters, want_attention=want_attention,
+                                         length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
+                                         sampling=sampling, required=required)
+            self.group_output = self.sample_output = None
+            self.required_output = bank_best(r)
+            pred, best = r['predicted_ids'], r['best_slot']              # (T, B, W), (B,)
+            T, B = pred.shape[:2]
+            attn = None
+            if want_attention:
+                hist = r['attn_hist'].reshape(T, B, beam_size, self.spec.H, self.spec.M)
+                attn = hist[:, np.arange(B), best].transpose(1, 2, 0, 3)      # (B, H, T, M) of the chosen caption
+            if top_beam:
+                return pred[:, np.arange(B), best].T.copy(), attn
+            return pred.transpose(2, 1, 0).copy(), attn
         constrained = constraints is not None and constraints.active
         grouped = groups is not None and groups.active
         sampled = sampling is not None and sampling.active
@@ -433,6 +451,15 @@ def group_best(r):
     Wg = W // int(r['groups'])
     return dict(ids=r['predicted_ids'][:, :, ::Wg].transpose(1, 2, 0).copy(), scores=r['scores'][-1][:, ::Wg].copy(),
                 log_probs=r['log_probs'][:, ::Wg].copy())
+
+
+def bank_best(r):
+    """The bank-best captions of a Decoder.beam_search(required=) result: ids (B, banks, T), their final `scores` and
+    unpenalised log-probabilities (B, banks; -inf for an empty bank), and per image the chosen slot's bank and `met`."""
+    W = r['predicted_ids'].shape[2]
+    Wb = W // int(r['banks'])
+    return dict(ids=r['predicted_ids'][:, :, ::Wb].transpose(1, 2, 0).copy(), scores=r['scores'][-1][:, ::Wb].copy(),
+                log_probs=r['log_probs'][:, ::Wb].copy(), bank=np.asarray(r['best_slot']) // Wb, met=np.asarray(r['met']))
 
 
 def sample_set(r):
@@ -576,6 +603,18 @@ class CaptionModel(ModelBase):
         self._images_sampled = base + int(B)
         return base
 
+    def _required_rows(self, B):
+        """The BeamRequired of the next B images of the run when self.required_table (a BeamRequired over every image of the
+        run, in input order: decoder.required_from_config) is set, else None."""
+        table = self.__dict__.get('required_table')
+        if table is None:
+            return None
+        base = self.__dict__.get('_images_required', 0)
+        self._images_required = base + int(B)
+        if base + int(B) > table.ids.shape[0]:
+            raise ValueError('required_table holds %d images, the run decodes more' % table.ids.shape[0])
+        return cdec.BeamRequired(table.ids[base:base + int(B)])
+
     def infer(self, batch=None, constraints=None, groups=None, sampling=None, truncation=None):
         """== sess.run(m_infer.infer_output) -> [dec_preds (B,T), attention_maps (B,H,T,M)].
         constraints: decoder.BeamConstraints; None reads the configuration (infer_min_length, infer_no_repeat_ngram,
@@ -609,7 +648,8 @@ class CaptionModel(ModelBase):
         ids, attn = self._decode_features(im_embed, fm, c.infer_beam_size, c.infer_max_length, top_beam=True,
                                           length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
                                           constraints=constraints, groups=groups, sampling=sampling,
-                                          image_base=self._image_base(sampling, fm.shape[0]), truncation=truncation)
+                                          image_base=self._image_base(sampling, fm.shape[0]), truncation=truncation,
+                                          required=self._required_rows(fm.shape[0]))
         self.infer_output = [ids, attn]
         return self.infer_output
 
@@ -634,6 +674,7 @@ class CaptionModel(ModelBase):
         if sampling is None:
             sampling = cdec.sampling_from_config(c)
         constrained = constrained or (sampling is not None and sampling.active)  # (so does sampling)
+        constrained = constrained or self.__dict__.get('required_table') is not None      # (and required words)
         if truncation is None:
             truncation = cdec.truncation_from_config(c)
         if truncation is not None:
@@ -650,7 +691,8 @@ class CaptionModel(ModelBase):
                                                   want_attention=want_attention, length_penalty_weight=lp,
                                                   constraints=constraints, groups=groups, sampling=sampling,
                                                   image_base=self._image_base(sampling, feats[1].shape[0]),
-                                                  truncation=truncation)
+                                                  truncation=truncation,
+                                                  required=self._required_rows(feats[1].shape[0]))
                 yield [ids, attn]
         iters = self.decoder.max_iterations(c.infer_max_length, len(c.wtoi))
         lanes = [streams.lane(torch, self.device, 'infer%d' % k) for k in range(NL)]
@@ -930,16 +972,20 @@ class CaptionEnsemble(object):
         if sampled:
             base = self.__dict__.get('_images_sampled', 0)
             self._images_sampled = base + int(feats[0][1].shape[0])
+        required = CaptionModel._required_rows(self, feats[0][1].shape[0])
         r = self.decoder.beam_search([f[1] for f in feats], [f[0] for f in feats], W, iters, want_attention=True,
                                      length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
                                      constraints=constraints, groups=groups, sampling=sampling, image_base=base,
-                                     truncation=truncation)
+                                     truncation=truncation, required=required)
         pred = r['predicted_ids']                                  # (T, B, W)
         T, B = pred.shape[:2]
+        self.required_output = bank_best(r) if required is not None else None
         self.group_output = group_best(r) if r['groups'] > 1 else None
         self.sample_output = sample_set(r) if sampled else None
         # (sampling: per image the sample of highest log-probability, the lowest slot on ties; else the top beam)
         best = np.argmax(r['log_probs'], axis=1) if sampled else np.zeros(B, np.int64)
+        if required is not None:            # (required words: the best of the highest bank that holds a caption)
+            best = np.asarray(r['best_slot'])
         hist = r['attn_hist'].reshape(T, B, W, spec.H, spec.M)[:, np.arange(B), best]
         self.infer_output = [pred[:, np.arange(B), best].T.copy(), hist.transpose(1, 2, 0, 3)]
         return self.infer_output

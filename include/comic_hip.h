@@ -546,6 +546,66 @@ int comic_beam_step_diverse(const float* logits, const float* weights, int n_mod
                             int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int V,
                             int end_id, float length_penalty_weight, const uint32_t* bits, int words,
                             const comic_beam_groups* groups, void* workspace, int64_t workspace_bytes, void* stream);
+/* Beam search with required words (Anderson et al. 2017, "Guided Open Vocabulary Image Captioning with Constrained Beam
+ * Search"; the bank form of Post & Vilar 2018; extends rnn_decoder_beam_search, common/ops_rnn.py:49-112): every image
+ * names up to n_words = C words (1 <= C <= 4) of stride = S tokens each (1 <= S <= 4; 1 for word tokens, the radix word
+ * length for radix tokens) that its caption has to contain.  banks = C*S + 1 must divide the beam width W; Wb = W / banks,
+ * and slot w of an entry belongs to bank w / Wb.  The words are a DEVICE table req, int32 [B][C][S]: row (b, q) is the S
+ * tokens of required word q of image b, or all -1 for "no word here"; tokens lie in [0, V) and none equals end_id.  The
+ * kernels read the table at run time, so a captured graph replays with a new table.
+ *   Progress of a history h[0..L-1] (the tokens emitted so far) of entry b, with k = L mod S:
+ *     met_q       row q is padding, or some i with i % S == 0 and i + S <= L has h[i..i+S-1] == req[b][q];
+ *     m           = #{q : met_q};
+ *     partial     k > 0 and some unmet q has h[L-k..L-1] == req[b][q][0..k-1];
+ *     progress(h) = S*m + (k if partial else 0), in [0, C*S].  With S == 1: the number of required words present.
+ *   Destination bank of candidate (w, v): progress(h_w ++ v) for a live parent w, w / Wb for a finished one (it stays
+ *   where it is; _mask_probs makes it emit <EOS> as ever).
+ *   Selection, per entry and per bank c, the banks independent of each other: among the candidates of ALL W parents and
+ *   all V tokens -- total and score exactly the plain step's, _mask_probs, the ban bits and the length penalty as in
+ *   comic_beam_step_constrained -- those with dest == c and a finite total (not -inf, not NaN) are eligible; bank c takes
+ *   its Wb best, score descending, then entry-wide flat index w*V + v ascending, into the slots c*Wb + r in rank order:
+ *   word, parent (an entry-wide slot, possibly of another bank), scores = the score, log_probs (the state) = the
+ *   unpenalised total, finished and lengths as the plain step.  A slot for which no eligible candidate is left is written
+ *   as a DEAD slot: parent = the slot itself, word = end_id, scores = log_probs = -inf, finished = 1, lengths = the slot's
+ *   own previous length (a bank is legitimately empty for many steps; this replaces the lowest-untaken-index corner).
+ *   Initial state: entry b has one live slot, the first slot of bank S * (number of padding rows of b), with
+ *   log-probability 0; every other slot is finished with -inf.  An image without words starts in the top bank, which is
+ *   then plain beam search of width Wb.
+ *   Result: slot c*Wb is bank c's best; the caption of an image is the first slot of the highest bank whose first slot
+ *   has a finite final score, and met = bank / S of that slot.  Hypotheses that finish in lower banks are returned on
+ *   purpose: the fallback when the full set is unreachable within max_steps.
+ *   What a step needs per live row is a table: base (int32 [B*W]) = S * m of the row, where every token without a special
+ *   leads, and special (int32 [B*W][4][2] of (token, dest); token -1 = unused): per unmet word q whose first k tokens are
+ *   the row's tail, the token req[b][q][k] with dest S*m + k + 1 when k + 1 < S, else S * (m + the number of unmet words
+ *   this token completes).  Specials that name the same token carry the same dest (the first one decides).  The step is
+ *   defined on that table alone.
+ * Limits: 1 <= n_words <= 4, 1 <= stride <= 4, W % (n_words*stride + 1) == 0, V <= 65 536; no beam groups, no sampling. */
+typedef struct comic_beam_required {
+  int32_t n_words, stride;
+} comic_beam_required;
+/* One step of the required-word bookkeeping as a raw operator (csrc/beam_required.hip; common/ops_rnn.py:49-112 has no
+ * counterpart), to run BEFORE step t on the state step t - 1 left.  prev_words / prev_parents [B*W]: step t - 1's word_ids
+ * / parent_ids (null at t == 0); req: the device table above; hist [2][B*W][max_steps]: the token histories, advanced
+ * exactly as comic_beam_bans advances them (the executor keeps ONE pair when a decode has constraints too).  Writes base
+ * [B*W] and special [B*W][4][2] for every row (the step consults those of live rows only).  Parents are clamped to [0,W)
+ * and tokens to [0,V) before they index anything.  (Named _table: the struct has the plain name.) */
+int comic_beam_required_table(const int32_t* prev_words, const int32_t* prev_parents, const int32_t* req, int32_t* hist,
+                              int32_t* base, int32_t* special, const comic_beam_required* required, int t, int B, int W,
+                              int V, int max_steps, int end_id, void* stream);
+/* The initial state above from the table's padding rows, as a raw operator: log_probs, finished, lengths [B*W]. */
+int comic_beam_required_init(const int32_t* req, float* log_probs, int32_t* finished, int64_t* lengths, int B, int W, int V,
+                             int end_id, const comic_beam_required* required, void* stream);
+/* comic_beam_step_ensemble / comic_beam_step_constrained (common/ops_rnn.py:49-112) under banks, as a raw operator on the
+ * table (base, special) above; 2 <= banks <= 17, W % banks == 0.  bits may be NULL: no bans, and `words` is ignored.  A
+ * special whose token is outside [0,V) is unused; a dest outside [0,banks) leads nowhere.  One workgroup per entry, or,
+ * where comic_beam_step_ensemble would run split and `workspace` holds comic_beam_step_required_workspace bytes, the
+ * statistics once and a chunk launch + a merge per bank (1 + 2 banks launches ordered by the stream);
+ * comic_beam_step_ensemble_path() reports the form. */
+int64_t comic_beam_step_required_workspace(int n_models, int B, int W, int V);
+int comic_beam_step_required(const float* logits, const float* weights, int n_models, float* log_probs, int32_t* finished,
+                             int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int V,
+                             int end_id, float length_penalty_weight, const uint32_t* bits, int words, const int32_t* base,
+                             const int32_t* special, int banks, void* workspace, int64_t workspace_bytes, void* stream);
 /* Sampling inside the beam step (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112): the W slots of an entry
  * (1 <= W <= 64) are W independent chains, each drawn from the step distribution at a temperature by the Gumbel-max rule
  * with noise from a counter-based generator -- nothing is stored.  All W slots start live with log-probability 0; a
@@ -906,6 +966,26 @@ int comic_decoder_beam_truncated(const comic_decoder_desc* descs, const comic_de
                                  int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
                                  float* const* attn_hists, int32_t* steps_executed, void* workspace,
                                  int64_t workspace_bytes, void* stream);
+
+/* Beam search with required words (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112):
+ * comic_decoder_beam_ensemble / comic_decoder_beam_constrained -- the same loop; a single decoder is n_models == 1 with
+ * weight 1 -- whose initial state comes from the table's padding rows and whose every step first runs the bookkeeping
+ * (comic_beam_required_table) and then ranks by banks (comic_beam_step_required; the rule at comic_beam_required).  required and
+ * req (device, int32 [B][n_words][stride]) must not be NULL.  constraints may be NULL; given, their rules hold with the
+ * head-room extended by the specials: V >= W + n_suppress + 1 + max_steps + 4.  The length penalty of descs[0] applies.
+ * groups (more than one group) and sampling do not combine with required words: anything but NULL / one group is refused.
+ * Slot c * (W / banks) of the outputs is bank c's best.  Everything else as comic_decoder_beam_ensemble.
+ * workspace: comic_decoder_beam_required_workspace(descs, n_models, B*W, max_steps, constrained) bytes. */
+int64_t comic_decoder_beam_required_workspace(const comic_decoder_desc* descs, int n_models, int rows, int max_steps,
+                                              int constrained);
+int comic_decoder_beam_required(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                const float* const* fms, const float* const* im_embeds, const float* weights, int n_models,
+                                int B, int W, int max_steps, const comic_beam_constraints* constraints,
+                                const comic_beam_groups* groups, const comic_beam_sampling* sampling,
+                                const comic_beam_required* required, const int32_t* req, int32_t* step_ids,
+                                int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
+                                float* const* attn_hists, int32_t* steps_executed, void* workspace, int64_t workspace_bytes,
+                                void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Op-level entries of the executor-only kernel forms                        */

@@ -67,6 +67,12 @@ def create_parser():
     a('--infer_top_p', type=float, default=None,
       help='Sampling: draw every token from the smallest set of likeliest tokens whose probability reaches p (the nucleus; '
            'after --infer_top_k; 1 = off; needs --infer_sample).')
+    a('--infer_require_file', type=str, default=None,
+      help='Beam search with required words: a JSON file of image file name or image_id -> list of words the caption has '
+           'to contain (word and radix tokens); also writes caption_required___N.json with the words met and every '
+           'non-empty bank\'s best caption.  --infer_beam_size must be a multiple of words * tokens per word + 1.')
+    a('--infer_require_words', type=int, default=None,
+      help='Required words per image, 1 to 4 (default: the longest list in the file, at most 4); further words are dropped.')
     return p
 
 
@@ -96,12 +102,15 @@ def main(argv=None):
     save_name = {'test': 'infer_test_', 'valid': 'infer_valid_', 'coco_test': 'infer_cocoTest_',
                  'coco_valid': 'infer_cocoValid_'}[c.infer_set] + save_name
     # constrained, grouped and sampled captions get a directory of their own: they never overwrite the plain ones
-    from comic_amd.decoder import (constraints_dir_suffix, groups_dir_suffix, groups_from_config, sampling_dir_suffix,
-                                   sampling_from_config, truncation_dir_suffix, truncation_from_config)
+    from comic_amd.decoder import (constraints_dir_suffix, groups_dir_suffix, groups_from_config, required_dir_suffix,
+                                   required_from_config, sampling_dir_suffix, sampling_from_config, truncation_dir_suffix,
+                                   truncation_from_config)
     groups_from_config(c)           # (refuses groups that do not divide infer_beam_size before anything is loaded)
     sampling_from_config(c)         # (refuses sampling with more than one group or a length penalty likewise)
     truncation_from_config(c)       # (refuses --infer_top_k / --infer_top_p without --infer_sample likewise)
+    required_from_config(c)         # (refuses a beam size that the banks do not divide, and char tokens, likewise)
     save_name += constraints_dir_suffix(c) + groups_dir_suffix(c) + sampling_dir_suffix(c) + truncation_dir_suffix(c)
+    save_name += required_dir_suffix(c)
     c.infer_save_path = pjoin(c.infer_checkpoints_dir, save_name)
     if os.path.exists(c.infer_save_path):
         print('\nINFO: `eval_log_path` already exists.')
