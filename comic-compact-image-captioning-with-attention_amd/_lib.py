@@ -257,6 +257,14 @@ _SIGS = {
                                      P]),
     'comic_op_gru_bwd1': (c_int, [P, P, c_int, P, c_float, P, c_int, P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, P]),
     'comic_op_gru_bwd2': (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
+    # ... and of the fused / streaming LSTM step kernels and the operand hand-off behind the beam merge
+    'comic_op_lstm_step_fused': (c_int, [P, P, c_int64, P, c_int] + [P] * 7 + [c_float, P, c_int, P, P, P, c_int, c_int, c_int,
+                                                                              c_int, P, c_int, P]),
+    'comic_op_input_grad_fused': (c_int, [P, P, c_int64, P, P, c_float, P, P, P, P] + [c_int] * 6 + [P]),
+    'comic_op_lstm_grad_fused': (c_int, [P, P, c_int64] + [P] * 6 + [c_float, P, c_int, P, P, P, c_int, c_int, P]),
+    'comic_op_infer_lstm_step_workspace': (c_int64, [c_int] * 5),
+    'comic_op_infer_lstm_step': (c_int, [P, P, P, c_int] + [P] * 11 + [c_int] * 6 + [P, c_int, P, c_int64, P]),
+    'comic_op_beam_step_prep': (c_int, [P] * 9 + [c_int] * 5 + [P] * 6 + [c_int, c_int, P, c_int64, P]),
     'comic_scorer_create': (c_void_p, [c_char_p, P, c_int64, c_double]),
     'comic_scorer_destroy': (None, [c_void_p]),
     'comic_scorer_score': (c_int, [c_void_p, P, c_int, P, P, P, P, c_int]),

@@ -32,6 +32,7 @@
 
 #include "beam_pack.h"
 #include "conv_common.h"
+#include "exec_entries.h"
 #include "lstm_prep.h"
 #include "lstm_stream_dev.h"
 

@@ -35,16 +35,6 @@ int comic_embed_bwd_set(const int32_t* ids, const float* dout, float* dtable, in
 int comic_gemm_bf16x3_impl(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int lda,
                            int ldb, int ldc, int trans_a, int trans_b, float alpha, float beta, void* ws,
                            int64_t ws_bytes, hipStream_t st);
-// beam_logits.hip
-bool comic_beam_logits_supported(int D, int V, int R, int W);
-int64_t comic_beam_logits_pack_bytes(int D, int V);
-int64_t comic_beam_logits_partial_floats(int D, int V, int R, int W, int max_steps);
-int comic_beam_logits_begin(float* partials, int B, int W, int V, int max_steps, hipStream_t st);
-int comic_beam_pack_wo(const float* W_o, const float* b_o, int ld, void* wo_frag, int D, int V, hipStream_t st);
-int comic_beam_logits_step(const float* y, const void* y_frag_in, const void* wo_frag, float* partials, float* log_probs,
-                           int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores,
-                           int32_t* steps_executed, int t, int max_steps, int B, int W, int D, int V, int end_id,
-                           const LstmPrepArgs* prep, hipStream_t st);
 // score_logits.hip
 bool comic_score_stream_supported(int D, int V);
 int64_t comic_score_logits_ws_bytes(int D, int V, long rows, int stream);
@@ -52,37 +42,6 @@ float* comic_score_logits_buffer(void* ws);
 int comic_score_logits(const float* y, const float* W_o, const float* b_o, const int32_t* targets_bt, const float* wmask_bt,
                        const int32_t* lens, const unsigned* err, int B, int T, int Tp, int D, int V, int stream,
                        float* token_logp_tb, float* caption_logp, void* ws, int64_t ws_bytes, hipStream_t st);
-bool comic_lstm_stream_supported(int D, int E, int A, int R);
-int64_t comic_lstm_stream_kfrag_floats(int D, int Wd);
-int64_t comic_lstm_stream_xfrag_floats(int R, int Wd);
-int64_t comic_lstm_stream_part_bytes(int D, int Wd, int R);
-int comic_lstm_stream_pack(const float* K, void* k_frag, int D, int Wd, hipStream_t st);
-int comic_lstm_stream_step(const float* table, const int32_t* ids, const int32_t* parent, int W, const float* att_src,
-                           const float* h_src, const float* c_src, const void* k_frag, const float* bias, void* x_frag,
-                           float* c_in, float* part, int64_t part_bytes, float* c_state, float* h_state, float* y,
-                           void* y_frag, int R, int E, int A, int D, int V, int skip_prep, hipStream_t st);
-bool comic_stream_gemm_supported(int Kin, int N, int R);
-int64_t comic_stream_gemm_wfrag_floats(int Kin, int N);
-int64_t comic_stream_gemm_part_bytes(int Kin, int N, int R);
-int comic_stream_gemm_pack(const float* Wm, void* w_frag, int Kin, int N, hipStream_t st);
-int comic_stream_gemm(const void* x_frag, const void* w_frag, float* part, int64_t part_bytes, int R, int Kin, int N, int* S,
-                      hipStream_t st);
-LstmStreamArgs comic_stream_gemm_args(const void* x_frag, const void* w_frag, float* part, int R, int Kin, int N, int* S,
-                                      int* n_wg, int* lds_bytes, int max_wg);
-int comic_beam_logits_chunks(int V);
-int comic_beam_logits_launch(const float* y, const void* y_frag_in, const void* wo_frag, float* partials, int max_steps, int B,
-                             int W, int D, int V, const LstmStreamArgs* q, int n_q, int q_lds, hipStream_t st);
-int comic_beam_merge_launch(float* partials, float* log_probs, int32_t* finished, int64_t* lengths, int32_t* word_ids,
-                            int32_t* parent_ids, float* scores, int32_t* steps_executed, int t, int max_steps, int B, int W,
-                            int V, int end_id, const LstmPrepArgs* prep, hipStream_t st);
-int comic_stream_gemm2(const void* x_frag, const void* w_a, float* part_a, int N_a, int* S_a, const void* w_b, float* part_b,
-                       int N_b, int* S_b, int64_t part_bytes_each, int R, int Kin, hipStream_t st);
-bool comic_beam_step_small_supported(int V, int W);
-int comic_beam_counters_zero(void* cnt, int n, hipStream_t st);
-int comic_beam_step_small(const float* logits, const float* bias, int S, int ld, long slice_stride, float* log_probs,
-                          int32_t* finished, int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B,
-                          int W, int V, int end_id, void* cnt, int32_t* steps_executed, int t, int max_steps,
-                          const LstmPrepArgs* prep, hipStream_t st);
 // beam_step.hip
 int comic_beam_step_ws(const float* logits, float* log_probs, int32_t* finished, int64_t* lengths, int32_t* word_ids,
                        int32_t* parent_ids, float* scores, int B, int W, int V, int end_id, float lpw, void* ws,
@@ -110,22 +69,6 @@ int comic_beam_required_init_launch(const int32_t* req, float* log_probs, int32_
 // decode.hip
 int comic_ens_gather_state(const float* c, const float* h, const float* att, const int32_t* parent, float* c_out,
                            float* h_out, float* att_out, int R, int W, int D, int A, hipStream_t st);
-// decoder_fused.hip
-int comic_fused_step_supported(int D, int Wd);
-long comic_lstm_panel_floats(int D, int Wd, int mode);
-int comic_pack_lstm_panels(const float* K, float* fwd_panel, float* bwd_panel, int D, int Wd, hipStream_t st);
-int comic_lstm_step_fused(const float* xh, int ld_xh, const float* K, const float* bias, const float* c_prev,
-                          const float* h_prev, float* gates_act, float* c_new, float* y, const float* mask_out,
-                          float keep_out, const int32_t* lens, int t, float* c_state, float* h_state, float* xh_next,
-                          int xh_ld, int B, int D, int Wd, hipStream_t st);
-int comic_pack_wq_panel(const float* Wq, float* panel, int D, hipStream_t st);
-int comic_lstm_grad_fused(const float* dq, const float* wq_panel, const float* gates_act, const float* c_prev,
-                          const float* c_new, const float* dy, const float* mask_out, float keep_out,
-                          const int32_t* lens, int t, float* dc_state, float* dh_state, float* dg, int B, int D,
-                          hipStream_t st);
-int comic_input_grad_fused(const float* dg, const float* K, const float* mask, float keep, float* demb, float* datt,
-                           float* dh, const int32_t* lens, int t, int carry, int B, int E, int A, int D,
-                           hipStream_t st);
 
 namespace {
 
@@ -1830,9 +1773,12 @@ extern "C" int64_t comic_beam_step_dense_workspace(int B, int W, int D, int V) {
   if (B <= 0 || W <= 0 || D <= 0 || V <= 0) return -1;
   return ((int64_t)(D + 1) * wo_pad_cols(V) + beam_dense_region(B, W, D, V)) * 4 + kSplitKBytes + 4096;
 }
-extern "C" int comic_beam_step_dense(const float* y, const float* W_o, const float* b_o, float* log_probs, int32_t* finished,
-                                     int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W,
-                                     int D, int V, int end_id, void* workspace, int64_t workspace_bytes, void* stream) {
+// (prep: the NEXT step's operand rows through the parents just chosen, as the beam loop hands them to the streaming LSTM
+// step -- comic_op_beam_step_prep; only the merge and the small step take it)
+static int beam_step_dense_impl(const float* y, const float* W_o, const float* b_o, float* log_probs, int32_t* finished,
+                                int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int D,
+                                int V, int end_id, const LstmPrepArgs* prep, void* workspace, int64_t workspace_bytes,
+                                void* stream) {
   COMIC_REQUIRE(y && W_o && b_o && log_probs && finished && lengths && word_ids && parent_ids && scores && workspace,
                 "beam_step_dense: null pointer");
   COMIC_REQUIRE(B > 0 && W > 0 && W <= 64 && D > 0 && V >= W, "beam_step_dense: bad shape");
@@ -1851,16 +1797,101 @@ extern "C" int comic_beam_step_dense(const float* y, const float* W_o, const flo
     RC(comic_beam_pack_wo(W_o, b_o, V, wo, D, V, st));
     RC(comic_beam_logits_begin(region, B, W, V, 1, st));
     return comic_beam_logits_step(y, nullptr, wo, region, log_probs, finished, lengths, word_ids, parent_ids, scores, steps, 0, 1,
-                                  B, W, D, V, end_id, nullptr, st);
+                                  B, W, D, V, end_id, prep, st);
   }
+  COMIC_REQUIRE(!prep || comic_beam_step_small_supported(V, W),
+                "beam_step_prep: neither the merge nor the small step serves this shape (D %d, V %d, beam %d)", D, V, W);
   RC(comic_gemm_bf16x3_impl(y, W_o, region, b_o, R, V, D, D, V, V, 0, 0, 1.f, 0.f, splitk, kSplitKBytes, st));
   if (comic_beam_step_small_supported(V, W)) {
     RC(comic_beam_counters_zero(cnt, 1, st));
     return comic_beam_step_small(region, nullptr, 1, V, 0, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V,
-                                 end_id, cnt, steps, 0, 1, nullptr, st);
+                                 end_id, cnt, steps, 0, 1, prep, st);
   }
   return comic_beam_step_ws(region, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, V, end_id, 0.f, splitk,
                             kSplitKBytes, st);
+}
+extern "C" int comic_beam_step_dense(const float* y, const float* W_o, const float* b_o, float* log_probs, int32_t* finished,
+                                     int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W,
+                                     int D, int V, int end_id, void* workspace, int64_t workspace_bytes, void* stream) {
+  return beam_step_dense_impl(y, W_o, b_o, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, D, V, end_id,
+                              nullptr, workspace, workspace_bytes, stream);
+}
+
+// ---- op-level entries of the decode loops' LSTM half step and of the operand hand-off behind the beam merge ----------------
+// (include/comic_hip.h, "op-level entries"; tests only.)  comic_op_beam_step_prep: comic_beam_step_dense with the record the
+// beam loop passes when the streaming LSTM step follows; x_frag: comic_lstm_stream_xfrag_floats(B W, E + A + D) floats,
+// c_in [B W][D].  Workspace: comic_beam_step_dense_workspace.
+extern "C" int comic_op_beam_step_prep(const float* y, const float* W_o, const float* b_o, float* log_probs, int32_t* finished,
+                                       int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W,
+                                       int D, int V, int end_id, const float* table, const float* att, const float* h,
+                                       const float* c, void* x_frag, float* c_in, int E, int A, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+  COMIC_REQUIRE(table && att && h && c && x_frag && c_in, "beam_step_prep: null pointer");
+  COMIC_REQUIRE(E > 0 && A > 0 && D > 0 && E % 8 == 0 && A % 8 == 0 && D % 8 == 0,
+                "beam_step_prep: the operand thirds must be multiples of 8 (E %d, A %d, D %d)", E, A, D);
+  const LstmPrepArgs prep{table, att, h, c, (uint4*)x_frag, c_in, E, A, D, V, (E + A + D + 31) / 32};
+  return beam_step_dense_impl(y, W_o, b_o, log_probs, finished, lengths, word_ids, parent_ids, scores, B, W, D, V, end_id, &prep,
+                              workspace, workspace_bytes, stream);
+}
+
+// comic_op_infer_lstm_step: infer_step_lstm on raw parameters.  stream = 0: infer_prep_kernel + comic_lstm_step_fused over
+// the forward panel; stream = 1: comic_lstm_stream_pack once, then comic_lstm_stream_step (x_frag / y_frag:
+// comic_lstm_stream_xfrag_floats(R, Wd) / (R, D) floats).  stop / stop_t: the decode loops' stop word for these launches.
+static int64_t op_infer_lstm_carve(int R, int D, int E, int A, int stream, void* base, int64_t bytes, float** wpack, float** xh,
+                                   void** part) {
+  const int Wd = E + A + D;
+  Bump w(base, (size_t)bytes);
+  *wpack = w.take<float>(stream ? comic_lstm_stream_kfrag_floats(D, Wd) : comic_lstm_panel_floats(D, Wd, 0));
+  *xh = w.take<float>(stream ? 0 : (size_t)R * Wd);
+  *part = w.take<char>(stream ? comic_lstm_stream_part_bytes(D, Wd, R) : 0);
+  return w.ok ? (int64_t)w.off : -1;
+}
+extern "C" int64_t comic_op_infer_lstm_step_workspace(int R, int D, int E, int A, int stream) {
+  if (R <= 0 || D <= 0 || E <= 0 || A <= 0) return -1;
+  float *a, *b;
+  void* c;
+  return op_infer_lstm_carve(R, D, E, A, stream, nullptr, 0, &a, &b, &c);
+}
+extern "C" int comic_op_infer_lstm_step(const float* table, const int32_t* ids, const int32_t* parent, int W,
+                                        const float* att_src, const float* h_src, const float* c_src, const float* K,
+                                        const float* bias, float* c_in, float* c2, float* h2, float* y, void* x_frag,
+                                        void* y_frag, int R, int E, int A, int D, int V, int stream_lstm, const int32_t* stop,
+                                        int stop_t, void* workspace, int64_t workspace_bytes, void* stream) {
+  COMIC_REQUIRE(table && ids && att_src && h_src && c_src && K && c_in && c2 && h2 && y && workspace, "op_infer_lstm_step: null pointer");
+  COMIC_REQUIRE(R > 0 && W > 0 && R % W == 0 && D > 0 && E > 0 && A > 0 && V > 0, "op_infer_lstm_step: bad shape");
+  const int Wd = E + A + D;
+  if (stream_lstm) {
+    COMIC_REQUIRE(x_frag && y_frag, "op_infer_lstm_step: null fragment buffer");
+    COMIC_REQUIRE(comic_lstm_stream_supported(D, E, A, R), "op_infer_lstm_step: the streaming step does not serve D %d, E %d, A %d, rows %d", D, E, A, R);
+    COMIC_REQUIRE(comic_lstm_stream_part_bytes(D, Wd, R) <= kSplitKBytes, "op_infer_lstm_step: K-slice partials beyond the split-K scratch");
+  } else {
+    COMIC_REQUIRE(comic_fused_step_supported(D, Wd), "op_infer_lstm_step: the fused step does not serve D %d, Wd %d", D, Wd);
+  }
+  float *wpack, *xh;
+  void* part;
+  const int64_t need = op_infer_lstm_carve(R, D, E, A, stream_lstm, workspace, workspace_bytes, &wpack, &xh, &part);
+  COMIC_REQUIRE(need >= 0, "op_infer_lstm_step: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  comic_decoder_desc d{};
+  d.D = D; d.E = E; d.A = A; d.V = V;
+  comic_decoder_params p{};
+  p.emb = const_cast<float*>(table); p.b = const_cast<float*>(bias);      // read only by the step
+  StepBufs sb{};
+  sb.xh = xh; sb.y = y; sb.c2 = c2; sb.h2 = h2;
+  StreamBufs sm{wpack, x_frag, y_frag, nullptr};
+  if (stream_lstm) RC(comic_lstm_stream_pack(K, wpack, D, Wd, st));
+  else RC(comic_pack_lstm_panels(K, wpack, nullptr, D, Wd, st));
+  struct Scope {              // the stop word and the split-K scratch of this call only
+    void* saved_ws = g_splitk_ws;
+    ~Scope() {
+      g_comic_stop = ComicStop();
+      g_splitk_ws = saved_ws;
+    }
+  } scope;
+  g_comic_stop.p = stop;
+  g_comic_stop.t = stop_t;
+  g_splitk_ws = part;
+  return infer_step_lstm(&d, &p, wpack, ids, parent, W, c_src, h_src, att_src, sb, c_in, R, st, stream_lstm ? &sm : nullptr);
 }
 
 // ---- beam search: what a single decoder and every member of an ensemble share ---------------------------------------------

@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "exec_entries.h"
 
 namespace {
 

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "conv_common.h"
+#include "exec_entries.h"
 #include "lstm_prep.h"
 #include "lstm_stream_dev.h"
 
@@ -151,6 +152,11 @@ __global__ __launch_bounds__(256) void lstm_cell_kernel(const float* __restrict_
         w[j] = hl == 0 ? hh : pack_bf16x2(x[2 * j] - __uint_as_float(hh << 16), x[2 * j + 1] - __uint_as_float(hh & 0xFFFF0000u));
       }
       y_frag[((size_t)(r >> 4) * KS + (d >> 5)) * 128 + hl * 64 + ((d >> 3) & 3) * 16 + (r & 15)] = make_uint4(w[0], w[1], w[2], w[3]);
+      // D % 32 != 0: the row's last segment also zeroes the K pad of its last k-step (the consumers multiply it by the
+      // packed matrix's zero rows, and 0 x stale bits may be NaN)
+      if (d + 8 == D)
+        for (int k = D; k < KS * 32; k += 8)
+          y_frag[((size_t)(r >> 4) * KS + (k >> 5)) * 128 + hl * 64 + ((k >> 3) & 3) * 16 + (r & 15)] = make_uint4(0u, 0u, 0u, 0u);
     }
   }
 }

@@ -1,6 +1,7 @@
 // Op-level C entries of the executor-only kernel forms (include/comic_hip.h, "op-level entries of the executor-only
 // forms"): each forwards its arguments to the internal entry of exec_entries.h and does nothing else, so a test can put
-// one form on its own operands.  No product code calls these.
+// one form on its own operands; the entries of the fused step kernels first pack the weights as the executors do once
+// per call.  No product code calls these.
 #include "exec_entries.h"
 
 extern "C" {
@@ -100,6 +101,57 @@ int comic_op_gru_bwd1(const float* dy, const float* dy_part, int S, const float*
 int comic_op_gru_bwd2(float* dxh2, int ld, const float* ru, int ld_ru, const float* h_prev, float* dpre, int ld_dpre, int B,
                       int D, int EA, void* stream) {
   return comic_gru_bwd2(dxh2, ld, ru, ld_ru, h_prev, dpre, ld_dpre, B, D, EA, (hipStream_t)stream);
+}
+
+// ---- the fused LSTM step kernels (decoder_fused.hip) on the raw parameters: pack the panel the executors pack once per
+// call (panel_floats: comic_lstm_panel_floats of the shape, checked), then the host function they call per step.
+namespace {
+struct OpStopScope {          // the decode loops' stop word for the launches of one entry, as the executors scope it
+  OpStopScope(const int32_t* stop, int t) {
+    g_comic_stop.p = stop;
+    g_comic_stop.t = t;
+  }
+  ~OpStopScope() { g_comic_stop = ComicStop(); }
+};
+}  // namespace
+
+int comic_op_lstm_step_fused(const float* K, float* panel, int64_t panel_floats, const float* xh, int ld_xh,
+                             const float* bias, const float* c_prev, const float* h_prev, float* gates_act, float* c_new,
+                             float* y, const float* mask_out, float keep_out, const int32_t* lens, int t, float* c_state,
+                             float* h_state, float* xh_next, int xh_ld, int B, int D, int Wd, const int32_t* stop,
+                             int stop_t, void* stream) {
+  COMIC_REQUIRE(K && panel && D > 0 && Wd > 0 && comic_fused_step_supported(D, Wd), "op_lstm_step_fused: unsupported shape (D %d, Wd %d)", D, Wd);
+  COMIC_REQUIRE(panel_floats >= comic_lstm_panel_floats(D, Wd, 0), "op_lstm_step_fused: panel too small");
+  hipStream_t st = (hipStream_t)stream;
+  int rc = comic_pack_lstm_panels(K, panel, nullptr, D, Wd, st);
+  if (rc) return rc;
+  OpStopScope stop_scope(stop, stop_t);
+  return comic_lstm_step_fused(xh, ld_xh, panel, bias, c_prev, h_prev, gates_act, c_new, y, mask_out, keep_out, lens, t,
+                               c_state, h_state, xh_next, xh_ld, B, D, Wd, st);
+}
+
+int comic_op_input_grad_fused(const float* K, float* panel, int64_t panel_floats, const float* dg, const float* mask,
+                              float keep, float* demb, float* datt, float* dh, const int32_t* lens, int t, int carry, int B,
+                              int E, int A, int D, void* stream) {
+  COMIC_REQUIRE(K && panel && D > 0 && E >= 0 && A >= 0 && comic_fused_step_supported(D, E + A + D),
+                "op_input_grad_fused: unsupported shape (D %d, E %d, A %d)", D, E, A);
+  COMIC_REQUIRE(panel_floats >= comic_lstm_panel_floats(D, E + A + D, 1), "op_input_grad_fused: panel too small");
+  hipStream_t st = (hipStream_t)stream;
+  int rc = comic_pack_lstm_panels(K, nullptr, panel, D, E + A + D, st);
+  if (rc) return rc;
+  return comic_input_grad_fused(dg, panel, mask, keep, demb, datt, dh, lens, t, carry, B, E, A, D, st);
+}
+
+int comic_op_lstm_grad_fused(const float* W_q, float* panel, int64_t panel_floats, const float* dq, const float* gates_act,
+                             const float* c_prev, const float* c_new, const float* dy, const float* mask_out,
+                             float keep_out, const int32_t* lens, int t, float* dc_state, float* dh_state, float* dg, int B,
+                             int D, void* stream) {
+  COMIC_REQUIRE(D > 0 && panel_floats >= (int64_t)D * D, "op_lstm_grad_fused: panel too small");
+  hipStream_t st = (hipStream_t)stream;
+  int rc = comic_pack_wq_panel(W_q, panel, D, st);        // refuses D % 16 != 0, as the step itself does
+  if (rc) return rc;
+  return comic_lstm_grad_fused(dq, panel, gates_act, c_prev, c_new, dy, mask_out, keep_out, lens, t, dc_state, dh_state,
+                               dg, B, D, st);
 }
 
 }  // extern "C"

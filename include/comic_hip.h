@@ -1063,6 +1063,48 @@ int comic_op_gru_bwd1(const float* dy, const float* dy_part, int S, const float*
                       int ld_cand, const float* h_prev, float* dpre, int ld_dpre, int B, int D, void* stream);
 int comic_op_gru_bwd2(float* dxh2, int ld, const float* ru, int ld_ru, const float* h_prev, float* dpre, int ld_dpre, int B,
                       int D, int EA, void* stream);
+/* The fused and streaming LSTM step kernels (csrc/decoder_fused.hip, csrc/lstm_stream.hip, csrc/lstm_prep.h) and the operand
+ * hand-off behind the beam merge (csrc/beam_logits.hip).  The first three take the RAW row-major parameter and a panel
+ * scratch, pack it as the executors do once per call, and launch the per-step host function:
+ *   comic_op_lstm_step_fused     K [Wd][4D]; panel_floats >= ceil(D/4) * ceil(Wd/16) * 256; xh rows of ld_xh floats, xh_next
+ *                                rows of xh_ld floats (only D columns written); stop (may be NULL): a device word, the
+ *                                launches write nothing when *stop <= stop_t (the decode loops' early exit);
+ *   comic_op_input_grad_fused    K [Wd][4D]; panel_floats >= ceil(Wd/16) * (4D/16) * 256; demb may be NULL; datt is read and
+ *                                written ((carry && !finished ? 0 : old) + v), dh accumulated;
+ *   comic_op_lstm_grad_fused     W_q [D][D]; panel_floats >= D*D; D % 16 == 0, an error otherwise (nothing written);
+ *   comic_op_infer_lstm_step     the LSTM half of a decode step: row r gathers att / h / c of source row
+ *                                (r / W) * W + clamp(parent[r], 0, W - 1) (parent NULL: r), an id outside [0, V) embeds as
+ *                                zeros; stream_lstm = 0: the fp32 gather + the fused step (x_frag / y_frag unused);
+ *                                1: the streaming step (33 ... 256 rows, D % 16 == 0, E % 8 == 0, A % 8 == 0, an error
+ *                                otherwise), which also leaves the operand rows and y as bf16 hi / lo fragments
+ *                                [16-row tile][k32-step][hi, lo][lane (r % 16, seg % 4)] x 8 bf16: ceil16(R) * ceil(Wd/32) * 32
+ *                                and ceil16(R) * ceil(D/32) * 32 floats;
+ *   comic_op_beam_step_prep      comic_beam_step_dense (same workspace) that also prepares the NEXT step's operand rows
+ *                                (x_frag as above, c_in [B W][D]) through the words and parents it has just chosen; an
+ *                                error where neither the merge kernel (V >= 4096, D % 128 == 0) nor the small step
+ *                                (V <= 1024, W <= 8) serves the shape. */
+int comic_op_lstm_step_fused(const float* K, float* panel, int64_t panel_floats, const float* xh, int ld_xh,
+                             const float* bias, const float* c_prev, const float* h_prev, float* gates_act, float* c_new,
+                             float* y, const float* mask_out, float keep_out, const int32_t* lens, int t, float* c_state,
+                             float* h_state, float* xh_next, int xh_ld, int B, int D, int Wd, const int32_t* stop,
+                             int stop_t, void* stream);
+int comic_op_input_grad_fused(const float* K, float* panel, int64_t panel_floats, const float* dg, const float* mask,
+                              float keep, float* demb, float* datt, float* dh, const int32_t* lens, int t, int carry, int B,
+                              int E, int A, int D, void* stream);
+int comic_op_lstm_grad_fused(const float* W_q, float* panel, int64_t panel_floats, const float* dq, const float* gates_act,
+                             const float* c_prev, const float* c_new, const float* dy, const float* mask_out,
+                             float keep_out, const int32_t* lens, int t, float* dc_state, float* dh_state, float* dg, int B,
+                             int D, void* stream);
+int64_t comic_op_infer_lstm_step_workspace(int R, int D, int E, int A, int stream_lstm);
+int comic_op_infer_lstm_step(const float* table, const int32_t* ids, const int32_t* parent, int W, const float* att_src,
+                             const float* h_src, const float* c_src, const float* K, const float* bias, float* c_in,
+                             float* c2, float* h2, float* y, void* x_frag, void* y_frag, int R, int E, int A, int D, int V,
+                             int stream_lstm, const int32_t* stop, int stop_t, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+int comic_op_beam_step_prep(const float* y, const float* W_o, const float* b_o, float* log_probs, int32_t* finished,
+                            int64_t* lengths, int32_t* word_ids, int32_t* parent_ids, float* scores, int B, int W, int D,
+                            int V, int end_id, const float* table, const float* att, const float* h, const float* c,
+                            void* x_frag, float* c_in, int E, int A, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* SCST reward scorer (host, multi-threaded)  common/scst/scorers.py:43-171      */
