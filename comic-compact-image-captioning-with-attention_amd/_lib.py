@@ -152,6 +152,8 @@ _SIGS = {
                                       c_float, P, c_int64, P]),
     'comic_gemm_group_workspace': (c_int64, [P, c_int]),
     'comic_gemm_group': (c_int, [P, c_int, P, c_int64, P]),
+    'comic_gemm_group_form': (c_int, [P, c_int, P, c_int64, c_int, P]),
+    'comic_gemm_group_resident': (c_int, [c_int]),
     'comic_embed_fwd': (c_int, [P, P, P, c_int, c_int, c_int, P]),
     'comic_embed_bwd': (c_int, [P, P, P, c_int, c_int, c_int, P]),
     'comic_dropout_apply': (c_int, [P, P, c_float, P, c_int64, P]),

@@ -39,4 +39,6 @@ struct ComicGemmGroup {
 // launch needs.
 int comic_gemm_group_plan(ComicGemmGroup& g, int target_items, int64_t* slab_bytes, int* n_tickets);
 constexpr int kGemmGroupTargetItems = 640;   // work items a grouped launch aims at (split-K degree follows from it)
-int comic_gemm_group_launch(const ComicGemmGroup& g, int n_wg, hipStream_t st);
+// form: 0 = the library's choice, 1 = four-wave, 2 = producer / consumer one per CU, 3 = producer / consumer two per CU
+// (comic_gemm_group_form in comic_hip.h); all forms give the same bits
+int comic_gemm_group_launch(const ComicGemmGroup& g, int n_wg, hipStream_t st, int form = 0);

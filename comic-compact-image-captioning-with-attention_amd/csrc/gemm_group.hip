@@ -20,7 +20,7 @@
 namespace {
 
 constexpr int GB = 128;                 // tile edge
-constexpr int kGemmGroupSlots = 512;    // workgroups of the four-wave kernel resident together: two per CU (80 KiB of LDS each)
+constexpr int kGemmGroupSlots = 512;    // workgroups resident together: two per CU in forms 1 (80 KiB of LDS each) and 3 (72 KiB, <= 128 registers)
 constexpr int kItemOverhead = 6;        // k-tiles a work item costs beside its k loop (prologue, partial-tile store, its share of the combine)
 constexpr int kSc1 = 16;                // cache-policy bit of raw buffer accesses: sc1
 typedef __attribute__((ext_vector_type(4))) unsigned gg_u32x4_t;
@@ -64,8 +64,17 @@ __device__ __forceinline__ void gg_emit(const ComicGemmProb& p, int m, int n, fl
   }
 }
 
-template <bool PC>
-__global__ __launch_bounds__(PC ? 512 : 256) void gemm_group_x3_kernel(ComicGemmGroup g) {
+// FORM (comic_gemm_group_form): 1 = four waves in lockstep (x3_mainloop: any operand alignment), two workgroups per CU;
+// 2 = producer / consumer waves, loads four k-tiles deep, one workgroup per CU; 3 = producer / consumer waves, loads two
+// k-tiles deep, at most 128 registers per wave: two workgroups per CU.  Same plan, same products in the same order, same
+// combine: the three forms give the same bits.
+template <int FORM>
+__global__ __launch_bounds__(FORM == 1 ? 256 : 512)
+#if defined(__HIP_DEVICE_COMPILE__)
+__attribute__((amdgpu_waves_per_eu(FORM == 3 ? 4 : 1, FORM == 3 ? 4 : 2)))
+#endif
+void gemm_group_x3_kernel(ComicGemmGroup g) {
+  constexpr bool PC = FORM != 1;
   constexpr int NT = PC ? 512 : 256;                   // threads; PC: waves 0-3 own the output quadrants, waves 4-7 stream operands
   constexpr int LDS = PC ? kGroupLdsPc : kGroupLds;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -106,17 +115,19 @@ __global__ __launch_bounds__(PC ? 512 : 256) void gemm_group_x3_kernel(ComicGemm
   if (p.ones_a) {
     // column sums in exact fp32 (a bias gradient is a sum with cancellation: the 16 mantissa bits of a hi + lo pair are
     // not enough for it): thread = (4 columns, k rows kg, kg + KG, ...), the row groups combined in a fixed order
-    constexpr int KG = NT / 32;
+    // (KG = 8 row groups in every form -- the streaming waves of the 512-thread forms sit this out -- so that the sum has
+    // the same order, hence the same bits, whichever form runs the launch)
+    constexpr int KG = 8;
     float4* red = (float4*)smem;                       // [KG][32]
     const int cg = tid & 31, kg = tid >> 5, n = n0 + 4 * cg;
     const bool vec = (p.ldb % 4 == 0) && (((uintptr_t)p.B & 15) == 0);
     float4 sm = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (n < p.N)
+    if (n < p.N && kg < KG)
       for (int k = kbeg + kg; k < kend; k += KG) {
         const float4 v = load4(p.B + (size_t)k * p.ldb + n, p.N - n, vec);
         sm.x += v.x; sm.y += v.y; sm.z += v.z; sm.w += v.w;
       }
-    red[kg * 32 + cg] = sm;
+    if (kg < KG) red[kg * 32 + cg] = sm;
     __syncthreads();
     if (tid < 32) {
       float4 tot = red[cg];
@@ -132,9 +143,10 @@ __global__ __launch_bounds__(PC ? 512 : 256) void gemm_group_x3_kernel(ComicGemm
   } else {
     f32x4_t acc[4][4];
     if constexpr (PC) {
-      if (p.type == COMIC_GG_TN) x3_mainloop_pc<false, false>(p.A, p.B, p.M, p.N, p.lda, p.ldb, m0, n0, kbeg, kend, smem, acc);
-      else if (p.type == COMIC_GG_NN) x3_mainloop_pc<true, false>(p.A, p.B, p.M, p.N, p.lda, p.ldb, m0, n0, kbeg, kend, smem, acc);
-      else x3_mainloop_pc<true, true>(p.A, p.B, p.M, p.N, p.lda, p.ldb, m0, n0, kbeg, kend, smem, acc);
+      constexpr int DEPTH = FORM == 3 ? 2 : 4;
+      if (p.type == COMIC_GG_TN) x3_mainloop_pc<false, false, DEPTH>(p.A, p.B, p.M, p.N, p.lda, p.ldb, m0, n0, kbeg, kend, smem, acc);
+      else if (p.type == COMIC_GG_NN) x3_mainloop_pc<true, false, DEPTH>(p.A, p.B, p.M, p.N, p.lda, p.ldb, m0, n0, kbeg, kend, smem, acc);
+      else x3_mainloop_pc<true, true, DEPTH>(p.A, p.B, p.M, p.N, p.lda, p.ldb, m0, n0, kbeg, kend, smem, acc);
     } else {
       if (p.type == COMIC_GG_TN)
         x3_mainloop<GB, false, false, GB>(p.A, p.B, p.M, p.N, p.lda, p.ldb, m0, n0, kbeg, kend, smem, acc);
@@ -265,32 +277,52 @@ int comic_gemm_group_plan(ComicGemmGroup& g, int target_items, int64_t* slab_byt
   return wg;
 }
 
-int comic_gemm_group_launch(const ComicGemmGroup& g_in, int n_wg, hipStream_t st) {
-  ComicGemmGroup g = g_in;
-  g.xcd_chunk = n_wg / 8;          // work items of one XCD are neighbours in the item order
-  COMIC_REQUIRE(n_wg > 0, "gemm_group: empty launch");
-  // producer / consumer kernel (one 8-wave workgroup per CU) when every product can be loaded 16 bytes at a time and the
-  // launch fits the chip in one round; beyond that the four-wave kernel (two workgroups per CU) measured faster (the
-  // weight-gradient group of the decoder step: 98 against 118 us; its single-round launches 19-23 against 23-29 us)
-  bool pc = n_wg <= 256;
-  for (int i = 0; i < g.n && pc; ++i) {
+namespace {
+// forms 2 and 3 load 16 bytes at a time: every product's rows 16-byte aligned, contiguous extents multiples of 4
+bool gg_vec_ok(const ComicGemmGroup& g) {
+  for (int i = 0; i < g.n; ++i) {
     const ComicGemmProb& p = g.p[i];
     if (p.ones_a) continue;
     const bool a_kc = p.type != COMIC_GG_TN, b_kc = p.type == COMIC_GG_NT;
-    pc = p.lda % 4 == 0 && p.ldb % 4 == 0 && ((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.B & 15) == 0 &&
-         (!(a_kc || b_kc) || p.K % 4 == 0);
+    if (!(p.lda % 4 == 0 && p.ldb % 4 == 0 && ((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.B & 15) == 0 &&
+          (!(a_kc || b_kc) || p.K % 4 == 0)))
+      return false;
   }
-  static PerDeviceOnce once, once_pc;
-  bool& done = pc ? once_pc.slot() : once.slot();
-  const int lds = pc ? kGroupLdsPc : kGroupLds;
+  return true;
+}
+const void* gg_kernel(int form) {
+  return form == 1 ? (const void*)gemm_group_x3_kernel<1> : form == 2 ? (const void*)gemm_group_x3_kernel<2> : (const void*)gemm_group_x3_kernel<3>;
+}
+int gg_lds(int form) { return form == 1 ? kGroupLds : kGroupLdsPc; }
+int gg_reserve_lds(int form) {
+  static PerDeviceOnce once[3];
+  bool& done = once[form - 1].slot();
   if (!done) {
-    const void* fn = pc ? (const void*)gemm_group_x3_kernel<true> : (const void*)gemm_group_x3_kernel<false>;
-    COMIC_REQUIRE(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess,
-                  "gemm_group: cannot reserve %d bytes of LDS", lds);
+    COMIC_REQUIRE(hipFuncSetAttribute(gg_kernel(form), hipFuncAttributeMaxDynamicSharedMemorySize, gg_lds(form)) == hipSuccess,
+                  "gemm_group: cannot reserve %d bytes of LDS", gg_lds(form));
     done = true;
   }
-  if (pc) hipLaunchKernelGGL(gemm_group_x3_kernel<true>, dim3((unsigned)n_wg), dim3(512), lds, st, g);
-  else hipLaunchKernelGGL(gemm_group_x3_kernel<false>, dim3((unsigned)n_wg), dim3(256), lds, st, g);
+  return 0;
+}
+}  // namespace
+
+// form 0: the library's choice -- the twice-resident producer / consumer kernel (3) whenever every product can be loaded 16
+// bytes at a time, at any item count, the four-wave kernel (1) otherwise.  On the decoder step's six launches
+// (profiles/r15_decoder_step_timeline.txt) form 3 took 94 and 34 us where form 1 took 99
+// and 42 (356 and 288 items), and 24 / 20 / 14 / 20 us where form 2 took 24 / 22 / 16 / 20 (<= 256 items): no launch class
+// is left on form 2, which stays selectable through comic_gemm_group_form.
+int comic_gemm_group_launch(const ComicGemmGroup& g_in, int n_wg, hipStream_t st, int form) {
+  ComicGemmGroup g = g_in;
+  g.xcd_chunk = n_wg / 8;          // work items of one XCD are neighbours in the item order
+  COMIC_REQUIRE(n_wg > 0, "gemm_group: empty launch");
+  COMIC_REQUIRE(form >= 0 && form <= 3, "gemm_group: form %d", form);
+  const bool vec = gg_vec_ok(g);
+  if (form == 0) form = vec ? 3 : 1;
+  COMIC_REQUIRE(form == 1 || vec, "gemm_group: form %d needs 16-byte loadable operands", form);
+  if (int rc = gg_reserve_lds(form)) return rc;
+  if (form == 1) hipLaunchKernelGGL(gemm_group_x3_kernel<1>, dim3((unsigned)n_wg), dim3(256), kGroupLds, st, g);
+  else if (form == 2) hipLaunchKernelGGL(gemm_group_x3_kernel<2>, dim3((unsigned)n_wg), dim3(512), kGroupLdsPc, st, g);
+  else hipLaunchKernelGGL(gemm_group_x3_kernel<3>, dim3((unsigned)n_wg), dim3(512), kGroupLdsPc, st, g);
   COMIC_LAUNCH_CHECK("gemm_group");
   return 0;
 }
@@ -321,17 +353,40 @@ extern "C" int64_t comic_gemm_group_workspace(const comic_gemm_prob* probs, int 
   return slab + 256 + (int64_t)nt * 4;
 }
 
-extern "C" int comic_gemm_group(const comic_gemm_prob* probs, int n, void* workspace, int64_t workspace_bytes, void* stream) {
+extern "C" int comic_gemm_group_form(const comic_gemm_prob* probs, int n, void* workspace, int64_t workspace_bytes, int form,
+                                     void* stream) {
+  COMIC_REQUIRE(form >= 0 && form <= 3, "gemm_group: form %d", form);
   ComicGemmGroup g;
   if (int rc = gg_from_public(probs, n, g)) return rc;
   int64_t slab = 0;
   int nt = 0;
   const int wg = comic_gemm_group_plan(g, kPublicTarget, &slab, &nt);
   if (wg < 0) return 2;
+  // before anything is enqueued: a form the operands do not allow launches nothing (not even the ticket memset)
+  COMIC_REQUIRE(form < 2 || gg_vec_ok(g), "gemm_group: form %d needs 16-byte loadable operands", form);
   const int64_t slab_al = (slab + 255) / 256 * 256;
   COMIC_REQUIRE(nt == 0 || (workspace && workspace_bytes >= slab_al + (int64_t)nt * 4), "gemm_group: workspace too small");
   g.slab = (float*)workspace;
   g.tickets = nt ? (unsigned*)((char*)workspace + slab_al) : nullptr;
   if (nt) COMIC_REQUIRE(hipMemsetAsync(g.tickets, 0, (size_t)nt * 4, (hipStream_t)stream) == hipSuccess, "gemm_group: memset");
-  return comic_gemm_group_launch(g, wg, (hipStream_t)stream);
+  return comic_gemm_group_launch(g, wg, (hipStream_t)stream, form);
+}
+
+extern "C" int comic_gemm_group(const comic_gemm_prob* probs, int n, void* workspace, int64_t workspace_bytes, void* stream) {
+  return comic_gemm_group_form(probs, n, workspace, workspace_bytes, 0, stream);
+}
+
+// workgroups of a form that fit one CU together (by registers, LDS and threads)
+extern "C" int comic_gemm_group_resident(int form) {
+  if (form < 1 || form > 3) {        // (< 0: error -- a count cannot double as an error code here)
+    comic_set_error("gemm_group: form %d", form);
+    return -1;
+  }
+  if (gg_reserve_lds(form)) return -1;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gg_kernel(form), form == 1 ? 256 : 512, gg_lds(form)) != hipSuccess) {
+    comic_set_error("gemm_group: occupancy query failed");
+    return -1;
+  }
+  return nb;
 }

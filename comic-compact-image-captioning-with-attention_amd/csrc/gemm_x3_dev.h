@@ -331,7 +331,8 @@ __device__ __forceinline__ void x3_mainloop(const float* __restrict__ A, const f
 // read fragments, multiply -- so a k-tile costs the SUM of those phases (about 2000 cycles alone on a CU, 2.5 us per k-tile
 // with two workgroups per CU: 20 % of the matrix peak on d K).  Here the roles are split (the loader-wave idea of the
 // convolution kernels): waves 0-3 own the 2 x 2 output quadrants and only read fragments and issue MFMAs; waves 4-7 only
-// stream: buffer loads four k-tiles deep into four register sets, hi / lo split, LDS stores into the other of two stages.
+// stream: buffer loads DEPTH (four or two) k-tiles deep into as many register sets, hi / lo split, LDS stores into the other
+// of two stages.
 // One workgroup barrier per k-tile: behind it tile kt + 1 is complete and stage kt % 2 is free again.  The k-contiguous LDS
 // image has 64-byte rows (no pad) and the 16-byte chunk j of row r sits at j ^ swz(r >> 2), swz = {0, 3, 2, 1}: the lane
 // groups of ds_read_b128 ({0-3, 12-15, 20-27}, ...) then hit sixteen distinct bank quads (the padded 80-byte rows gave
@@ -343,12 +344,15 @@ struct X3TilePc {
 };
 __device__ __forceinline__ int x3_swz(int row) { return (0x6C >> (((row >> 2) & 3) * 2)) & 3; }   // {0, 3, 2, 1}
 
-template <int ROWS, bool KC, int NCH>
+// TIGHT: chunk after chunk (a scheduling barrier between them).  Left alone the scheduler splits all chunks of a tile at
+// once -- 32 registers of hi / lo pairs and residuals beside the staged tiles -- which does not fit 128 registers.
+template <int ROWS, bool KC, int NCH, bool TIGHT = false>
 __device__ __forceinline__ void x3pc_store_tile(unsigned char* hi_base, unsigned char* lo_base, int tid,
                                                 const float4 (&in)[NCH]) {
   using T = X3TilePc<ROWS, KC>;
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
+    if (TIGHT) __builtin_amdgcn_sched_barrier(0);
     const int q = tid + 256 * i;
     uint32_t h0, l0, h1, l1;
     split_bf16x2(in[i].x, in[i].y, h0, l0);
@@ -386,21 +390,26 @@ __device__ __forceinline__ bf16x8_t x3pc_frag(const unsigned char* base, int row
 }
 
 // 128 x 128 tile, 512 threads.  acc is meaningful in waves 0-3 only (quadrant wm = wave >> 1, wn = wave & 1, layout as above).
-template <bool A_KC, bool B_KC>
+// DEPTH = register sets of the producers = k-tiles a global load has to land:
+//   4: 128 staging VGPRs, and the consumers keep all sixteen fragments of a k-tile: 174 VGPRs, ONE workgroup per CU;
+//   2: 64 staging VGPRs, and the consumers keep the A fragments (ah, al of the four m sub-tiles) and read bh[i], bl[i] of
+//      n sub-tile i right before its twelve MFMAs: at most 128 unified registers, TWO workgroups per CU (LDS: 2 x 72 KiB);
+//      the second workgroup hides the load latency that the deeper prefetch hid.
+// Both roles run one workgroup barrier before the loop and one per k-tile of `nk`, which is derived ONCE, here, for both:
+// the k-tile count rounded up to a multiple of DEPTH (the register sets rotate with period DEPTH, the stages with period 2;
+// tiles past kend load zeros).  The products per accumulator (lo*hi, hi*lo, hi*hi) and the ascending k order are the same
+// for every DEPTH and the same as x3_mainloop_v's: the forms give the same bits.
+template <bool A_KC, bool B_KC, int DEPTH>
 __device__ __forceinline__ void x3_mainloop_pc(const float* __restrict__ A, const float* __restrict__ B, int M, int N, int lda,
                                                int ldb, int m0, int n0, int kbeg, int kend, unsigned char* smem,
                                                f32x4_t (&acc)[4][4]) {
+  static_assert(DEPTH == 2 || DEPTH == 4, "register sets of the producers");
   constexpr int BM = 128, BN = 128, BKx = 32, NCH = 4;
   constexpr int ABYTES = X3TilePc<BM, A_KC>::BYTES, BBYTES = X3TilePc<BN, B_KC>::BYTES;
   constexpr int STAGE = 2 * (ABYTES + BBYTES);          // A hi | A lo | B hi | B lo
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // k-tiles, rounded up to a multiple of 4 (the register sets rotate with period 4; tiles past kend load zeros)
-  const int nk = ((kend - kbeg + BKx - 1) / BKx + 3) & ~3;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  const int nk = ((kend - kbeg + BKx - 1) / BKx + DEPTH - 1) & ~(DEPTH - 1);
   if (wave >= 4) {
     // ---------------------------------------------------------------- producers ------------
     const int pt = tid - 256;
@@ -408,61 +417,96 @@ __device__ __forceinline__ void x3_mainloop_pc(const float* __restrict__ A, cons
     X3Src<BN, B_KC, NCH, true> sb;
     sa.init(A, lda, m0, M, kbeg, kend, pt);
     sb.init(B, ldb, n0, N, kbeg, kend, pt);
-    float4 ar[4][NCH], br[4][NCH];
+    float4 ar[DEPTH][NCH], br[DEPTH][NCH];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
+    for (int s = 0; s < DEPTH; ++s) {
       sa.load(kbeg + s * BKx, pt, ar[s]);
       sb.load(kbeg + s * BKx, pt, br[s]);
     }
     auto put = [&](int stage, const float4 (&a)[NCH], const float4 (&b)[NCH]) {
       unsigned char* st = smem + stage * STAGE;
-      x3pc_store_tile<BM, A_KC, NCH>(st, st + ABYTES, pt, a);
-      x3pc_store_tile<BN, B_KC, NCH>(st + 2 * ABYTES, st + 2 * ABYTES + BBYTES, pt, b);
+      x3pc_store_tile<BM, A_KC, NCH, DEPTH == 2>(st, st + ABYTES, pt, a);
+      x3pc_store_tile<BN, B_KC, NCH, DEPTH == 2>(st + 2 * ABYTES, st + 2 * ABYTES + BBYTES, pt, b);
+      if (DEPTH == 2) __builtin_amdgcn_sched_barrier(0);
     };
     put(0, ar[0], br[0]);
-    sa.load(kbeg + 4 * BKx, pt, ar[0]);
-    sb.load(kbeg + 4 * BKx, pt, br[0]);
+    sa.load(kbeg + DEPTH * BKx, pt, ar[0]);
+    sb.load(kbeg + DEPTH * BKx, pt, br[0]);
     __syncthreads();
-    // iteration kt: tile kt + 1 (set (kt + 1) % 4) -> stage (kt + 1) % 2, then tile kt + 5 is requested into that set
+    // iteration kt: tile kt + 1 (set (kt + 1) % DEPTH) -> stage (kt + 1) % 2, then tile kt + 1 + DEPTH is requested into that set
     auto step = [&](int kt, auto s_) {
-      constexpr int S = decltype(s_)::value;             // (kt + 1) % 4
+      constexpr int S = decltype(s_)::value;             // (kt + 1) % DEPTH
       put(S & 1, ar[S], br[S]);
-      sa.load(kbeg + (kt + 5) * BKx, pt, ar[S]);
-      sb.load(kbeg + (kt + 5) * BKx, pt, br[S]);
+      sa.load(kbeg + (kt + 1 + DEPTH) * BKx, pt, ar[S]);
+      sb.load(kbeg + (kt + 1 + DEPTH) * BKx, pt, br[S]);
       __syncthreads();
     };
-    for (int kt = 0; kt < nk; kt += 4) {
-      step(kt, std::integral_constant<int, 1>());
-      step(kt + 1, std::integral_constant<int, 2>());
-      step(kt + 2, std::integral_constant<int, 3>());
-      step(kt + 3, std::integral_constant<int, 0>());
+    for (int kt = 0; kt < nk; kt += DEPTH) {
+      if constexpr (DEPTH == 4) {
+        step(kt, std::integral_constant<int, 1>());
+        step(kt + 1, std::integral_constant<int, 2>());
+        step(kt + 2, std::integral_constant<int, 3>());
+        step(kt + 3, std::integral_constant<int, 0>());
+      } else {
+        step(kt, std::integral_constant<int, 1>());
+        step(kt + 1, std::integral_constant<int, 0>());
+      }
     }
   } else {
     // ---------------------------------------------------------------- consumers ------------
+    // (acc is zeroed HERE, not before the roles part: zeroed for all waves it stayed live -- 64 registers of zeros --
+    // through the producers' loop, which then spilled its staging registers at the 128-register budget)
     const int wm = wave >> 1, wn = wave & 1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
     __syncthreads();
     auto step = [&](auto p_) {
       constexpr int P = decltype(p_)::value;             // kt % 2
       const unsigned char* st = smem + P * STAGE;
-      bf16x8_t bh[4], bl[4], ah[4], al[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        bh[i] = x3pc_frag<BN, B_KC>(st + 2 * ABYTES, wn * 64 + i * 16, lane);
-        bl[i] = x3pc_frag<BN, B_KC>(st + 2 * ABYTES + BBYTES, wn * 64 + i * 16, lane);
-      }
+      bf16x8_t ah[4], al[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         ah[j] = x3pc_frag<BM, A_KC>(st, wm * 64 + j * 16, lane);
         al[j] = x3pc_frag<BM, A_KC>(st + ABYTES, wm * 64 + j * 16, lane);
       }
+      if constexpr (DEPTH == 4) {
+        bf16x8_t bh[4], bl[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[i], ah[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[i], al[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[i], ah[j], acc[i][j], 0, 0, 0);
+        for (int i = 0; i < 4; ++i) {
+          bh[i] = x3pc_frag<BN, B_KC>(st + 2 * ABYTES, wn * 64 + i * 16, lane);
+          bl[i] = x3pc_frag<BN, B_KC>(st + 2 * ABYTES + BBYTES, wn * 64 + i * 16, lane);
         }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[i], ah[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[i], al[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[i], ah[j], acc[i][j], 0, 0, 0);
+          }
+      } else {
+        // B fragments of n sub-tile i + 1 are read while the twelve MFMAs of sub-tile i run; the scheduling barriers keep
+        // the compiler from reading all of them at the top (it did, and spilled accumulators)
+        bf16x8_t bh[2], bl[2];
+        bh[0] = x3pc_frag<BN, B_KC>(st + 2 * ABYTES, wn * 64, lane);
+        bl[0] = x3pc_frag<BN, B_KC>(st + 2 * ABYTES + BBYTES, wn * 64, lane);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (i < 3) {
+            bh[(i + 1) & 1] = x3pc_frag<BN, B_KC>(st + 2 * ABYTES, wn * 64 + (i + 1) * 16, lane);
+            bl[(i + 1) & 1] = x3pc_frag<BN, B_KC>(st + 2 * ABYTES + BBYTES, wn * 64 + (i + 1) * 16, lane);
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[i & 1], ah[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[i & 1], al[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[i & 1], ah[j], acc[i][j], 0, 0, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
       __syncthreads();
     };
     for (int kt = 0; kt < nk; kt += 2) {

@@ -358,6 +358,19 @@ typedef struct comic_gemm_prob {
 } comic_gemm_prob;
 int64_t comic_gemm_group_workspace(const comic_gemm_prob* probs, int n);
 int comic_gemm_group(const comic_gemm_prob* probs, int n, void* workspace, int64_t workspace_bytes, void* stream);
+/* The same call with the kernel form chosen by the caller (A/B runs and tests; comic_gemm_group is form 0):
+ *   0 = as the library chooses (3 when every operand can be loaded 16 bytes at a time, 1 otherwise);
+ *   1 = four waves in lockstep, two workgroups per CU (any operand alignment);
+ *   2 = loader + MFMA waves, loads four k-tiles deep, one 8-wave workgroup per CU;
+ *   3 = loader + MFMA waves, loads two k-tiles deep, two 8-wave workgroups per CU.
+ * Forms 2 and 3 need lda % 4 == ldb % 4 == 0, A and B 16-byte aligned and K % 4 == 0 where an operand is k-contiguous
+ * (types 1, 2); a form the operands do not allow returns non-zero and enqueues nothing.  The split plan depends on the
+ * problems only: every form gives the same bits.
+ * comic_gemm_group_resident(form in 1..3): workgroups of that form that fit one CU together
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor at the form's threads and dynamic LDS); < 0 on error. */
+int comic_gemm_group_form(const comic_gemm_prob* probs, int n, void* workspace, int64_t workspace_bytes, int form,
+                          void* stream);
+int comic_gemm_group_resident(int form);
 
 /* Skinny product for the decode steps: out[R][N] = x[R][Kin] W[Kin][N] + bias for 33 ... 256 rows (batch x beam), Kin a
  * multiple of 8, any N -- the [TF-1.9] dense layers inside rnn_decoder_beam_search's step (BasicLSTMCell's gate product
