@@ -177,6 +177,8 @@ _SIGS = {
     'comic_adam_tf': (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, P]),
     'comic_adam_tf_gated': (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, P, P]),
     'comic_momentum_tf_gated': (c_int, [P, P, P, c_int64, c_float, c_float, c_float, c_float, P, P]),
+    'comic_adam_tf_ema': (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, P, P, c_float, P]),
+    'comic_momentum_tf_ema': (c_int, [P, P, P, c_int64, c_float, c_float, c_float, c_float, P, P, c_float, P]),
     'comic_debug_occupy_cus': (c_int, [c_int, c_int, P]),
     'comic_colsum': (c_int, [P, P, c_int, c_int, c_float, P]),
     'comic_ln_tanh_fwd': (c_int, [P, P, P, P, P, c_int, c_int, c_float, P]),

@@ -12,7 +12,8 @@ the variable NAMES and the restore logic.  Two containers:
     written from the published formats and pinned by round trips only (no TensorFlow here).
 In the bundle the Adam slots use tf.train.AdamOptimizer's names under the train-op scope
 (`optimise/caption/<variable>/Adam`, `/Adam_1`, `optimise/caption/beta{1,2}_power`,
-model_base.py:387-401); the `.npz` container keeps them as flat arrays.
+model_base.py:387-401); the `.npz` container keeps them as flat arrays.  The moving-average shadows of `--ema_decay`
+travel with the slots: per variable as `<variable>/ExponentialMovingAverage` in the bundle, flat in the `.npz`.
 """
 from __future__ import annotations
 
@@ -172,6 +173,50 @@ def adam_from_tf(dec_spec, arrays):
             {k: arrays[ADAM_SCOPE + n + '/Adam_1'] for k, n in names.items()})
 
 
+EMA_SUFFIX = '/ExponentialMovingAverage'
+
+
+def ema_to_tf(dec_spec, ema):
+    """The decoder's moving-average shadows (keyed like the parameters) -> {`<variable name>/ExponentialMovingAverage`: array},
+    tf.train.ExponentialMovingAverage's average_name(var)."""
+    return {n + EMA_SUFFIX: np.asarray(ema[k], np.float32) for k, n in decoder_var_names(dec_spec).items()}
+
+
+def ema_from_tf(dec_spec, arrays):
+    """Inverse of ema_to_tf: -> dict keyed like the decoder parameters, or None unless every shadow is present."""
+    names = decoder_var_names(dec_spec)
+    if not all(n + EMA_SUFFIX in arrays for n in names.values()):
+        return None
+    return {k: arrays[n + EMA_SUFFIX] for k, n in names.items()}
+
+
+def average_variables(dicts):
+    """`--infer_average`: the mean of several checkpoints' `Model/` variables, per variable, accumulated in float64 and
+    rounded once to float32.  dicts: {name: array} of each checkpoint (at least one); they must agree in the names and
+    shapes of their `Model/` variables (ValueError naming the first mismatch).  Everything else (global_step) is taken
+    from the last one."""
+    dicts = list(dicts)
+    if not dicts:
+        raise ValueError('nothing to average')
+    names = sorted(k for k in dicts[0] if k.startswith('Model/'))
+    for i, d in enumerate(dicts[1:], 1):
+        theirs = sorted(k for k in d if k.startswith('Model/'))
+        if theirs != names:
+            odd = sorted(set(names) ^ set(theirs))[0]
+            raise ValueError('checkpoints 0 and %d do not hold the same variables: `%s` is in one only' % (i, odd))
+        for k in names:
+            if np.shape(d[k]) != np.shape(dicts[0][k]):
+                raise ValueError('checkpoints 0 and %d disagree in the shape of `%s`: %s vs %s'
+                                 % (i, k, np.shape(dicts[0][k]), np.shape(d[k])))
+    out = {k: v for k, v in dicts[-1].items() if not k.startswith('Model/')}
+    for k in names:
+        acc = np.zeros(np.shape(dicts[0][k]), np.float64)
+        for d in dicts:
+            acc += np.asarray(d[k], np.float64)
+        out[k] = (acc / len(dicts)).astype(np.float32)
+    return out
+
+
 def restore(path, cnn_param_names, dec_spec, resume_training=False, exclude_scopes=None, head_names='unset'):
     """ModelBase.restore_model logic: returns (cnn_params | None, dec_params | None, extra).
     * every model variable present -> whole `Model/` (and, when resuming, step + Adam slots)
@@ -197,7 +242,9 @@ def _restore(arrays, path, cnn_param_names, dec_spec, resume_training, exclude_s
     if all(v in arrays for v in model_vars):
         cnn = {n: arrays[CNN_SCOPE + n] for n in cnn_param_names if not excluded(CNN_SCOPE + n)}
         dec = {k: arrays[v] for k, v in names.items() if not excluded(v)}
-        extra = {k: v for k, v in arrays.items() if not k.startswith('Model/')} if resume_training else {}
+        # (the shadows of `--ema_decay` sit under `Model/` in the bundle, by TF's average_name: slots, not model variables)
+        extra = {k: v for k, v in arrays.items()
+                 if not k.startswith('Model/') or k.endswith(EMA_SUFFIX)} if resume_training else {}
         return cnn, dec, extra
     cnn = {}
     for n in cnn_param_names:

@@ -1104,9 +1104,12 @@ __global__ __launch_bounds__(256) void xent_maploss_kernel(float* __restrict__ l
 }
 
 // ------------------------------------------------------------------ optimiser etc. ----
+// EMA: the launch also keeps tf.train.ExponentialMovingAverage's shadow of w, s += (w_new - s) * omd (omd = 1 - decay),
+// behind the same gate; the instantiation without it ignores s / omd (null / 0) and is the update as it always was.
+template <bool EMA>
 __global__ void adam_tf_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                                float* __restrict__ v, long n, float lr_t, float b1, float b2, float eps, float l2,
-                               float gscale, const float* __restrict__ skip) {
+                               float gscale, const float* __restrict__ skip, float* __restrict__ s, float omd) {
   if (skip && skip[0] != 0.f) return;                     // a voided step (comic_decoder_params::status): no update at all
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1117,6 +1120,7 @@ __global__ void adam_tf_kernel(float* __restrict__ w, const float* __restrict__ 
   m[i] = mi;
   v[i] = vi;
   w[i] = wi - (mi * lr_t) / (sqrtf(vi) + eps);
+  if (EMA) s[i] = s[i] + (w[i] - s[i]) * omd;
 }
 
 // ---- legacy encoder head (model_base.py:80-91): y = tanh(LayerNorm(x) * gamma + beta), eps 1e-12, over the last axis ----
@@ -1173,8 +1177,10 @@ __global__ void ln_tanh_bwd_rows_kernel(const float* __restrict__ dy, const floa
 }
 
 // tf.train.MomentumOptimizer (use_nesterov=False), ApplyMomentum [TF-1.9]: accum = momentum*accum + g; w -= lr*accum
+template <bool EMA>      // the shadow: as adam_tf_kernel
 __global__ void momentum_tf_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ accum, long n,
-                                   float lr, float momentum, float l2, float gscale, const float* __restrict__ skip) {
+                                   float lr, float momentum, float l2, float gscale, const float* __restrict__ skip,
+                                   float* __restrict__ s, float omd) {
   if (skip && skip[0] != 0.f) return;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1183,6 +1189,7 @@ __global__ void momentum_tf_kernel(float* __restrict__ w, const float* __restric
   const float ai = accum[i] * momentum + ge;
   accum[i] = ai;
   w[i] = wi - lr * ai;
+  if (EMA) s[i] = s[i] + (w[i] - s[i]) * omd;
 }
 
 // ---- per-variable gradient clipping: slim.learning.clip_gradient_norms -> tf.clip_by_norm per tensor (model_base.py:394-401) ----
@@ -1564,17 +1571,28 @@ extern "C" int comic_xent_fwd_bwd(float* logits, const int32_t* targets_bt, cons
 extern "C" int comic_adam_tf(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1,
                              float beta2, float eps, float l2, float gscale, void* stream) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(adam_tf_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
-                     (long)n, lr_t, beta1, beta2, eps, l2, gscale, (const float*)nullptr);
+  hipLaunchKernelGGL(adam_tf_kernel<false>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
+                     (long)n, lr_t, beta1, beta2, eps, l2, gscale, (const float*)nullptr, (float*)nullptr, 0.f);
   COMIC_LAUNCH_CHECK("adam_tf");
   return 0;
 }
 extern "C" int comic_adam_tf_gated(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1,
                                    float beta2, float eps, float l2, float gscale, const float* skip_flag, void* stream) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(adam_tf_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
-                     (long)n, lr_t, beta1, beta2, eps, l2, gscale, skip_flag);
+  hipLaunchKernelGGL(adam_tf_kernel<false>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
+                     (long)n, lr_t, beta1, beta2, eps, l2, gscale, skip_flag, (float*)nullptr, 0.f);
   COMIC_LAUNCH_CHECK("adam_tf_gated");
+  return 0;
+}
+extern "C" int comic_adam_tf_ema(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1,
+                                 float beta2, float eps, float l2, float gscale, const float* skip_flag, float* shadow,
+                                 float one_minus_decay, void* stream) {
+  COMIC_REQUIRE(w && g && m && v && shadow && n > 0, "adam_tf_ema: null pointer or no elements");
+  COMIC_REQUIRE(one_minus_decay > 0.f && one_minus_decay <= 1.f, "adam_tf_ema: one_minus_decay %g outside (0, 1]",
+                (double)one_minus_decay);
+  hipLaunchKernelGGL(adam_tf_kernel<true>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
+                     (long)n, lr_t, beta1, beta2, eps, l2, gscale, skip_flag, shadow, one_minus_decay);
+  COMIC_LAUNCH_CHECK("adam_tf_ema");
   return 0;
 }
 
@@ -1612,17 +1630,28 @@ extern "C" int comic_ln_tanh_bwd_rows(const float* dy, const float* y, const flo
 extern "C" int comic_momentum_tf(float* w, const float* g, float* accum, int64_t n, float lr, float momentum, float l2,
                                  float gscale, void* stream) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(momentum_tf_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, accum,
-                     (long)n, lr, momentum, l2, gscale, (const float*)nullptr);
+  hipLaunchKernelGGL(momentum_tf_kernel<false>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, accum,
+                     (long)n, lr, momentum, l2, gscale, (const float*)nullptr, (float*)nullptr, 0.f);
   COMIC_LAUNCH_CHECK("momentum_tf");
   return 0;
 }
 extern "C" int comic_momentum_tf_gated(float* w, const float* g, float* accum, int64_t n, float lr, float momentum, float l2,
                                        float gscale, const float* skip_flag, void* stream) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(momentum_tf_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, accum,
-                     (long)n, lr, momentum, l2, gscale, skip_flag);
+  hipLaunchKernelGGL(momentum_tf_kernel<false>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, accum,
+                     (long)n, lr, momentum, l2, gscale, skip_flag, (float*)nullptr, 0.f);
   COMIC_LAUNCH_CHECK("momentum_tf_gated");
+  return 0;
+}
+extern "C" int comic_momentum_tf_ema(float* w, const float* g, float* accum, int64_t n, float lr, float momentum, float l2,
+                                     float gscale, const float* skip_flag, float* shadow, float one_minus_decay,
+                                     void* stream) {
+  COMIC_REQUIRE(w && g && accum && shadow && n > 0, "momentum_tf_ema: null pointer or no elements");
+  COMIC_REQUIRE(one_minus_decay > 0.f && one_minus_decay <= 1.f, "momentum_tf_ema: one_minus_decay %g outside (0, 1]",
+                (double)one_minus_decay);
+  hipLaunchKernelGGL(momentum_tf_kernel<true>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g,
+                     accum, (long)n, lr, momentum, l2, gscale, skip_flag, shadow, one_minus_decay);
+  COMIC_LAUNCH_CHECK("momentum_tf_ema");
   return 0;
 }
 

@@ -79,9 +79,9 @@ class LegacyEncoderHead:
         L.check(self.lib.comic_colsum(b['pb'].data_ptr(), g.view('ln_beta').data_ptr(), B, C_, 0.0, st), 'd beta')
         return g
 
-    def export_params(self):
-        """{TF variable name: array}"""
-        return {TF_NAMES[k]: v for k, v in self.params.to_numpy().items()}
+    def export_params(self, params=None):
+        """{TF variable name: array} of the variables, or of a buffer with their layout (the moving-average shadow)."""
+        return {TF_NAMES[k]: v for k, v in (self.params if params is None else params).to_numpy().items()}
 
     def load_named(self, arrays):
         self.params.load({k: arrays[n] for k, n in TF_NAMES.items()})

@@ -158,23 +158,71 @@ class ModelBase(object):
     def _create_optimiser(self):
         c, share = self._config, self._share
         clip = float(getattr(c, 'clip_gradient_norm', 0) or 0)      # per-variable tf.clip_by_norm (model_base.py:394-401)
+        ema = float(getattr(c, 'ema_decay', 0) or 0)                # `--ema_decay`: a shadow of every trained variable
         if 'opt' not in share:
             share['opt'] = optim.make_optimiser(c.optimiser, self.decoder.params, epsilon=c.adam_epsilon,
-                                                l2_decay=getattr(c, 'l2_decay', 1e-5), clip_norm=clip)
+                                                l2_decay=getattr(c, 'l2_decay', 1e-5), clip_norm=clip,
+                                                ema_decay=ema)
             share['legacy_lr'] = c.lr_start
         self.opt = share['opt']
         if self.head is not None and 'opt_head' not in share:
             share['opt_head'] = optim.make_optimiser(c.optimiser, self.head.params, epsilon=c.adam_epsilon,
-                                                     l2_decay=getattr(c, 'l2_decay', 1e-5), clip_norm=clip)
+                                                     l2_decay=getattr(c, 'l2_decay', 1e-5), clip_norm=clip,
+                                                     ema_decay=ema)
         if self.cnn_trainable and 'opt_cnn' not in share:
             # gradient_multipliers scale the whole CNN gradient, L2 term included (model_base.py:388-401)
             enc = self._encoder_for(self._batch_size)
             mult = float(getattr(c, 'cnn_grad_multiplier', 1.0))
             l2 = getattr(c, 'l2_decay', 1e-5) * mult
             share['opt_cnn'] = (optim.make_optimiser(c.optimiser, enc.w_master, epsilon=c.adam_epsilon, l2_decay=l2,
-                                                     clip_norm=clip),
+                                                     clip_norm=clip, ema_decay=ema),
                                 optim.make_optimiser(c.optimiser, enc.beta, epsilon=c.adam_epsilon, l2_decay=l2,
-                                                     clip_norm=clip), mult)
+                                                     clip_norm=clip, ema_decay=ema), mult)
+
+    def _optimisers(self):
+        """Every optimiser of the run: the decoder's, the legacy head's, the two of the CNN (weights, betas)."""
+        sh = self._share
+        return [sh[k] for k in ('opt', 'opt_head') if k in sh] + list(sh.get('opt_cnn', ())[:2])
+
+    @property
+    def has_ema(self):
+        return any(o.ema is not None for o in self._optimisers())
+
+    def _restore_ema(self, extra):
+        """The shadows of `--ema_decay`.  TF's rule: a shadow starts at its variable's initial value -- so they are reset
+        AFTER the variables are in place (from scratch; a new stage on the previous stage's checkpoint, whose step count and
+        warm-up restart; a full checkpoint without shadows), and a resumed run loads them from the full checkpoint: flat
+        arrays in the `.npz` container, `<variable>/ExponentialMovingAverage` (TF's average_name) in the bundle.  The BN
+        moving statistics are frozen and have no shadow."""
+        if not self.has_ema:
+            return
+        for o in self._optimisers():
+            o.ema_reset()
+        if not extra:
+            return
+        sh, T, sfx = self._share, self.torch, ckpt.EMA_SUFFIX
+        o = sh['opt']
+        if 'optimise/caption/ema' in extra:
+            o.ema.flat.copy_(T.from_numpy(extra['optimise/caption/ema'])[:o.ema.numel])
+        else:
+            e = ckpt.ema_from_tf(self.spec, extra)
+            if e:
+                o.ema.load(e)
+        if 'opt_head' in sh:
+            from .encoder_head import TF_NAMES
+            oh = sh['opt_head']
+            if 'optimise/caption/head_ema' in extra:
+                oh.ema.data.copy_(T.from_numpy(extra['optimise/caption/head_ema']))
+            elif all(TF_NAMES[k] + sfx in extra for k in TF_NAMES):
+                oh.ema.load({k: extra[TF_NAMES[k] + sfx] for k in TF_NAMES})
+        if 'opt_cnn' in sh:
+            ow, ob, _ = sh['opt_cnn']
+            if 'optimise/caption/cnn_w_ema' in extra and 'optimise/caption/cnn_b_ema' in extra:
+                ow.ema.data.copy_(T.from_numpy(extra['optimise/caption/cnn_w_ema']))
+                ob.ema.data.copy_(T.from_numpy(extra['optimise/caption/cnn_b_ema']))
+            else:
+                enc = next(iter(sh['encoders'].values()))
+                enc.import_slots(ow.ema, ob.ema, extra, sfx[1:], ckpt.CNN_SCOPE)
 
     @property
     def global_step(self):
@@ -195,6 +243,7 @@ class ModelBase(object):
         c = self._config
         if not c.checkpoint_path:
             print('INFO: Training entire model from scratch.')
+            self._restore_ema(None)
             return (self.lr if lr is None else lr) if self.is_training() else None
         path = c.checkpoint_path
         if os.path.isdir(path):
@@ -263,6 +312,7 @@ class ModelBase(object):
                 elif enc.import_slots(ow.m, ob.m, extra, 'Adam', sc):
                     enc.import_slots(ow.v, ob.v, extra, 'Adam_1', sc)
             print('INFO: Resume training from checkpoint: {}'.format(path))
+        self._restore_ema(extra if 'opt' in self._share else None)
         if not self.is_training():
             return None
         if lr is not None and getattr(c, 'legacy', False):
@@ -291,6 +341,7 @@ class ModelBase(object):
         if 'opt_cnn' in self._share:
             for o in self._share['opt_cnn'][:2]:
                 bufs += [o.m.data, o.v.data]
+        bufs += [o.ema.data for o in self._optimisers() if o.ema is not None]
         for b in bufs:
             dp.dist.broadcast(b, 0)
         step = self.torch.tensor([self.global_step], dtype=self.torch.int64, device=self.device)
@@ -313,6 +364,9 @@ class ModelBase(object):
             else:
                 extra = {'optimise/caption/adam_m': o.m.flat.cpu().numpy(),
                          'optimise/caption/adam_v': o.v.flat.cpu().numpy()}
+            if o.ema is not None:       # the shadows travel with the slots: flat, or per variable under TF's average_name
+                extra.update(ckpt.ema_to_tf(self.spec, o.ema.to_numpy()) if fmt == 'tf' else
+                             {'optimise/caption/ema': o.ema.flat.cpu().numpy()})
         if self.head is not None:
             extra.update(self.head.export_params())
             if not compact and 'opt_head' in self._share:
@@ -329,6 +383,9 @@ class ModelBase(object):
                 else:
                     extra.update({'optimise/caption/head_adam_m': oh.m.data.cpu().numpy(),
                                   'optimise/caption/head_adam_v': oh.v.data.cpu().numpy()})
+                if oh.ema is not None:
+                    extra.update({n + ckpt.EMA_SUFFIX: v for n, v in self.head.export_params(oh.ema).items()} if fmt == 'tf'
+                                 else {'optimise/caption/head_ema': oh.ema.data.cpu().numpy()})
         if 'opt_cnn' in self._share:      # fine-tuned CNN variables back into the checkpoint layout
             self._share['cnn_params'].update(next(iter(self._share['encoders'].values())).export_params())
             if not compact:
@@ -346,8 +403,29 @@ class ModelBase(object):
                                   'optimise/caption/cnn_w_adam_v': ow.v.data.cpu().numpy(),
                                   'optimise/caption/cnn_b_adam_m': ob.m.data.cpu().numpy(),
                                   'optimise/caption/cnn_b_adam_v': ob.v.data.cpu().numpy()})
+                if ow.ema is not None and fmt == 'tf':
+                    enc = next(iter(self._share['encoders'].values()))
+                    extra.update({ckpt.CNN_SCOPE + k: v
+                                  for k, v in enc.export_slots(ow.ema, ob.ema, ckpt.EMA_SUFFIX[1:]).items()})
+                elif ow.ema is not None:
+                    extra.update({'optimise/caption/cnn_w_ema': ow.ema.data.cpu().numpy(),
+                                  'optimise/caption/cnn_b_ema': ob.ema.data.cpu().numpy()})
         return ckpt.save(save_path, self.global_step, self._share['cnn_params'], self.spec,
                          self.decoder.params.to_numpy(), extra, max_to_keep, fmt=fmt)
+
+    def save_ema(self, save_path, max_to_keep=None):
+        """`model_ema-N`: an ordinary compact checkpoint (same names and shapes as `model_compact-N`, the run's container)
+        with the shadow in place of every trained variable; the untrained ones (frozen CNN, BN statistics) are copied."""
+        fmt = getattr(self._config, 'checkpoint_format', 'npz')
+        extra = {}
+        if self.head is not None:
+            extra.update(self.head.export_params(self._share['opt_head'].ema))
+        cnn_params = dict(self._share['cnn_params'])
+        if 'opt_cnn' in self._share:
+            ow, ob, _ = self._share['opt_cnn']
+            cnn_params.update(next(iter(self._share['encoders'].values())).export_params(ow.ema, ob.ema))
+        return ckpt.save(save_path, self.global_step, cnn_params, self.spec, self._share['opt'].ema.to_numpy(), extra,
+                         max_to_keep, fmt=fmt)
 
     # ---- decode (model_base.py:692-757, :272-314) ----------------------------------------
     def _decode(self, images, beam_size, max_length, top_beam=True, want_attention=True, length_penalty_weight=0.0,

@@ -1003,11 +1003,13 @@ class CnnEncoder:
             self._pack_into(i, flat_w, flat_b, arrays[a], arrays[b])
         return True
 
-    def export_params(self):
-        """Trainable CNN variables back in the slim checkpoint layout: {name: HWIO weights / beta}."""
+    def export_params(self, flat_w=None, flat_b=None):
+        """Trainable CNN variables back in the slim checkpoint layout: {name: HWIO weights / beta}.  flat_w / flat_b: buffers
+        with the masters' layout to read instead of the masters (the optimisers' moving-average shadows)."""
         out = {}
+        flat_w, flat_b = self.w_master if flat_w is None else flat_w, self.beta if flat_b is None else flat_b
         for i, (prefix, kh, kw, cin, cout, stem) in enumerate(self.plan.weights):
-            out[prefix + '/weights'], out[prefix + '/BatchNorm/beta'] = self._unpack(i, self.w_master, self.beta)
+            out[prefix + '/weights'], out[prefix + '/BatchNorm/beta'] = self._unpack(i, flat_w, flat_b)
         return out
 
     def export_grads(self):

@@ -28,6 +28,14 @@ def legacy_lr_reduce(lr, epoch, lr_end, every_n_epochs):
     return lr
 
 
+def ema_rate(decay, t):
+    """tf.train.ExponentialMovingAverage(decay, num_updates=n).apply(): the decay of one shadow update is
+    min(decay, (1 + n) / (10 + n)), so that the average warms up; n = t - 1 for the optimiser's count t AFTER step() has
+    incremented it (the t of lr_t), i.e. the number of updates applied before this one."""
+    n = t - 1
+    return min(float(decay), (1.0 + n) / (10.0 + n))
+
+
 class GradClip:
     """`--clip_gradient_norm c` (train.py:137 -> model_base.py:394-401): slim.learning.create_train_op clips EVERY variable's
     gradient by that tensor's own norm (clip_gradient_norms -> tf.clip_by_norm [TF-1.9 slim]), after the gradient
@@ -57,7 +65,7 @@ class GradClip:
 
 
 class AdamTF:
-    def __init__(self, params, beta1=0.9, beta2=0.999, epsilon=1e-2, l2_decay=1e-5, clip_norm=0.0):
+    def __init__(self, params, beta1=0.9, beta2=0.999, epsilon=1e-2, l2_decay=1e-5, clip_norm=0.0, ema_decay=0.0):
         self.lib = L.load()
         self.params = params
         self.m = params.like()
@@ -65,6 +73,21 @@ class AdamTF:
         self.beta1, self.beta2, self.eps, self.l2 = beta1, beta2, epsilon, l2_decay
         self.t = 0                      # number of applied updates (== global_step)
         self.clip = GradClip(params, clip_norm) if clip_norm and clip_norm > 0 else None
+        self._ema_init(ema_decay)
+
+    def _ema_init(self, ema_decay):
+        """`--ema_decay d` (tf.train.ExponentialMovingAverage): a shadow of every variable, updated inside the update
+        launch (comic_*_tf_ema) behind the same gate and ranges.  d = 0: no shadow, the launches of the gated forms."""
+        self.ema_decay = float(ema_decay or 0.0)
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError('ema_decay must be in [0, 1): %r' % (ema_decay,))
+        self.ema = self.params.like() if self.ema_decay > 0 else None
+        self.ema_reset()
+
+    def ema_reset(self):
+        """A shadow starts at its variable's value (TF: the initial value): call after the variables are in place."""
+        if self.ema is not None:
+            self.ema.flat.copy_(self.params.flat)
 
     def step(self, grads, lr, grad_scale=1.0, skip=None, ranges=None, before_range=None):
         """skip: the status word of ANOTHER gradient buffer that gates this update too (the CNN optimisers of cnn_finetune
@@ -83,21 +106,34 @@ class AdamTF:
         if self.clip is not None:
             assert ranges is None, 'per-variable clipping reads whole variables: one launch over the flat buffer'
             self.clip.apply(self.params, grads, self.l2, grad_scale, skip=st)
+        omd = 1.0 - ema_rate(self.ema_decay, self.t) if self.ema is not None else 0.0
         for i, (lo, hi) in enumerate(ranges or [(0, self.params.numel)]):
             if before_range is not None:
                 before_range(i)
+            if self.ema is not None:
+                L.check(self.lib.comic_adam_tf_ema(self.params.data.data_ptr() + 4 * lo, grads.data.data_ptr() + 4 * lo,
+                                                   self.m.data.data_ptr() + 4 * lo, self.v.data.data_ptr() + 4 * lo, hi - lo,
+                                                   lr_t, self.beta1, self.beta2, self.eps, self.l2, grad_scale,
+                                                   st.data_ptr() if st is not None else None,
+                                                   self.ema.data.data_ptr() + 4 * lo, omd, L.stream_ptr()), 'adam_tf_ema')
+                continue
             L.check(self.lib.comic_adam_tf_gated(self.params.data.data_ptr() + 4 * lo, grads.data.data_ptr() + 4 * lo,
                                                  self.m.data.data_ptr() + 4 * lo, self.v.data.data_ptr() + 4 * lo, hi - lo,
                                                  lr_t, self.beta1, self.beta2, self.eps, self.l2, grad_scale,
                                                  st.data_ptr() if st is not None else None, L.stream_ptr()), 'adam_tf')
 
     def state_dict(self):
-        return dict(t=self.t, m=self.m.data.clone(), v=self.v.data.clone())
+        sd = dict(t=self.t, m=self.m.data.clone(), v=self.v.data.clone())
+        if self.ema is not None:
+            sd['ema'] = self.ema.data.clone()
+        return sd
 
     def load_state_dict(self, sd):
         self.t = int(sd['t'])
         self.m.data.copy_(sd['m'])
         self.v.data.copy_(sd['v'])
+        if self.ema is not None and 'ema' in sd:
+            self.ema.data.copy_(sd['ema'])
 
 
 class MomentumTF:
@@ -105,7 +141,7 @@ class MomentumTF:
     `--optimiser sgd`): accum = momentum*accum + g, w -= lr*accum, with the same L2 fold as AdamTF.  Same interface
     (`t`, `step`, `m` = the accumulator; `v` stays zero so checkpoints keep one layout)."""
 
-    def __init__(self, params, momentum=0.9, l2_decay=1e-5, clip_norm=0.0, **_):
+    def __init__(self, params, momentum=0.9, l2_decay=1e-5, clip_norm=0.0, ema_decay=0.0, **_):
         self.lib = L.load()
         self.params = params
         self.m = params.like()
@@ -114,6 +150,10 @@ class MomentumTF:
         self.beta1, self.beta2, self.eps = momentum, 0.0, 0.0
         self.t = 0
         self.clip = GradClip(params, clip_norm) if clip_norm and clip_norm > 0 else None
+        self._ema_init(ema_decay)
+
+    _ema_init = AdamTF._ema_init
+    ema_reset = AdamTF.ema_reset
 
     def step(self, grads, lr, grad_scale=1.0, skip=None, ranges=None, before_range=None):
         """ranges / before_range: as AdamTF.step."""
@@ -122,9 +162,17 @@ class MomentumTF:
         if self.clip is not None:
             assert ranges is None, 'per-variable clipping reads whole variables: one launch over the flat buffer'
             self.clip.apply(self.params, grads, self.l2, grad_scale, skip=st)
+        omd = 1.0 - ema_rate(self.ema_decay, self.t) if self.ema is not None else 0.0
         for i, (lo, hi) in enumerate(ranges or [(0, self.params.numel)]):
             if before_range is not None:
                 before_range(i)
+            if self.ema is not None:
+                L.check(self.lib.comic_momentum_tf_ema(self.params.data.data_ptr() + 4 * lo, grads.data.data_ptr() + 4 * lo,
+                                                       self.m.data.data_ptr() + 4 * lo, hi - lo, lr, self.momentum, self.l2,
+                                                       grad_scale, st.data_ptr() if st is not None else None,
+                                                       self.ema.data.data_ptr() + 4 * lo, omd, L.stream_ptr()),
+                        'momentum_tf_ema')
+                continue
             L.check(self.lib.comic_momentum_tf_gated(self.params.data.data_ptr() + 4 * lo, grads.data.data_ptr() + 4 * lo,
                                                      self.m.data.data_ptr() + 4 * lo, hi - lo, lr, self.momentum, self.l2,
                                                      grad_scale, st.data_ptr() if st is not None else None, L.stream_ptr()),
@@ -134,10 +182,11 @@ class MomentumTF:
     load_state_dict = AdamTF.load_state_dict
 
 
-def make_optimiser(name, params, epsilon=1e-2, l2_decay=1e-5, clip_norm=0.0):
-    """`_get_optimiser` (model_base.py:852-883) + create_train_op's clip_gradient_norm (model_base.py:394-401)."""
+def make_optimiser(name, params, epsilon=1e-2, l2_decay=1e-5, clip_norm=0.0, ema_decay=0.0):
+    """`_get_optimiser` (model_base.py:852-883) + create_train_op's clip_gradient_norm (model_base.py:394-401);
+    ema_decay > 0: a tf.train.ExponentialMovingAverage shadow of the variables (`opt.ema`)."""
     if name == 'adam':
-        return AdamTF(params, epsilon=epsilon, l2_decay=l2_decay, clip_norm=clip_norm)
+        return AdamTF(params, epsilon=epsilon, l2_decay=l2_decay, clip_norm=clip_norm, ema_decay=ema_decay)
     if name == 'sgd':
-        return MomentumTF(params, l2_decay=l2_decay, clip_norm=clip_norm)
+        return MomentumTF(params, l2_decay=l2_decay, clip_norm=clip_norm, ema_decay=ema_decay)
     raise ValueError('Unknown optimiser.')

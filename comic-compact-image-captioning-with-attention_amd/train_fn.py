@@ -93,6 +93,8 @@ def _train_loop(inputs_man, device, dp):
         if save or (step + 1) == c.max_step:
             if dp is None or dp.rank == 0:
                 m_train.save(c.save_path + '_compact', compact=True, max_to_keep=c.max_saves)
+                if m_train.has_ema:             # --ema_decay: the averaged weights as a compact checkpoint of their own
+                    m_train.save_ema(c.save_path + '_ema', max_to_keep=c.max_saves)
                 m_train.save(c.save_path, compact=False, max_to_keep=2)
             if m_valid is not None:
                 _run_eval_loop(c, m_valid, global_step)
@@ -215,6 +217,8 @@ def _scst_loop(inputs_man, idx_ngram, device, dp):
         save = save and (step + 100) < c.max_step
         if (save or (step + 1) == c.max_step) and (dp is None or dp.rank == 0):
             m_train.save(c.save_path + '_compact', compact=True, max_to_keep=c.max_saves)
+            if m_train.has_ema:
+                m_train.save_ema(c.save_path + '_ema', max_to_keep=c.max_saves)
             m_train.save(c.save_path, compact=False, max_to_keep=2)
         if (step + 1) % num_batches == 0:
             t = time.time() - start_epoch

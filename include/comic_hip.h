@@ -730,6 +730,16 @@ int comic_adam_tf_gated(float* w, const float* g, float* m, float* v, int64_t n,
                         float epsilon, float l2, float gscale, const float* skip_flag, void* stream);
 int comic_momentum_tf_gated(float* w, const float* g, float* accum, int64_t n, float lr, float momentum, float l2,
                             float gscale, const float* skip_flag, void* stream);
+/* The gated updates with tf.train.ExponentialMovingAverage's shadow of w kept in the same launch (`--ema_decay`): after the
+ * new w[i] is formed,  shadow[i] = shadow[i] + (w_new - shadow[i]) * one_minus_decay  (TF's shadow -= (1 - decay) *
+ * (shadow - var), applied to the UPDATED variable; one_minus_decay = 1 - min(decay, (1 + n) / (10 + n)) computed by the
+ * caller, 0 < one_minus_decay <= 1).  w, m, v / accum get the bits of the gated forms; a voided step (skip_flag[0] != 0)
+ * leaves the shadow untouched as well.  n > 0 is any element count (callers pass ranges); shadow must not be NULL. */
+int comic_adam_tf_ema(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
+                      float epsilon, float l2, float gscale, const float* skip_flag, float* shadow, float one_minus_decay,
+                      void* stream);
+int comic_momentum_tf_ema(float* w, const float* g, float* accum, int64_t n, float lr, float momentum, float l2,
+                          float gscale, const float* skip_flag, float* shadow, float one_minus_decay, void* stream);
 /* Gradient clipping of `--clip_gradient_norm` (train.py:137 -> model_base.py:394-401: slim.learning.create_train_op(
  * clip_gradient_norm=c) = clip_gradient_norms [TF-1.9 slim]: tf.clip_by_norm on EVERY variable's gradient by that tensor's
  * own L2 norm, after the gradient multipliers).  The clipped quantity is g_eff = g*gscale + l2*w (the L2 term is part of

@@ -73,14 +73,69 @@ def create_parser():
            'non-empty bank\'s best caption.  --infer_beam_size must be a multiple of words * tokens per word + 1.')
     a('--infer_require_words', type=int, default=None,
       help='Required words per image, 1 to 4 (default: the longest list in the file, at most 4); further words are dropped.')
+    a('--infer_ema', action='store_true', default=None,
+      help='Decode the averaged weights of a run trained with --ema_decay: the `model_ema-N` checkpoints instead of '
+           '`model_compact-N`; output goes to a directory of its own (`..._ema`).')
+    a('--infer_average', action='store_true', default=None,
+      help='Average the variables of the (at least two) checkpoints of --infer_checkpoints into ONE model and decode that; '
+           'output goes to `..._avg_<n1>+<n2>+...`.  Not together with --infer_ensemble.')
     return p
+
+
+def checkpoint_prefix(args):
+    """`model_compact-`, or `model_ema-` with --infer_ema (train.py --ema_decay writes both, with the same variables)."""
+    return 'model_ema-' if getattr(args, 'infer_ema', None) else 'model_compact-'
+
+
+def ema_dir_suffix(args):
+    return '_ema' if getattr(args, 'infer_ema', None) else ''
+
+
+def average_dir_suffix(args):
+    if not getattr(args, 'infer_average', None):
+        return ''
+    return '_avg_' + '+'.join(str(n) for n in args.infer_checkpoints)
+
+
+def check_weight_averaging(args, files=None):
+    """Refusals of --infer_ema / --infer_average, before anything is loaded.  args.infer_checkpoints: the list of numbers;
+    files: the names in the run directory (None: not looked at)."""
+    if getattr(args, 'infer_ema', None) and files is not None and not any(f.startswith('model_ema-') for f in files):
+        raise ValueError('--infer_ema: `{}` holds no `model_ema-*` checkpoint: train the run with --ema_decay'.format(
+            args.infer_checkpoints_dir))
+    if getattr(args, 'infer_average', None):
+        if getattr(args, 'infer_ensemble', None):
+            raise ValueError('--infer_average builds one model, --infer_ensemble decodes several: choose one')
+        if len(args.infer_checkpoints) < 2:
+            raise ValueError('--infer_average needs at least two --infer_checkpoints, got {}'.format(
+                ','.join(args.infer_checkpoints) or 'none'))
+
+
+def _ckpt_path(directory, ckpt_prefix, ckpt_num):
+    path = pjoin(directory, ckpt_prefix + ckpt_num)
+    return path + '.npz' if os.path.isfile(path + '.npz') else path       # else: TF bundle prefix
+
+
+def write_average(c, ckpt_prefix):
+    """--infer_average: the mean of the listed checkpoints, written into the output directory as a compact `.npz`
+    checkpoint numbered like the last of them -- what the single-checkpoint path then decodes (and a checkpoint like any
+    other: beside a config.pkl every consumer of `model_compact-N` reads it).  Returns (path, number)."""
+    from comic_amd import checkpoint as ckpt
+    import numpy as np
+    num = c.infer_checkpoints[-1]
+    path = pjoin(c.infer_save_path, 'model_compact-{}.npz'.format(num))
+    if not os.path.isfile(path):
+        mean = ckpt.average_variables(ckpt.load(_ckpt_path(c.infer_checkpoints_dir, ckpt_prefix, n))
+                                      for n in c.infer_checkpoints)
+        np.savez(path, **mean)
+    return path, num
 
 
 def main(argv=None):
     from comic_amd import configuration as conf, infer_fn as infer
     from comic_amd.configuration import natural_keys
-    ckpt_prefix = 'model_compact-'
     args = create_parser().parse_args(argv)
+    ckpt_prefix = checkpoint_prefix(args)
     if not os.path.isabs(args.infer_checkpoints_dir):
         args.infer_checkpoints_dir = pjoin(BASE_DIR, 'experiments', args.infer_checkpoints_dir)
     if args.infer_checkpoints == 'all':
@@ -96,6 +151,7 @@ def main(argv=None):
         args.infer_checkpoints = args.infer_checkpoints.split(',')
         if len(args.infer_checkpoints) < 1:
             raise ValueError('`infer_checkpoints` must be either `all` or a list of comma-separated checkpoint numbers.')
+    check_weight_averaging(args, os.listdir(args.infer_checkpoints_dir) if os.path.isdir(args.infer_checkpoints_dir) else None)
     c = conf.load_config(pjoin(args.infer_checkpoints_dir, 'config.pkl'))
     c.__dict__.update({k: v for k, v in args.__dict__.items() if v is not None})
     save_name = 'beam_{}_lpen_{}'.format(c.infer_beam_size, c.infer_length_penalty_weight)
@@ -111,6 +167,7 @@ def main(argv=None):
     required_from_config(c)         # (refuses a beam size that the banks do not divide, and char tokens, likewise)
     save_name += constraints_dir_suffix(c) + groups_dir_suffix(c) + sampling_dir_suffix(c) + truncation_dir_suffix(c)
     save_name += required_dir_suffix(c)
+    save_name += ema_dir_suffix(c) + average_dir_suffix(c)      # averaged weights never overwrite the plain captions either
     c.infer_save_path = pjoin(c.infer_checkpoints_dir, save_name)
     if os.path.exists(c.infer_save_path):
         print('\nINFO: `eval_log_path` already exists.')
@@ -122,9 +179,9 @@ def main(argv=None):
     scores_combined = {}
     if getattr(c, 'infer_ensemble', None):
         return run_ensemble(c, ckpt_prefix)
-    for ckpt_num in c.infer_checkpoints:
-        path = pjoin(c.infer_checkpoints_dir, ckpt_prefix + ckpt_num)
-        path = path + '.npz' if os.path.isfile(path + '.npz') else path       # else: TF bundle prefix
+    averaged = write_average(c, ckpt_prefix) if getattr(c, 'infer_average', None) else None
+    for ckpt_num in ([averaged[1]] if averaged else c.infer_checkpoints):
+        path = averaged[0] if averaged else _ckpt_path(c.infer_checkpoints_dir, ckpt_prefix, ckpt_num)
         # metric scores: the native BLEU / ROUGE-L / CIDEr scorers when the annotation file is there (the reference
         # shells out to the Java COCO toolkit for METEOR / SPICE / PTB tokenisation as well, infer_fn.py:295-315)
         ann = c.annotations_file if os.path.isabs(c.annotations_file) else pjoin(c.dataset_dir, 'captions', c.annotations_file)
@@ -144,8 +201,7 @@ def run_ensemble(c, ckpt_prefix):
     from comic_amd import infer_fn as infer
     paths = []
     for ckpt_num in c.infer_checkpoints:
-        path = pjoin(c.infer_checkpoints_dir, ckpt_prefix + ckpt_num)
-        paths.append(path + '.npz' if os.path.isfile(path + '.npz') else path)
+        paths.append(_ckpt_path(c.infer_checkpoints_dir, ckpt_prefix, ckpt_num))
     weights = None
     if getattr(c, 'infer_ensemble_weights', None):
         weights = [float(w) for w in str(c.infer_ensemble_weights).split(',')]

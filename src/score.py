@@ -39,6 +39,8 @@ def create_parser():
     a('--loader_cache_gb', type=float, default=None, help='Coefficient cache of the split JPEG decoder, GB.')
     a('--cnn_dtype', type=str, default=None, choices=['bf16', 'f16', 'f32', 'bf16x3'],
       help='CNN plan of the scoring run (default: the training run\'s), as in infer.py.')
+    a('--infer_ema', action='store_true', default=None,
+      help='Score with the averaged weights of a run trained with --ema_decay (`model_ema-N`), as in infer.py.')
     return p
 
 
@@ -128,7 +130,11 @@ def main(argv=None):
     args = create_parser().parse_args(argv)
     if not os.path.isabs(args.infer_checkpoints_dir):
         args.infer_checkpoints_dir = pjoin(BASE_DIR, 'experiments', args.infer_checkpoints_dir)
-    ckpts = find_checkpoints(args.infer_checkpoints_dir, args.infer_checkpoints)
+    prefix = 'model_ema-' if args.infer_ema else 'model_compact-'
+    if args.infer_ema and not any(f.startswith(prefix) for f in os.listdir(args.infer_checkpoints_dir)):
+        raise ValueError('--infer_ema: `{}` holds no `model_ema-*` checkpoint: train the run with --ema_decay'.format(
+            args.infer_checkpoints_dir))
+    ckpts = find_checkpoints(args.infer_checkpoints_dir, args.infer_checkpoints, prefix)
     with open(args.captions_file) as f:
         entries = json.load(f)
     c = conf.load_config(pjoin(args.infer_checkpoints_dir, 'config.pkl'))
@@ -136,7 +142,7 @@ def main(argv=None):
     import torch
     torch.cuda.set_device(int(str(c.gpu).split(',')[0]))
     for n in ckpts:
-        path = pjoin(c.infer_checkpoints_dir, 'model_compact-' + n)
+        path = pjoin(c.infer_checkpoints_dir, prefix + n)
         if not (os.path.isfile(path) or os.path.isfile(path + '.npz') or os.path.isfile(path + '.index')):
             print('WARNING: `{}` not found. Checkpoint skipped.'.format(os.path.basename(path)))
             continue

@@ -2,7 +2,7 @@
 """train.py -- same flags, mode chaining, run-directory naming and kwargs as the reference
 CLI (reference src/train.py:25-312), driving the MI355X-native path.
 
-Differences (all additive): `--cnn_dtype {bf16,f16,f32,bf16x3}`, `--checkpoint_format {npz,tf}`; launched under
+Differences (all additive): `--cnn_dtype {bf16,f16,f32,bf16x3}`, `--checkpoint_format {npz,tf}`, `--ema_decay`; launched under
 `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel (one process
 per GPU, RCCL gradient all-reduce); the slim checkpoint is not downloaded (no network):
 pass `--checkpoint_path` (an .npz with slim variable names) or train the CNN from random init.
@@ -91,6 +91,10 @@ def create_parser():
     a('--loader_cache_gb', type=float, default=0.0,
       help='With --loader_split_jpeg: keep the decoded DCT coefficients of the images in host memory (as their non-zeros: about the '
            'size of the JPEG files) up to this many GB; the epochs after the first skip file reads and Huffman decoding.')
+    a('--ema_decay', type=float, default=0.0,
+      help='Keep an exponential moving average of every trained variable (tf.train.ExponentialMovingAverage with '
+           'num_updates: decay min(d, (1 + n) / (10 + n))), updated inside the optimiser launch; `model_ema-N` is written '
+           'beside `model_compact-N` (infer.py / score.py --infer_ema).  0 = off, else in (0, 1).')
     return p
 
 
@@ -152,6 +156,8 @@ def build_kwargs(args):
                   log_path=log_path, save_path=pjoin(log_path, 'model'))
     kwargs.update(args.__dict__)
     kwargs.pop('log_root', None)
+    if kwargs.get('ema_decay') == 0:            # off: the configuration of a run without the flag
+        kwargs.pop('ema_decay')
     check_supported(kwargs)
     return kwargs, train_fn_name, overwrite
 
@@ -164,12 +170,20 @@ def refuse_unsupported_dtype(train_mode, cnn_dtype):
                                   'with --cnn_dtype bf16 or bf16x3 (decoder / scst runs and infer.py take f16)')
 
 
+def refuse_bad_ema_decay(ema_decay):
+    """--ema_decay outside [0, 1) (1 would freeze the shadow at the initial values).  Called before anything touches the GPU."""
+    d = float(ema_decay or 0.0)
+    if not 0.0 <= d < 1.0:
+        raise ValueError('--ema_decay must be in [0, 1) (0 = off), got {}'.format(ema_decay))
+
+
 def check_supported(kw):
     """Options of the reference that this hot path does not implement fail HERE instead of silently training a different
     model.  Refused: --train_mode cnn_finetune with --cnn_dtype f16 (refuse_unsupported_dtype).  --clip_gradient_norm (model_base.py:394-401) is per-variable tf.clip_by_norm
     in front of the optimiser (optim.GradClip), --rnn_name LN_LSTM / GRU (model_base.py:622-629) run on the per-step
     launch chain."""
     refuse_unsupported_dtype(kw.get('train_mode'), kw.get('cnn_dtype'))
+    refuse_bad_ema_decay(kw.get('ema_decay'))
     bad = []
     # --initialiser: `he` / `none` select TensorFlow's default initialiser in the reference (model_base.py:823-831:
     # every value but `xavier` returns None), which for these float variables is glorot_uniform == Xavier-uniform
@@ -181,6 +195,7 @@ def check_supported(kw):
 def main(argv=None):
     args = create_parser().parse_args(argv)
     refuse_unsupported_dtype(args.train_mode, args.cnn_dtype)
+    refuse_bad_ema_decay(args.ema_decay)
     import torch
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
