@@ -238,6 +238,9 @@ _SIGS = {
     'comic_decoder_beam_truncated_workspace': (c_int64, [P, c_int, c_int, c_int, c_int]),
     'comic_decoder_beam_truncated': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P,
                                              c_int64, P]),
+    'comic_caption_consensus_workspace': (c_int64, [c_int, c_int, c_int, c_int]),
+    'comic_caption_consensus': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, c_int64, c_double, c_double,
+                                        P, P, P, c_int64, P]),
     # op-level entries of the executor-only kernel forms (tests only; the argument lists are csrc/exec_entries.h's)
     'comic_attn_splits': (c_int, [c_int, c_int]),
     'comic_attn_bwd_scratch': (C.c_long, [c_int, c_int, c_int, c_int]),

@@ -530,6 +530,29 @@ def required_image_key(filename):
     return str(int(found[0])) if found else None
 
 
+def config_wtoi(c):
+    """The word -> index map of a configuration: c.wtoi, or, before the input manager has read the vocabulary, the same
+    file."""
+    wtoi = getattr(c, 'wtoi', None)
+    if wtoi is None:
+        with open(os.path.join(c.dataset_dir, 'captions', c.dataset_file_pattern.format('wtoi')) + '.json') as f:
+            wtoi = json.load(f)
+    return wtoi
+
+
+def word_stride(c, wtoi):
+    """Tokens per word: 1 for `word` tokens, the radix word length for `radix` tokens."""
+    return len(number_to_base(len(wtoi), c.radix_base)) if c.token_type == 'radix' else 1
+
+
+def word_encoding(c, wtoi):
+    """word -> list of word_stride tokens, for `word` and `radix` tokens (required words, the consensus idf table)."""
+    if c.token_type == 'radix':
+        from .ops import build_radix_wtoi
+        return build_radix_wtoi(wtoi, c.radix_base)
+    return {w: [int(i)] for w, i in wtoi.items()}
+
+
 def required_from_config(c, filenames=None):
     """The required words a configuration asks for (infer_require_file, infer_require_words), or None when it names no
     file.  The file is JSON: image file name (with or without its directory) or image_id -> list of words.  Words map
@@ -553,11 +576,8 @@ def required_from_config(c, filenames=None):
     C_ = int(C_)
     if not 1 <= C_ <= BeamRequired.MAX_WORDS:
         raise ValueError('infer_require_words must be in [1,%d], got %d' % (BeamRequired.MAX_WORDS, C_))
-    wtoi = getattr(c, 'wtoi', None)
-    if wtoi is None:                  # before the input manager has read the vocabulary: the same file
-        with open(os.path.join(c.dataset_dir, 'captions', c.dataset_file_pattern.format('wtoi')) + '.json') as f:
-            wtoi = json.load(f)
-    S = len(number_to_base(len(wtoi), c.radix_base)) if c.token_type == 'radix' else 1
+    wtoi = config_wtoi(c)
+    S = word_stride(c, wtoi)
     if S > BeamRequired.MAX_STRIDE:
         raise ValueError('infer_require_file: a radix word of %d tokens exceeds %d' % (S, BeamRequired.MAX_STRIDE))
     banks = C_ * S + 1
@@ -567,11 +587,7 @@ def required_from_config(c, filenames=None):
     out = dict(n_words=C_, stride=S, banks=banks)
     if filenames is None:
         return out
-    if c.token_type == 'radix':
-        from .ops import build_radix_wtoi
-        enc = build_radix_wtoi(wtoi, c.radix_base)
-    else:
-        enc = {w: [int(i)] for w, i in wtoi.items()}
+    enc = word_encoding(c, wtoi)
     ids = np.full((len(filenames), C_, S), -1, np.int32)
     words, dropped = [], []
     for k, f in enumerate(filenames):
@@ -763,6 +779,219 @@ def truncation_dir_suffix(c):
     if p is not None and float(p) < 1.0:
         out += '_p%g' % float(p)
     return out
+
+
+def _splitmix64(z):
+    """csrc/splitmix.h on a numpy uint64 array (wraps modulo 2^64)."""
+    with np.errstate(over='ignore'):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def ngram_keys(tokens):
+    """The 64-bit keys of n n-grams of m tokens each (int array [n, m]; comic_caption_consensus): h = splitmix64(m), then
+    h = splitmix64(h ^ token) token by token; a result of 0 becomes 1.  -> uint64 [n]."""
+    tokens = np.asarray(tokens, np.int64)
+    h = _splitmix64(np.full(tokens.shape[0], tokens.shape[1], np.uint64))
+    for s in range(tokens.shape[1]):
+        h = _splitmix64(h ^ tokens[:, s].astype(np.uint64))
+    return np.where(h == 0, np.uint64(1), h)
+
+
+class NgramIdf:
+    """The idf table of the consensus selector in the form the device reads (comic_caption_consensus): uint64 keys[cap]
+    (0 = empty) beside double g[cap], g = log(ref_len) - log(max(1, df)) formed here in double; open addressing with
+    linear probing from key & (cap - 1), cap a power of two of at least twice the number of entries.  An n-gram the table
+    does not hold gets log_ref_len.  kept / skipped count the n-grams of the source that went in / were left out."""
+
+    def __init__(self, keys, g, log_ref_len, stride, kept=None, skipped=0):
+        self.keys = np.ascontiguousarray(keys, np.uint64)
+        self.g = np.ascontiguousarray(g, np.float64)
+        self.cap = int(self.keys.shape[0])
+        if self.cap < 1 or self.cap & (self.cap - 1) or self.g.shape != self.keys.shape:
+            raise ValueError('idf: keys and g must share a power-of-two capacity, got %r and %r' % (self.keys.shape, self.g.shape))
+        self.log_ref_len, self.stride = float(log_ref_len), int(stride)
+        self.kept = int((self.keys != 0).sum()) if kept is None else int(kept)
+        self.skipped = int(skipped)
+        self._dev = {}
+
+    def __repr__(self):
+        return 'NgramIdf(%d n-grams in %d slots, stride=%d, %d skipped)' % (self.kept, self.cap, self.stride, self.skipped)
+
+    @classmethod
+    def from_document_frequency(cls, df, ref_len, encode, stride):
+        """df: {tuple of words: document count}; encode: word -> list of `stride` tokens (word_encoding).  N-grams that
+        hold a word outside `encode` or one of <GO> / <EOS> / <PAD> are skipped and counted."""
+        stride = int(stride)
+        log_ref_len = math.log(float(ref_len))
+        by_len, skipped = {}, 0
+        for ng, cnt in df.items():
+            if any(w in ('<GO>', '<EOS>', '<PAD>') or w not in encode for w in ng):
+                skipped += 1
+                continue
+            toks = [t for w in ng for t in encode[w]]
+            if len(toks) != len(ng) * stride:
+                raise ValueError('idf: the n-gram %r maps to %d tokens, not %d words of stride %d'
+                                 % (ng, len(toks), len(ng), stride))
+            rows, gs = by_len.setdefault(len(toks), ([], []))
+            rows.append(toks)
+            gs.append(log_ref_len - math.log(max(1.0, float(cnt))))
+        key_list, g_list = [], []
+        for m in sorted(by_len):
+            rows, gs = by_len[m]
+            key_list += ngram_keys(np.asarray(rows, np.int64).reshape(len(rows), m)).tolist()
+            g_list += gs
+        cap = 2
+        while cap < 2 * len(key_list):
+            cap *= 2
+        keys, g, kept = [0] * cap, [0.0] * cap, 0
+        for key, val in zip(key_list, g_list):
+            at = key & (cap - 1)
+            while keys[at] != 0 and keys[at] != key:
+                at = (at + 1) & (cap - 1)
+            if keys[at] == key:            # two n-grams, one 64-bit key: the first stays
+                skipped += 1
+                continue
+            keys[at], g[at] = key, val
+            kept += 1
+        return cls(np.array(keys, np.uint64), np.array(g, np.float64), log_ref_len, stride, kept, skipped)
+
+    @classmethod
+    def from_pickle(cls, path, config):
+        """The `{pattern}scst-words.p` file of scst/prepro_ngrams.py, through the configuration's vocabulary."""
+        from .scst.scorers import load_df_pickle
+        if config.token_type == 'char':
+            raise ValueError('infer_consensus_df: the idf table needs `word` or `radix` tokens, not `char`')
+        d = load_df_pickle(path)
+        wtoi = config_wtoi(config)
+        idf = cls.from_document_frequency(d['document_frequency'], d['ref_len'], word_encoding(config, wtoi),
+                                          word_stride(config, wtoi))
+        print('INFO: consensus idf: %d n-grams of %s kept, %d skipped (outside the vocabulary or with <GO> / <EOS> / <PAD>)'
+              % (idf.kept, path, idf.skipped))
+        return idf
+
+    def device(self, torch, device):
+        """(keys, g) as device tensors (the keys as the int64 view of the uint64 words); uploaded once per device."""
+        t = self._dev.get(str(device))
+        if t is None:
+            t = self._dev[str(device)] = (torch.from_numpy(self.keys.view(np.int64)).to(device),
+                                          torch.from_numpy(self.g).to(device))
+        return t
+
+
+class Consensus:
+    """Consensus (minimum-Bayes-risk) selection among the W candidates of an image (comic_caption_consensus; no counterpart
+    in common/ops_rnn.py): the utility of a candidate is its mean CIDEr-D similarity (n-grams of 1..4 words, sigma) to its
+    siblings, weighted by `weights`: 'uniform' (the Monte-Carlo estimate, for samples) or 'posterior' (the softmax of the
+    final log-probabilities over the slots, for n-best lists; a slot of -inf neither votes nor can be chosen).  stride: the
+    tokens of a word (1 for `word` tokens, the radix word length for `radix`); idf: an NgramIdf or None (every n-gram
+    weighs 1).  Immutable; hashable by (weights, stride, sigma, the table's identity)."""
+    MODES = {'uniform': 0, 'posterior': 1}          # COMIC_CONSENSUS_*
+    MAX_W, MAX_UNITS, MAX_STRIDE = 32, 64, 8
+
+    def __init__(self, weights='uniform', stride=1, idf=None, sigma=6.0):
+        self.weights, self.stride, self.idf, self.sigma = str(weights), int(stride), idf, float(sigma)
+
+    def key(self):
+        return (self.weights, self.stride, self.sigma, id(self.idf) if self.idf is not None else None)
+
+    def __eq__(self, other):
+        return isinstance(other, Consensus) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'Consensus(weights=%r, stride=%d, idf=%r, sigma=%r)' % (self.weights, self.stride, self.idf, self.sigma)
+
+    def check(self, beam, max_steps):
+        """The rules of the C side, on the host before any GPU call; raises ValueError naming the field."""
+        if self.weights not in self.MODES:
+            raise ValueError("consensus: weights must be 'uniform' or 'posterior', got %r" % self.weights)
+        if not 1 <= self.stride <= self.MAX_STRIDE:
+            raise ValueError('consensus: stride must be in [1,%d], got %d' % (self.MAX_STRIDE, self.stride))
+        if not (self.sigma > 0.0 and math.isfinite(self.sigma)):
+            raise ValueError('consensus: sigma must be finite and > 0, got %r' % self.sigma)
+        if self.idf is not None and self.idf.stride != self.stride:
+            raise ValueError('consensus: the idf table was built for stride %d, not %d' % (self.idf.stride, self.stride))
+        if not 1 <= int(beam) <= self.MAX_W:
+            raise ValueError('consensus: the number of candidates (beam) must be in [1,%d], got %d' % (self.MAX_W, int(beam)))
+        if not 1 <= int(max_steps) <= self.MAX_UNITS * self.stride:
+            raise ValueError('consensus: max_steps = %d exceeds %d words of %d tokens'
+                             % (int(max_steps), self.MAX_UNITS, self.stride))
+
+
+def caption_consensus(lib, torch, ids, end_id, cons, log_probs=None, posterior=None):
+    """One comic_caption_consensus launch on the device tensor ids [T, B, W] (int32, contiguous) -> device tensors
+    (utility [B, W] float64, best [B] int32).  posterior: None follows cons.weights; True forces the posterior weights
+    (log_probs [B, W] float32 on the device is then needed)."""
+    T, B, W = (int(x) for x in ids.shape)
+    cons.check(W, T)
+    if posterior is None:
+        posterior = cons.weights == 'posterior'
+    if posterior and log_probs is None:
+        raise ValueError("consensus: weights='posterior' needs log_probs")
+    assert ids.dtype == torch.int32 and ids.is_contiguous()
+    if posterior:
+        assert log_probs.dtype == torch.float32 and log_probs.is_contiguous() and tuple(log_probs.shape) == (B, W)
+    util = torch.empty((B, W), dtype=torch.float64, device=ids.device)
+    best = torch.empty(B, dtype=torch.int32, device=ids.device)
+    if lib.comic_caption_consensus_workspace(B, W, T, cons.stride) != 0:
+        raise L.ComicHipError('caption_consensus: the workspace query failed')
+    keys, g = cons.idf.device(torch, ids.device) if cons.idf is not None else (None, None)
+    L.check(lib.comic_caption_consensus(
+        ids.data_ptr(), T, B, W, int(end_id), cons.stride, log_probs.data_ptr() if posterior else None, 1 if posterior else 0,
+        L.ptr(keys), L.ptr(g), cons.idf.cap if cons.idf is not None else 0,
+        cons.idf.log_ref_len if cons.idf is not None else 0.0, cons.sigma, util.data_ptr(), best.data_ptr(), None, 0,
+        L.stream_ptr()), 'caption_consensus')
+    return util, best
+
+
+def _attach_consensus(dec, out, pred, cons, forced_posterior, last_scores, on_device):
+    """The consensus launch of a beam_search on its device `pred` [T, B, W]; the result gains `consensus` [B, W] and
+    `consensus_best` [B].  The posterior weights read the final log-probabilities: last_scores, the last executed row of
+    the decode's device `scores`, where that is what the result reports (on_device); the host forms the others (beam
+    groups, required words under a length penalty), and those [B, W] floats are uploaded."""
+    torch = dec.torch
+    posterior = forced_posterior or cons.weights == 'posterior'
+    lp = None
+    if posterior:
+        lp = last_scores if on_device else \
+            torch.from_numpy(np.ascontiguousarray(out['log_probs'], np.float32)).to(pred.device)
+    util, best = caption_consensus(dec.lib, torch, pred, dec.spec.end_id, cons, lp, posterior)
+    out['consensus'], out['consensus_best'] = util.cpu().numpy(), best.cpu().numpy()
+
+
+def consensus_from_config(c, load_idf=True):
+    """The Consensus a configuration asks for (infer_consensus, infer_consensus_df), or None when it sets neither: the
+    uniform weights over the samples, the words of the configuration's token type, and the idf table of the
+    `{pattern}scst-words.p` file infer_consensus_df names (without it every n-gram weighs 1).  `char` tokens,
+    infer_consensus without infer_sample and infer_consensus_df without infer_consensus are ValueErrors.
+    load_idf=False: the checks alone, the file is not read (the Consensus then carries no table)."""
+    on, path = getattr(c, 'infer_consensus', None), getattr(c, 'infer_consensus_df', None)
+    if not on and not path:
+        return None
+    if not on:
+        raise ValueError('infer_consensus_df applies to the consensus selection only: set infer_consensus')
+    if not getattr(c, 'infer_sample', None):
+        raise ValueError('infer_consensus selects among samples: set infer_sample')
+    if c.token_type == 'char':
+        raise ValueError('infer_consensus: the consensus needs `word` or `radix` tokens, not `char`')
+    S = word_stride(c, config_wtoi(c))
+    if path and not os.path.isfile(path):
+        raise ValueError('infer_consensus_df: %s is no file' % path)
+    cons = Consensus('uniform', S, NgramIdf.from_pickle(path, c) if path and load_idf else None)
+    cons.check(c.infer_beam_size, int(c.infer_max_length) * S)
+    return cons
+
+
+def consensus_dir_suffix(c):
+    """'_cns' when the configuration sets infer_consensus, '_cns_df' when it names infer_consensus_df as well, else ''."""
+    if not getattr(c, 'infer_consensus', None):
+        return ''
+    return '_cns_df' if getattr(c, 'infer_consensus_df', None) else '_cns'
 
 
 def process_inputs(captions, token_type):
@@ -1331,7 +1560,8 @@ class Decoder:
         return fetch
 
     def beam_search(self, fm, im_embed, beam, max_steps, want_attention=True, use_graph=True, length_penalty_weight=0.0,
-                    constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None):
+                    constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None,
+                    consensus=None):
         """rnn_decoder_beam_search (ops_rnn.py:49-112).  Returns predicted_ids [T,B,W] (after
         gather_tree), scores [T,B,W] (with length_penalty_weight != 0: the penalised scores the beams were ranked by,
         BeamSearchDecoder's `scores` output), the raw step/parent ids and, unless want_attention=False, the
@@ -1356,7 +1586,14 @@ class Decoder:
         constraints and a length penalty (not with groups or sampling: ValueError).  Slot c * (beam / banks) of
         predicted_ids and scores is bank c's best; the result gains `banks`, `best_slot` [B] (the caption's slot: the
         highest bank that holds a hypothesis) and `met` [B] (the required words that bank stands for, padding included),
-        and `log_probs` [B,W], the final unpenalised log-probabilities.  None: today's path."""
+        and `log_probs` [B,W], the final unpenalised log-probabilities.  None: today's path.
+        consensus: a Consensus; one comic_caption_consensus launch on the device ids right after the tree gather, outside
+        the captured graph, with every decode above: the result gains `consensus` [B,W] float64, every candidate's mean
+        CIDEr-D similarity to its siblings, and `consensus_best` [B] int32, the slot of the largest.  The posterior
+        weights read `log_probs` (without groups, sampling or required words: the last `scores`); with required= they
+        are forced, so that a dead slot (-inf) neither votes nor is chosen.  None: today's path, launch for launch."""
+        if consensus is not None:
+            consensus.check(beam, max_steps)
         if truncation is not None:
             truncation.check(sampling)
         if required is not None:
@@ -1376,7 +1613,8 @@ class Decoder:
                 ens = self._self_ensemble = EnsembleDecoder([self])
             return ens.beam_search(fm, im_embed, beam, max_steps, want_attention=want_attention, use_graph=use_graph,
                                    length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
-                                   sampling=sampling, image_base=image_base, truncation=truncation, required=required)
+                                   sampling=sampling, image_base=image_base, truncation=truncation, required=required,
+                                   consensus=consensus)
         torch, s = self.torch, self.spec
         B, W = fm.shape[0], beam
         # (a non-zero length penalty is another captured graph: the weight is baked into the step kernel's arguments)
@@ -1403,9 +1641,26 @@ class Decoder:
         ln = ctx.lengths.cpu().numpy()
         out = dict(predicted_ids=pred.cpu().numpy(), scores=ctx.scores[:T].cpu().numpy(),
                    step_ids=ctx.step_ids[:T].cpu().numpy(), parent_ids=par, lengths=ln, groups=1)
+        if consensus is not None:
+            _attach_consensus(self, out, pred, consensus, False, ctx.scores[T - 1], True)
         if want_attention:
             out['attn_hist'] = gather_tree_from_array(ctx.hist[:T].cpu().numpy(), par, ln, s.end_id)
         return out
+
+    def consensus(self, ids, cons, log_probs=None):
+        """The raw consensus operator (comic_caption_consensus) on ids [T,B,W], a device tensor or a numpy array of
+        candidates as the tree gather leaves them, under the Consensus `cons`; log_probs [B,W] (float32) is what
+        weights='posterior' reads.  -> (utility [B,W] float64, best [B] int32), numpy."""
+        torch = self.torch
+        ids = ids if torch.is_tensor(ids) else torch.from_numpy(np.ascontiguousarray(ids, np.int32))
+        if ids.dim() != 3:
+            raise ValueError('consensus: ids must be [T, B, W], got shape %r' % (tuple(ids.shape),))
+        ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
+        if log_probs is not None:
+            lp = log_probs if torch.is_tensor(log_probs) else torch.from_numpy(np.ascontiguousarray(log_probs, np.float32))
+            log_probs = lp.to(device=self.device, dtype=torch.float32).contiguous()
+        util, best = caption_consensus(self.lib, torch, ids, self.spec.end_id, cons, log_probs)
+        return util.cpu().numpy(), best.cpu().numpy()
 
 
 def _gather_tree_host(step_ids, parent_ids, max_len, end_token):
@@ -1560,7 +1815,8 @@ class EnsembleDecoder:
         return ctx
 
     def beam_search(self, fms, im_embeds, beam, max_steps, want_attention=False, use_graph=True, length_penalty_weight=0.0,
-                    constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None):
+                    constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None,
+                    consensus=None):
         """fms / im_embeds: one device tensor (every member reads the same features) or a sequence with one per member.
         Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's.  constraints: a
         BeamConstraints; active ones run comic_decoder_beam_constrained, None / inactive ones today's entry point.
@@ -1571,8 +1827,12 @@ class EnsembleDecoder:
         truncation: a BeamTruncation; an active one (sampling only) runs comic_decoder_beam_truncated; the log-probabilities
         stay the untruncated ones, as Decoder.beam_search describes; None / inactive: today's entry points, call for call.
         required: a BeamRequired; runs comic_decoder_beam_required (with the constraints, if any), as Decoder.beam_search
-        describes; None: today's entry points."""
+        describes; None: today's entry points.
+        consensus: a Consensus; one comic_caption_consensus launch on the gathered ids, as Decoder.beam_search describes;
+        None: today's launches."""
         torch, n = self.torch, len(self.decoders)
+        if consensus is not None:
+            consensus.check(beam, max_steps)
         if required is not None:
             B0 = int((fms if torch.is_tensor(fms) else fms[0]).shape[0])
             required.check(self.spec, beam, B0, max_steps, constraints, groups, sampling)
@@ -1669,6 +1929,9 @@ class EnsembleDecoder:
                 lp = (lp * (((5.0 + ln.astype(np.float32)) / 6.0) ** np.float32(length_penalty_weight))).astype(np.float32)
             out['log_probs'], out['banks'] = lp, required.banks
             out['best_slot'], out['met'] = required.result(out['scores'][-1])
+        if consensus is not None:
+            _attach_consensus(self, out, pred, consensus, required is not None, ctx.scores[T - 1],
+                              grp is None and not (required is not None and length_penalty_weight))
         if want_attention:
             out['attn_hist'] = gather_tree_from_array(ctx.hist[:T].cpu().numpy(), par, ln, s.end_id)
         return out

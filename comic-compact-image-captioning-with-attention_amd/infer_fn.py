@@ -117,8 +117,8 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
         if grp is not None:
             G = grp['ids'].shape[1]
             grp_caps = [id_to_caption(grp['ids'][:, g], c) for g in range(G)]
-        # with sampling word_ids is, per image, the sample of highest log-probability; every sample goes to
-        # caption_samples___N.json
+        # with sampling word_ids is, per image, the sample of highest log-probability (with --infer_consensus: the one of
+        # largest consensus, which every sample then carries); every sample goes to caption_samples___N.json
         if smp is not None:
             smp_caps = [id_to_caption(smp['ids'][:, k], c, skip_unmapped=True) for k in range(smp['ids'].shape[1])]
         # with required words word_ids is, per image, the best caption of the highest bank that holds one; every non-empty
@@ -154,7 +154,8 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
                         for k in range(len(rq_caps)) if np.isfinite(rqo['scores'][i, k])]))
             if smp is not None:
                 samples_json.append(dict(image_id=image_id, captions=[
-                    dict(sample=k, caption=str(smp_caps[k][i]), log_prob=float(smp['log_probs'][i, k]))
+                    dict(sample=k, caption=str(smp_caps[k][i]), log_prob=float(smp['log_probs'][i, k]),
+                         **(dict(consensus=float(smp['consensus'][i, k])) if 'consensus' in smp else {}))
                     for k in range(len(smp_caps))]))
     print('\nExample captions:\n{}\n'.format('\n'.join(captions[:3])))
     t = time.time() - start_time

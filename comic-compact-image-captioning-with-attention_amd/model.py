@@ -429,14 +429,14 @@ class ModelBase(object):
 
     # ---- decode (model_base.py:692-757, :272-314) ----------------------------------------
     def _decode(self, images, beam_size, max_length, top_beam=True, want_attention=True, length_penalty_weight=0.0,
-                constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None):
+                constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None, consensus=None):
         im_embed, fm = self._encode(images)
         return self._decode_features(im_embed, fm, beam_size, max_length, top_beam, want_attention, length_penalty_weight,
-                                     constraints, groups, sampling, image_base, truncation, required)
+                                     constraints, groups, sampling, image_base, truncation, required, consensus)
 
     def _decode_features(self, im_embed, fm, beam_size, max_length, top_beam=True, want_attention=True,
                          length_penalty_weight=0.0, constraints=None, groups=None, sampling=None, image_base=0,
-                         truncation=None, required=None):
+                         truncation=None, required=None, consensus=None):
         """constraints: decoder.BeamConstraints in TOKENS (decoder.constraints_from_config translates a configuration's
         words); beam search only.  groups: decoder.BeamGroups; an active one decodes by diverse beam search: the top beam is
         group 0's best (the caption of beam search of width beam / groups), and self.group_output holds the group-best
@@ -447,8 +447,13 @@ class ModelBase(object):
         likeliest tokens and / or the top_p nucleus (sampling only: ValueError otherwise); the log-probabilities stay the
         model's own, untruncated.  required: decoder.BeamRequired with the batch's rows; decodes by banks of constraint progress:
         the top beam is, per image, the best caption of the highest bank that holds one, and self.required_output holds
-        every bank's best (bank_best), None otherwise."""
+        every bank's best (bank_best), None otherwise.  consensus: decoder.Consensus; with active sampling the top beam is,
+        per image, the sample that agrees most with its siblings (the result's consensus_best) instead of the likeliest,
+        the attention maps are that sample's, and sample_output gains `consensus` (B, n); sampling only: ValueError
+        otherwise."""
         c = self._config
+        if consensus is not None and not (sampling is not None and sampling.active):
+            raise ValueError('consensus selects among samples: it needs an active BeamSampling')
         iters = self.decoder.max_iterations(max_length, len(c.wtoi))
         self.required_output = None
         if required is not None:
@@ -477,11 +482,13 @@ class ModelBase(object):
             sampling.check(beam_size, length_penalty_weight, groups)
             r = self.decoder.beam_search(fm, im_embed, beam_size, iters, want_attention=want_attention,
                                          constraints=constraints, sampling=sampling, image_base=image_base,
-                                         truncation=truncation)
+                                         truncation=truncation, consensus=consensus)
             self.sample_output = sample_set(r)
             pred = r['predicted_ids']                                  # (T, B, n)
             T, B = pred.shape[:2]
             best = np.argmax(r['log_probs'], axis=1)                   # (the lowest slot on ties)
+            if consensus is not None:
+                best = np.asarray(r['consensus_best'], np.int64)
             attn = None
             if want_attention:
                 hist = r['attn_hist'].reshape(T, B, beam_size, self.spec.H, self.spec.M)
@@ -540,11 +547,26 @@ def bank_best(r):
                 log_probs=r['log_probs'][:, ::Wb].copy(), bank=np.asarray(r['best_slot']) // Wb, met=np.asarray(r['met']))
 
 
+def decode_consensus(model, consensus):
+    """The Consensus of a decode of `model` (a CaptionModel or a CaptionEnsemble): the argument, else what the model's
+    configuration asks for (decoder.consensus_from_config, read once: the idf table is built and uploaded one time per
+    model)."""
+    if consensus is not None:
+        return consensus
+    if '_consensus_cfg' not in model.__dict__:
+        model._consensus_cfg = cdec.consensus_from_config(model._config)
+    return model._consensus_cfg
+
+
 def sample_set(r):
     """Every sample of a sampled Decoder.beam_search result: ids (B, n, T), their log-probabilities (B, n) under the model
-    (unperturbed, untempered) and their lengths (B, n), in slot order."""
-    return dict(ids=r['predicted_ids'].transpose(1, 2, 0).copy(), log_probs=np.asarray(r['log_probs']).copy(),
-                lengths=np.asarray(r['lengths']).copy())
+    (unperturbed, untempered) and their lengths (B, n), in slot order; after a decode with consensus= also `consensus`
+    (B, n), every sample's mean CIDEr-D similarity to its siblings."""
+    out = dict(ids=r['predicted_ids'].transpose(1, 2, 0).copy(), log_probs=np.asarray(r['log_probs']).copy(),
+               lengths=np.asarray(r['lengths']).copy())
+    if 'consensus' in r:
+        out['consensus'] = np.asarray(r['consensus']).copy()
+    return out
 
 
 class CaptionModel(ModelBase):
@@ -693,7 +715,7 @@ class CaptionModel(ModelBase):
             raise ValueError('required_table holds %d images, the run decodes more' % table.ids.shape[0])
         return cdec.BeamRequired(table.ids[base:base + int(B)])
 
-    def infer(self, batch=None, constraints=None, groups=None, sampling=None, truncation=None):
+    def infer(self, batch=None, constraints=None, groups=None, sampling=None, truncation=None, consensus=None):
         """== sess.run(m_infer.infer_output) -> [dec_preds (B,T), attention_maps (B,H,T,M)].
         constraints: decoder.BeamConstraints; None reads the configuration (infer_min_length, infer_no_repeat_ngram,
         infer_suppress_words).  groups: decoder.BeamGroups; None reads the configuration (infer_beam_groups,
@@ -702,6 +724,8 @@ class CaptionModel(ModelBase):
         With active sampling infer_beam_size is the number of samples per image, dec_preds is per image the sample of
         highest log-probability and self.sample_output = dict(ids (B,n,T), log_probs (B,n), lengths (B,n)).
         truncation: decoder.BeamTruncation; None reads the configuration (infer_top_k, infer_top_p); sampling only.
+        consensus: decoder.Consensus; None reads the configuration (infer_consensus, infer_consensus_df); sampling only:
+        dec_preds is then per image the sample that agrees most with its siblings, and sample_output gains `consensus`.
         Batches drawn from the input pipeline are decoded with the encoder forward of the NEXT group of batches already
         running on a second stream (the decode steps are small launches that leave most of the GPU idle;
         config.pipeline_encoder, default on; config.pipeline_encoder_group batches per forward, 0 = auto).  Same
@@ -727,11 +751,12 @@ class CaptionModel(ModelBase):
                                           length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
                                           constraints=constraints, groups=groups, sampling=sampling,
                                           image_base=self._image_base(sampling, fm.shape[0]), truncation=truncation,
-                                          required=self._required_rows(fm.shape[0]))
+                                          required=self._required_rows(fm.shape[0]), consensus=decode_consensus(self, consensus))
         self.infer_output = [ids, attn]
         return self.infer_output
 
-    def infer_pipelined(self, want_attention=True, constraints=None, groups=None, sampling=None, truncation=None):
+    def infer_pipelined(self, want_attention=True, constraints=None, groups=None, sampling=None, truncation=None,
+                        consensus=None):
         """Generator over the batches of the input pipeline -> [dec_preds (B,T), attention_maps or None] in input order, with
         the decode loops of THREE batches in flight (COMIC_INFER_IN_FLIGHT; one stream and one buffer set of the decoder each:
         Decoder.beam_search_ids(slot=)).
@@ -740,8 +765,9 @@ class CaptionModel(ModelBase):
         baseline (tools/beam_time.py TWO=1), the same ids; three in flight +6 % over two (24.5k against 23.1k captions/s on one
         box; four and five lose: 23.9k, 19.3k -- each loop streams the 52 MB vocabulary projection per step).  Only the captions-only beam search runs this way (no attention
         maps, no length penalty, no beam constraints, no beam groups: what `infer.py` writes unless --save_attention_maps);
-        everything else yields infer().  constraints, groups, sampling, truncation: as infer()."""
+        everything else yields infer().  constraints, groups, sampling, truncation, consensus: as infer()."""
         c, torch = self._config, self.torch
+        consensus = decode_consensus(self, consensus)
         lp = getattr(c, 'infer_length_penalty_weight', 0.0)
         if constraints is None:
             constraints = cdec.constraints_from_config(c)
@@ -752,6 +778,8 @@ class CaptionModel(ModelBase):
         if sampling is None:
             sampling = cdec.sampling_from_config(c)
         constrained = constrained or (sampling is not None and sampling.active)  # (so does sampling)
+        if consensus is not None and not (sampling is not None and sampling.active):
+            raise ValueError('consensus selects among samples: it needs an active BeamSampling')
         constrained = constrained or self.__dict__.get('required_table') is not None      # (and required words)
         if truncation is None:
             truncation = cdec.truncation_from_config(c)
@@ -770,7 +798,7 @@ class CaptionModel(ModelBase):
                                                   constraints=constraints, groups=groups, sampling=sampling,
                                                   image_base=self._image_base(sampling, feats[1].shape[0]),
                                                   truncation=truncation,
-                                                  required=self._required_rows(feats[1].shape[0]))
+                                                  required=self._required_rows(feats[1].shape[0]), consensus=consensus)
                 yield [ids, attn]
         iters = self.decoder.max_iterations(c.infer_max_length, len(c.wtoi))
         lanes = [streams.lane(torch, self.device, 'infer%d' % k) for k in range(NL)]
@@ -1025,10 +1053,11 @@ class CaptionEnsemble(object):
             return [(m._embed(net), fm) for m in self.models]
         return [m._encode(images) for m in self.models]
 
-    def infer(self, batch=None, constraints=None, groups=None, sampling=None, truncation=None):
+    def infer(self, batch=None, constraints=None, groups=None, sampling=None, truncation=None, consensus=None):
         """-> [dec_preds (B,T), attention_maps (B,H,T,M) of member 0], as CaptionModel.infer; without `batch` the images
-        come from member 0's input pipeline.  constraints, groups, sampling, truncation: as CaptionModel.infer."""
+        come from member 0's input pipeline.  constraints, groups, sampling, truncation, consensus: as CaptionModel.infer."""
         c = self._config
+        consensus = decode_consensus(self, consensus)
         if constraints is None:
             constraints = cdec.constraints_from_config(c)
         if groups is None:
@@ -1038,6 +1067,8 @@ class CaptionEnsemble(object):
         if truncation is None:
             truncation = cdec.truncation_from_config(c)
         sampled = sampling is not None and sampling.active
+        if consensus is not None and not sampled:
+            raise ValueError('consensus selects among samples: it needs an active BeamSampling')
         if batch is None:
             batch = next(self.models[0].batch_ops)
         images = batch[0] if isinstance(batch, (tuple, list)) else batch
@@ -1054,7 +1085,7 @@ class CaptionEnsemble(object):
         r = self.decoder.beam_search([f[1] for f in feats], [f[0] for f in feats], W, iters, want_attention=True,
                                      length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
                                      constraints=constraints, groups=groups, sampling=sampling, image_base=base,
-                                     truncation=truncation, required=required)
+                                     truncation=truncation, required=required, consensus=consensus)
         pred = r['predicted_ids']                                  # (T, B, W)
         T, B = pred.shape[:2]
         self.required_output = bank_best(r) if required is not None else None
@@ -1062,6 +1093,8 @@ class CaptionEnsemble(object):
         self.sample_output = sample_set(r) if sampled else None
         # (sampling: per image the sample of highest log-probability, the lowest slot on ties; else the top beam)
         best = np.argmax(r['log_probs'], axis=1) if sampled else np.zeros(B, np.int64)
+        if consensus is not None:           # (consensus: the sample that agrees most with its siblings)
+            best = np.asarray(r['consensus_best'], np.int64)
         if required is not None:            # (required words: the best of the highest bank that holds a caption)
             best = np.asarray(r['best_slot'])
         hist = r['attn_hist'].reshape(T, B, W, spec.H, spec.M)[:, np.arange(B), best]

@@ -702,6 +702,47 @@ int comic_gather_rows(const float* in, const int32_t* parent, float* out, int ro
 int comic_gather_tree(const int32_t* step_ids, const int32_t* parent_ids, const int32_t* max_len,
                       int32_t* out, int T, int B, int W, int end_id, void* stream);
 
+/* Consensus (minimum-Bayes-risk) selection among the W decoded candidates of every image (csrc/consensus.hip; no
+ * counterpart in common/ops_rnn.py): each candidate's mean CIDEr-D similarity to its siblings, directly on token ids, in
+ * one launch -- the similarity of the host scorer below (ciderD_scorer.py:52-222) with the siblings as references.
+ *   Inputs per image b: ids_tbw[:, b, :], W rows of T ids as comic_gather_tree leaves them (every position after the
+ *     first end_id holds end_id); a word length stride >= 1 (1 for `word` tokens, the radix word length for `radix`).
+ *   Units.  L = index of the first end_id of a row (T without one), U = L / stride: a trailing partial word is dropped
+ *     and <EOS> is never a unit.  Unit i is the tokens [i*stride, (i+1)*stride); an n-gram of order k is k consecutive
+ *     units, k = 1..4.
+ *   Weights.  g(ng) = 1 without a table.  With one, g(ng) = log(ref_len) - log(max(1, df(ng))), formed in double on the
+ *     HOST and stored in the table; an n-gram that the table does not hold gets log_ref_len.  The device evaluates no log.
+ *   Vectors.  vec_k[ng] = tf(ng) * g(ng); norm_k = sqrt(sum vec_k^2); len = max(U - 1, 0), the bigram count (the host
+ *     scorer's own rule).
+ *   Similarity of candidate h against sibling r.  Per order k: val_k = sum over the n-grams of h, in order of first
+ *     occurrence, of min(vec_h[ng], vec_r[ng]) * vec_r[ng]; divided by norm_h * norm_r when both are non-zero; times
+ *     exp(-(len_h - len_r)^2 / (2 sigma^2)).  sim = 10 * mean_k val_k.
+ *   Utility.  u[b, w] = sum_{j != w} pi_j sim(c_w, c_j) / sum_{j != w} pi_j, j ascending.  COMIC_CONSENSUS_UNIFORM:
+ *     pi = 1 (the Monte-Carlo estimate over samples; duplicates count once per slot; log_probs is not read and may be
+ *     NULL).  COMIC_CONSENSUS_POSTERIOR: pi = softmax over the W slots of log_probs [B, W] (float32; computed in double;
+ *     -inf gives 0).  A slot with pi = 0 neither votes nor can be chosen, and its utility is -inf.  A zero denominator
+ *     (W = 1, say) gives u = 0.
+ *   Result.  utility_bw [B, W] double; best_b [B]: the slot of largest utility among those with pi > 0, the lowest on
+ *     ties; 0 when there is none.
+ *   Arithmetic.  All float64; every sum is formed by one lane in one fixed order, so two runs give the same bits and no
+ *     result depends on how workgroups interleave.
+ *   Table.  table_keys_or_null: uint64 keys[table_cap] (0 = empty) beside double table_g[table_cap], open addressing with
+ *     linear probing from key & (table_cap - 1); table_cap a power of two, at least twice the number of entries (the
+ *     builder's rule; a probe sequence is cut off after table_cap slots).  The key of an n-gram of m = k * stride tokens:
+ *     h = splitmix64(m), then h = splitmix64(h ^ uint64(token)) for every token in order (csrc/splitmix.h); a result of
+ *     0 is stored and looked up as 1.  INSIDE THE KERNEL TWO N-GRAMS ARE EQUAL WHEN THEIR 64-BIT KEYS ARE: two different
+ *     n-grams of an image that collide (probability ~ n^2 / 2^65 for n n-grams) are counted as one.
+ *   Limits, refused before any launch (rc 2; the workspace query returns -1): 1 <= W <= 32; U <= 64, i.e.
+ *     T <= 64 * stride; 1 <= stride <= 8.
+ * workspace: comic_caption_consensus_workspace bytes (0: every intermediate lives in LDS), may be NULL when that is 0. */
+#define COMIC_CONSENSUS_UNIFORM 0
+#define COMIC_CONSENSUS_POSTERIOR 1
+int64_t comic_caption_consensus_workspace(int B, int W, int T, int stride);
+int comic_caption_consensus(const int32_t* ids_tbw, int T, int B, int W, int end_id, int stride,
+                            const float* log_probs_or_null, int weights_mode, const uint64_t* table_keys_or_null,
+                            const double* table_g, int64_t table_cap, double log_ref_len, double sigma,
+                            double* utility_bw, int32_t* best_b, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Optimiser (model_base.py:852-883; tf.train.AdamOptimizer ApplyAdam, TF-1.9)  */
 /* ------------------------------------------------------------------------- */

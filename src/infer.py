@@ -67,6 +67,13 @@ def create_parser():
     a('--infer_top_p', type=float, default=None,
       help='Sampling: draw every token from the smallest set of likeliest tokens whose probability reaches p (the nucleus; '
            'after --infer_top_k; 1 = off; needs --infer_sample).')
+    a('--infer_consensus', action='store_true', default=None,
+      help='Sampling: captions___N.json keeps, per image, the sample that agrees most with its siblings (their mean '
+           'CIDEr-D similarity, computed on the device) instead of the likeliest; caption_samples___N.json gains every '
+           'sample\'s `consensus`.  Needs --infer_sample; word and radix tokens; output goes to `..._cns`.')
+    a('--infer_consensus_df', type=str, default=None,
+      help='Consensus: the `{pattern}scst-words.p` document-frequency pickle of scst/prepro_ngrams.py for the idf weights of '
+           'the n-grams (without it every n-gram weighs 1); output goes to `..._cns_df`.  Needs --infer_consensus.')
     a('--infer_require_file', type=str, default=None,
       help='Beam search with required words: a JSON file of image file name or image_id -> list of words the caption has '
            'to contain (word and radix tokens); also writes caption_required___N.json with the words met and every '
@@ -158,15 +165,16 @@ def main(argv=None):
     save_name = {'test': 'infer_test_', 'valid': 'infer_valid_', 'coco_test': 'infer_cocoTest_',
                  'coco_valid': 'infer_cocoValid_'}[c.infer_set] + save_name
     # constrained, grouped and sampled captions get a directory of their own: they never overwrite the plain ones
-    from comic_amd.decoder import (constraints_dir_suffix, groups_dir_suffix, groups_from_config, required_dir_suffix,
-                                   required_from_config, sampling_dir_suffix, sampling_from_config, truncation_dir_suffix,
-                                   truncation_from_config)
+    from comic_amd.decoder import (consensus_dir_suffix, consensus_from_config, constraints_dir_suffix, groups_dir_suffix,
+                                   groups_from_config, required_dir_suffix, required_from_config, sampling_dir_suffix,
+                                   sampling_from_config, truncation_dir_suffix, truncation_from_config)
     groups_from_config(c)           # (refuses groups that do not divide infer_beam_size before anything is loaded)
     sampling_from_config(c)         # (refuses sampling with more than one group or a length penalty likewise)
     truncation_from_config(c)       # (refuses --infer_top_k / --infer_top_p without --infer_sample likewise)
     required_from_config(c)         # (refuses a beam size that the banks do not divide, and char tokens, likewise)
     save_name += constraints_dir_suffix(c) + groups_dir_suffix(c) + sampling_dir_suffix(c) + truncation_dir_suffix(c)
-    save_name += required_dir_suffix(c)
+    consensus_from_config(c, load_idf=False)      # (refuses --infer_consensus without --infer_sample, and char tokens)
+    save_name += consensus_dir_suffix(c) + required_dir_suffix(c)
     save_name += ema_dir_suffix(c) + average_dir_suffix(c)      # averaged weights never overwrite the plain captions either
     c.infer_save_path = pjoin(c.infer_checkpoints_dir, save_name)
     if os.path.exists(c.infer_save_path):
