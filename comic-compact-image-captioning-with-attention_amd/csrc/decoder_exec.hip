@@ -2108,7 +2108,7 @@ extern "C" int comic_decoder_beam(const comic_decoder_desc* d, const comic_decod
 // and one ensemble step (beam_step.hip) ranks the candidates for all of them.  Members follow the SAME ids / parents.
 namespace {
 // Workspace of the ensemble loop: the members' InferBufs one after another, then the shared blocks.  carve_ens is the ONE
-// definition: comic_decoder_beam_ensemble_workspace runs it over a null base.  A constrained loop (ban_steps > 0) adds the
+// definition: comic_decoder_beam_search_workspace runs it over a null base.  A constrained loop (ban_steps > 0) adds the
 // ban masks and the two history buffers of beam_bans.hip.
 struct EnsBufs {
   InferBufs m[kEnsMax];
@@ -2131,8 +2131,18 @@ int64_t ens_step_ws_bound(int n, int rows) { return comic_beam_step_split_bytes(
 // truncated: the masks even without constraints, and the truncation's scratch rows
 // required words (req_steps > 0): the banked step's state copy, the per-step table, and the histories unless the
 // constraints keep them already
-EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64_t bytes, int ban_steps = 0,
-                  bool sampled = false, bool truncated = false, int req_steps = 0) {
+struct EnsShape {
+  int ban_steps;
+  bool sampled, truncated;
+  int req_steps;
+};
+// The ONE derivation of that shape from "which options are present": the workspace query and the run both use it.
+EnsShape ens_shape(const comic_beam_options& o, int max_steps) {
+  return EnsShape{o.constraints ? max_steps : 0, o.sampling != nullptr, o.truncation != nullptr, o.required ? max_steps : 0};
+}
+EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64_t bytes, const EnsShape& shape) {
+  const int ban_steps = shape.ban_steps, req_steps = shape.req_steps;
+  const bool sampled = shape.sampled, truncated = shape.truncated;
   EnsBufs e{};
   size_t off = 0;
   e.ok = true;
@@ -2170,32 +2180,43 @@ EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64
 }
 }  // namespace
 
-extern "C" int64_t comic_decoder_beam_ensemble_workspace(const comic_decoder_desc* descs, int n_models, int rows,
-                                                         int max_steps) {
-  (void)max_steps;
+extern "C" int64_t comic_decoder_beam_search_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                       int max_steps, const comic_beam_options* options) {
+  const comic_beam_options o = options ? *options : comic_beam_options{};
   if (!descs || n_models < 1 || n_models > kEnsMax || rows <= 0) return -1;
   for (int m = 0; m < n_models; ++m)
     if (descs[m].D <= 0 || descs[m].V <= 0 || descs[m].M <= 0 || descs[m].H <= 0) return -1;
-  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0).bytes;
-}
-extern "C" int64_t comic_decoder_beam_constrained_workspace(const comic_decoder_desc* descs, int n_models, int rows,
-                                                            int max_steps) {
-  if (max_steps <= 0 || comic_decoder_beam_ensemble_workspace(descs, n_models, rows, max_steps) < 0) return -1;
-  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0, max_steps).bytes;
+  if ((o.constraints || o.required) && max_steps <= 0) return -1;
+  if (o.truncation && comic_beam_truncate_workspace(n_models, rows, 1, descs[0].V) < 0) return -1;
+  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0, ens_shape(o, max_steps)).bytes;
 }
 
 // The ONE ensemble loop.  cons null: comic_decoder_beam_ensemble, launch for launch as it always was; else every step
 // builds the beams' ban masks first (beam_bans.hip) and ranks through them (the Bans policy of beam_step.hip).  grp null:
 // one beam of width W; else the first slot of every group starts live and every step ranks under the Groups policy.  smp
-// null: no sampling; else (grp is null) every slot starts live and step t ranks under the Samples policy.  trc null: no
-// truncation; else (smp is not null) every step narrows the mask by top-k / top-p (beam_truncate.hip) before it ranks.
-static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decoder_params* params, const float* const* fms,
-                             const float* const* im_embeds, const float* weights, int n_models, int B, int W, int max_steps,
-                             int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
-                             float* const* attn_hists, int32_t* steps_executed, const comic_beam_constraints* cons,
-                             const comic_beam_groups* grp, const comic_beam_sampling* smp, void* workspace,
-                             int64_t workspace_bytes, void* stream, const comic_beam_truncation* trc = nullptr,
-                             const comic_beam_required* rqd = nullptr, const int32_t* req = nullptr) {
+// null: no sampling; else (grp is one group at the most) every slot starts live and step t ranks under the Samples policy.
+// trc null: no truncation; else (smp is not null) every step narrows the mask by top-k / top-p (beam_truncate.hip) before
+// it ranks.  rqd null: no required words; else (no sampling, one group at the most, which is no groups) the banks.
+extern "C" int comic_decoder_beam_search(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                         const float* const* fms, const float* const* im_embeds, const float* weights,
+                                         int n_models, int B, int W, int max_steps, const comic_beam_options* options,
+                                         int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths,
+                                         int32_t* finished, float* const* attn_hists, int32_t* steps_executed,
+                                         void* workspace, int64_t workspace_bytes, void* stream) {
+  const comic_beam_options o = options ? *options : comic_beam_options{};
+  const comic_beam_constraints* cons = o.constraints;
+  const comic_beam_sampling* smp = o.sampling;
+  const comic_beam_truncation* trc = o.truncation;
+  const comic_beam_required* rqd = o.required;
+  const comic_beam_groups* grp = rqd ? nullptr : o.groups;
+  const int32_t* req = o.req;
+  COMIC_REQUIRE(!rqd || !o.groups || o.groups->groups <= 1, "beam_required: groups = %d does not combine with required words",
+                o.groups ? o.groups->groups : 0);
+  COMIC_REQUIRE(!rqd || !smp, "beam_required: sampling does not combine with required words");
+  COMIC_REQUIRE(!smp || !grp || grp->groups <= 1, "beam_sampled: sampling does not combine with groups = %d",
+                grp ? grp->groups : 0);
+  COMIC_REQUIRE(!trc || smp, "beam_truncated: null sampling");
+  COMIC_REQUIRE(!rqd || req, "beam_required: null req table");
   COMIC_REQUIRE(descs && params && fms && im_embeds && weights && step_ids && parent_ids && scores && lengths && finished &&
                     steps_executed && workspace,
                 "beam_ensemble: null pointer");
@@ -2216,8 +2237,7 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
   if (trc) RC(comic_beam_truncation_check(trc, "beam_truncated", V, true));
   if (rqd) RC(comic_beam_required_check(rqd, "beam_required", W, V, descs[0].end_id, max_steps, cons));
   hipStream_t st = (hipStream_t)stream;
-  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, cons ? max_steps : 0, smp != nullptr, trc != nullptr,
-                        rqd ? max_steps : 0);
+  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, ens_shape(o, max_steps));
   COMIC_REQUIRE(L.ok && (int64_t)L.bytes <= workspace_bytes, "beam_ensemble: workspace too small");
   g_splitk_ws = L.m[0].splitk;               // members run back to back on the one stream: one split-K scratch serves all
   const float lpw = descs[0].length_penalty_weight;
@@ -2315,14 +2335,56 @@ static int beam_ensemble_run(const comic_decoder_desc* descs, const comic_decode
   return 0;
 }
 
+// ---- the named per-option entries: the frozen version-1 forms -----------------------------------------------------------------
+// Each is its own null checks and one forwarding call.  A workspace query knows its options by their presence alone.
+namespace {
+comic_beam_options present(int cons, bool smp = false, bool trc = false, bool rqd = false) {
+  static const comic_beam_constraints c{};
+  static const comic_beam_sampling s{};
+  static const comic_beam_truncation t{};
+  static const comic_beam_required r{};
+  return comic_beam_options{cons ? &c : nullptr, nullptr, smp ? &s : nullptr, trc ? &t : nullptr, rqd ? &r : nullptr, nullptr};
+}
+}  // namespace
+
+extern "C" int64_t comic_decoder_beam_ensemble_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                         int max_steps) {
+  return comic_decoder_beam_search_workspace(descs, n_models, rows, max_steps, nullptr);
+}
+extern "C" int64_t comic_decoder_beam_constrained_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                            int max_steps) {
+  const comic_beam_options o = present(1);
+  return comic_decoder_beam_search_workspace(descs, n_models, rows, max_steps, &o);
+}
+extern "C" int64_t comic_decoder_beam_diverse_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                        int max_steps, int constrained) {
+  const comic_beam_options o = present(constrained);
+  return comic_decoder_beam_search_workspace(descs, n_models, rows, max_steps, &o);
+}
+extern "C" int64_t comic_decoder_beam_sampled_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                        int max_steps, int constrained) {
+  const comic_beam_options o = present(constrained, true);
+  return comic_decoder_beam_search_workspace(descs, n_models, rows, max_steps, &o);
+}
+extern "C" int64_t comic_decoder_beam_truncated_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                          int max_steps, int constrained) {
+  const comic_beam_options o = present(constrained, true, true);
+  return comic_decoder_beam_search_workspace(descs, n_models, rows, max_steps, &o);
+}
+extern "C" int64_t comic_decoder_beam_required_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                         int max_steps, int constrained) {
+  const comic_beam_options o = present(constrained, false, false, true);
+  return comic_decoder_beam_search_workspace(descs, n_models, rows, max_steps, &o);
+}
+
 extern "C" int comic_decoder_beam_ensemble(const comic_decoder_desc* descs, const comic_decoder_params* params,
                                            const float* const* fms, const float* const* im_embeds, const float* weights,
                                            int n_models, int B, int W, int max_steps, int32_t* step_ids, int32_t* parent_ids,
                                            float* scores, int64_t* lengths, int32_t* finished, float* const* attn_hists,
                                            int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream) {
-  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
-                           lengths, finished, attn_hists, steps_executed, nullptr, nullptr, nullptr, workspace, workspace_bytes,
-                           stream);
+  return comic_decoder_beam_search(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, nullptr, step_ids,
+                                   parent_ids, scores, lengths, finished, attn_hists, steps_executed, workspace,
+                                   workspace_bytes, stream);
 }
 
 extern "C" int comic_decoder_beam_constrained(const comic_decoder_desc* descs, const comic_decoder_params* params,
@@ -2333,15 +2395,10 @@ extern "C" int comic_decoder_beam_constrained(const comic_decoder_desc* descs, c
                                               float* const* attn_hists, int32_t* steps_executed, void* workspace,
                                               int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(constraints, "beam_constrained: null constraints");
-  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
-                           lengths, finished, attn_hists, steps_executed, constraints, nullptr, nullptr, workspace,
-                           workspace_bytes, stream);
-}
-
-extern "C" int64_t comic_decoder_beam_diverse_workspace(const comic_decoder_desc* descs, int n_models, int rows,
-                                                        int max_steps, int constrained) {
-  return constrained ? comic_decoder_beam_constrained_workspace(descs, n_models, rows, max_steps)
-                     : comic_decoder_beam_ensemble_workspace(descs, n_models, rows, max_steps);
+  const comic_beam_options o{constraints, nullptr, nullptr, nullptr, nullptr, nullptr};
+  return comic_decoder_beam_search(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, &o, step_ids,
+                                   parent_ids, scores, lengths, finished, attn_hists, steps_executed, workspace,
+                                   workspace_bytes, stream);
 }
 
 extern "C" int comic_decoder_beam_diverse(const comic_decoder_desc* descs, const comic_decoder_params* params,
@@ -2352,15 +2409,10 @@ extern "C" int comic_decoder_beam_diverse(const comic_decoder_desc* descs, const
                                           int32_t* finished, float* const* attn_hists, int32_t* steps_executed,
                                           void* workspace, int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(groups, "beam_diverse: null groups");
-  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
-                           lengths, finished, attn_hists, steps_executed, constraints, groups, nullptr, workspace,
-                           workspace_bytes, stream);
-}
-
-extern "C" int64_t comic_decoder_beam_sampled_workspace(const comic_decoder_desc* descs, int n_models, int rows,
-                                                        int max_steps, int constrained) {
-  if (comic_decoder_beam_diverse_workspace(descs, n_models, rows, max_steps, constrained) < 0) return -1;
-  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0, constrained ? max_steps : 0, true).bytes;
+  const comic_beam_options o{constraints, groups, nullptr, nullptr, nullptr, nullptr};
+  return comic_decoder_beam_search(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, &o, step_ids,
+                                   parent_ids, scores, lengths, finished, attn_hists, steps_executed, workspace,
+                                   workspace_bytes, stream);
 }
 
 extern "C" int comic_decoder_beam_sampled(const comic_decoder_desc* descs, const comic_decoder_params* params,
@@ -2371,16 +2423,10 @@ extern "C" int comic_decoder_beam_sampled(const comic_decoder_desc* descs, const
                                           int32_t* finished, float* const* attn_hists, int32_t* steps_executed,
                                           void* workspace, int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(sampling, "beam_sampled: null sampling");
-  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
-                           lengths, finished, attn_hists, steps_executed, constraints, nullptr, sampling, workspace,
-                           workspace_bytes, stream);
-}
-
-extern "C" int64_t comic_decoder_beam_truncated_workspace(const comic_decoder_desc* descs, int n_models, int rows,
-                                                          int max_steps, int constrained) {
-  if (comic_decoder_beam_sampled_workspace(descs, n_models, rows, max_steps, constrained) < 0) return -1;
-  if (comic_beam_truncate_workspace(n_models, rows, 1, descs[0].V) < 0) return -1;
-  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0, constrained ? max_steps : 0, true, true).bytes;
+  const comic_beam_options o{constraints, nullptr, sampling, nullptr, nullptr, nullptr};
+  return comic_decoder_beam_search(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, &o, step_ids,
+                                   parent_ids, scores, lengths, finished, attn_hists, steps_executed, workspace,
+                                   workspace_bytes, stream);
 }
 
 extern "C" int comic_decoder_beam_truncated(const comic_decoder_desc* descs, const comic_decoder_params* params,
@@ -2393,15 +2439,10 @@ extern "C" int comic_decoder_beam_truncated(const comic_decoder_desc* descs, con
                                             void* stream) {
   COMIC_REQUIRE(sampling, "beam_truncated: null sampling");
   COMIC_REQUIRE(truncation, "beam_truncated: null truncation");
-  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
-                           lengths, finished, attn_hists, steps_executed, constraints, nullptr, sampling, workspace,
-                           workspace_bytes, stream, truncation);
-}
-
-extern "C" int64_t comic_decoder_beam_required_workspace(const comic_decoder_desc* descs, int n_models, int rows,
-                                                         int max_steps, int constrained) {
-  if (max_steps <= 0 || comic_decoder_beam_ensemble_workspace(descs, n_models, rows, max_steps) < 0) return -1;
-  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0, constrained ? max_steps : 0, false, false, max_steps).bytes;
+  const comic_beam_options o{constraints, nullptr, sampling, truncation, nullptr, nullptr};
+  return comic_decoder_beam_search(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, &o, step_ids,
+                                   parent_ids, scores, lengths, finished, attn_hists, steps_executed, workspace,
+                                   workspace_bytes, stream);
 }
 
 extern "C" int comic_decoder_beam_required(const comic_decoder_desc* descs, const comic_decoder_params* params,
@@ -2414,10 +2455,8 @@ extern "C" int comic_decoder_beam_required(const comic_decoder_desc* descs, cons
                                            int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream) {
   COMIC_REQUIRE(required, "beam_required: null required");
   COMIC_REQUIRE(req, "beam_required: null req table");
-  COMIC_REQUIRE(!groups || groups->groups <= 1, "beam_required: groups = %d does not combine with required words",
-                groups ? groups->groups : 0);
-  COMIC_REQUIRE(!sampling, "beam_required: sampling does not combine with required words");
-  return beam_ensemble_run(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, step_ids, parent_ids, scores,
-                           lengths, finished, attn_hists, steps_executed, constraints, nullptr, nullptr, workspace,
-                           workspace_bytes, stream, nullptr, required, req);
+  const comic_beam_options o{constraints, groups, sampling, nullptr, required, req};
+  return comic_decoder_beam_search(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, &o, step_ids,
+                                   parent_ids, scores, lengths, finished, attn_hists, steps_executed, workspace,
+                                   workspace_bytes, stream);
 }

@@ -252,7 +252,17 @@ class FlatParams:
         return int(sum(int(np.prod(s)) if len(s) else 1 for s in self.shapes.values()))
 
 
-class BeamConstraints:
+class _Keyed:
+    """Equality and hash of an immutable option class, from its key()."""
+
+    def __eq__(self, other):
+        return type(other) is type(self) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+
+class BeamConstraints(_Keyed):
     """What a beam may emit (comic_beam_constraints; extends rnn_decoder_beam_search, ops_rnn.py:49-112), in TOKENS:
     min_length: no <EOS> before that many tokens; no_repeat_ngram = n: no n-gram twice (0: off), with windows that start at
     multiples of ngram_stride (n % ngram_stride == 0; the radix word length makes the windows whole words); suppress: up to
@@ -266,12 +276,6 @@ class BeamConstraints:
 
     def key(self):
         return (self.min_length, self.no_repeat_ngram, self.ngram_stride, self.suppress)
-
-    def __eq__(self, other):
-        return isinstance(other, BeamConstraints) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         return 'BeamConstraints(min_length=%d, no_repeat_ngram=%d, ngram_stride=%d, suppress=%r)' % self.key()
@@ -351,7 +355,7 @@ def constraints_dir_suffix(c):
     return '_min%d_ngram%d_sup%d' % (int(m or 0), int(n or 0), len(sup or ()))
 
 
-class BeamGroups:
+class BeamGroups(_Keyed):
     """Diverse beam search (comic_beam_groups; Vijayakumar et al. 2016 with the Hamming diversity; extends
     rnn_decoder_beam_search, ops_rnn.py:49-112): the beam is split into `groups` groups of beam / groups slots, decided in
     order at every step; a later group ranks a candidate token by its score minus `diversity` times the number of slots of
@@ -364,12 +368,6 @@ class BeamGroups:
 
     def key(self):
         return (self.groups, self.diversity)
-
-    def __eq__(self, other):
-        return isinstance(other, BeamGroups) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         return 'BeamGroups(groups=%d, diversity=%r)' % self.key()
@@ -434,7 +432,7 @@ def groups_dir_suffix(c):
     return '_grp%d_div%g' % (int(1 if g is None else g), float(0.0 if d is None else d))
 
 
-class BeamRequired:
+class BeamRequired(_Keyed):
     """Beam search with required words (comic_beam_required; Anderson et al. 2017, the bank form of Post & Vilar 2018;
     extends rnn_decoder_beam_search, ops_rnn.py:49-112).  ids: int32 [B, C, S], -1 padded: row (b, q) is the S tokens of
     required word q of image b (S = 1 for word tokens, the radix word length for radix tokens), or all -1.  The beam is
@@ -452,12 +450,6 @@ class BeamRequired:
 
     def key(self):
         return (self.n_words, self.stride)
-
-    def __eq__(self, other):
-        return isinstance(other, BeamRequired) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         return 'BeamRequired(n_words=%d, stride=%d, images=%d)' % (self.n_words, self.stride, self.ids.shape[0])
@@ -621,7 +613,7 @@ def required_dir_suffix(c):
     return '_req%d_%s' % (required_from_config(c)['n_words'], os.path.splitext(os.path.basename(path))[0])
 
 
-class BeamSampling:
+class BeamSampling(_Keyed):
     """Sampling inside the beam step (comic_beam_sampling; extends rnn_decoder_beam_search, ops_rnn.py:49-112): the `beam`
     slots of an image are `beam` independent chains, each drawn from the step distribution at `temperature` by the
     Gumbel-max rule, with noise from a counter-based generator keyed by (seed, the image's index in the run, slot, step,
@@ -634,12 +626,6 @@ class BeamSampling:
 
     def key(self):
         return (self.temperature, self.seed, self.enabled)
-
-    def __eq__(self, other):
-        return isinstance(other, BeamSampling) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         return 'BeamSampling(temperature=%r, seed=%d%s)' % (self.temperature, self.seed, '' if self.enabled else ', enabled=False')
@@ -705,7 +691,7 @@ def sampling_dir_suffix(c):
     return '_smp_t%g_s%d' % (float(1.0 if t is None else t), int(0 if seed is None else seed))
 
 
-class BeamTruncation:
+class BeamTruncation(_Keyed):
     """Top-k and nucleus (top-p) truncation of the sampled step (comic_beam_truncation; extends rnn_decoder_beam_search,
     ops_rnn.py:49-112): a live slot draws from the `top_k` likeliest tokens of the tempered step distribution only
     (0 = off; ties by lowest id), and of those from the smallest set of likeliest tokens whose probability, renormalised
@@ -720,12 +706,6 @@ class BeamTruncation:
 
     def key(self):
         return (self.top_k, self.top_p)
-
-    def __eq__(self, other):
-        return isinstance(other, BeamTruncation) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         return 'BeamTruncation(top_k=%d, top_p=%r)' % self.key()
@@ -881,7 +861,7 @@ class NgramIdf:
         return t
 
 
-class Consensus:
+class Consensus(_Keyed):
     """Consensus (minimum-Bayes-risk) selection among the W candidates of an image (comic_caption_consensus; no counterpart
     in common/ops_rnn.py): the utility of a candidate is its mean CIDEr-D similarity (n-grams of 1..4 words, sigma) to its
     siblings, weighted by `weights`: 'uniform' (the Monte-Carlo estimate, for samples) or 'posterior' (the softmax of the
@@ -896,12 +876,6 @@ class Consensus:
 
     def key(self):
         return (self.weights, self.stride, self.sigma, id(self.idf) if self.idf is not None else None)
-
-    def __eq__(self, other):
-        return isinstance(other, Consensus) and self.key() == other.key()
-
-    def __hash__(self):
-        return hash(self.key())
 
     def __repr__(self):
         return 'Consensus(weights=%r, stride=%d, idf=%r, sigma=%r)' % (self.weights, self.stride, self.idf, self.sigma)
@@ -964,6 +938,52 @@ def _attach_consensus(dec, out, pred, cons, forced_posterior, last_scores, on_de
     out['consensus'], out['consensus_best'] = util.cpu().numpy(), best.cpu().numpy()
 
 
+def _beam_outputs(ctx, torch, device, B, W, max_steps):
+    """The beam executors' output buffers of a decode context (Decoder._infer_ctx, EnsembleDecoder._ctx)."""
+    i32 = dict(dtype=torch.int32, device=device)
+    # rows past the executed steps are never written (device-side early exit): poison them so a
+    # kernel that indexes through them fails the same way every time
+    ctx.step_ids = torch.full((max_steps, B, W), 0x7f7f7f7f, **i32)
+    ctx.parent_ids = torch.full((max_steps, B, W), 0x7f7f7f7f, **i32)
+    ctx.scores = torch.empty((max_steps, B, W), dtype=torch.float32, device=device)
+    ctx.lengths = torch.empty((B, W), dtype=torch.int64, device=device)
+    ctx.finished = torch.empty((B, W), **i32)
+    ctx.steps = torch.empty(1, **i32)
+
+
+def _beam_result(dec, ctx, B, W, opts, want_attention):
+    """The result dict of a beam_search from its finished context: the tree gather, the fetches, what the options add
+    (`groups`, `log_probs`, `banks`, `best_slot`, `met`), the consensus launch and the beam-sorted alignments (ctx.hist)."""
+    torch, s, lpw = dec.torch, dec.spec, opts.length_penalty_weight
+    grp, smp, rqd = opts.grp, opts.smp, opts.required
+    T = int(ctx.steps.item())
+    max_len = ctx.lengths.max(dim=1).values.to(torch.int32).contiguous()
+    pred = torch.empty((T, B, W), dtype=torch.int32, device=dec.device)
+    L.check(dec.lib.comic_gather_tree(ctx.step_ids[:T].data_ptr(), ctx.parent_ids[:T].data_ptr(), max_len.data_ptr(),
+                                      pred.data_ptr(), T, B, W, s.end_id, L.stream_ptr()), 'gather_tree')
+    par = ctx.parent_ids[:T].cpu().numpy()
+    ln = ctx.lengths.cpu().numpy()
+    out = dict(predicted_ids=pred.cpu().numpy(), scores=ctx.scores[:T].cpu().numpy(),
+               step_ids=ctx.step_ids[:T].cpu().numpy(), parent_ids=par, lengths=ln, groups=1)
+    if grp is not None:
+        out['groups'] = grp.groups
+        out['log_probs'] = grp.final_log_probs(out['scores'], out['step_ids'], ln, s.end_id, lpw)
+    if smp is not None:                 # the state after the last executed step: a finished chain's carries over
+        out['log_probs'] = out['scores'][-1].copy()
+    if rqd is not None:                 # the unpenalised totals: the last scores times the length penalty's divisor
+        lp = out['scores'][-1].copy()
+        if lpw:
+            lp = (lp * (((5.0 + ln.astype(np.float32)) / 6.0) ** np.float32(lpw))).astype(np.float32)
+        out['log_probs'], out['banks'] = lp, rqd.banks
+        out['best_slot'], out['met'] = rqd.result(out['scores'][-1])
+    if opts.consensus is not None:
+        _attach_consensus(dec, out, pred, opts.consensus, rqd is not None, ctx.scores[T - 1],
+                          grp is None and not (rqd is not None and lpw))
+    if want_attention:
+        out['attn_hist'] = gather_tree_from_array(ctx.hist[:T].cpu().numpy(), par, ln, s.end_id)
+    return out
+
+
 def consensus_from_config(c, load_idf=True):
     """The Consensus a configuration asks for (infer_consensus, infer_consensus_df), or None when it sets neither: the
     uniform weights over the samples, the words of the configuration's token type, and the idf table of the
@@ -992,6 +1012,97 @@ def consensus_dir_suffix(c):
     if not getattr(c, 'infer_consensus', None):
         return ''
     return '_cns_df' if getattr(c, 'infer_consensus_df', None) else '_cns'
+
+
+def _active(option):
+    return option if option is not None and option.active else None
+
+
+@dataclass(frozen=True)
+class BeamOptions:
+    """Which decode a beam search is, as one immutable value (comic_beam_options; extends rnn_decoder_beam_search,
+    ops_rnn.py:49-112): the length penalty, the five executor options, the consensus selection that follows the decode, and
+    image_base, the index in the run of the batch's first image (sampling).  Built once per call, checked once, keyed
+    once and handed to the one C entry, comic_decoder_beam_search.  cons / grp / smp / trc are the ACTIVE options or None:
+    what the executor is given."""
+    length_penalty_weight: float = 0.0
+    constraints: BeamConstraints | None = None
+    groups: BeamGroups | None = None
+    sampling: BeamSampling | None = None
+    truncation: BeamTruncation | None = None
+    required: BeamRequired | None = None
+    consensus: Consensus | None = None
+    image_base: int = 0
+
+    cons = property(lambda self: _active(self.constraints))
+    grp = property(lambda self: _active(self.groups))
+    smp = property(lambda self: _active(self.sampling))
+    trc = property(lambda self: _active(self.truncation))
+
+    @classmethod
+    def of(cls, options, **keywords):
+        """The one BeamOptions of a beam_search call: `options`, or the option keywords; both is a ValueError."""
+        if options is None:
+            return cls(**keywords)
+        if any(v is not None and v != 0 for v in keywords.values()):
+            raise ValueError('beam_search: give `options` or the option keywords, not both')
+        return options
+
+    @property
+    def active(self):
+        """Whether any executor option is on: the ensemble executor decodes, not Decoder's fast single-member one."""
+        return any(x is not None for x in (self.cons, self.grp, self.smp, self.required))
+
+    def check(self, spec, beam, batch, max_steps):
+        """Every option's rules and the rules between them, on the host before anything is built or launched."""
+        if self.consensus is not None:
+            self.consensus.check(beam, max_steps)
+        if self.truncation is not None:
+            self.truncation.check(self.sampling)
+        if self.required is not None:
+            self.required.check(spec, beam, batch, max_steps, self.constraints, self.groups, self.sampling)
+        if self.groups is not None:
+            self.groups.check(beam, spec.V)
+        if self.sampling is not None:
+            self.sampling.check(beam, self.length_penalty_weight, self.groups)
+        if self.cons is not None:
+            self.cons.check(spec, beam, max_steps)
+
+    def ctx_key(self):
+        """What a captured graph bakes in: the penalty weight, the constraints, the groups, the temperature, top_k / top_p
+        (the floats as the fp32 values the kernels see) and (n_words, stride).  Not what is written in front of every launch:
+        the seed, image_base and the required table.  None and every inactive option give the plain key."""
+        return (float(self.length_penalty_weight),) + tuple(
+            None if x is None else key(x) for x, key in (
+                (self.cons, BeamConstraints.key), (self.grp, BeamGroups.key), (self.smp, BeamSampling.ctx_key),
+                (self.trc, BeamTruncation.ctx_key), (self.required, BeamRequired.ctx_key)))
+
+    def c_record(self, ctx):
+        """The comic_beam_options of a decode context.  The structs it points to are kept alive on the context (ctx.cons,
+        .grp, .smp, .trc, .rqd: None where the option is off); sampling and required words name the context's device words
+        ctx.seed and ctx.req."""
+        ctx.cons, ctx.grp, ctx.trc, ctx.rqd = (None if x is None else x.c_struct()
+                                               for x in (self.cons, self.grp, self.trc, self.required))
+        ctx.smp = None if self.smp is None else self.smp.c_struct(ctx.seed.data_ptr())
+        return L.BeamOptions(*[None if x is None else C.addressof(x) for x in (ctx.cons, ctx.grp, ctx.smp, ctx.trc, ctx.rqd)],
+                             ctx.req.data_ptr() if self.required is not None else None)
+
+
+def options_from_config(c, load=True):
+    """The BeamOptions a configuration asks for, without the per-batch parts (the required rows, image_base).
+    load=False: the refusals alone, in the order the command line has always raised them, with nothing read that a run
+    reads later: no idf table, and no constraints (their words map through the vocabulary of the input manager)."""
+    grp, smp, trc = groups_from_config(c), sampling_from_config(c), truncation_from_config(c)
+    required_from_config(c)
+    cns = consensus_from_config(c, load_idf=load)
+    return BeamOptions(getattr(c, 'infer_length_penalty_weight', 0.0) or 0.0, constraints_from_config(c) if load else None,
+                       grp, smp, trc, None, cns)
+
+
+def decode_dir_suffix(c):
+    """The directory suffix of a configuration's decode: every option's own, in the order they were added."""
+    return (constraints_dir_suffix(c) + groups_dir_suffix(c) + sampling_dir_suffix(c) + truncation_dir_suffix(c)
+            + consensus_dir_suffix(c) + required_dir_suffix(c))
 
 
 def process_inputs(captions, token_type):
@@ -1419,14 +1530,7 @@ class Decoder:
                 ctx.logits = torch.empty((max_steps, B, s.V), **f32) if want_logits else None
                 ctx.first_eos = torch.empty(B, **i32)
             else:
-                # rows past the executed steps are never written (device-side early exit): poison them so a
-                # kernel that indexes through them fails the same way every time
-                ctx.step_ids = torch.full((max_steps, B, W), 0x7f7f7f7f, **i32)
-                ctx.parent_ids = torch.full((max_steps, B, W), 0x7f7f7f7f, **i32)
-                ctx.scores = torch.empty((max_steps, B, W), **f32)
-                ctx.lengths = torch.empty((B, W), dtype=torch.int64, device=self.device)
-                ctx.finished = torch.empty((B, W), **i32)
-                ctx.steps = torch.empty(1, **i32)
+                _beam_outputs(ctx, torch, self.device, B, W, max_steps)
             ctx.desc = s.desc(False)
             ctx.nbytes = int(self.lib.comic_decoder_infer_workspace(C.byref(ctx.desc), R, max_steps))
             ctx.ws = torch.empty(ctx.nbytes, dtype=torch.uint8, device=self.device)   # own workspace: graph-stable
@@ -1521,6 +1625,15 @@ class Decoder:
         hist = ctx.hist[:t_exec].reshape(t_exec, B, s.H, s.M).permute(1, 2, 0, 3).clone()
         return out_ids, hist, (ctx.logits[:t_exec].permute(1, 0, 2).clone() if want_logits else None)
 
+    def _launch_beam(self, ctx, B, W, max_steps):
+        """The comic_decoder_beam call of a 'beam' context (capturable): beam_search_ids' and the plain beam_search's."""
+        ctx.desc.flags = L.decoder_flags_from_env()
+        L.check(self.lib.comic_decoder_beam(C.byref(ctx.desc), C.byref(ctx.ptab), ctx.fm.data_ptr(), ctx.im.data_ptr(), B, W,
+                                            max_steps, ctx.step_ids.data_ptr(), ctx.parent_ids.data_ptr(),
+                                            ctx.scores.data_ptr(), ctx.lengths.data_ptr(), ctx.finished.data_ptr(),
+                                            ctx.hist.data_ptr(), ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
+                                            L.stream_ptr()), 'decoder_beam')
+
     def beam_search_ids(self, fm, im_embed, beam, max_steps, use_graph=True, slot=0):
         """Beam search for its predicted ids alone, fetched WITHOUT draining the stream: the loop, gather_tree over all
         max_steps rows (rows past the executed steps come out as end_id) and the copies to pinned memory are enqueued, an
@@ -1531,16 +1644,7 @@ class Decoder:
         B, W = fm.shape[0], beam
         ctx = self._infer_ctx('beam', B, W, max_steps, False, fm, im_embed, slot=slot)
         ctx.desc.length_penalty_weight = 0.0
-
-        def launch():
-            ctx.desc.flags = L.decoder_flags_from_env()
-            L.check(self.lib.comic_decoder_beam(C.byref(ctx.desc), C.byref(ctx.ptab), ctx.fm.data_ptr(),
-                                                ctx.im.data_ptr(), B, W, max_steps, ctx.step_ids.data_ptr(),
-                                                ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(),
-                                                ctx.lengths.data_ptr(), ctx.finished.data_ptr(), ctx.hist.data_ptr(),
-                                                ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes, L.stream_ptr()),
-                    'decoder_beam')
-        self._run_infer(ctx, launch, use_graph)
+        self._run_infer(ctx, lambda: self._launch_beam(ctx, B, W, max_steps), use_graph)
         if getattr(ctx, 'pred', None) is None:
             ctx.pred = torch.empty((max_steps, B, W), dtype=torch.int32, device=self.device)
             ctx.pred_host = torch.empty((max_steps, B, W), dtype=torch.int32).pin_memory()
@@ -1561,28 +1665,28 @@ class Decoder:
 
     def beam_search(self, fm, im_embed, beam, max_steps, want_attention=True, use_graph=True, length_penalty_weight=0.0,
                     constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None,
-                    consensus=None):
+                    consensus=None, options=None):
         """rnn_decoder_beam_search (ops_rnn.py:49-112).  Returns predicted_ids [T,B,W] (after
         gather_tree), scores [T,B,W] (with length_penalty_weight != 0: the penalised scores the beams were ranked by,
         BeamSearchDecoder's `scores` output), the raw step/parent ids and, unless want_attention=False, the
         beam-sorted alignment history [T,B*W,H*M] (numpy; BeamSearchDecoderMultiHead,
         ops_rnn.py:807-845 -- host post-processing that only visualisation needs).
-        constraints: a BeamConstraints; active ones decode as a one-member ensemble through the constrained executor
-        (comic_decoder_beam_constrained), None / inactive ones change nothing.
-        groups: a BeamGroups (diverse beam search); an active one (groups > 1) decodes the same way through
-        comic_decoder_beam_diverse, alone or with constraints: slot g * (beam / groups) of predicted_ids and scores is
+        The options below come as these keywords or as one BeamOptions in `options` (both: ValueError); any active one
+        decodes as a one-member ensemble through the one executor entry (comic_decoder_beam_search).
+        constraints: a BeamConstraints; None / inactive ones change nothing.
+        groups: a BeamGroups (diverse beam search); an active one (groups > 1) decodes alone or with constraints: slot g * (beam / groups) of predicted_ids and scores is
         group g's best caption, and the result carries `log_probs` [B,W] (BeamGroups.final_log_probs).  None / inactive:
         today's path.  The result's `groups` holds the number of groups (1 without).
-        sampling: a BeamSampling; an active one draws `beam` samples per image through comic_decoder_beam_sampled, alone or
-        with constraints (not with more than one group or a length penalty: ValueError): slot w of predicted_ids is sample
+        sampling: a BeamSampling; an active one draws `beam` samples per image, alone or with
+        constraints (not with more than one group or a length penalty: ValueError): slot w of predicted_ids is sample
         w, `scores` the chains' running log p(caption | image) and `log_probs` [B,beam] the final ones; image_base is the
         index in the run of the batch's first image (the noise of an image does not depend on its batch).  None /
         inactive: today's path.
         truncation: a BeamTruncation; an active one (with active sampling: ValueError otherwise) restricts every draw to the
-        top_k likeliest tokens and / or the top_p nucleus through comic_decoder_beam_truncated.  `scores` / `log_probs` stay
+        top_k likeliest tokens and / or the top_p nucleus.  `scores` / `log_probs` stay
         the model's own unperturbed, untempered, UNTRUNCATED log p(caption | image) -- Decoder.score reproduces them -- not
         the log-probability under the truncated distribution.  None / inactive: today's path, call for call.
-        required: a BeamRequired (one row of words per image); decodes through comic_decoder_beam_required, alone or with
+        required: a BeamRequired (one row of words per image); decodes by banks, alone or with
         constraints and a length penalty (not with groups or sampling: ValueError).  Slot c * (beam / banks) of
         predicted_ids and scores is bank c's best; the result gains `banks`, `best_slot` [B] (the caption's slot: the
         highest bank that holds a hypothesis) and `met` [B] (the required words that bank stands for, padding included),
@@ -1592,60 +1696,22 @@ class Decoder:
         CIDEr-D similarity to its siblings, and `consensus_best` [B] int32, the slot of the largest.  The posterior
         weights read `log_probs` (without groups, sampling or required words: the last `scores`); with required= they
         are forced, so that a dead slot (-inf) neither votes nor is chosen.  None: today's path, launch for launch."""
-        if consensus is not None:
-            consensus.check(beam, max_steps)
-        if truncation is not None:
-            truncation.check(sampling)
-        if required is not None:
-            required.check(self.spec, beam, fm.shape[0], max_steps, constraints, groups, sampling)
-        constrained = constraints is not None and constraints.active
-        grouped = groups is not None and groups.active
-        sampled = sampling is not None and sampling.active
-        if groups is not None:
-            groups.check(beam, self.spec.V)
-        if sampling is not None:
-            sampling.check(beam, length_penalty_weight, groups)
-        if constrained or grouped or sampled or required is not None:
-            if constrained:
-                constraints.check(self.spec, beam, max_steps)
+        opts = BeamOptions.of(options, length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
+                              sampling=sampling, truncation=truncation, required=required, consensus=consensus,
+                              image_base=image_base)
+        B, W = fm.shape[0], beam
+        opts.check(self.spec, W, B, max_steps)
+        if opts.active:
             ens = self.__dict__.get('_self_ensemble')
             if ens is None:
                 ens = self._self_ensemble = EnsembleDecoder([self])
-            return ens.beam_search(fm, im_embed, beam, max_steps, want_attention=want_attention, use_graph=use_graph,
-                                   length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
-                                   sampling=sampling, image_base=image_base, truncation=truncation, required=required,
-                                   consensus=consensus)
-        torch, s = self.torch, self.spec
-        B, W = fm.shape[0], beam
+            return ens._decode([fm], [im_embed], W, max_steps, want_attention, use_graph, opts)
         # (a non-zero length penalty is another captured graph: the weight is baked into the step kernel's arguments)
-        ctx = self._infer_ctx('beam' if not length_penalty_weight else 'beam_lp%r' % float(length_penalty_weight), B, W,
-                              max_steps, False, fm, im_embed)
-        ctx.desc.length_penalty_weight = float(length_penalty_weight)
-
-        def launch():
-            ctx.desc.flags = L.decoder_flags_from_env()
-            L.check(self.lib.comic_decoder_beam(C.byref(ctx.desc), C.byref(ctx.ptab), ctx.fm.data_ptr(),
-                                                ctx.im.data_ptr(), B, W, max_steps, ctx.step_ids.data_ptr(),
-                                                ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(),
-                                                ctx.lengths.data_ptr(), ctx.finished.data_ptr(), ctx.hist.data_ptr(),
-                                                ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes, L.stream_ptr()),
-                    'decoder_beam')
-        self._run_infer(ctx, launch, use_graph)
-        T = int(ctx.steps.item())
-        max_len = ctx.lengths.max(dim=1).values.to(torch.int32).contiguous()
-        pred = torch.empty((T, B, W), dtype=torch.int32, device=self.device)
-        L.check(self.lib.comic_gather_tree(ctx.step_ids[:T].data_ptr(), ctx.parent_ids[:T].data_ptr(),
-                                           max_len.data_ptr(), pred.data_ptr(), T, B, W, s.end_id, L.stream_ptr()),
-                'gather_tree')
-        par = ctx.parent_ids[:T].cpu().numpy()
-        ln = ctx.lengths.cpu().numpy()
-        out = dict(predicted_ids=pred.cpu().numpy(), scores=ctx.scores[:T].cpu().numpy(),
-                   step_ids=ctx.step_ids[:T].cpu().numpy(), parent_ids=par, lengths=ln, groups=1)
-        if consensus is not None:
-            _attach_consensus(self, out, pred, consensus, False, ctx.scores[T - 1], True)
-        if want_attention:
-            out['attn_hist'] = gather_tree_from_array(ctx.hist[:T].cpu().numpy(), par, ln, s.end_id)
-        return out
+        lpw = float(opts.length_penalty_weight)
+        ctx = self._infer_ctx('beam' if not lpw else 'beam_lp%r' % lpw, B, W, max_steps, False, fm, im_embed)
+        ctx.desc.length_penalty_weight = lpw
+        self._run_infer(ctx, lambda: self._launch_beam(ctx, B, W, max_steps), use_graph)
+        return _beam_result(self, ctx, B, W, opts, want_attention)
 
     def consensus(self, ids, cons, log_probs=None):
         """The raw consensus operator (comic_caption_consensus) on ids [T,B,W], a device tensor or a numpy array of
@@ -1736,75 +1802,37 @@ class EnsembleDecoder:
         self.torch, self.lib, self.device = decoders[0].torch, decoders[0].lib, decoders[0].device
         self._ctxs = {}
 
-    def _ctx(self, B, W, max_steps, lpw, feats, cons=None, grp=None, smp=None, trc=None, rqd=None):
+    def _ctx(self, B, W, max_steps, feats, opts):
         """Persistent buffers (+ a hipGraph of the whole loop, captured on the second call with the shape), as
-        Decoder._infer_ctx.  cons: active BeamConstraints (they are baked into the captured launches) or None; grp: active
-        BeamGroups (baked in likewise) or None; smp: active BeamSampling or None -- its temperature is baked in and part
-        of the key, its seed words are not: they live in ctx.seed, which beam_search writes in front of every launch;
-        trc: active BeamTruncation (with smp) or None -- baked in, part of the key; rqd: BeamRequired or None -- its
-        (n_words, stride) are baked in and part of the key, its table is not: it lives in ctx.req, which beam_search
-        writes in front of every launch."""
+        Decoder._infer_ctx, keyed by the shape and opts.ctx_key(): what the captured launches bake in.  What they do not --
+        the seed words and the required table -- lives in ctx.seed and ctx.req, which _decode writes in front of every
+        launch."""
         torch, n = self.torch, len(self.decoders)
-        key = (B, W, max_steps, float(lpw)) if cons is None else (B, W, max_steps, float(lpw), cons.key())
-        if grp is not None:
-            key = (B, W, max_steps, float(lpw), cons.key() if cons is not None else None, grp.key())
-        if smp is not None:
-            key = (B, W, max_steps, float(lpw), cons.key() if cons is not None else None, None, smp.ctx_key())
-            if trc is not None:
-                key = key + (trc.ctx_key(),)
-        if rqd is not None:
-            key = (B, W, max_steps, float(lpw), cons.key() if cons is not None else None, None, rqd.ctx_key())
+        key = (B, W, max_steps, opts.ctx_key())
         ctx = self._ctxs.get(key)
         if ctx is None:
             ctx = type('EnsembleCtx', (), {})()
             R = B * W
-            i32 = dict(dtype=torch.int32, device=self.device)
             f32 = dict(dtype=torch.float32, device=self.device)
             specs = [d.spec for d in self.decoders]
             ctx.fm = [torch.empty((B, s.M, s.C), **f32) for s in specs]
             ctx.im = [torch.empty((B, s.Cg), **f32) for s in specs]
             ctx.hist = torch.empty((max_steps, R, specs[0].H * specs[0].M), **f32)      # member 0's alignments
-            # rows past the executed steps are never written (device-side early exit): poisoned, as Decoder._infer_ctx
-            ctx.step_ids = torch.full((max_steps, B, W), 0x7f7f7f7f, **i32)
-            ctx.parent_ids = torch.full((max_steps, B, W), 0x7f7f7f7f, **i32)
-            ctx.scores = torch.empty((max_steps, B, W), **f32)
-            ctx.lengths = torch.empty((B, W), dtype=torch.int64, device=self.device)
-            ctx.finished = torch.empty((B, W), **i32)
-            ctx.steps = torch.empty(1, **i32)
+            _beam_outputs(ctx, torch, self.device, B, W, max_steps)
             ctx.descs = (L.DecoderDesc * n)(*[s.desc(False) for s in specs])
-            ctx.descs[0].length_penalty_weight = float(lpw)
+            ctx.descs[0].length_penalty_weight = float(opts.length_penalty_weight)
             ctx.ptabs = (L.DecoderParams * n)(*[d.params.table() for d in self.decoders])
             ctx.fm_ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ctx.fm])
             ctx.im_ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ctx.im])
             ctx.hist_ptrs = (C.c_void_p * n)(*([ctx.hist.data_ptr()] + [None] * (n - 1)))
             ctx.wts = (C.c_float * n)(*self.weights)
-            ctx.cons = cons.c_struct() if cons is not None else None
-            ctx.grp = grp.c_struct() if grp is not None else None
-            ctx.smp = None
-            if smp is not None:
+            if opts.smp is not None:
                 ctx.seed = torch.zeros(2, dtype=torch.int64, device=self.device)       # uint64[2]: {seed, image_base}
-                ctx.smp = smp.c_struct(ctx.seed.data_ptr())
-            ctx.trc = trc.c_struct() if trc is not None else None
-            ctx.rqd = None
-            if rqd is not None:
-                ctx.req = torch.full((B, rqd.n_words, rqd.stride), -1, **i32)
-                ctx.rqd = rqd.c_struct()
-            ws_fn = self.lib.comic_decoder_beam_ensemble_workspace if cons is None else \
-                self.lib.comic_decoder_beam_constrained_workspace
-            if rqd is not None:
-                ctx.nbytes = int(self.lib.comic_decoder_beam_required_workspace(ctx.descs, n, R, max_steps,
-                                                                                0 if cons is None else 1))
-            elif trc is not None:
-                ctx.nbytes = int(self.lib.comic_decoder_beam_truncated_workspace(ctx.descs, n, R, max_steps,
-                                                                                 0 if cons is None else 1))
-            elif smp is not None:
-                ctx.nbytes = int(self.lib.comic_decoder_beam_sampled_workspace(ctx.descs, n, R, max_steps,
-                                                                               0 if cons is None else 1))
-            elif grp is not None:
-                ctx.nbytes = int(self.lib.comic_decoder_beam_diverse_workspace(ctx.descs, n, R, max_steps,
-                                                                               0 if cons is None else 1))
-            else:
-                ctx.nbytes = int(ws_fn(ctx.descs, n, R, max_steps))
+            if opts.required is not None:
+                ctx.req = torch.full((B, opts.required.n_words, opts.required.stride), -1, dtype=torch.int32,
+                                     device=self.device)
+            ctx.options = opts.c_record(ctx)
+            ctx.nbytes = int(self.lib.comic_decoder_beam_search_workspace(ctx.descs, n, R, max_steps, C.byref(ctx.options)))
             assert ctx.nbytes > 0, 'the ensemble workspace query failed'
             ctx.ws = torch.empty(ctx.nbytes, dtype=torch.uint8, device=self.device)
             ctx.graph, ctx.calls = None, 0
@@ -1816,122 +1844,41 @@ class EnsembleDecoder:
 
     def beam_search(self, fms, im_embeds, beam, max_steps, want_attention=False, use_graph=True, length_penalty_weight=0.0,
                     constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None,
-                    consensus=None):
+                    consensus=None, options=None):
         """fms / im_embeds: one device tensor (every member reads the same features) or a sequence with one per member.
-        Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's.  constraints: a
-        BeamConstraints; active ones run comic_decoder_beam_constrained, None / inactive ones today's entry point.
-        groups: a BeamGroups; an active one runs comic_decoder_beam_diverse (with the constraints, if any), as
-        Decoder.beam_search describes; None / inactive: today's entry points.
-        sampling, image_base: a BeamSampling; an active one runs comic_decoder_beam_sampled (with the constraints, if any),
-        as Decoder.beam_search describes; None / inactive: today's entry points.
-        truncation: a BeamTruncation; an active one (sampling only) runs comic_decoder_beam_truncated; the log-probabilities
-        stay the untruncated ones, as Decoder.beam_search describes; None / inactive: today's entry points, call for call.
-        required: a BeamRequired; runs comic_decoder_beam_required (with the constraints, if any), as Decoder.beam_search
-        describes; None: today's entry points.
-        consensus: a Consensus; one comic_caption_consensus launch on the gathered ids, as Decoder.beam_search describes;
-        None: today's launches."""
+        Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's.  The options -- these keywords
+        or one BeamOptions in `options` -- are Decoder.beam_search's and mean what they mean there; every decode runs
+        through comic_decoder_beam_search, and None / inactive options are the plain ensemble decode, launch for launch."""
+        opts = BeamOptions.of(options, length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
+                              sampling=sampling, truncation=truncation, required=required, consensus=consensus,
+                              image_base=image_base)
         torch, n = self.torch, len(self.decoders)
-        if consensus is not None:
-            consensus.check(beam, max_steps)
-        if required is not None:
-            B0 = int((fms if torch.is_tensor(fms) else fms[0]).shape[0])
-            required.check(self.spec, beam, B0, max_steps, constraints, groups, sampling)
-        cons = constraints if constraints is not None and constraints.active else None
-        if groups is not None:
-            groups.check(beam, self.spec.V)
-        grp = groups if groups is not None and groups.active else None
-        if sampling is not None:
-            sampling.check(beam, length_penalty_weight, groups)
-        smp = sampling if sampling is not None and sampling.active else None
-        if truncation is not None:
-            truncation.check(sampling)
-        trc = truncation if truncation is not None and truncation.active else None
-        if cons is not None:
-            cons.check(self.spec, beam, max_steps)
         if torch.is_tensor(fms):
             fms = [fms] * n
         if torch.is_tensor(im_embeds):
             im_embeds = [im_embeds] * n
+        opts.check(self.spec, beam, int(fms[0].shape[0]), max_steps)
+        return self._decode(fms, im_embeds, beam, max_steps, want_attention, use_graph, opts)
+
+    def _decode(self, fms, im_embeds, beam, max_steps, want_attention, use_graph, opts):
+        """The decode of checked options: one feature tensor per member."""
+        torch, n = self.torch, len(self.decoders)
         assert len(fms) == n and len(im_embeds) == n
-        B, W = int(fms[0].shape[0]), int(beam)
-        ctx = self._ctx(B, W, int(max_steps), length_penalty_weight, list(zip(fms, im_embeds)), cons, grp, smp, trc, required)
-        if required is not None:            # on the stream, in front of the launch or the replay that reads it
-            ctx.req.copy_(torch.from_numpy(required.ids))
-        if smp is not None:                 # on the stream, in front of the launch or the replay that reads them
-            ctx.seed.copy_(torch.from_numpy(smp.seed_words(image_base)))
+        B, W, max_steps = int(fms[0].shape[0]), int(beam), int(max_steps)
+        ctx = self._ctx(B, W, max_steps, list(zip(fms, im_embeds)), opts)
+        if opts.required is not None:       # on the stream, in front of the launch or the replay that reads it
+            ctx.req.copy_(torch.from_numpy(opts.required.ids))
+        if opts.smp is not None:            # on the stream, in front of the launch or the replay that reads them
+            ctx.seed.copy_(torch.from_numpy(opts.smp.seed_words(opts.image_base)))
 
         def launch():
             flags = L.decoder_flags_from_env()
             for k in range(n):
                 ctx.descs[k].flags = flags
-            if ctx.rqd is not None:
-                L.check(self.lib.comic_decoder_beam_required(
-                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps,
-                    C.byref(ctx.cons) if ctx.cons is not None else None, None, None, C.byref(ctx.rqd), ctx.req.data_ptr(),
-                    ctx.step_ids.data_ptr(), ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(),
-                    ctx.finished.data_ptr(), ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
-                    L.stream_ptr()), 'decoder_beam_required')
-                return
-            if ctx.trc is not None:
-                L.check(self.lib.comic_decoder_beam_truncated(
-                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps,
-                    C.byref(ctx.cons) if ctx.cons is not None else None, C.byref(ctx.smp), C.byref(ctx.trc),
-                    ctx.step_ids.data_ptr(), ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(),
-                    ctx.finished.data_ptr(), ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
-                    L.stream_ptr()), 'decoder_beam_truncated')
-                return
-            if ctx.smp is not None:
-                L.check(self.lib.comic_decoder_beam_sampled(
-                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps,
-                    C.byref(ctx.cons) if ctx.cons is not None else None, C.byref(ctx.smp), ctx.step_ids.data_ptr(),
-                    ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(), ctx.finished.data_ptr(),
-                    ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes, L.stream_ptr()),
-                    'decoder_beam_sampled')
-                return
-            if ctx.grp is not None:
-                L.check(self.lib.comic_decoder_beam_diverse(
-                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps,
-                    C.byref(ctx.cons) if ctx.cons is not None else None, C.byref(ctx.grp), ctx.step_ids.data_ptr(),
-                    ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(), ctx.finished.data_ptr(),
-                    ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes, L.stream_ptr()),
-                    'decoder_beam_diverse')
-                return
-            if ctx.cons is not None:
-                L.check(self.lib.comic_decoder_beam_constrained(
-                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps, C.byref(ctx.cons),
-                    ctx.step_ids.data_ptr(), ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(),
-                    ctx.finished.data_ptr(), ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
-                    L.stream_ptr()), 'decoder_beam_constrained')
-                return
-            L.check(self.lib.comic_decoder_beam_ensemble(
-                ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps, ctx.step_ids.data_ptr(),
-                ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(), ctx.finished.data_ptr(),
-                ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes, L.stream_ptr()), 'decoder_beam_ensemble')
+            L.check(self.lib.comic_decoder_beam_search(
+                ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps, C.byref(ctx.options),
+                ctx.step_ids.data_ptr(), ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(),
+                ctx.finished.data_ptr(), ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
+                L.stream_ptr()), 'decoder_beam_search')
         Decoder._run_infer(self, ctx, launch, use_graph)
-        s = self.spec
-        T = int(ctx.steps.item())
-        max_len = ctx.lengths.max(dim=1).values.to(torch.int32).contiguous()
-        pred = torch.empty((T, B, W), dtype=torch.int32, device=self.device)
-        L.check(self.lib.comic_gather_tree(ctx.step_ids[:T].data_ptr(), ctx.parent_ids[:T].data_ptr(), max_len.data_ptr(),
-                                           pred.data_ptr(), T, B, W, s.end_id, L.stream_ptr()), 'gather_tree')
-        par = ctx.parent_ids[:T].cpu().numpy()
-        ln = ctx.lengths.cpu().numpy()
-        out = dict(predicted_ids=pred.cpu().numpy(), scores=ctx.scores[:T].cpu().numpy(),
-                   step_ids=ctx.step_ids[:T].cpu().numpy(), parent_ids=par, lengths=ln, groups=1)
-        if grp is not None:
-            out['groups'] = grp.groups
-            out['log_probs'] = grp.final_log_probs(out['scores'], out['step_ids'], ln, s.end_id, length_penalty_weight)
-        if smp is not None:                 # the state after the last executed step: a finished chain's carries over
-            out['log_probs'] = out['scores'][-1].copy()
-        if required is not None:            # the unpenalised totals: the last scores times the length penalty's divisor
-            lp = out['scores'][-1].copy()
-            if length_penalty_weight:
-                lp = (lp * (((5.0 + ln.astype(np.float32)) / 6.0) ** np.float32(length_penalty_weight))).astype(np.float32)
-            out['log_probs'], out['banks'] = lp, required.banks
-            out['best_slot'], out['met'] = required.result(out['scores'][-1])
-        if consensus is not None:
-            _attach_consensus(self, out, pred, consensus, required is not None, ctx.scores[T - 1],
-                              grp is None and not (required is not None and length_penalty_weight))
-        if want_attention:
-            out['attn_hist'] = gather_tree_from_array(ctx.hist[:T].cpu().numpy(), par, ln, s.end_id)
-        return out
+        return _beam_result(self, ctx, B, W, opts, want_attention)

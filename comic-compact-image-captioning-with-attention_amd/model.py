@@ -18,6 +18,7 @@ Models built with reuse=True share encoder/decoder/optimiser objects with the fi
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 
 import numpy as np
@@ -428,96 +429,48 @@ class ModelBase(object):
                          max_to_keep, fmt=fmt)
 
     # ---- decode (model_base.py:692-757, :272-314) ----------------------------------------
-    def _decode(self, images, beam_size, max_length, top_beam=True, want_attention=True, length_penalty_weight=0.0,
-                constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None, consensus=None):
+    def _decode(self, images, beam_size, max_length, top_beam=True, want_attention=True, options=None):
         im_embed, fm = self._encode(images)
-        return self._decode_features(im_embed, fm, beam_size, max_length, top_beam, want_attention, length_penalty_weight,
-                                     constraints, groups, sampling, image_base, truncation, required, consensus)
+        return self._decode_features(im_embed, fm, beam_size, max_length, top_beam, want_attention, options)
 
-    def _decode_features(self, im_embed, fm, beam_size, max_length, top_beam=True, want_attention=True,
-                         length_penalty_weight=0.0, constraints=None, groups=None, sampling=None, image_base=0,
-                         truncation=None, required=None, consensus=None):
-        """constraints: decoder.BeamConstraints in TOKENS (decoder.constraints_from_config translates a configuration's
-        words); beam search only.  groups: decoder.BeamGroups; an active one decodes by diverse beam search: the top beam is
-        group 0's best (the caption of beam search of width beam / groups), and self.group_output holds the group-best
-        captions of the batch (group_best), None otherwise.  sampling: decoder.BeamSampling; an active one draws beam_size
-        samples per image (image_base: the number of images decoded before this batch in the run): the top beam is, per
-        image, the sample of highest log-probability (lowest slot on ties), and self.sample_output holds every sample
-        (sample_set), None otherwise.  truncation: decoder.BeamTruncation; an active one restricts every draw to the top_k
-        likeliest tokens and / or the top_p nucleus (sampling only: ValueError otherwise); the log-probabilities stay the
-        model's own, untruncated.  required: decoder.BeamRequired with the batch's rows; decodes by banks of constraint progress:
-        the top beam is, per image, the best caption of the highest bank that holds one, and self.required_output holds
-        every bank's best (bank_best), None otherwise.  consensus: decoder.Consensus; with active sampling the top beam is,
-        per image, the sample that agrees most with its siblings (the result's consensus_best) instead of the likeliest,
-        the attention maps are that sample's, and sample_output gains `consensus` (B, n); sampling only: ValueError
-        otherwise."""
+    def _decode_features(self, im_embed, fm, beam_size, max_length, top_beam=True, want_attention=True, options=None):
+        """options: a decoder.BeamOptions (None: the plain decode), its constraints in TOKENS
+        (decoder.constraints_from_config translates a configuration's words); beam search only.  The top beam is, per
+        image, slot `best` of the decode, and the attention maps are that slot's: with required words the best caption of
+        the highest bank that holds one (self.required_output holds every bank's best, bank_best); with consensus the
+        sample that agrees most with its siblings (sampling only: ValueError otherwise); with active sampling the sample
+        of highest log-probability, the lowest slot on ties (self.sample_output holds every sample, sample_set, and with
+        consensus their `consensus` (B, n)); else slot 0, with active groups group 0's best (self.group_output holds the
+        group-best captions, group_best).  The three outputs are None where their option is off."""
         c = self._config
-        if consensus is not None and not (sampling is not None and sampling.active):
-            raise ValueError('consensus selects among samples: it needs an active BeamSampling')
+        opts = model_options(options if options is not None else cdec.BeamOptions(), beam_size)
         iters = self.decoder.max_iterations(max_length, len(c.wtoi))
-        self.required_output = None
-        if required is not None:
-            r = self.decoder.beam_search(fm, im_embed, beam_size, iters, want_attention=want_attention,
-                                         length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
-                                         sampling=sampling, required=required)
-            self.group_output = self.sample_output = None
-            self.required_output = bank_best(r)
-            pred, best = r['predicted_ids'], r['best_slot']              # (T, B, W), (B,)
+        self.required_output = self.group_output = self.sample_output = None
+        if beam_size > 1 or opts.smp is not None or opts.required is not None:
+            if not want_attention and not opts.length_penalty_weight and not opts.active:
+                # captions alone: the ids come back through pinned memory behind one event (no stream drain per array)
+                r = {'predicted_ids': self.decoder.beam_search_ids(fm, im_embed, beam_size, iters)()}
+            else:
+                r = self.decoder.beam_search(fm, im_embed, beam_size, iters, want_attention=want_attention, options=opts)
+            pred = r['predicted_ids']                                  # (T, B, W)
             T, B = pred.shape[:2]
+            best = np.zeros(B, np.int64)
+            if opts.required is not None:
+                self.required_output = bank_best(r)
+                best = r['best_slot']
+            elif opts.smp is not None:
+                self.sample_output = sample_set(r)
+                best = np.argmax(r['log_probs'], axis=1)               # (the lowest slot on ties)
+                if opts.consensus is not None:
+                    best = np.asarray(r['consensus_best'], np.int64)
+            elif opts.grp is not None:
+                self.group_output = group_best(r)
             attn = None
             if want_attention:
                 hist = r['attn_hist'].reshape(T, B, beam_size, self.spec.H, self.spec.M)
                 attn = hist[:, np.arange(B), best].transpose(1, 2, 0, 3)      # (B, H, T, M) of the chosen caption
             if top_beam:
                 return pred[:, np.arange(B), best].T.copy(), attn
-            return pred.transpose(2, 1, 0).copy(), attn
-        constrained = constraints is not None and constraints.active
-        grouped = groups is not None and groups.active
-        sampled = sampling is not None and sampling.active
-        self.group_output = None
-        self.sample_output = None
-        if truncation is not None:
-            truncation.check(sampling)
-        if sampled:
-            sampling.check(beam_size, length_penalty_weight, groups)
-            r = self.decoder.beam_search(fm, im_embed, beam_size, iters, want_attention=want_attention,
-                                         constraints=constraints, sampling=sampling, image_base=image_base,
-                                         truncation=truncation, consensus=consensus)
-            self.sample_output = sample_set(r)
-            pred = r['predicted_ids']                                  # (T, B, n)
-            T, B = pred.shape[:2]
-            best = np.argmax(r['log_probs'], axis=1)                   # (the lowest slot on ties)
-            if consensus is not None:
-                best = np.asarray(r['consensus_best'], np.int64)
-            attn = None
-            if want_attention:
-                hist = r['attn_hist'].reshape(T, B, beam_size, self.spec.H, self.spec.M)
-                attn = hist[:, np.arange(B), best].transpose(1, 2, 0, 3)      # (B, H, T, M) of the chosen sample
-            if top_beam:
-                return pred[:, np.arange(B), best].T.copy(), attn
-            return pred.transpose(2, 1, 0).copy(), attn
-        if constrained and beam_size <= 1:
-            raise ValueError('beam constraints need beam search: infer_beam_size must be at least 2')
-        if grouped and beam_size <= 1:
-            raise ValueError('beam groups need beam search: infer_beam_size must be at least 2')
-        if beam_size > 1:
-            if not want_attention and not length_penalty_weight and not constrained and not grouped:
-                # captions alone: the ids come back through pinned memory behind one event (no stream drain per array)
-                r = {'predicted_ids': self.decoder.beam_search_ids(fm, im_embed, beam_size, iters)()}
-            else:
-                r = self.decoder.beam_search(fm, im_embed, beam_size, iters, want_attention=want_attention,
-                                             length_penalty_weight=length_penalty_weight, constraints=constraints,
-                                             groups=groups)
-            pred = r['predicted_ids']                                  # (T, B, W)
-            T = pred.shape[0]
-            if grouped:
-                self.group_output = group_best(r)
-            attn = None
-            if want_attention:
-                hist = r['attn_hist'].reshape(T, -1, beam_size, self.spec.H, self.spec.M)[:, :, 0]
-                attn = hist.transpose(1, 2, 0, 3)                      # (B, H, T, M) of beam 0
-            if top_beam:
-                return pred[:, :, 0].T.copy(), attn
             return pred.transpose(2, 1, 0).copy(), attn               # (W, B, T)
         if beam_size == 0:
             # _decoder_rnn_scst(0): the sampled rollout (model_base.py:716-726 sample=True -> SampleEmbeddingHelper,
@@ -547,15 +500,62 @@ def bank_best(r):
                 log_probs=r['log_probs'][:, ::Wb].copy(), bank=np.asarray(r['best_slot']) // Wb, met=np.asarray(r['met']))
 
 
-def decode_consensus(model, consensus):
-    """The Consensus of a decode of `model` (a CaptionModel or a CaptionEnsemble): the argument, else what the model's
-    configuration asks for (decoder.consensus_from_config, read once: the idf table is built and uploaded one time per
-    model)."""
-    if consensus is not None:
-        return consensus
-    if '_consensus_cfg' not in model.__dict__:
-        model._consensus_cfg = cdec.consensus_from_config(model._config)
-    return model._consensus_cfg
+def consensus_needs_samples(opts):
+    if opts.consensus is not None and opts.smp is None:
+        raise ValueError('consensus selects among samples: it needs an active BeamSampling')
+
+
+def model_options(opts, beam_size):
+    """The options CaptionModel._decode_features hands its decoder, after the model's own rules: the consensus selects among
+    samples; a decode by banks leaves a truncation out (it does not sample); else a truncation needs active sampling, an
+    inactive sampling is none, and without sampling constraints and groups need a beam."""
+    consensus_needs_samples(opts)
+    if opts.required is not None:
+        return dataclasses.replace(opts, truncation=None)
+    if opts.truncation is not None:
+        opts.truncation.check(opts.sampling)
+    if opts.smp is not None:
+        return opts
+    if beam_size <= 1 and opts.cons is not None:
+        raise ValueError('beam constraints need beam search: infer_beam_size must be at least 2')
+    if beam_size <= 1 and opts.grp is not None:
+        raise ValueError('beam groups need beam search: infer_beam_size must be at least 2')
+    return dataclasses.replace(opts, sampling=None)
+
+
+def decode_options(model, constraints, groups, sampling, truncation, consensus):
+    """The BeamOptions of a decode of `model` (a CaptionModel or a CaptionEnsemble), without the per-batch parts
+    (batch_options): every argument, else what the model's configuration asks for.  The configuration's consensus is read
+    once: the idf table is built and uploaded one time per model."""
+    c = model._config
+    if consensus is None:
+        if '_consensus_cfg' not in model.__dict__:
+            model._consensus_cfg = cdec.consensus_from_config(c)
+        consensus = model._consensus_cfg
+    return cdec.BeamOptions(
+        length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
+        constraints=constraints if constraints is not None else cdec.constraints_from_config(c),
+        groups=groups if groups is not None else cdec.groups_from_config(c),
+        sampling=sampling if sampling is not None else cdec.sampling_from_config(c),
+        truncation=truncation if truncation is not None else cdec.truncation_from_config(c), consensus=consensus)
+
+
+def batch_options(model, opts, B):
+    """opts for the next B images of the run: with image_base, the number of images sampled before them (the noise of a
+    sampled decode is keyed by it), and the rows of model.required_table (a BeamRequired over every image of the run, in
+    input order: decoder.required_from_config) when that is set."""
+    base = 0
+    if opts.smp is not None:
+        base = model.__dict__.get('_images_sampled', 0)
+        model._images_sampled = base + int(B)
+    required, table = None, model.__dict__.get('required_table')
+    if table is not None:
+        at = model.__dict__.get('_images_required', 0)
+        model._images_required = at + int(B)
+        if at + int(B) > table.ids.shape[0]:
+            raise ValueError('required_table holds %d images, the run decodes more' % table.ids.shape[0])
+        required = cdec.BeamRequired(table.ids[at:at + int(B)])
+    return dataclasses.replace(opts, image_base=base, required=required)
 
 
 def sample_set(r):
@@ -695,26 +695,6 @@ class CaptionModel(ModelBase):
         res = self.decoder.train_step(fm, im_embed, np.asarray(captions), training=False, use_graph=True)
         return res['loss']
 
-    def _image_base(self, sampling, B):
-        """The number of images decoded before this batch of B in the run (the noise of a sampled decode is keyed by it)."""
-        if sampling is None or not sampling.active:
-            return 0
-        base = self.__dict__.get('_images_sampled', 0)
-        self._images_sampled = base + int(B)
-        return base
-
-    def _required_rows(self, B):
-        """The BeamRequired of the next B images of the run when self.required_table (a BeamRequired over every image of the
-        run, in input order: decoder.required_from_config) is set, else None."""
-        table = self.__dict__.get('required_table')
-        if table is None:
-            return None
-        base = self.__dict__.get('_images_required', 0)
-        self._images_required = base + int(B)
-        if base + int(B) > table.ids.shape[0]:
-            raise ValueError('required_table holds %d images, the run decodes more' % table.ids.shape[0])
-        return cdec.BeamRequired(table.ids[base:base + int(B)])
-
     def infer(self, batch=None, constraints=None, groups=None, sampling=None, truncation=None, consensus=None):
         """== sess.run(m_infer.infer_output) -> [dec_preds (B,T), attention_maps (B,H,T,M)].
         constraints: decoder.BeamConstraints; None reads the configuration (infer_min_length, infer_no_repeat_ngram,
@@ -739,19 +719,9 @@ class CaptionModel(ModelBase):
             if feats is None:
                 raise StopIteration('infer(): the input pipeline is exhausted')
             im_embed, fm = feats
-        if constraints is None:
-            constraints = cdec.constraints_from_config(c)
-        if groups is None:
-            groups = cdec.groups_from_config(c)
-        if sampling is None:
-            sampling = cdec.sampling_from_config(c)
-        if truncation is None:
-            truncation = cdec.truncation_from_config(c)
+        opts = decode_options(self, constraints, groups, sampling, truncation, consensus)
         ids, attn = self._decode_features(im_embed, fm, c.infer_beam_size, c.infer_max_length, top_beam=True,
-                                          length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
-                                          constraints=constraints, groups=groups, sampling=sampling,
-                                          image_base=self._image_base(sampling, fm.shape[0]), truncation=truncation,
-                                          required=self._required_rows(fm.shape[0]), consensus=decode_consensus(self, consensus))
+                                          options=batch_options(self, opts, fm.shape[0]))
         self.infer_output = [ids, attn]
         return self.infer_output
 
@@ -767,24 +737,9 @@ class CaptionModel(ModelBase):
         maps, no length penalty, no beam constraints, no beam groups: what `infer.py` writes unless --save_attention_maps);
         everything else yields infer().  constraints, groups, sampling, truncation, consensus: as infer()."""
         c, torch = self._config, self.torch
-        consensus = decode_consensus(self, consensus)
-        lp = getattr(c, 'infer_length_penalty_weight', 0.0)
-        if constraints is None:
-            constraints = cdec.constraints_from_config(c)
-        constrained = constraints is not None and constraints.active
-        if groups is None:
-            groups = cdec.groups_from_config(c)
-        constrained = constrained or (groups is not None and groups.active)     # (either keeps to the one-loop path)
-        if sampling is None:
-            sampling = cdec.sampling_from_config(c)
-        constrained = constrained or (sampling is not None and sampling.active)  # (so does sampling)
-        if consensus is not None and not (sampling is not None and sampling.active):
-            raise ValueError('consensus selects among samples: it needs an active BeamSampling')
-        constrained = constrained or self.__dict__.get('required_table') is not None      # (and required words)
-        if truncation is None:
-            truncation = cdec.truncation_from_config(c)
-        if truncation is not None:
-            truncation.check(sampling)
+        opts = decode_options(self, constraints, groups, sampling, truncation, consensus)
+        lp = opts.length_penalty_weight
+        constrained = opts.active or self.__dict__.get('required_table') is not None     # (these keep to the one-loop path)
         NL = max(1, min(5, int(os.environ.get('COMIC_INFER_IN_FLIGHT', '3'))))      # decode loops in flight (3: measured best of 1-5)
         if want_attention or lp or constrained or c.infer_beam_size <= 1 or not str(self.device).startswith('cuda'):
             NL = 1
@@ -794,12 +749,10 @@ class CaptionModel(ModelBase):
                 if feats is None:
                     return
                 ids, attn = self._decode_features(feats[0], feats[1], c.infer_beam_size, c.infer_max_length, top_beam=True,
-                                                  want_attention=want_attention, length_penalty_weight=lp,
-                                                  constraints=constraints, groups=groups, sampling=sampling,
-                                                  image_base=self._image_base(sampling, feats[1].shape[0]),
-                                                  truncation=truncation,
-                                                  required=self._required_rows(feats[1].shape[0]), consensus=consensus)
+                                                  want_attention=want_attention,
+                                                  options=batch_options(self, opts, feats[1].shape[0]))
                 yield [ids, attn]
+        model_options(opts, c.infer_beam_size)            # (the rules _decode_features runs for every other decode)
         iters = self.decoder.max_iterations(c.infer_max_length, len(c.wtoi))
         lanes = [streams.lane(torch, self.device, 'infer%d' % k) for k in range(NL)]
         pending = [None] * NL
@@ -1057,18 +1010,8 @@ class CaptionEnsemble(object):
         """-> [dec_preds (B,T), attention_maps (B,H,T,M) of member 0], as CaptionModel.infer; without `batch` the images
         come from member 0's input pipeline.  constraints, groups, sampling, truncation, consensus: as CaptionModel.infer."""
         c = self._config
-        consensus = decode_consensus(self, consensus)
-        if constraints is None:
-            constraints = cdec.constraints_from_config(c)
-        if groups is None:
-            groups = cdec.groups_from_config(c)
-        if sampling is None:
-            sampling = cdec.sampling_from_config(c)
-        if truncation is None:
-            truncation = cdec.truncation_from_config(c)
-        sampled = sampling is not None and sampling.active
-        if consensus is not None and not sampled:
-            raise ValueError('consensus selects among samples: it needs an active BeamSampling')
+        opts = decode_options(self, constraints, groups, sampling, truncation, consensus)
+        consensus_needs_samples(opts)
         if batch is None:
             batch = next(self.models[0].batch_ops)
         images = batch[0] if isinstance(batch, (tuple, list)) else batch
@@ -1076,26 +1019,19 @@ class CaptionEnsemble(object):
         spec = self.decoder.spec
         iters = self.models[0].decoder.max_iterations(c.infer_max_length, len(c.wtoi))
         W = c.infer_beam_size
-        assert W > 1 or sampled, 'the ensemble decodes by beam search: infer_beam_size must be at least 2'
-        base = 0
-        if sampled:
-            base = self.__dict__.get('_images_sampled', 0)
-            self._images_sampled = base + int(feats[0][1].shape[0])
-        required = CaptionModel._required_rows(self, feats[0][1].shape[0])
-        r = self.decoder.beam_search([f[1] for f in feats], [f[0] for f in feats], W, iters, want_attention=True,
-                                     length_penalty_weight=getattr(c, 'infer_length_penalty_weight', 0.0),
-                                     constraints=constraints, groups=groups, sampling=sampling, image_base=base,
-                                     truncation=truncation, required=required, consensus=consensus)
+        assert W > 1 or opts.smp is not None, 'the ensemble decodes by beam search: infer_beam_size must be at least 2'
+        opts = batch_options(self, opts, feats[0][1].shape[0])
+        r = self.decoder.beam_search([f[1] for f in feats], [f[0] for f in feats], W, iters, want_attention=True, options=opts)
         pred = r['predicted_ids']                                  # (T, B, W)
         T, B = pred.shape[:2]
-        self.required_output = bank_best(r) if required is not None else None
+        self.required_output = bank_best(r) if opts.required is not None else None
         self.group_output = group_best(r) if r['groups'] > 1 else None
-        self.sample_output = sample_set(r) if sampled else None
+        self.sample_output = sample_set(r) if opts.smp is not None else None
         # (sampling: per image the sample of highest log-probability, the lowest slot on ties; else the top beam)
-        best = np.argmax(r['log_probs'], axis=1) if sampled else np.zeros(B, np.int64)
-        if consensus is not None:           # (consensus: the sample that agrees most with its siblings)
+        best = np.argmax(r['log_probs'], axis=1) if opts.smp is not None else np.zeros(B, np.int64)
+        if opts.consensus is not None:      # (consensus: the sample that agrees most with its siblings)
             best = np.asarray(r['consensus_best'], np.int64)
-        if required is not None:            # (required words: the best of the highest bank that holds a caption)
+        if opts.required is not None:       # (required words: the best of the highest bank that holds a caption)
             best = np.asarray(r['best_slot'])
         hist = r['attn_hist'].reshape(T, B, W, spec.H, spec.M)[:, np.arange(B), best]
         self.infer_output = [pred[:, np.arange(B), best].T.copy(), hist.transpose(1, 2, 0, 3)]

@@ -1051,6 +1051,30 @@ int comic_decoder_beam_required(const comic_decoder_desc* descs, const comic_dec
                                 float* const* attn_hists, int32_t* steps_executed, void* workspace, int64_t workspace_bytes,
                                 void* stream);
 
+/* Which decode a beam search is, as ONE value (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112): the options of
+ * the six entries above, each with the rules it has there.  Every pointer may be NULL: that option is off; a NULL record
+ * is comic_decoder_beam_ensemble.  Refused before anything else is read: required words with more than one group or with
+ * sampling, sampling with more than one group, a truncation without sampling, required words without their table.
+ * comic_decoder_beam_search is the ONE executor loop and the entry the Python package calls; the named entries above are
+ * its stable per-option forms: their own null checks and one forwarding call.  The workspace depends on which options are
+ * present only (and, under constraints or required words, on max_steps): comic_decoder_beam_search_workspace returns what
+ * the named query of the same combination returns, -1 where that does. */
+typedef struct comic_beam_options {
+  const comic_beam_constraints* constraints;
+  const comic_beam_groups* groups;
+  const comic_beam_sampling* sampling;
+  const comic_beam_truncation* truncation; /* needs sampling */
+  const comic_beam_required* required;     /* needs req; not with groups > 1 or sampling */
+  const int32_t* req;                      /* device [B][n_words][stride] */
+} comic_beam_options;
+int64_t comic_decoder_beam_search_workspace(const comic_decoder_desc* descs, int n_models, int rows, int max_steps,
+                                            const comic_beam_options* options);
+int comic_decoder_beam_search(const comic_decoder_desc* descs, const comic_decoder_params* params, const float* const* fms,
+                              const float* const* im_embeds, const float* weights, int n_models, int B, int W,
+                              int max_steps, const comic_beam_options* options, int32_t* step_ids, int32_t* parent_ids,
+                              float* scores, int64_t* lengths, int32_t* finished, float* const* attn_hists,
+                              int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Op-level entries of the executor-only kernel forms                        */
 /* ------------------------------------------------------------------------- */

@@ -165,16 +165,12 @@ def main(argv=None):
     save_name = {'test': 'infer_test_', 'valid': 'infer_valid_', 'coco_test': 'infer_cocoTest_',
                  'coco_valid': 'infer_cocoValid_'}[c.infer_set] + save_name
     # constrained, grouped and sampled captions get a directory of their own: they never overwrite the plain ones
-    from comic_amd.decoder import (consensus_dir_suffix, consensus_from_config, constraints_dir_suffix, groups_dir_suffix,
-                                   groups_from_config, required_dir_suffix, required_from_config, sampling_dir_suffix,
-                                   sampling_from_config, truncation_dir_suffix, truncation_from_config)
-    groups_from_config(c)           # (refuses groups that do not divide infer_beam_size before anything is loaded)
-    sampling_from_config(c)         # (refuses sampling with more than one group or a length penalty likewise)
-    truncation_from_config(c)       # (refuses --infer_top_k / --infer_top_p without --infer_sample likewise)
-    required_from_config(c)         # (refuses a beam size that the banks do not divide, and char tokens, likewise)
-    save_name += constraints_dir_suffix(c) + groups_dir_suffix(c) + sampling_dir_suffix(c) + truncation_dir_suffix(c)
-    consensus_from_config(c, load_idf=False)      # (refuses --infer_consensus without --infer_sample, and char tokens)
-    save_name += consensus_dir_suffix(c) + required_dir_suffix(c)
+    from comic_amd.decoder import decode_dir_suffix, options_from_config
+    # refused before anything is loaded: groups that do not divide infer_beam_size; sampling with more than one group or a
+    # length penalty; --infer_top_k / --infer_top_p or --infer_consensus without --infer_sample; required words or a consensus
+    # on char tokens; a beam size that the banks of the required words do not divide
+    options_from_config(c, load=False)
+    save_name += decode_dir_suffix(c)
     save_name += ema_dir_suffix(c) + average_dir_suffix(c)      # averaged weights never overwrite the plain captions either
     c.infer_save_path = pjoin(c.infer_checkpoints_dir, save_name)
     if os.path.exists(c.infer_save_path):

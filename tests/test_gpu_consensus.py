@@ -356,13 +356,13 @@ def test_decode_features_returns_the_consensus_best_sample(tiny_run):  # noqa: F
         m.restore_model()
         im_embed, fm = m._next_infer_features()
         ids, attn = m._decode_features(im_embed, fm, 4, c.infer_max_length, top_beam=True, want_attention=True,
-                                       sampling=smp, consensus=cons)
+                                       options=cdec.BeamOptions(sampling=smp, consensus=cons))
         out = m.sample_output
         # the same decode once more, raw (the noise is keyed by the seed and the image's index, both the same)
         raw = m.decoder.beam_search(fm, im_embed, 4, m.decoder.max_iterations(c.infer_max_length, len(c.wtoi)),
                                     want_attention=True, sampling=smp, consensus=cons)
         with pytest.raises(ValueError, match='sampl'):
-            m._decode_features(im_embed, fm, 4, c.infer_max_length, consensus=cons)
+            m._decode_features(im_embed, fm, 4, c.infer_max_length, options=cdec.BeamOptions(consensus=cons))
     finally:
         man.close()
         mdl.reset_default_graph()

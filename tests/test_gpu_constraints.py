@@ -351,7 +351,8 @@ def test_none_and_inactive_constraints_change_nothing():
             assert sorted(res) == sorted(base)
             for k in base:
                 np.testing.assert_array_equal(res[k], base[k], err_msg=k)
-    assert '_self_ensemble' not in dec.__dict__ and all(len(k) == 4 for k in ens._ctxs)     # today's contexts only
+    plain_key = cdec.BeamOptions().ctx_key()                                      # the plain contexts only
+    assert '_self_ensemble' not in dec.__dict__ and all(k[3] == plain_key for k in ens._ctxs)
 
 
 # ------------------------------------------------------------------ 10. / 11. model and CLI --------------------------------
@@ -402,7 +403,7 @@ def test_model_level_words_on_radix_tokens(tiny_run):
         m.restore_model()
         im_embed, fm = m._next_infer_features()
         ids, _ = m._decode_features(im_embed, fm, 3, c.infer_max_length, top_beam=True, want_attention=False,
-                                    constraints=cons)
+                                    options=cdec.BeamOptions(constraints=cons))
     finally:
         man.close()
         mdl.reset_default_graph()

@@ -343,6 +343,50 @@ def test_streaming_lstm_members_match_the_single_decoder():
     assert_close(np.where(fin, res['scores'], 0), np.where(fin, single['scores'], 0), 1e-5, 'scores')
 
 
+def test_named_entries_and_the_options_entry_decode_the_same_bits():
+    """The frozen per-option entries forward to comic_decoder_beam_search, which is what beam_search calls: on one context,
+    the named C entry and then beam_search with the same option leave the same step_ids, parent_ids, scores and lengths up
+    to steps_executed, to the bit, and the context's workspace is the named query's.  V = 258 takes the one-workgroup
+    step; V = 2304 (W * V = 9216 >= 8192, 2 chunks) the split step.  Both sides run the one loop, so this guards the
+    forwarding, the argument order and the record Python builds, no more: that the loop still computes the bits it did
+    is shown by tools/beam_digest.py on the two builds (profiles/r16_beam_digest_*.txt) and, for the workspace, by
+    tests/golden/beam_workspace_sizes.json."""
+    lib = L.load()
+    B, W, steps = 2, 4, 6
+    smp = cdec.BeamSampling(0.8, 3)
+    rqd = cdec.BeamRequired(np.array([[[7]], [[9]]], np.int32))                # 1 word, stride 1: 2 banks
+    cases = (('diverse', dict(groups=cdec.BeamGroups(2, 0.5)), lambda c: (None, C.byref(c.grp))),
+             ('sampled', dict(sampling=smp), lambda c: (None, C.byref(c.smp))),
+             ('truncated', dict(sampling=smp, truncation=cdec.BeamTruncation(top_k=5)),
+              lambda c: (None, C.byref(c.smp), C.byref(c.trc))),
+             ('required', dict(required=rqd), lambda c: (None, None, None, C.byref(c.rqd), c.req.data_ptr())))
+    fm, im = (dev(a[:B]) for a in _features())
+    for V in (258, 2304):
+        spec, cfg = _spec_and_cfg(V=V)
+        ens = cdec.EnsembleDecoder([cdec.Decoder(spec, _rand_params(cfg, 5, EOS_BIAS), DEV)])
+        for name, kw, option_args in cases:
+            opts = cdec.BeamOptions(**kw)
+            ctx = ens._ctx(B, W, steps, [(fm, im)], opts)
+            assert ctx.nbytes == getattr(lib, 'comic_decoder_beam_%s_workspace' % name)(ctx.descs, 1, B * W, steps, 0), (V, name)
+            if opts.smp is not None:
+                ctx.seed.copy_(torch.from_numpy(smp.seed_words(0)))
+            if opts.required is not None:
+                ctx.req.copy_(torch.from_numpy(rqd.ids))
+            L.check(getattr(lib, 'comic_decoder_beam_' + name)(
+                ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, 1, B, W, steps, *option_args(ctx),
+                ctx.step_ids.data_ptr(), ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(),
+                ctx.finished.data_ptr(), ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes, stream()), name)
+            T = int(ctx.steps.item())
+            named = dict(step_ids=ctx.step_ids[:T].cpu().numpy(), parent_ids=ctx.parent_ids[:T].cpu().numpy(),
+                         scores=ctx.scores[:T].cpu().numpy(), lengths=ctx.lengths.cpu().numpy())
+            res = ens.beam_search(fm, im, W, steps, use_graph=False, **kw)
+            assert ens._ctx(B, W, steps, [(fm, im)], opts) is ctx              # (the decode ran on that very context)
+            assert res['step_ids'].shape[0] == T, (V, name)
+            for k, a in named.items():
+                np.testing.assert_array_equal(res[k].view(np.int32 if a.itemsize == 4 else np.int64),
+                                              a.view(np.int32 if a.itemsize == 4 else np.int64), err_msg='%d %s %s' % (V, name, k))
+
+
 def _run(module_path, argv):
     import importlib.util
     spec = importlib.util.spec_from_file_location('cli_' + os.path.basename(module_path)[:-3], module_path)

@@ -480,7 +480,8 @@ def test_none_changes_nothing():
         assert sorted(res) == sorted(base)
         for k in base:
             np.testing.assert_array_equal(res[k], base[k], err_msg=k)
-    assert '_self_ensemble' not in dec.__dict__ and all(len(k) == 4 for k in ens._ctxs)     # today's contexts only
+    plain_key = cdec.BeamOptions().ctx_key()                                      # the plain contexts only
+    assert '_self_ensemble' not in dec.__dict__ and all(k[3] == plain_key for k in ens._ctxs)
 
 
 # ------------------------------------------------------------------ CLI ---------------------------------------------------

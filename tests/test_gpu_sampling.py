@@ -380,7 +380,7 @@ def test_refused_on_the_host_and_by_the_executor():
     # the executor's own refusals: a length penalty in the descriptor, a null sampling
     lib = L.load()
     ens = cdec.EnsembleDecoder([dec])
-    ctx = ens._ctx(fm.shape[0], N_DEC, MAX_STEPS, 0.0, [(dev(fm), dev(im))], None, None, BeamSampling(TEMP, 1))
+    ctx = ens._ctx(fm.shape[0], N_DEC, MAX_STEPS, [(dev(fm), dev(im))], cdec.BeamOptions(sampling=BeamSampling(TEMP, 1)))
 
     def call(smp):
         return lib.comic_decoder_beam_sampled(ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, 1, fm.shape[0], N_DEC,

@@ -427,7 +427,8 @@ def test_refused_on_the_host_and_by_the_executor():
     assert '_self_ensemble' not in dec.__dict__                               # refused before anything was built
     lib = L.load()
     ens = cdec.EnsembleDecoder([dec])
-    ctx = ens._ctx(fm.shape[0], N_DEC, MAX_STEPS, 0.0, [(dev(fm), dev(im))], None, None, smp, BeamTruncation(5))
+    ctx = ens._ctx(fm.shape[0], N_DEC, MAX_STEPS, [(dev(fm), dev(im))],
+                   cdec.BeamOptions(sampling=smp, truncation=BeamTruncation(5)))
 
     def call(s, t):
         return lib.comic_decoder_beam_truncated(ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, 1, fm.shape[0], N_DEC,

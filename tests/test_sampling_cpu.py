@@ -214,13 +214,13 @@ def test_none_and_inactive_sampling_leave_the_call_path_alone():
         assert '_self_ensemble' not in dec.__dict__
 
     class Ens:
-        def beam_search(self, *a, **k):
-            seen.update(k)
+        def _decode(self, *a):
+            seen['options'] = a[-1]
             raise _Stop('ensemble')
     dec._self_ensemble = Ens()
     with pytest.raises(_Stop, match='ensemble'):
         dec.beam_search(fm, None, 4, 14, sampling=BeamSampling(0.7, 3), image_base=9)
-    assert seen['sampling'] == BeamSampling(0.7, 3) and seen['image_base'] == 9
+    assert seen['options'].sampling == BeamSampling(0.7, 3) and seen['options'].image_base == 9
     # refused on the host before anything is routed
     with pytest.raises(ValueError, match='beam groups'):
         dec.beam_search(fm, None, 4, 14, sampling=BeamSampling(0.7, 3), groups=BeamGroups(2, 0.5))

@@ -5,7 +5,10 @@ the Python Decoder / EnsembleDecoder API and ctypes only -- the same file runs a
 Decoders: the smallest geometry of tests/test_gpu_path.py (V = 258) and the same with V = 9001, batch 4, beam 3, MAX_STEPS
 steps, under the default switches, COMIC_BEAM_LOGITS=0, COMIC_FUSED_STEP=0 and length_penalty_weight = 0.7; a 2-member
 ensemble at both vocabularies with and without the penalty.  Every decode runs eagerly and then as a replayed hipGraph; one
-sha256 per run over step_ids, parent_ids, scores and lengths up to steps_executed.
+sha256 per run over step_ids, parent_ids, scores and lengths up to steps_executed, and over log_probs where the result has them.
+Option decodes, at both vocabularies with batch 4 and beam 4, through the keyword API alone: constraints (min_length 4,
+no_repeat_ngram 2), two groups at diversity 0.5, sampling (temperature 0.8, seed 2), sampling under top_k 5 / top_p 0.9, one
+required word per image, and a 2-member ensemble with the constraints and the sampling together.
 Step operators: comic_beam_step (one-member cases) and comic_beam_step_ensemble with and without its workspace on the
 inputs of tests/test_gpu_ensemble.py's STEP_CASES; one sha256 over word, parent, scores, log_probs, finished, lengths.
 comic_beam_step_dense at (B, W, V, D) = (4, 3, 3100, 96), (4, 5, 2500, 96), (4, 9, 2500, 96): GEMM + the single-member
@@ -26,6 +29,7 @@ from tests.test_gpu_ensemble import STEP_CASES, step_case  # noqa: E402
 DEV = 'cuda:0'
 BASE = dict(D=128, E=64, C=192, Cg=192, H=8, M=25)                 # tests/test_gpu_path.py: _spec_and_cfg
 B, W, MAX_STEPS = 4, 3, 10
+OPTION_W = 4                                                        # the option decodes: two groups, two banks
 SWITCHES = [('default', {}, 0.0), ('no_beam_logits', {'COMIC_BEAM_LOGITS': '0'}, 0.0),
             ('no_fused_step', {'COMIC_FUSED_STEP': '0'}, 0.0), ('length_penalty', {}, 0.7)]
 
@@ -43,7 +47,8 @@ def decode_digests(search, path):
     for name, use_graph in (('eager', False), ('capture', True), ('replay', True)):
         r = search(use_graph)
         if name != 'capture':
-            out.append('%s T=%d %s' % (name, r['step_ids'].shape[0], sha(r[k] for k in ('step_ids', 'parent_ids', 'scores', 'lengths'))))
+            keys = ('step_ids', 'parent_ids', 'scores', 'lengths') + (('log_probs',) if 'log_probs' in r else ())
+            out.append('%s T=%d %s' % (name, r['step_ids'].shape[0], sha(r[k] for k in keys)))
     return 'path %s %s' % (path(), ' '.join(out))
 
 
@@ -69,6 +74,17 @@ def decoders():
             line = decode_digests(lambda g: ens.beam_search(fm, im, W, MAX_STEPS, use_graph=g, length_penalty_weight=lpw),
                                   lambda: int(ens.lib.comic_beam_step_ensemble_path()))
             print('ensemble V=%d lpw=%.1f %s' % (V, lpw, line), flush=True)
+        cons, smp = cdec.BeamConstraints(min_length=4, no_repeat_ngram=2), cdec.BeamSampling(0.8, 2)
+        rqd = cdec.BeamRequired(np.arange(5, 5 + B, dtype=np.int32).reshape(B, 1, 1))
+        dec = cdec.Decoder(spec, None, DEV, seed=3)
+        for name, search, kw in (('constraints', dec, dict(constraints=cons)), ('groups', dec, dict(groups=cdec.BeamGroups(2, 0.5))),
+                                 ('sampling', dec, dict(sampling=smp)),
+                                 ('truncation', dec, dict(sampling=smp, truncation=cdec.BeamTruncation(5, 0.9))),
+                                 ('required', dec, dict(required=rqd)),
+                                 ('ensemble_constraints_sampling', ens, dict(constraints=cons, sampling=smp))):
+            line = decode_digests(lambda g: search.beam_search(fm, im, OPTION_W, MAX_STEPS, want_attention=False, use_graph=g, **kw),
+                                  lambda: int(ens.lib.comic_beam_step_ensemble_path()))
+            print('options V=%d %s %s' % (V, name, line), flush=True)
 
 
 def step(c, lpw, form):
