@@ -53,7 +53,7 @@ class ModelBase(object):
             # frozen CNN (every mode but cnn_finetune): forward-only plan with the pool branches rewritten
             frozen = bool(getattr(c, 'freeze_scopes', 'Model/encoder/cnn'))
             # --cnn_dtype bf16x3: hi / lo split activations and filters on the bf16 kernels (nets.CnnPlan(x3=True)),
-            # the fast plan at the fp32 parity bar, every train mode (cnn_finetune: csrc/conv.hip conv_backward_x3)
+            # the fast plan at the fp32 parity bar, every train mode (cnn_finetune: csrc/conv_bwd.hip conv_backward_x3)
             x3 = getattr(c, 'cnn_dtype', 'bf16') == 'bf16x3'
             plan = nets.get_network_fn(c.cnn_name, num_classes=None, is_training=False)(
                 tuple(c.cnn_input_size), c.cnn_fm_attention, pool_after_projection=frozen, fuse_pools=frozen, x3=x3)

@@ -1036,7 +1036,7 @@ class CnnEncoder:
         t = type('CnnTrainState', (), {})()
         t.dw, t.dbeta = self.w_master.like(), self.beta.like()
         # gradient buffers: the plan dtype and geometry of the activation buffers; x3 plans ("bf16x3"): fp32 buffers of the
-        # LOGICAL channels (an activation buffer holds three bf16 regions of them: csrc/conv.hip conv_backward_x3)
+        # LOGICAL channels (an activation buffer holds three bf16 regions of them: csrc/conv_bwd.hip conv_backward_x3)
         geo, sizes, total = [], [], 0
         for bi, (H, W, Cc, f32) in enumerate(plan.buffers):
             g32 = f32 or self.dcode == 0 or x3

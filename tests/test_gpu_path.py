@@ -502,7 +502,7 @@ def test_inception_v3_backward_224_f32():
 
 
 def test_inception_v3_backward_224_bf16x3_meets_the_fp32_bar():
-    """cnn_finetune on the bf16x3 plan (csrc/conv.hip conv_backward_x3: d conv as [hi | lo | hi] regions, the weight
+    """cnn_finetune on the bf16x3 plan (csrc/conv_bwd.hip conv_backward_x3: d conv as [hi | lo | hi] regions, the weight
     gradient as three bf16 products x_hi dz_hi + x_lo dz_hi + x_hi dz_lo, backward-data as the x3 conv of d conv against
     [Wt_hi | Wt_hi | Wt_lo] into fp32 gradient buffers, pools through hi + lo): d weights / d beta of all 94 convs at the bar
     of the exact-fp32 plan, 1e-3 per variable (test_inception_v3_backward_224_f32), where the plain bf16 plan is at 4e-2.

@@ -1,11 +1,13 @@
-"""One cnn_finetune step (InceptionV3 trainable + decoder) repeated: a target for rocprofv3 --kernel-trace."""
+"""One cnn_finetune step (InceptionV3 trainable + decoder) repeated: a target for rocprofv3 --kernel-trace.
+DTYPE=bf16 (default) | bf16x3 | f32: the plan the step runs on."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import numpy as np, torch
 from comic_amd import decoder as cdec, nets, trainer
 B = int(os.environ.get('B', '32'))
-plan = nets.CnnPlan('inception_v3', (224, 224))
-tr = trainer.CaptionTrainer(plan.init_params(0), cdec.DecoderSpec(), None, B, (224, 224), 'bf16', 'cuda:0', seed=5, plan=plan)
+DTYPE = os.environ.get('DTYPE', 'bf16')
+plan = nets.CnnPlan('inception_v3', (224, 224), x3=DTYPE == 'bf16x3')
+tr = trainer.CaptionTrainer(plan.init_params(0), cdec.DecoderSpec(), None, B, (224, 224), DTYPE, 'cuda:0', seed=5, plan=plan)
 tr.enable_cnn_finetune()
 if os.environ.get('COMIC_AUTOTUNE', '1') == '1':
     tr.encoder.autotune(cache=os.environ.get('COMIC_TUNE_CACHE') or None)
