@@ -248,6 +248,10 @@ _SIGS = {
     'comic_caption_consensus_workspace': (c_int64, [c_int, c_int, c_int, c_int]),
     'comic_caption_consensus': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, c_int64, c_double, c_double,
                                         P, P, P, c_int64, P]),
+    'comic_scst_reward_workspace': (c_int64, [c_int] * 8),
+    'comic_scst_reward': (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int,
+                                  P, P, c_int64, c_double, c_double, c_double, P, c_int, P, P, P, P, P, P]),
+    'comic_scst_coefficients': (c_int, [P, P, c_int, c_int, P, P, P]),
     # op-level entries of the executor-only kernel forms (tests only; the argument lists are csrc/exec_entries.h's)
     'comic_attn_splits': (c_int, [c_int, c_int]),
     'comic_attn_bwd_scratch': (C.c_long, [c_int, c_int, c_int, c_int]),

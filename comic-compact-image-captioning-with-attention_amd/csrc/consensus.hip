@@ -29,7 +29,7 @@
 
 #include "../../include/comic_hip.h"
 #include "common.h"
-#include "splitmix.h"
+#include "ngram_dev.h"
 
 namespace {
 
@@ -103,10 +103,7 @@ __global__ __launch_bounds__(kConsThreads) void consensus_kernel(
     const int p = e / W, w = e - p * W, k = p / Ucap, i = p - k * Ucap;
     u64 key = 0;
     if (i + k + 1 <= S.U[w]) {
-      const int m = (k + 1) * stride, t0 = i * stride;
-      key = splitmix64((u64)m);
-      for (int s = 0; s < m; ++s) key = splitmix64(key ^ (u64)(uint32_t)rows[(t0 + s) * W + w]);
-      if (key == 0) key = 1;
+      key = ngram_key(rows + (size_t)i * stride * W + w, (k + 1) * stride, W);
     }
     keys[e] = key;
   }
@@ -116,17 +113,7 @@ __global__ __launch_bounds__(kConsThreads) void consensus_kernel(
     const int p = e / W, w = e - p * W, k = p / Ucap, i = p - k * Ucap;
     const u64 key = keys[e];
     double tf = 0.0;
-    if (key) {
-      const int n = S.U[w] - k;
-      bool later = false;
-      int c = 0;
-      for (int q = 0; q < n; ++q)
-        if (keys[(k * Ucap + q) * W + w] == key) {
-          ++c;
-          later |= q < i;
-        }
-      tf = later ? -1.0 : (double)c;
-    }
+    if (key) tf = ngram_tf(keys + (size_t)k * Ucap * W + w, S.U[w] - k, W, i);
     vec[e] = tf;
   }
   __syncthreads();
@@ -139,21 +126,7 @@ __global__ __launch_bounds__(kConsThreads) void consensus_kernel(
       keys[e] = 0;
       continue;
     }
-    double g = 1.0;
-    if (tab_keys) {
-      g = log_ref_len;
-      const u64 mask = (u64)tab_cap - 1;
-      u64 at = key & mask;
-      for (long long n = 0; n < tab_cap; ++n) {              // bounded: a table without an empty slot cannot hang it
-        const u64 kk = tab_keys[at];
-        if (kk == key) {
-          g = tab_g[at];
-          break;
-        }
-        if (kk == 0) break;
-        at = (at + 1) & mask;
-      }
-    }
+    const double g = ngram_idf(tab_keys, tab_g, tab_cap, log_ref_len, key);
     vec[e] = tf * g;
   }
   __syncthreads();

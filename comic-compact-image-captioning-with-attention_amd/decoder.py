@@ -15,7 +15,7 @@ import ctypes as C
 import json
 import math
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -801,14 +801,14 @@ class NgramIdf:
         return 'NgramIdf(%d n-grams in %d slots, stride=%d, %d skipped)' % (self.kept, self.cap, self.stride, self.skipped)
 
     @classmethod
-    def from_document_frequency(cls, df, ref_len, encode, stride):
+    def from_document_frequency(cls, df, ref_len, encode, stride, special=('<GO>', '<EOS>', '<PAD>')):
         """df: {tuple of words: document count}; encode: word -> list of `stride` tokens (word_encoding).  N-grams that
-        hold a word outside `encode` or one of <GO> / <EOS> / <PAD> are skipped and counted."""
+        hold a word outside `encode` or one of `special` (<GO> / <EOS> / <PAD>) are skipped and counted."""
         stride = int(stride)
         log_ref_len = math.log(float(ref_len))
         by_len, skipped = {}, 0
         for ng, cnt in df.items():
-            if any(w in ('<GO>', '<EOS>', '<PAD>') or w not in encode for w in ng):
+            if any(w in special or w not in encode for w in ng):
                 skipped += 1
                 continue
             toks = [t for w in ng for t in encode[w]]
@@ -938,6 +938,19 @@ def _attach_consensus(dec, out, pred, cons, forced_posterior, last_scores, on_de
     out['consensus'], out['consensus_best'] = util.cpu().numpy(), best.cpu().numpy()
 
 
+def _attach_reward(dec, out, pred, opts):
+    """The reward launch of a beam_search on its device `pred` [T, B, W], right after the tree gather and outside the
+    captured graph, as the consensus launch; the result gains `reward` [B, W'] float64 and `advantage` [W, B] float32
+    (numpy) and keeps the device tensors of all five outputs in `reward_device` for the caller."""
+    base = opts.reward_baseline_ids
+    if base is not None:
+        base = base if dec.torch.is_tensor(base) else dec.torch.from_numpy(np.ascontiguousarray(base, np.int32))
+        base = base.to(device=pred.device, dtype=dec.torch.int32).contiguous()
+    res = scst_reward(dec.lib, dec.torch, pred, opts.reward_refs, opts.reward, base)
+    out['reward_device'] = res
+    out['reward'], out['advantage'] = res['reward'].cpu().numpy(), res['advantage'].cpu().numpy()
+
+
 def _beam_outputs(ctx, torch, device, B, W, max_steps):
     """The beam executors' output buffers of a decode context (Decoder._infer_ctx, EnsembleDecoder._ctx)."""
     i32 = dict(dtype=torch.int32, device=device)
@@ -979,6 +992,8 @@ def _beam_result(dec, ctx, B, W, opts, want_attention):
     if opts.consensus is not None:
         _attach_consensus(dec, out, pred, opts.consensus, rqd is not None, ctx.scores[T - 1],
                           grp is None and not (rqd is not None and lpw))
+    if opts.reward is not None:
+        _attach_reward(dec, out, pred, opts)
     if want_attention:
         out['attn_hist'] = gather_tree_from_array(ctx.hist[:T].cpu().numpy(), par, ln, s.end_id)
     return out
@@ -1014,6 +1029,180 @@ def consensus_dir_suffix(c):
     return '_cns_df' if getattr(c, 'infer_consensus_df', None) else '_cns'
 
 
+class RewardVocab:
+    """word -> word id for the device reward (comic_scst_reward): the ids of the configuration's wtoi, and, for a word
+    outside it, an extended id >= len(wtoi), assigned on first sight and kept, one per distinct string.  Such a word matches
+    among references and in the idf table and never a rollout: the kernel drops every rollout word id >= n_ids.
+    n_ids: the ids that ops.id_to_caption(skip_unmapped=True) turns into text -- len(wtoi), less one where no word carries
+    the id len(wtoi) - 1 ('-1' is <PAD>).  token_type / radix_base / word_len say how a rollout spells a word."""
+
+    def __init__(self, config):
+        if config.token_type == 'char':
+            raise ValueError('scst_reward: the device reward needs `word` or `radix` tokens, not `char`')
+        wtoi = config_wtoi(config)
+        self.token_type = config.token_type
+        self.radix_base = int(config.radix_base) if self.token_type == 'radix' else 0
+        self.word_len = word_stride(config, wtoi)
+        self.size = len(wtoi)
+        self.ids = {w: int(i) for w, i in wtoi.items() if int(i) >= 0}
+        # radix_ids_to_captions_and_ids's `simple` rule: joining and splitting the words of a caption must be the identity
+        bad = [w for w in self.ids if not w or w.split() != [w]]
+        if bad:
+            raise ValueError('scst_reward: the vocabulary holds an empty word or one with white space (%r): text and word ids '
+                             'would part' % bad[0])
+        self.n_ids = self.size - (0 if (self.size - 1) in set(self.ids.values()) else 1)
+        self.end_id = int(wtoi['<EOS>']) if self.token_type == 'word' else self.radix_base + 1
+        self.extended = {}
+        self._extended_from = max([self.size] + [i + 1 for i in self.ids.values()])      # beyond every id of the table
+
+    def id(self, word):
+        i = self.ids.get(word)
+        if i is None:
+            i = self.extended.get(word)
+            if i is None:
+                i = self.extended[word] = self._extended_from + len(self.extended)
+        return i
+
+    def encode(self, caption):
+        """A caption's text -> the list of its word ids (str.split, as the host scorer's precook)."""
+        return [self.id(w) for w in caption.split()]
+
+
+class RewardRefs:
+    """The reference captions of a batch in the form the device reward reads: refs int32 [B, R, Lr] of word ids, -1 padded,
+    and n_refs int32 [B].  pack() builds it from the [[str]] an InputManager_SCST yields; device() uploads it once."""
+    MAX_R, MAX_WORDS = 8, 64
+
+    def __init__(self, refs, n_refs):
+        self.refs = np.ascontiguousarray(refs, np.int32)
+        self.n_refs = np.ascontiguousarray(n_refs, np.int32)
+        if self.refs.ndim != 3 or self.n_refs.shape != self.refs.shape[:1]:
+            raise ValueError('reward_refs: refs must be [B, R, Lr] and n_refs [B], got %r and %r'
+                             % (self.refs.shape, self.n_refs.shape))
+        self._dev = None
+
+    @classmethod
+    def pack(cls, refs, vocab):
+        rows = [[vocab.encode(r) for r in rl] for rl in refs]
+        if not rows or any(not rl for rl in rows):
+            raise ValueError('reward_refs: every image needs at least one reference')
+        R = max(len(rl) for rl in rows)
+        Lr = max(1, max(len(r) for rl in rows for r in rl))
+        if R > cls.MAX_R:
+            raise ValueError('reward_refs: %d references of an image exceed %d' % (R, cls.MAX_R))
+        if Lr > cls.MAX_WORDS:
+            raise ValueError('reward_refs: a reference of %d words exceeds %d' % (Lr, cls.MAX_WORDS))
+        out = np.full((len(rows), R, Lr), -1, np.int32)
+        for b, rl in enumerate(rows):
+            for r, ws in enumerate(rl):
+                out[b, r, :len(ws)] = ws
+        return cls(out, [len(rl) for rl in rows])
+
+    def device(self, torch, device):
+        if self._dev is None or self._dev[0] != str(device):
+            self._dev = (str(device), torch.from_numpy(self.refs).to(device), torch.from_numpy(self.n_refs).to(device))
+        return self._dev[1:]
+
+
+class Reward(_Keyed):
+    """The SCST reward on the device (comic_scst_reward; captionScorer.get_hypo_scores, common/scst/scorers.py:43-171):
+    CIDEr-D * weights_ciderD + sum_k BLEU-k * weights_bleu[k] of every rollout against its image's references, and the
+    advantage against `baseline`: 'none', 'greedy' (the reward of a baseline rollout) or 'mean' (the mean reward of the
+    image's other rollouts: leave-one-out).  idf: an NgramIdf of stride 1 built through `vocab` (from_pickle) or None (every
+    n-gram weighs 1); vocab: the RewardVocab the references are packed with.  Immutable; hashable by (weights, baseline,
+    sigma, the identities of table and vocabulary)."""
+    BASELINES = {'none': 0, 'greedy': 1, 'mean': 2}   # COMIC_SCST_BASELINE_*
+    MAX_W, MAX_WORDS, MAX_WORD_LEN = 32, 64, 8
+
+    def __init__(self, weights_ciderD=1.0, weights_bleu=(0.0, 0.0, 0.0, 0.0), idf=None, baseline='greedy', vocab=None,
+                 sigma=6.0):
+        self.weights_ciderD, self.weights_bleu = float(weights_ciderD), tuple(float(w) for w in weights_bleu)
+        self.idf, self.baseline, self.vocab, self.sigma = idf, str(baseline), vocab, float(sigma)
+
+    def key(self):
+        return (self.weights_ciderD, self.weights_bleu, self.baseline, self.sigma, id(self.idf), id(self.vocab))
+
+    def __repr__(self):
+        return 'Reward(weights_ciderD=%r, weights_bleu=%r, idf=%r, baseline=%r)' % (
+            self.weights_ciderD, self.weights_bleu, self.idf, self.baseline)
+
+    @classmethod
+    def from_pickle(cls, path, config, baseline='greedy', weights_ciderD=None, weights_bleu=None):
+        """The Reward of a configuration: its vocabulary, its scst_weight_* (unless given) and the `{pattern}scst-words.p`
+        file of scst/prepro_ngrams.py as a stride-1 word-id table.  Every n-gram of the file goes in: a word outside the
+        vocabulary through its extended id, so that no reference n-gram loses its document frequency."""
+        from .scst.scorers import load_df_pickle
+        vocab = RewardVocab(config)
+        d = path if isinstance(path, dict) else load_df_pickle(path)
+        df = {(tuple(ng.split()) if isinstance(ng, str) else tuple(ng)): cnt for ng, cnt in d['document_frequency'].items()}
+        encode = {w: [vocab.id(w)] for ng in df for w in ng}
+        idf = NgramIdf.from_document_frequency(df, d['ref_len'], encode, 1, special=())
+        wc = getattr(config, 'scst_weight_ciderD', 1.0) if weights_ciderD is None else weights_ciderD
+        wb = getattr(config, 'scst_weight_bleu', (0.0,) * 4) if weights_bleu is None else weights_bleu
+        return cls(wc, wb, idf, baseline, vocab)
+
+    def check(self, beam, max_steps, baseline_steps=None):
+        """The rules of the C side, on the host before any GPU call; raises ValueError naming the field."""
+        if self.vocab is None:
+            raise ValueError('reward: vocab is missing (a RewardVocab; Reward.from_pickle builds it)')
+        if self.baseline not in self.BASELINES:
+            raise ValueError("reward: baseline must be 'none', 'greedy' or 'mean', got %r" % self.baseline)
+        if len(self.weights_bleu) != 4:
+            raise ValueError('reward: weights_bleu must hold 4 weights, got %d' % len(self.weights_bleu))
+        if not all(math.isfinite(w) for w in (self.weights_ciderD,) + self.weights_bleu):
+            raise ValueError('reward: weights_ciderD and weights_bleu must be finite')
+        if not (self.sigma > 0.0 and math.isfinite(self.sigma)):
+            raise ValueError('reward: sigma must be finite and > 0, got %r' % self.sigma)
+        if self.idf is not None and self.idf.stride != 1:
+            raise ValueError('reward: the idf table must be built on word ids (stride 1), not stride %d' % self.idf.stride)
+        wl = self.vocab.word_len
+        if not 1 <= wl <= self.MAX_WORD_LEN:
+            raise ValueError('reward: a word of %d tokens exceeds %d' % (wl, self.MAX_WORD_LEN))
+        if not 1 <= int(beam) <= self.MAX_W:
+            raise ValueError('reward: the number of rollouts (beam) must be in [1,%d], got %d' % (self.MAX_W, int(beam)))
+        if self.baseline == 'mean' and int(beam) < 2:
+            raise ValueError("reward: baseline 'mean' (leave-one-out) needs beam >= 2, got %d" % int(beam))
+        if not 1 <= int(max_steps) <= self.MAX_WORDS * wl:
+            raise ValueError('reward: max_steps = %d exceeds %d words of %d tokens' % (int(max_steps), self.MAX_WORDS, wl))
+        if self.baseline == 'greedy' and baseline_steps is None:
+            raise ValueError("reward: baseline 'greedy' needs baseline_ids")
+        if baseline_steps is not None and not 1 <= int(baseline_steps) <= self.MAX_WORDS * wl:
+            raise ValueError('reward: baseline_ids of %d steps exceed %d words of %d tokens'
+                             % (int(baseline_steps), self.MAX_WORDS, wl))
+
+
+def scst_reward(lib, torch, ids, refs, reward, baseline_ids=None, baseline_first_eos=None):
+    """One comic_scst_reward launch on the device tensors ids [T, B, W] and baseline_ids [T0, B] or None (int32,
+    contiguous; baseline_first_eos [B] int32: the greedy decode's first <EOS> positions, which bound the rows it wrote) against the RewardRefs `refs` -> dict of device tensors: cider [B, W'], bleu [B, W', 4], reward [B, W'],
+    baseline [B, W] (float64) and advantage [W, B] (float32, hypothesis-major: the row order of the update)."""
+    T, B, W = (int(x) for x in ids.shape)
+    T0 = None if baseline_ids is None else int(baseline_ids.shape[0])
+    reward.check(W, T, T0)
+    v = reward.vocab
+    assert ids.dtype == torch.int32 and ids.is_contiguous()
+    if baseline_ids is not None:
+        assert baseline_ids.dtype == torch.int32 and baseline_ids.is_contiguous() and tuple(baseline_ids.shape) == (T0, B)
+    if refs.refs.shape[0] != B:
+        raise ValueError('reward_refs: references of %d images for a batch of %d' % (refs.refs.shape[0], B))
+    R, Lr = (int(x) for x in refs.refs.shape[1:])
+    if lib.comic_scst_reward_workspace(B, W, int(T0 is not None), T, T0 or 0, v.word_len, R, Lr) < 0:
+        raise ValueError('reward: %s' % lib.comic_last_error().decode())
+    refs_dev, n_dev = refs.device(torch, ids.device)
+    Wt = W + (T0 is not None)
+    f64 = dict(dtype=torch.float64, device=ids.device)
+    out = dict(cider=torch.empty((B, Wt), **f64), bleu=torch.empty((B, Wt, 4), **f64), reward=torch.empty((B, Wt), **f64),
+               baseline=torch.empty((B, W), **f64), advantage=torch.empty((W, B), dtype=torch.float32, device=ids.device))
+    keys, g = reward.idf.device(torch, ids.device) if reward.idf is not None else (None, None)
+    L.check(lib.comic_scst_reward(
+        ids.data_ptr(), T, B, W, L.ptr(baseline_ids), T0 or 0, L.ptr(baseline_first_eos), 1 if v.token_type == 'radix' else 0, v.end_id,
+        v.radix_base, v.word_len, v.n_ids, refs_dev.data_ptr(), n_dev.data_ptr(), R, Lr, L.ptr(keys), L.ptr(g),
+        reward.idf.cap if reward.idf is not None else 0, reward.idf.log_ref_len if reward.idf is not None else 0.0,
+        reward.sigma, reward.weights_ciderD, (C.c_double * 4)(*reward.weights_bleu), Reward.BASELINES[reward.baseline],
+        out['cider'].data_ptr(), out['bleu'].data_ptr(), out['reward'].data_ptr(), out['baseline'].data_ptr(),
+        out['advantage'].data_ptr(), L.stream_ptr()), 'scst_reward')
+    return out
+
+
 def _active(option):
     return option if option is not None and option.active else None
 
@@ -1033,6 +1222,9 @@ class BeamOptions:
     required: BeamRequired | None = None
     consensus: Consensus | None = None
     image_base: int = 0
+    reward: Reward | None = None
+    reward_refs: RewardRefs | None = None
+    reward_baseline_ids: object = field(default=None, compare=False, hash=False)     # (an array: no part of the value)
 
     cons = property(lambda self: _active(self.constraints))
     grp = property(lambda self: _active(self.groups))
@@ -1044,7 +1236,7 @@ class BeamOptions:
         """The one BeamOptions of a beam_search call: `options`, or the option keywords; both is a ValueError."""
         if options is None:
             return cls(**keywords)
-        if any(v is not None and v != 0 for v in keywords.values()):
+        if any(v is not None and not (isinstance(v, (int, float)) and v == 0) for v in keywords.values()):
             raise ValueError('beam_search: give `options` or the option keywords, not both')
         return options
 
@@ -1057,6 +1249,12 @@ class BeamOptions:
         """Every option's rules and the rules between them, on the host before anything is built or launched."""
         if self.consensus is not None:
             self.consensus.check(beam, max_steps)
+        if self.reward is not None:
+            if self.reward_refs is None:
+                raise ValueError('reward: reward_refs (the RewardRefs of the batch) is missing')
+            self.reward.check(beam, max_steps, None if self.reward_baseline_ids is None else self.reward_baseline_ids.shape[0])
+        elif self.reward_refs is not None or self.reward_baseline_ids is not None:
+            raise ValueError('reward_refs / reward_baseline_ids apply to the reward only: give reward')
         if self.truncation is not None:
             self.truncation.check(self.sampling)
         if self.required is not None:
@@ -1288,7 +1486,10 @@ class Decoder:
         the rollouts are back and scores them on the host while it runs (the same kernels in the same order: same bits).
         masks: None -> generated on device when training; dict(init_in, inp, out, alpha) of
         device tensors or numpy arrays -> injected (parity tests).  rewards [B] -> SCST loss
-        mean_b(xent_b * reward_b) (model_base.py:342-347).
+        mean_b(xent_b * reward_b) (model_base.py:342-347).  rewards as a float32 DEVICE tensor [B] (the advantage of
+        Decoder.scst_reward): the loss coefficients are formed on the stream by comic_scst_coefficients with the float32
+        operations of the host formula -- same bits, no host copy of them and no synchronisation; the tensor must stay
+        unchanged until the step has executed.
         xe_denom: override of the XE normaliser sum(w)+1e-12 (data parallel: global token count / world size,
         so that the rank-mean of the gradients equals the single-process gradient of the global batch).
         dp: a trainer.DataParallel with world > 1 -> the same normaliser formed ON THE DEVICE: the token count of
@@ -1306,7 +1507,16 @@ class Decoder:
         inputs, targets, wmask, lens = process_inputs(captions, s.token_type)
         B, T = inputs.shape
         Tp = int(lens.max())
-        if rewards is None:
+        dev_rewards = rewards if torch.is_tensor(rewards) else None
+        if dev_rewards is not None:
+            # a float32 device tensor [B]: comic_scst_coefficients forms coef / rs on the stream from the staged mask,
+            # into the device staging block; the host writes neither
+            if tuple(dev_rewards.shape) != (B,) or dev_rewards.dtype != torch.float32 or not dev_rewards.is_cuda:
+                raise ValueError('train_step: device rewards must be a float32 device tensor [%d], got %s %r'
+                                 % (B, dev_rewards.dtype, tuple(dev_rewards.shape)))
+            dev_rewards = dev_rewards.contiguous()
+            rs = coef = np.zeros((B, T), np.float32)
+        elif rewards is None:
             den_xe = np.float32(xe_denom) if xe_denom is not None else np.float32(wmask.sum() + np.float32(1e-12))
             rs = np.full((B, T), np.float32(1.0) / den_xe, np.float32)
             coef = wmask / den_xe
@@ -1322,12 +1532,15 @@ class Decoder:
         if phase == 'bwd':          # second call of a split step: only the coefficients are new
             assert getattr(ctx, 'split_open', False), 'train_step(phase="bwd") without its phase="fwd" call'
             ctx.split_open = False
-            slot = ctx.stage[(ctx.calls - 1) % 2]                 # the slot its forward call staged: same inputs
-            slot.copied.synchronize()
-            fh = slot.f32.numpy()
-            fh[BT:2 * BT] = coef.reshape(-1); fh[2 * BT:] = rs.reshape(-1)
-            ctx.stage_dev.copy_(slot.buf, non_blocking=True)
-            slot.copied.record(torch.cuda.current_stream())
+            if dev_rewards is not None:                           # the mask is on the device since the forward call
+                self._device_coefficients(ctx, dev_rewards)
+            else:
+                slot = ctx.stage[(ctx.calls - 1) % 2]             # the slot its forward call staged: same inputs
+                slot.copied.synchronize()
+                fh = slot.f32.numpy()
+                fh[BT:2 * BT] = coef.reshape(-1); fh[2 * BT:] = rs.reshape(-1)
+                ctx.stage_dev.copy_(slot.buf, non_blocking=True)
+                slot.copied.record(torch.cuda.current_stream())
             self._run_train_phase(ctx, 'bwd', use_graph)
             return dict(loss=ctx.loss[0], map_loss=ctx.map_loss[0], logits=ctx.logits.permute(1, 0, 2), ids=ctx.ids.t(),
                         attn_maps=ctx.hist.permute(1, 2, 0, 3), dfm=ctx.dfm, dim_embed=ctx.dim, Tp=Tp)
@@ -1343,6 +1556,8 @@ class Decoder:
                 seed = (self._dropout_base + self._dropout_calls) & 0x7FFFFFFFFFFFFFFF
             slot.seed[0] = int(seed)
         ctx.stage_dev.copy_(slot.buf, non_blocking=True)
+        if dev_rewards is not None and phase != 'fwd':
+            self._device_coefficients(ctx, dev_rewards)
         if masks is not None:
             for k, v in masks.items():
                 ctx.masks[k].copy_(v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, np.float32)))
@@ -1389,6 +1604,14 @@ class Decoder:
         ctx.calls += 1
         return dict(loss=ctx.loss[0], map_loss=ctx.map_loss[0], logits=ctx.logits.permute(1, 0, 2), ids=ctx.ids.t(),
                     attn_maps=ctx.hist.permute(1, 2, 0, 3), dfm=ctx.dfm, dim_embed=ctx.dim, Tp=Tp)
+
+    def _device_coefficients(self, ctx, rewards):
+        """coef and rs of the device staging block from its mask and the device rewards [B] (comic_scst_coefficients):
+        stream-ordered behind the staging copy, in front of the step that reads them."""
+        B, T = ctx.key[:2]
+        f = ctx.f32.data_ptr()
+        L.check(self.lib.comic_scst_coefficients(f, rewards.data_ptr(), B, T, f + 4 * B * T, f + 8 * B * T,
+                                                 L.stream_ptr()), 'scst_coefficients')
 
     def _run_train_phase(self, ctx, phase, use_graph):
         """One half of a split step, eagerly or from its own hipGraph (captured at the second use of the shape)."""
@@ -1558,7 +1781,9 @@ class Decoder:
         """rnn_decoder_search(greedy) (ops_rnn.py:115-180).  -> ids [B,T_exec] (numpy int32),
         attn_maps [B,H,T_exec,M] (device), logits [B,T_exec,V] or None.
         defer: only enqueue the loop and return a function that fetches the result (the SCST step converts the beam
-        rollouts to text on the host while this loop runs)."""
+        rollouts to text on the host while this loop runs); fetch.ids_device / fetch.first_eos_device are then the device
+        ids [max_steps,B], whose rows past the executed steps the loop never writes, and the first <EOS> positions [B]
+        that say which rows those are (the SCST reward's baseline row takes both)."""
         torch, s = self.torch, self.spec
         B = fm.shape[0]
         ctx = self._infer_ctx('greedy', B, 1, max_steps, want_logits, fm, im_embed)
@@ -1597,6 +1822,7 @@ class Decoder:
                 out_ids = ctx.ids[:t_exec].t().contiguous().cpu().numpy()
             hist = ctx.hist[:t_exec].reshape(t_exec, B, s.H, s.M).permute(1, 2, 0, 3).clone()
             return out_ids, hist, (ctx.logits[:t_exec].permute(1, 0, 2).clone() if want_logits else None)
+        fetch.ids_device, fetch.first_eos_device = ctx.ids, ctx.first_eos
         return fetch if defer else fetch()
 
     def sample(self, fm, im_embed, max_steps, seed=0, noise=None, want_logits=False):
@@ -1634,17 +1860,32 @@ class Decoder:
                                             ctx.hist.data_ptr(), ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
                                             L.stream_ptr()), 'decoder_beam')
 
-    def beam_search_ids(self, fm, im_embed, beam, max_steps, use_graph=True, slot=0):
+    def beam_search_ids(self, fm, im_embed, beam, max_steps, use_graph=True, slot=0, sampling=None, image_base=0,
+                        reward=None, reward_refs=None, reward_baseline_ids=None):
         """Beam search for its predicted ids alone, fetched WITHOUT draining the stream: the loop, gather_tree over all
         max_steps rows (rows past the executed steps come out as end_id) and the copies to pinned memory are enqueued, an
         event marks their end, and the returned function waits for that event only -- work enqueued behind it (the greedy
         rollout of the SCST step) keeps running while the host turns these ids into text.  -> fetch() -> [T,B,W] int32,
-        the same values as beam_search()['predicted_ids']."""
+        the same values as beam_search()['predicted_ids'].
+        sampling: an active BeamSampling draws `beam` samples per image instead (beam_search's sampling= / image_base=).
+        reward: a Reward with reward_refs (and reward_baseline_ids for baseline='greedy'): the reward launch follows the
+        tree gather on the device ids, all max_steps rows of them; fetch.reward is the dict of its device tensors
+        (Decoder.scst_reward; None without) and fetch.ids_device the device ids [max_steps,B,W]."""
         torch, s = self.torch, self.spec
         B, W = fm.shape[0], beam
-        ctx = self._infer_ctx('beam', B, W, max_steps, False, fm, im_embed, slot=slot)
-        ctx.desc.length_penalty_weight = 0.0
-        self._run_infer(ctx, lambda: self._launch_beam(ctx, B, W, max_steps), use_graph)
+        opts = BeamOptions(sampling=sampling, image_base=image_base, reward=reward, reward_refs=reward_refs,
+                           reward_baseline_ids=reward_baseline_ids)
+        if sampling is not None or reward is not None:
+            opts.check(s, W, B, max_steps)
+        if opts.smp is not None:
+            ens = self.__dict__.get('_self_ensemble')
+            if ens is None:
+                ens = self._self_ensemble = EnsembleDecoder([self])
+            ctx = ens._enqueue([fm], [im_embed], W, max_steps, use_graph, opts)
+        else:
+            ctx = self._infer_ctx('beam', B, W, max_steps, False, fm, im_embed, slot=slot)
+            ctx.desc.length_penalty_weight = 0.0
+            self._run_infer(ctx, lambda: self._launch_beam(ctx, B, W, max_steps), use_graph)
         if getattr(ctx, 'pred', None) is None:
             ctx.pred = torch.empty((max_steps, B, W), dtype=torch.int32, device=self.device)
             ctx.pred_host = torch.empty((max_steps, B, W), dtype=torch.int32).pin_memory()
@@ -1661,11 +1902,18 @@ class Decoder:
         def fetch():
             ctx.fetched.synchronize()
             return ctx.pred_host[:int(ctx.steps_host[0])].numpy().copy()
+        fetch.ids_device, fetch.reward = ctx.pred, None
+        if reward is not None:
+            base = reward_baseline_ids
+            if base is not None:
+                base = base if torch.is_tensor(base) else torch.from_numpy(np.ascontiguousarray(base, np.int32))
+                base = base.to(device=self.device, dtype=torch.int32).contiguous()
+            fetch.reward = scst_reward(self.lib, torch, ctx.pred, reward_refs, reward, base)
         return fetch
 
     def beam_search(self, fm, im_embed, beam, max_steps, want_attention=True, use_graph=True, length_penalty_weight=0.0,
                     constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None,
-                    consensus=None, options=None):
+                    consensus=None, options=None, reward=None, reward_refs=None, reward_baseline_ids=None):
         """rnn_decoder_beam_search (ops_rnn.py:49-112).  Returns predicted_ids [T,B,W] (after
         gather_tree), scores [T,B,W] (with length_penalty_weight != 0: the penalised scores the beams were ranked by,
         BeamSearchDecoder's `scores` output), the raw step/parent ids and, unless want_attention=False, the
@@ -1695,10 +1943,15 @@ class Decoder:
         the captured graph, with every decode above: the result gains `consensus` [B,W] float64, every candidate's mean
         CIDEr-D similarity to its siblings, and `consensus_best` [B] int32, the slot of the largest.  The posterior
         weights read `log_probs` (without groups, sampling or required words: the last `scores`); with required= they
-        are forced, so that a dead slot (-inf) neither votes nor is chosen.  None: today's path, launch for launch."""
+        are forced, so that a dead slot (-inf) neither votes nor is chosen.  None: today's path, launch for launch.
+        reward: a Reward, with reward_refs (the RewardRefs of the batch) and, for baseline='greedy', reward_baseline_ids
+        [T0,B]: one comic_scst_reward launch on the device ids right after the tree gather, outside the captured graph,
+        with every decode above: the result gains `reward` [B,W'] float64, `advantage` [W,B] float32 and `reward_device`,
+        the operator's device tensors (Decoder.scst_reward).  None: today's path, launch for launch."""
         opts = BeamOptions.of(options, length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
                               sampling=sampling, truncation=truncation, required=required, consensus=consensus,
-                              image_base=image_base)
+                              image_base=image_base, reward=reward, reward_refs=reward_refs,
+                              reward_baseline_ids=reward_baseline_ids)
         B, W = fm.shape[0], beam
         opts.check(self.spec, W, B, max_steps)
         if opts.active:
@@ -1727,6 +1980,25 @@ class Decoder:
             log_probs = lp.to(device=self.device, dtype=torch.float32).contiguous()
         util, best = caption_consensus(self.lib, torch, ids, self.spec.end_id, cons, log_probs)
         return util.cpu().numpy(), best.cpu().numpy()
+
+    def scst_reward(self, ids, refs, reward, baseline_ids=None, baseline_first_eos=None):
+        """The raw reward operator (comic_scst_reward) on ids [T,B,W] and baseline_ids [T0,B] or None, device tensors or
+        numpy arrays of rollouts as the tree gather / the greedy decode leave them, against the RewardRefs `refs` under the
+        Reward `reward`.  -> dict of DEVICE tensors: cider [B,W'], bleu [B,W',4], reward [B,W'], baseline [B,W] (float64)
+        and advantage [W,B] (float32; .reshape(-1) is what train_step(rewards=) takes).  Nothing is synchronised."""
+        torch = self.torch
+
+        def dev(a, nd, what):
+            a = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.int32))
+            if a.dim() != nd:
+                raise ValueError('scst_reward: %s must have %d dimensions, got shape %r' % (what, nd, tuple(a.shape)))
+            return a.to(device=self.device, dtype=torch.int32).contiguous()
+        ids = dev(ids, 3, 'ids')
+        if baseline_ids is not None:
+            baseline_ids = dev(baseline_ids, 2, 'baseline_ids')
+        if baseline_first_eos is not None:
+            baseline_first_eos = dev(baseline_first_eos, 1, 'baseline_first_eos')
+        return scst_reward(self.lib, torch, ids, refs, reward, baseline_ids, baseline_first_eos)
 
 
 def _gather_tree_host(step_ids, parent_ids, max_len, end_token):
@@ -1844,14 +2116,15 @@ class EnsembleDecoder:
 
     def beam_search(self, fms, im_embeds, beam, max_steps, want_attention=False, use_graph=True, length_penalty_weight=0.0,
                     constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None,
-                    consensus=None, options=None):
+                    consensus=None, options=None, reward=None, reward_refs=None, reward_baseline_ids=None):
         """fms / im_embeds: one device tensor (every member reads the same features) or a sequence with one per member.
         Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's.  The options -- these keywords
         or one BeamOptions in `options` -- are Decoder.beam_search's and mean what they mean there; every decode runs
         through comic_decoder_beam_search, and None / inactive options are the plain ensemble decode, launch for launch."""
         opts = BeamOptions.of(options, length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
                               sampling=sampling, truncation=truncation, required=required, consensus=consensus,
-                              image_base=image_base)
+                              image_base=image_base, reward=reward, reward_refs=reward_refs,
+                              reward_baseline_ids=reward_baseline_ids)
         torch, n = self.torch, len(self.decoders)
         if torch.is_tensor(fms):
             fms = [fms] * n
@@ -1862,6 +2135,11 @@ class EnsembleDecoder:
 
     def _decode(self, fms, im_embeds, beam, max_steps, want_attention, use_graph, opts):
         """The decode of checked options: one feature tensor per member."""
+        ctx = self._enqueue(fms, im_embeds, beam, max_steps, use_graph, opts)
+        return _beam_result(self, ctx, int(fms[0].shape[0]), int(beam), opts, want_attention)
+
+    def _enqueue(self, fms, im_embeds, beam, max_steps, use_graph, opts):
+        """The launches of a decode of checked options, without a fetch -> its context."""
         torch, n = self.torch, len(self.decoders)
         assert len(fms) == n and len(im_embeds) == n
         B, W, max_steps = int(fms[0].shape[0]), int(beam), int(max_steps)
@@ -1881,4 +2159,4 @@ class EnsembleDecoder:
                 ctx.finished.data_ptr(), ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
                 L.stream_ptr()), 'decoder_beam_search')
         Decoder._run_infer(self, ctx, launch, use_graph)
-        return _beam_result(self, ctx, B, W, opts, want_attention)
+        return ctx

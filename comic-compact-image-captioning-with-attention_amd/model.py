@@ -868,9 +868,19 @@ class CaptionModel_SCST(ModelBase):
             self._create_optimiser()
         print('INFO: Model `{}` initialisation complete.'.format(scst_mode))
 
-    def sample(self, imgs, defer_greedy=False):
+    def sample(self, imgs, defer_greedy=False, rollout='beam', temperature=1.0, greedy=True, reward=None,
+               reward_refs=None):
         """-> (dec_preds_beam (beam,B,T), dec_preds_greedy (B,T)); beam search with
         infer_max_length=20, length penalty 0 (model_base.py:208-215).
+        rollout='sample': the scst_beam_size rollouts of an image are independent samples drawn inside the beam step
+        (decoder.BeamSampling(temperature, seed=rand_seed)); image_base, the index in the run of the batch's first image, is
+        (global step * world size + rank) * batch size, so a resumed or data-parallel run never reuses noise.
+        greedy=False: no greedy rollout is enqueued and the second value is None (the leave-one-out baseline needs none).
+        reward (a decoder.Reward, with reward_refs, the batch's RewardRefs): the reward launch is enqueued behind the
+        rollouts on their device ids -- behind the greedy rollout where that is the baseline -- and self.rollout_reward is
+        the dict of its device tensors (Decoder.scst_reward); None otherwise.
+        Any of the three takes the deferred form:
+        the second value is a fetch function (or None).  The defaults are today's launches in today's order.
         defer_greedy: the beam rollouts are enqueued first and fetched without draining the stream, the greedy rollout is
         enqueued behind them and the second return value is a function that fetches it: the caller turns the beam ids into
         text meanwhile (same parameters, same features: the order of the two rollouts changes nothing)."""
@@ -888,6 +898,30 @@ class CaptionModel_SCST(ModelBase):
         # ... and the training step on the same images that follows (train_fn_scst: the CNN is frozen in SCST mode, so
         # run_train_scst takes these features instead of a second forward)
         self._share['scst_features'] = (imgs, im_embed.clone(), fm.clone())
+        self.rollout_reward = None
+        if rollout != 'beam' or not greedy or reward is not None:
+            from .decoder import BeamSampling
+            dec = self.decoder
+            iters = dec.max_iterations(20, len(c.wtoi))
+            B = int(fm.shape[0])
+            smp = None
+            if rollout == 'sample':
+                smp = BeamSampling(temperature, seed=int(c.rand_seed))
+            elif rollout != 'beam':
+                raise ValueError("scst_rollout must be 'beam' or 'sample', got %r" % (rollout,))
+            by_row = reward is not None and reward.baseline == 'greedy'
+            if by_row and not greedy:
+                raise ValueError("the reward's 'greedy' baseline needs the greedy rollout")
+            fetch_beam = dec.beam_search_ids(
+                fm, im_embed, c.scst_beam_size, iters, sampling=smp,
+                image_base=(self.global_step * self.dp.world + self.dp.rank) * B if smp is not None else 0)
+            fetch_greedy = dec.greedy(fm, im_embed, iters, defer=True) if greedy else None
+            if reward is not None:
+                self.rollout_reward = dec.scst_reward(fetch_beam.ids_device, reward_refs, reward,
+                                                      fetch_greedy.ids_device if by_row else None,
+                                                      fetch_greedy.first_eos_device if by_row else None)
+            beam = fetch_beam().transpose(2, 1, 0).copy()                 # (W, B, T)
+            return beam, ((lambda: fetch_greedy()[0]) if greedy else None)
         if defer_greedy and c.scst_beam_size > 1:
             iters = self.decoder.max_iterations(20, len(c.wtoi))
             fetch_beam = self.decoder.beam_search_ids(fm, im_embed, c.scst_beam_size, iters)
@@ -930,7 +964,8 @@ class CaptionModel_SCST(ModelBase):
     def run_train_scst(self, imgs, captions, rewards, tile=1):
         """One reward-weighted update on `tile` hypotheses per image.  imgs: the batch tiled `tile`
         times (tile=1, the reference's feed) or the untiled batch with tile=beam: the frozen encoder
-        then runs once and (im_embed, fm) are tiled -- same values, 1/tile of the CNN work."""
+        then runs once and (im_embed, fm) are tiled -- same values, 1/tile of the CNN work.
+        rewards: numpy, or a float32 device tensor (self.rollout_reward['advantage']): no host round trip."""
         kept = self._share.pop('scst_features', None)
         if kept is not None and kept[0] is imgs and 'opt_cnn' not in self._share:
             im_embed, fm = kept[1], kept[2]          # the sampling pass's features of these very images
@@ -943,10 +978,17 @@ class CaptionModel_SCST(ModelBase):
             self._share['scst_open'] = np.asarray(captions)
             return None
         lr = self.lr
-        res = self.decoder.train_step(fm, im_embed, np.asarray(captions), rewards=np.asarray(rewards, np.float32),
+        res = self.decoder.train_step(fm, im_embed, np.asarray(captions), rewards=self._rewards(rewards),
                                       training=True, use_graph=True)
         self.dp.exchange_and_step(self.opt, self.decoder.grads, lr)
         return res['loss']
+
+    def _rewards(self, rewards):
+        """float32 numpy rewards, or a device tensor (the advantage of the device reward, any shape of tile * batch
+        elements in the row order of the captions): it stays on the device (Decoder.train_step)."""
+        if self.torch.is_tensor(rewards):
+            return rewards.reshape(-1)
+        return np.asarray(rewards, np.float32)
 
     def begin_train_scst(self, imgs, captions, tile=1):
         """The part of run_train_scst that needs no reward -- encoder features, teacher-forced forward to the logits -- enqueued
@@ -957,7 +999,7 @@ class CaptionModel_SCST(ModelBase):
         """Loss, backward and update of the step begin_train_scst started (same kernels in the same order as run_train_scst)."""
         captions = self._share.pop('scst_open')
         lr = self.lr
-        res = self.decoder.train_step(None, None, captions, rewards=np.asarray(rewards, np.float32), training=True,
+        res = self.decoder.train_step(None, None, captions, rewards=self._rewards(rewards), training=True,
                                       use_graph=True, phase='bwd')
         self.dp.exchange_and_step(self.opt, self.decoder.grads, lr)
         return res['loss']

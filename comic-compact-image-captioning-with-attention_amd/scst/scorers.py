@@ -57,6 +57,23 @@ class captionScorer(object):
         L.check(self.lib.comic_scorer_score(self._h, hy, n, rf, per, cider, bleu, self.n_threads), 'scorer_score')
         return np.frombuffer(cider, np.float64).copy(), np.frombuffer(bleu, np.float64).reshape(n, 4).copy()
 
+    def _total(self, cider, bleu):
+        total = np.zeros(len(cider))
+        w = self.weights
+        if 'ciderD' in w and np.amax(w['ciderD']) > 0:
+            total = total + cider * w['ciderD']
+        if 'bleu' in w and np.amax(w['bleu']) > 0:
+            for i, wi in enumerate(w['bleu']):
+                total = total + bleu[:, i] * wi
+        return total
+
+    def get_scores(self, refs, sample):
+        """The weighted scores of `sample` alone (the order of get_hypo_scores: sample i uses refs[i % len(refs)]): what a
+        baseline formed among the samples needs -- no greedy caption is scored."""
+        n = len(refs)
+        assert isinstance(refs, list) and isinstance(sample, list) and len(sample) % n == 0
+        return self._total(*self._score([s[0] for s in sample], [list(refs[i % n]) for i in range(len(sample))]))
+
     def get_hypo_scores(self, refs, sample, greedy, best_hypo_only=False):
         """Same contract as the reference: `sample` = [[im0_h0],...,[imN_h0],[im0_h1],...];
         returns (final_hypo, sc_sample, sc_greedy) with the greedy baseline tiled to len(sample)."""
@@ -67,14 +84,7 @@ class captionScorer(object):
         mult = ns // ng
         hypos = [g[0] for g in greedy] + [s[0] for s in sample]
         rlist = [list(refs[i]) for i in range(ng)] + [list(refs[i % ng]) for i in range(ns)]
-        cider, bleu = self._score(hypos, rlist)
-        total = np.zeros(ng + ns)
-        w = self.weights
-        if 'ciderD' in w and np.amax(w['ciderD']) > 0:
-            total = total + cider * w['ciderD']
-        if 'bleu' in w and np.amax(w['bleu']) > 0:
-            for i, wi in enumerate(w['bleu']):
-                total = total + bleu[:, i] * wi
+        total = self._total(*self._score(hypos, rlist))
         sc_greedy, sc_sample = total[:ng], total[ng:]
         if ns > ng and best_hypo_only:
             sc = sc_sample.reshape(mult, ng)

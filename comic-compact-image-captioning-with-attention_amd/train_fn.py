@@ -121,6 +121,108 @@ def train_fn_scst(config, idx_ngram=False, device='cuda:0', dp=None):
         inputs_man.close()
 
 
+def scst_options(c):
+    """The SCST options of a configuration (absent in one written before they existed: the defaults): rollout 'beam' /
+    'sample', temperature, baseline 'greedy' / 'mean', reward 'host' / 'device'; `default` says all are today's."""
+    from types import SimpleNamespace
+    o = SimpleNamespace(rollout=getattr(c, 'scst_rollout', None) or 'beam',
+                        temperature=float(getattr(c, 'scst_temperature', None) or 1.0),
+                        baseline=getattr(c, 'scst_baseline', None) or 'greedy', reward=getattr(c, 'scst_reward', None) or 'host')
+    o.default = (o.rollout, o.baseline, o.reward) == ('beam', 'greedy', 'host')
+    return o
+
+
+def leave_one_out(scores, W):
+    """scores [W * B], hypothesis-major -> the advantage against the mean of the image's other W - 1 scores, summed in
+    ascending order of the hypothesis (the device reward's LEAVE_ONE_OUT baseline), and that baseline; both [W * B]."""
+    sc = np.asarray(scores, np.float64).reshape(W, -1)
+    base = np.zeros_like(sc)
+    for i in range(W):
+        for j in range(W):
+            if j != i:
+                base[i] += sc[j]
+    base /= (W - 1)
+    return (sc - base).reshape(-1), base.reshape(-1)
+
+
+def scst_step(c, inputs_man, m_sample, m_train, scorer, imgs, refs, prefetch=None, reward=None, log=True):
+    """One SCST step: rollouts -> reward -> update.  prefetch: called where the host would otherwise wait (the next batch's
+    encoder forward); reward: the decoder.Reward of --scst_reward device.  log: fetch what the log lines print.
+    -> namespace(ppl, rewards, hypos, hypos_idx, cap_greedy, sc_greedy, mean_reward, mean_baseline, max_reward,
+    max_baseline, ids); rewards is what the update took: numpy [W * B], or with the device reward the float32 device tensor
+    [W, B]; the four statistics are None when they would cost a fetch that `log` did not ask for, sc_greedy is None without
+    a host-scored greedy rollout; ids are the rollouts' ids [W * B, T].  With the default options the launches and the host
+    work are the ones of the loop before the options existed, in their order."""
+    from types import SimpleNamespace
+    o = scst_options(c)
+    out = SimpleNamespace(cap_greedy=None, sc_greedy=None, mean_reward=None, mean_baseline=None, max_reward=None,
+                          max_baseline=None)
+    # `cap_beam` is (beam_size, batch_size, time) -> (beam_size * batch_size, time):
+    # [[im0_hypo0], ..., [imN_hypo0], [im0_hypo1], ..., [imN_hypo1]]   (train_fn.py:226-238)
+    # (the greedy rollout runs on the device while the host turns the beam rollouts into text and ids)
+    if o.default:
+        cap_beam, fetch_greedy = m_sample.sample(imgs, defer_greedy=True)
+    else:
+        packed = None
+        if o.reward == 'device':
+            from .decoder import RewardRefs
+            packed = RewardRefs.pack(refs, reward.vocab)
+        cap_beam, fetch_greedy = m_sample.sample(imgs, defer_greedy=True, rollout=o.rollout, temperature=o.temperature,
+                                                 greedy=o.baseline == 'greedy',
+                                                 reward=reward if o.reward == 'device' else None, reward_refs=packed)
+    W = cap_beam.shape[0]
+    cap_beam = np.reshape(cap_beam, [-1, cap_beam.shape[-1]])
+    out.ids = cap_beam
+    # every sampled hypothesis is trained on (get_hypo_scores returns `sample` itself), so the update's forward pass --
+    # which no reward enters -- is enqueued BEFORE the host scores the rollouts and runs on the device meanwhile.
+    # The reference feeds the images tiled by the beam size (train_fn.py:251-253); the CNN is frozen and
+    # deterministic, so the encoder runs once and its two outputs are tiled instead
+    if o.rollout == 'sample':
+        # sampled digits can spell the one word id the table lacks: it is skipped, as the ids beyond the vocabulary are
+        cap_beam = [[s] for s in id_to_caption(cap_beam, c, skip_unmapped=True)]
+        hypos_idx = inputs_man.captions_to_batched_ids(cap_beam)
+    elif c.token_type == 'radix' and getattr(inputs_man, 'radix_wtoi', None) is not None:
+        # ids -> text -> target ids in one pass (equal to the two calls; the host work between the rollouts and the
+        # update's forward pass is what the device waits for)
+        caps, hypos_idx = radix_ids_to_captions_and_ids(cap_beam, c, inputs_man.radix_wtoi)
+        cap_beam = [[s] for s in caps]
+    else:
+        cap_beam = [[s] for s in id_to_caption(cap_beam, c)]
+        hypos_idx = inputs_man.captions_to_batched_ids(cap_beam)
+    # the update's forward pass goes to the device BEFORE the host looks at the greedy rollout (which is still running:
+    # its ids come back through an event of their own), so the device runs rollouts and update back to back
+    m_train.begin_train_scst(imgs, hypos_idx, tile=c.scst_beam_size)
+    if fetch_greedy is not None and (o.reward == 'host' or log):
+        out.cap_greedy = [[s] for s in id_to_caption(fetch_greedy(), c, skip_unmapped=o.rollout == 'sample')]
+    if prefetch is not None:
+        prefetch()
+    if o.reward == 'device':
+        dev = m_sample.rollout_reward
+        rewards = dev['advantage']
+        if log:                                   # the only fetches of the device path, at the log steps
+            r, base = dev['reward'].cpu().numpy(), dev['baseline'].cpu().numpy()
+            out.mean_reward, out.max_reward = float((r[:, :W] - base).mean()), float(r[:, :W].max())
+            out.mean_baseline, out.max_baseline = float(base.mean()), float(base.max())
+        out.hypos = cap_beam
+    elif o.baseline == 'greedy':
+        hypos, sc_sample, sc_greedy = scorer.get_hypo_scores(refs, cap_beam, out.cap_greedy)
+        rewards = sc_sample - sc_greedy
+        assert hypos is cap_beam and hypos_idx.shape[0] == sc_sample.shape[0]
+        out.hypos, out.sc_greedy = hypos, sc_greedy
+        if log:
+            out.mean_reward, out.mean_baseline, out.max_reward = np.mean(rewards), np.mean(sc_greedy), np.amax(sc_sample)
+    else:
+        sc_sample = scorer.get_scores(refs, cap_beam)
+        rewards, base = leave_one_out(sc_sample, W)
+        out.hypos = cap_beam
+        if log:
+            out.mean_reward, out.mean_baseline, out.max_reward = np.mean(rewards), np.mean(base), np.amax(sc_sample)
+    out.ppl = m_train.finish_train_scst(rewards)
+    out.rewards, out.hypos_idx = rewards, hypos_idx
+    out.reward_device = dev if o.reward == 'device' else None
+    return out
+
+
 def _scst_loop(inputs_man, idx_ngram, device, dp):
     inputs_man.enable_device_preprocess(device)
     c = inputs_man.config
@@ -143,7 +245,15 @@ def _scst_loop(inputs_man, idx_ngram, device, dp):
     print('INFO: Graph constructed. SCST training begins now.')
     start_epoch = time.time()
     greedy_high_sc = 0
+    high_reward, high_base = -np.inf, 0     # (the device reward: the largest seen at the log steps, where it is fetched)
     ahead = None
+    opts = scst_options(c)
+    reward = None
+    if opts.reward == 'device':
+        from .decoder import Reward
+        iters = m_sample.decoder.max_iterations(20, len(c.wtoi))
+        reward = Reward.from_pickle(idf_fp, c, baseline=opts.baseline)
+        reward.check(c.scst_beam_size, iters, iters if opts.baseline == 'greedy' else None)
     # --encoder_group G > 1 (frozen CNN): the images of the next G steps go through ONE encoder forward, enqueued while the
     # host scores the current step (CaptionModel_SCST.prefetch_group); 1 = one forward per step, prefetched one step ahead
     group = int(getattr(c, 'encoder_group', 1) or 0)
@@ -159,56 +269,45 @@ def _scst_loop(inputs_man, idx_ngram, device, dp):
             imgs, refs = queue.pop(0)
         else:
             imgs, refs = ahead if ahead is not None else next(inputs_man.batch_train)
-        # `cap_beam` is (beam_size, batch_size, time) -> (beam_size * batch_size, time):
-        # [[im0_hypo0], ..., [imN_hypo0], [im0_hypo1], ..., [imN_hypo1]]   (train_fn.py:226-238)
-        # (the greedy rollout runs on the device while the host turns the beam rollouts into text and ids)
-        cap_beam, fetch_greedy = m_sample.sample(imgs, defer_greedy=True)
-        cap_beam = np.reshape(cap_beam, [-1, cap_beam.shape[-1]])
-        # every sampled hypothesis is trained on (get_hypo_scores returns `sample` itself), so the update's forward pass --
-        # which no reward enters -- is enqueued BEFORE the host scores the rollouts and runs on the device meanwhile.
-        # The reference feeds the images tiled by the beam size (train_fn.py:251-253); the CNN is frozen and
-        # deterministic, so the encoder runs once and its two outputs are tiled instead
-        if c.token_type == 'radix' and getattr(inputs_man, 'radix_wtoi', None) is not None:
-            # ids -> text -> target ids in one pass (equal to the two calls; the host work between the rollouts and the
-            # update's forward pass is what the device waits for)
-            caps, hypos_idx = radix_ids_to_captions_and_ids(cap_beam, c, inputs_man.radix_wtoi)
-            cap_beam = [[s] for s in caps]
-        else:
-            cap_beam = [[s] for s in id_to_caption(cap_beam, c)]
-            hypos_idx = inputs_man.captions_to_batched_ids(cap_beam)
-        # the update's forward pass goes to the device BEFORE the host looks at the greedy rollout (which is still running:
-        # its ids come back through an event of their own), so the device runs rollouts and update back to back
-        m_train.begin_train_scst(imgs, hypos_idx, tile=c.scst_beam_size)
-        cap_greedy = [[s] for s in id_to_caption(fetch_greedy(), c)]
-        # the next batch's encoder forward joins the update's forward pass on the device while the host scores
-        if group > 1:
-            if not queue and step + 1 < c.max_step:
-                queue = [next(inputs_man.batch_train) for _ in range(min(group, c.max_step - step - 1))]
-                m_sample.prefetch_group([b[0] for b in queue])
-        else:
-            ahead = next(inputs_man.batch_train) if step + 1 < c.max_step else None
-            if ahead is not None:
-                m_sample.prefetch_features(ahead[0])
-        hypos, sc_sample, sc_greedy = scorer.get_hypo_scores(refs, cap_beam, cap_greedy)
-        rewards = sc_sample - sc_greedy
-        greedy_high_sc = max(greedy_high_sc, np.amax(sc_greedy))
-        assert hypos is cap_beam and hypos_idx.shape[0] == sc_sample.shape[0]
-        ppl = m_train.finish_train_scst(rewards)
+        def prefetch():
+            # the next batch's encoder forward joins the update's forward pass on the device while the host scores
+            nonlocal queue, ahead
+            if group > 1:
+                if not queue and step + 1 < c.max_step:
+                    queue = [next(inputs_man.batch_train) for _ in range(min(group, c.max_step - step - 1))]
+                    m_sample.prefetch_group([b[0] for b in queue])
+            else:
+                ahead = next(inputs_man.batch_train) if step + 1 < c.max_step else None
+                if ahead is not None:
+                    m_sample.prefetch_features(ahead[0])
+        res = scst_step(c, inputs_man, m_sample, m_train, scorer, imgs, refs, prefetch=prefetch, reward=reward,
+                        log=(step + 1) % n_steps_log == 0)
+        ppl, hypos, cap_greedy = res.ppl, res.hypos, res.cap_greedy
+        if res.sc_greedy is not None:
+            greedy_high_sc = max(greedy_high_sc, np.amax(res.sc_greedy))
+        if res.max_reward is not None:
+            high_reward = max(high_reward, res.max_reward)
+        if res.max_baseline is not None:
+            high_base = max(high_base, res.max_baseline)
         global_step = m_train.global_step
         if (step + 1) % (n_steps_log * 5) == 0:
             t = time.time() - start_epoch
             speed = (step + 1 - start_step) * c.batch_size_train / t
             logstr = '\n   Training speed: {:7.2f} examples/sec.'.format(speed)
-            logstr += '\n   mean reward: \t{:8.4f}'.format(np.mean(rewards))
-            logstr += '\n   greedy high score: \t{:8.4f}'.format(greedy_high_sc)
-            logstr += '\n   greedy: \t\t`{}`'.format(cap_greedy[0][0])
+            logstr += '\n   mean reward: \t{:8.4f}'.format(res.mean_reward)
+            if opts.baseline == 'greedy':
+                logstr += '\n   greedy high score: \t{:8.4f}'.format(greedy_high_sc if res.sc_greedy is not None else high_base)
+                logstr += '\n   greedy: \t\t`{}`'.format(cap_greedy[0][0])
+            else:
+                logstr += '\n   high reward: \t{:8.4f}'.format(high_reward)
             logstr += '\n   top beam: \t\t`{}`\n'.format(hypos[0][0])
             print(logstr)
         elif (step + 1) % n_steps_log == 0:
             _check_loss(ppl, global_step, m_train, dp)
             logstr = '   Epoch {:2d} ~~ {:6.2f} %  ~  '.format(epoch, ((step % num_batches) + 1) / num_batches * 100)
-            logstr += 'Greedy score {:8.4f} ~ Loss {:8.4f} ~ LR {:5.3e} ~ Step {}'.format(
-                np.mean(sc_greedy), float(ppl), m_train.lr, global_step)
+            logstr += '{} {:8.4f} ~ Loss {:8.4f} ~ LR {:5.3e} ~ Step {}'.format(
+                'Greedy score' if opts.baseline == 'greedy' else 'Mean baseline', res.mean_baseline, float(ppl), m_train.lr,
+                global_step)
             print(logstr)
         if num_batches > 5000:
             save = (step + 1) % int(num_batches / 2) == 0

@@ -743,6 +743,64 @@ int comic_caption_consensus(const int32_t* ids_tbw, int T, int B, int W, int end
                             const double* table_g, int64_t table_cap, double log_ref_len, double sigma,
                             double* utility_bw, int32_t* best_b, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The SCST reward on the device (csrc/scst_reward.hip): CIDEr-D and per-sentence BLEU-1..4 of the W rollouts of every
+ * image (and of an optional baseline rollout) against the image's reference captions, the baseline and the advantage,
+ * in one launch -- captionScorer.get_hypo_scores, common/scst/scorers.py:43-171, over ciderD_scorer.py:52-222 and
+ * bleu_scorer.py:23-263, on word ids instead of text.
+ *   Rollouts.  ids_tbw [T, B, W] int32 as comic_gather_tree leaves them; baseline_ids_t0b_or_null [T0, B] (the greedy
+ *     caption) adds a row: W' = W + 1 with it, W without.  baseline_first_eos_b_or_null [B] (comic_decoder_greedy's
+ *     first_eos): the greedy loop ends when every image has emitted <EOS> and never writes the rows behind, so with it
+ *     only the rows t < min(T0, max_b first_eos[b] + 1) of the baseline ids are read -- what the host reads; NULL: all T0.
+ *   Canonical words.  Every rollout is first reduced to the word ids that ops.id_to_caption(skip_unmapped=True) turns
+ *     into text.  COMIC_SCST_TOKENS_WORD: the tokens t with 0 <= t < vocab and t != end_id, in order, wherever they stand
+ *     (word_len must be 1).  COMIC_SCST_TOKENS_RADIX: the digits 0 <= t < radix_base in order; ONE trailing digit is
+ *     dropped when their count is no multiple of word_len, whatever the remainder; groups of word_len digits combine
+ *     most significant first, a short last group (word_len > 2) decodes as it stands; word ids >= vocab are dropped.
+ *     vocab is the number of word ids the table maps: len(itow), less one where the table lacks the id len(itow) - 1.
+ *     All n-gram work is on these word ids, one id per word, for both token types.
+ *   References.  refs_brl [B, R, Lr] int32 word ids, negative = padding (skipped); n_refs_b [B], 1 <= n_refs <= R (clamped
+ *     to [0, R]; 0 references give NaN).  A word outside the vocabulary carries an extended id >= vocab, one per distinct
+ *     string (decoder.RewardVocab): it matches among references and in the table, never a rollout.
+ *   Table.  As comic_caption_consensus's, built with one token per word (stride 1) through the same extended ids; NULL:
+ *     every n-gram weighs 1.
+ *   CIDEr-D of rollout h.  vec, norm and len as comic_caption_consensus states them (len = the bigram count, the host
+ *     scorer's own rule), for h and for every reference; val_k(h, r) as there; cider = 10 * (sum_k sum_r val_k(h, r)) / 4
+ *     / n_refs, r ascending inside k ascending.
+ *   BLEU-1..4 of rollout h.  correct_k = sum over the distinct n-grams of h of min(tf_h, max_r tf_r); guess_k =
+ *     max(0, words - k + 1); running product of (correct_k + 1e-15) / (guess_k + 1e-9), bleu_k = product^(1/k); the
+ *     reference length is the closest to the rollout's, ties to the shorter; ratio = (words + 1e-15) / (reflen + 1e-9),
+ *     and every bleu_k is multiplied by exp(1 - 1 / ratio) when ratio < 1.
+ *   Reward.  r = cider * w_cider + bleu_1 * w_bleu4[0] + ... + bleu_4 * w_bleu4[3], added in that order.  A metric whose
+ *     largest weight is <= 0 is skipped: it adds nothing and its output is 0.  w_bleu4 is a HOST pointer.
+ *   Baseline, for the W rollouts.  COMIC_SCST_BASELINE_NONE: 0.  _ROW: the reward of the baseline row (which must be
+ *     given).  _LEAVE_ONE_OUT: (sum_{j != i} r_j) / (W - 1), j ascending; needs W >= 2.
+ *   Results.  cider_bw [B, W'], bleu_bw4 [B, W', 4], reward_bw [B, W'] and baseline_bw [B, W] double; advantage_wb
+ *     [W, B] float32 = float32(r - baseline), hypothesis-major (row w * B + b): the row order of the SCST update.
+ *   Arithmetic.  All float64; every sum is formed by one lane in one fixed order: two runs give the same bits.
+ *   Limits, refused before any launch (rc 2; the workspace query returns -1): 1 <= W <= 32, 1 <= R <= 8, 1 <= Lr <= 64,
+ *     1 <= word_len <= 8, T and T0 <= 64 * word_len, and the LDS of the geometry -- (W' + R) captions of
+ *     Ucap = max(ceil(T / word_len), ceil(T0 / word_len), Lr) words at 72 bytes a word, plus 11 776 bytes -- within a
+ *     workgroup's 160 KiB.  comic_scst_reward_workspace returns those LDS bytes (no global workspace is needed).
+ *
+ * comic_scst_coefficients: the two float32 blocks that comic_decoder_train_step's SCST loss reads, formed on the device
+ * from the staged mask wmask_rt [rows, T] and advantage_r [rows] with the float32 operations of the host formula
+ * (Decoder.train_step): den = sum_t wmask + 1e-12f; rb = adv / rows; row_scale = rb / den; coef = wmask / den * rb.
+ * Correctly rounded division, no contraction: bit-equal to numpy. */
+#define COMIC_SCST_TOKENS_WORD 0
+#define COMIC_SCST_TOKENS_RADIX 1
+#define COMIC_SCST_BASELINE_NONE 0
+#define COMIC_SCST_BASELINE_ROW 1
+#define COMIC_SCST_BASELINE_LEAVE_ONE_OUT 2
+int64_t comic_scst_reward_workspace(int B, int W, int has_baseline_row, int T, int T0, int word_len, int R, int Lr);
+int comic_scst_reward(const int32_t* ids_tbw, int T, int B, int W, const int32_t* baseline_ids_t0b_or_null, int T0,
+                      const int32_t* baseline_first_eos_b_or_null, int token_mode, int end_id, int radix_base, int word_len, int vocab, const int32_t* refs_brl,
+                      const int32_t* n_refs_b, int R, int Lr, const uint64_t* table_keys_or_null, const double* table_g,
+                      int64_t table_cap, double log_ref_len, double sigma, double w_cider, const double* w_bleu4,
+                      int baseline_mode, double* cider_bw, double* bleu_bw4, double* reward_bw, double* baseline_bw,
+                      float* advantage_wb, void* stream);
+int comic_scst_coefficients(const float* wmask_rt, const float* advantage_r, int rows, int T, float* coef_rt,
+                            float* row_scale_rt, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Optimiser (model_base.py:852-883; tf.train.AdamOptimizer ApplyAdam, TF-1.9)  */
 /* ------------------------------------------------------------------------- */

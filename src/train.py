@@ -65,6 +65,14 @@ def create_parser():
     a('--scst_beam_size', type=int, default=7, help='The beam size for SCST sampling.')
     a('--scst_weight_ciderD', type=float, default=1.0, help='The weight for CIDEr-D metric during SCST training.')
     a('--scst_weight_bleu', type=str, default='0,0,0,2', help='The weight for BLEU metrics during SCST training.')
+    a('--scst_rollout', type=str, default='beam', choices=['beam', 'sample'],
+      help='SCST rollouts: `beam` search, or `sample`: scst_beam_size independent samples per image, drawn on the device.')
+    a('--scst_temperature', type=float, default=1.0, help='Temperature of the sampled SCST rollouts.')
+    a('--scst_baseline', type=str, default='greedy', choices=['greedy', 'mean'],
+      help='SCST baseline: the reward of the `greedy` rollout, or `mean`: the mean reward of the image\'s other rollouts '
+           '(leave-one-out; no greedy rollout is decoded; needs --scst_beam_size >= 2).')
+    a('--scst_reward', type=str, default='host', choices=['host', 'device'],
+      help='Where the SCST reward is formed: the `host` scorer on text, or one launch on the `device` (word / radix tokens).')
     a('--freeze_scopes', type=str, default='Model/encoder/cnn', help='The scopes to freeze / do not train.')
     a('--checkpoint_path', type=str, default=None, help='The checkpoint path.')
     a('--checkpoint_exclude_scopes', type=str, default='', help='The scopes to exclude when restoring from checkpoint.')
@@ -144,6 +152,7 @@ def build_kwargs(args):
         args.freeze_scopes, args.checkpoint_path = 'Model/encoder/cnn', cnnft_dir
         scst = 'beam_{}_CrD_{}_B1_{}_B4_{}'.format(args.scst_beam_size, args.scst_weight_ciderD,
                                                    args.scst_weight_bleu[0], args.scst_weight_bleu[-1])
+        scst += scst_dir_suffix(args)
         log_path = pjoin(log_root, '{}_cnnFT_SCST_{}_run_{:02d}'.format(name, scst, args.run))
         train_fn_name = 'train_fn_scst'
     args.resume_training = overwrite = os.path.exists(log_path)
@@ -177,13 +186,49 @@ def refuse_bad_ema_decay(ema_decay):
         raise ValueError('--ema_decay must be in [0, 1) (0 = off), got {}'.format(ema_decay))
 
 
+def scst_dir_suffix(args):
+    """'_smp' ('_smp_t0.7' when the temperature is not 1) for sampled rollouts and / or '_loo' for the leave-one-out
+    baseline; '' for the defaults.  Where the reward is formed changes no name: it changes no result beyond rounding."""
+    out = ''
+    if getattr(args, 'scst_rollout', 'beam') == 'sample':
+        t = float(getattr(args, 'scst_temperature', 1.0))
+        out += '_smp' if t == 1.0 else '_smp_t%g' % t
+    if getattr(args, 'scst_baseline', 'greedy') == 'mean':
+        out += '_loo'
+    return out
+
+
+def refuse_bad_scst_options(kw):
+    """--scst_baseline mean, --scst_rollout sample or --scst_reward device with one rollout per image (the one-rollout
+    step decodes through another path, which has none of them), --scst_reward device with `char`
+    tokens (the device reward works on words) and a temperature that is not finite and > 0.  Called before anything
+    touches the GPU."""
+    if kw.get('train_mode') != 'scst':
+        return
+    if kw.get('scst_baseline', 'greedy') == 'mean' and int(kw.get('scst_beam_size', 7)) < 2:
+        raise ValueError('--scst_baseline mean needs --scst_beam_size >= 2, got {}'.format(kw.get('scst_beam_size')))
+    if kw.get('scst_reward', 'host') == 'device' and kw.get('token_type') == 'char':
+        raise ValueError('--scst_reward device needs `word` or `radix` tokens, not `char` (use --scst_reward host)')
+    if int(kw.get('scst_beam_size', 7)) < 2 and (kw.get('scst_reward', 'host') == 'device'
+                                                 or kw.get('scst_rollout', 'beam') == 'sample'):
+        raise ValueError('--scst_rollout sample and --scst_reward device need --scst_beam_size >= 2, got {}'.format(
+            kw.get('scst_beam_size')))
+    if kw.get('scst_reward', 'host') == 'device' and int(kw.get('scst_beam_size', 7)) > 32:
+        raise ValueError('--scst_reward device takes --scst_beam_size <= 32, got {}'.format(kw.get('scst_beam_size')))
+    t = float(kw.get('scst_temperature', 1.0))
+    if kw.get('scst_rollout', 'beam') == 'sample' and not (t > 0.0 and t < float('inf')):
+        raise ValueError('--scst_temperature must be finite and > 0, got {}'.format(kw.get('scst_temperature')))
+
+
 def check_supported(kw):
     """Options of the reference that this hot path does not implement fail HERE instead of silently training a different
-    model.  Refused: --train_mode cnn_finetune with --cnn_dtype f16 (refuse_unsupported_dtype).  --clip_gradient_norm (model_base.py:394-401) is per-variable tf.clip_by_norm
-    in front of the optimiser (optim.GradClip), --rnn_name LN_LSTM / GRU (model_base.py:622-629) run on the per-step
-    launch chain."""
+    model.  Refused: --train_mode cnn_finetune with --cnn_dtype f16 (refuse_unsupported_dtype); --scst_baseline mean with
+    --scst_beam_size 1 and --scst_reward device with `char` tokens (refuse_bad_scst_options).  --clip_gradient_norm
+    (model_base.py:394-401) is per-variable tf.clip_by_norm in front of the optimiser (optim.GradClip), --rnn_name
+    LN_LSTM / GRU (model_base.py:622-629) run on the per-step launch chain."""
     refuse_unsupported_dtype(kw.get('train_mode'), kw.get('cnn_dtype'))
     refuse_bad_ema_decay(kw.get('ema_decay'))
+    refuse_bad_scst_options(kw)
     bad = []
     # --initialiser: `he` / `none` select TensorFlow's default initialiser in the reference (model_base.py:823-831:
     # every value but `xavier` returns None), which for these float variables is glorot_uniform == Xavier-uniform
@@ -196,6 +241,7 @@ def main(argv=None):
     args = create_parser().parse_args(argv)
     refuse_unsupported_dtype(args.train_mode, args.cnn_dtype)
     refuse_bad_ema_decay(args.ema_decay)
+    refuse_bad_scst_options(vars(args))
     import torch
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
