@@ -115,6 +115,10 @@ class BeamOptions(C.Structure):      # struct comic_beam_options
     _fields_ = [(n, c_void_p) for n in ('constraints', 'groups', 'sampling', 'truncation', 'required', 'req')]
 
 
+class BeamPrefix(C.Structure):       # struct comic_beam_prefix
+    _fields_ = [('max_tokens', c_int32)]
+
+
 class GemmProb(C.Structure):         # struct comic_gemm_prob
     _fields_ = [(n, c_void_p) for n in ('A', 'B', 'C', 'bias', 'mask')] + [(n, c_int32) for n in (
         'M', 'N', 'K', 'lda', 'ldb', 'ldc', 'ld_mask')] + [(n, c_float) for n in ('alpha', 'beta', 'keep')] + [
@@ -245,6 +249,11 @@ _SIGS = {
     # the entry the package decodes through; the named per-option entries above stay bound for the tests of the stable ABI
     'comic_decoder_beam_search_workspace': (c_int64, [P, c_int, c_int, c_int, P]),
     'comic_decoder_beam_search': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, c_int64, P]),
+    # ... and from a forced prefix: the record and its device table travel beside the options
+    'comic_beam_prefix_mask': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'comic_decoder_beam_search_prefixed_workspace': (c_int64, [P, c_int, c_int, c_int, P, P]),
+    'comic_decoder_beam_search_prefixed': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P,
+                                                   c_int64, P]),
     'comic_caption_consensus_workspace': (c_int64, [c_int, c_int, c_int, c_int]),
     'comic_caption_consensus': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, c_int64, c_double, c_double,
                                         P, P, P, c_int64, P]),

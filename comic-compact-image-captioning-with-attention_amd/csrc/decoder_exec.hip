@@ -66,6 +66,10 @@ int comic_beam_required_launch(const int32_t* prev_words, const int32_t* prev_pa
                                int max_steps, int write_hist, hipStream_t st);
 int comic_beam_required_init_launch(const int32_t* req, float* log_probs, int32_t* finished, int64_t* lengths, int B, int W,
                                     const comic_beam_required* q, hipStream_t st);
+// beam_prefix.hip
+int comic_beam_prefix_check(const comic_beam_prefix* p, const char* who, int V, int max_steps);
+int comic_beam_prefix_launch(const int32_t* pfx, const int32_t* finished, uint32_t* bits, int t, int B, int W, int V, int P,
+                             int has_bans, hipStream_t st);
 // decode.hip
 int comic_ens_gather_state(const float* c, const float* h, const float* att, const int32_t* parent, float* c_out,
                            float* h_out, float* att_out, int R, int W, int D, int A, hipStream_t st);
@@ -2117,7 +2121,7 @@ struct EnsBufs {
   int32_t* ids;                    // [R] start ids
   void* step_ws;
   int64_t step_bytes;
-  uint32_t* bits;                  // [R][ceil(V / 32)] ban masks (constrained or truncated only)
+  uint32_t* bits;                  // [R][ceil(V / 32)] ban masks (constrained, truncated or prefixed only)
   int32_t* ban_hist;               // [2][R][max_steps] token histories in beam order (constrained only)
   void* trunc_ws;                  // comic_beam_truncate's scratch rows (truncated only; none while a row fits in LDS)
   int64_t trunc_bytes;
@@ -2131,14 +2135,17 @@ int64_t ens_step_ws_bound(int n, int rows) { return comic_beam_step_split_bytes(
 // truncated: the masks even without constraints, and the truncation's scratch rows
 // required words (req_steps > 0): the banked step's state copy, the per-step table, and the histories unless the
 // constraints keep them already
+// prefixed: the masks even without constraints or truncation (the last block, so every other decode's layout stands)
 struct EnsShape {
   int ban_steps;
   bool sampled, truncated;
   int req_steps;
+  bool prefixed;
 };
 // The ONE derivation of that shape from "which options are present": the workspace query and the run both use it.
-EnsShape ens_shape(const comic_beam_options& o, int max_steps) {
-  return EnsShape{o.constraints ? max_steps : 0, o.sampling != nullptr, o.truncation != nullptr, o.required ? max_steps : 0};
+EnsShape ens_shape(const comic_beam_options& o, int max_steps, const comic_beam_prefix* prefix) {
+  return EnsShape{o.constraints ? max_steps : 0, o.sampling != nullptr, o.truncation != nullptr, o.required ? max_steps : 0,
+                  prefix != nullptr};
 }
 EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64_t bytes, const EnsShape& shape) {
   const int ban_steps = shape.ban_steps, req_steps = shape.req_steps;
@@ -2174,21 +2181,28 @@ EnsBufs carve_ens(const comic_decoder_desc* descs, int n, int R, void* ws, int64
     e.req_special = w.take<int32_t>((size_t)R * 8);
     if (ban_steps <= 0) e.ban_hist = w.take<int32_t>((size_t)2 * R * req_steps);
   }
+  if (shape.prefixed && ban_steps <= 0 && !truncated) e.bits = w.take<uint32_t>((size_t)R * ((descs[0].V + 31) / 32));
   e.ok = e.ok && w.ok;
   e.bytes = off + w.off;
   return e;
 }
 }  // namespace
 
-extern "C" int64_t comic_decoder_beam_search_workspace(const comic_decoder_desc* descs, int n_models, int rows,
-                                                       int max_steps, const comic_beam_options* options) {
+extern "C" int64_t comic_decoder_beam_search_prefixed_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                                int max_steps, const comic_beam_options* options,
+                                                                const comic_beam_prefix* prefix) {
   const comic_beam_options o = options ? *options : comic_beam_options{};
   if (!descs || n_models < 1 || n_models > kEnsMax || rows <= 0) return -1;
   for (int m = 0; m < n_models; ++m)
     if (descs[m].D <= 0 || descs[m].V <= 0 || descs[m].M <= 0 || descs[m].H <= 0) return -1;
   if ((o.constraints || o.required) && max_steps <= 0) return -1;
   if (o.truncation && comic_beam_truncate_workspace(n_models, rows, 1, descs[0].V) < 0) return -1;
-  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0, ens_shape(o, max_steps)).bytes;
+  if (prefix && (prefix->max_tokens < 1 || prefix->max_tokens >= max_steps || descs[0].V > 65536)) return -1;
+  return (int64_t)carve_ens(descs, n_models, rows, nullptr, 0, ens_shape(o, max_steps, prefix)).bytes;
+}
+extern "C" int64_t comic_decoder_beam_search_workspace(const comic_decoder_desc* descs, int n_models, int rows,
+                                                       int max_steps, const comic_beam_options* options) {
+  return comic_decoder_beam_search_prefixed_workspace(descs, n_models, rows, max_steps, options, nullptr);
 }
 
 // The ONE ensemble loop.  cons null: comic_decoder_beam_ensemble, launch for launch as it always was; else every step
@@ -2197,13 +2211,21 @@ extern "C" int64_t comic_decoder_beam_search_workspace(const comic_decoder_desc*
 // null: no sampling; else (grp is one group at the most) every slot starts live and step t ranks under the Samples policy.
 // trc null: no truncation; else (smp is not null) every step narrows the mask by top-k / top-p (beam_truncate.hip) before
 // it ranks.  rqd null: no required words; else (no sampling, one group at the most, which is no groups) the banks.
-extern "C" int comic_decoder_beam_search(const comic_decoder_desc* descs, const comic_decoder_params* params,
-                                         const float* const* fms, const float* const* im_embeds, const float* weights,
-                                         int n_models, int B, int W, int max_steps, const comic_beam_options* options,
-                                         int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths,
-                                         int32_t* finished, float* const* attn_hists, int32_t* steps_executed,
-                                         void* workspace, int64_t workspace_bytes, void* stream) {
+// prefix null: no forced prefix; else the first P = max_tokens steps write the forcing masks (beam_prefix.hip) over the
+// constraints' and rank through L.bits whichever policy is on; from step P on the launches are those of a null prefix.
+extern "C" int comic_decoder_beam_search_prefixed(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                                  const float* const* fms, const float* const* im_embeds,
+                                                  const float* weights, int n_models, int B, int W, int max_steps,
+                                                  const comic_beam_options* options, const comic_beam_prefix* prefix,
+                                                  const int32_t* pfx, int32_t* step_ids, int32_t* parent_ids, float* scores,
+                                                  int64_t* lengths, int32_t* finished, float* const* attn_hists,
+                                                  int32_t* steps_executed, void* workspace, int64_t workspace_bytes,
+                                                  void* stream) {
   const comic_beam_options o = options ? *options : comic_beam_options{};
+  COMIC_REQUIRE(!prefix || pfx, "beam_prefixed: null prefix table");
+  COMIC_REQUIRE(!prefix || (prefix->max_tokens >= 1 && prefix->max_tokens < max_steps),
+                "beam_prefixed: max_tokens %d outside [1,%d)", prefix ? prefix->max_tokens : 0, max_steps);
+  const int P = prefix ? prefix->max_tokens : 0;
   const comic_beam_constraints* cons = o.constraints;
   const comic_beam_sampling* smp = o.sampling;
   const comic_beam_truncation* trc = o.truncation;
@@ -2236,8 +2258,9 @@ extern "C" int comic_decoder_beam_search(const comic_decoder_desc* descs, const 
   if (smp) RC(comic_beam_sampling_check(smp, trc ? "beam_truncated" : "beam_sampled", descs[0].length_penalty_weight, W));
   if (trc) RC(comic_beam_truncation_check(trc, "beam_truncated", V, true));
   if (rqd) RC(comic_beam_required_check(rqd, "beam_required", W, V, descs[0].end_id, max_steps, cons));
+  if (prefix) RC(comic_beam_prefix_check(prefix, "beam_prefixed", V, max_steps));
   hipStream_t st = (hipStream_t)stream;
-  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, ens_shape(o, max_steps));
+  EnsBufs L = carve_ens(descs, n, R, workspace, workspace_bytes, ens_shape(o, max_steps, prefix));
   COMIC_REQUIRE(L.ok && (int64_t)L.bytes <= workspace_bytes, "beam_ensemble: workspace too small");
   g_splitk_ws = L.m[0].splitk;               // members run back to back on the one stream: one split-K scratch serves all
   const float lpw = descs[0].length_penalty_weight;
@@ -2303,25 +2326,29 @@ extern "C" int comic_decoder_beam_search(const comic_decoder_desc* descs, const 
     if (cons)
       RC(comic_beam_bans_launch(t == 0 ? nullptr : (const int32_t*)ids_in, par_in, finished, lengths, L.ban_hist, L.bits, t, B,
                                 W, V, max_steps, descs[0].end_id, cons, st));
+    // (inside the prefix the forcing masks go over the constraints'; from here on `masked` is what `cons` was)
+    const bool forcing = t < P;
+    const bool masked = cons || forcing;
+    if (forcing) RC(comic_beam_prefix_launch(pfx, finished, L.bits, t, B, W, V, P, cons ? 1 : 0, st));
     if (trc)
       RC(comic_beam_truncate(L.logits, weights, n, finished, L.bits, (V + 31) / 32, B, W, V, smp->temperature, trc,
-                             cons ? 1 : 0, L.trunc_ws, L.trunc_bytes, (void*)st));
+                             masked ? 1 : 0, L.trunc_ws, L.trunc_bytes, (void*)st));
     if (rqd) {
       // (with constraints the ban launch above has advanced the ONE pair of histories; this launch only reads them)
       RC(comic_beam_required_launch(t == 0 ? nullptr : (const int32_t*)ids_in, par_in, req, L.ban_hist, L.req_base,
                                     L.req_special, rqd, t, B, W, V, max_steps, cons ? 0 : 1, st));
       RC(comic_beam_step_required(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
-                                  B, W, V, descs[0].end_id, lpw, cons ? L.bits : nullptr, (V + 31) / 32, L.req_base,
+                                  B, W, V, descs[0].end_id, lpw, masked ? L.bits : nullptr, (V + 31) / 32, L.req_base,
                                   L.req_special, rqd->n_words * rqd->stride + 1, L.step_ws, L.step_bytes, (void*)st));
     } else if (smp) {
       RC(comic_beam_step_sampled(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
-                                 B, W, V, descs[0].end_id, (cons || trc) ? L.bits : nullptr, (V + 31) / 32, smp, t, L.step_ws,
+                                 B, W, V, descs[0].end_id, (masked || trc) ? L.bits : nullptr, (V + 31) / 32, smp, t, L.step_ws,
                                  L.step_bytes, (void*)st));
     } else if (grp) {
       RC(comic_beam_step_diverse(L.logits, weights, n, L.log_probs, finished, lengths, word, parent, scores + (size_t)t * R,
-                                 B, W, V, descs[0].end_id, lpw, cons ? L.bits : nullptr, (V + 31) / 32, grp, L.step_ws,
+                                 B, W, V, descs[0].end_id, lpw, masked ? L.bits : nullptr, (V + 31) / 32, grp, L.step_ws,
                                  L.step_bytes, (void*)st));
-    } else if (cons) {
+    } else if (masked) {
       RC(comic_beam_step_constrained(L.logits, weights, n, L.log_probs, finished, lengths, word, parent,
                                      scores + (size_t)t * R, B, W, V, descs[0].end_id, lpw, L.bits, (V + 31) / 32, L.step_ws,
                                      L.step_bytes, (void*)st));
@@ -2333,6 +2360,17 @@ extern "C" int comic_decoder_beam_search(const comic_decoder_desc* descs, const 
     COMIC_LAUNCH_CHECK("all_finished");
   }
   return 0;
+}
+
+extern "C" int comic_decoder_beam_search(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                         const float* const* fms, const float* const* im_embeds, const float* weights,
+                                         int n_models, int B, int W, int max_steps, const comic_beam_options* options,
+                                         int32_t* step_ids, int32_t* parent_ids, float* scores, int64_t* lengths,
+                                         int32_t* finished, float* const* attn_hists, int32_t* steps_executed,
+                                         void* workspace, int64_t workspace_bytes, void* stream) {
+  return comic_decoder_beam_search_prefixed(descs, params, fms, im_embeds, weights, n_models, B, W, max_steps, options,
+                                            nullptr, nullptr, step_ids, parent_ids, scores, lengths, finished, attn_hists,
+                                            steps_executed, workspace, workspace_bytes, stream);
 }
 
 // ---- the named per-option entries: the frozen version-1 forms -----------------------------------------------------------------

@@ -613,6 +613,178 @@ def required_dir_suffix(c):
     return '_req%d_%s' % (required_from_config(c)['n_words'], os.path.splitext(os.path.basename(path))[0])
 
 
+class BeamPrefix(_Keyed):
+    """Forced-prefix decoding (comic_beam_prefix; extends rnn_decoder_beam_search, ops_rnn.py:49-112).  ids: int32 [B, P],
+    padded with -1 at the end of each row: the tokens (not words: a radix word is S tokens) the caption of image b must
+    start with.  The length of a row is the index of its first -1; it may be 0 and differs per image.  Hashable by P only:
+    the table lives in device memory and is written in front of every launch or replay, so one decode context and one
+    captured graph serve every table of a width."""
+    MAX_V = 65536
+
+    def __init__(self, ids):
+        self.ids = np.ascontiguousarray(np.asarray(ids, np.int32))
+        self.max_tokens = int(self.ids.shape[1]) if self.ids.ndim == 2 else 0
+
+    def key(self):
+        return (self.max_tokens,)
+
+    def __repr__(self):
+        return 'BeamPrefix(max_tokens=%d, images=%d)' % (self.max_tokens, self.ids.shape[0] if self.ids.ndim else 0)
+
+    @property
+    def active(self):
+        return True
+
+    def ctx_key(self):
+        return ('prefix',) + self.key()
+
+    @property
+    def lengths(self):
+        """[B]: the index of the first -1 of each row (P for a full row)."""
+        pad = self.ids < 0
+        return np.where(pad.any(axis=1), pad.argmax(axis=1), self.ids.shape[1]).astype(np.int64)
+
+    def check(self, spec, beam=None, batch=None, max_steps=None):
+        """The rules of the C side and of the table, on the host before any GPU call; raises ValueError naming the field."""
+        V = int(spec.V)
+        if self.ids.ndim != 2:
+            raise ValueError('prefix: ids must be [B, max_tokens], got shape %r' % (self.ids.shape,))
+        if batch is not None and self.ids.shape[0] != int(batch):
+            raise ValueError('prefix: the table holds %d images, the batch %d' % (self.ids.shape[0], int(batch)))
+        if self.max_tokens < 1 or (max_steps is not None and self.max_tokens >= int(max_steps)):
+            raise ValueError('prefix: max_tokens %d is outside [1,%s)'
+                             % (self.max_tokens, 'max_steps' if max_steps is None else int(max_steps)))
+        if V > self.MAX_V:
+            raise ValueError('prefix: V = %d exceeds %d' % (V, self.MAX_V))
+        pad = self.ids < 0
+        if (pad[:, :-1] & ~pad[:, 1:]).any():
+            raise ValueError('prefix: a -1 is followed by a token (rows are padded at the end only)')
+        if (self.ids >= V).any():
+            raise ValueError('prefix: token %d is outside the vocabulary of %d' % (int(self.ids.max()), V))
+        if (self.ids == spec.end_id).any():
+            raise ValueError('prefix: end_id %d cannot be part of a prefix' % spec.end_id)
+        if (self.ids == spec.start_id).any():
+            raise ValueError('prefix: start_id %d cannot be part of a prefix' % spec.start_id)
+
+    def c_struct(self):
+        r = L.BeamPrefix()
+        r.max_tokens = self.max_tokens
+        return r
+
+    def prefix_log_probs(self, out, length_penalty_weight=0.0, groups=None, end_id=None):
+        """[B, W] float32 from a beam_search result `out`: log p(prefix | image) of every slot's caption, the sum of its
+        forced steps' log-probabilities -- the total its ancestor held after step len - 1, read from the result's
+        `scores` through `parent_ids` with no launch.  0 for an image without a prefix.  `scores` are penalised ranks under
+        a length penalty or beam groups: the divisor ((5 + len) / 6)^lpw and the diversity penalty lambda * count of the
+        step are taken out again."""
+        sc, par, ids = (np.asarray(out[k]) for k in ('scores', 'parent_ids', 'step_ids'))
+        T, B, W = sc.shape
+        lpw = float(length_penalty_weight or 0.0)
+        n = np.minimum(self.lengths, T)                                # [B]
+        if not n.any():
+            return np.zeros((B, W), np.float32)
+        rows = np.arange(B)[:, None]
+        slot = np.tile(np.arange(W), (B, 1))                           # the ancestor of every final slot, step by step
+        for t in range(T - 1, int(n.min()) - 1, -1):
+            slot = np.where((t >= n)[:, None], par[t][rows, slot], slot)       # (executed steps: parents in [0, W))
+        last = np.maximum(n - 1, 0)[:, None]                           # the last forced step of every image
+        v = sc[last, rows, slot].astype(np.float32)
+        if groups is not None and groups.groups > 1 and groups.diversity:
+            Wg = W // groups.groups
+            tok = ids[last, rows, np.arange(W)[None, :]]               # [B, W]: the words of that step, slot by slot
+            mine = np.take_along_axis(tok, slot, axis=1)
+            before = np.arange(W)[None, None, :] < ((slot // Wg) * Wg)[:, :, None]
+            count = ((tok[:, None, :] == mine[:, :, None]) & before).sum(axis=2) * (mine != end_id)
+            v = v + np.float32(groups.diversity) * count.astype(np.float32)
+        if lpw:
+            v = v * (((5.0 + n.astype(np.float32)) / 6.0) ** np.float32(lpw))[:, None]
+        return np.where((n > 0)[:, None], v, np.float32(0.0)).astype(np.float32)
+
+
+def prefix_words(c):
+    """The --infer_prefix string of a configuration as its list of words ([] when it is not given)."""
+    text = getattr(c, 'infer_prefix', None)
+    return [] if not text else str(text).split()
+
+
+def prefix_from_config(c, filenames=None, max_steps=None):
+    """The forced prefixes a configuration asks for (infer_prefix: one string for every image; infer_prefix_file: JSON,
+    image file name or image_id -> string or list of words, found by the keys of infer_require_file), or None when it names
+    neither.  Both is a ValueError.  Words map through word_encoding (`word` and `radix` tokens; `char` tokens are refused).
+    With infer_prefix a word outside the vocabulary or a special token is a ValueError that names it; in a file an image's
+    prefix is cut before its first such word and the cut words are reported.
+    filenames None: the checks alone -> dict(stride).  Else -> dict(stride, prefix (a BeamPrefix over all the images, in
+    order; P is the longest prefix of the run), words, cut (lists of words per image)).  max_steps: P >= max_steps is a
+    ValueError."""
+    text, path = getattr(c, 'infer_prefix', None), getattr(c, 'infer_prefix_file', None)
+    if not text and not path:
+        return None
+    if text and path:
+        raise ValueError('infer_prefix and infer_prefix_file: give one of them, not both')
+    flag = 'infer_prefix' if text else 'infer_prefix_file'
+    if c.token_type == 'char':
+        raise ValueError('%s: a forced prefix needs `word` or `radix` tokens, not `char`' % flag)
+    wtoi = config_wtoi(c)
+    S = word_stride(c, wtoi)
+    enc = word_encoding(c, wtoi)
+    special = ('<GO>', '<EOS>', '<PAD>')
+    table = None
+    if text:
+        fixed = prefix_words(c)
+        for w in fixed:
+            if w in special or w not in enc:
+                raise ValueError('infer_prefix: %r is %s' % (w, 'a special token' if w in special else 'outside the vocabulary'))
+        longest = len(fixed)
+    else:
+        with open(path) as f:
+            table = json.load(f)
+        if not isinstance(table, dict) or not all(isinstance(v, (str, list)) for v in table.values()):
+            raise ValueError('infer_prefix_file: %s must hold a JSON object of image -> string or list of words' % path)
+        table = {k: (v.split() if isinstance(v, str) else [str(w) for w in v]) for k, v in table.items()}
+        longest = max([len(v) for v in table.values()] or [0])
+    out = dict(stride=S)
+    if max_steps is not None and text and longest * S >= int(max_steps):
+        raise ValueError('infer_prefix: %d tokens do not leave a step of the %d for the caption' % (longest * S, int(max_steps)))
+    if filenames is None:
+        return out
+    words, cut = [], []
+    for f in filenames:
+        asked = fixed if text else None
+        if table is not None:
+            for key in (f, os.path.basename(f), required_image_key(f)):
+                if key is not None and key in table:
+                    asked = table[key]
+                    break
+        asked = list(asked or [])
+        n = next((k for k, w in enumerate(asked) if w in special or w not in enc), len(asked))
+        words.append(asked[:n])
+        cut.append(asked[n:])
+    P = max(1, max(len(w) for w in words) * S) if words else 1
+    if max_steps is not None and P >= int(max_steps):
+        raise ValueError('%s: the longest prefix, %d tokens, does not leave a step of the %d for the caption'
+                         % (flag, P, int(max_steps)))
+    ids = np.full((len(filenames), P), -1, np.int32)
+    for k, w in enumerate(words):
+        toks = [t for x in w for t in enc[x]]
+        ids[k, :len(toks)] = toks
+    print('INFO: forced prefix: %d of %d images start from a prefix, %d tokens at the most; %d words cut (outside the '
+          'vocabulary or special)' % (sum(1 for w in words if w), len(filenames), P, sum(len(x) for x in cut)))
+    out.update(prefix=BeamPrefix(ids), words=words, cut=cut)
+    return out
+
+
+def prefix_dir_suffix(c):
+    """'_pfx_{words joined by -}' for infer_prefix, '_pfx_{stem of the file}' for infer_prefix_file, else ''."""
+    text, path = getattr(c, 'infer_prefix', None), getattr(c, 'infer_prefix_file', None)
+    if text and path:
+        raise ValueError('infer_prefix and infer_prefix_file: give one of them, not both')
+    if text:
+        return '_pfx_' + '-'.join(prefix_words(c))
+    if path:
+        return '_pfx_' + os.path.splitext(os.path.basename(path))[0]
+    return ''
+
+
 class BeamSampling(_Keyed):
     """Sampling inside the beam step (comic_beam_sampling; extends rnn_decoder_beam_search, ops_rnn.py:49-112): the `beam`
     slots of an image are `beam` independent chains, each drawn from the step distribution at `temperature` by the
@@ -989,6 +1161,14 @@ def _beam_result(dec, ctx, B, W, opts, want_attention):
             lp = (lp * (((5.0 + ln.astype(np.float32)) / 6.0) ** np.float32(lpw))).astype(np.float32)
         out['log_probs'], out['banks'] = lp, rqd.banks
         out['best_slot'], out['met'] = rqd.result(out['scores'][-1])
+    pfx = getattr(opts, 'prefix', None)
+    if pfx is not None:
+        if 'log_probs' not in out:      # the plain beam: the last scores times the length penalty's divisor
+            lp = out['scores'][-1].copy()
+            if lpw:
+                lp = (lp * (((5.0 + ln.astype(np.float32)) / 6.0) ** np.float32(lpw))).astype(np.float32)
+            out['log_probs'] = lp
+        out['prefix_log_prob'] = pfx.prefix_log_probs(out, lpw, grp, s.end_id)
     if opts.consensus is not None:
         _attach_consensus(dec, out, pred, opts.consensus, rqd is not None, ctx.scores[T - 1],
                           grp is None and not (rqd is not None and lpw))
@@ -1225,6 +1405,7 @@ class BeamOptions:
     reward: Reward | None = None
     reward_refs: RewardRefs | None = None
     reward_baseline_ids: object = field(default=None, compare=False, hash=False)     # (an array: no part of the value)
+    prefix: BeamPrefix | None = None
 
     cons = property(lambda self: _active(self.constraints))
     grp = property(lambda self: _active(self.groups))
@@ -1243,7 +1424,7 @@ class BeamOptions:
     @property
     def active(self):
         """Whether any executor option is on: the ensemble executor decodes, not Decoder's fast single-member one."""
-        return any(x is not None for x in (self.cons, self.grp, self.smp, self.required))
+        return any(x is not None for x in (self.cons, self.grp, self.smp, self.required, self.prefix))
 
     def check(self, spec, beam, batch, max_steps):
         """Every option's rules and the rules between them, on the host before anything is built or launched."""
@@ -1255,6 +1436,8 @@ class BeamOptions:
             self.reward.check(beam, max_steps, None if self.reward_baseline_ids is None else self.reward_baseline_ids.shape[0])
         elif self.reward_refs is not None or self.reward_baseline_ids is not None:
             raise ValueError('reward_refs / reward_baseline_ids apply to the reward only: give reward')
+        if self.prefix is not None:
+            self.prefix.check(spec, beam, batch, max_steps)
         if self.truncation is not None:
             self.truncation.check(self.sampling)
         if self.required is not None:
@@ -1275,6 +1458,11 @@ class BeamOptions:
                 (self.cons, BeamConstraints.key), (self.grp, BeamGroups.key), (self.smp, BeamSampling.ctx_key),
                 (self.trc, BeamTruncation.ctx_key), (self.required, BeamRequired.ctx_key)))
 
+    def context_key(self):
+        """The key of a decode context: ctx_key(), and the prefix's (its width alone) behind it when there is one --
+        prefix=None keys the contexts of a decode without one exactly as before."""
+        return self.ctx_key() if self.prefix is None else self.ctx_key() + (self.prefix.ctx_key(),)
+
     def c_record(self, ctx):
         """The comic_beam_options of a decode context.  The structs it points to are kept alive on the context (ctx.cons,
         .grp, .smp, .trc, .rqd: None where the option is off); sampling and required words name the context's device words
@@ -1287,11 +1475,12 @@ class BeamOptions:
 
 
 def options_from_config(c, load=True):
-    """The BeamOptions a configuration asks for, without the per-batch parts (the required rows, image_base).
+    """The BeamOptions a configuration asks for, without the per-batch parts (the required rows, the prefix rows, image_base).
     load=False: the refusals alone, in the order the command line has always raised them, with nothing read that a run
     reads later: no idf table, and no constraints (their words map through the vocabulary of the input manager)."""
     grp, smp, trc = groups_from_config(c), sampling_from_config(c), truncation_from_config(c)
     required_from_config(c)
+    prefix_from_config(c)
     cns = consensus_from_config(c, load_idf=load)
     return BeamOptions(getattr(c, 'infer_length_penalty_weight', 0.0) or 0.0, constraints_from_config(c) if load else None,
                        grp, smp, trc, None, cns)
@@ -1300,7 +1489,7 @@ def options_from_config(c, load=True):
 def decode_dir_suffix(c):
     """The directory suffix of a configuration's decode: every option's own, in the order they were added."""
     return (constraints_dir_suffix(c) + groups_dir_suffix(c) + sampling_dir_suffix(c) + truncation_dir_suffix(c)
-            + consensus_dir_suffix(c) + required_dir_suffix(c))
+            + consensus_dir_suffix(c) + required_dir_suffix(c) + prefix_dir_suffix(c))
 
 
 def process_inputs(captions, token_type):
@@ -1861,7 +2050,7 @@ class Decoder:
                                             L.stream_ptr()), 'decoder_beam')
 
     def beam_search_ids(self, fm, im_embed, beam, max_steps, use_graph=True, slot=0, sampling=None, image_base=0,
-                        reward=None, reward_refs=None, reward_baseline_ids=None):
+                        reward=None, reward_refs=None, reward_baseline_ids=None, prefix=None):
         """Beam search for its predicted ids alone, fetched WITHOUT draining the stream: the loop, gather_tree over all
         max_steps rows (rows past the executed steps come out as end_id) and the copies to pinned memory are enqueued, an
         event marks their end, and the returned function waits for that event only -- work enqueued behind it (the greedy
@@ -1870,14 +2059,15 @@ class Decoder:
         sampling: an active BeamSampling draws `beam` samples per image instead (beam_search's sampling= / image_base=).
         reward: a Reward with reward_refs (and reward_baseline_ids for baseline='greedy'): the reward launch follows the
         tree gather on the device ids, all max_steps rows of them; fetch.reward is the dict of its device tensors
-        (Decoder.scst_reward; None without) and fetch.ids_device the device ids [max_steps,B,W]."""
+        (Decoder.scst_reward; None without) and fetch.ids_device the device ids [max_steps,B,W].
+        prefix: a BeamPrefix: every caption starts with its image's row (beam_search's prefix=)."""
         torch, s = self.torch, self.spec
         B, W = fm.shape[0], beam
         opts = BeamOptions(sampling=sampling, image_base=image_base, reward=reward, reward_refs=reward_refs,
-                           reward_baseline_ids=reward_baseline_ids)
-        if sampling is not None or reward is not None:
+                           reward_baseline_ids=reward_baseline_ids, prefix=prefix)
+        if sampling is not None or reward is not None or prefix is not None:
             opts.check(s, W, B, max_steps)
-        if opts.smp is not None:
+        if opts.smp is not None or prefix is not None:
             ens = self.__dict__.get('_self_ensemble')
             if ens is None:
                 ens = self._self_ensemble = EnsembleDecoder([self])
@@ -1913,7 +2103,7 @@ class Decoder:
 
     def beam_search(self, fm, im_embed, beam, max_steps, want_attention=True, use_graph=True, length_penalty_weight=0.0,
                     constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None,
-                    consensus=None, options=None, reward=None, reward_refs=None, reward_baseline_ids=None):
+                    consensus=None, options=None, reward=None, reward_refs=None, reward_baseline_ids=None, prefix=None):
         """rnn_decoder_beam_search (ops_rnn.py:49-112).  Returns predicted_ids [T,B,W] (after
         gather_tree), scores [T,B,W] (with length_penalty_weight != 0: the penalised scores the beams were ranked by,
         BeamSearchDecoder's `scores` output), the raw step/parent ids and, unless want_attention=False, the
@@ -1947,11 +2137,18 @@ class Decoder:
         reward: a Reward, with reward_refs (the RewardRefs of the batch) and, for baseline='greedy', reward_baseline_ids
         [T0,B]: one comic_scst_reward launch on the device ids right after the tree gather, outside the captured graph,
         with every decode above: the result gains `reward` [B,W'] float64, `advantage` [W,B] float32 and `reward_device`,
-        the operator's device tensors (Decoder.scst_reward).  None: today's path, launch for launch."""
+        the operator's device tensors (Decoder.scst_reward).  None: today's path, launch for launch.
+        prefix: a BeamPrefix (one row of tokens per image, -1 padded); every caption of image b starts with row b, with
+        every decode above (comic_decoder_beam_search_prefixed).  `scores` / `log_probs` stay the model's
+        log p(prefix + continuation | image) -- Decoder.score of the whole caption reproduces them -- and lengths count the
+        forced tokens.  Inside the prefix the slots that do not carry it hold -inf (plain beam and groups: all but the
+        first of each group).  The result gains `log_probs` [B,W] where it has none (the plain beam's final unpenalised
+        totals) and `prefix_log_prob` [B,W], log p(prefix | image) of every slot's caption
+        (BeamPrefix.prefix_log_probs).  None: today's path, context for context."""
         opts = BeamOptions.of(options, length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
                               sampling=sampling, truncation=truncation, required=required, consensus=consensus,
                               image_base=image_base, reward=reward, reward_refs=reward_refs,
-                              reward_baseline_ids=reward_baseline_ids)
+                              reward_baseline_ids=reward_baseline_ids, prefix=prefix)
         B, W = fm.shape[0], beam
         opts.check(self.spec, W, B, max_steps)
         if opts.active:
@@ -2080,7 +2277,7 @@ class EnsembleDecoder:
         the seed words and the required table -- lives in ctx.seed and ctx.req, which _decode writes in front of every
         launch."""
         torch, n = self.torch, len(self.decoders)
-        key = (B, W, max_steps, opts.ctx_key())
+        key = (B, W, max_steps, opts.context_key())
         ctx = self._ctxs.get(key)
         if ctx is None:
             ctx = type('EnsembleCtx', (), {})()
@@ -2104,7 +2301,15 @@ class EnsembleDecoder:
                 ctx.req = torch.full((B, opts.required.n_words, opts.required.stride), -1, dtype=torch.int32,
                                      device=self.device)
             ctx.options = opts.c_record(ctx)
-            ctx.nbytes = int(self.lib.comic_decoder_beam_search_workspace(ctx.descs, n, R, max_steps, C.byref(ctx.options)))
+            ctx.prefix = ctx.pfx = None
+            if opts.prefix is None:
+                ctx.nbytes = int(self.lib.comic_decoder_beam_search_workspace(ctx.descs, n, R, max_steps,
+                                                                              C.byref(ctx.options)))
+            else:
+                ctx.prefix = opts.prefix.c_struct()
+                ctx.pfx = torch.full((B, opts.prefix.max_tokens), -1, dtype=torch.int32, device=self.device)
+                ctx.nbytes = int(self.lib.comic_decoder_beam_search_prefixed_workspace(
+                    ctx.descs, n, R, max_steps, C.byref(ctx.options), C.byref(ctx.prefix)))
             assert ctx.nbytes > 0, 'the ensemble workspace query failed'
             ctx.ws = torch.empty(ctx.nbytes, dtype=torch.uint8, device=self.device)
             ctx.graph, ctx.calls = None, 0
@@ -2116,7 +2321,7 @@ class EnsembleDecoder:
 
     def beam_search(self, fms, im_embeds, beam, max_steps, want_attention=False, use_graph=True, length_penalty_weight=0.0,
                     constraints=None, groups=None, sampling=None, image_base=0, truncation=None, required=None,
-                    consensus=None, options=None, reward=None, reward_refs=None, reward_baseline_ids=None):
+                    consensus=None, options=None, reward=None, reward_refs=None, reward_baseline_ids=None, prefix=None):
         """fms / im_embeds: one device tensor (every member reads the same features) or a sequence with one per member.
         Returns the dict of Decoder.beam_search; `attn_hist` (want_attention) is member 0's.  The options -- these keywords
         or one BeamOptions in `options` -- are Decoder.beam_search's and mean what they mean there; every decode runs
@@ -2124,7 +2329,7 @@ class EnsembleDecoder:
         opts = BeamOptions.of(options, length_penalty_weight=length_penalty_weight, constraints=constraints, groups=groups,
                               sampling=sampling, truncation=truncation, required=required, consensus=consensus,
                               image_base=image_base, reward=reward, reward_refs=reward_refs,
-                              reward_baseline_ids=reward_baseline_ids)
+                              reward_baseline_ids=reward_baseline_ids, prefix=prefix)
         torch, n = self.torch, len(self.decoders)
         if torch.is_tensor(fms):
             fms = [fms] * n
@@ -2148,15 +2353,23 @@ class EnsembleDecoder:
             ctx.req.copy_(torch.from_numpy(opts.required.ids))
         if opts.smp is not None:            # on the stream, in front of the launch or the replay that reads them
             ctx.seed.copy_(torch.from_numpy(opts.smp.seed_words(opts.image_base)))
+        if opts.prefix is not None:         # likewise: the graph bakes in the table's width, not its content
+            ctx.pfx.copy_(torch.from_numpy(opts.prefix.ids))
 
         def launch():
             flags = L.decoder_flags_from_env()
             for k in range(n):
                 ctx.descs[k].flags = flags
-            L.check(self.lib.comic_decoder_beam_search(
-                ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps, C.byref(ctx.options),
-                ctx.step_ids.data_ptr(), ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(),
-                ctx.finished.data_ptr(), ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
-                L.stream_ptr()), 'decoder_beam_search')
+            outs = (ctx.step_ids.data_ptr(), ctx.parent_ids.data_ptr(), ctx.scores.data_ptr(), ctx.lengths.data_ptr(),
+                    ctx.finished.data_ptr(), ctx.hist_ptrs, ctx.steps.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
+                    L.stream_ptr())
+            if ctx.prefix is None:
+                L.check(self.lib.comic_decoder_beam_search(
+                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps, C.byref(ctx.options),
+                    *outs), 'decoder_beam_search')
+            else:
+                L.check(self.lib.comic_decoder_beam_search_prefixed(
+                    ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps, C.byref(ctx.options),
+                    C.byref(ctx.prefix), ctx.pfx.data_ptr(), *outs), 'decoder_beam_search_prefixed')
         Decoder._run_infer(self, ctx, launch, use_graph)
         return ctx

@@ -91,6 +91,11 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
     req = cdec.required_from_config(c, filenames)
     if req is not None:
         m_infer.required_table = req['required']
+    # a forced prefix (--infer_prefix, --infer_prefix_file): likewise the table of the whole run
+    decoder0 = m_infer.models[0].decoder if ensemble else m_infer.decoder
+    pfx = cdec.prefix_from_config(c, filenames, max_steps=decoder0.max_iterations(c.infer_max_length, len(c.wtoi)))
+    if pfx is not None:
+        m_infer.prefix_table = pfx['prefix']
     num_batches = int(c.split_sizes['infer'] / batch_size)
     raw_outputs = dict(captions={}, attention={}, image_ids={}, beam_size=c.infer_beam_size,
                        max_caption_length=c.infer_max_length, checkpoint_path=curr_ckpt_path,
@@ -99,6 +104,7 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
     groups_json = []                # diverse beam search: the group-best captions of every image
     samples_json = []               # sampling: every sample of every image, with its log-probability
     required_json = []              # required words: per image the words, met, and every non-empty bank's best caption
+    prefix_json = []                # forced prefix: per image the prefix words, the cut words and the two log-probabilities
     print('INFO: Graph constructed. Starting inference.')
     start_time = time.time()
     captions = []
@@ -152,6 +158,11 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
                         dict(bank=k, caption=str(rq_caps[k][i]), score=float(rqo['scores'][i, k]),
                              log_prob=float(rqo['log_probs'][i, k]))
                         for k in range(len(rq_caps)) if np.isfinite(rqo['scores'][i, k])]))
+            pfo = getattr(m_infer, 'prefix_output', None)
+            if pfx is not None and pfo is not None:
+                n_img = step * batch_size + i
+                prefix_json.append(dict(image_id=image_id, prefix=pfx['words'][n_img], cut=pfx['cut'][n_img],
+                                        log_prob=float(pfo['log_prob'][i]), prefix_log_prob=float(pfo['prefix_log_prob'][i])))
             if smp is not None:
                 samples_json.append(dict(image_id=image_id, captions=[
                     dict(sample=k, caption=str(smp_caps[k][i]), log_prob=float(smp['log_probs'][i, k]),
@@ -172,6 +183,9 @@ def _inference_loop(inputs_man, curr_ckpt_path, ckpt_dir, ckpt_file, ckpt_num, d
     if required_json:
         with open(pjoin(c.infer_save_path, 'caption_required___{}.json'.format(ckpt_num)), 'w') as f:
             json.dump(required_json, f)
+    if prefix_json:
+        with open(pjoin(c.infer_save_path, 'caption_prefix___{}.json'.format(ckpt_num)), 'w') as f:
+            json.dump(prefix_json, f)
     if samples_json:
         with open(pjoin(c.infer_save_path, 'caption_samples___{}.json'.format(ckpt_num)), 'w') as f:
             json.dump(samples_json, f)

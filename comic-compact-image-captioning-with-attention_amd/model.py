@@ -441,12 +441,14 @@ class ModelBase(object):
         sample that agrees most with its siblings (sampling only: ValueError otherwise); with active sampling the sample
         of highest log-probability, the lowest slot on ties (self.sample_output holds every sample, sample_set, and with
         consensus their `consensus` (B, n)); else slot 0, with active groups group 0's best (self.group_output holds the
-        group-best captions, group_best).  The three outputs are None where their option is off."""
+        group-best captions, group_best).  With a prefix (options.prefix, a decoder.BeamPrefix) every caption starts with its
+        image's row and self.prefix_output holds the chosen caption's log_prob and prefix_log_prob (prefix_best).  The four
+        outputs are None where their option is off."""
         c = self._config
         opts = model_options(options if options is not None else cdec.BeamOptions(), beam_size)
         iters = self.decoder.max_iterations(max_length, len(c.wtoi))
-        self.required_output = self.group_output = self.sample_output = None
-        if beam_size > 1 or opts.smp is not None or opts.required is not None:
+        self.required_output = self.group_output = self.sample_output = self.prefix_output = None
+        if beam_size > 1 or opts.smp is not None or opts.required is not None or opts.prefix is not None:
             if not want_attention and not opts.length_penalty_weight and not opts.active:
                 # captions alone: the ids come back through pinned memory behind one event (no stream drain per array)
                 r = {'predicted_ids': self.decoder.beam_search_ids(fm, im_embed, beam_size, iters)()}
@@ -465,6 +467,8 @@ class ModelBase(object):
                     best = np.asarray(r['consensus_best'], np.int64)
             elif opts.grp is not None:
                 self.group_output = group_best(r)
+            if opts.prefix is not None:
+                self.prefix_output = prefix_best(r, best)
             attn = None
             if want_attention:
                 hist = r['attn_hist'].reshape(T, B, beam_size, self.spec.H, self.spec.M)
@@ -489,6 +493,13 @@ def group_best(r):
     Wg = W // int(r['groups'])
     return dict(ids=r['predicted_ids'][:, :, ::Wg].transpose(1, 2, 0).copy(), scores=r['scores'][-1][:, ::Wg].copy(),
                 log_probs=r['log_probs'][:, ::Wg].copy())
+
+
+def prefix_best(r, best):
+    """Of a Decoder.beam_search(prefix=) result and the chosen slots `best` (B): the chosen captions' log_prob and
+    prefix_log_prob (B), log p(caption | image) and log p(prefix | image) under the model."""
+    rows = np.arange(len(best))
+    return dict(log_prob=np.asarray(r['log_probs'])[rows, best].copy(), prefix_log_prob=r['prefix_log_prob'][rows, best].copy())
 
 
 def bank_best(r):
@@ -543,7 +554,8 @@ def decode_options(model, constraints, groups, sampling, truncation, consensus):
 def batch_options(model, opts, B):
     """opts for the next B images of the run: with image_base, the number of images sampled before them (the noise of a
     sampled decode is keyed by it), and the rows of model.required_table (a BeamRequired over every image of the run, in
-    input order: decoder.required_from_config) when that is set."""
+    input order: decoder.required_from_config) when that is set, and likewise the rows of model.prefix_table (a BeamPrefix
+    over every image of the run: decoder.prefix_from_config; every batch keeps the run's width, so one context serves)."""
     base = 0
     if opts.smp is not None:
         base = model.__dict__.get('_images_sampled', 0)
@@ -555,7 +567,14 @@ def batch_options(model, opts, B):
         if at + int(B) > table.ids.shape[0]:
             raise ValueError('required_table holds %d images, the run decodes more' % table.ids.shape[0])
         required = cdec.BeamRequired(table.ids[at:at + int(B)])
-    return dataclasses.replace(opts, image_base=base, required=required)
+    prefix, table = opts.prefix, model.__dict__.get('prefix_table')
+    if table is not None:
+        at = model.__dict__.get('_images_prefixed', 0)
+        model._images_prefixed = at + int(B)
+        if at + int(B) > table.ids.shape[0]:
+            raise ValueError('prefix_table holds %d images, the run decodes more' % table.ids.shape[0])
+        prefix = cdec.BeamPrefix(table.ids[at:at + int(B)])
+    return dataclasses.replace(opts, image_base=base, required=required, prefix=prefix)
 
 
 def sample_set(r):
@@ -739,7 +758,8 @@ class CaptionModel(ModelBase):
         c, torch = self._config, self.torch
         opts = decode_options(self, constraints, groups, sampling, truncation, consensus)
         lp = opts.length_penalty_weight
-        constrained = opts.active or self.__dict__.get('required_table') is not None     # (these keep to the one-loop path)
+        constrained = (opts.active or self.__dict__.get('required_table') is not None     # (these keep to the one-loop path)
+                       or self.__dict__.get('prefix_table') is not None)
         NL = max(1, min(5, int(os.environ.get('COMIC_INFER_IN_FLIGHT', '3'))))      # decode loops in flight (3: measured best of 1-5)
         if want_attention or lp or constrained or c.infer_beam_size <= 1 or not str(self.device).startswith('cuda'):
             NL = 1
@@ -1062,6 +1082,7 @@ class CaptionEnsemble(object):
         iters = self.models[0].decoder.max_iterations(c.infer_max_length, len(c.wtoi))
         W = c.infer_beam_size
         assert W > 1 or opts.smp is not None, 'the ensemble decodes by beam search: infer_beam_size must be at least 2'
+        self.prefix_output = None
         opts = batch_options(self, opts, feats[0][1].shape[0])
         r = self.decoder.beam_search([f[1] for f in feats], [f[0] for f in feats], W, iters, want_attention=True, options=opts)
         pred = r['predicted_ids']                                  # (T, B, W)
@@ -1075,6 +1096,8 @@ class CaptionEnsemble(object):
             best = np.asarray(r['consensus_best'], np.int64)
         if opts.required is not None:       # (required words: the best of the highest bank that holds a caption)
             best = np.asarray(r['best_slot'])
+        if opts.prefix is not None:
+            self.prefix_output = prefix_best(r, best)
         hist = r['attn_hist'].reshape(T, B, W, spec.H, spec.M)[:, np.arange(B), best]
         self.infer_output = [pred[:, np.arange(B), best].T.copy(), hist.transpose(1, 2, 0, 3)]
         return self.infer_output

@@ -1133,6 +1133,48 @@ int comic_decoder_beam_search(const comic_decoder_desc* descs, const comic_decod
                               float* scores, int64_t* lengths, int32_t* finished, float* const* attn_hists,
                               int32_t* steps_executed, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Forced-prefix decoding (extends rnn_decoder_beam_search, common/ops_rnn.py:49-112): every caption of image b starts
+ * with the tokens of row b of pfx, device int32 [B][max_tokens], padded with -1 at the end of each row (the length is the
+ * index of the first -1; it may be 0 and differs per image).  At step t row (b, w) is FORCED when t < max_tokens,
+ * 0 <= pfx[b][t] < V and the row is live: it may emit pfx[b][t] alone -- its ban mask has every bit below V set except
+ * that token's, REPLACING what the constraints put there (inside the prefix the prefix wins over min_length, n-gram
+ * blocking and suppressed words).  A row that is not forced keeps the constraints' mask, or an all-zero one; a finished
+ * row bans nothing.  The mask is applied after the log-softmax: the forced token keeps the model's own step
+ * log-probability, and log_probs / scores are the model's log p(prefix + continuation | image).  Lengths, the length
+ * penalty, min_length, the n-gram histories and the required-word bookkeeping count the forced tokens; a required word
+ * the prefix contains counts as produced.
+ * A forced live row has ONE finite candidate, so the steps' precondition "every live beam keeps W unbanned candidates"
+ * holds from step len on, not inside the prefix.  There the other slots follow the steps' all-(-inf) rule: plain beam
+ * and each group: the first slot carries the prefix, the others hold totals of -inf and lose to the carrier's candidates
+ * at the first free step; samples: every slot is a chain of its own and carries it; banks: the candidate lands in the bank
+ * its progress selects, the other slots are dead slots.  No -inf slot is an ancestor of a slot with a finite final score.
+ * The record travels beside comic_beam_options, not in it (that record is frozen). */
+typedef struct comic_beam_prefix {
+  int32_t max_tokens;                      /* P, the width of the table: 1 <= P < max_steps */
+} comic_beam_prefix;
+/* The masks of step t as a raw operator (common/ops_rnn.py:49-112; csrc/beam_prefix.hip): one launch for all B*W rows.
+ * pfx [B][P], finished [B*W], bits [B*W][ceil(V/32)] (16-byte aligned).  has_bans as for comic_beam_truncate: != 0: bits
+ * holds the constraints' mask (comic_beam_bans) and is updated in place (forced and finished rows are rewritten, the
+ * others untouched); 0: every word of every row is written.  t >= P forces nobody.  A table entry outside [0,V) is "not
+ * forced", never an index.  V <= 65 536. */
+int comic_beam_prefix_mask(const int32_t* pfx, const int32_t* finished, uint32_t* bits, int t, int B, int W, int V, int P,
+                           int has_bans, void* stream);
+/* comic_decoder_beam_search (common/ops_rnn.py:49-112) from a prefix.  options may be NULL.  prefix NULL: exactly
+ * comic_decoder_beam_search / its workspace query (which are these calls with a NULL prefix); else pfx must not be NULL,
+ * 1 <= max_tokens < max_steps and V <= 65 536, checked before anything is read.  For t < max_tokens every step writes
+ * the masks (after comic_beam_bans, before comic_beam_truncate and comic_beam_required_table) and ranks through them
+ * whichever policy is on; for t >= max_tokens the launches are those of the same decode without a prefix.  max_tokens is
+ * baked into a captured graph; the table's content is read at run time. */
+int64_t comic_decoder_beam_search_prefixed_workspace(const comic_decoder_desc* descs, int n_models, int rows, int max_steps,
+                                                     const comic_beam_options* options, const comic_beam_prefix* prefix);
+int comic_decoder_beam_search_prefixed(const comic_decoder_desc* descs, const comic_decoder_params* params,
+                                       const float* const* fms, const float* const* im_embeds, const float* weights,
+                                       int n_models, int B, int W, int max_steps, const comic_beam_options* options,
+                                       const comic_beam_prefix* prefix, const int32_t* pfx, int32_t* step_ids,
+                                       int32_t* parent_ids, float* scores, int64_t* lengths, int32_t* finished,
+                                       float* const* attn_hists, int32_t* steps_executed, void* workspace,
+                                       int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Op-level entries of the executor-only kernel forms                        */
 /* ------------------------------------------------------------------------- */

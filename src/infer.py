@@ -80,6 +80,14 @@ def create_parser():
            'non-empty bank\'s best caption.  --infer_beam_size must be a multiple of words * tokens per word + 1.')
     a('--infer_require_words', type=int, default=None,
       help='Required words per image, 1 to 4 (default: the longest list in the file, at most 4); further words are dropped.')
+    a('--infer_prefix', type=str, default=None,
+      help='Forced-prefix decoding: every caption starts with these words, e.g. "a close up of" (word and radix tokens; a '
+           'word outside the vocabulary is an error); also writes caption_prefix___N.json with the caption\'s log_prob and '
+           'prefix_log_prob; output goes to `..._pfx_<words joined by ->`.  Not together with --infer_prefix_file.')
+    a('--infer_prefix_file', type=str, default=None,
+      help='Forced-prefix decoding per image: a JSON file of image file name or image_id -> string or list of words the '
+           'caption starts with; a prefix is cut before its first word outside the vocabulary (reported in '
+           'caption_prefix___N.json); output goes to `..._pfx_<file stem>`.')
     a('--infer_ema', action='store_true', default=None,
       help='Decode the averaged weights of a run trained with --ema_decay: the `model_ema-N` checkpoints instead of '
            '`model_compact-N`; output goes to a directory of its own (`..._ema`).')
@@ -168,7 +176,8 @@ def main(argv=None):
     from comic_amd.decoder import decode_dir_suffix, options_from_config
     # refused before anything is loaded: groups that do not divide infer_beam_size; sampling with more than one group or a
     # length penalty; --infer_top_k / --infer_top_p or --infer_consensus without --infer_sample; required words or a consensus
-    # on char tokens; a beam size that the banks of the required words do not divide
+    # on char tokens; a beam size that the banks of the required words do not divide; --infer_prefix with --infer_prefix_file,
+    # on char tokens or with a word outside the vocabulary
     options_from_config(c, load=False)
     save_name += decode_dir_suffix(c)
     save_name += ema_dir_suffix(c) + average_dir_suffix(c)      # averaged weights never overwrite the plain captions either
