@@ -459,6 +459,16 @@ __global__ __launch_bounds__(kThreads) void decoder_fwd_persistent_kernel(ComicP
       // reductions of the two rows interleave); the phase is VALU-bound (about 150 wave instructions per row)
       if constexpr (BIGM) {
         if (a.method == 0) {
+          // ONE-PASS VARIANCE: var = max(Q / D - mean^2, 0) from the quarters' sum z, sum z^2 -- every other LayerNorm of
+          // the library, the backward loop's recomputation of these statistics included, takes two passes.  Its error
+          // grows with (row mean / row std)^2.  Measured on an MI355X against the float64 oracle, post-ReLU features with
+          // a rank-one offset in W_m (tests/test_gpu_path.py, ..._on_post_relu_features): attention maps 8.7e-6 off at
+          // mean / std = 32 (M = 130, H = 16) where the two-pass launch chain is 9.1e-7 off, 1.6e-6 against 1.1e-6 at
+          // mean / std = 12 (M = 196, H = 4); the step bar is 1e-3.  A float32 numpy emulation of this form
+          // (tests/test_regimes_cpu.py, D = 512) puts the probabilities 5.8e-5 off at 32, 1.4e-4 at 48 (past the 1e-4
+          // of the op tests), 4.8e-4 at 64 and 8.7e-4 at 96: it leaves the step bar near mean / std = 100.  Should that
+          // matter, accumulate about a pivot (the row's first channel) and merge the quarters as (mean, M2) pairs in
+          // quarter order (Chan): no second pass over the keys, the same result in all four workgroups.
           // (i) partial statistics of this quarter's 128 channels: thread (row tid >> 1, channel half tid & 1); the walk
           // over the 64 channels starts at a per-thread rotation so that the lanes of a wave hit distinct LDS banks
           const int pm = tid >> 1, ph = tid & 1;

@@ -212,7 +212,12 @@ __global__ __launch_bounds__(kThreads) void decoder_bwd_persistent_kernel(ComicP
         };
         // (i) -- none: the forward's scaled scores s enter the backward only through d tau = -(sum_m ds_m s_m) / tau, and
         // with alpha = softmax(s), s_m = log alpha_m + c, sum_m ds_m = 0: the sum is sum_m ds_m log alpha_m, taken from the
-        // SAVED probabilities below.  The rows' LayerNorm / tanh are computed once per step, in (iii).
+        // SAVED probabilities below.  In float32 sum_m ds_m is not zero but a rounding residue of the size of eps * |d alpha|,
+        // and the sum multiplies it by whatever constant the s_m share: log alpha_m itself carries -log M (about -5).  With
+        // near-uniform maps d tau is a small difference, and where the values carry a common offset (post-ReLU features
+        // through a tied projection) d alpha is large: the residue times log M was 1.6e-3 of d tau at M = 130 (4e-4 at
+        // M = 64 / 196) against 2e-5 of the per-step launches.  So the sum takes log(alpha_m M): the same total, centred.
+        // The rows' LayerNorm / tanh are computed once per step, in (iii).
         // d att state of step t: (finished at t+1 ? carried : 0) + d att of step t+1's operand
         if (t + 1 < Tp) {
           wait_written<2>(dv2, ds_r, dso, off2, 3u, wt);
@@ -281,7 +286,7 @@ __global__ __launch_bounds__(kThreads) void decoder_bwd_persistent_kernel(ComicP
           if (h >= H) continue;
           const float dsv = al_[hh] * (da_[hh] - dot_l[h]);      // softmax backward (the launch requires prob == 0)
           if (in) {
-            dtau -= dsv * (al_[hh] > 0.f ? logf(al_[hh]) : 0.f);
+            dtau -= dsv * (al_[hh] > 0.f ? logf(al_[hh] * (float)M) : 0.f);
             sd[h * SP + lane] = dsv * inv_scale;
             sa[h * SP + lane] = a.mask_alpha ? (al_[hh] / a.keep_alpha) * mk_[hh] : al_[hh];
           }

@@ -16,6 +16,7 @@ import functools
 
 import numpy as np
 
+from tests import regimes
 from tests.test_gpu_ensemble import F32_MIN, GAP, ref_step_lp, step_case
 
 _C0, _C1, _C2 = np.uint64(0x9E3779B97F4A7C15), np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
@@ -89,6 +90,17 @@ def sampled_inputs(shape, state):
     c = {k: c[k] for k in ('logits', 'wts', 'end_id', 'log_probs', 'finished', 'lengths')}
     if state == 'init':
         c['log_probs'], c['finished'], c['lengths'] = init_state(shape[1], shape[2])
+    c['lp'] = ref_step_lp(c['logits'], c['wts'])
+    return c
+
+
+def peaked_inputs(shape, state='mid'):
+    """sampled_inputs with the members' logits in the regime `peaked` of tests/regimes.py (rows 30 N(0,1) + 200 / - 200
+    with a dominant entry, another one in every member), lp the float64 step distribution of these; a fresh dict whose
+    logits the caller may edit (recompute lp then)"""
+    n, B, W, V = shape
+    c = dict(sampled_inputs(shape, state))
+    c['logits'] = regimes.peaked_logits(np.random.default_rng(V), n * B * W, V)[0].reshape(n, B, W, V)
     c['lp'] = ref_step_lp(c['logits'], c['wts'])
     return c
 

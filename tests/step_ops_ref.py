@@ -9,6 +9,7 @@ import numpy as np
 
 from oracle import decoder_ref as dr
 from oracle.cnn_ref import bf16_round
+from tests import regimes
 from tests.exec_ops_ref import GATES_TOL, f64
 from tests.gpu_util import elementwise_excess, rel_err
 
@@ -77,18 +78,45 @@ def gate_bias(rng, D):
     return (np.repeat([0.3, -0.5, 0.7, -0.2], D) + 0.1 * rng.standard_normal(4 * D)).astype(np.float32)
 
 
-def step_inputs(B, D, EA, seed=None):
+def saturate_step(b, c):
+    """regime 'saturated' (tests/regimes.py) of one step's operands: the gate biases uniform over +-100 (both ends
+    present), so that the pre-activations [x;h] K + b cross every branch of the sigmoid / tanh forms and the expf overflow
+    point while the product keeps its normal-regime rounding; the previous cell states scaled to reach +-50"""
+    bs = np.random.default_rng(len(b)).uniform(-regimes.PEAK, regimes.PEAK, len(b))
+    bs[0], bs[-1] = regimes.PEAK, -regimes.PEAK
+    return bs.astype(np.float32), regimes.saturate(c, regimes.CELL_PEAK)
+
+
+def step_inputs(B, D, EA, seed=None, regime=None):
+    """regime: None or 'saturated'; the draws are those of regime None"""
     Wd = EA + D
     rng = np.random.default_rng(1000 * B + D + EA if seed is None else seed)
+    inp = _step_draws(rng, B, D, Wd)
+    if regime is not None:
+        assert regime == 'saturated', regime
+        inp['b'], inp['c'] = saturate_step(inp['b'], inp['c'])
+    return inp
+
+
+def _step_draws(rng, B, D, Wd):
     return dict(K=(rng.standard_normal((Wd, 4 * D)) / np.sqrt(Wd)).astype(np.float32), b=gate_bias(rng, D),
                 xh=rng.standard_normal((B, Wd)).astype(np.float32),
                 c=rng.standard_normal((B, D)).astype(np.float32), h=(0.5 * rng.standard_normal((B, D))).astype(np.float32),
                 mask=(rng.random((B, D)) < KEEP).astype(np.float32), lens=lens_for(B))
 
 
-def grad_inputs(B, E, A, D):
+def grad_inputs(B, E, A, D, regime=None):
+    """regime 'saturated': the gate gradients of saturated cells, exact zeros but for one element in eight"""
     Wd = E + A + D
     rng = np.random.default_rng(B + 7 * E + 11 * A + 13 * D)
+    inp = _grad_draws(rng, B, E, A, D, Wd)
+    if regime is not None:
+        assert regime == 'saturated', regime
+        inp['dg'] = inp['dg'] * (np.random.default_rng(Wd).random(inp['dg'].shape) < 0.125).astype(np.float32)
+    return inp
+
+
+def _grad_draws(rng, B, E, A, D, Wd):
     return dict(K=(rng.standard_normal((Wd, 4 * D)) / np.sqrt(Wd)).astype(np.float32),
                 dg=rng.standard_normal((B, 4 * D)).astype(np.float32),
                 mask=(rng.random((B, E + A)) < KEEP).astype(np.float32),
@@ -96,9 +124,9 @@ def grad_inputs(B, E, A, D):
                 lens=lens_for(B))
 
 
-def qgrad_inputs(B, D):
+def qgrad_inputs(B, D, regime=None):
     rng = np.random.default_rng(3 * B + D)
-    st = step_inputs(B, D, 16, seed=B + D)
+    st = step_inputs(B, D, 16, seed=B + D, regime=regime)
     fw = lstm_step_ref(st['xh'], st['K'], st['b'], st['c'], None, None, 1.0, None, 0)
     return dict(Wq=(rng.standard_normal((D, D)) / np.sqrt(D)).astype(np.float32),
                 dq=rng.standard_normal((B, D)).astype(np.float32), dy=rng.standard_normal((B, D)).astype(np.float32),
@@ -107,8 +135,17 @@ def qgrad_inputs(B, D):
                 dh=(1 + rng.standard_normal((B, D))).astype(np.float32), lens=st['lens'])
 
 
-def infer_inputs(R, W, D, E, A, V=37, seed=None):
-    """one decode step's sources: non-identity parents with -1 and W + 3 (the clamp), the ids -1 and V (zero rows)"""
+def infer_inputs(R, W, D, E, A, V=37, seed=None, regime=None):
+    """one decode step's sources: non-identity parents with -1 and W + 3 (the clamp), the ids -1 and V (zero rows);
+    regime 'saturated': b and c as in step_inputs"""
+    inp = _infer_draws(R, W, D, E, A, V, seed)
+    if regime is not None:
+        assert regime == 'saturated', regime
+        inp['b'], inp['c'] = saturate_step(inp['b'], inp['c'])
+    return inp
+
+
+def _infer_draws(R, W, D, E, A, V, seed):
     rng = np.random.default_rng(R + 3 * W + 5 * D + E + A if seed is None else seed)
     Wd = E + A + D
     ids = rng.integers(0, V, R).astype(np.int32)

@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 import comic_amd._lib as L
 from oracle import decoder_ref as dr
 from tests import exec_ops_ref as R
-from tests.gpu_util import DEV, F32_RTOL, P, assert_close, dev, lib, stream, sync
+from tests import regimes as G
+from tests.gpu_util import DEV, F32_RTOL, P, assert_close, dev, elementwise_excess, lib, stream, sync
 
 NAN = float('nan')
 
@@ -28,13 +29,36 @@ def host(t):
     return t.detach().cpu().numpy()
 
 
-def chk(name, got, ref, tol):
+def chk(name, got, ref, tol, elementwise=None, restated=None):
+    """elementwise=True: the element-wise criterion of gpu_util beside the max-norm one at any bar (the peaked and
+    saturated regimes of tests/regimes.py, whose tensors span many magnitudes).  restated: the error of the float32
+    restatement of the reference on the same operands; the bar is then regimes.bar(tol, restated), printed beside it."""
+    if restated is not None:
+        name, tol = '%s [float32 restatement %.2e]' % (name, restated), G.bar(tol, restated)
     got = host(got) if isinstance(got, torch.Tensor) else np.asarray(got)
     ref = np.asarray(ref, np.float64)
     fin = np.isfinite(got).all()
     e = float(np.abs(got.astype(np.float64) - ref).max() / (np.abs(ref).max() + 1e-30)) if fin else NAN
-    print('  %-44s err %.3e  bar %.1e' % (name, e, tol))
-    return assert_close(got, ref, tol, name)
+    if elementwise:
+        print('  %-44s err %.3e  element-wise %.3e  bar %.1e' % (name, e, elementwise_excess(got, ref, 1.0) if fin else NAN, tol))
+    else:
+        print('  %-44s err %.3e  bar %.1e' % (name, e, tol))
+    return assert_close(got, ref, tol, name, elementwise=elementwise)
+
+
+# The regimes of tests/regimes.py the attention / LayerNorm kernels run in.  The attention forward and the LN_LSTM forward
+# compute the float32 restatement of their reference here, print its error and take their bar from regimes.bar().  Every
+# other case below uses its op's normal bar as a constant: that is sound only because tests/test_regimes_cpu.py holds the
+# restatement below a quarter of that bar ON THE SAME OPERANDS -- both sides must build them with the same shared builder
+# (attn_inputs, ln_lstm_regime, saturate_partials, xent_operands_peaked, step_ops_ref's *_inputs) at the same shapes and
+# seeds.  A case added or re-seeded here needs its twin there.
+ATTN_REGIMES = [('offset', 4), ('offset', 32), 'saturated']
+LN_LSTM_REGIMES = [('offset', 4), ('offset', 8), 'saturated']           # 8, not 32: see tests/test_regimes_cpu.py
+
+
+def ew(regime):
+    """peaked and saturated regimes get the element-wise check too"""
+    return True if regime in ('saturated', 'peaked') else None
 
 
 def ptr(t, col=0):
@@ -51,16 +75,22 @@ def desc(case, B=None):
 class Fwd:
     """operands of one case on the device + the float64 reference, computed once and left unchanged"""
 
-    def __init__(self, case, use_mask, mem_div=1):
+    def __init__(self, case, use_mask, mem_div=1, regime=None):
         B, M, D, H, Cv, method, prob, tied = case
-        self.case, self.keep, self.mem_div = case, 0.9, mem_div
-        inp = R.attn_inputs(case, mem_rows=B // mem_div if mem_div > 1 else None)
+        self.case, self.keep, self.mem_div, self.regime = case, 0.9, mem_div, regime
+        inp = R.attn_inputs(case, mem_rows=B // mem_div if mem_div > 1 else None, regime=regime)
         self.inp = inp
         self.mask = (inp['rng'].random((B, H, M)) < self.keep).astype(np.float32) if use_mask else None
         keys, values = inp['keys'], inp['values']
         if mem_div > 1:
             keys, values = R.mem_repeat(keys, mem_div), R.mem_repeat(values, mem_div)
         self.alpha, self.alpha_d, self.ctx, _ = R.attn_fwd_ref(case, keys, values, inp['q'], inp['p'], self.mask, self.keep)
+        self.restated = dict(alpha=None, alpha_d=None, ctx=None)
+        if regime is not None:                                  # the float32 oracle on the same operands, for the bar rule
+            with np.errstate(over='ignore'):
+                r32 = R.attn_fwd_ref(case, keys, values, inp['q'], inp['p'], self.mask, self.keep, dtype=np.float32)
+            self.restated = {k: G.rel_err(a, b) for k, a, b in zip(('alpha', 'alpha_d', 'ctx'), r32,
+                                                                   (self.alpha, self.alpha_d, self.ctx))}
         self.d_keys = dev(inp['keys'])
         self.d_values = self.d_keys if tied else dev(inp['values'])
         self.d_q = dev(inp['q'])
@@ -69,8 +99,8 @@ class Fwd:
 
 
 @functools.lru_cache(maxsize=2)
-def fwd_case(case, use_mask, mem_div=1):
-    return Fwd(case, use_mask, mem_div)
+def fwd_case(case, use_mask, mem_div=1, regime=None):
+    return Fwd(case, use_mask, mem_div, regime)
 
 
 def launch_fwd(f, scratch, q=None, q_parts=1, q_out=None, lens=None, t=0, att_prev=None, att_next=None, xh_next=None,
@@ -92,9 +122,21 @@ def launch_fwd(f, scratch, q=None, q_parts=1, q_out=None, lens=None, t=0, att_pr
 def check_fwd(f, out, tag):
     rc, alpha, alpha_d, ctx = out
     assert rc == 0, (tag, lib().comic_last_error())
-    chk(tag + ' alpha', alpha, f.alpha, R.ATTN_FWD_TOL)
-    chk(tag + ' alpha_d', alpha_d, f.alpha_d, R.ATTN_FWD_TOL)
-    chk(tag + ' ctx', ctx, f.ctx, R.ATTN_FWD_TOL)
+    chk(tag + ' alpha', alpha, f.alpha, R.ATTN_FWD_TOL, ew(f.regime), f.restated['alpha'])
+    chk(tag + ' alpha_d', alpha_d, f.alpha_d, R.ATTN_FWD_TOL, ew(f.regime), f.restated['alpha_d'])
+    chk(tag + ' ctx', ctx, f.ctx, R.ATTN_FWD_TOL, ew(f.regime), f.restated['ctx'])
+
+
+@pytest.mark.parametrize('regime', ATTN_REGIMES, ids=str)
+@pytest.mark.parametrize('case,S', R.SPLIT_CASES[:2], ids=lambda v: 'x'.join(map(str, v[:5])) if isinstance(v, tuple) else 'S%d' % v)
+def test_attn_fwd_forms_off_unit_scale(case, S, regime):
+    """the one-workgroup and the split form on LayerNorm rows with a mean of 4 and 32 standard deviations and with the
+    gains x 40 (tanh arguments to +-180: both branches of fast_tanh, __expf overflow); the two smallest add_LN entries
+    of SPLIT_CASES, softmax / tied and sigmoid / independent"""
+    assert lib().comic_attn_splits(case[0], case[1]) == S
+    f = fwd_case(case, True, 1, regime)
+    check_fwd(f, launch_fwd(f, scratch=False), '%s one-workgroup:' % (regime,))
+    check_fwd(f, launch_fwd(f, scratch=True), '%s split S=%d:' % (regime, S))
 
 
 @pytest.mark.parametrize('use_mask', [False, True])
@@ -131,13 +173,23 @@ def test_attn_fwd_channel_share_wider_than_the_workgroup():
 @pytest.mark.parametrize('scratch', [False, True])
 @pytest.mark.parametrize('case', R.EPILOGUE_CASES, ids=lambda c: 'x'.join(map(str, c[:5])))
 def test_attn_fwd_fused_epilogue(case, scratch, q_parts):
+    run_fused_epilogue(case, scratch, q_parts)
+
+
+@pytest.mark.parametrize('regime', ATTN_REGIMES, ids=str)
+def test_attn_fwd_fused_epilogue_off_unit_scale(regime):
+    run_fused_epilogue(R.EPILOGUE_CASES[0], False, 5, regime)
+
+
+def run_fused_epilogue(case, scratch, q_parts, regime=None):
     """lens / t / att_prev -> att_next, xh_next at a column offset of wider rows under mask_next / keep_in, q from its
     split-K partials (sum_q_parts: four slices at a time + remainder) and q_out.  Measured on an MI355X: q_out is
     bit-equal to the float32 sum in slice order in all twelve cases (asserted at 1e-6, as the kernel may re-associate)"""
     B, M, D, H, Cv = case[:5]
     S = lib().comic_attn_splits(B, M) if scratch else 1
     assert S == (8 if (scratch and M >= 49) else 1)
-    f = fwd_case(case, True)
+    f = fwd_case(case, True, 1, regime)
+    e = ew(regime)
     rng = np.random.default_rng(q_parts)
     parts = rng.standard_normal((q_parts, B, D)).astype(np.float32)
     parts[0] = f.inp['q'] - parts[1:].sum(0)                         # the partials add up to (about) the case's q
@@ -162,14 +214,14 @@ def test_attn_fwd_fused_epilogue(case, scratch, q_parts):
     assert rc == 0, lib().comic_last_error()
     print('  q_out bit-equal to the float32 sum in slice order: %s' % bool(np.array_equal(host(q_out), q32)))
     chk('q_out', q_out, q32, 1e-6)
-    chk('alpha', alpha, alpha_r, R.ATTN_FWD_TOL)
-    chk('alpha_d', alpha_d, alpha_d_r, R.ATTN_FWD_TOL)
-    chk('ctx', ctx, ctx_r, R.ATTN_FWD_TOL)
-    chk('att_next', att_next, att_next_r, R.ATTN_FWD_TOL)
+    chk('alpha', alpha, alpha_r, R.ATTN_FWD_TOL, e)
+    chk('alpha_d', alpha_d, alpha_d_r, R.ATTN_FWD_TOL, e)
+    chk('ctx', ctx, ctx_r, R.ATTN_FWD_TOL, e)
+    chk('att_next', att_next, att_next_r, R.ATTN_FWD_TOL, e)
     np.testing.assert_array_equal(host(att_next)[fin], att_prev[fin])            # finished rows: the previous state, exactly
     np.testing.assert_array_equal(host(att_next)[~fin], host(ctx)[~fin])
     xh_h = host(xh)
-    chk('xh_next', xh_h[:, xh_off:xh_off + Cv], xh_r, R.ATTN_FWD_TOL)
+    chk('xh_next', xh_h[:, xh_off:xh_off + Cv], xh_r, R.ATTN_FWD_TOL, e)
     assert np.isnan(xh_h[:, :xh_off]).all() and np.isnan(xh_h[:, xh_off + Cv:]).all(), 'xh_next written outside its columns'
     # the pre-summed q in one slice gives the same step
     rc, alpha1, alpha_d1, ctx1 = launch_fwd(f, scratch, q=dev(q32))
@@ -197,6 +249,15 @@ def test_attn_fwd_shared_memories(mc):
     check_fwd(f, launch_fwd(f, scratch), 'mem_div=%d:' % W)
 
 
+@pytest.mark.parametrize('regime', ATTN_REGIMES, ids=str)
+def test_attn_fwd_shared_memories_off_unit_scale(regime):
+    """mem_div = 3 on the add_LN entry of MEM_DIV_CASES"""
+    entries, W, M, D, H, Cv, method, tied, scratch = MEM_DIV_CASES[5]
+    assert (W, method) == (3, 'add_LN')
+    f = fwd_case((entries * W, M, D, H, Cv, method, 'softmax', tied), True, W, regime)
+    check_fwd(f, launch_fwd(f, scratch), '%s mem_div=%d:' % (regime, W))
+
+
 def test_attn_fwd_shared_memories_refuse_a_ragged_batch():
     case = (9, 9, 64, 2, 64, 'dot', 'softmax', True)
     f = fwd_case(case, False, 3)
@@ -206,9 +267,9 @@ def test_attn_fwd_shared_memories_refuse_a_ragged_batch():
 
 # ============================================================================ attention, backward ====================
 class Bwd:
-    def __init__(self, case, with_dmap=True, with_lens=True):
+    def __init__(self, case, with_dmap=True, with_lens=True, regime=None):
         B, M, D, H, Cv, method, prob, tied = case
-        f = self.f = fwd_case(case, True)
+        f = self.f = fwd_case(case, True, 1, regime)
         rng = np.random.default_rng(B + M + D)
         self.dctx = rng.standard_normal((B, Cv)).astype(np.float32)
         self.dmap = (0.01 * rng.standard_normal((B, M))).astype(np.float32) if with_dmap else None
@@ -227,8 +288,8 @@ class Bwd:
 
 
 @functools.lru_cache(maxsize=2)
-def bwd_case(case, with_dmap=True, with_lens=True):
-    return Bwd(case, with_dmap, with_lens)
+def bwd_case(case, with_dmap=True, with_lens=True, regime=None):
+    return Bwd(case, with_dmap, with_lens, regime)
 
 
 BWD_MODES = {'add': (0, False), 'overwrite': (1, False), 'split2': (2, False), 'split_scratch': (2, True)}
@@ -301,6 +362,20 @@ def test_attn_bwd_forms(case, S, mode):
             assert x is None or torch.equal(x, y), '%s %s: two launches differ' % (mode, name)
 
 
+@pytest.mark.parametrize('regime', ATTN_REGIMES, ids=str)
+@pytest.mark.parametrize('mode', ['add', 'overwrite', 'split2'])
+def test_attn_bwd_forms_off_unit_scale(mode, regime):
+    """pgrad_overwrite 0, 1, 2 on the smallest add_LN softmax case of test_attn_bwd_forms (the split form refuses
+    sigmoid).  The backward re-derives mean and 1 / std of keys + q in two passes; at gains x 40 most of 1 - tanh^2 is an
+    exact zero, so the gradients are held element-wise as well"""
+    case, S = R.BWD_CASES[-1]
+    assert lib().comic_attn_splits(case[0], case[1]) == S == 1
+    b = bwd_case(case, True, True, regime)
+    out = launch_bwd(b, mode)
+    check_bwd(b, mode, out)
+    assert all(x is None or bool(torch.isfinite(x).all()) for x in out[1:])
+
+
 @pytest.mark.parametrize('mode', ['overwrite', 'split_scratch'])
 @pytest.mark.parametrize('case', [R.BWD_CASES[0][0], R.BWD_CASES[-1][0]], ids=lambda c: 'x'.join(map(str, c[:5])))
 def test_attn_bwd_without_map_loss_and_lens(case, mode):
@@ -316,7 +391,10 @@ XENT_GEOM = [  # t_rows, t_stride, B, H, M  ->  n = t_rows*B*M map elements
     (7, 9, 48, 8, 196)]         # 65856: 258 pieces, more than one pass of the final 256-thread sum
 
 
-def xent_operands(V, t_rows, t_stride, B, rng):
+def xent_operands(V, t_rows, t_stride, B, rng, regime=None):
+    if regime is not None:
+        assert regime == 'peaked', regime
+        return R.xent_operands_peaked(V, t_rows, t_stride, B, rng)
     logits = (3 * rng.standard_normal((t_rows, B, V))).astype(np.float32)
     lens = rng.integers(1, t_stride + 1, B).astype(np.int32)
     lens[:3] = (t_rows, 3, t_stride)
@@ -326,13 +404,14 @@ def xent_operands(V, t_rows, t_stride, B, rng):
     return logits, lens, targets, wmask, coef
 
 
-def check_xent(V, t_rows, B, ops, d_logits, loss_rows, dlog, ids, ld_dl):
+def check_xent(V, t_rows, B, ops, d_logits, loss_rows, dlog, ids, ld_dl, regime=None):
     logits, lens, targets, wmask, coef = ops
     lg, xent, dl_ref, amax = R.xent_ref(logits, targets, coef, wmask, lens)
     np.testing.assert_array_equal(host(d_logits), lg)                           # finished rows zeroed in place
-    chk('xent rows', host(loss_rows).reshape(t_rows, B), xent, R.XENT_TOL)
+    # element-wise too: a max-norm relative to the largest loss row (230 in the peaked regime) hides the small rows
+    chk('xent rows', host(loss_rows).reshape(t_rows, B), xent, R.XENT_TOL, True)
     dl = host(dlog).reshape(t_rows, B, ld_dl)
-    chk('dlogits', dl[..., :V], dl_ref, R.XENT_TOL)
+    chk('dlogits', dl[..., :V], dl_ref, R.XENT_TOL, ew(regime))
     assert (dl[..., V:] == 0).all(), 'padding columns of d logits are not exactly zero'
     np.testing.assert_array_equal(host(ids).reshape(t_rows, B), amax)
 
@@ -341,11 +420,21 @@ def check_xent(V, t_rows, B, ops, d_logits, loss_rows, dlog, ids, ld_dl):
 @pytest.mark.parametrize('geom', XENT_GEOM, ids=lambda g: 'n%d' % (g[0] * g[2] * g[4]))
 @pytest.mark.parametrize('V', [258, 1000])
 def test_xent_maploss(V, geom, with_dmap):
+    run_xent_maploss(V, geom, with_dmap)
+
+
+def test_xent_maploss_peaked_logits():
+    """logit rows 30 N(0,1) +- 200 with a dominant entry: an all-equal row, a target that is the arg-max (loss below
+    float32 epsilon) and a target whose probability underflows (loss 150, finite)"""
+    run_xent_maploss(258, XENT_GEOM[0], True, 'peaked')
+
+
+def run_xent_maploss(V, geom, with_dmap, regime=None):
     """xent_maploss_kernel: the sequence loss with ld_dl > V and the attention-map loss in one launch; the last-arriver
     ticket is zero again afterwards, so a second launch needs no re-zeroing and gives the same bits"""
     t_rows, t_stride, B, H, M = geom
     rng = np.random.default_rng(V + M)
-    ops = xent_operands(V, t_rows, t_stride, B, rng)
+    ops = xent_operands(V, t_rows, t_stride, B, rng, regime)
     logits, lens, targets, wmask, coef = ops
     hist = (rng.random((t_rows, B, H, M)) * (2.0 / H)).astype(np.float32)
     scale, ld_dl = 0.7, V + 6
@@ -368,7 +457,7 @@ def test_xent_maploss(V, geom, with_dmap):
         assert int(ticket.item()) == 0, 'the ticket is not zero after the launch'
         runs.append((loss_rows, dlog, ids, dmap, map_loss))
     loss_rows, dlog, ids, dmap, map_loss = runs[0]
-    check_xent(V, t_rows, B, ops, d_logits, loss_rows, dlog, ids, ld_dl)
+    check_xent(V, t_rows, B, ops, d_logits, loss_rows, dlog, ids, ld_dl, regime)
     chk('map_loss', map_loss, [loss_ref], R.XENT_TOL)
     if with_dmap:
         chk('dmap', dmap, dmap_ref, R.XENT_TOL)
@@ -378,9 +467,17 @@ def test_xent_maploss(V, geom, with_dmap):
 
 @pytest.mark.parametrize('V', [258, 1000])
 def test_xent_fewer_rows_than_the_table_stride(V):
+    run_xent_fewer_rows(V)
+
+
+def test_xent_peaked_logits():
+    run_xent_fewer_rows(258, 'peaked')
+
+
+def run_xent_fewer_rows(V, regime=None):
     """comic_xent_ex with t_rows < t_stride: the [B, t_stride] tables are indexed b*t_stride + t"""
     t_rows, t_stride, B = 5, 7, 3
-    ops = xent_operands(V, t_rows, t_stride, B, np.random.default_rng(V))
+    ops = xent_operands(V, t_rows, t_stride, B, np.random.default_rng(V), regime)
     logits, lens, targets, wmask, coef = ops
     d_logits = dev(logits)
     loss_rows, dlog = nan(t_rows * B), nan(t_rows * B, V)
@@ -388,7 +485,7 @@ def test_xent_fewer_rows_than_the_table_stride(V):
     L.check(lib().comic_op_xent(ptr(d_logits), P(targets), P(coef), P(wmask), P(lens),
                                 ptr(loss_rows), ptr(dlog), ptr(ids), t_rows, t_stride, B, V, stream()), 'xent')
     sync()
-    check_xent(V, t_rows, B, ops, d_logits, loss_rows, dlog, ids, V)
+    check_xent(V, t_rows, B, ops, d_logits, loss_rows, dlog, ids, V, regime)
 
 
 # ============================================================================ LN_LSTM ===============================
@@ -402,6 +499,18 @@ def partials(rng, S, *shape):
 @pytest.mark.parametrize('S', [1, 3])
 @pytest.mark.parametrize('D', R.LN_LSTM_D)
 def test_ln_lstm_fwd_bwd(D, S):
+    run_ln_lstm(D, S)
+
+
+@pytest.mark.parametrize('regime', LN_LSTM_REGIMES, ids=str)
+@pytest.mark.parametrize('D', [128, 512])
+def test_ln_lstm_off_unit_scale(D, regime):
+    """the four gate rows and the cell row with a mean of 4 and 8 standard deviations (R.ln_lstm_regime), and the five
+    gains x 40 with cell states to +-50: pre-activations beyond +-100, tanh(c) = +-1"""
+    run_ln_lstm(D, 3, regime)
+
+
+def run_ln_lstm(D, S, regime=None):
     """PER = 1, 2, 4, 8 units per thread with the last 256-chunk full and partial (d < D guards), S split-K partials,
     finished rows, output dropout, h into the next operand row at an offset, and NULL previous states"""
     B, t, lens = CELL_B, CELL_T, CELL_LENS
@@ -416,12 +525,24 @@ def test_ln_lstm_fwd_bwd(D, S):
     fin = t >= lens
     live = (~fin)[:, None].astype(np.float64)
     xh_ld, xh_off = D + 24, 8
-    d_g, d_ln, d_mask, d_lens = dev(g), dev(ln_dev), dev(mask), dev(lens)
+    d_mask, d_lens = dev(mask), dev(lens)
+    g0, ln0, e = g, ln, ew(regime)
     for null_state in (False, True):
-        tag = 'D=%d S=%d%s ' % (D, S, ' null state' if null_state else '')
+        tag = 'D=%d S=%d%s%s ' % (D, S, ' null state' if null_state else '', '' if regime is None else ' %s' % (regime,))
         c = None if null_state else rng.standard_normal((B, D)).astype(np.float32)
         h = None if null_state else rng.standard_normal((B, D)).astype(np.float32)
+        if regime is not None:
+            g, c, ln = R.ln_lstm_regime(g0, c, ln0, regime)
+            ln_dev[:, :D] = ln
+        d_g, d_ln = dev(g), dev(ln_dev)
         fw = R.ln_lstm_fwd_ref(R.f64(g).sum(0), ln, c)
+        rs = dict.fromkeys(fw)
+        if regime is not None:                                  # the float32 restatement (partials added in the kernel's order)
+            g32 = g[0]
+            for k in range(1, S):
+                g32 = g32 + g[k]
+            with np.errstate(over='ignore'):
+                rs = {k: G.rel_err(v, fw[k]) for k, v in R.ln_lstm_fwd_ref(g32, ln, c, dtype=np.float32).items()}
         d_c, d_h = (None, None) if null_state else (dev(c), dev(h))
         ga, xhat, rstd, c_new, y = nan(B, 4 * D), nan(B, 5 * D), nan(B, 8), nan(B, D), nan(B, D)
         cs, hs, xh = nan(B, D), nan(B, D), nan(B, xh_ld)
@@ -430,15 +551,15 @@ def test_ln_lstm_fwd_bwd(D, S):
                                            ptr(xh, xh_off), xh_ld, stream()), 'ln_lstm_fwd')
         sync()
         hs_ref = R.state_select(fin, R.f64(h), fw['h_new'])
-        chk(tag + 'gates_act', ga, fw['gates_act'], R.GATES_TOL)
-        chk(tag + 'xhat', xhat, fw['xhat'], R.GATES_TOL)
-        chk(tag + 'rstd', host(rstd)[:, :5], fw['rstd'], R.GATES_TOL)
-        chk(tag + 'c_new', c_new, fw['c_new'], R.GATES_TOL)
-        chk(tag + 'y', y, dr.dropout(fw['h_new'], R.f64(mask), KEEP_OUT), R.GATES_TOL)
-        chk(tag + 'c_state', cs, R.state_select(fin, R.f64(c), fw['c_new']), R.GATES_TOL)
-        chk(tag + 'h_state', hs, hs_ref, R.GATES_TOL)
+        chk(tag + 'gates_act', ga, fw['gates_act'], R.GATES_TOL, e, rs['gates_act'])
+        chk(tag + 'xhat', xhat, fw['xhat'], R.GATES_TOL, e, rs['xhat'])
+        chk(tag + 'rstd', host(rstd)[:, :5], fw['rstd'], R.GATES_TOL, e, rs['rstd'])
+        chk(tag + 'c_new', c_new, fw['c_new'], R.GATES_TOL, e, rs['c_new'])
+        chk(tag + 'y', y, dr.dropout(fw['h_new'], R.f64(mask), KEEP_OUT), R.GATES_TOL, e, rs['h_new'])
+        chk(tag + 'c_state', cs, R.state_select(fin, R.f64(c), fw['c_new']), R.GATES_TOL, e, rs['c_new'])
+        chk(tag + 'h_state', hs, hs_ref, R.GATES_TOL, e, rs['h_new'])
         xh_h = host(xh)
-        chk(tag + 'xh_next', xh_h[:, xh_off:xh_off + D], hs_ref, R.GATES_TOL)
+        chk(tag + 'xh_next', xh_h[:, xh_off:xh_off + D], hs_ref, R.GATES_TOL, e, rs['h_new'])
         assert np.isnan(xh_h[:, :xh_off]).all() and np.isnan(xh_h[:, xh_off + D:]).all()
         # ---- backward on the float32 roundings of the reference's saved tensors ----
         f32 = {k: v.astype(np.float32) for k, v in fw.items()}
@@ -494,6 +615,16 @@ def test_ln_lstm_scatter(D):
 @pytest.mark.parametrize('EA', [64 + 192, 100])
 @pytest.mark.parametrize('D', R.GRU_D)
 def test_gru_kernels(D, EA, S):
+    run_gru(D, EA, S)
+
+
+def test_gru_kernels_saturated():
+    """the smallest test_gru_kernels case with both products scaled to reach +-100: expf(-x) is inf, r (1 - r) and
+    1 - cand^2 are exact zeros almost everywhere; forward and gradients held element-wise"""
+    run_gru(R.GRU_D[0], 64 + 192, 1, 'saturated')
+
+
+def run_gru(D, EA, S, regime=None):
     """gru_gates_fwd / gru_out_fwd / gru_bwd1 / gru_bwd2 on their own operands, padded leading dimensions, finished
     rows and a NULL previous state"""
     B, t, lens = CELL_B, CELL_T, CELL_LENS
@@ -504,6 +635,10 @@ def test_gru_kernels(D, EA, S):
     g1, g2 = partials(rng, S, B, 2 * D), partials(rng, S, B, D)
     b_g = (1 + 0.1 * rng.standard_normal(2 * D)).astype(np.float32)
     b_c = (0.1 * rng.standard_normal(D)).astype(np.float32)
+    e = ew(regime)
+    if regime is not None:
+        assert regime == 'saturated', regime
+        g1, g2 = G.saturate_partials(g1, b_g), G.saturate_partials(g2, b_c)
     xh_ld, ld_ru, xh2_ld, ld_cand, ld_dpre, xn_ld, xn_off = Wd + 8, 2 * D + 4, Wd + 16, D + 12, 3 * D + 4, Wd + 8, EA
     xh_in = rng.standard_normal((B, xh_ld)).astype(np.float32)
     mask = (rng.random((B, D)) < KEEP_OUT).astype(np.float32)
@@ -519,10 +654,10 @@ def test_gru_kernels(D, EA, S):
                                              ptr(xh2), xh2_ld, B, D, EA, stream()), 'gru_gates_fwd')
         sync()
         ru_h, xh2_h = host(ru), host(xh2)
-        chk(tag + 'ru', ru_h[:, :2 * D], np.concatenate([r, u], 1), R.GATES_TOL)
+        chk(tag + 'ru', ru_h[:, :2 * D], np.concatenate([r, u], 1), R.GATES_TOL, e)
         assert np.isnan(ru_h[:, 2 * D:]).all() and np.isnan(xh2_h[:, Wd:]).all()
         np.testing.assert_array_equal(xh2_h[:, :EA], xh_in[:, :EA])                 # the x / att columns: a copy
-        chk(tag + 'xh2 r*h', xh2_h[:, EA:Wd], r * h64, R.GATES_TOL)
+        chk(tag + 'xh2 r*h', xh2_h[:, EA:Wd], r * h64, R.GATES_TOL, e)
         # candidate + new state, on the float32 rounding of the reference gates
         ru32 = np.full((B, ld_ru), NAN, np.float32)
         ru32[:, :D], ru32[:, D:2 * D] = r, u
@@ -535,11 +670,11 @@ def test_gru_kernels(D, EA, S):
                                            ptr(d_mask), KEEP_OUT, ptr(d_lens), t, ptr(hs), ptr(xn, xn_off), xn_ld, B, D,
                                            stream()), 'gru_out_fwd')
         sync()
-        chk(tag + 'cand', host(cand_o)[:, :D], cand, R.GATES_TOL)
+        chk(tag + 'cand', host(cand_o)[:, :D], cand, R.GATES_TOL, e)
         assert np.isnan(host(cand_o)[:, D:]).all()
-        chk(tag + 'y', y, dr.dropout(h_new, R.f64(mask), KEEP_OUT), R.GATES_TOL)
-        chk(tag + 'h_state', hs, hs_ref, R.GATES_TOL)
-        chk(tag + 'xh_next', host(xn)[:, xn_off:xn_off + D], hs_ref, R.GATES_TOL)
+        chk(tag + 'y', y, dr.dropout(h_new, R.f64(mask), KEEP_OUT), R.GATES_TOL, e)
+        chk(tag + 'h_state', hs, hs_ref, R.GATES_TOL, e)
+        chk(tag + 'xh_next', host(xn)[:, xn_off:xn_off + D], hs_ref, R.GATES_TOL, e)
         assert np.isnan(host(xn)[:, :xn_off]).all() and np.isnan(host(xn)[:, xn_off + D:]).all()
         # ---- backward ----
         cand32 = np.full((B, ld_cand), NAN, np.float32)
@@ -574,6 +709,15 @@ def test_gru_kernels(D, EA, S):
 # ============================================================================ LSTM gates, executor form =============
 @pytest.mark.parametrize('D', [128, 100])
 def test_lstm_gates_split_k_partials_and_bias(D):
+    run_lstm_gates_split_k(D)
+
+
+def test_lstm_gates_saturated():
+    """comic_lstm_gates_fwd / _bwd and the executor forms with pre-activations to +-100 and cell states to +-50"""
+    run_lstm_gates_split_k(128, 'saturated')
+
+
+def run_lstm_gates_split_k(D, regime=None):
     """S = 3 partials + bias / dy_part / xh_next: the public op on the pre-summed, biased product gives the same step"""
     B, S, t, lens = 6, 3, 2, np.array([3, 1, 5, 2, 9, 2], np.int32)
     rng = np.random.default_rng(D)
@@ -583,6 +727,10 @@ def test_lstm_gates_split_k_partials_and_bias(D):
     h = rng.standard_normal((B, D)).astype(np.float32)
     mask = (rng.random((B, D)) < KEEP_OUT).astype(np.float32)
     fin = t >= lens
+    e = ew(regime)
+    if regime is not None:
+        assert regime == 'saturated', regime
+        g, c = G.saturate_partials(g, bias), G.saturate(c, G.CELL_PEAK)
     g32 = ((g[0] + g[1]) + g[2]) + bias                       # float32, the kernel's order
     xh_ld, xh_off = D + 24, 8
     d_c, d_h, d_mask, d_lens = dev(c), dev(h), dev(mask), dev(lens)
@@ -604,14 +752,14 @@ def test_lstm_gates_split_k_partials_and_bias(D):
     si, tj, sf, so = dr.sigmoid(i), np.tanh(j), dr.sigmoid(f_ + 1), dr.sigmoid(o)
     c2 = c * sf + si * tj
     h2 = np.tanh(c2) * so
-    chk('fwd gates', ex['ga'], np.concatenate([si, tj, sf, so], 1), R.GATES_TOL)
-    chk('fwd c_new', ex['c_new'], c2, R.GATES_TOL)
-    chk('fwd y', ex['y'], dr.dropout(h2, R.f64(mask), KEEP_OUT), R.GATES_TOL)
-    chk('fwd c_state', ex['cs'], np.where(fin[:, None], c, c2), R.GATES_TOL)
+    chk('fwd gates', ex['ga'], np.concatenate([si, tj, sf, so], 1), R.GATES_TOL, e)
+    chk('fwd c_new', ex['c_new'], c2, R.GATES_TOL, e)
+    chk('fwd y', ex['y'], dr.dropout(h2, R.f64(mask), KEEP_OUT), R.GATES_TOL, e)
+    chk('fwd c_state', ex['cs'], np.where(fin[:, None], c, c2), R.GATES_TOL, e)
     hs_ref = np.where(fin[:, None], h, h2)
-    chk('fwd h_state', ex['hs'], hs_ref, R.GATES_TOL)
+    chk('fwd h_state', ex['hs'], hs_ref, R.GATES_TOL, e)
     xh_h = host(xh)
-    chk('fwd xh_next', xh_h[:, xh_off:xh_off + D], hs_ref, R.GATES_TOL)
+    chk('fwd xh_next', xh_h[:, xh_off:xh_off + D], hs_ref, R.GATES_TOL, e)
     assert np.isnan(xh_h[:, :xh_off]).all() and np.isnan(xh_h[:, xh_off + D:]).all()
     # ---- backward: dy + S partials ----
     dy = rng.standard_normal((B, D)).astype(np.float32)

@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 
 import comic_amd._lib as L
 from oracle import beam_ref, cnn_ref, decoder_ref as dr
-from tests.gpu_util import DEV, F32_RTOL, P, assert_close, dev, lib, rel_err, stream, sync
+from tests import exec_ops_ref, regimes
+from tests.gpu_util import DEV, F32_RTOL, P, assert_close, dev, elementwise_excess, lib, rel_err, stream, sync
 
 
 # ------------------------------------------------------------------------ GEMM -----------
@@ -1012,6 +1013,18 @@ ATTN_CASES = [
 @pytest.mark.parametrize('case', ATTN_CASES)
 @pytest.mark.parametrize('use_mask', [False, True])
 def test_attn_step_fwd_bwd(case, use_mask):
+    _attn_step_fwd_bwd(case, use_mask)
+
+
+@pytest.mark.parametrize('regime', [('offset', 4), ('offset', 32), 'saturated'], ids=str)
+def test_attn_step_fwd_bwd_off_unit_scale(regime):
+    """The first add_LN case on operands off zero mean and unit scale (tests/regimes.py), against the oracle in float64:
+    LayerNorm rows keys + q with a mean of 4 and 32 standard deviations, and gains x 40 (tanh arguments to +-180).
+    tests/test_regimes_cpu.py holds the float32 oracle below a quarter of these bars on the same operands."""
+    _attn_step_fwd_bwd(ATTN_CASES[0], True, regime)
+
+
+def _attn_step_fwd_bwd(case, use_mask, regime=None):
     B, M, D, H, Cv, method, prob, tied = case
     rng = np.random.default_rng(B * M + D)
     cfg = dr.DecoderConfig(rnn_size=D, attn_num_heads=H, attn_alignment_method=method, attn_probability_fn=prob,
@@ -1024,9 +1037,20 @@ def test_attn_step_fwd_bwd(case, use_mask):
              v=(rng.standard_normal(D) / math.sqrt(D / H) * 3).astype(np.float32), tau=np.array(2.5, np.float32))
     keep = 0.9
     mask = (rng.random((B, H, M)) < keep).astype(np.float32) if use_mask else None
+    if regime == 'saturated':
+        p['ln_g'] = p['ln_g'] * np.float32(regimes.LN_GAIN_SCALE)
+    elif regime is not None:
+        keys = regimes.offset(keys, regime[1] * math.sqrt(2.0))     # keys + q has standard deviation sqrt(2)
+        values = keys if tied else values
+    dev_ops = keys, values, q, p, mask                              # what the device gets: float32
+    if regime is not None:                                          # the reference in float64 on the same operands
+        keys, values, q, mask = (None if x is None else x.astype(np.float64) for x in (keys, values, q, mask))
+        p = {k: v.astype(np.float64) for k, v in p.items()}
     alpha_ref, ac = dr.attention_scores(p, cfg, keys, q)
     alpha_d_ref = dr.dropout(alpha_ref, mask, keep)
     ctx_ref = dr.context(cfg, alpha_d_ref, values)
+    ref_ops = keys, values, q, p, mask
+    keys, values, q, p, mask = dev_ops
     d = L.AttnDesc(B=B, M=M, D=D, H=H, Cv=Cv, method=0 if method == 'add_LN' else 1,
                    prob=0 if prob == 'softmax' else 1, tied=int(tied))
     dk = dev(keys)
@@ -1041,16 +1065,22 @@ def test_attn_step_fwd_bwd(case, use_mask):
                                       dp['tau'].data_ptr(), L.ptr(dmask), keep, alpha.data_ptr(), alpha_d.data_ptr(),
                                       ctx.data_ptr(), stream()), 'attn_fwd')
     sync()
-    assert_close(alpha.cpu().numpy(), alpha_ref, 1e-4, 'alpha')
-    assert_close(alpha_d.cpu().numpy(), alpha_d_ref, 1e-4, 'alpha_d')
-    assert_close(ctx.cpu().numpy(), ctx_ref, 1e-4, 'ctx')
+    ew = True if regime == 'saturated' else None                     # element-wise as well where tanh saturates
+    for name, got, ref in (('alpha', alpha, alpha_ref), ('alpha_d', alpha_d, alpha_d_ref), ('ctx', ctx, ctx_ref)):
+        if regime is not None:
+            print('  %s %-8s err %.3e  bar 1.0e-04' % (regime, name, rel_err(got.cpu().numpy(), ref)))
+        assert_close(got.cpu().numpy(), ref, 1e-4, name, elementwise=ew)
     # ---- backward vs the oracle's analytic backward ----
     dctx = rng.standard_normal((B, Cv)).astype(np.float32)
     dmap = (0.01 * rng.standard_normal((B, M))).astype(np.float32)
+    dctx_dev, dmap_dev = dctx, dmap
+    keys, values, q, p, mask = ref_ops
+    if regime is not None:
+        dctx, dmap = dctx.astype(np.float64), dmap.astype(np.float64)
     vs = values.reshape(B, M, H, Cv // H)
     dalpha_d = np.einsum('bhd,bmhd->bhm', dctx.reshape(B, H, Cv // H), vs) + dmap[:, None, :]
     dvalues_ref = np.einsum('bhm,bhd->bmhd', alpha_d_ref, dctx.reshape(B, H, Cv // H)).reshape(B, M, Cv)
-    dalpha = dalpha_d / np.float32(keep) * mask if use_mask else dalpha_d
+    dalpha = dalpha_d / alpha_ref.dtype.type(keep) * mask if use_mask else dalpha_d
     grads = {k: np.zeros_like(v) for k, v in p.items()}
     dk_ref, dq_ref = dr._attention_backward(p, cfg, keys, q, ac, alpha_ref, dalpha, grads)
     dq = torch.empty((B, D), device=DEV)
@@ -1060,7 +1090,7 @@ def test_attn_step_fwd_bwd(case, use_mask):
     L.check(lib().comic_attn_step_bwd(C.byref(d), dk.data_ptr(), dvv.data_ptr(), dq_in.data_ptr(),
                                       dp['ln_g'].data_ptr(), dp['ln_b'].data_ptr(), dp['v'].data_ptr(),
                                       dp['tau'].data_ptr(), alpha.data_ptr(), L.ptr(dmask), keep,
-                                      P(dctx), P(dmap), dq.data_ptr(), dkeys.data_ptr(),
+                                      P(dctx_dev), P(dmap_dev), dq.data_ptr(), dkeys.data_ptr(),
                                       dvalues.data_ptr(), pgrad.data_ptr(), stream()), 'attn_bwd')
     sync()
     assert_close(dq.cpu().numpy(), dq_ref, F32_RTOL, 'dq')
@@ -1079,6 +1109,18 @@ def test_attn_step_fwd_bwd(case, use_mask):
 
 @pytest.mark.parametrize('V', [258, 25599])
 def test_xent_fwd_bwd(V):
+    _xent_fwd_bwd(V)
+
+
+@pytest.mark.parametrize('V', [258, 25599])
+def test_xent_fwd_bwd_peaked_logits(V):
+    """Logit rows 30 N(0,1) + 200 / - 200 with one dominant entry (tests/regimes.py): expf overflows without the max
+    subtraction; an all-equal row (uniform softmax, arg-max 0), a row whose target is its arg-max (loss below float32
+    epsilon) and a row whose target lies 150 below the maximum (its probability underflows; the loss is 150)."""
+    _xent_fwd_bwd(V, 'peaked')
+
+
+def _xent_fwd_bwd(V, regime=None):
     rng = np.random.default_rng(V)
     T, B = 7, 5
     logits = (3 * rng.standard_normal((T, B, V))).astype(np.float32)
@@ -1086,6 +1128,8 @@ def test_xent_fwd_bwd(V):
     targets = rng.integers(0, V, (B, T)).astype(np.int32)
     wmask = (np.arange(T)[None, :] < lens[:, None]).astype(np.float32)
     coef = (wmask / wmask.sum()).astype(np.float32)
+    if regime is not None:
+        logits, lens, targets, wmask, coef = exec_ops_ref.xent_operands_peaked(V, T, T, B, np.random.default_rng(V), lens=lens)
     dl = dev(logits)
     loss_rows = torch.empty(T * B, device=DEV); dlog = torch.empty((T, B, V), device=DEV)
     ids = torch.empty((T, B), dtype=torch.int32, device=DEV)
@@ -1097,9 +1141,15 @@ def test_xent_fwd_bwd(V):
     lsm = dr.log_softmax(lg.astype(np.float64), -1)
     xent = -np.take_along_axis(lsm, targets.T[..., None], 2)[..., 0] * wmask.T
     np.testing.assert_array_equal(dl.cpu().numpy(), lg)                      # finished rows zeroed
-    assert_close(loss_rows.cpu().numpy().reshape(T, B), xent, 1e-5, 'xent rows')
+    got = loss_rows.cpu().numpy().reshape(T, B)
+    print('  xent rows V=%d %s: err %.3e  element-wise %.3e  bar 1.0e-05, rows %.3g ... %.3g' % (
+        V, regime, rel_err(got, xent), elementwise_excess(got, xent, 1.0), xent.min(), xent.max()))
+    # element-wise too: the max-norm is relative to the largest row (230 with peaked logits), which hides the small ones
+    assert_close(got, xent, 1e-5, 'xent rows', elementwise=True)
+    if regime is not None:
+        assert got[2, 0] == pytest.approx(150.0, rel=1e-5) and 0 <= got[1, 0] < np.finfo(np.float32).eps
     oh = np.zeros_like(lsm); np.put_along_axis(oh, targets.T[..., None], 1.0, 2)
-    assert_close(dlog.cpu().numpy(), (np.exp(lsm) - oh) * coef.T[..., None], 1e-5, 'dlogits')
+    assert_close(dlog.cpu().numpy(), (np.exp(lsm) - oh) * coef.T[..., None], 1e-5, 'dlogits', elementwise=regime is not None)
     np.testing.assert_array_equal(ids.cpu().numpy(), lg.argmax(-1))
 
 
@@ -1112,14 +1162,26 @@ def test_argmax_ties_lowest_index():
 
 
 def test_beam_step_vs_oracle_step():
+    _beam_step_vs_oracle_step()
+
+
+def test_beam_step_peaked_logits():
+    """logit rows 30 N(0,1) + 200 / - 200 with a dominant entry (tests/regimes.py), the step restated in float64"""
+    _beam_step_vs_oracle_step('peaked')
+
+
+def _beam_step_vs_oracle_step(regime=None):
     rng = np.random.default_rng(5)
     B, W, V, end = 4, 3, 258, 257
     logits = (2 * rng.standard_normal((B, W, V))).astype(np.float32)
     logits[0, 0, 5] = logits[0, 0, 9] = 40.0            # exact tie -> lower flat index first
+    if regime is not None:
+        logits = regimes.peaked_logits(np.random.default_rng(5), B * W, V)[0].reshape(B, W, V)
+        logits[0, 0, 5] = logits[0, 0, 9] = logits[0, 0].max() + 10
     lp = np.array([[0, -1.5, -2.0]] * B, np.float32); lp[1] = [0, -np.inf, -np.inf]
     fin = np.zeros((B, W), np.int32); fin[2, 1] = 1; fin[3] = 1
     lens = rng.integers(0, 5, (B, W)).astype(np.int64)
-    step = dr.log_softmax(logits, -1)
+    step = dr.log_softmax(logits if regime is None else logits.astype(np.float64), -1)
     row = np.full(V, np.finfo(np.float32).min, np.float32); row[end] = 0
     step = np.where(fin[:, :, None].astype(bool), row[None, None, :], step)
     total = (lp[:, :, None] + step).reshape(B, W * V)
@@ -1132,7 +1194,10 @@ def test_beam_step_vs_oracle_step():
     np.testing.assert_array_equal(word.cpu().numpy(), order % V)
     np.testing.assert_array_equal(par.cpu().numpy(), order // V)
     ref_sc = np.take_along_axis(total, order, 1)
-    assert_close(sc.cpu().numpy(), ref_sc, 1e-6, 'beam scores')
+    if regime is not None:
+        print('  beam scores %s: err %.3e  element-wise %.3e  bar 1.0e-06' % (
+            regime, rel_err(sc.cpu().numpy(), ref_sc), elementwise_excess(sc.cpu().numpy(), ref_sc, 1.0)))
+    assert_close(sc.cpu().numpy(), ref_sc, 1e-6, 'beam scores', elementwise=regime is not None)
     bidx = np.arange(B)[:, None]
     pf = fin[bidx, order // V].astype(bool)
     np.testing.assert_array_equal(d_fin.cpu().numpy().astype(bool), pf | (order % V == end))
@@ -1146,25 +1211,25 @@ def test_beam_step_vs_oracle_step():
 @pytest.mark.parametrize('B,W,V,D', [(4, 3, 258, 128), (5, 8, 9000, 128), (6, 3, 8962, 256), (3, 5, 1000, 64), (4, 3, 2500, 96),
                                      (4, 3, 3100, 96), (4, 5, 2500, 96), (4, 9, 2500, 96)])
 def test_beam_step_dense_vs_oracle_step(B, W, V, D):
+    _beam_step_dense_vs_oracle_step(B, W, V, D)
+
+
+@pytest.mark.parametrize('B,W,V,D', [(4, 3, 258, 128), (4, 3, 2500, 96), (5, 8, 9000, 128)])
+def test_beam_step_dense_peaked_logits(B, W, V, D):
+    """The register-resident form, the single-member split form and the streaming-projection form with W_o scaled so that
+    the logits spread like 30 N(0,1) and b_o + 200 (tests/regimes.py): the chunk partials' exp(pmax - mx) underflow for
+    most chunks, expf overflows without the max subtraction; a finished beam, an entry whose other beams are at -inf and
+    an entry with every beam finished as in the sibling.  The step is restated in float64."""
+    _beam_step_dense_vs_oracle_step(B, W, V, D, 'peaked')
+
+
+def _beam_step_dense_vs_oracle_step(B, W, V, D, regime=None):
     """One beam step from the decoder outputs through the kernels the decode loop uses for the shape (streaming projection
     + chunk top-k + merge; register-resident small step; GEMM + comic_beam_step) against the [TF-1.9] step restated in
     numpy: exact ties between duplicate vocabulary columns (lower flat index first, also across chunks and beams), a
     finished beam, an entry whose other beams are at -inf, an entry with every beam finished."""
-    rng = np.random.default_rng(B + W + V)
-    end = V - 1
-    y = rng.standard_normal((B, W, D)).astype(np.float32)
-    Wo = (rng.standard_normal((D, V)) / np.sqrt(D)).astype(np.float32)
-    bo = (0.1 * rng.standard_normal(V)).astype(np.float32)
-    Wo[:, 7] = Wo[:, 3]; bo[7] = bo[3]                          # duplicate columns: exact ties, same chunk
-    Wo[:, V - 5] = Wo[:, 3]; bo[V - 5] = bo[3]                  # ... and in the last chunk
-    Wo[:, 3] *= 3.0; Wo[:, 7] *= 3.0; Wo[:, V - 5] *= 3.0       # make them likely winners for some rows
-    y[0, 1] = y[0, 0]                                           # two beams of entry 0 with identical logits
-    lp = np.tile(np.linspace(0, -2.0, W, dtype=np.float32), (B, 1))
-    lp[0, 1] = lp[0, 0]                                         # ... and equal totals: ties across beams
-    lp[1, 1:] = -np.inf
-    fin = np.zeros((B, W), np.int32); fin[2, 1] = 1; fin[B - 1] = 1
-    lens = rng.integers(0, 5, (B, W)).astype(np.int64)
-    logits = (y.reshape(B * W, D).astype(np.float64) @ Wo.astype(np.float64) + bo).astype(np.float32).reshape(B, W, V)
+    o = exec_ops_ref.dense_beam_operands(B, W, V, D, regime)
+    end, y, Wo, bo, lp, fin, lens, logits = (o[k] for k in ('end', 'y', 'Wo', 'bo', 'lp', 'fin', 'lens', 'logits'))
     step = dr.log_softmax(logits, -1)
     row = np.full(V, np.finfo(np.float32).min, np.float32); row[end] = 0
     step = np.where(fin[:, :, None].astype(bool), row[None, None, :], step)
@@ -1191,7 +1256,12 @@ def test_beam_step_dense_vs_oracle_step(B, W, V, D):
                 assert abs(total[b, fl[b, k]] - ref_sc[b, k]) <= 2e-4 * max(1.0, abs(ref_sc[b, k])), (b, k, fl[b, k], order[b, k])
         assert len(set(fl[b].tolist())) == W
     fin_sc = np.isfinite(ref_sc) & (np.abs(ref_sc) < 1e30)
-    assert_close(np.where(fin_sc, got_sc, 0), np.where(fin_sc, ref_sc, 0), 2e-4, 'beam scores')
+    if regime is not None:
+        print('  dense beam scores %s (%d,%d,%d,%d): |logits| to %.0f, err %.3e  element-wise %.3e  bar 2.0e-04' % (
+            regime, B, W, V, D, np.abs(logits).max(), rel_err(np.where(fin_sc, got_sc, 0), np.where(fin_sc, ref_sc, 0)),
+            elementwise_excess(np.where(fin_sc, got_sc, 0), np.where(fin_sc, ref_sc, 0), 1.0)))
+    # peaked: max|ref| is 17 ... 34 where the sibling's is about 2 and most kept scores lie in 0 ... -2, so element-wise too
+    assert_close(np.where(fin_sc, got_sc, 0), np.where(fin_sc, ref_sc, 0), 2e-4, 'beam scores', elementwise=regime is not None)
     dup = {3, 7, V - 5}
     for b in range(B):
         ws_b = [int(x) for x in got_w[b]]
@@ -1347,6 +1417,37 @@ def test_legacy_encoder_head_matches_oracle():
         assert_close(g[k], gref[k], 1e-3, 'legacy d ' + k)
     assert set(head.export_params()) == {'Model/encoder/LN_tanh/beta', 'Model/encoder/LN_tanh/gamma',
                                          'Model/encoder/im_embed/weight'}
+
+
+@pytest.mark.parametrize('r', regimes.OFFSETS)
+@pytest.mark.parametrize('C_', [192, 2048])
+def test_ln_tanh_kernels_on_non_negative_rows(C_, r):
+    """comic_ln_tanh_fwd / comic_ln_tanh_bwd_rows on their own operands: pooled post-ReLU features are non-negative, so
+    the head's LayerNorm rows have a mean of several standard deviations (here 4 and 32).  y and xhat at the bar of the
+    same formula in the attention step (1e-4), the per-row gradient terms at 1e-3 on the float32 roundings of the
+    reference's saved tensors; outputs NaN before the launch."""
+    B = 5
+    rng = np.random.default_rng(C_ + r)
+    x = regimes.nonneg_offset(rng, (B, C_), r)
+    gamma = rng.uniform(0.5, 1.5, C_).astype(np.float32)
+    beta = (0.1 * rng.standard_normal(C_)).astype(np.float32)
+    dy = rng.standard_normal((B, C_)).astype(np.float32)
+    x64 = x.astype(np.float64)
+    mean = x64.mean(1, keepdims=True)
+    xhat_ref = (x64 - mean) / np.sqrt(((x64 - mean) ** 2).mean(1, keepdims=True) + 1e-12)
+    y_ref = np.tanh(xhat_ref * gamma + beta)
+    y, xhat, pg, pb = (torch.full((B, C_), float('nan'), device=DEV) for _ in range(4))
+    L.check(lib().comic_ln_tanh_fwd(P(x), P(gamma), P(beta), y.data_ptr(), xhat.data_ptr(), B, C_, 1e-12, stream()), 'ln_tanh_fwd')
+    sync()
+    for name, got, ref in (('y', y, y_ref), ('xhat', xhat, xhat_ref)):
+        print('  LN_tanh C=%d offset(%d) %-5s err %.3e  bar 1.0e-04' % (C_, r, name, rel_err(got.cpu().numpy(), ref)))
+        assert_close(got.cpu().numpy(), ref, 1e-4, name, elementwise=True)
+    y32, xh32 = y_ref.astype(np.float32), xhat_ref.astype(np.float32)
+    L.check(lib().comic_ln_tanh_bwd_rows(P(dy), P(y32), P(xh32), pg.data_ptr(), pb.data_ptr(), B, C_, stream()), 'ln_tanh_bwd_rows')
+    sync()
+    t = dy.astype(np.float64) * (1.0 - y32.astype(np.float64) ** 2)
+    assert_close(pg.cpu().numpy(), t * xh32, F32_RTOL, 'd gamma rows')
+    assert_close(pb.cpu().numpy(), t, F32_RTOL, 'd beta rows')
 
 
 def test_process_decode_pool_equals_thread_decode(tmp_path):

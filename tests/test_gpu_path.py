@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 import comic_amd._lib as L
 from comic_amd import decoder as cdec, nets
 from oracle import beam_ref, cnn_ref, decoder_ref as dr
+from tests import exec_ops_ref
 from tests.gpu_util import DEV, F32_RTOL, assert_close, dev, rel_err, sync
 
 
@@ -772,6 +773,45 @@ def test_decoder_train_step_matches_oracle(kw, use_dropout, scst):
     assert_close(res['dim_embed'].cpu().numpy(), dim, F32_RTOL, 'dim_embed')
 
 
+@pytest.mark.parametrize('path', [3, 0], ids=['time_loops', 'step_launches'])
+@pytest.mark.parametrize('geo', exec_ops_ref.FEATURE_GEOMETRIES, ids=lambda g: 'M%d_H%d' % (g.get('M', 25), g.get('H', 8)))
+def test_decoder_train_step_matches_oracle_on_post_relu_features(geo, path, monkeypatch):
+    """test_decoder_train_step_matches_oracle in the `features` regime of tests/regimes.py, against the oracle in FLOAT64:
+    fm, im = |N(0,1)| and W_m + delta 1 1^T, so that the LayerNorm rows keys + q of the oracle itself have a mean of 32
+    standard deviations (12 at M = 196, H = 4: exec_ops_ref.features_r).  B = 6, Lc = 11, no dropout; the small-memory
+    loops (M = 25), the own-rows backward loop (M = 64) and the large-memory forward loop, whose variance is one-pass
+    (M = 196 / 130), each through both persistent loops (path 3) and through the per-step launch chain (path 0): both
+    are held to the reference, not only to each other.  tests/test_regimes_cpu.py holds the float32 oracle below a
+    tenth of this bar on the same operands."""
+    fc = exec_ops_ref.features_case(geo)
+    spec, _ = _spec_and_cfg(**geo)
+    out, caps = fc['out'], fc['caps']
+    lens = out['cache']['lens']
+    if path == 0:
+        monkeypatch.setenv('COMIC_PERSIST', '0')
+        monkeypatch.setenv('COMIC_PERSIST_BWD', '0')
+    dec = cdec.Decoder(spec, fc['p'], DEV)
+    res = dec.train_step(dev(fc['fm']), dev(fc['im']), caps, training=False, want_input_grads=True)
+    sync()
+    assert dec.lib.comic_decoder_train_path() == path
+    g = dec.grads.to_numpy()
+    pairs = [('logits', res['logits'].cpu().numpy(), out['logits']), ('attn_maps', res['attn_maps'].cpu().numpy(), out['attn_maps']),
+             ('dfm', res['dfm'].cpu().numpy(), fc['dfm']), ('dim_embed', res['dim_embed'].cpu().numpy(), fc['dim'])]
+    pairs += [('grad ' + k, g[k], fc['grads'][k]) for k in fc['grads']]
+    print('  %s path %d, z mean / std %.1f: loss %.6f (oracle %.6f)' % (geo, path, exec_ops_ref.z_ratio(out), float(res['loss']),
+                                                                      float(out['xe'])))
+    for name, got, ref in pairs:
+        print('    %-12s err %.3e  bar %.1e' % (name, rel_err(got, ref), F32_RTOL))
+    for name, got, ref in pairs:
+        assert_close(got, ref, F32_RTOL, name)
+    assert abs(float(res['loss']) - float(out['xe'])) <= F32_RTOL * abs(float(out['xe'])) + 1e-6
+    assert abs(float(res['map_loss']) - float(out['map_loss'])) <= F32_RTOL * abs(float(out['map_loss'])) + 1e-7
+    # arg-max ids of the live steps, where the float64 logits decide them by more than the bar
+    lg = np.sort(out['logits'], -1)
+    clear = (np.arange(lg.shape[1])[None, :] < lens[:, None]) & (lg[..., -1] - lg[..., -2] > F32_RTOL * np.abs(out['logits']).max())
+    np.testing.assert_array_equal(res['ids'].cpu().numpy()[clear], out['ids'][clear])
+
+
 @pytest.mark.parametrize('geo', [dict(C=832, Cg=1024, M=196), dict(M=64)])
 def test_large_memory_loops_graph_replay_equals_eager(geo):
     """The large-memory forms of the persistent loops under hipGraph capture / replay, on a second decoder with the same
@@ -1202,6 +1242,43 @@ def test_greedy_and_beam_match_oracle(kw):
         fin = np.isfinite(scores)
         assert_close(np.where(fin, res['scores'], 0), np.where(fin, scores, 0), 1e-4, 'beam scores')
         assert_close(res['attn_hist'], hist, F32_RTOL, 'beam alignment history')
+
+
+@pytest.mark.parametrize('kw', exec_ops_ref.DECODE_FEATURE_GEOMETRIES, ids=['persistent_greedy_D512', 'launch_chain_D128'])
+def test_greedy_and_beam_match_oracle_on_post_relu_features(kw):
+    """One add_LN variant of test_persistent_greedy_loop_matches_oracle (D = 512: the greedy loop as one launch) and one of
+    test_greedy_and_beam_match_oracle (D = 128: per-step launches) in the `features` regime of tests/regimes.py -- the
+    operands of exec_ops_ref.features_case, whose LayerNorm rows keys + q have a mean of 32 standard deviations -- against
+    the oracle in float64: ids bit-exact as in the siblings, logits, attention maps and the beam's alignment history at
+    F32_RTOL, beam scores at 1e-4."""
+    fc = exec_ops_ref.features_case(kw)
+    spec, _ = _spec_and_cfg(**kw)
+    cfg, fm, im, max_steps = fc['cfg'], fc['fm'], fc['im'], 12
+    # b_o as drawn: post-ReLU features give every row nearly the same small logits, so the siblings' EOS bias of 1.5 would
+    # end every caption at its first token; without it all twelve steps run (top-2 gaps of the float64 logits: 2e-3 and more)
+    p = fc['p']
+    p64, fm64, im64 = {k: v.astype(np.float64) for k, v in p.items()}, fm.astype(np.float64), im.astype(np.float64)
+    g_ids, g_logits, g_map = beam_ref.greedy_decode(p64, cfg, fm64, im64, max_steps)
+    dec = cdec.Decoder(spec, p, DEV)
+    ids, amap, logits = dec.greedy(dev(fm), dev(im), max_steps, want_logits=True)
+    print('  greedy %s: logits err %.3e, maps err %.3e  bar %.1e' % (kw, rel_err(logits.cpu().numpy(), g_logits),
+                                                                    rel_err(amap.cpu().numpy(), g_map), F32_RTOL))
+    np.testing.assert_array_equal(ids, g_ids)
+    assert_close(logits.cpu().numpy(), g_logits, F32_RTOL, 'greedy logits')
+    assert_close(amap.cpu().numpy(), g_map, F32_RTOL, 'greedy attention maps')
+    if spec.D == 512:
+        dec.greedy(dev(fm), dev(im), max_steps, use_graph=False)
+        assert dec.lib.comic_decoder_greedy_path() == 1            # the persistent loop really ran
+    pred, scores, hist, dbg = beam_ref.beam_search_decode(p64, cfg, fm64, im64, 3, max_steps, return_debug=True)
+    res = dec.beam_search(dev(fm), dev(im), 3, max_steps)
+    np.testing.assert_array_equal(res['step_ids'], dbg['step_ids'])
+    np.testing.assert_array_equal(res['parent_ids'], dbg['parent_ids'])
+    np.testing.assert_array_equal(res['predicted_ids'], pred)
+    fin = np.isfinite(scores)
+    print('  beam 3: scores err %.3e  bar 1.0e-04, alignment history err %.3e  bar %.1e' % (
+        rel_err(np.where(fin, res['scores'], 0), np.where(fin, scores, 0)), rel_err(res['attn_hist'], hist), F32_RTOL))
+    assert_close(np.where(fin, res['scores'], 0), np.where(fin, scores, 0), 1e-4, 'beam scores')
+    assert_close(res['attn_hist'], hist, F32_RTOL, 'beam alignment history')
 
 
 @pytest.mark.parametrize('B,W,V,D', [(5, 3, 9000, 128), (50, 3, 8962, 128), (32, 8, 4300, 256), (7, 5, 25599, 512),

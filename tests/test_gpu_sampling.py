@@ -123,6 +123,20 @@ def test_sampled_step_matches_float64(shape, state, temp):
     _check_step(got, ref)
 
 
+def test_sampled_step_peaked_logits():
+    """Three members whose rows each have one dominant entry: the step distribution is log w_m at three tokens and below
+    -25 elsewhere, the noise decides between the three; scores and ids against the float64 reference as in the sibling"""
+    shape, temp = (3, 3, 4, 258), 0.7
+    c = sref.peaked_inputs(shape)
+    g = sref.noise(SEED, 0, shape[1], shape[2], 0, shape[3])[2]
+    ref = sref.ref_select_sampled(c['lp'], c['log_probs'], c['finished'], c['lengths'], c['end_id'], g, sref.inv_temp_of(temp))
+    share = _noise_decides(c, ref)
+    print('peaked: reference rank-gap margin %.2f (must exceed 1); %.2f of the live slots leave the greedy choice' % (ref['margin'], share))
+    assert ref['margin'] > 1.0
+    assert np.abs(c['logits']).max() > 250
+    _check_step(run_step_sampled(*_state(c), temp), ref)
+
+
 def test_other_seed_words_and_step():
     """Seed 5, base 1000, t 3: checked on the CPU, the smallest margin over the 28 cases is 16; here the two split shapes
     and the radix one."""

@@ -6,7 +6,8 @@ import torch
 
 from comic_amd import decoder as cdec
 from oracle import decoder_ref as dr
-from tests.gpu_util import DEV, F32_RTOL, assert_close, dev, rel_err, sync
+from tests import exec_ops_ref
+from tests.gpu_util import DEV, F32_RTOL, assert_close, dev, elementwise_excess, rel_err, sync
 from tests.test_gpu_path import _rand_params, _spec_and_cfg
 
 pytestmark = pytest.mark.gpu
@@ -165,6 +166,35 @@ def test_per_step_forms(kw, env, monkeypatch):
     assert dec.lib.comic_decoder_score_path() & 1 == 0
     assert_close(res['token_log_probs'].cpu().numpy(), want, F32_RTOL, 'token log-probs')
     assert_close(res['log_prob'].cpu().numpy(), want.sum(axis=1), F32_RTOL, 'caption log-probs')
+
+
+# per-step launches and the persistent forward loop at V = 258 (one partial per row: score_rows_kernel, the merge loop of
+# score_merge_kernel runs once), and V = 4099: 37 chunk partials per row, the chunk merge proper (path 3, as `large_tile`)
+@pytest.mark.parametrize('name,env,path', [('V258', {'COMIC_PERSIST': '0'}, 0), ('V258', {}, 1), ('V4099', {}, 3)],
+                         ids=['per_step_V258', 'persistent_V258', 'chunk_merge_V4099'])
+def test_score_peaked_logits(name, env, path, monkeypatch):
+    """The regime `peaked` of tests/regimes.py through the output projection, against the oracle in float64: W_o scaled so
+    that the logits spread like 30 N(0,1), b_o + 200 (expf overflows without the max subtraction; a chunk partial's
+    exp(pmax - mx) underflows for most chunks).  Token log-probs reach -150 and further, so they are held element-wise
+    beside the max-norm, at the bar of test_per_step_forms.  The operands are exec_ops_ref.score_peaked_case, on which
+    tests/test_regimes_cpu.py holds the float32 oracle below a tenth of the bar."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    c = exec_ops_ref.score_peaked_case(name)
+    spec, _ = _spec_and_cfg(**exec_ops_ref.SCORE_PEAKED_GEOMETRIES[name])
+    cfg, p, fm, im, caps, out = (c[k] for k in ('cfg', 'p', 'fm', 'im', 'caps', 'out'))
+    _, targets, wmask, _ = dr.process_inputs(caps, cfg.token_type)
+    want = _log_softmax_at(out['logits'], targets, wmask)
+    assert np.abs(out['logits']).max() > 250 and want.min() < -100
+    dec = cdec.Decoder(spec, p, DEV)
+    res = dec.score(dev(fm), dev(im), caps)
+    sync()
+    assert dec.lib.comic_decoder_score_path() == path         # 3: the streaming projection and its 37-chunk merge really ran
+    tok, logp = res['token_log_probs'].cpu().numpy(), res['log_prob'].cpu().numpy()
+    print('  V=%d: token log-probs %.1f ... %.1f, err %.3e  element-wise %.3e  bar %.1e' % (
+        spec.V, want.min(), want[wmask > 0].max(), rel_err(tok, want), elementwise_excess(tok, want, 1.0), F32_RTOL))
+    assert_close(tok, want, F32_RTOL, 'token log-probs')
+    assert_close(logp, want.sum(axis=1), F32_RTOL, 'caption log-probs')
 
 
 @pytest.mark.parametrize('name', ['small', 'large_block'])

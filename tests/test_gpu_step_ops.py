@@ -60,18 +60,18 @@ def cdiv(a, b):
 
 # ============================================================================ lstm_step_fused ========================
 @functools.lru_cache(maxsize=None)
-def step_case(shape):
+def step_case(shape, regime=None):
     B, D, EA = shape
-    inp = S.step_inputs(B, D, EA)
+    inp = S.step_inputs(B, D, EA, regime=regime)
     full = S.lstm_step_ref(inp['xh'], inp['K'], inp['b'], inp['c'], inp['h'], inp['mask'], S.KEEP, inp['lens'], T)
     infer = S.lstm_step_ref(inp['xh'], inp['K'], inp['b'], inp['c'], None, None, 1.0, None, 0)
     return inp, full, infer
 
 
-def launch_step(shape, full, stop_value=None):
+def launch_step(shape, full, stop_value=None, regime=None):
     B, D, EA = shape
     Wd = EA + D
-    inp = step_case(shape)[0]
+    inp = step_case(shape, regime)[0]
     ld_xh, xh_ld, xh_off = Wd + 12, D + 24, 8
     xh = nan(B, ld_xh)
     xh[:, :Wd] = dev(inp['xh'])
@@ -93,14 +93,25 @@ def launch_step(shape, full, stop_value=None):
 @pytest.mark.parametrize('full', [True, False], ids=['all_outputs', 'inference_call'])
 @pytest.mark.parametrize('shape', S.FUSED_SHAPES, ids=str)
 def test_lstm_step_fused(shape, full):
+    run_lstm_step_fused(shape, full)
+
+
+@pytest.mark.parametrize('shape', S.FUSED_SHAPES[:2], ids=str)
+def test_lstm_step_fused_saturated(shape):
+    """the regime `saturated` of tests/regimes.py: gate pre-activations uniform over +-100 (expf(-x) is inf beyond
+    88.7), previous cell states to +-50 (tanh(c) = +-1), on the two smallest shapes"""
+    run_lstm_step_fused(shape, True, 'saturated')
+
+
+def run_lstm_step_fused(shape, full, regime=None):
     """lstm_step_fused_wide_kernel<2> over the forward panel of pack_lstm_panels_kernel (mode 0): one unit tile in a
     two-tile workgroup (D = 4), an odd tile count and Wd % 16 = 4 (D = 36, Wd = 68), ragged row tiles, a finished row in
     the last one; operand and xh_next rows wider than Wd / D.  `inference_call`: every optional argument null."""
     B, D, EA = shape
     assert lib() is not None
-    _, ref_full, ref_infer = step_case(shape)
+    _, ref_full, ref_infer = step_case(shape, regime)
     ref = ref_full if full else ref_infer
-    rc, out, (off, _) = launch_step(shape, full)
+    rc, out, (off, _) = launch_step(shape, full, regime=regime)
     assert rc == 0, lib().comic_last_error()
     tag = '%s %s: ' % (shape, 'full' if full else 'infer')
     for k in ('y', 'c_state', 'h_state') + (('gates_act', 'c_new') if full else ()):
@@ -139,11 +150,21 @@ def test_lstm_step_fused_refuses_unsupported_shapes():
 # ============================================================================ input_grad_fused =======================
 @pytest.mark.parametrize('shape', S.GRAD_SHAPES, ids=str)
 def test_input_grad_fused(shape):
+    run_input_grad_fused(shape)
+
+
+@pytest.mark.parametrize('shape', S.GRAD_SHAPES[:2], ids=str)
+def test_input_grad_fused_saturated(shape):
+    """the gate gradients of saturated cells: exact zeros but for one element in eight"""
+    run_input_grad_fused(shape, 'saturated')
+
+
+def run_input_grad_fused(shape, regime=None):
     """input_grad_fused_wide_kernel<2> over the backward panel (mode 1): E | A and A | D inside a 16-feature tile, a
     ragged last feature tile, an odd tile count; carry 0 / 1, mask present / null, demb null"""
     B, E, A, D = shape
     Wd = E + A + D
-    inp = S.grad_inputs(B, E, A, D)
+    inp = S.grad_inputs(B, E, A, D, regime=regime)
     n_panel = cdiv(Wd, 16) * (4 * D // 16) * 256
     d_K, d_dg, d_mask, d_lens = dev(inp['K']), dev(inp['dg']), dev(inp['mask']), dev(inp['lens'])
     for carry, use_mask, use_demb in ((0, True, True), (1, True, True), (1, False, True), (0, False, False)):
@@ -169,10 +190,21 @@ def test_input_grad_fused(shape):
 @pytest.mark.parametrize('bare', [False, True], ids=['dy_mask_cprev', 'none_of_them'])
 @pytest.mark.parametrize('shape', S.QGRAD_SHAPES, ids=str)
 def test_lstm_grad_fused(shape, bare):
+    run_lstm_grad_fused(shape, bare)
+
+
+@pytest.mark.parametrize('shape', S.QGRAD_SHAPES[:2], ids=str)
+def test_lstm_grad_fused_saturated(shape):
+    """the saved activations of a saturated step: s (1 - s) and 1 - tanh^2 underflow, d gates is mostly exact zeros;
+    finite everywhere and equal to the reference element-wise, so neither a NaN nor a stray non-zero can hide"""
+    run_lstm_grad_fused(shape, False, 'saturated')
+
+
+def run_lstm_grad_fused(shape, bare, regime=None):
     """lstm_grad_fused_kernel over the W_q panel: dy_total = dy + dq W_q^T, output-dropout and cell backward, the
     finished-row rule; with and without dy / mask_out / c_prev"""
     B, D = shape
-    q = S.qgrad_inputs(B, D)
+    q = S.qgrad_inputs(B, D, regime=regime)
     ref = S.lstm_grad_ref(q['dq'], q['Wq'], q['gates_act'], None if bare else q['c'], q['c_new'], None if bare else q['dy'],
                           None if bare else q['mask'], S.KEEP, q['lens'], T, q['dc'], q['dh'])
     panel = ff(4 * D * D)
@@ -213,9 +245,9 @@ def xfrag_bytes(R, Kin):
 
 
 @functools.lru_cache(maxsize=None)
-def infer_case(shape, seed=None):
+def infer_case(shape, seed=None, regime=None):
     R, W, D, E, A = shape
-    inp = S.infer_inputs(R, W, D, E, A, seed=seed)
+    inp = S.infer_inputs(R, W, D, E, A, seed=seed, regime=regime)
     return (inp,) + S.infer_step_ref(inp, W)
 
 
@@ -296,10 +328,32 @@ def test_infer_lstm_step_stream_path(shape, slices):
     check_states(tag, out, ref, S.STREAM_TOL)
 
 
+def test_infer_lstm_step_saturated():
+    """comic_op_infer_lstm_step with gate pre-activations over +-100 and cell states to +-50: the fused path on its
+    smallest shape, the streaming path on its smallest shape, and both on the shape both serve"""
+    for shape, mode, tol in ((S.INFER_FUSED_SHAPES[0], 0, S.GATES_TOL), (S.STREAM_SHAPES[0][0], 1, S.STREAM_TOL),
+                             (S.BOTH_SHAPE, 0, S.GATES_TOL), (S.BOTH_SHAPE, 1, S.STREAM_TOL)):
+        inp, x, c_in, ref = infer_case(shape, None, 'saturated')
+        rc, out = launch_infer(shape, mode, inp=inp)
+        sync()
+        assert rc == 0, lib().comic_last_error()
+        np.testing.assert_array_equal(host(out['c_in']), c_in)
+        check_states('%s saturated %s: ' % (shape, 'stream' if mode else 'fused'), out, ref, tol)
+
+
 def test_infer_lstm_step_stream_and_fused_agree():
+    run_stream_and_fused_agree()
+
+
+def test_infer_lstm_step_stream_and_fused_agree_saturated():
+    run_stream_and_fused_agree('saturated')
+
+
+def run_stream_and_fused_agree(regime=None):
     shape = S.BOTH_SHAPE
-    rc1, o1 = launch_infer(shape, 1)
-    rc0, o0 = launch_infer(shape, 0)
+    inp = infer_case(shape, None, regime)[0]
+    rc1, o1 = launch_infer(shape, 1, inp=inp)
+    rc0, o0 = launch_infer(shape, 0, inp=inp)
     sync()
     assert rc1 == 0 and rc0 == 0, lib().comic_last_error()
     np.testing.assert_array_equal(host(o1['c_in']), host(o0['c_in']))

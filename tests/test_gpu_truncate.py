@@ -95,6 +95,32 @@ def test_truncate_matches_the_sandwich(shape, state, temp):
             np.testing.assert_array_equal(np.argmin(dropped, axis=2)[live], np.argmax(c['lp'], axis=2)[live])
 
 
+def test_truncate_peaked_logits():
+    """The regime `peaked` of tests/regimes.py on the widest entry (64 rows of V = 300), temperature 1: rows 30 N(0,1) + 200 /
+    - 200 whose dominant token alone holds all but 1e-11 of the mass -- the first token exceeds p, the nucleus is that token
+    -- and one row whose masses are 0.30, 0.25, 0.20, 0.14, 0.06 and a tail of 0.05: p = 0.9 is reached only at the fifth
+    token (0.89 before it), p = 0.5 at the second (0.30 before it).  The pass rule is the sibling's."""
+    shape = (1, 1, 64, 300)
+    c = sref.peaked_inputs(shape)
+    V, row = shape[3], int(np.flatnonzero(c['finished'][0] == 0)[3])
+    q = np.r_[0.30, 0.25, 0.20, 0.14, 0.06, np.full(V - 5, 0.05 / (V - 5))]
+    c['logits'][0, 0, row] = (200.0 + np.log(q))[np.random.default_rng(3).permutation(V)]
+    c['lp'] = sref.ref_step_lp(c['logits'], c['wts'])
+    for top_k, top_p in ((0, 0.9), (0, 0.5), (5, 0.9), (5, 1.0), (1, 1.0)):
+        ref = tref.truncate_ref(c['lp'], c['finished'], sref.inv_temp_of(1.0), top_k, top_p)
+        print('peaked top_k %d top_p %g: band %d, smallest must_keep %d, k_clear %s' % (top_k, top_p, ref['band'], ref['keep_min'],
+                                                                                     ref['k_clear']))
+        assert ref['k_clear']
+        if top_p < 1.0:                                         # the reference itself: one token, and five / two in the crafted row
+            kept = {bw: int(r['exact'].sum()) for bw, r in ref['rows'].items() if r is not None}
+            # (within the top five, whose mass is 0.95, p = 0.9 is reached at the fourth token)
+            assert kept[0, row] == {(0, 0.9): 5, (0, 0.5): 2, (5, 0.9): 4}[top_k, top_p]
+            assert all(n == 1 for bw, n in kept.items() if bw != (0, row))
+            assert ref['band'] == 0
+        dropped, _ = run_truncate(c, 1.0, top_k, top_p)
+        tref.check_mask(dropped, ref, top_k, top_p, exact=top_p < 1.0 or top_k == 1)
+
+
 # ------------------------------------------------------------------ 2. under an incoming ban mask ------------------------
 @functools.lru_cache(maxsize=None)
 def _banned(shape, state, temp, ban_seed):
