@@ -156,9 +156,14 @@ __global__ __launch_bounds__(256) void act_grad_x3_kernel(ActGradX3Args a, float
       for (int i = 0; i < EPC; ++i) {
         const float g = yv[i] > 0.f ? gv[i] : 0.f;
         sum[i] += g;
-        const float z = g * sc[i];
-        hi[i] = bf16_to_f32(f32_to_bf16(z));
-        lo[i] = z - hi[i];
+        {
+          // z is the ROUNDED product, the value act_grad_kernel stores on the fp32 plan: contracted, z - hi becomes
+          // fma(g, sc, -hi) and lo is the residue of another number
+#pragma clang fp contract(off)
+          const float z = g * sc[i];
+          hi[i] = bf16_to_f32(f32_to_bf16(z));
+          lo[i] = z - hi[i];
+        }
       }
       bf16_t* dst = a.dz + (((size_t)b * a.Hd + ho * a.dil) * a.Wd + wo * a.dil) * 3 * a.C + c0;
       store_vec<bf16_t>(dst, hi);
@@ -886,6 +891,20 @@ int conv_backward(const comic_cnn_op* op, const void* x, int xc, const void* y, 
   COMIC_REQUIRE(wt && wt->scale && gr && gr->w_master && gr->dw && gr->dbeta, "conv backward: missing weight / gradient record");
   COMIC_REQUIRE(op->Cout % EPC == 0 && op->dst_coff % EPC == 0 && yc % EPC == 0, "conv backward: misaligned output slice");
   COMIC_REQUIRE(op->SH == op->SW && (op->SH == 1 || op->SH == 2), "conv backward: stride must be 1 or 2");
+  // what the launches below require of the conv is checked in front of the first of them, so a refused call leaves dw,
+  // d beta and gx as they were: the weight gradient's input slice, and for the backward-data convolution the conditions of
+  // the forward kernels it runs on (comic_run_op, with Cin in the place of Cout)
+  if (stem) {
+    COMIC_REQUIRE(op->Cin <= 4, "stem conv backward: needs Cin <= 4");
+  } else {
+    COMIC_REQUIRE(op->Cin % EPC == 0 && op->src_coff % EPC == 0 && xc % EPC == 0, "conv backward: misaligned input slice");
+    if (gx || fuse) {
+      COMIC_REQUIRE(gr->w_bwd, "conv backward: missing backward-data filter buffer");
+      COMIC_REQUIRE(op->Cin % 16 == 0 && op->src_coff % 4 == 0 && xc % 4 == 0 && op->src_coff + op->Cin <= xc,
+                    "conv backward: the backward-data convolution needs Cin %% 16 == 0 (got %d) and its slice inside the %d "
+                    "channels of the source", op->Cin, xc);
+    }
+  }
   const int K = op->KH * op->KW * op->Cin, Kpad = (K + 63) / 64 * 64;
   const int dil = op->SH;
   // zero-dilated d conv geometry: output pixel (ho, wo) sits at (ho*dil, wo*dil); the backward-data
@@ -949,6 +968,18 @@ int conv_backward_x3(const comic_cnn_op* op, const void* x, int xc, const void* 
   COMIC_REQUIRE(op->Cout % 8 == 0 && op->dst_coff % 8 == 0 && (stem || (op->Cin % 3 == 0 && xc % 3 == 0)) &&
                     (op->out_f32 || yc % 3 == 0), "conv backward (x3): channel regions do not fit the buffers");
   const int cin = stem ? op->Cin : op->Cin / 3, x_lo = stem ? 0 : xc / 3, y_lo = op->out_f32 ? 0 : yc / 3;
+  // (as in conv_backward: every refusal in front of the first launch)
+  if (stem) {
+    COMIC_REQUIRE(op->Cin <= 4, "stem conv backward: needs Cin <= 4");
+  } else {
+    COMIC_REQUIRE(cin % 8 == 0 && op->src_coff % 8 == 0 && x_lo % 8 == 0, "conv backward (x3): misaligned input slice");
+    if (gx) {
+      COMIC_REQUIRE(gr->w_bwd, "conv backward (x3): missing backward-data filter buffer");
+      COMIC_REQUIRE(cin % 16 == 0 && op->src_coff % 4 == 0 && gxc % 4 == 0 && op->src_coff + cin <= gxc,
+                    "conv backward (x3): the backward-data convolution needs Cin %% 16 == 0 (got %d) and its slice inside the "
+                    "%d channels of the source gradient", cin, gxc);
+    }
+  }
   const int K = op->KH * op->KW * cin, Kpad = (K + 63) / 64 * 64;
   const int dil = op->SH;
   const int Hd = (op->Ho - 1) * dil + 1, Wd = (op->Wo - 1) * dil + 1;

@@ -264,7 +264,11 @@ typedef struct comic_conv_grad {
  * to wgrad_stream behind its act_grad launch and runs beside the backward-data chain of the earlier layers on `stream`
  * (at batch 32 neither chain fills the chip: 7.2 -> 5.x ms per cnn_finetune step).  The call joins the lanes before it
  * returns: work issued on `stream` afterwards (all-reduce, optimiser) sees every gradient.  lanes = 1 / wgrad_stream = NULL:
- * one chain on `stream`. */
+ * one chain on `stream`.
+ * A conv the backward cannot run (stride above 2, a misaligned slice, a source with a gradient buffer whose Cin is no
+ * multiple of 16: its backward-data convolution runs on the forward kernels) is refused in front of that conv's first
+ * launch: its dw, dbeta and source gradient come back as they were.  (A patch-resident bwd_tile id that refuses the
+ * layer is found out by its launcher, behind the conv's activation and weight gradients.) */
 int64_t comic_cnn_backward_scratch_bytes(const comic_cnn_op* ops, int n_ops, int batch, int dtype, int lanes);
 int comic_cnn_backward(const comic_cnn_op* ops, int n_ops, void* const* buffers,
                        void* const* grad_buffers, const int32_t* buf_channels,
