@@ -119,6 +119,14 @@ class BeamPrefix(C.Structure):       # struct comic_beam_prefix
     _fields_ = [('max_tokens', c_int32)]
 
 
+SOFT_MAX_K = 32                      # COMIC_SOFT_MAX_K
+
+
+class SoftTargets(C.Structure):      # struct comic_soft_targets
+    _fields_ = [('smoothing', c_float), ('teacher_weight', c_float), ('K', c_int32), ('ids_tbk', c_void_p),
+                ('probs_tbk', c_void_p), ('nll_rows', c_void_p)]
+
+
 class GemmProb(C.Structure):         # struct comic_gemm_prob
     _fields_ = [(n, c_void_p) for n in ('A', 'B', 'C', 'bias', 'mask')] + [(n, c_int32) for n in (
         'M', 'N', 'K', 'lda', 'ldb', 'ldc', 'ld_mask')] + [(n, c_float) for n in ('alpha', 'beta', 'keep')] + [
@@ -204,6 +212,12 @@ _SIGS = {
     'comic_decoder_infer_workspace': (c_int64, [P, c_int, c_int]),
     'comic_decoder_train_step': (c_int, [P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P,
                                          P, P, P, P, P, c_int64, P]),
+    # ... against soft targets (label smoothing, top-K distillation): the same arguments and the record
+    'comic_decoder_train_step_soft': (c_int, [P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P,
+                                              P, P, P, P, P, c_int64, P, P]),
+    'comic_xent_soft': (c_int, [P, P, P, P, P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_float, c_float, c_int, P, P,
+                                P]),
+    'comic_teacher_topk': (c_int, [P, P, c_int, P, c_int, c_int, c_int, c_int, c_float, c_int, P, P, P]),
     'comic_decoder_score_workspace': (c_int64, [P, c_int, c_int]),
     'comic_decoder_score': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, c_int64, P]),
     'comic_decoder_score_path': (c_int, []),

@@ -887,6 +887,7 @@ struct StepIO {
   float *token_logp_tb, *caption_logp;        // [T][B], [B]: scoring
   void* workspace;
   int64_t workspace_bytes;
+  const comic_soft_targets* soft;             // soft targets of the sequence loss, or null (comic_decoder_train_step_soft)
 };
 
 // The decisions of one call, taken once after validation
@@ -1184,7 +1185,12 @@ struct TeacherForcedStep {
   int loss_and_padding() {
     const long n = (long)Tp * B * M;
     const int nparts = (int)cdiv64(n, 256);               // partial sums of the map loss
-    if (pl.grp) {       // both losses in one launch (d logits rows are ldl floats apart)
+    const comic_soft_targets* soft = io.soft;
+    if (soft) {         // soft targets: their own launch on either layout of d logits; the map loss as its two launches below
+      RC(comic_xent_soft_ex(io.logits_tb, io.targets_bt, io.coef_bt, io.wmask_bt, io.lens, io.loss_rows, soft->nll_rows, L.dlogits,
+                            pl.ldl, io.ids_tb, Tp, T, B, V, soft->smoothing, soft->teacher_weight, soft->K, soft->ids_tbk,
+                            soft->probs_tbk, st));
+    } else if (pl.grp) {       // both losses in one launch (d logits rows are ldl floats apart)
       COMIC_REQUIRE(nparts <= L.maploss_partials_cap(), "train_step: map-loss scratch too small");
       RC(comic_xent_maploss(io.logits_tb, io.targets_bt, io.coef_bt, io.wmask_bt, io.lens, io.loss_rows, L.dlogits, pl.ldl,
                             io.ids_tb, Tp, T, B, V, pl.attn_hist, L.dmap, L.maploss_partials(), io.map_loss, L.loss_ticket(), H, M,
@@ -1199,8 +1205,9 @@ struct TeacherForcedStep {
       (void)hipMemcpyAsync(io.ids_tb + (size_t)t * B, io.ids_tb + (size_t)(Tp - 1) * B, sizeof(int32_t) * B,
                            hipMemcpyDeviceToDevice, st);
       RC(fill(io.loss_rows + (size_t)t * B, 0.f, B, st));
+      if (soft && soft->nll_rows) RC(fill(soft->nll_rows + (size_t)t * B, 0.f, B, st));
     }
-    if (!pl.grp) {
+    if (!pl.grp || soft) {
       float* partial = L.maploss_partials();
       COMIC_REQUIRE(nparts <= L.maploss_partials_cap(), "train_step: map-loss scratch too small");
       hipLaunchKernelGGL(maploss_part_kernel, dim3(nparts), dim3(256), 0, st, (const float*)pl.attn_hist, L.dmap, partial, Tp, B,
@@ -1519,6 +1526,40 @@ extern "C" int64_t comic_decoder_train_workspace(const comic_decoder_desc* d, in
   return (int64_t)L.bytes;
 }
 
+extern "C" int comic_decoder_train_step_soft(const comic_decoder_desc* d, const comic_decoder_params* p,
+                                             const comic_decoder_params* gr, const float* fm, const float* im_embed,
+                                             const int32_t* inputs_bt, const int32_t* targets_bt, const float* wmask_bt,
+                                             const float* coef_bt, const int32_t* lens, int B, int T, int Tp,
+                                             const float* mask_init_in, const float* mask_in, const float* mask_out,
+                                             const float* mask_alpha, float* logits_tb, int32_t* ids_tb, float* attn_hist,
+                                             float* loss_rows, float* map_loss, float* dfm, float* dim_embed,
+                                             void* workspace, int64_t workspace_bytes, void* stream,
+                                             const comic_soft_targets* soft) {
+  if (soft) {           // refused before anything is launched
+    COMIC_REQUIRE(d, "train_step_soft: null descriptor");
+    COMIC_REQUIRE(soft->smoothing >= 0.f && soft->smoothing < 1.f, "train_step_soft: smoothing %g outside [0, 1)",
+                  (double)soft->smoothing);
+    COMIC_REQUIRE(soft->teacher_weight >= 0.f && soft->teacher_weight <= 1.f, "train_step_soft: teacher_weight %g outside [0, 1]",
+                  (double)soft->teacher_weight);
+    COMIC_REQUIRE(soft->smoothing + soft->teacher_weight <= 1.f, "train_step_soft: smoothing + teacher_weight = %g exceeds 1",
+                  (double)(soft->smoothing + soft->teacher_weight));
+    if (soft->teacher_weight > 0.f) {
+      COMIC_REQUIRE(soft->ids_tbk && soft->probs_tbk, "train_step_soft: teacher_weight %g without a teacher table",
+                    (double)soft->teacher_weight);
+      COMIC_REQUIRE(soft->K >= 1 && soft->K <= COMIC_SOFT_MAX_K && soft->K <= d->V,
+                    "train_step_soft: K %d outside [1, min(%d, V)]", soft->K, COMIC_SOFT_MAX_K);
+    }
+  }
+  StepIO io{};
+  io.soft = soft;
+  io.fm = fm; io.im_embed = im_embed; io.inputs_bt = inputs_bt; io.targets_bt = targets_bt; io.wmask_bt = wmask_bt;
+  io.coef_bt = coef_bt; io.lens = lens; io.B = B; io.T = T; io.Tp = Tp;
+  io.mask_init_in = mask_init_in; io.mask_in = mask_in; io.mask_out = mask_out; io.mask_alpha = mask_alpha;
+  io.logits_tb = logits_tb; io.ids_tb = ids_tb; io.attn_hist = attn_hist; io.loss_rows = loss_rows; io.map_loss = map_loss;
+  io.dfm = dfm; io.dim_embed = dim_embed; io.workspace = workspace; io.workspace_bytes = workspace_bytes;
+  return teacher_forced_step(d, p, gr, io, stream);
+}
+
 extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic_decoder_params* p,
                                         const comic_decoder_params* gr, const float* fm, const float* im_embed,
                                         const int32_t* inputs_bt, const int32_t* targets_bt, const float* wmask_bt,
@@ -1527,13 +1568,9 @@ extern "C" int comic_decoder_train_step(const comic_decoder_desc* d, const comic
                                         const float* mask_alpha, float* logits_tb, int32_t* ids_tb, float* attn_hist,
                                         float* loss_rows, float* map_loss, float* dfm, float* dim_embed,
                                         void* workspace, int64_t workspace_bytes, void* stream) {
-  StepIO io{};
-  io.fm = fm; io.im_embed = im_embed; io.inputs_bt = inputs_bt; io.targets_bt = targets_bt; io.wmask_bt = wmask_bt;
-  io.coef_bt = coef_bt; io.lens = lens; io.B = B; io.T = T; io.Tp = Tp;
-  io.mask_init_in = mask_init_in; io.mask_in = mask_in; io.mask_out = mask_out; io.mask_alpha = mask_alpha;
-  io.logits_tb = logits_tb; io.ids_tb = ids_tb; io.attn_hist = attn_hist; io.loss_rows = loss_rows; io.map_loss = map_loss;
-  io.dfm = dfm; io.dim_embed = dim_embed; io.workspace = workspace; io.workspace_bytes = workspace_bytes;
-  return teacher_forced_step(d, p, gr, io, stream);
+  return comic_decoder_train_step_soft(d, p, gr, fm, im_embed, inputs_bt, targets_bt, wmask_bt, coef_bt, lens, B, T, Tp,
+                                       mask_init_in, mask_in, mask_out, mask_alpha, logits_tb, ids_tb, attn_hist, loss_rows,
+                                       map_loss, dfm, dim_embed, workspace, workspace_bytes, stream, nullptr);
 }
 
 // the scoring layout (the caller takes no alignment history: the workspace holds it), with the flags that select the

@@ -23,6 +23,12 @@ int comic_xent_maploss(float* logits, const int32_t* targets_bt, const float* co
                        const int32_t* lens, float* loss_rows, float* dlogits, int ld_dl, int32_t* ids_tb, int t_rows,
                        int t_stride, int B, int V, const float* hist, float* dmap, float* partial, float* map_loss,
                        unsigned* ticket, int H, int M, float scale, hipStream_t st);
+// xent_soft.hip: the sequence loss against soft targets (row stride ld_dl of d logits; a null table with
+// teacher_weight 0 is label smoothing alone)
+int comic_xent_soft_ex(float* logits, const int32_t* targets_bt, const float* coef_bt, const float* wmask_bt,
+                       const int32_t* lens, float* loss_rows, float* nll_rows, float* dlogits, int ld_dl, int32_t* ids_tb,
+                       int t_rows, int t_stride, int B, int V, float smoothing, float teacher_weight, int K,
+                       const int32_t* ids_tbk, const float* probs_tbk, hipStream_t st);
 int comic_attn_fwd_ex(const comic_attn_desc* d, const float* keys, const float* values, const float* q,
                       const float* ln_g, const float* ln_b, const float* v, const float* tau, const float* mask_alpha,
                       float keep_alpha, float* alpha, float* alpha_d, float* ctx, const int32_t* lens, int t,

@@ -1492,6 +1492,91 @@ def decode_dir_suffix(c):
             + consensus_dir_suffix(c) + required_dir_suffix(c) + prefix_dir_suffix(c))
 
 
+TEACHER_LDS_BYTES = 160 * 1024          # comic_teacher_topk holds a row of V probabilities + 2048 bytes of scratch in LDS
+
+
+@dataclass(frozen=True)
+class SoftTargets:
+    """Soft targets of the XE loss as one immutable value (comic_soft_targets): for a token with target y the loss is the
+    cross-entropy H(q, p) against q = (1 - smoothing - teacher_weight) e_y + smoothing / V + teacher_weight q_T, with q_T
+    the renormalised top_k entries of a teacher's mean tempered softmax (Decoder.teacher_targets).  H(q, p), not the KL
+    divergence: they differ by the entropy of q, a constant in the parameters.  The student's temperature is 1 (no
+    temperature^2 factor); `temperature` is the teacher's.  Checked at construction."""
+    smoothing: float = 0.0
+    teacher_weight: float = 0.0
+    top_k: int = 16
+    temperature: float = 1.0
+
+    def __post_init__(self):
+        e, w = self.smoothing, self.teacher_weight
+        for name, x in (('smoothing', e), ('teacher_weight', w), ('temperature', self.temperature)):
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or math.isnan(x):
+                raise ValueError('SoftTargets: %s must be a number, got %r' % (name, x))
+        if not 0.0 <= e < 1.0:
+            raise ValueError('SoftTargets: smoothing must be in [0, 1), got %r' % (e,))
+        if not 0.0 <= w <= 1.0:
+            raise ValueError('SoftTargets: teacher_weight must be in [0, 1], got %r' % (w,))
+        if e + w > 1.0:
+            raise ValueError('SoftTargets: smoothing + teacher_weight must not exceed 1, got %r' % (e + w,))
+        if isinstance(self.top_k, bool) or not isinstance(self.top_k, int) or not 1 <= self.top_k <= L.SOFT_MAX_K:
+            raise ValueError('SoftTargets: top_k must be an integer in [1, %d], got %r' % (L.SOFT_MAX_K, self.top_k))
+        if not 0.0 < self.temperature < math.inf:
+            raise ValueError('SoftTargets: temperature must be in (0, inf), got %r' % (self.temperature,))
+
+    @property
+    def active(self):
+        return self.smoothing > 0.0 or self.teacher_weight > 0.0
+
+    @property
+    def distils(self):
+        return self.teacher_weight > 0.0
+
+    def ctx_key(self):
+        """What a captured training graph bakes in: the two weights as the fp32 values the kernel sees, and K when a table
+        is read.  Not the table's contents (copied in front of every launch) nor the teacher's temperature."""
+        return (float(np.float32(self.smoothing)), float(np.float32(self.teacher_weight)),
+                self.top_k if self.distils else 0)
+
+    def check_vocabulary(self, V):
+        if self.distils and self.top_k > V:
+            raise ValueError('SoftTargets: top_k %d exceeds the vocabulary size %d' % (self.top_k, V))
+
+
+def soft_targets_from_config(c):
+    """The SoftTargets a configuration asks for (label_smoothing, distill_*), or None when every field is at its default."""
+    eps = float(getattr(c, 'label_smoothing', 0.0) or 0.0)
+    lam = float(getattr(c, 'distill_weight', 0.0) or 0.0) if getattr(c, 'distill_checkpoints', None) else 0.0
+    if eps == 0.0 and lam == 0.0:
+        return None
+    k, tau = getattr(c, 'distill_top_k', None), getattr(c, 'distill_temperature', None)
+    return SoftTargets(eps, lam, 16 if k is None else int(k), 1.0 if tau is None else float(tau))
+
+
+def teacher_table(members, weights, fm, im_embed, captions, top_k, temperature):
+    """ids, probs [T,B,K] of the members' weighted mean tempered softmax (comic_teacher_topk): every member runs the
+    forward-only phase of its own executor on the same features and captions, then ONE launch covers their logits.
+    Nothing is synchronised; the tables are persistent per shape on the first member (valid until its next call)."""
+    first = members[0]
+    torch, V = first.torch, first.spec.V
+    SoftTargets(0.0, 1.0, top_k, temperature).check_vocabulary(V)          # K and the temperature, before any launch
+    if V * 4 + 2048 > TEACHER_LDS_BYTES:
+        raise ValueError('teacher_targets: a row of V = %d probabilities does not fit the %d bytes of LDS (V <= %d)'
+                         % (V, TEACHER_LDS_BYTES, (TEACHER_LDS_BYTES - 2048) // 4))
+    ctxs = [m._forward_logits(fm, im_embed, captions) for m in members]
+    B, T, Tp = ctxs[0].key[:3]
+    tabs = first.__dict__.setdefault('_teacher_tabs', {})
+    tab = tabs.get((B, T, top_k))
+    if tab is None:
+        tab = tabs[(B, T, top_k)] = (torch.zeros((T, B, top_k), dtype=torch.int32, device=first.device),
+                                     torch.zeros((T, B, top_k), dtype=torch.float32, device=first.device))
+    n = len(members)
+    ptrs = (C.c_void_p * n)(*[c.logits.data_ptr() for c in ctxs])
+    w = (C.c_float * n)(*weights)
+    L.check(first.lib.comic_teacher_topk(ptrs, w, n, ctxs[0].i32.data_ptr() + 8 * B * T, B, T, Tp, V, float(temperature),
+                                         int(top_k), tab[0].data_ptr(), tab[1].data_ptr(), L.stream_ptr()), 'teacher_topk')
+    return tab
+
+
 def process_inputs(captions, token_type):
     """ModelBase._process_inputs (model_base.py:501-528) on the host.
     -> inputs [B,T] int32, targets [B,T] int32, masks [B,T] fp32, lens [B] int32."""
@@ -1557,9 +1642,12 @@ class Decoder:
         return out
 
     # ------------------------------------------------------------------ training -------
-    def _train_ctx(self, B, T, Tp, training, gen_masks, want_input_grads):
-        """Persistent device buffers (+ hipGraph) of one training-step shape."""
+    def _train_ctx(self, B, T, Tp, training, gen_masks, want_input_grads, soft=None):
+        """Persistent device buffers (+ hipGraph) of one training-step shape; `soft` (an active SoftTargets) keys a context
+        of its own, whose graph holds the record's scalars."""
         key = (B, T, Tp, bool(training), bool(gen_masks), bool(want_input_grads))
+        if soft is not None:
+            key += (soft.ctx_key(),)
         ctx = self._ctx.get(key)
         if ctx is not None:
             return ctx
@@ -1612,8 +1700,34 @@ class Decoder:
         ctx.desc = s.desc(training)
         ctx.nbytes = self.lib.comic_decoder_train_workspace(C.byref(ctx.desc), B, T)
         ctx.ws = torch.empty(int(ctx.nbytes), dtype=torch.uint8, device=dev)
+        ctx.soft = None
+        if soft is not None:    # the record, the hard-loss rows and the step's own copy of the teacher's table
+            K = soft.top_k
+            ctx.nll_rows = torch.zeros(T * B, **f32)
+            ctx.nll = torch.zeros(1, **f32)
+            ctx.t_ids = torch.zeros((T, B, K), dtype=torch.int32, device=dev) if soft.distils else None
+            ctx.t_probs = torch.zeros((T, B, K), **f32) if soft.distils else None
+            ctx.soft = L.SoftTargets(soft.smoothing, soft.teacher_weight, K if soft.distils else 0, L.ptr(ctx.t_ids),
+                                     L.ptr(ctx.t_probs), ctx.nll_rows.data_ptr())
         self._ctx[key] = ctx
         return ctx
+
+    def _stage_teacher(self, ctx, soft, teacher):
+        """The teacher's table of this step into the context's own (a captured graph holds addresses), on the stream."""
+        if soft is None or not soft.distils:
+            return
+        torch = self.torch
+        if teacher is None:
+            raise ValueError('train_step: teacher_weight %g without a teacher table (teacher=(ids, probs))'
+                             % soft.teacher_weight)
+        ids, probs = teacher
+        want = tuple(ctx.t_ids.shape)
+        if (not torch.is_tensor(ids) or not torch.is_tensor(probs) or tuple(ids.shape) != want or tuple(probs.shape) != want
+                or ids.dtype != torch.int32 or probs.dtype != torch.float32 or not ids.is_cuda or not probs.is_cuda):
+            raise ValueError('train_step: teacher must be device tensors (ids int32, probs float32) of shape [T, B, K] = %r'
+                             % (want,))
+        ctx.t_ids.copy_(ids)
+        ctx.t_probs.copy_(probs)
 
     def voided_steps(self):
         """Training steps the device voided so far (a bounded wait of a persistent loop expired: NaN loss, no update;
@@ -1631,7 +1745,7 @@ class Decoder:
         """Device-only part of a training step (no host sync, no host memcpy): capturable.
         phase 'fwd' / 'bwd': the forward to the logits / the loss and the backward (COMIC_DEC_PHASE_*)."""
         torch, s = self.torch, self.spec
-        B, T, Tp, training, gen_masks, _ = ctx.key
+        B, T, Tp, training, gen_masks = ctx.key[:5]
         st = L.stream_ptr()
         m = ctx.masks or {}
         if training and gen_masks and phase != 'bwd':
@@ -1652,23 +1766,28 @@ class Decoder:
         ptab, gtab = self.params.table(), self.grads.table()
         ctx.desc.flags = (L.decoder_flags_from_env() | {None: 0, 'fwd': L.DEC_PHASE_FWD, 'bwd': L.DEC_PHASE_BWD}[phase]
                           | (L.DEC_INJECT_TIMEOUT if ctx.__dict__.pop('inject_timeout', False) else 0))
-        L.check(self.lib.comic_decoder_train_step(
-            C.byref(ctx.desc), C.byref(ptab), C.byref(gtab), ctx.fm_in.data_ptr(), ctx.im_in.data_ptr(),
-            i32.data_ptr(), i32.data_ptr() + 4 * BT, f32.data_ptr(), f32.data_ptr() + 4 * BT,
-            i32.data_ptr() + 8 * BT, B, T, Tp,
-            L.ptr(m.get('init_in')), L.ptr(m.get('inp')), L.ptr(m.get('out')), L.ptr(m.get('alpha')),
-            ctx.logits.data_ptr(), ctx.ids.data_ptr(), ctx.hist.data_ptr(), ctx.loss_rows.data_ptr(),
-            ctx.map_loss.data_ptr(), L.ptr(ctx.dfm), L.ptr(ctx.dim), ctx.ws.data_ptr(), ctx.nbytes, st),
-            'decoder_train_step')
+        args = (C.byref(ctx.desc), C.byref(ptab), C.byref(gtab), ctx.fm_in.data_ptr(), ctx.im_in.data_ptr(),
+                i32.data_ptr(), i32.data_ptr() + 4 * BT, f32.data_ptr(), f32.data_ptr() + 4 * BT,
+                i32.data_ptr() + 8 * BT, B, T, Tp,
+                L.ptr(m.get('init_in')), L.ptr(m.get('inp')), L.ptr(m.get('out')), L.ptr(m.get('alpha')),
+                ctx.logits.data_ptr(), ctx.ids.data_ptr(), ctx.hist.data_ptr(), ctx.loss_rows.data_ptr(),
+                ctx.map_loss.data_ptr(), L.ptr(ctx.dfm), L.ptr(ctx.dim), ctx.ws.data_ptr(), ctx.nbytes, st)
+        if ctx.soft is None:
+            L.check(self.lib.comic_decoder_train_step(*args), 'decoder_train_step')
+        else:
+            L.check(self.lib.comic_decoder_train_step_soft(*args, C.byref(ctx.soft)), 'decoder_train_step_soft')
         if phase == 'fwd':
             return
         # sequence_loss reduction (model_base.py:337-347): rows carry xent*w; rs = 1/denominator (* reward/B)
         L.check(self.lib.comic_weighted_sum_tb(ctx.loss_rows.data_ptr(), f32.data_ptr() + 4 * 2 * BT, T, B,
                                                ctx.loss.data_ptr(), st), 'weighted_sum_tb')
+        if ctx.soft is not None:            # the hard loss beside the optimised one, by the same reduction
+            L.check(self.lib.comic_weighted_sum_tb(ctx.nll_rows.data_ptr(), f32.data_ptr() + 4 * 2 * BT, T, B,
+                                                   ctx.nll.data_ptr(), st), 'weighted_sum_tb')
 
     def train_step(self, fm, im_embed, captions, masks=None, rewards=None, training=True, seed=None,
                    want_input_grads=False, xe_denom=None, use_graph=False, on_inputs_consumed=None, dp=None,
-                   copy_inputs=True, phase=None, inject_timeout=False):
+                   copy_inputs=True, phase=None, inject_timeout=False, soft=None, teacher=None):
         """One teacher-forced forward + backward.  `captions` [B,L] int (PAD = -1).
         phase: None = the whole step.  'fwd' = everything no loss coefficient enters (forward to the logits; `rewards` is
         ignored) and 'bwd' = the rest, with the SAME captions and now the rewards: the SCST step enqueues 'fwd' as soon as
@@ -1690,9 +1809,21 @@ class Decoder:
         called after the step's launches rather than before them.  Ignored with use_graph (a graph holds addresses).
         use_graph: replay the step from a hipGraph captured per (B, T, T') shape (the second call with
         a shape captures it) -- removes the ~450 host launches of a step from the critical path.
-        Returns dict(loss, map_loss, logits [B,T,V], ids [B,T], attn_maps [B,H,T',M]) (device views
+        soft: a SoftTargets -> the loss is the cross-entropy against its soft targets (label smoothing, and with
+        teacher_weight > 0 the `teacher` table (ids, probs), device tensors [T,B,K] of teacher_targets); one launch of the
+        step changes (csrc/xent_soft.hip), `loss` is the optimised soft loss and `nll` the hard one.  None, an inactive
+        record or training=False: the step of always.  With `rewards` a ValueError: soft targets are XE training.
+        Returns dict(loss, nll, map_loss, logits [B,T,V], ids [B,T], attn_maps [B,H,T',M]) (device views
         of persistent buffers: valid until the next call with the same shape)."""
         torch, s = self.torch, self.spec
+        soft = _active(soft) if training else None
+        if soft is not None:
+            if rewards is not None:
+                raise ValueError('train_step: soft targets and SCST rewards do not combine')
+            soft.check_vocabulary(s.V)
+            if soft.distils and teacher is None and phase != 'fwd':
+                raise ValueError('train_step: teacher_weight %g without a teacher table (teacher=(ids, probs))'
+                                 % soft.teacher_weight)
         inputs, targets, wmask, lens = process_inputs(captions, s.token_type)
         B, T = inputs.shape
         Tp = int(lens.max())
@@ -1716,8 +1847,15 @@ class Decoder:
             coef = wmask / den * rb
         gen_masks = bool(training and masks is None)
         use_masks = bool(training or masks is not None)
-        ctx = self._train_ctx(B, T, Tp, use_masks, gen_masks, want_input_grads)
+        ctx = self._train_ctx(B, T, Tp, use_masks, gen_masks, want_input_grads, soft)
         BT = B * T
+
+        def result():
+            return dict(loss=ctx.loss[0], nll=(ctx.loss if ctx.soft is None else ctx.nll)[0], map_loss=ctx.map_loss[0],
+                        logits=ctx.logits.permute(1, 0, 2), ids=ctx.ids.t(), attn_maps=ctx.hist.permute(1, 2, 0, 3),
+                        dfm=ctx.dfm, dim_embed=ctx.dim, Tp=Tp)
+        if phase != 'fwd':
+            self._stage_teacher(ctx, soft, teacher)
         if phase == 'bwd':          # second call of a split step: only the coefficients are new
             assert getattr(ctx, 'split_open', False), 'train_step(phase="bwd") without its phase="fwd" call'
             ctx.split_open = False
@@ -1731,8 +1869,7 @@ class Decoder:
                 ctx.stage_dev.copy_(slot.buf, non_blocking=True)
                 slot.copied.record(torch.cuda.current_stream())
             self._run_train_phase(ctx, 'bwd', use_graph)
-            return dict(loss=ctx.loss[0], map_loss=ctx.map_loss[0], logits=ctx.logits.permute(1, 0, 2), ids=ctx.ids.t(),
-                        attn_maps=ctx.hist.permute(1, 2, 0, 3), dfm=ctx.dfm, dim_embed=ctx.dim, Tp=Tp)
+            return result()
         slot = ctx.stage[ctx.calls % 2]
         if slot.copied is not None:
             slot.copied.synchronize()
@@ -1791,8 +1928,19 @@ class Decoder:
         if direct and on_inputs_consumed is not None:   # stream order: whatever the caller enqueues now runs after the step
             on_inputs_consumed()
         ctx.calls += 1
-        return dict(loss=ctx.loss[0], map_loss=ctx.map_loss[0], logits=ctx.logits.permute(1, 0, 2), ids=ctx.ids.t(),
-                    attn_maps=ctx.hist.permute(1, 2, 0, 3), dfm=ctx.dfm, dim_embed=ctx.dim, Tp=Tp)
+        return result()
+
+    def _forward_logits(self, fm, im_embed, captions):
+        """The forward-only phase of this decoder's executor without dropout (phase='fwd', training=False, the call the
+        SCST step makes): -> the context whose .logits [T,B,V] hold rows t < T' and whose staging block holds lens."""
+        self.train_step(fm, im_embed, captions, training=False, phase='fwd')
+        inputs, _, _, lens = process_inputs(captions, self.spec.token_type)
+        return self._train_ctx(inputs.shape[0], inputs.shape[1], int(lens.max()), False, False, False)
+
+    def teacher_targets(self, fm, im_embed, captions, top_k=16, temperature=1.0):
+        """This decoder as a teacher: ids, probs [T,B,top_k] (int32, float32 device tensors) of its tempered softmax on the
+        captions' teacher-forced rows, for train_step(soft=, teacher=) of a student (teacher_table)."""
+        return teacher_table([self], [1.0], fm, im_embed, captions, top_k, temperature)
 
     def _device_coefficients(self, ctx, rewards):
         """coef and rs of the device staging block from its mask and the device rewards [B] (comic_scst_coefficients):
@@ -2270,6 +2418,12 @@ class EnsembleDecoder:
         self.spec = decoders[0].spec
         self.torch, self.lib, self.device = decoders[0].torch, decoders[0].lib, decoders[0].device
         self._ctxs = {}
+
+    def teacher_targets(self, fm, im_embed, captions, top_k=16, temperature=1.0, weights=None):
+        """The ensemble as a teacher: ids, probs [T,B,top_k] of the members' weighted mean tempered softmax on the captions'
+        teacher-forced rows (teacher_table); every member reads the same fm / im_embed.  weights: the ensemble's, or these."""
+        w = self.weights if weights is None else check_ensemble([d.spec for d in self.decoders], weights)
+        return teacher_table(self.decoders, w, fm, im_embed, captions, top_k, temperature)
 
     def _ctx(self, B, W, max_steps, feats, opts):
         """Persistent buffers (+ a hipGraph of the whole loop, captured on the second call with the shape), as

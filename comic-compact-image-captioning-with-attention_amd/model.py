@@ -601,7 +601,7 @@ class CaptionModel(ModelBase):
         self._build(bs, device, dp)
         if self.is_training():
             self._create_optimiser()
-        self.dec_log_ppl = None
+        self.dec_log_ppl = self.dec_nll = None
         print('INFO: Model `{}` initialisation complete.'.format(mode))
 
     # ---- frozen-CNN pipelining (decoder mode): trainer.EncoderPipeline behind the reference API -------------
@@ -656,6 +656,21 @@ class CaptionModel(ModelBase):
                 self._submit_group()
         return im_embed, fm, self._cap_queue.popleft(), consumed
 
+    def _soft_targets(self, fm, im_embed, captions):
+        """(SoftTargets, teacher table) of this step from config.label_smoothing / config.distill_*, or (None, None): the
+        record is built once, the teacher decoder(s) are restored at the first step, and the table is computed on this
+        stream from the SAME fm / im_embed / captions, in front of the student's step (which may release the features)."""
+        if '_soft' not in self.__dict__:
+            self._soft = cdec.soft_targets_from_config(self._config)
+            self._teacher = None
+            if self._soft is not None and self._soft.distils:
+                from . import distill
+                self._teacher = distill.load_teachers(self._config, self.spec, self.device)
+        soft = self._soft
+        if soft is None or not soft.distils:
+            return soft, None
+        return soft, self._teacher.teacher_targets(fm, im_embed, captions, soft.top_k, soft.temperature)
+
     def run_train_step(self, batch=None):
         """== sess.run(m_train.dec_log_ppl): one XE update (train_fn.py:120-121).  With a frozen CNN and batches
         drawn from the input pipeline the encoder forward of the NEXT step(s) runs on a second stream under this
@@ -671,9 +686,11 @@ class CaptionModel(ModelBase):
         lr = self.lr
         ft = self.cnn_trainable
         want_in = ft or self.head is not None
+        soft, table = self._soft_targets(fm, im_embed, cap)
         res = self.decoder.train_step(fm, im_embed, cap, training=True, dp=self.dp, use_graph=not want_in,
                                       want_input_grads=want_in, on_inputs_consumed=consumed,
-                                      copy_inputs=consumed is None)
+                                      copy_inputs=consumed is None, soft=soft, teacher=table)
+        self.dec_nll = res['nll'] if soft is not None else None     # the hard loss beside the optimised one (soft runs)
         self._dec_reduced = False
         if ft:
             self._cnn_update(res, lr)

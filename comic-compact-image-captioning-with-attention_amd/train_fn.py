@@ -55,6 +55,9 @@ def _train_loop(inputs_man, device, dp):
     num_batches = int(c.split_sizes['train'] / (c.batch_size_train * max(1, int(getattr(c, 'dp_world', 1) or 1))))   # global batches
     lr = c.lr_start
     n_steps_log = int(num_batches / c.num_logs_per_epoch)
+    if getattr(c, 'distill_checkpoints', None):        # the teachers against the full configuration (the vocabulary is known now)
+        from . import distill
+        distill.check_teachers(c)
     m_train = mdl.CaptionModel(c, mode='train', batch_ops=inputs_man.batch_train, reuse=False, name='train',
                                device=device, dp=dp)
     m_train.dset_size = c.split_sizes['train']
@@ -83,6 +86,8 @@ def _train_loop(inputs_man, device, dp):
             _check_loss(ppl, global_step, m_train, dp)
             logstr = 'Epoch {:2d} ~~ {:6.2f} %  ~  '.format(epoch, ((step % num_batches) + 1) / num_batches * 100)
             logstr += 'Perplexity {:8.4f} ~ LR {:5.3e} ~ '.format(float(np.exp(float(ppl))), m_train.lr)
+            if m_train.dec_nll is not None:         # soft targets: the hard loss beside the optimised one
+                logstr += 'dec_nll {:8.4f} ~ '.format(float(m_train.dec_nll))
             logstr += 'Step {}'.format(global_step)
             print('   ' + logstr)
         if num_batches > 5000:

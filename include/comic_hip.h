@@ -942,6 +942,63 @@ int comic_decoder_train_step(const comic_decoder_desc* d, const comic_decoder_pa
                              float* map_loss, float* dfm, float* dim_embed, void* workspace,
                              int64_t workspace_bytes, void* stream);
 
+/* Soft-target XE training: label smoothing and distillation from a teacher's top-K table.  For a live token row with
+ * logits z, p = softmax(z), target y, eps = smoothing in [0, 1), lam = teacher_weight in [0, 1], eps + lam <= 1:
+ *   q_T(v)    = sum_k [ids_k = v] probs_k / S,  S = sum_k probs_k    (the table holds raw probabilities; the loss
+ *                                                                      renormalises the kept mass)
+ *   q         = (1 - eps - lam) e_y + eps / V + lam q_T
+ *   loss_rows = wmask (lse(z) - sum_v q_v z_v)     the cross-entropy H(q, p), NOT the KL divergence: they differ by the
+ *                                                  entropy of q, a constant in the parameters
+ *   nll_rows  = wmask (lse(z) - z_y)               the hard loss, so that logged perplexities stay comparable
+ *   dlogits   = (p - q) coef                       (the student's temperature is 1; no tau^2 factor)
+ * Rows with t >= lens[b], the arg-max ids, coef and wmask: as in comic_xent_fwd_bwd.  The ids of a table row are
+ * distinct and in [0, V), its probs >= 0 with S > 0 on live rows; rows past lens are never read.
+ *   ids_tbk / probs_tbk [T,B,K] (device; both NULL with teacher_weight 0: label smoothing alone), 1 <= K <= min(32, V);
+ *   nll_rows [T*B] (device) or NULL. */
+#define COMIC_SOFT_MAX_K 32
+typedef struct comic_soft_targets {
+  float smoothing;
+  float teacher_weight;
+  int K;
+  const int32_t* ids_tbk;
+  const float* probs_tbk;
+  float* nll_rows;
+} comic_soft_targets;
+
+/* comic_decoder_train_step against soft targets.  soft == NULL IS comic_decoder_train_step: the same launches, the same
+ * bits.  With a record, the ONE launch between the logits product and the backward is the soft loss (csrc/xent_soft.hip)
+ * and, where the map loss rode on that launch, its two own launches follow (the partial sums and their combination in
+ * piece order: the bits of the fused form); everything else of the step is unchanged.  With COMIC_DEC_PHASE_FWD /
+ * _BWD the record matters in the BWD call only.  The coefficients must be the XE step's: soft targets and SCST
+ * rewards do not combine. */
+int comic_decoder_train_step_soft(const comic_decoder_desc* d, const comic_decoder_params* p,
+                                  const comic_decoder_params* grads, const float* fm,
+                                  const float* im_embed, const int32_t* inputs_bt,
+                                  const int32_t* targets_bt, const float* wmask_bt, const float* coef_bt,
+                                  const int32_t* lens, int B, int T, int Tp, const float* mask_init_in,
+                                  const float* mask_in, const float* mask_out, const float* mask_alpha,
+                                  float* logits_tb, int32_t* ids_tb, float* attn_hist, float* loss_rows,
+                                  float* map_loss, float* dfm, float* dim_embed, void* workspace,
+                                  int64_t workspace_bytes, void* stream, const comic_soft_targets* soft);
+
+/* The soft loss alone, on its own operands (the launch of comic_decoder_train_step_soft): logits [t_stride,B,V] of
+ * which t_rows steps are live, the [B,t_stride] tables of comic_xent_fwd_bwd, d logits rows ld_dl >= V floats apart
+ * (columns V .. ld_dl-1 are written as zeros). */
+int comic_xent_soft(float* logits, const int32_t* targets_bt, const float* coef_bt, const float* wmask_bt,
+                    const int32_t* lens, float* loss_rows, float* nll_rows, float* dlogits, int ld_dl,
+                    int32_t* ids_tb, int t_rows, int t_stride, int B, int V, float smoothing, float teacher_weight,
+                    int K, const int32_t* ids_tbk, const float* probs_tbk, void* stream);
+
+/* The teacher's table: for every live row (t < Tp and t < lens[b]) of n <= 8 members' time-major logits [T,B,V],
+ *   pbar(v) = sum_m weights[m] softmax(z_m / temperature)(v),
+ * the K largest pbar ordered by (pbar descending, id ascending) -- ties at the boundary go to the lowest id -- as
+ * ids [T,B,K] and probs [T,B,K] = those pbar values.  Other rows get ids 0 .. K-1 and probs 0.  logits and weights are
+ * HOST arrays of n entries (device pointers / weights >= 0 summing to 1); 1 <= K <= min(32, V); temperature in (0, inf).
+ * One workgroup per row holds pbar in LDS: V * 4 + 2048 bytes must fit 160 KB (V <= 40448), a larger V is refused.  No
+ * atomics, fixed summation orders: two runs give the same bits. */
+int comic_teacher_topk(const float* const* logits, const float* weights, int n, const int32_t* lens, int B, int T, int Tp,
+                       int V, float temperature, int K, int32_t* ids, float* probs, void* stream);
+
 /* Which form of the time loops the LAST comic_decoder_train_step of this thread used: bit 0 = forward loop as one
  * persistent launch (csrc/decoder_persist.hip), bit 1 = backward loop as one persistent launch
  * (csrc/decoder_persist_bwd.hip); 0 = per-step launches.  The choice depends on the shape (D = 512, B <= 64, ...), the

@@ -2,7 +2,8 @@
 """train.py -- same flags, mode chaining, run-directory naming and kwargs as the reference
 CLI (reference src/train.py:25-312), driving the MI355X-native path.
 
-Differences (all additive): `--cnn_dtype {bf16,f16,f32,bf16x3}`, `--checkpoint_format {npz,tf}`, `--ema_decay`; launched under
+Differences (all additive): `--cnn_dtype {bf16,f16,f32,bf16x3}`, `--checkpoint_format {npz,tf}`, `--ema_decay`, `--label_smoothing`,
+`--distill_checkpoints / _weight / _top_k / _temperature / _weights`; launched under
 `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel (one process
 per GPU, RCCL gradient all-reduce); the slim checkpoint is not downloaded (no network):
 pass `--checkpoint_path` (an .npz with slim variable names) or train the CNN from random init.
@@ -103,6 +104,17 @@ def create_parser():
       help='Keep an exponential moving average of every trained variable (tf.train.ExponentialMovingAverage with '
            'num_updates: decay min(d, (1 + n) / (10 + n))), updated inside the optimiser launch; `model_ema-N` is written '
            'beside `model_compact-N` (infer.py / score.py --infer_ema).  0 = off, else in (0, 1).')
+    a('--label_smoothing', type=float, default=0.0,
+      help='Label smoothing of the XE loss (decoder / cnn_finetune): this share of every target is spread uniformly over the '
+           'vocabulary.  0 = off, else in (0, 1).')
+    a('--distill_checkpoints', type=str, default='',
+      help='Distil teacher checkpoint(s) into this model (--train_mode decoder): p1[,p2...], `model_compact-N` / `model_ema-N` '
+           'paths, each with the config.pkl of its run beside it; several teach as an ensemble.')
+    a('--distill_weight', type=float, default=0.0,
+      help='Share of every target taken from the teacher, in (0, 1]; label_smoothing + distill_weight <= 1.')
+    a('--distill_top_k', type=int, default=16, help='Entries of the teacher distribution kept per token (1 ... 32).')
+    a('--distill_temperature', type=float, default=1.0, help='Temperature of the teacher softmax.')
+    a('--distill_weights', type=str, default='', help='Weights w1,... of several teachers (>= 0, summing to 1; default uniform).')
     return p
 
 
@@ -129,12 +141,15 @@ def build_kwargs(args):
                      'h{}'.format(args.attn_num_heads), args.cnn_fm_projection[:3], args.name])
     if args.legacy:
         name = 'legacy_' + name
-    dec_dir = pjoin(log_root, '{}_run_{:02d}'.format(name, args.run))
-    cnnft_dir = pjoin(log_root, '{}_cnnFT_run_{:02d}'.format(name, args.run))
+    # a soft-target run gets a directory of its own: `_ls<eps>` for both XE modes (cnn_finetune continues the decoder run
+    # of the same --label_smoothing), `_kd<weight>_k<K>_t<temperature>` for a distilled decoder run
+    smooth, distil = soft_dir_suffixes(args)
+    dec_dir = pjoin(log_root, '{}{}_run_{:02d}'.format(name, smooth, args.run))
+    cnnft_dir = pjoin(log_root, '{}{}_cnnFT_run_{:02d}'.format(name, smooth, args.run))
     train_fn_name = 'train_fn'
     if args.train_mode == 'decoder':
         assert args.freeze_scopes == 'Model/encoder/cnn'
-        log_path = dec_dir
+        log_path = pjoin(log_root, '{}{}{}_run_{:02d}'.format(name, smooth, distil, args.run))
     elif args.train_mode == 'cnn_finetune':
         if args.legacy:
             raise NotImplementedError
@@ -167,6 +182,11 @@ def build_kwargs(args):
     kwargs.pop('log_root', None)
     if kwargs.get('ema_decay') == 0:            # off: the configuration of a run without the flag
         kwargs.pop('ema_decay')
+    if not kwargs.get('label_smoothing'):       # likewise the soft-target flags
+        kwargs.pop('label_smoothing', None)
+    if not kwargs.get('distill_checkpoints'):
+        for k in ('distill_checkpoints', 'distill_weight', 'distill_top_k', 'distill_temperature', 'distill_weights'):
+            kwargs.pop(k, None)
     check_supported(kwargs)
     return kwargs, train_fn_name, overwrite
 
@@ -184,6 +204,29 @@ def refuse_bad_ema_decay(ema_decay):
     d = float(ema_decay or 0.0)
     if not 0.0 <= d < 1.0:
         raise ValueError('--ema_decay must be in [0, 1) (0 = off), got {}'.format(ema_decay))
+
+
+def refuse_bad_soft_options(kw):
+    """--label_smoothing / --distill_*: any of them with scst, distillation outside decoder mode, values out of range, and a
+    teacher whose configuration (the config.pkl beside its checkpoint) differs from the student's in the token type, the radix
+    base, the vocabulary size, the CNN, its input size or the attended feature map.  Called before anything touches the GPU."""
+    from comic_amd import distill
+    if not any(kw.get(k) for k in distill.FLAGS):
+        return
+    distill.refuse_bad_soft_options(kw)
+    if kw.get('distill_checkpoints') and 'token_type' in kw:
+        from types import SimpleNamespace
+        distill.check_teachers(SimpleNamespace(**kw))   # (a word / char vocabulary is built later: train_fn checks its size)
+
+
+def soft_dir_suffixes(args):
+    """('_ls0.1', '_kd0.5_k16_t2') for --label_smoothing 0.1 and --distill_weight 0.5 --distill_top_k 16
+    --distill_temperature 2 with --distill_checkpoints; '' for a flag at its default."""
+    smooth = '_ls%g' % args.label_smoothing if getattr(args, 'label_smoothing', 0.0) else ''
+    distil = ''
+    if getattr(args, 'distill_checkpoints', ''):
+        distil = '_kd%g_k%d_t%g' % (args.distill_weight, args.distill_top_k, args.distill_temperature)
+    return smooth, distil
 
 
 def scst_dir_suffix(args):
@@ -229,6 +272,7 @@ def check_supported(kw):
     refuse_unsupported_dtype(kw.get('train_mode'), kw.get('cnn_dtype'))
     refuse_bad_ema_decay(kw.get('ema_decay'))
     refuse_bad_scst_options(kw)
+    refuse_bad_soft_options(kw)
     bad = []
     # --initialiser: `he` / `none` select TensorFlow's default initialiser in the reference (model_base.py:823-831:
     # every value but `xavier` returns None), which for these float variables is glorot_uniform == Xavier-uniform
@@ -242,6 +286,7 @@ def main(argv=None):
     refuse_unsupported_dtype(args.train_mode, args.cnn_dtype)
     refuse_bad_ema_decay(args.ema_decay)
     refuse_bad_scst_options(vars(args))
+    refuse_bad_soft_options(vars(args))
     import torch
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
