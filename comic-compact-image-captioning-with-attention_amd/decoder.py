@@ -1110,15 +1110,20 @@ def _attach_consensus(dec, out, pred, cons, forced_posterior, last_scores, on_de
     out['consensus'], out['consensus_best'] = util.cpu().numpy(), best.cpu().numpy()
 
 
+def _baseline_ids(torch, base, device):
+    """The reward's baseline rollout [T0,B] (a tensor, an array or None) as a contiguous int32 tensor on `device`."""
+    if base is None:
+        return None
+    base = base if torch.is_tensor(base) else torch.from_numpy(np.ascontiguousarray(base, np.int32))
+    return base.to(device=device, dtype=torch.int32).contiguous()
+
+
 def _attach_reward(dec, out, pred, opts):
     """The reward launch of a beam_search on its device `pred` [T, B, W], right after the tree gather and outside the
     captured graph, as the consensus launch; the result gains `reward` [B, W'] float64 and `advantage` [W, B] float32
     (numpy) and keeps the device tensors of all five outputs in `reward_device` for the caller."""
-    base = opts.reward_baseline_ids
-    if base is not None:
-        base = base if dec.torch.is_tensor(base) else dec.torch.from_numpy(np.ascontiguousarray(base, np.int32))
-        base = base.to(device=pred.device, dtype=dec.torch.int32).contiguous()
-    res = scst_reward(dec.lib, dec.torch, pred, opts.reward_refs, opts.reward, base)
+    res = scst_reward(dec.lib, dec.torch, pred, opts.reward_refs, opts.reward,
+                      _baseline_ids(dec.torch, opts.reward_baseline_ids, pred.device))
     out['reward_device'] = res
     out['reward'], out['advantage'] = res['reward'].cpu().numpy(), res['advantage'].cpu().numpy()
 
@@ -1134,6 +1139,14 @@ def _beam_outputs(ctx, torch, device, B, W, max_steps):
     ctx.lengths = torch.empty((B, W), dtype=torch.int64, device=device)
     ctx.finished = torch.empty((B, W), **i32)
     ctx.steps = torch.empty(1, **i32)
+
+
+def _unpenalised_totals(last_scores, lengths, lpw):
+    """The final log-probabilities [B,W] from the last penalised scores: times the length penalty's divisor."""
+    lp = last_scores.copy()
+    if lpw:
+        lp = (lp * (((5.0 + lengths.astype(np.float32)) / 6.0) ** np.float32(lpw))).astype(np.float32)
+    return lp
 
 
 def _beam_result(dec, ctx, B, W, opts, want_attention):
@@ -1155,20 +1168,13 @@ def _beam_result(dec, ctx, B, W, opts, want_attention):
         out['log_probs'] = grp.final_log_probs(out['scores'], out['step_ids'], ln, s.end_id, lpw)
     if smp is not None:                 # the state after the last executed step: a finished chain's carries over
         out['log_probs'] = out['scores'][-1].copy()
-    if rqd is not None:                 # the unpenalised totals: the last scores times the length penalty's divisor
-        lp = out['scores'][-1].copy()
-        if lpw:
-            lp = (lp * (((5.0 + ln.astype(np.float32)) / 6.0) ** np.float32(lpw))).astype(np.float32)
-        out['log_probs'], out['banks'] = lp, rqd.banks
+    if rqd is not None:
+        out['log_probs'], out['banks'] = _unpenalised_totals(out['scores'][-1], ln, lpw), rqd.banks
         out['best_slot'], out['met'] = rqd.result(out['scores'][-1])
-    pfx = getattr(opts, 'prefix', None)
-    if pfx is not None:
-        if 'log_probs' not in out:      # the plain beam: the last scores times the length penalty's divisor
-            lp = out['scores'][-1].copy()
-            if lpw:
-                lp = (lp * (((5.0 + ln.astype(np.float32)) / 6.0) ** np.float32(lpw))).astype(np.float32)
-            out['log_probs'] = lp
-        out['prefix_log_prob'] = pfx.prefix_log_probs(out, lpw, grp, s.end_id)
+    if opts.prefix is not None:
+        if 'log_probs' not in out:      # the plain beam
+            out['log_probs'] = _unpenalised_totals(out['scores'][-1], ln, lpw)
+        out['prefix_log_prob'] = opts.prefix.prefix_log_probs(out, lpw, grp, s.end_id)
     if opts.consensus is not None:
         _attach_consensus(dec, out, pred, opts.consensus, rqd is not None, ctx.scores[T - 1],
                           grp is None and not (rqd is not None and lpw))
@@ -1564,15 +1570,14 @@ def teacher_table(members, weights, fm, im_embed, captions, top_k, temperature):
                          % (V, TEACHER_LDS_BYTES, (TEACHER_LDS_BYTES - 2048) // 4))
     ctxs = [m._forward_logits(fm, im_embed, captions) for m in members]
     B, T, Tp = ctxs[0].key[:3]
-    tabs = first.__dict__.setdefault('_teacher_tabs', {})
-    tab = tabs.get((B, T, top_k))
+    tab = first._teacher_tabs.get((B, T, top_k))
     if tab is None:
-        tab = tabs[(B, T, top_k)] = (torch.zeros((T, B, top_k), dtype=torch.int32, device=first.device),
+        tab = first._teacher_tabs[(B, T, top_k)] = (torch.zeros((T, B, top_k), dtype=torch.int32, device=first.device),
                                      torch.zeros((T, B, top_k), dtype=torch.float32, device=first.device))
     n = len(members)
     ptrs = (C.c_void_p * n)(*[c.logits.data_ptr() for c in ctxs])
     w = (C.c_float * n)(*weights)
-    L.check(first.lib.comic_teacher_topk(ptrs, w, n, ctxs[0].i32.data_ptr() + 8 * B * T, B, T, Tp, V, float(temperature),
+    L.check(first.lib.comic_teacher_topk(ptrs, w, n, ctxs[0].stage.ptr['lens'], B, T, Tp, V, float(temperature),
                                          int(top_k), tab[0].data_ptr(), tab[1].data_ptr(), L.stream_ptr()), 'teacher_topk')
     return tab
 
@@ -1594,6 +1599,159 @@ def process_inputs(captions, token_type):
             np.ascontiguousarray(masks, np.float32), lens)
 
 
+DEVICE_REWARDS = 'device'               # loss_coefficients(rewards=): comic_scst_coefficients forms them on the stream
+
+
+def loss_coefficients(wmask, rewards, xe_denom, B):
+    """coef, rs [B,T] float32 of the sequence loss (model_base.py:337-347) from the mask: the per-token coefficient the
+    kernels multiply the cross-entropy by, and the row scale of the loss reduction.  rewards None: XE, normalised by
+    sum(w) + 1e-12 or by `xe_denom`; a host array [B]: SCST, mean_b(xent_b * reward_b); DEVICE_REWARDS: zeros, which the
+    device overwrites.  Float32 operations in this order: comic_scst_coefficients repeats them bit for bit."""
+    T = wmask.shape[1]
+    if rewards is DEVICE_REWARDS:
+        rs = coef = np.zeros((B, T), np.float32)
+    elif rewards is None:
+        den_xe = np.float32(xe_denom) if xe_denom is not None else np.float32(wmask.sum() + np.float32(1e-12))
+        rs = np.full((B, T), np.float32(1.0) / den_xe, np.float32)
+        coef = wmask / den_xe
+    else:
+        den = wmask.sum(axis=1, keepdims=True) + np.float32(1e-12)
+        rb = (np.asarray(rewards, np.float32)[:, None] / np.float32(B))
+        rs = np.broadcast_to(rb / den, (B, T)).astype(np.float32)
+        coef = wmask / den * rb
+    return coef, rs
+
+
+def train_stage_fields(B, T):
+    """ONE staging block per training step: [seed int64 | inputs, targets, lens int32 | wmask, coef, row scale fp32]."""
+    return (('seed', 'int64', (1,)), ('inputs', 'int32', (B, T)), ('targets', 'int32', (B, T)), ('lens', 'int32', (B,)),
+            ('wmask', 'float32', (B, T)), ('coef', 'float32', (B, T)), ('row_scale', 'float32', (B, T)))
+
+
+def score_stage_fields(B, T):
+    """ONE staging block per scoring call: [inputs, targets, lens int32 | wmask fp32]."""
+    return train_stage_fields(B, T)[1:5]
+
+
+def staging_layout(fields):
+    """Byte offset of every field (name, dtype, shape) of a staging block, and the block's size: the fields follow each
+    other in order, and where the dtype changes the offset is rounded up to 8 bytes.  Pure: no GPU, no torch."""
+    offsets, at, last = {}, 0, None
+    for name, dtype, shape in fields:
+        if last is not None and dtype != last:
+            at = (at + 7) // 8 * 8
+        offsets[name], last = at, dtype
+        at += np.dtype(dtype).itemsize * int(np.prod(shape))
+    return offsets, at
+
+
+class Staging:
+    """The small host-written operands of a step as one device block, fed by ONE copy from pinned memory.  Two pinned slots
+    are used alternately: the host may run ahead of the GPU, and an async H2D copy reads its pinned source when the STREAM
+    gets there, so a slot is rewritten only after the copy that last used it has executed (an event per slot).
+    dev[name] / ptr[name]: the field's device view / address; every view, device or host, is flat (the kernels' view)."""
+
+    def __init__(self, torch, device, fields):
+        self.torch = torch
+        offsets, self.nbytes = staging_layout(fields)
+
+        def views(buf):
+            return {name: buf[offsets[name]:offsets[name] + np.dtype(dtype).itemsize * int(np.prod(shape))]
+                    .view(getattr(torch, dtype)) for name, dtype, shape in fields}
+        self.buf = torch.zeros(self.nbytes, dtype=torch.uint8, device=device)
+        self.dev = views(self.buf)
+        self.ptr = {name: t.data_ptr() for name, t in self.dev.items()}
+        self._slots = []
+        for _ in range(2):
+            buf = torch.zeros(self.nbytes, dtype=torch.uint8).pin_memory()
+            self._slots.append((buf, {name: t.numpy() for name, t in views(buf).items()}, torch.cuda.Event()))
+        self._taken = -1                # slots taken so far - 1: its own counter, nobody else's
+
+    def next_slot(self):
+        """Take the next slot, once the copy that last read it has executed -> its host views (numpy, by name)."""
+        self._taken += 1
+        return self.last_slot()
+
+    def last_slot(self):
+        """The slot the last upload used, once that copy has executed -> its host views: a second upload of one step."""
+        _, host, copied = self._slots[self._taken % 2]
+        copied.synchronize()            # (returns at once on an event that was never recorded)
+        return host
+
+    def upload(self):
+        """The taken slot to the device block on the current stream, and the slot's event behind the copy."""
+        buf, _, copied = self._slots[self._taken % 2]
+        self.buf.copy_(buf, non_blocking=True)
+        copied.record(self.torch.cuda.current_stream())
+
+    def send(self, fields, again=False):
+        """`fields` (arrays or numbers by name) into the next slot -- again=True: into the slot the last upload used, whose
+        other fields stand -- and that slot to the device."""
+        host = self.last_slot() if again else self.next_slot()
+        for name, value in fields.items():
+            host[name][:] = np.reshape(value, -1)
+        self.upload()
+
+
+class GraphRunner:
+    """Eager or hipGraph execution of a context's launches: run(what, launch, use_graph) calls launch() eagerly; with
+    use_graph the second use of `what` on this context captures it and every later one replays the graph.  Uses count
+    whether or not they asked for a graph.  what: None for the context's whole launch sequence, 'fwd' / 'bwd' for the
+    halves of a split training step; each has its own counter and its own graph."""
+
+    def __init__(self, torch):
+        self.torch, self.uses, self.graphs = torch, {}, {}
+
+    def run(self, what, launch, use_graph):
+        torch = self.torch
+        self.uses[what] = used = self.uses.get(what, 0) + 1
+        graph = self.graphs.get(what)
+        if use_graph and graph is None and used >= 2:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+                launch()
+            self.graphs[what] = graph
+        if use_graph and graph is not None:
+            graph.replay()
+        else:
+            launch()
+
+
+class _Context:
+    """Persistent buffers of one shape of one entry point, with the graphs of its launches.  The constructors
+    (Decoder._train_ctx, _score_ctx, _infer_ctx, EnsembleDecoder._ctx) add the buffers every use needs; what is set later,
+    or only for some uses, is declared in the subclasses."""
+
+    def __init__(self, torch, key):
+        self.key, self.runner = key, GraphRunner(torch)
+
+    @property
+    def graph(self):
+        """The graph of the whole step / scoring call / decode loop, or None before its capture."""
+        return self.runner.graphs.get(None)
+
+
+class _StepContext(_Context):
+    """A training or scoring context."""
+    stage = None                        # the Staging block
+    masks = None                        # training: the dropout masks by name (views of mask_buf)
+    soft = None                         # training with soft targets: the comic_soft_targets record
+    fm_in = im_in = None                # what the step reads: the caller's tensors in place, or the context's copies
+    split_open = False                  # a phase='fwd' call waits for its phase='bwd'
+    inject_timeout = False              # the next eager step runs with COMIC_DEC_INJECT_TIMEOUT (tests)
+
+
+class _DecodeContext(_Context):
+    """A greedy / beam / ensemble decode context."""
+    ids_host = eos_host = None          # greedy(defer=True): pinned copies of ids and first_eos
+    pred = pred_host = steps_host = None    # beam_search_ids: the gathered ids, pinned copies of them and of steps
+    fetched = None                      # the event behind those copies
+    keep = None                         # a temporary the enqueued launches still read
+    seed = req = None                   # sampling / required words: device words written in front of every launch
+    prefix = pfx = None                 # forced prefix: the comic_beam_prefix record and the device table
+    cons = grp = smp = trc = rqd = None     # the C structs of the active options, kept alive (BeamOptions.c_record)
+
+
 class Decoder:
     """Device decoder: parameters, gradients and native step calls."""
 
@@ -1609,7 +1767,7 @@ class Decoder:
         self._ws_bytes = 0
         self._dropout_calls = 0
         self.set_dropout_stream(seed, 0)
-        self._ctx = {}
+        self._ctx, self._score_ctxs, self._infer_ctxs, self._teacher_tabs = {}, {}, {}, {}
 
     # ------------------------------------------------------------------ helpers --------
     def _workspace(self, nbytes):
@@ -1652,31 +1810,12 @@ class Decoder:
         if ctx is not None:
             return ctx
         torch, s, dev = self.torch, self.spec, self.device
-        from types import SimpleNamespace
-        ctx = SimpleNamespace(key=key, calls=0, graph=None)
+        ctx = _StepContext(torch, key)
         f32 = dict(dtype=torch.float32, device=dev)
-        # ONE staging block per step: [seed int64 | inputs, targets, lens int32 | wmask, coef, row scale fp32]
-        n_i32, n_f32 = 2 * B * T + B, 3 * B * T
-        o_i32, o_f32 = 8, 8 + 4 * ((n_i32 + 1) // 2 * 2)
-        nbytes = o_f32 + 4 * n_f32
-
-        def views(buf):
-            return (buf[:8].view(torch.int64), buf[o_i32:o_i32 + 4 * n_i32].view(torch.int32),
-                    buf[o_f32:o_f32 + 4 * n_f32].view(torch.float32))
-        ctx.stage_dev = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        ctx.seed, ctx.i32, ctx.f32 = views(ctx.stage_dev)
-        # pinned staging, two slots used alternately: the host may run ahead of the GPU, and an async H2D copy
-        # reads its pinned source when the STREAM gets there, so a slot is rewritten only after the copy that last
-        # used it has executed (event per slot)
-        ctx.stage = []
-        for _ in range(2):
-            buf = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-            sd, i32, f32v = views(buf)
-            ctx.stage.append(SimpleNamespace(buf=buf, seed=sd, i32=i32, f32=f32v, copied=None))
+        ctx.stage = Staging(torch, dev, train_stage_fields(B, T))
         ctx.fm = torch.empty((B, s.M, s.C), **f32)
         ctx.im = torch.empty((B, s.Cg), **f32)
         EA = s.E + s.A
-        ctx.masks = None
         if training:
             # one buffer, four views (generated by ONE launch: comic_dropout_masks4_dev)
             shapes = dict(init_in=(B, EA), inp=(Tp, B, EA), out=(Tp, B, s.D), alpha=(Tp, B, s.H, s.M))
@@ -1700,7 +1839,6 @@ class Decoder:
         ctx.desc = s.desc(training)
         ctx.nbytes = self.lib.comic_decoder_train_workspace(C.byref(ctx.desc), B, T)
         ctx.ws = torch.empty(int(ctx.nbytes), dtype=torch.uint8, device=dev)
-        ctx.soft = None
         if soft is not None:    # the record, the hard-loss rows and the step's own copy of the teacher's table
             K = soft.top_k
             ctx.nll_rows = torch.zeros(T * B, **f32)
@@ -1750,7 +1888,7 @@ class Decoder:
         m = ctx.masks or {}
         if training and gen_masks and phase != 'bwd':
             L.check(self.lib.comic_dropout_masks4_dev(ctx.mask_buf.data_ptr(), ctx.mask_n4, ctx.mask_keep4,
-                                                      ctx.seed.data_ptr(), st), 'dropout_masks4')
+                                                      ctx.stage.ptr['seed'], st), 'dropout_masks4')
             if s.recurrent_dropout:
                 # variational recurrent dropout (model_base.py:645; [TF-1.9] DropoutWrapper draws its input / output
                 # noise once per run with a batch dimension of 1): the first row of the drawn masks serves every batch
@@ -1761,14 +1899,13 @@ class Decoder:
                 m['inp'].copy_(row_in.expand_as(m['inp']))
                 m['init_in'].copy_(row_in.expand_as(m['init_in']))
                 m['out'].copy_(row_out.expand_as(m['out']))
-        BT = B * T
-        i32, f32 = ctx.i32, ctx.f32
+        at = ctx.stage.ptr
         ptab, gtab = self.params.table(), self.grads.table()
+        inject, ctx.inject_timeout = ctx.inject_timeout, False
         ctx.desc.flags = (L.decoder_flags_from_env() | {None: 0, 'fwd': L.DEC_PHASE_FWD, 'bwd': L.DEC_PHASE_BWD}[phase]
-                          | (L.DEC_INJECT_TIMEOUT if ctx.__dict__.pop('inject_timeout', False) else 0))
+                          | (L.DEC_INJECT_TIMEOUT if inject else 0))
         args = (C.byref(ctx.desc), C.byref(ptab), C.byref(gtab), ctx.fm_in.data_ptr(), ctx.im_in.data_ptr(),
-                i32.data_ptr(), i32.data_ptr() + 4 * BT, f32.data_ptr(), f32.data_ptr() + 4 * BT,
-                i32.data_ptr() + 8 * BT, B, T, Tp,
+                at['inputs'], at['targets'], at['wmask'], at['coef'], at['lens'], B, T, Tp,
                 L.ptr(m.get('init_in')), L.ptr(m.get('inp')), L.ptr(m.get('out')), L.ptr(m.get('alpha')),
                 ctx.logits.data_ptr(), ctx.ids.data_ptr(), ctx.hist.data_ptr(), ctx.loss_rows.data_ptr(),
                 ctx.map_loss.data_ptr(), L.ptr(ctx.dfm), L.ptr(ctx.dim), ctx.ws.data_ptr(), ctx.nbytes, st)
@@ -1779,10 +1916,10 @@ class Decoder:
         if phase == 'fwd':
             return
         # sequence_loss reduction (model_base.py:337-347): rows carry xent*w; rs = 1/denominator (* reward/B)
-        L.check(self.lib.comic_weighted_sum_tb(ctx.loss_rows.data_ptr(), f32.data_ptr() + 4 * 2 * BT, T, B,
+        L.check(self.lib.comic_weighted_sum_tb(ctx.loss_rows.data_ptr(), at['row_scale'], T, B,
                                                ctx.loss.data_ptr(), st), 'weighted_sum_tb')
         if ctx.soft is not None:            # the hard loss beside the optimised one, by the same reduction
-            L.check(self.lib.comic_weighted_sum_tb(ctx.nll_rows.data_ptr(), f32.data_ptr() + 4 * 2 * BT, T, B,
+            L.check(self.lib.comic_weighted_sum_tb(ctx.nll_rows.data_ptr(), at['row_scale'], T, B,
                                                    ctx.nll.data_ptr(), st), 'weighted_sum_tb')
 
     def train_step(self, fm, im_embed, captions, masks=None, rewards=None, training=True, seed=None,
@@ -1815,120 +1952,113 @@ class Decoder:
         record or training=False: the step of always.  With `rewards` a ValueError: soft targets are XE training.
         Returns dict(loss, nll, map_loss, logits [B,T,V], ids [B,T], attn_maps [B,H,T',M]) (device views
         of persistent buffers: valid until the next call with the same shape)."""
-        torch, s = self.torch, self.spec
+        soft = self._checked_soft(soft, training, rewards, teacher, phase)
+        inputs, targets, wmask, lens = process_inputs(captions, self.spec.token_type)
+        B, T = inputs.shape
+        Tp = int(lens.max())
+        dev_rewards = self._checked_device_rewards(rewards, B)
+        coef, rs = loss_coefficients(wmask, rewards if dev_rewards is None else DEVICE_REWARDS, xe_denom, B)
+        gen_masks = bool(training and masks is None)
+        use_masks = bool(training or masks is not None)
+        ctx = self._train_ctx(B, T, Tp, use_masks, gen_masks, want_input_grads, soft)
+        if phase != 'fwd':
+            self._stage_teacher(ctx, soft, teacher)
+        if phase == 'bwd':          # second call of a split step: only the coefficients are new
+            assert ctx.split_open, 'train_step(phase="bwd") without its phase="fwd" call'
+            ctx.split_open = False
+            if dev_rewards is not None:                           # the mask is on the device since the forward call
+                self._device_coefficients(ctx, dev_rewards)
+            else:                                                 # into the slot its forward call staged: same inputs
+                ctx.stage.send(dict(coef=coef, row_scale=rs), again=True)
+            ctx.runner.run('bwd', lambda: self._train_device(ctx, 'bwd'), use_graph)
+            return self._train_result(ctx, Tp)
+        fields = dict(inputs=inputs, targets=targets, lens=lens, wmask=wmask, coef=coef, row_scale=rs)
+        if gen_masks:
+            fields['seed'] = self._dropout_seed(seed)
+        ctx.stage.send(fields)
+        if dev_rewards is not None and phase != 'fwd':
+            self._device_coefficients(ctx, dev_rewards)
+        if masks is not None:
+            self._inject_masks(ctx, masks)
+        if dp is not None and dp.world > 1 and rewards is None:
+            self._rescale_data_parallel(ctx, dp)
+        direct = self._bind_inputs(ctx, fm, im_embed, not copy_inputs and not use_graph, on_inputs_consumed)
+        if phase == 'fwd':
+            ctx.split_open = True
+        if inject_timeout:          # fault injection of THIS call (COMIC_DEC_INJECT_TIMEOUT, tests): eager launches only
+            assert not use_graph and phase is None
+            ctx.inject_timeout = True
+        ctx.runner.run(phase, lambda: self._train_device(ctx, phase), use_graph)
+        if direct and on_inputs_consumed is not None:   # stream order: whatever the caller enqueues now runs after the step
+            on_inputs_consumed()
+        return None if phase == 'fwd' else self._train_result(ctx, Tp)
+
+    def _checked_soft(self, soft, training, rewards, teacher, phase):
+        """The active SoftTargets of a train_step call or None, refused where they do not apply."""
         soft = _active(soft) if training else None
         if soft is not None:
             if rewards is not None:
                 raise ValueError('train_step: soft targets and SCST rewards do not combine')
-            soft.check_vocabulary(s.V)
+            soft.check_vocabulary(self.spec.V)
             if soft.distils and teacher is None and phase != 'fwd':
                 raise ValueError('train_step: teacher_weight %g without a teacher table (teacher=(ids, probs))'
                                  % soft.teacher_weight)
-        inputs, targets, wmask, lens = process_inputs(captions, s.token_type)
-        B, T = inputs.shape
-        Tp = int(lens.max())
-        dev_rewards = rewards if torch.is_tensor(rewards) else None
-        if dev_rewards is not None:
-            # a float32 device tensor [B]: comic_scst_coefficients forms coef / rs on the stream from the staged mask,
-            # into the device staging block; the host writes neither
-            if tuple(dev_rewards.shape) != (B,) or dev_rewards.dtype != torch.float32 or not dev_rewards.is_cuda:
-                raise ValueError('train_step: device rewards must be a float32 device tensor [%d], got %s %r'
-                                 % (B, dev_rewards.dtype, tuple(dev_rewards.shape)))
-            dev_rewards = dev_rewards.contiguous()
-            rs = coef = np.zeros((B, T), np.float32)
-        elif rewards is None:
-            den_xe = np.float32(xe_denom) if xe_denom is not None else np.float32(wmask.sum() + np.float32(1e-12))
-            rs = np.full((B, T), np.float32(1.0) / den_xe, np.float32)
-            coef = wmask / den_xe
-        else:
-            den = wmask.sum(axis=1, keepdims=True) + np.float32(1e-12)
-            rb = (np.asarray(rewards, np.float32)[:, None] / np.float32(B))
-            rs = np.broadcast_to(rb / den, (B, T)).astype(np.float32)
-            coef = wmask / den * rb
-        gen_masks = bool(training and masks is None)
-        use_masks = bool(training or masks is not None)
-        ctx = self._train_ctx(B, T, Tp, use_masks, gen_masks, want_input_grads, soft)
-        BT = B * T
+        return soft
 
-        def result():
-            return dict(loss=ctx.loss[0], nll=(ctx.loss if ctx.soft is None else ctx.nll)[0], map_loss=ctx.map_loss[0],
-                        logits=ctx.logits.permute(1, 0, 2), ids=ctx.ids.t(), attn_maps=ctx.hist.permute(1, 2, 0, 3),
-                        dfm=ctx.dfm, dim_embed=ctx.dim, Tp=Tp)
-        if phase != 'fwd':
-            self._stage_teacher(ctx, soft, teacher)
-        if phase == 'bwd':          # second call of a split step: only the coefficients are new
-            assert getattr(ctx, 'split_open', False), 'train_step(phase="bwd") without its phase="fwd" call'
-            ctx.split_open = False
-            if dev_rewards is not None:                           # the mask is on the device since the forward call
-                self._device_coefficients(ctx, dev_rewards)
-            else:
-                slot = ctx.stage[(ctx.calls - 1) % 2]             # the slot its forward call staged: same inputs
-                slot.copied.synchronize()
-                fh = slot.f32.numpy()
-                fh[BT:2 * BT] = coef.reshape(-1); fh[2 * BT:] = rs.reshape(-1)
-                ctx.stage_dev.copy_(slot.buf, non_blocking=True)
-                slot.copied.record(torch.cuda.current_stream())
-            self._run_train_phase(ctx, 'bwd', use_graph)
-            return result()
-        slot = ctx.stage[ctx.calls % 2]
-        if slot.copied is not None:
-            slot.copied.synchronize()
-        ih, fh = slot.i32.numpy(), slot.f32.numpy()
-        ih[:BT] = inputs.reshape(-1); ih[BT:2 * BT] = targets.reshape(-1); ih[2 * BT:] = lens
-        fh[:BT] = wmask.reshape(-1); fh[BT:2 * BT] = coef.reshape(-1); fh[2 * BT:] = rs.reshape(-1)
-        if gen_masks:
-            if seed is None:
-                self._dropout_calls += 1
-                seed = (self._dropout_base + self._dropout_calls) & 0x7FFFFFFFFFFFFFFF
-            slot.seed[0] = int(seed)
-        ctx.stage_dev.copy_(slot.buf, non_blocking=True)
-        if dev_rewards is not None and phase != 'fwd':
-            self._device_coefficients(ctx, dev_rewards)
-        if masks is not None:
-            for k, v in masks.items():
-                ctx.masks[k].copy_(v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, np.float32)))
-        if dp is not None and dp.world > 1 and rewards is None:
-            f = ctx.f32                                  # device views [wmask | coef | row scale]
-            inv = 1.0 / dp.global_xe_denominator(f[:BT])
-            torch.mul(f[:BT], inv, out=f[BT:2 * BT])
-            f[2 * BT:3 * BT] = inv
-        if slot.copied is None:
-            slot.copied = torch.cuda.Event()
-        slot.copied.record(torch.cuda.current_stream())
+    def _checked_device_rewards(self, rewards, B):
+        """`rewards` where it is a device tensor (else None): float32 [B], contiguous.  comic_scst_coefficients then forms
+        coef / rs on the stream from the staged mask, into the device staging block; the host writes neither."""
+        torch = self.torch
+        if not torch.is_tensor(rewards):
+            return None
+        if tuple(rewards.shape) != (B,) or rewards.dtype != torch.float32 or not rewards.is_cuda:
+            raise ValueError('train_step: device rewards must be a float32 device tensor [%d], got %s %r'
+                             % (B, rewards.dtype, tuple(rewards.shape)))
+        return rewards.contiguous()
+
+    def _dropout_seed(self, seed):
+        """The seed of a step's device-generated masks: the caller's, or the next of this decoder's stream."""
+        if seed is None:
+            self._dropout_calls += 1
+            seed = (self._dropout_base + self._dropout_calls) & 0x7FFFFFFFFFFFFFFF
+        return int(seed)
+
+    def _inject_masks(self, ctx, masks):
+        """Given dropout masks (device tensors or numpy arrays) into the context's own, on the stream."""
+        torch = self.torch
+        for k, v in masks.items():
+            ctx.masks[k].copy_(v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, np.float32)))
+
+    def _rescale_data_parallel(self, ctx, dp):
+        """coef and the row scale of the device staging block from the GLOBAL token count (train_step's dp=): formed on
+        the stream behind the staging copy, no host synchronisation."""
+        d = ctx.stage.dev
+        inv = 1.0 / dp.global_xe_denominator(d['wmask'])
+        self.torch.mul(d['wmask'], inv, out=d['coef'])
+        d['row_scale'][:] = inv
+
+    def _bind_inputs(self, ctx, fm, im_embed, in_place, on_inputs_consumed):
+        """ctx.fm_in / .im_in, what the step reads: the caller's tensors (in_place, where they are contiguous: -> True, and
+        the caller is told after the step's launches) or the context's copies, after which the caller's may be overwritten."""
+        torch, s = self.torch, self.spec
+        B = ctx.key[0]
         assert fm.shape == (B, s.M, s.C) and im_embed.shape == (B, s.Cg), (fm.shape, im_embed.shape)
         assert fm.dtype == torch.float32 and im_embed.dtype == torch.float32
-        direct = (not copy_inputs and not use_graph and fm.is_contiguous() and im_embed.is_contiguous())
-        if direct:
+        if in_place and fm.is_contiguous() and im_embed.is_contiguous():
             ctx.fm_in, ctx.im_in = fm, im_embed
-        else:
-            ctx.fm.copy_(fm)
-            ctx.im.copy_(im_embed)
-            ctx.fm_in, ctx.im_in = ctx.fm, ctx.im
-            if on_inputs_consumed is not None:      # the encoder buffers may be overwritten from here on
-                on_inputs_consumed()
-        if phase == 'fwd':
-            ctx.split_open = True
-            self._run_train_phase(ctx, 'fwd', use_graph)
-            if direct and on_inputs_consumed is not None:
-                on_inputs_consumed()
-            ctx.calls += 1
-            return None
-        if inject_timeout:          # fault injection of THIS call (COMIC_DEC_INJECT_TIMEOUT, tests): eager launches only
-            assert not use_graph and phase is None
-            ctx.inject_timeout = True
-        if use_graph and ctx.graph is None and ctx.calls >= 1:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                self._train_device(ctx)
-            ctx.graph = g
-        if use_graph and ctx.graph is not None:
-            ctx.graph.replay()
-        else:
-            self._train_device(ctx)
-        if direct and on_inputs_consumed is not None:   # stream order: whatever the caller enqueues now runs after the step
+            return True
+        ctx.fm.copy_(fm)
+        ctx.im.copy_(im_embed)
+        ctx.fm_in, ctx.im_in = ctx.fm, ctx.im
+        if on_inputs_consumed is not None:      # the encoder buffers may be overwritten from here on
             on_inputs_consumed()
-        ctx.calls += 1
-        return result()
+        return False
+
+    @staticmethod
+    def _train_result(ctx, Tp):
+        return dict(loss=ctx.loss[0], nll=(ctx.loss if ctx.soft is None else ctx.nll)[0], map_loss=ctx.map_loss[0],
+                    logits=ctx.logits.permute(1, 0, 2), ids=ctx.ids.t(), attn_maps=ctx.hist.permute(1, 2, 0, 3),
+                    dfm=ctx.dfm, dim_embed=ctx.dim, Tp=Tp)
 
     def _forward_logits(self, fm, im_embed, captions):
         """The forward-only phase of this decoder's executor without dropout (phase='fwd', training=False, the call the
@@ -1946,53 +2076,23 @@ class Decoder:
         """coef and rs of the device staging block from its mask and the device rewards [B] (comic_scst_coefficients):
         stream-ordered behind the staging copy, in front of the step that reads them."""
         B, T = ctx.key[:2]
-        f = ctx.f32.data_ptr()
-        L.check(self.lib.comic_scst_coefficients(f, rewards.data_ptr(), B, T, f + 4 * B * T, f + 8 * B * T,
+        at = ctx.stage.ptr
+        L.check(self.lib.comic_scst_coefficients(at['wmask'], rewards.data_ptr(), B, T, at['coef'], at['row_scale'],
                                                  L.stream_ptr()), 'scst_coefficients')
-
-    def _run_train_phase(self, ctx, phase, use_graph):
-        """One half of a split step, eagerly or from its own hipGraph (captured at the second use of the shape)."""
-        torch = self.torch
-        graphs = ctx.__dict__.setdefault('phase_graphs', {})
-        used = ctx.__dict__.setdefault('phase_calls', {})
-        used[phase] = used.get(phase, 0) + 1
-        if use_graph and phase not in graphs and used[phase] >= 2:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                self._train_device(ctx, phase)
-            graphs[phase] = g
-        if use_graph and phase in graphs:
-            graphs[phase].replay()
-        else:
-            self._train_device(ctx, phase)
 
     # ------------------------------------------------------------------ scoring --------
     def _score_ctx(self, B, T, Tp, want_attention):
         """Persistent device buffers (+ hipGraph) of one scoring shape: a context and staging slots of their own, so a
         scoring call between two training steps of the same shape disturbs neither."""
         key = (B, T, Tp, bool(want_attention))
-        ctxs = self.__dict__.setdefault('_score_ctxs', {})
-        ctx = ctxs.get(key)
+        ctx = self._score_ctxs.get(key)
         if ctx is not None:
             return ctx
         torch, s, dev = self.torch, self.spec, self.device
-        from types import SimpleNamespace
-        ctx = SimpleNamespace(key=key, calls=0, graph=None)
+        ctx = _StepContext(torch, key)
         f32 = dict(dtype=torch.float32, device=dev)
-        # ONE staging block per call: [inputs, targets int32 [B,T] | lens int32 [B] (+ pad) | wmask fp32 [B,T]]
-        n_i32 = 2 * B * T + B
-        o_f32 = 4 * ((n_i32 + 1) // 2 * 2)
-        nbytes = o_f32 + 4 * B * T
-
-        def views(buf):
-            return buf[:4 * n_i32].view(torch.int32), buf[o_f32:].view(torch.float32)
-        ctx.stage_dev = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        ctx.i32, ctx.f32 = views(ctx.stage_dev)
-        ctx.stage = []
-        for _ in range(2):      # pinned, used alternately (see _train_ctx)
-            buf = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-            i32, f32v = views(buf)
-            ctx.stage.append(SimpleNamespace(buf=buf, i32=i32, f32=f32v, copied=None))
+        ctx.stage = Staging(torch, dev, score_stage_fields(B, T))
+        ctx.wmask = ctx.stage.dev['wmask']
         ctx.fm = torch.empty((B, s.M, s.C), **f32)
         ctx.im = torch.empty((B, s.Cg), **f32)
         ctx.token_logp = torch.zeros((T, B), **f32)
@@ -2002,18 +2102,18 @@ class Decoder:
         ctx.nbytes = self.lib.comic_decoder_score_workspace(C.byref(ctx.desc), B, T)
         assert ctx.nbytes > 0, 'comic_decoder_score_workspace failed'
         ctx.ws = torch.empty(int(ctx.nbytes), dtype=torch.uint8, device=dev)
-        ctxs[key] = ctx
+        self._score_ctxs[key] = ctx
         return ctx
 
     def _score_device(self, ctx):
         """Device-only part of a scoring call (no host sync, no host memcpy): capturable."""
         B, T, Tp, _ = ctx.key
-        BT = B * T
+        at = ctx.stage.ptr
         ptab = self.params.table()
         ctx.desc.flags = L.decoder_flags_from_env()
         L.check(self.lib.comic_decoder_score(
-            C.byref(ctx.desc), C.byref(ptab), ctx.fm.data_ptr(), ctx.im.data_ptr(), ctx.i32.data_ptr(),
-            ctx.i32.data_ptr() + 4 * BT, ctx.f32.data_ptr(), ctx.i32.data_ptr() + 8 * BT, B, T, Tp,
+            C.byref(ctx.desc), C.byref(ptab), ctx.fm.data_ptr(), ctx.im.data_ptr(), at['inputs'], at['targets'],
+            at['wmask'], at['lens'], B, T, Tp,
             ctx.token_logp.data_ptr(), ctx.logp.data_ptr(), L.ptr(ctx.hist), ctx.ws.data_ptr(), ctx.nbytes,
             L.stream_ptr()), 'decoder_score')
 
@@ -2029,32 +2129,12 @@ class Decoder:
         Tp = int(lens.max())
         assert Tp > 0, 'score: every caption is empty'
         ctx = self._score_ctx(B, T, Tp, want_attention)
-        BT = B * T
-        slot = ctx.stage[ctx.calls % 2]
-        if slot.copied is not None:
-            slot.copied.synchronize()
-        ih, fh = slot.i32.numpy(), slot.f32.numpy()
-        ih[:BT] = inputs.reshape(-1); ih[BT:2 * BT] = targets.reshape(-1); ih[2 * BT:] = lens
-        fh[:BT] = wmask.reshape(-1)
-        ctx.stage_dev.copy_(slot.buf, non_blocking=True)
-        if slot.copied is None:
-            slot.copied = torch.cuda.Event()
-        slot.copied.record(torch.cuda.current_stream())
+        ctx.stage.send(dict(inputs=inputs, targets=targets, lens=lens, wmask=wmask))
         assert fm.shape == (B, s.M, s.C) and im_embed.shape == (B, s.Cg), (fm.shape, im_embed.shape)
         assert fm.dtype == torch.float32 and im_embed.dtype == torch.float32
         ctx.fm.copy_(fm)
         ctx.im.copy_(im_embed)
-        if use_graph and ctx.graph is None and ctx.calls >= 1:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                self._score_device(ctx)
-            ctx.graph = g
-        if use_graph and ctx.graph is not None:
-            ctx.graph.replay()
-        else:
-            self._score_device(ctx)
-        ctx.calls += 1
-        ctx.wmask = ctx.f32[:BT]
+        ctx.runner.run(None, lambda: self._score_device(ctx), use_graph)
         return dict(token_log_probs=ctx.token_logp.t(), log_prob=ctx.logp, lengths=torch.from_numpy(lens.copy()),
                     attn_maps=ctx.hist.permute(1, 2, 0, 3) if ctx.hist is not None else None, Tp=Tp, wmask=ctx.wmask)
 
@@ -2075,10 +2155,9 @@ class Decoder:
         per step of host work."""
         torch, s = self.torch, self.spec
         key = (kind, B, W, max_steps, bool(want_logits), int(slot))      # slot: independent buffer sets (decodes in flight on several streams)
-        ctxs = self.__dict__.setdefault('_infer_ctxs', {})
-        ctx = ctxs.get(key)
+        ctx = self._infer_ctxs.get(key)
         if ctx is None:
-            ctx = type('InferCtx', (), {})()
+            ctx = _DecodeContext(torch, key)
             R = B * W
             i32 = dict(dtype=torch.int32, device=self.device)
             f32 = dict(dtype=torch.float32, device=self.device)
@@ -2095,24 +2174,10 @@ class Decoder:
             ctx.nbytes = int(self.lib.comic_decoder_infer_workspace(C.byref(ctx.desc), R, max_steps))
             ctx.ws = torch.empty(ctx.nbytes, dtype=torch.uint8, device=self.device)   # own workspace: graph-stable
             ctx.ptab = self.params.table()
-            ctx.graph, ctx.calls = None, 0
-            ctxs[key] = ctx
+            self._infer_ctxs[key] = ctx
         ctx.fm.copy_(fm.reshape(ctx.fm.shape))
         ctx.im.copy_(im_embed.reshape(ctx.im.shape))
         return ctx
-
-    def _run_infer(self, ctx, launch, use_graph):
-        torch = self.torch
-        if use_graph and ctx.graph is None and ctx.calls >= 1:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                launch()
-            ctx.graph = g
-        if use_graph and ctx.graph is not None:
-            ctx.graph.replay()
-        else:
-            launch()
-        ctx.calls += 1
 
     def greedy(self, fm, im_embed, max_steps, want_logits=False, use_graph=True, defer=False):
         """rnn_decoder_search(greedy) (ops_rnn.py:115-180).  -> ids [B,T_exec] (numpy int32),
@@ -2121,7 +2186,7 @@ class Decoder:
         rollouts to text on the host while this loop runs); fetch.ids_device / fetch.first_eos_device are then the device
         ids [max_steps,B], whose rows past the executed steps the loop never writes, and the first <EOS> positions [B]
         that say which rows those are (the SCST reward's baseline row takes both)."""
-        torch, s = self.torch, self.spec
+        torch = self.torch
         B = fm.shape[0]
         ctx = self._infer_ctx('greedy', B, 1, max_steps, want_logits, fm, im_embed)
 
@@ -2131,12 +2196,12 @@ class Decoder:
                                                   ctx.im.data_ptr(), B, max_steps, ctx.ids.data_ptr(),
                                                   L.ptr(ctx.logits), ctx.hist.data_ptr(), ctx.first_eos.data_ptr(),
                                                   ctx.ws.data_ptr(), ctx.nbytes, L.stream_ptr()), 'decoder_greedy')
-        self._run_infer(ctx, launch, use_graph)
+        ctx.runner.run(None, launch, use_graph)
         if defer:
             # the ids leave through pinned memory behind an event of their own (as beam_search_ids): the fetch then waits for
             # the rollout, not for whatever the caller has enqueued behind it in the meantime (the SCST step enqueues the
             # update's forward pass before it looks at the greedy captions)
-            if getattr(ctx, 'ids_host', None) is None:
+            if ctx.ids_host is None:
                 ctx.ids_host = torch.empty((max_steps, B), dtype=torch.int32).pin_memory()
                 ctx.eos_host = torch.empty(B, dtype=torch.int32).pin_memory()
                 ctx.fetched = torch.cuda.Event()
@@ -2152,13 +2217,7 @@ class Decoder:
                 fe = ctx.first_eos.cpu().numpy()
             if fe.min() < 0:                              # comic_persist_check_greedy: a bounded wait of the loop expired
                 raise L.ComicHipError('greedy: the persistent decode loop did not complete (a wait on another workgroup timed out)')
-            t_exec = int(min(max_steps, fe.max() + 1))   # loop ends when every row has emitted EOS
-            if defer:
-                out_ids = np.ascontiguousarray(ctx.ids_host[:t_exec].numpy().T)
-            else:
-                out_ids = ctx.ids[:t_exec].t().contiguous().cpu().numpy()
-            hist = ctx.hist[:t_exec].reshape(t_exec, B, s.H, s.M).permute(1, 2, 0, 3).clone()
-            return out_ids, hist, (ctx.logits[:t_exec].permute(1, 0, 2).clone() if want_logits else None)
+            return self._greedy_result(ctx, fe, max_steps, want_logits, ctx.ids_host if defer else None)
         fetch.ids_device, fetch.first_eos_device = ctx.ids, ctx.first_eos
         return fetch if defer else fetch()
 
@@ -2182,11 +2241,27 @@ class Decoder:
                                               max_steps, noise.data_ptr(), ctx.ids.data_ptr(), L.ptr(ctx.logits),
                                               ctx.hist.data_ptr(), ctx.first_eos.data_ptr(), ctx.ws.data_ptr(), ctx.nbytes,
                                               L.stream_ptr()), 'decoder_sample')
-        fe = ctx.first_eos.cpu().numpy()
-        t_exec = int(min(max_steps, fe.max() + 1))
-        out_ids = ctx.ids[:t_exec].t().contiguous().cpu().numpy()
+        return self._greedy_result(ctx, ctx.first_eos.cpu().numpy(), max_steps, want_logits)
+
+    def _greedy_result(self, ctx, first_eos, max_steps, want_logits, ids_host=None):
+        """ids [B,T_exec] (numpy), attn_maps [B,H,T_exec,M], logits [B,T_exec,V] or None of a finished greedy / sampled
+        loop from its first <EOS> positions (numpy); ids_host: the pinned copy of the ids where they were fetched already."""
+        s, B = self.spec, first_eos.shape[0]
+        t_exec = int(min(max_steps, first_eos.max() + 1))   # loop ends when every row has emitted EOS
+        if ids_host is not None:
+            out_ids = np.ascontiguousarray(ids_host[:t_exec].numpy().T)
+        else:
+            out_ids = ctx.ids[:t_exec].t().contiguous().cpu().numpy()
         hist = ctx.hist[:t_exec].reshape(t_exec, B, s.H, s.M).permute(1, 2, 0, 3).clone()
         return out_ids, hist, (ctx.logits[:t_exec].permute(1, 0, 2).clone() if want_logits else None)
+
+    def _own_ensemble(self):
+        """This decoder as a one-member ensemble, the executor of every beam option.  Created at its first use, in
+        __dict__: a decoder that never decodes with an option has no such attribute."""
+        ens = self.__dict__.get('_self_ensemble')
+        if ens is None:
+            ens = self._self_ensemble = EnsembleDecoder([self])
+        return ens
 
     def _launch_beam(self, ctx, B, W, max_steps):
         """The comic_decoder_beam call of a 'beam' context (capturable): beam_search_ids' and the plain beam_search's."""
@@ -2216,15 +2291,12 @@ class Decoder:
         if sampling is not None or reward is not None or prefix is not None:
             opts.check(s, W, B, max_steps)
         if opts.smp is not None or prefix is not None:
-            ens = self.__dict__.get('_self_ensemble')
-            if ens is None:
-                ens = self._self_ensemble = EnsembleDecoder([self])
-            ctx = ens._enqueue([fm], [im_embed], W, max_steps, use_graph, opts)
+            ctx = self._own_ensemble()._enqueue([fm], [im_embed], W, max_steps, use_graph, opts)
         else:
             ctx = self._infer_ctx('beam', B, W, max_steps, False, fm, im_embed, slot=slot)
             ctx.desc.length_penalty_weight = 0.0
-            self._run_infer(ctx, lambda: self._launch_beam(ctx, B, W, max_steps), use_graph)
-        if getattr(ctx, 'pred', None) is None:
+            ctx.runner.run(None, lambda: self._launch_beam(ctx, B, W, max_steps), use_graph)
+        if ctx.pred is None:
             ctx.pred = torch.empty((max_steps, B, W), dtype=torch.int32, device=self.device)
             ctx.pred_host = torch.empty((max_steps, B, W), dtype=torch.int32).pin_memory()
             ctx.steps_host = torch.empty(1, dtype=torch.int32).pin_memory()
@@ -2242,11 +2314,8 @@ class Decoder:
             return ctx.pred_host[:int(ctx.steps_host[0])].numpy().copy()
         fetch.ids_device, fetch.reward = ctx.pred, None
         if reward is not None:
-            base = reward_baseline_ids
-            if base is not None:
-                base = base if torch.is_tensor(base) else torch.from_numpy(np.ascontiguousarray(base, np.int32))
-                base = base.to(device=self.device, dtype=torch.int32).contiguous()
-            fetch.reward = scst_reward(self.lib, torch, ctx.pred, reward_refs, reward, base)
+            fetch.reward = scst_reward(self.lib, torch, ctx.pred, reward_refs, reward,
+                                       _baseline_ids(torch, reward_baseline_ids, self.device))
         return fetch
 
     def beam_search(self, fm, im_embed, beam, max_steps, want_attention=True, use_graph=True, length_penalty_weight=0.0,
@@ -2300,15 +2369,12 @@ class Decoder:
         B, W = fm.shape[0], beam
         opts.check(self.spec, W, B, max_steps)
         if opts.active:
-            ens = self.__dict__.get('_self_ensemble')
-            if ens is None:
-                ens = self._self_ensemble = EnsembleDecoder([self])
-            return ens._decode([fm], [im_embed], W, max_steps, want_attention, use_graph, opts)
+            return self._own_ensemble()._decode([fm], [im_embed], W, max_steps, want_attention, use_graph, opts)
         # (a non-zero length penalty is another captured graph: the weight is baked into the step kernel's arguments)
         lpw = float(opts.length_penalty_weight)
         ctx = self._infer_ctx('beam' if not lpw else 'beam_lp%r' % lpw, B, W, max_steps, False, fm, im_embed)
         ctx.desc.length_penalty_weight = lpw
-        self._run_infer(ctx, lambda: self._launch_beam(ctx, B, W, max_steps), use_graph)
+        ctx.runner.run(None, lambda: self._launch_beam(ctx, B, W, max_steps), use_graph)
         return _beam_result(self, ctx, B, W, opts, want_attention)
 
     def consensus(self, ids, cons, log_probs=None):
@@ -2434,7 +2500,7 @@ class EnsembleDecoder:
         key = (B, W, max_steps, opts.context_key())
         ctx = self._ctxs.get(key)
         if ctx is None:
-            ctx = type('EnsembleCtx', (), {})()
+            ctx = _DecodeContext(torch, key)
             R = B * W
             f32 = dict(dtype=torch.float32, device=self.device)
             specs = [d.spec for d in self.decoders]
@@ -2455,7 +2521,6 @@ class EnsembleDecoder:
                 ctx.req = torch.full((B, opts.required.n_words, opts.required.stride), -1, dtype=torch.int32,
                                      device=self.device)
             ctx.options = opts.c_record(ctx)
-            ctx.prefix = ctx.pfx = None
             if opts.prefix is None:
                 ctx.nbytes = int(self.lib.comic_decoder_beam_search_workspace(ctx.descs, n, R, max_steps,
                                                                               C.byref(ctx.options)))
@@ -2466,7 +2531,6 @@ class EnsembleDecoder:
                     ctx.descs, n, R, max_steps, C.byref(ctx.options), C.byref(ctx.prefix)))
             assert ctx.nbytes > 0, 'the ensemble workspace query failed'
             ctx.ws = torch.empty(ctx.nbytes, dtype=torch.uint8, device=self.device)
-            ctx.graph, ctx.calls = None, 0
             self._ctxs[key] = ctx
         for k, (fm, im) in enumerate(feats):
             ctx.fm[k].copy_(fm.reshape(ctx.fm[k].shape))
@@ -2525,5 +2589,5 @@ class EnsembleDecoder:
                 L.check(self.lib.comic_decoder_beam_search_prefixed(
                     ctx.descs, ctx.ptabs, ctx.fm_ptrs, ctx.im_ptrs, ctx.wts, n, B, W, max_steps, C.byref(ctx.options),
                     C.byref(ctx.prefix), ctx.pfx.data_ptr(), *outs), 'decoder_beam_search_prefixed')
-        Decoder._run_infer(self, ctx, launch, use_graph)
+        ctx.runner.run(None, launch, use_graph)
         return ctx
