@@ -195,6 +195,14 @@ _SIGS = {
     'comic_momentum_tf_gated': (c_int, [P, P, P, c_int64, c_float, c_float, c_float, c_float, P, P]),
     'comic_adam_tf_ema': (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, P, P, c_float, P]),
     'comic_momentum_tf_ema': (c_int, [P, P, P, c_int64, c_float, c_float, c_float, c_float, P, P, c_float, P]),
+    # `--prune_sparsity`: the masked forms of the two updates, the mask event and its helpers (csrc/prune.hip)
+    'comic_adam_tf_masked': (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, P, P, c_float,
+                                     P, c_int64, P]),
+    'comic_momentum_tf_masked': (c_int, [P, P, P, c_int64, c_float, c_float, c_float, c_float, P, P, c_float, P, c_int64, P]),
+    'comic_prune_workspace_bytes': (c_int64, [c_int64, c_int, c_int]),
+    'comic_prune_select': (c_int, [P, P, c_int64, P, c_int, P, c_int, P, P, P, P, c_int64, P]),
+    'comic_prune_mask_buffer': (c_int, [P, P, c_int64, c_int64, P]),
+    'comic_prune_mask_from_zeros': (c_int, [P, P, c_int64, P, c_int, P]),
     'comic_debug_occupy_cus': (c_int, [c_int, c_int, P]),
     'comic_colsum': (c_int, [P, P, c_int, c_int, c_float, P]),
     'comic_ln_tanh_fwd': (c_int, [P, P, P, P, P, c_int, c_int, c_float, P]),

@@ -217,6 +217,23 @@ def average_variables(dicts):
     return out
 
 
+def sparsity(path, dec_spec=None):
+    """The non-zero counts of a compact (or any) checkpoint's decoder: {'variables': {TF variable name: (non-zero elements,
+    elements)} for the prunable variables (prune.PRUNABLE) it holds, 'nonzero' and 'total': the counts over every variable
+    under `Model/decoder/rnn_decoder/`}.  dec_spec, when given, names the prunable variables exactly; without it they are
+    the decoder's variables with two dimensions."""
+    from . import prune
+    arrays = load(path)
+    dec = {k: v for k, v in arrays.items() if k.startswith(DEC_SCOPE) and not k.endswith(EMA_SUFFIX)}
+    if dec_spec is not None:
+        names = decoder_var_names(dec_spec)
+        chosen = [names[k] for k in prune.PRUNABLE if k in names and names[k] in dec]
+    else:
+        chosen = [k for k, v in dec.items() if np.ndim(v) == 2]
+    return dict(variables={k: (int(np.count_nonzero(dec[k])), int(np.size(dec[k]))) for k in chosen},
+                nonzero=int(sum(np.count_nonzero(v) for v in dec.values())), total=int(sum(np.size(v) for v in dec.values())))
+
+
 def restore(path, cnn_param_names, dec_spec, resume_training=False, exclude_scopes=None, head_names='unset'):
     """ModelBase.restore_model logic: returns (cnn_params | None, dec_params | None, extra).
     * every model variable present -> whole `Model/` (and, when resuming, step + Adam slots)

@@ -1106,13 +1106,21 @@ __global__ __launch_bounds__(256) void xent_maploss_kernel(float* __restrict__ l
 // ------------------------------------------------------------------ optimiser etc. ----
 // EMA: the launch also keeps tf.train.ExponentialMovingAverage's shadow of w, s += (w_new - s) * omd (omd = 1 - decay),
 // behind the same gate; the instantiation without it ignores s / omd (null / 0) and is the update as it always was.
-template <bool EMA>
+// MASKED (`--prune_sparsity`, prune.hip): bit (first + i) % 32 of mask word (first + i) / 32 says whether element i of this
+// range is live; a pruned element is left as the mask event wrote it (+0.0f in w, m, v and s) whatever its gradient is, a live
+// one gets the arithmetic of the unmasked instantiation.  `first` is the absolute index of the range's first element.
+__device__ __forceinline__ bool pruned_at(const uint32_t* __restrict__ mask, long a) {
+  return !((mask[a >> 5] >> (a & 31)) & 1u);
+}
+template <bool EMA, bool MASKED>
 __global__ void adam_tf_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                                float* __restrict__ v, long n, float lr_t, float b1, float b2, float eps, float l2,
-                               float gscale, const float* __restrict__ skip, float* __restrict__ s, float omd) {
+                               float gscale, const float* __restrict__ skip, float* __restrict__ s, float omd,
+                               const uint32_t* __restrict__ mask, long first) {
   if (skip && skip[0] != 0.f) return;                     // a voided step (comic_decoder_params::status): no update at all
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (MASKED && pruned_at(mask, first + i)) return;
   const float wi = w[i];
   const float ge = g[i] * gscale + l2 * wi;
   const float mi = m[i] + (ge - m[i]) * (1.f - b1);
@@ -1177,13 +1185,14 @@ __global__ void ln_tanh_bwd_rows_kernel(const float* __restrict__ dy, const floa
 }
 
 // tf.train.MomentumOptimizer (use_nesterov=False), ApplyMomentum [TF-1.9]: accum = momentum*accum + g; w -= lr*accum
-template <bool EMA>      // the shadow: as adam_tf_kernel
+template <bool EMA, bool MASKED>      // the shadow and the mask: as adam_tf_kernel
 __global__ void momentum_tf_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ accum, long n,
                                    float lr, float momentum, float l2, float gscale, const float* __restrict__ skip,
-                                   float* __restrict__ s, float omd) {
+                                   float* __restrict__ s, float omd, const uint32_t* __restrict__ mask, long first) {
   if (skip && skip[0] != 0.f) return;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (MASKED && pruned_at(mask, first + i)) return;
   const float wi = w[i];
   const float ge = g[i] * gscale + l2 * wi;
   const float ai = accum[i] * momentum + ge;
@@ -1571,16 +1580,18 @@ extern "C" int comic_xent_fwd_bwd(float* logits, const int32_t* targets_bt, cons
 extern "C" int comic_adam_tf(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1,
                              float beta2, float eps, float l2, float gscale, void* stream) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(adam_tf_kernel<false>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
-                     (long)n, lr_t, beta1, beta2, eps, l2, gscale, (const float*)nullptr, (float*)nullptr, 0.f);
+  hipLaunchKernelGGL((adam_tf_kernel<false, false>), dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
+                     (long)n, lr_t, beta1, beta2, eps, l2, gscale, (const float*)nullptr, (float*)nullptr, 0.f,
+                     (const uint32_t*)nullptr, 0L);
   COMIC_LAUNCH_CHECK("adam_tf");
   return 0;
 }
 extern "C" int comic_adam_tf_gated(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1,
                                    float beta2, float eps, float l2, float gscale, const float* skip_flag, void* stream) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(adam_tf_kernel<false>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
-                     (long)n, lr_t, beta1, beta2, eps, l2, gscale, skip_flag, (float*)nullptr, 0.f);
+  hipLaunchKernelGGL((adam_tf_kernel<false, false>), dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
+                     (long)n, lr_t, beta1, beta2, eps, l2, gscale, skip_flag, (float*)nullptr, 0.f,
+                     (const uint32_t*)nullptr, 0L);
   COMIC_LAUNCH_CHECK("adam_tf_gated");
   return 0;
 }
@@ -1590,9 +1601,29 @@ extern "C" int comic_adam_tf_ema(float* w, const float* g, float* m, float* v, i
   COMIC_REQUIRE(w && g && m && v && shadow && n > 0, "adam_tf_ema: null pointer or no elements");
   COMIC_REQUIRE(one_minus_decay > 0.f && one_minus_decay <= 1.f, "adam_tf_ema: one_minus_decay %g outside (0, 1]",
                 (double)one_minus_decay);
-  hipLaunchKernelGGL(adam_tf_kernel<true>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
-                     (long)n, lr_t, beta1, beta2, eps, l2, gscale, skip_flag, shadow, one_minus_decay);
+  hipLaunchKernelGGL((adam_tf_kernel<true, false>), dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
+                     (long)n, lr_t, beta1, beta2, eps, l2, gscale, skip_flag, shadow, one_minus_decay,
+                     (const uint32_t*)nullptr, 0L);
   COMIC_LAUNCH_CHECK("adam_tf_ema");
+  return 0;
+}
+// `--prune_sparsity`: the gated (shadow NULL) or EMA update of the live elements of a range that starts at element
+// `first` of the masked buffer
+extern "C" int comic_adam_tf_masked(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1,
+                                    float beta2, float eps, float l2, float gscale, const float* skip_flag, float* shadow,
+                                    float one_minus_decay, const uint32_t* mask, int64_t first, void* stream) {
+  COMIC_REQUIRE(w && g && m && v && mask && n > 0 && first >= 0,
+                "adam_tf_masked: null pointer, no elements or a negative first element");
+  COMIC_REQUIRE(!shadow || (one_minus_decay > 0.f && one_minus_decay <= 1.f),
+                "adam_tf_masked: one_minus_decay %g outside (0, 1]", (double)one_minus_decay);
+  const dim3 grid((unsigned)cdiv64(n, 256));
+  if (shadow)
+    hipLaunchKernelGGL((adam_tf_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, w, g, m, v, (long)n, lr_t, beta1,
+                       beta2, eps, l2, gscale, skip_flag, shadow, one_minus_decay, mask, (long)first);
+  else
+    hipLaunchKernelGGL((adam_tf_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, w, g, m, v, (long)n, lr_t, beta1,
+                       beta2, eps, l2, gscale, skip_flag, (float*)nullptr, 0.f, mask, (long)first);
+  COMIC_LAUNCH_CHECK("adam_tf_masked");
   return 0;
 }
 
@@ -1630,16 +1661,18 @@ extern "C" int comic_ln_tanh_bwd_rows(const float* dy, const float* y, const flo
 extern "C" int comic_momentum_tf(float* w, const float* g, float* accum, int64_t n, float lr, float momentum, float l2,
                                  float gscale, void* stream) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(momentum_tf_kernel<false>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, accum,
-                     (long)n, lr, momentum, l2, gscale, (const float*)nullptr, (float*)nullptr, 0.f);
+  hipLaunchKernelGGL((momentum_tf_kernel<false, false>), dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, accum,
+                     (long)n, lr, momentum, l2, gscale, (const float*)nullptr, (float*)nullptr, 0.f,
+                     (const uint32_t*)nullptr, 0L);
   COMIC_LAUNCH_CHECK("momentum_tf");
   return 0;
 }
 extern "C" int comic_momentum_tf_gated(float* w, const float* g, float* accum, int64_t n, float lr, float momentum, float l2,
                                        float gscale, const float* skip_flag, void* stream) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(momentum_tf_kernel<false>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, accum,
-                     (long)n, lr, momentum, l2, gscale, skip_flag, (float*)nullptr, 0.f);
+  hipLaunchKernelGGL((momentum_tf_kernel<false, false>), dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, accum,
+                     (long)n, lr, momentum, l2, gscale, skip_flag, (float*)nullptr, 0.f,
+                     (const uint32_t*)nullptr, 0L);
   COMIC_LAUNCH_CHECK("momentum_tf_gated");
   return 0;
 }
@@ -1649,9 +1682,27 @@ extern "C" int comic_momentum_tf_ema(float* w, const float* g, float* accum, int
   COMIC_REQUIRE(w && g && accum && shadow && n > 0, "momentum_tf_ema: null pointer or no elements");
   COMIC_REQUIRE(one_minus_decay > 0.f && one_minus_decay <= 1.f, "momentum_tf_ema: one_minus_decay %g outside (0, 1]",
                 (double)one_minus_decay);
-  hipLaunchKernelGGL(momentum_tf_kernel<true>, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g,
-                     accum, (long)n, lr, momentum, l2, gscale, skip_flag, shadow, one_minus_decay);
+  hipLaunchKernelGGL((momentum_tf_kernel<true, false>), dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g,
+                     accum, (long)n, lr, momentum, l2, gscale, skip_flag, shadow, one_minus_decay,
+                     (const uint32_t*)nullptr, 0L);
   COMIC_LAUNCH_CHECK("momentum_tf_ema");
+  return 0;
+}
+extern "C" int comic_momentum_tf_masked(float* w, const float* g, float* accum, int64_t n, float lr, float momentum,
+                                        float l2, float gscale, const float* skip_flag, float* shadow,
+                                        float one_minus_decay, const uint32_t* mask, int64_t first, void* stream) {
+  COMIC_REQUIRE(w && g && accum && mask && n > 0 && first >= 0,
+                "momentum_tf_masked: null pointer, no elements or a negative first element");
+  COMIC_REQUIRE(!shadow || (one_minus_decay > 0.f && one_minus_decay <= 1.f),
+                "momentum_tf_masked: one_minus_decay %g outside (0, 1]", (double)one_minus_decay);
+  const dim3 grid((unsigned)cdiv64(n, 256));
+  if (shadow)
+    hipLaunchKernelGGL((momentum_tf_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, w, g, accum, (long)n, lr,
+                       momentum, l2, gscale, skip_flag, shadow, one_minus_decay, mask, (long)first);
+  else
+    hipLaunchKernelGGL((momentum_tf_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, w, g, accum, (long)n, lr,
+                       momentum, l2, gscale, skip_flag, (float*)nullptr, 0.f, mask, (long)first);
+  COMIC_LAUNCH_CHECK("momentum_tf_masked");
   return 0;
 }
 

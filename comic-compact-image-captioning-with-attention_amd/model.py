@@ -25,7 +25,7 @@ import numpy as np
 
 from . import checkpoint as ckpt
 from . import decoder as cdec
-from . import encoder_head, nets, optim, streams
+from . import encoder_head, nets, optim, prune, streams
 from .trainer import DataParallel
 
 _SHARED = {}          # variable store of the current "graph" (tf.variable_scope('Model', AUTO_REUSE))
@@ -161,9 +161,11 @@ class ModelBase(object):
         clip = float(getattr(c, 'clip_gradient_norm', 0) or 0)      # per-variable tf.clip_by_norm (model_base.py:394-401)
         ema = float(getattr(c, 'ema_decay', 0) or 0)                # `--ema_decay`: a shadow of every trained variable
         if 'opt' not in share:
+            # `--prune_sparsity` / `--prune_keep_zeros`: the decoder's weight matrices only (prune.py)
+            pr = optim.PruneSpec.from_config(c, getattr(c, 'max_step', 0))
             share['opt'] = optim.make_optimiser(c.optimiser, self.decoder.params, epsilon=c.adam_epsilon,
                                                 l2_decay=getattr(c, 'l2_decay', 1e-5), clip_norm=clip,
-                                                ema_decay=ema)
+                                                ema_decay=ema, prune=pr)
             share['legacy_lr'] = c.lr_start
         self.opt = share['opt']
         if self.head is not None and 'opt_head' not in share:
@@ -188,6 +190,34 @@ class ModelBase(object):
     @property
     def has_ema(self):
         return any(o.ema is not None for o in self._optimisers())
+
+    @property
+    def prune_mask(self):
+        """The decoder optimiser's prune.PruneMask, or None."""
+        return getattr(self._share.get('opt'), 'mask', None)
+
+    def _restore_prune_mask(self, extra):
+        """A resumed run continues with exactly the mask it had (the words of `model-N`); --prune_keep_zeros builds its
+        frozen mask from the variables as loaded, and clears slots and shadow there."""
+        mask = self.prune_mask
+        if mask is None:
+            return
+        if extra and prune.MASK_KEY in extra:
+            mask.load(extra[prune.MASK_KEY])
+        elif mask.spec.keep_zeros:
+            self._share['opt'].prune_keep_zeros()
+
+    def prune_report(self):
+        """What a checkpoint save appends to model_size.txt while pruning is on (None otherwise): the step, the scheduled
+        sparsity, non-zero elements per prunable variable and of the whole decoder -- counted on the variables."""
+        mask = self.prune_mask
+        if mask is None:
+            return None
+        p = self.decoder.params.to_numpy()
+        counts = {k: (int(np.count_nonzero(p[k])), n) for k, _, n, _ in mask.segments}
+        s_t = None if mask.spec.keep_zeros else mask.spec.sparsity_at(self.global_step)
+        return prune.size_block(self.global_step, s_t, counts, sum(int(np.count_nonzero(v)) for v in p.values()),
+                                self.decoder.params.n_params())
 
     def _restore_ema(self, extra):
         """The shadows of `--ema_decay`.  TF's rule: a shadow starts at its variable's initial value -- so they are reset
@@ -245,6 +275,7 @@ class ModelBase(object):
         if not c.checkpoint_path:
             print('INFO: Training entire model from scratch.')
             self._restore_ema(None)
+            self._restore_prune_mask(None)
             return (self.lr if lr is None else lr) if self.is_training() else None
         path = c.checkpoint_path
         if os.path.isdir(path):
@@ -314,6 +345,7 @@ class ModelBase(object):
                     enc.import_slots(ow.v, ob.v, extra, 'Adam_1', sc)
             print('INFO: Resume training from checkpoint: {}'.format(path))
         self._restore_ema(extra if 'opt' in self._share else None)
+        self._restore_prune_mask(extra if 'opt' in self._share else None)
         if not self.is_training():
             return None
         if lr is not None and getattr(c, 'legacy', False):
@@ -343,6 +375,8 @@ class ModelBase(object):
             for o in self._share['opt_cnn'][:2]:
                 bufs += [o.m.data, o.v.data]
         bufs += [o.ema.data for o in self._optimisers() if o.ema is not None]
+        if self.prune_mask is not None:
+            bufs.append(self.prune_mask.words)
         for b in bufs:
             dp.dist.broadcast(b, 0)
         step = self.torch.tensor([self.global_step], dtype=self.torch.int64, device=self.device)
@@ -368,6 +402,8 @@ class ModelBase(object):
             if o.ema is not None:       # the shadows travel with the slots: flat, or per variable under TF's average_name
                 extra.update(ckpt.ema_to_tf(self.spec, o.ema.to_numpy()) if fmt == 'tf' else
                              {'optimise/caption/ema': o.ema.flat.cpu().numpy()})
+            if o.mask is not None:      # the mask words, in both containers: a resumed run continues with exactly this mask
+                extra[prune.MASK_KEY] = o.mask.to_numpy()
         if self.head is not None:
             extra.update(self.head.export_params())
             if not compact and 'opt_head' in self._share:

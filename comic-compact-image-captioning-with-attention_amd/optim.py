@@ -13,6 +13,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from .prune import PruneMask, PruneSpec, prune_sparsity_at  # noqa: F401  (the schedule is part of this module's interface)
 
 
 def cosine_lr(step, max_step, lr_start, lr_end):
@@ -57,15 +58,20 @@ class GradClip:
         self.chunks = torch.from_numpy(np.asarray(rows, np.int64).reshape(-1, 5)).to(params.device)
         self.partial = torch.zeros(max(1, self.n_chunks), dtype=torch.float32, device=params.device)
 
-    def apply(self, params, grads, l2, grad_scale, skip=None):
+    def apply(self, params, grads, l2, grad_scale, skip=None, mask=None):
+        """mask (a prune.PruneMask): the gradients of pruned weights are zeroed first -- the norm of a variable must not count
+        weights that no longer exist (one extra launch, in this combination only)."""
         st = skip if skip is not None else getattr(grads, 'status', None)
+        if mask is not None:
+            mask.mask_buffer(grads)
         L.check(self.lib.comic_clip_by_norm(grads.data.data_ptr(), params.data.data_ptr(), self.chunks.data_ptr(),
                                             self.n_chunks, l2, grad_scale, self.clip_norm, self.partial.data_ptr(),
                                             st.data_ptr() if st is not None else None, L.stream_ptr()), 'clip_by_norm')
 
 
 class AdamTF:
-    def __init__(self, params, beta1=0.9, beta2=0.999, epsilon=1e-2, l2_decay=1e-5, clip_norm=0.0, ema_decay=0.0):
+    def __init__(self, params, beta1=0.9, beta2=0.999, epsilon=1e-2, l2_decay=1e-5, clip_norm=0.0, ema_decay=0.0,
+                 prune=None):
         self.lib = L.load()
         self.params = params
         self.m = params.like()
@@ -74,6 +80,21 @@ class AdamTF:
         self.t = 0                      # number of applied updates (== global_step)
         self.clip = GradClip(params, clip_norm) if clip_norm and clip_norm > 0 else None
         self._ema_init(ema_decay)
+        self._prune_init(prune)
+
+    def _prune_init(self, prune):
+        """`prune` (a prune.PruneSpec or None): a bit mask over the flat buffer; the update launches are the masked forms
+        (comic_*_tf_masked) and a mask event (comic_prune_select on w, m, v and the shadow) follows the update whose count is
+        on the schedule.  None: no mask, the launches of the gated / EMA forms."""
+        self.mask = PruneMask(self.params, prune) if prune is not None else None
+
+    def prune_keep_zeros(self):
+        """--prune_keep_zeros: freeze the zeros of the variables as they are now (call after the checkpoint is loaded)."""
+        self.mask.from_zeros(self.m, self.v, self.ema)
+
+    def _prune_event(self):
+        if self.mask is not None and self.mask.spec.event_at(self.t):
+            self.mask.event(self.t, self.m, self.v, self.ema)
 
     def _ema_init(self, ema_decay):
         """`--ema_decay d` (tf.train.ExponentialMovingAverage): a shadow of every variable, updated inside the update
@@ -105,11 +126,19 @@ class AdamTF:
         st = skip if skip is not None else getattr(grads, 'status', None)
         if self.clip is not None:
             assert ranges is None, 'per-variable clipping reads whole variables: one launch over the flat buffer'
-            self.clip.apply(self.params, grads, self.l2, grad_scale, skip=st)
+            self.clip.apply(self.params, grads, self.l2, grad_scale, skip=st, mask=self.mask)
         omd = 1.0 - ema_rate(self.ema_decay, self.t) if self.ema is not None else 0.0
         for i, (lo, hi) in enumerate(ranges or [(0, self.params.numel)]):
             if before_range is not None:
                 before_range(i)
+            if self.mask is not None:
+                L.check(self.lib.comic_adam_tf_masked(self.params.data.data_ptr() + 4 * lo, grads.data.data_ptr() + 4 * lo,
+                                                      self.m.data.data_ptr() + 4 * lo, self.v.data.data_ptr() + 4 * lo, hi - lo,
+                                                      lr_t, self.beta1, self.beta2, self.eps, self.l2, grad_scale,
+                                                      st.data_ptr() if st is not None else None,
+                                                      self.ema.data.data_ptr() + 4 * lo if self.ema is not None else None, omd,
+                                                      self.mask.words.data_ptr(), lo, L.stream_ptr()), 'adam_tf_masked')
+                continue
             if self.ema is not None:
                 L.check(self.lib.comic_adam_tf_ema(self.params.data.data_ptr() + 4 * lo, grads.data.data_ptr() + 4 * lo,
                                                    self.m.data.data_ptr() + 4 * lo, self.v.data.data_ptr() + 4 * lo, hi - lo,
@@ -121,11 +150,14 @@ class AdamTF:
                                                  self.m.data.data_ptr() + 4 * lo, self.v.data.data_ptr() + 4 * lo, hi - lo,
                                                  lr_t, self.beta1, self.beta2, self.eps, self.l2, grad_scale,
                                                  st.data_ptr() if st is not None else None, L.stream_ptr()), 'adam_tf')
+        self._prune_event()     # behind every range's update, on the step's stream
 
     def state_dict(self):
         sd = dict(t=self.t, m=self.m.data.clone(), v=self.v.data.clone())
         if self.ema is not None:
             sd['ema'] = self.ema.data.clone()
+        if self.mask is not None:
+            sd['prune_mask'] = self.mask.words.clone()
         return sd
 
     def load_state_dict(self, sd):
@@ -134,6 +166,8 @@ class AdamTF:
         self.v.data.copy_(sd['v'])
         if self.ema is not None and 'ema' in sd:
             self.ema.data.copy_(sd['ema'])
+        if self.mask is not None and 'prune_mask' in sd:
+            self.mask.words.copy_(sd['prune_mask'])
 
 
 class MomentumTF:
@@ -141,7 +175,7 @@ class MomentumTF:
     `--optimiser sgd`): accum = momentum*accum + g, w -= lr*accum, with the same L2 fold as AdamTF.  Same interface
     (`t`, `step`, `m` = the accumulator; `v` stays zero so checkpoints keep one layout)."""
 
-    def __init__(self, params, momentum=0.9, l2_decay=1e-5, clip_norm=0.0, ema_decay=0.0, **_):
+    def __init__(self, params, momentum=0.9, l2_decay=1e-5, clip_norm=0.0, ema_decay=0.0, prune=None, **_):
         self.lib = L.load()
         self.params = params
         self.m = params.like()
@@ -151,9 +185,13 @@ class MomentumTF:
         self.t = 0
         self.clip = GradClip(params, clip_norm) if clip_norm and clip_norm > 0 else None
         self._ema_init(ema_decay)
+        self._prune_init(prune)
 
     _ema_init = AdamTF._ema_init
     ema_reset = AdamTF.ema_reset
+    _prune_init = AdamTF._prune_init
+    _prune_event = AdamTF._prune_event
+    prune_keep_zeros = AdamTF.prune_keep_zeros
 
     def step(self, grads, lr, grad_scale=1.0, skip=None, ranges=None, before_range=None):
         """ranges / before_range: as AdamTF.step."""
@@ -161,11 +199,19 @@ class MomentumTF:
         st = skip if skip is not None else getattr(grads, 'status', None)
         if self.clip is not None:
             assert ranges is None, 'per-variable clipping reads whole variables: one launch over the flat buffer'
-            self.clip.apply(self.params, grads, self.l2, grad_scale, skip=st)
+            self.clip.apply(self.params, grads, self.l2, grad_scale, skip=st, mask=self.mask)
         omd = 1.0 - ema_rate(self.ema_decay, self.t) if self.ema is not None else 0.0
         for i, (lo, hi) in enumerate(ranges or [(0, self.params.numel)]):
             if before_range is not None:
                 before_range(i)
+            if self.mask is not None:
+                L.check(self.lib.comic_momentum_tf_masked(self.params.data.data_ptr() + 4 * lo, grads.data.data_ptr() + 4 * lo,
+                                                          self.m.data.data_ptr() + 4 * lo, hi - lo, lr, self.momentum, self.l2,
+                                                          grad_scale, st.data_ptr() if st is not None else None,
+                                                          self.ema.data.data_ptr() + 4 * lo if self.ema is not None else None,
+                                                          omd, self.mask.words.data_ptr(), lo, L.stream_ptr()),
+                        'momentum_tf_masked')
+                continue
             if self.ema is not None:
                 L.check(self.lib.comic_momentum_tf_ema(self.params.data.data_ptr() + 4 * lo, grads.data.data_ptr() + 4 * lo,
                                                        self.m.data.data_ptr() + 4 * lo, hi - lo, lr, self.momentum, self.l2,
@@ -177,16 +223,18 @@ class MomentumTF:
                                                      self.m.data.data_ptr() + 4 * lo, hi - lo, lr, self.momentum, self.l2,
                                                      grad_scale, st.data_ptr() if st is not None else None, L.stream_ptr()),
                     'momentum_tf')
+        self._prune_event()
 
     state_dict = AdamTF.state_dict
     load_state_dict = AdamTF.load_state_dict
 
 
-def make_optimiser(name, params, epsilon=1e-2, l2_decay=1e-5, clip_norm=0.0, ema_decay=0.0):
+def make_optimiser(name, params, epsilon=1e-2, l2_decay=1e-5, clip_norm=0.0, ema_decay=0.0, prune=None):
     """`_get_optimiser` (model_base.py:852-883) + create_train_op's clip_gradient_norm (model_base.py:394-401);
-    ema_decay > 0: a tf.train.ExponentialMovingAverage shadow of the variables (`opt.ema`)."""
+    ema_decay > 0: a tf.train.ExponentialMovingAverage shadow of the variables (`opt.ema`); prune (a prune.PruneSpec):
+    gradual magnitude pruning of the variables it names (`opt.mask`)."""
     if name == 'adam':
-        return AdamTF(params, epsilon=epsilon, l2_decay=l2_decay, clip_norm=clip_norm, ema_decay=ema_decay)
+        return AdamTF(params, epsilon=epsilon, l2_decay=l2_decay, clip_norm=clip_norm, ema_decay=ema_decay, prune=prune)
     if name == 'sgd':
-        return MomentumTF(params, l2_decay=l2_decay, clip_norm=clip_norm, ema_decay=ema_decay)
+        return MomentumTF(params, l2_decay=l2_decay, clip_norm=clip_norm, ema_decay=ema_decay, prune=prune)
     raise ValueError('Unknown optimiser.')

@@ -38,6 +38,14 @@ def _model_size_report(m, log_path):
     return n
 
 
+def _prune_size_report(m, log_path):
+    """While pruning is on, every checkpoint save appends the step, the scheduled sparsity and the non-zero counts."""
+    block = m.prune_report()
+    if block is not None:
+        with open(pjoin(log_path, 'model_size.txt'), 'a') as f:
+            f.write(block)
+
+
 def train_fn(config, device='cuda:0', dp=None):
     """Main training function. To be called by `try_to_train()`."""
     print('INFO: Logging to `{}`.'.format(config.log_path))
@@ -101,6 +109,7 @@ def _train_loop(inputs_man, device, dp):
                 if m_train.has_ema:             # --ema_decay: the averaged weights as a compact checkpoint of their own
                     m_train.save_ema(c.save_path + '_ema', max_to_keep=c.max_saves)
                 m_train.save(c.save_path, compact=False, max_to_keep=2)
+                _prune_size_report(m_train, c.log_path)
             if m_valid is not None:
                 _run_eval_loop(c, m_valid, global_step)
         if (step + 1) % num_batches == 0:
@@ -324,6 +333,7 @@ def _scst_loop(inputs_man, idx_ngram, device, dp):
             if m_train.has_ema:
                 m_train.save_ema(c.save_path + '_ema', max_to_keep=c.max_saves)
             m_train.save(c.save_path, compact=False, max_to_keep=2)
+            _prune_size_report(m_train, c.log_path)
         if (step + 1) % num_batches == 0:
             t = time.time() - start_epoch
             print('\n\n>>> Epoch {:3d} complete'.format(epoch))

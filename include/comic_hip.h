@@ -843,6 +843,41 @@ int comic_adam_tf_ema(float* w, const float* g, float* m, float* v, int64_t n, f
                       void* stream);
 int comic_momentum_tf_ema(float* w, const float* g, float* accum, int64_t n, float lr, float momentum, float l2,
                           float gscale, const float* skip_flag, float* shadow, float one_minus_decay, void* stream);
+/* Gradual magnitude pruning (`--prune_sparsity`, Zhu & Gupta 2017; csrc/prune.hip).  The MASK of a flat buffer of n_total
+ * floats is ceil(n_total / 32) uint32 words: bit i % 32 of word i / 32 is 1 while element i is live; padding and variables
+ * that are never pruned keep their 1.  SEGMENTS: n_seg records of three int64 on the device, (first element, elements, group),
+ * ascending by first element and not overlapping -- the prunable variables without their alignment padding; group in
+ * [0, n_groups).  A segment that does not lie inside [0, n_total) or names an unknown group is ignored.
+ *
+ * comic_prune_select: one mask event.  For every group g the elements of its segments are ordered: already pruned elements
+ * first, then the live ones by ascending |w| compared on the IEEE bits of |w| (-0.0 == +0.0, -x == +x, denormals in their
+ * place), ties by lowest flat index; the first targets[g] (int64 on the device, clamped to the group's size) of that
+ * order are pruned afterwards.  A target that is not above the group's pruned count changes nothing: masks are sticky.  A
+ * newly pruned element gets its bit cleared and +0.0f in w, m, v and (when not NULL) shadow; every other bit and float of
+ * the five buffers keeps its bits.  Exact and independent of the order of execution (integer histograms, no float atomics,
+ * no sort): two runs on the same input give the same bytes.  workspace: comic_prune_workspace_bytes(n_total, n_seg,
+ * n_groups) bytes (-1: bad arguments), cleared by the call.
+ * comic_prune_mask_buffer: x[i] = +0.0f where bit first_bit + i of the mask is clear, i < n (the gradient in front of
+ * comic_clip_by_norm; the slots of a run started with --prune_keep_zeros).
+ * comic_prune_mask_from_zeros: the mask of --prune_keep_zeros: all ones, then bit i cleared where w[i] == 0 inside a segment
+ * (the groups of the table are not read). */
+int64_t comic_prune_workspace_bytes(int64_t n_total, int n_seg, int n_groups);
+int comic_prune_select(float* w, uint32_t* mask, int64_t n_total, const int64_t* segments, int n_seg,
+                       const int64_t* targets, int n_groups, float* m, float* v, float* shadow, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int comic_prune_mask_buffer(float* x, const uint32_t* mask, int64_t first_bit, int64_t n, void* stream);
+int comic_prune_mask_from_zeros(const float* w, uint32_t* mask, int64_t n_total, const int64_t* segments, int n_seg,
+                                void* stream);
+/* The gated (shadow == NULL; one_minus_decay unread) or EMA (shadow != NULL) updates under such a mask: element i of the range
+ * is element first + i of the masked buffer (first >= 0; a range of DataParallel.chunk_bounds starts on a word boundary, any
+ * other start works as well).  A live element gets the bits of comic_*_tf_gated / comic_*_tf_ema; a pruned one is left as the
+ * mask event wrote it, +0.0f in w, m, v / accum and shadow, whatever its gradient is; a voided step leaves everything. */
+int comic_adam_tf_masked(float* w, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
+                         float epsilon, float l2, float gscale, const float* skip_flag, float* shadow,
+                         float one_minus_decay, const uint32_t* mask, int64_t first, void* stream);
+int comic_momentum_tf_masked(float* w, const float* g, float* accum, int64_t n, float lr, float momentum, float l2,
+                             float gscale, const float* skip_flag, float* shadow, float one_minus_decay,
+                             const uint32_t* mask, int64_t first, void* stream);
 /* Gradient clipping of `--clip_gradient_norm` (train.py:137 -> model_base.py:394-401: slim.learning.create_train_op(
  * clip_gradient_norm=c) = clip_gradient_norms [TF-1.9 slim]: tf.clip_by_norm on EVERY variable's gradient by that tensor's
  * own L2 norm, after the gradient multipliers).  The clipped quantity is g_eff = g*gscale + l2*w (the L2 term is part of

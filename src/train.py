@@ -2,7 +2,7 @@
 """train.py -- same flags, mode chaining, run-directory naming and kwargs as the reference
 CLI (reference src/train.py:25-312), driving the MI355X-native path.
 
-Differences (all additive): `--cnn_dtype {bf16,f16,f32,bf16x3}`, `--checkpoint_format {npz,tf}`, `--ema_decay`, `--label_smoothing`,
+Differences (all additive): `--cnn_dtype {bf16,f16,f32,bf16x3}`, `--checkpoint_format {npz,tf}`, `--ema_decay`, `--prune_*`, `--label_smoothing`,
 `--distill_checkpoints / _weight / _top_k / _temperature / _weights`; launched under
 `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel (one process
 per GPU, RCCL gradient all-reduce); the slim checkpoint is not downloaded (no network):
@@ -115,6 +115,24 @@ def create_parser():
     a('--distill_top_k', type=int, default=16, help='Entries of the teacher distribution kept per token (1 ... 32).')
     a('--distill_temperature', type=float, default=1.0, help='Temperature of the teacher softmax.')
     a('--distill_weights', type=str, default='', help='Weights w1,... of several teachers (>= 0, summing to 1; default uniform).')
+    a('--prune_sparsity', type=float, default=0.0,
+      help='Gradual magnitude pruning (Zhu & Gupta 2017) of the decoder\'s weight matrices towards this share of zeros, the '
+           'masks chosen and kept on the device; the run directory gets `_pr<s>` (`_pr<s>g` for --prune_scope global).  '
+           '0 = off, else in (0, 1).')
+    a('--prune_start_step', type=int, default=-1, help='First mask event (default: 10 %% of the run\'s steps).')
+    a('--prune_end_step', type=int, default=-1,
+      help='Last mask event, where --prune_sparsity is reached (default: 60 %% of the run\'s steps, moved down to a multiple of '
+           '--prune_every behind the start; given, it must be one).')
+    a('--prune_every', type=int, default=100, help='Optimiser updates between two mask events.')
+    a('--prune_scope', type=str, default='layer', choices=['layer', 'global'],
+      help='`layer`: every variable reaches the sparsity on its own; `global`: the smallest weights of all prunable variables '
+           'together.')
+    a('--prune_variables', type=str, default='',
+      help='Comma list of the decoder variables to prune (default: every one with two dimensions: W_init, K, K_c, W_m, W_v, '
+           'W_q, W_a, W_o, emb, where present).')
+    a('--prune_keep_zeros', action='store_true',
+      help='A later stage on a pruned checkpoint: the zeros of the prunable variables as loaded stay zero (a frozen mask, no '
+           'schedule; not with --prune_sparsity).')
     return p
 
 
@@ -144,19 +162,23 @@ def build_kwargs(args):
     # a soft-target run gets a directory of its own: `_ls<eps>` for both XE modes (cnn_finetune continues the decoder run
     # of the same --label_smoothing), `_kd<weight>_k<K>_t<temperature>` for a distilled decoder run
     smooth, distil = soft_dir_suffixes(args)
+    # a pruned run likewise, `_pr<s>[g]` right behind the name -- of the stage that prunes only: it starts from the
+    # checkpoint of the plain earlier stage, and a later stage names the pruned one by `--name <name>_pr<s>`
+    from comic_amd import prune
+    pruned = name + prune.dir_suffix(args)
     dec_dir = pjoin(log_root, '{}{}_run_{:02d}'.format(name, smooth, args.run))
     cnnft_dir = pjoin(log_root, '{}{}_cnnFT_run_{:02d}'.format(name, smooth, args.run))
     train_fn_name = 'train_fn'
     if args.train_mode == 'decoder':
         assert args.freeze_scopes == 'Model/encoder/cnn'
-        log_path = pjoin(log_root, '{}{}{}_run_{:02d}'.format(name, smooth, distil, args.run))
+        log_path = pjoin(log_root, '{}{}{}_run_{:02d}'.format(pruned, smooth, distil, args.run))
     elif args.train_mode == 'cnn_finetune':
         if args.legacy:
             raise NotImplementedError
         if not os.path.exists(dec_dir):
             raise ValueError('Decoder training log path not found: {}'.format(dec_dir))
         args.lr_start, args.max_epoch, args.freeze_scopes, args.checkpoint_path = 1e-3, 10, '', dec_dir
-        log_path = cnnft_dir
+        log_path = pjoin(log_root, '{}{}_cnnFT_run_{:02d}'.format(pruned, smooth, args.run))
     else:
         if args.legacy:
             raise NotImplementedError
@@ -168,7 +190,7 @@ def build_kwargs(args):
         scst = 'beam_{}_CrD_{}_B1_{}_B4_{}'.format(args.scst_beam_size, args.scst_weight_ciderD,
                                                    args.scst_weight_bleu[0], args.scst_weight_bleu[-1])
         scst += scst_dir_suffix(args)
-        log_path = pjoin(log_root, '{}_cnnFT_SCST_{}_run_{:02d}'.format(name, scst, args.run))
+        log_path = pjoin(log_root, '{}_cnnFT_SCST_{}_run_{:02d}'.format(pruned, scst, args.run))
         train_fn_name = 'train_fn_scst'
     args.resume_training = overwrite = os.path.exists(log_path)
     for k, v in list(args.__dict__.items()):
@@ -187,6 +209,7 @@ def build_kwargs(args):
     if not kwargs.get('distill_checkpoints'):
         for k in ('distill_checkpoints', 'distill_weight', 'distill_top_k', 'distill_temperature', 'distill_weights'):
             kwargs.pop(k, None)
+    prune.pop_defaults(kwargs)                  # and the pruning flags
     check_supported(kwargs)
     return kwargs, train_fn_name, overwrite
 
@@ -204,6 +227,14 @@ def refuse_bad_ema_decay(ema_decay):
     d = float(ema_decay or 0.0)
     if not 0.0 <= d < 1.0:
         raise ValueError('--ema_decay must be in [0, 1) (0 = off), got {}'.format(ema_decay))
+
+
+def refuse_bad_prune_options(kw):
+    """--prune_*: values out of range, --prune_keep_zeros with --prune_sparsity, schedule flags without --prune_sparsity,
+    unknown or never-pruned variable names, an explicit end that is no multiple of --prune_every behind the start.  Called
+    before anything touches the GPU."""
+    from comic_amd import prune
+    prune.refuse_bad_prune_options(kw)
 
 
 def refuse_bad_soft_options(kw):
@@ -273,6 +304,7 @@ def check_supported(kw):
     refuse_bad_ema_decay(kw.get('ema_decay'))
     refuse_bad_scst_options(kw)
     refuse_bad_soft_options(kw)
+    refuse_bad_prune_options(kw)
     bad = []
     # --initialiser: `he` / `none` select TensorFlow's default initialiser in the reference (model_base.py:823-831:
     # every value but `xavier` returns None), which for these float variables is glorot_uniform == Xavier-uniform
@@ -287,6 +319,7 @@ def main(argv=None):
     refuse_bad_ema_decay(args.ema_decay)
     refuse_bad_scst_options(vars(args))
     refuse_bad_soft_options(vars(args))
+    refuse_bad_prune_options(vars(args))
     import torch
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
