@@ -24,6 +24,19 @@ class ImageDesc(C.Structure):           # struct comic_image_desc
                 ('ox', c_int32), ('sy', C.c_float), ('sx', C.c_float)]
 
 
+class ImageAug(C.Structure):            # struct comic_image_aug, one beside every comic_image_desc
+    _fields_ = [('mode', c_int32), ('cy', c_int32), ('cx', c_int32), ('ch', c_int32), ('cw', c_int32), ('sy', C.c_float),
+                ('sx', C.c_float), ('ops', C.c_uint8 * 4), ('brightness', C.c_float), ('saturation', C.c_float),
+                ('hue', C.c_float), ('contrast', C.c_float)]
+
+
+# ... as a numpy structured dtype (a batch's records are filled in one piece)
+IMAGE_AUG_DTYPE = [('mode', '<i4'), ('cy', '<i4'), ('cx', '<i4'), ('ch', '<i4'), ('cw', '<i4'), ('sy', '<f4'), ('sx', '<f4'),
+                   ('ops', 'u1', 4), ('brightness', '<f4'), ('saturation', '<f4'), ('hue', '<f4'), ('contrast', '<f4')]
+AUG_LEGACY, AUG_BOX = 0, 1              # COMIC_AUG_*
+AUG_OP_NONE, AUG_OP_BRIGHTNESS, AUG_OP_SATURATION, AUG_OP_HUE, AUG_OP_CONTRAST = 0, 1, 2, 3, 4      # COMIC_AUG_OP_*
+
+
 class ConvWeight(C.Structure):
     _fields_ = [('w', c_void_p), ('scale', c_void_p), ('shift', c_void_p), ('w_frag', c_void_p)]
 
@@ -180,6 +193,10 @@ _SIGS = {
     'comic_jpeg_pixels': (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P]),
     'comic_jpeg_preprocess': (c_int, [P, P, c_int, c_int, P, P, P, P, c_int, c_int, c_int, P]),
     'comic_jpeg_preprocess_packed': (c_int, [P, P, c_int, c_int, P, P, P, P, c_int, c_int, c_int, P]),
+    # `--cnn_input_augment_crop / _color`: the same with a comic_image_aug record per image and the workspace of the sums
+    'comic_image_preprocess_aug': (c_int, [P, P, P, c_int, P, c_int, P, c_int, c_int, c_int, P]),
+    'comic_jpeg_preprocess_aug': (c_int, [P, P, c_int, c_int, P, P, P, P, c_int, P, P, c_int, c_int, c_int, P]),
+    'comic_jpeg_preprocess_packed_aug': (c_int, [P, P, c_int, c_int, P, P, P, P, c_int, P, P, c_int, c_int, c_int, P]),
     'comic_weighted_sum_tb': (c_int, [P, P, c_int, c_int, P, P]),
     'comic_lstm_gates_fwd': (c_int, [P, P, P, P, P, P, P, P, c_float, P, c_int, P, P, c_int, c_int, P]),
     'comic_lstm_gates_bwd': (c_int, [P, P, P, P, P, c_float, P, c_int, P, P, P, c_int, c_int, P]),

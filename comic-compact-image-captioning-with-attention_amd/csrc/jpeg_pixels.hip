@@ -11,7 +11,7 @@
 //   jpeg_idct_kernel   one thread per 8x8 block: 128 B of coefficients in registers, both passes, 8 rows of 8 bytes out
 //                      into the component's plane (neighbouring threads write neighbouring 8-byte pieces of a row)
 //   jpeg_colour_kernel one thread per four pixels of a row: Y + the chroma neighbourhood -> 12 bytes of RGB
-#include "common.h"
+#include "augment_dev.h"
 #include "../../include/comic_jpeg.h"
 
 namespace {
@@ -241,20 +241,6 @@ __global__ __launch_bounds__(64) void jpeg_colour_kernel(const comic_jpeg_info* 
 // roundings, contraction off) whose four taps per output pixel are converted from the planes on the fly: the RGB image is
 // never written (59 MB per 64 images of 640 x 480, and the 88 us of jpeg_colour_kernel).  Images of the PIL path (ncomp == 0)
 // are read from the RGB blob as before.
-struct ImgDesc {                  // comic_image_desc
-  int64_t offset;
-  int32_t in_h, in_w;
-  int32_t flip, oy, ox;
-  float sy, sx;
-};
-
-__device__ __forceinline__ float lerp_rn(float a, float b, float w) {
-#pragma clang fp contract(off)
-  const float d = b - a;
-  const float m = d * w;
-  return a + m;
-}
-
 template <int HS, int VS>
 __device__ __forceinline__ void tap_rgb(const comic_jpeg_info* in, const uint8_t* __restrict__ planes, int y, int x, int (&rgb)[3]) {
   const uint8_t* base = planes + in->coef_base;
@@ -284,40 +270,87 @@ __device__ __forceinline__ void tap(const comic_jpeg_info* in, const uint8_t* __
   }
 }
 
+__device__ __forceinline__ void read_taps(const comic_jpeg_info* in, const uint8_t* __restrict__ planes,
+                                          const uint8_t* __restrict__ src, int in_w, const Taps& t, float (&v)[3]) {
+  int t00[3], t01[3], t10[3], t11[3];
+  tap(in, planes, src, in_w, t.y0, t.x0, t00);
+  tap(in, planes, src, in_w, t.y0, t.x1, t01);
+  tap(in, planes, src, in_w, t.y1, t.x0, t10);
+  tap(in, planes, src, in_w, t.y1, t.x1, t11);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = bilinear_u8(t00[c], t01[c], t10[c], t11[c], t.wy, t.wx);
+}
+
 __global__ __launch_bounds__(256) void jpeg_preprocess_kernel(const comic_jpeg_info* __restrict__ infos,
                                                               const uint8_t* __restrict__ planes, const uint8_t* __restrict__ blob,
                                                               const ImgDesc* __restrict__ desc, float* __restrict__ dst, int out_h,
                                                               int out_w, int resize) {
-#pragma clang fp contract(off)
   const int i = blockIdx.y;
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= out_h * out_w) return;
-  const comic_jpeg_info* in = infos + i;
   const ImgDesc d = desc[i];
-  const int y = p / out_w, x = p % out_w;
-  const int Y = d.oy + y;
-  const int X = d.flip ? resize - 1 - (d.ox + x) : d.ox + x;
-  const float ys = (float)Y * d.sy, xs = (float)X * d.sx;
-  const int y0 = (int)floorf(ys), x0 = (int)floorf(xs);
-  const int y1 = min((int)ceilf(ys), d.in_h - 1), x1 = min((int)ceilf(xs), d.in_w - 1);
-  const float wy = ys - (float)y0, wx = xs - (float)x0;
-  const float inv255 = (float)(1.0 / 255);
-  const uint8_t* src = blob + d.offset;
-  int t00[3], t01[3], t10[3], t11[3];
-  tap(in, planes, src, d.in_w, y0, x0, t00);
-  tap(in, planes, src, d.in_w, y0, x1, t01);
-  tap(in, planes, src, d.in_w, y1, x0, t10);
-  tap(in, planes, src, d.in_w, y1, x1, t11);
+  float v[3];
+  read_taps(infos + i, planes, blob + d.offset, d.in_w, taps_legacy(d, p / out_w, p % out_w, resize), v);
   float* o = dst + ((size_t)i * out_h * out_w + p) * 3;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float p00 = (float)t00[c] * inv255, p01 = (float)t01[c] * inv255;
-    const float p10 = (float)t10[c] * inv255, p11 = (float)t11[c] * inv255;
-    const float top = lerp_rn(p00, p01, wx), bot = lerp_rn(p10, p11, wx);
-    const float v = lerp_rn(top, bot, wy);
-    const float centred = v - 0.5f;
-    o[c] = centred * 2.0f;
+  for (int c = 0; c < 3; ++c) o[c] = to_network_range(v[c]);
+}
+
+// ... with a comic_image_aug record beside every descriptor (image_preprocess_aug_kernel of csrc/preprocess.hip, the taps
+// converted from the planes)
+template <bool SUMS>
+__global__ __launch_bounds__(256) void jpeg_preprocess_aug_kernel(const comic_jpeg_info* __restrict__ infos,
+                                                                  const uint8_t* __restrict__ planes, const uint8_t* __restrict__ blob,
+                                                                  const ImgDesc* __restrict__ desc, const ImgAug* __restrict__ aug,
+                                                                  long long* __restrict__ sums, float* __restrict__ dst, int out_h,
+                                                                  int out_w, int resize) {
+  const int i = blockIdx.y;
+  const ImgAug a = aug[i];
+  const int at = aug_contrast_at(a);
+  if (SUMS && at == 4) return;
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = p < out_h * out_w;
+  if (!SUMS && !live) return;
+  float v[3] = {0.f, 0.f, 0.f};
+  if (live) {
+    const ImgDesc d = desc[i];
+    const int y = p / out_w, x = p % out_w;
+    read_taps(infos + i, planes, blob + d.offset, d.in_w,
+              a.mode == COMIC_AUG_BOX ? taps_box(d, a, y, x, out_w) : taps_legacy(d, y, x, resize), v);
   }
+  if (SUMS) {
+    if (live) colour_ops_until(a, at, v);
+    aug_accumulate(v, live, sums + 3 * i);
+  } else {
+    float mean[3] = {0.f, 0.f, 0.f};
+    if (at < 4) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) mean[c] = aug_mean(sums[3 * i + c], out_h * out_w);
+    }
+    colour_ops_all(a, mean, v);
+    float* o = dst + ((size_t)i * out_h * out_w + p) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = to_network_range(v[c]);
+  }
+}
+
+// the launches behind the inverse DCT of the two _aug entries
+int launch_preprocess_aug(const void* infos, const uint8_t* planes, const uint8_t* blob, const void* desc, const void* aug,
+                          int contrast, void* aug_ws, int n, float* dst, int out_h, int out_w, int resize, hipStream_t st) {
+  const dim3 grid(cdiv(out_h * out_w, 256), n);
+  if (contrast) {
+    if (hipMemsetAsync(aug_ws, 0, (size_t)n * 3 * sizeof(long long), st) != hipSuccess) {
+      comic_set_error("jpeg_preprocess_aug: clearing the workspace failed");
+      return 1;
+    }
+    hipLaunchKernelGGL(jpeg_preprocess_aug_kernel<true>, grid, dim3(256), 0, st, (const comic_jpeg_info*)infos, planes, blob,
+                       (const ImgDesc*)desc, (const ImgAug*)aug, (long long*)aug_ws, dst, out_h, out_w, resize);
+    COMIC_LAUNCH_CHECK("jpeg_preprocess_aug (sums)");
+  }
+  hipLaunchKernelGGL(jpeg_preprocess_aug_kernel<false>, grid, dim3(256), 0, st, (const comic_jpeg_info*)infos, planes, blob,
+                     (const ImgDesc*)desc, (const ImgAug*)aug, (long long*)aug_ws, dst, out_h, out_w, resize);
+  COMIC_LAUNCH_CHECK("jpeg_preprocess_aug");
+  return 0;
 }
 
 }  // namespace
@@ -329,7 +362,6 @@ extern "C" int comic_jpeg_preprocess(const int16_t* coef, const void* infos, int
   COMIC_REQUIRE(n > 0 && n <= 65535 && max_blocks >= 0 && out_h > 0 && out_w > 0 && resize >= out_h && resize >= out_w,
                 "jpeg_preprocess: bad sizes");
   COMIC_REQUIRE(((uintptr_t)coef & 15) == 0 && ((uintptr_t)planes & 7) == 0, "jpeg_preprocess: coefficient / plane blob alignment");
-  static_assert(sizeof(ImgDesc) == 40, "comic_image_desc layout");
   hipStream_t st = (hipStream_t)stream;
   if (max_blocks > 0) {
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3(cdiv(max_blocks, 256), n), dim3(256), 0, st, coef, (const comic_jpeg_info*)infos,
@@ -359,6 +391,40 @@ extern "C" int comic_jpeg_preprocess_packed(const uint16_t* packed, const void* 
                      planes, blob, (const ImgDesc*)desc, dst, out_h, out_w, resize);
   COMIC_LAUNCH_CHECK("jpeg_preprocess");
   return 0;
+}
+
+extern "C" int comic_jpeg_preprocess_aug(const int16_t* coef, const void* infos, int n, int max_blocks, uint8_t* planes,
+                                         const uint8_t* blob, const void* desc, const void* aug, int contrast, void* aug_ws,
+                                         float* dst, int out_h, int out_w, int resize, void* stream) {
+  COMIC_REQUIRE(coef && infos && planes && desc && aug && aug_ws && dst, "jpeg_preprocess_aug: null pointer");
+  COMIC_REQUIRE(n > 0 && n <= 65535 && max_blocks >= 0 && out_h > 0 && out_w > 0 && resize >= out_h && resize >= out_w,
+                "jpeg_preprocess_aug: bad sizes");
+  COMIC_REQUIRE(((uintptr_t)coef & 15) == 0 && ((uintptr_t)planes & 7) == 0 && ((uintptr_t)aug_ws & 7) == 0,
+                "jpeg_preprocess_aug: coefficient / plane blob / workspace alignment");
+  hipStream_t st = (hipStream_t)stream;
+  if (max_blocks > 0) {
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3(cdiv(max_blocks, 256), n), dim3(256), 0, st, coef, (const comic_jpeg_info*)infos,
+                       planes);
+    COMIC_LAUNCH_CHECK("jpeg_idct");
+  }
+  return launch_preprocess_aug(infos, planes, blob, desc, aug, contrast, aug_ws, n, dst, out_h, out_w, resize, st);
+}
+
+extern "C" int comic_jpeg_preprocess_packed_aug(const uint16_t* packed, const void* infos, int n, int max_blocks, uint8_t* planes,
+                                                const uint8_t* blob, const void* desc, const void* aug, int contrast,
+                                                void* aug_ws, float* dst, int out_h, int out_w, int resize, void* stream) {
+  COMIC_REQUIRE(packed && infos && planes && desc && aug && aug_ws && dst, "jpeg_preprocess_packed_aug: null pointer");
+  COMIC_REQUIRE(n > 0 && n <= 65535 && max_blocks >= 0 && out_h > 0 && out_w > 0 && resize >= out_h && resize >= out_w,
+                "jpeg_preprocess_packed_aug: bad sizes");
+  COMIC_REQUIRE(((uintptr_t)packed & 3) == 0 && ((uintptr_t)planes & 7) == 0 && ((uintptr_t)aug_ws & 7) == 0,
+                "jpeg_preprocess_packed_aug: blob / workspace alignment");
+  hipStream_t st = (hipStream_t)stream;
+  if (max_blocks > 0) {
+    hipLaunchKernelGGL(jpeg_idct_packed_kernel, dim3(cdiv(max_blocks, 256), n), dim3(256), 0, st, packed,
+                       (const comic_jpeg_info*)infos, planes);
+    COMIC_LAUNCH_CHECK("jpeg_idct_packed");
+  }
+  return launch_preprocess_aug(infos, planes, blob, desc, aug, contrast, aug_ws, n, dst, out_h, out_w, resize, st);
 }
 
 extern "C" int comic_jpeg_pixels(const int16_t* coef, const void* infos, int n, int max_blocks, int max_w, int max_h,

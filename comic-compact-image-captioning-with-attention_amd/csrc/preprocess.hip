@@ -8,55 +8,68 @@
 // arithmetic at TF-1.9's rounding points (convert_image_dtype: cast * (1/255); resize_bilinear_op.cc compute_lerp:
 // top = tl + (tr - tl) * xl, bottom likewise, out = top + (bottom - top) * yl); contraction into FMAs is
 // switched off (#pragma clang fp contract(off)) so every operation rounds on its own.  Parity reference: oracle/preprocess_ref.py (bit-identical).
-#include "common.h"
+// comic_image_preprocess_aug: the same launch with the training augmentations of augment_dev.h (a box of the source image
+// instead of the resize and the window, slim's distort_color), which the reference carries at :45-156 and never calls.
+#include "augment_dev.h"
 
 namespace {
 
-struct ImgDesc {
-  int64_t offset;     // byte offset of the image in the uint8 blob (H x W x 3, row-major)
-  int32_t in_h, in_w;
-  int32_t flip, oy, ox;
-  float sy, sx;       // float32(in_h / 256), float32(in_w / 256)
-};
-
-// a + (b - a) * w, three roundings (resize_bilinear_op.cc compute_lerp [TF-1.9]).  HIP's __f*_rn intrinsics are plain
-// operators on AMD and hipcc contracts a + b * c into an FMA by default (-ffp-contract=fast): contraction is switched
-// off for these functions, the TF kernel (built without FMA) rounds after the product.
-__device__ __forceinline__ float lerp_rn(float a, float b, float w) {
-#pragma clang fp contract(off)
-  const float d = b - a;
-  const float m = d * w;
-  return a + m;
+__device__ __forceinline__ void read_taps(const uint8_t* __restrict__ src, int in_w, const Taps& t, float (&v)[3]) {
+  const uint8_t* r0 = src + (size_t)t.y0 * in_w * 3;
+  const uint8_t* r1 = src + (size_t)t.y1 * in_w * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    v[c] = bilinear_u8(r0[t.x0 * 3 + c], r0[t.x1 * 3 + c], r1[t.x0 * 3 + c], r1[t.x1 * 3 + c], t.wy, t.wx);
 }
 
 __global__ __launch_bounds__(256) void image_preprocess_kernel(const uint8_t* __restrict__ blob,
                                                                const ImgDesc* __restrict__ desc, float* __restrict__ dst,
                                                                int out_h, int out_w, int resize) {
-#pragma clang fp contract(off)
   const int i = blockIdx.y;
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= out_h * out_w) return;
   const ImgDesc d = desc[i];
-  const int y = p / out_w, x = p % out_w;
-  const int Y = d.oy + y;
-  const int X = d.flip ? resize - 1 - (d.ox + x) : d.ox + x;
-  const float ys = (float)Y * d.sy, xs = (float)X * d.sx;
-  const int y0 = (int)floorf(ys), x0 = (int)floorf(xs);
-  const int y1 = min((int)ceilf(ys), d.in_h - 1), x1 = min((int)ceilf(xs), d.in_w - 1);
-  const float wy = ys - (float)y0, wx = xs - (float)x0;
-  const float inv255 = (float)(1.0 / 255);
-  const uint8_t* src = blob + d.offset;
-  const uint8_t* r0 = src + (size_t)y0 * d.in_w * 3;
-  const uint8_t* r1 = src + (size_t)y1 * d.in_w * 3;
+  float v[3];
+  read_taps(blob + d.offset, d.in_w, taps_legacy(d, p / out_w, p % out_w, resize), v);
   float* o = dst + ((size_t)i * out_h * out_w + p) * 3;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float p00 = (float)r0[x0 * 3 + c] * inv255, p01 = (float)r0[x1 * 3 + c] * inv255;
-    const float p10 = (float)r1[x0 * 3 + c] * inv255, p11 = (float)r1[x1 * 3 + c] * inv255;
-    const float top = lerp_rn(p00, p01, wx), bot = lerp_rn(p10, p11, wx);
-    const float v = lerp_rn(top, bot, wy);
-    const float centred = v - 0.5f;
-    o[c] = centred * 2.0f;
+  for (int c = 0; c < 3; ++c) o[c] = to_network_range(v[c]);
+}
+
+// The same with a comic_image_aug record beside every descriptor: the box geometry and the colour ops of augment_dev.h.
+// SUMS: the first of two passes of a batch with contrast ops -- the pixel up to its contrast op, added to the image's
+// channel sums (images without a contrast op leave at once); otherwise the pass that writes dst.
+template <bool SUMS>
+__global__ __launch_bounds__(256) void image_preprocess_aug_kernel(const uint8_t* __restrict__ blob,
+                                                                   const ImgDesc* __restrict__ desc,
+                                                                   const ImgAug* __restrict__ aug, long long* __restrict__ sums,
+                                                                   float* __restrict__ dst, int out_h, int out_w, int resize) {
+  const int i = blockIdx.y;
+  const ImgAug a = aug[i];
+  const int at = aug_contrast_at(a);
+  if (SUMS && at == 4) return;
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = p < out_h * out_w;
+  if (!SUMS && !live) return;
+  float v[3] = {0.f, 0.f, 0.f};
+  if (live) {
+    const ImgDesc d = desc[i];
+    const int y = p / out_w, x = p % out_w;
+    read_taps(blob + d.offset, d.in_w, a.mode == COMIC_AUG_BOX ? taps_box(d, a, y, x, out_w) : taps_legacy(d, y, x, resize), v);
+  }
+  if (SUMS) {
+    if (live) colour_ops_until(a, at, v);
+    aug_accumulate(v, live, sums + 3 * i);
+  } else {
+    float mean[3] = {0.f, 0.f, 0.f};
+    if (at < 4) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) mean[c] = aug_mean(sums[3 * i + c], out_h * out_w);
+    }
+    colour_ops_all(a, mean, v);
+    float* o = dst + ((size_t)i * out_h * out_w + p) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = to_network_range(v[c]);
   }
 }
 
@@ -66,9 +79,30 @@ extern "C" int comic_image_preprocess(const uint8_t* blob, const void* desc, int
                                       int resize, void* stream) {
   COMIC_REQUIRE(blob && desc && dst, "image_preprocess: null pointer");
   COMIC_REQUIRE(n > 0 && out_h > 0 && out_w > 0 && resize >= out_h && resize >= out_w, "image_preprocess: bad sizes");
-  static_assert(sizeof(ImgDesc) == 40, "comic_image_desc layout");
   hipLaunchKernelGGL(image_preprocess_kernel, dim3(cdiv(out_h * out_w, 256), n), dim3(256), 0, (hipStream_t)stream, blob,
                      (const ImgDesc*)desc, dst, out_h, out_w, resize);
   COMIC_LAUNCH_CHECK("image_preprocess");
+  return 0;
+}
+
+extern "C" int comic_image_preprocess_aug(const uint8_t* blob, const void* desc, const void* aug, int contrast, void* aug_ws,
+                                          int n, float* dst, int out_h, int out_w, int resize, void* stream) {
+  COMIC_REQUIRE(blob && desc && aug && aug_ws && dst, "image_preprocess_aug: null pointer");
+  COMIC_REQUIRE(n > 0 && out_h > 0 && out_w > 0 && resize >= out_h && resize >= out_w, "image_preprocess_aug: bad sizes");
+  COMIC_REQUIRE(((uintptr_t)aug_ws & 7) == 0, "image_preprocess_aug: workspace alignment");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(cdiv(out_h * out_w, 256), n);
+  if (contrast) {
+    if (hipMemsetAsync(aug_ws, 0, (size_t)n * 3 * sizeof(long long), st) != hipSuccess) {
+      comic_set_error("image_preprocess_aug: clearing the workspace failed");
+      return 1;
+    }
+    hipLaunchKernelGGL(image_preprocess_aug_kernel<true>, grid, dim3(256), 0, st, blob, (const ImgDesc*)desc,
+                       (const ImgAug*)aug, (long long*)aug_ws, dst, out_h, out_w, resize);
+    COMIC_LAUNCH_CHECK("image_preprocess_aug (sums)");
+  }
+  hipLaunchKernelGGL(image_preprocess_aug_kernel<false>, grid, dim3(256), 0, st, blob, (const ImgDesc*)desc,
+                     (const ImgAug*)aug, (long long*)aug_ws, dst, out_h, out_w, resize);
+  COMIC_LAUNCH_CHECK("image_preprocess_aug");
   return 0;
 }

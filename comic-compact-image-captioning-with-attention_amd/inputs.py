@@ -24,7 +24,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import ops
+from . import augment as _aug, ops
+from .augment import augment_params           # noqa: F401 -- the loader's pure parameter function
 
 pjoin = os.path.join
 
@@ -114,6 +115,19 @@ def draw_augmentation(augment, height, width, rng):
         return False, (256 - height) // 2, (256 - width) // 2
     flip = rng.random() < 0.5
     return flip, rng.randrange(0, 256 - height + 1), rng.randrange(0, 256 - width + 1)
+
+
+class AugKeys(object):
+    """The `params` of a batch under --cnn_input_augment_crop area / --cnn_input_augment_color: ONE 64-bit key per image, drawn
+    in the producer thread; the parameters follow from it where the image sizes are known (augment.augment_params)."""
+    __slots__ = ('keys',)
+
+    def __init__(self, keys):
+        self.keys = np.asarray(keys, np.uint64)
+
+
+def draw_keys(n, rng):
+    return AugKeys([rng.getrandbits(64) for _ in range(n)])
 
 
 def decode_image(path_or_array):
@@ -301,10 +315,11 @@ class JpegSplitPool(object):
 
 class PackedImages(object):
     """A batch of decoded images packed back to back (+ one comic_image_desc per image) by the producer thread."""
-    __slots__ = ('slot', 'blob', 'desc', 'n', 'total')
+    __slots__ = ('slot', 'blob', 'desc', 'n', 'total', 'aug')
 
     def __init__(self, slot, blob, desc, n, total):
         self.slot, self.blob, self.desc, self.n, self.total = slot, blob, desc, n, total
+        self.aug = None                          # augment.AugmentParams of a batch drawn as AugKeys
 
 
 class DevicePreprocessor(object):
@@ -320,11 +335,12 @@ class DevicePreprocessor(object):
       finish(packed)         consumer thread: host-to-device copies + the launch; staging slots come back to the free
                              list once the event recorded behind their copies has completed (polled here)."""
 
-    def __init__(self, device, height, width, resize=256, slots=8):
+    def __init__(self, device, height, width, resize=256, slots=8, spec=None):
         import torch
         from . import _lib as L
         self.torch, self.L, self.lib = torch, L, L.load()
         self.device, self.h, self.w, self.resize = device, int(height), int(width), int(resize)
+        self.spec = spec                         # augment.AugmentSpec of a loader that draws AugKeys, else None
         self._max_slots = int(slots)
         self._n_slots = 0
         self._free = queue.Queue()
@@ -352,6 +368,7 @@ class DevicePreprocessor(object):
             blob, dbuf = np.empty(total, np.uint8), np.zeros(dbytes, np.uint8)
         desc = (L.ImageDesc * n).from_buffer(dbuf)
         off = 0
+        params, ap = self._resolve(params, [im.shape[0] for im in images_u8], [im.shape[1] for im in images_u8])
         for i, (im, (flip, oy, ox)) in enumerate(zip(images_u8, params)):
             assert im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3, (im.dtype, im.shape)
             ih, iw = int(im.shape[0]), int(im.shape[1])
@@ -362,7 +379,34 @@ class DevicePreprocessor(object):
             d.sy, d.sx = np.float32(ih / self.resize), np.float32(iw / self.resize)
             off += nb
         del desc
-        return PackedImages(slot, blob, dbuf, n, total)
+        packed = PackedImages(slot, blob, dbuf, n, total)
+        packed.aug = ap
+        return packed
+
+    def _resolve(self, params, in_h, in_w):
+        """The params of a batch -> ([(flip, oy, ox)], AugmentParams or None): keys become parameters here, where the sizes
+        are known."""
+        if not isinstance(params, AugKeys):
+            return params, None
+        ap = _aug.augment_params(params.keys, in_h, in_w, self.spec)
+        return list(zip(ap.flip.tolist(), ap.oy.tolist(), ap.ox.tolist())), ap
+
+    def _aug_on_device(self, ap, n, pinned=None):
+        """Consumer thread: the comic_image_aug records of a batch and the workspace of the contrast sums on the device ->
+        the three arguments of the _aug entries."""
+        torch = self.torch
+        nb = n * 48
+        ws = self.__dict__.get('_dev_aug_ws')
+        if ws is None or ws.numel() < 3 * n:
+            ws = self._dev_aug_ws = torch.empty(3 * max(n, 64), dtype=torch.int64, device=self.device)
+            self._dev_aug = torch.empty(48 * max(n, 64), dtype=torch.uint8, device=self.device)
+        recs = ap.aug.view(np.uint8).reshape(-1)
+        if pinned is not None:
+            pinned.numpy()[:nb] = recs
+            self._dev_aug[:nb].copy_(pinned[:nb], non_blocking=True)
+        else:
+            self._dev_aug[:nb].copy_(torch.from_numpy(np.array(recs, copy=True)))
+        return self._dev_aug.data_ptr(), int(ap.contrast), ws.data_ptr()
 
     def pack_paths(self, pool, paths, params):
         """Producer half for a DecodePool: the worker processes decode straight into a shared-memory block (no copy in
@@ -370,7 +414,8 @@ class DevicePreprocessor(object):
         import ctypes as C
         L = self.L
         blk, total, pending = pool.decode_batch_async(paths)
-        return PackedImages(('shm', pool, blk, pending, list(paths), list(params)), None, None, len(paths), total)
+        return PackedImages(('shm', pool, blk, pending, list(paths), params if isinstance(params, AugKeys) else list(params)), None,
+                            None, len(paths), total)
 
     # ---- split JPEG decode: coefficients from the host threads, pixels on the device ------------------------------------
     _DESC_DTYPE = np.dtype({'names': ['offset', 'in_h', 'in_w', 'flip', 'oy', 'ox', 'sy', 'sx'],
@@ -395,6 +440,8 @@ class DevicePreprocessor(object):
                         infos=torch.zeros(n * 512, dtype=torch.uint8).pin_memory(),
                         desc=torch.zeros(n * 40, dtype=torch.uint8).pin_memory(),
                         status=np.zeros(n, np.int32))
+            if self.spec is not None:
+                slot['aug'] = torch.zeros(n * 48, dtype=torch.uint8).pin_memory()
             self._all_coef.append(slot)
             self._free_coef.put(slot)
         with torch.cuda.device(self.device):
@@ -426,7 +473,8 @@ class DevicePreprocessor(object):
         # the consumer finds their pixels ready instead of decoding them inside its step
         known = self.__dict__.setdefault('_pil_known', set())
         early = {i: self._pil_threads().submit(decode_image, p) for i, p in enumerate(paths) if p in known} if known else {}
-        return PackedImages(('split', jpool, handle, slot, list(paths), list(params), early), None, None, len(paths), 0)
+        return PackedImages(('split', jpool, handle, slot, list(paths), params if isinstance(params, AugKeys) else list(params),
+                             early), None, None, len(paths), 0)
 
     def _pil_threads(self):
         pool = self.__dict__.get('_pil_pool')
@@ -445,6 +493,8 @@ class DevicePreprocessor(object):
             # threads of this batch may still write into the slot: it is retired with the batch, a fresh one takes its place
             fresh = dict(coef=torch.empty_like(slot['coef']).pin_memory(), infos=torch.zeros_like(slot['infos']).pin_memory(),
                          desc=torch.zeros_like(slot['desc']).pin_memory(), status=np.zeros_like(slot['status']))
+            if 'aug' in slot:
+                fresh['aug'] = torch.zeros_like(slot['aug']).pin_memory()
             self._all_coef.append(fresh)             # (the retired slot stays in the list too)
             self._free_coef.put(fresh)
             raise
@@ -485,9 +535,14 @@ class DevicePreprocessor(object):
             pixel_bytes += (im.size + 15) // 16 * 16
         desc = slot['desc'].numpy()[:n * 40].view(self._DESC_DTYPE)      # pinned: every copy of the batch is asynchronous
         desc['offset'], desc['in_h'], desc['in_w'] = off, h, w
-        desc['flip'] = [int(bool(p[0])) for p in params]
-        desc['oy'] = [int(p[1]) for p in params]
-        desc['ox'] = [int(p[2]) for p in params]
+        ap = None
+        if isinstance(params, AugKeys):
+            ap = _aug.augment_params(params.keys, h, w, self.spec)
+            desc['flip'], desc['oy'], desc['ox'] = ap.flip, ap.oy, ap.ox
+        else:
+            desc['flip'] = [int(bool(p[0])) for p in params]
+            desc['oy'] = [int(p[1]) for p in params]
+            desc['ox'] = [int(p[2]) for p in params]
         desc['sy'] = (h / self.resize).astype(np.float32)
         desc['sx'] = (w / self.resize).astype(np.float32)
         with torch.cuda.device(self.device):
@@ -506,11 +561,18 @@ class DevicePreprocessor(object):
             dev_desc[:n * 40].copy_(slot['desc'][:n * 40], non_blocking=True)
             out = torch.empty((n, self.h, self.w, 3), dtype=torch.float32, device=self.device)
             # packed blocks -> inverse DCT, then resize / flip / crop / scale with the taps converted from the component planes
-            L.check(self.lib.comic_jpeg_preprocess_packed(self._dev_coef.data_ptr(), dev_infos.data_ptr(), n,
-                                                          int(infos['coef_count'][ok].max()) // 64 if ok.any() else 0,
-                                                          self._dev_planes.data_ptr(), self._dev_blob.data_ptr() if late else None,
-                                                          dev_desc.data_ptr(), out.data_ptr(), self.h, self.w, self.resize, st),
-                    'jpeg_preprocess_packed')
+            max_blocks = int(infos['coef_count'][ok].max()) // 64 if ok.any() else 0
+            if ap is None:
+                L.check(self.lib.comic_jpeg_preprocess_packed(self._dev_coef.data_ptr(), dev_infos.data_ptr(), n, max_blocks,
+                                                              self._dev_planes.data_ptr(), self._dev_blob.data_ptr() if late else None,
+                                                              dev_desc.data_ptr(), out.data_ptr(), self.h, self.w, self.resize, st),
+                        'jpeg_preprocess_packed')
+            else:               # ... the box / colour ops of the batch's comic_image_aug records in the same launch
+                L.check(self.lib.comic_jpeg_preprocess_packed_aug(self._dev_coef.data_ptr(), dev_infos.data_ptr(), n, max_blocks,
+                                                                  self._dev_planes.data_ptr(),
+                                                                  self._dev_blob.data_ptr() if late else None, dev_desc.data_ptr(),
+                                                                  *self._aug_on_device(ap, n, slot['aug']), out.data_ptr(), self.h,
+                                                                  self.w, self.resize, st), 'jpeg_preprocess_packed_aug')
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
         self._pending.append((('coef', slot), ev))
@@ -522,12 +584,24 @@ class DevicePreprocessor(object):
         n = len(geo)
         dbuf = np.zeros(n * C.sizeof(L.ImageDesc), np.uint8)
         desc = (L.ImageDesc * n).from_buffer(dbuf)
+        params, ap = self._resolve(params, [g[1] for g in geo], [g[2] for g in geo])
         for i, ((off, ih, iw), (flip, oy, ox)) in enumerate(zip(geo, params)):
             d = desc[i]
             d.offset, d.in_h, d.in_w, d.flip, d.oy, d.ox = off, ih, iw, int(bool(flip)), int(oy), int(ox)
             d.sy, d.sx = np.float32(ih / self.resize), np.float32(iw / self.resize)
         del desc
-        return dbuf
+        return dbuf, ap
+
+    def _image_preprocess(self, dev_desc, ap, n, out):
+        """comic_image_preprocess of the device blob, or its _aug form for a batch with comic_image_aug records."""
+        L = self.L
+        if ap is None:
+            L.check(self.lib.comic_image_preprocess(self._dev_blob.data_ptr(), dev_desc.data_ptr(), n, out.data_ptr(),
+                                                    self.h, self.w, self.resize, L.stream_ptr()), 'image_preprocess')
+        else:
+            L.check(self.lib.comic_image_preprocess_aug(self._dev_blob.data_ptr(), dev_desc.data_ptr(),
+                                                        *self._aug_on_device(ap, n), n, out.data_ptr(), self.h, self.w,
+                                                        self.resize, L.stream_ptr()), 'image_preprocess_aug')
 
     # ---- consumer side ------------------------------------------------------------------------------------------
     def _reap(self):
@@ -609,7 +683,7 @@ class DevicePreprocessor(object):
             except ValueError:
                 slot[1].release(slot[2])
                 raise
-            packed.desc = self._fill_desc(geo, slot[5])
+            packed.desc, packed.aug = self._fill_desc(geo, slot[5])
             host = self._shm_tensor(slot[2])
             with torch.cuda.device(self.device):
                 if self._dev_blob is None or self._dev_blob.numel() < total:
@@ -617,8 +691,7 @@ class DevicePreprocessor(object):
                 dev_desc = torch.from_numpy(packed.desc[:dbytes]).to(self.device)
                 self._dev_blob[:total].copy_(host[:total], non_blocking=True)
                 out = torch.empty((n, self.h, self.w, 3), dtype=torch.float32, device=self.device)
-                L.check(self.lib.comic_image_preprocess(self._dev_blob.data_ptr(), dev_desc.data_ptr(), n, out.data_ptr(),
-                                                        self.h, self.w, self.resize, L.stream_ptr()), 'image_preprocess')
+                self._image_preprocess(dev_desc, packed.aug, n, out)
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream())
             self._pending.append((slot, ev))
@@ -640,8 +713,7 @@ class DevicePreprocessor(object):
             self._dev_blob[:total].copy_(slot['blob'][:total], non_blocking=True)
             dev_desc.copy_(slot['desc'][:dbytes], non_blocking=True)
             out = torch.empty((n, self.h, self.w, 3), dtype=torch.float32, device=self.device)
-            L.check(self.lib.comic_image_preprocess(self._dev_blob.data_ptr(), dev_desc.data_ptr(), n, out.data_ptr(),
-                                                    self.h, self.w, self.resize, L.stream_ptr()), 'image_preprocess')
+            self._image_preprocess(dev_desc, packed.aug, n, out)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
         if recycle:
@@ -653,14 +725,24 @@ class DevicePreprocessor(object):
         return self.finish(self.pack(images_u8, params))
 
 
-def preprocess_image(path_or_array, height, width, augment, rng, params=None):
+def preprocess_image(path_or_array, height, width, augment, rng, params=None, aug=None):
+    """`aug`: the image's comic_image_aug record (augment.augment_params) -- the box instead of the 256 x 256 resize and
+    the window, and the colour ops, as the device computes them (include/comic_hip.h)."""
     img = decode_image(path_or_array)
     img = img.astype(np.float32) * np.float32(1.0 / 255)      # tf.image.convert_image_dtype [TF-1.9]
-    img = resize_bilinear_tf1(img, 256, 256)
     flip, oy, ox = params if params is not None else draw_augmentation(augment, height, width, rng)
-    if flip:
-        img = img[:, ::-1]
-    img = img[oy:oy + height, ox:ox + width]
+    if aug is not None and int(aug['mode']) == _aug.L.AUG_BOX:
+        cy, cx, ch, cw = (int(aug[k]) for k in ('cy', 'cx', 'ch', 'cw'))
+        img = resize_bilinear_tf1(img[cy:cy + ch, cx:cx + cw], height, width)
+        if flip:
+            img = img[:, ::-1]
+    else:
+        img = resize_bilinear_tf1(img, 256, 256)
+        if flip:
+            img = img[:, ::-1]
+        img = img[oy:oy + height, ox:ox + width]
+    if aug is not None:
+        img = _aug.distort_color(img, aug)
     return np.ascontiguousarray((img - np.float32(0.5)) * np.float32(2.0))
 
 
@@ -707,6 +789,8 @@ class InputManager(object):
         self._world = max(1, int(getattr(c, 'dp_world', 1) or 1))
         self._rank = int(getattr(c, 'dp_rank', 0) or 0)
         self._aug_rng = random.Random(c.rand_seed + 7919 * (self._rank + 1)) if self._world > 1 else self._rng
+        # --cnn_input_augment_crop / _color (None with the flags at their defaults: the draws are draw_augmentation's)
+        self._aug_spec = None if is_inference else _aug.spec_from_config(c)
         # decode / resize workers (the reference maps with num_parallel_calls=3, :169; one MI355X consumes three
         # orders of magnitude more images per second than a TF-1 CPU pipeline) and batches kept ahead of the step
         self._pool = ThreadPoolExecutor(max_workers=int(getattr(c, 'loader_threads', 0)) or min(16, os.cpu_count() or 3))
@@ -815,7 +899,7 @@ class InputManager(object):
         if not str(device).startswith('cuda') or getattr(self, '_devpre', None) is not None:
             return                                   # (a second call: the loader of this manager is set up)
         h, w = self.config.cnn_input_size
-        self._devpre = DevicePreprocessor(device, h, w)
+        self._devpre = DevicePreprocessor(device, h, w, spec=self._aug_spec)
         c = self.config
         # the split JPEG decoder is the default loader; --loader_processes N (an explicit request) or --no-loader_split_jpeg
         # select the PIL loaders
@@ -847,7 +931,10 @@ class InputManager(object):
 
     def _load_many(self, paths, augment):
         h, w = self.config.cnn_input_size
-        params = [draw_augmentation(augment, h, w, self._aug_rng) for _ in paths]
+        if augment and self._aug_spec is not None:
+            params = draw_keys(len(paths), self._aug_rng)        # one key per image: the sizes are not known here
+        else:
+            params = [draw_augmentation(augment, h, w, self._aug_rng) for _ in paths]
         devpre = getattr(self, '_devpre', None)
         dpool = getattr(self, '_decode_pool', None)
         if devpre is not None and getattr(self, '_jpeg_pool', None) is not None and all(isinstance(p, str) for p in paths):
@@ -856,6 +943,12 @@ class InputManager(object):
             return devpre.pack_paths(dpool, paths, params)      # decode in worker processes, straight into staging
         if devpre is not None:       # CPU half here (producer thread); the device half runs in Prefetch's consumer hook
             return devpre.pack(list(self._pool.map(decode_image, paths)), params)
+        if isinstance(params, AugKeys):
+            images = list(self._pool.map(decode_image, paths))
+            ap = _aug.augment_params(params.keys, [im.shape[0] for im in images], [im.shape[1] for im in images],
+                                        self._aug_spec)
+            todo = zip(images, zip(ap.flip.tolist(), ap.oy.tolist(), ap.ox.tolist()), ap.aug)
+            return np.stack(list(self._pool.map(lambda a: preprocess_image(a[0], h, w, augment, None, a[1], a[2]), todo)))
         return np.stack(list(self._pool.map(lambda a: self._load(a[0], augment, a[1]), zip(paths, params))))
 
     def _batches(self, data, batch_size, is_training, augment):

@@ -229,6 +229,47 @@ int comic_jpeg_preprocess_packed(const uint16_t* packed, const void* infos, int 
                                  const uint8_t* blob, const void* desc, float* dst /* [n,out_h,out_w,3] */, int out_h, int out_w,
                                  int resize, void* stream);
 
+/* Training augmentation inside the same launches (`--cnn_input_augment_crop area`, `--cnn_input_augment_color fast|full`):
+ * slim's distorted_bounding_box_crop and distort_color, which the reference carries and preprocess_for_train never calls
+ * (common/inputs/preprocessing/inception_preprocessing_radix.py:45-156 beside :158-234).  One comic_image_aug record per image
+ * travels BESIDE its comic_image_desc (whose offset / in_h / in_w / flip hold in both modes).
+ *   geometry  COMIC_AUG_LEGACY: the resize to `resize`, flip and (oy, ox) window of the descriptor, as above.
+ *             COMIC_AUG_BOX: resize_bilinear_tf1(src[cy:cy+ch, cx:cx+cw], out_h, out_w), then the flip -- for output (y, x):
+ *             X = flip ? out_w-1-x : x, ys = float32(y) * sy, y0 = floor(ys), y1 = min(ceil(ys), ch-1), wy = ys - y0 (x alike
+ *             with X), taps at (cy + y0|y1, cx + x0|x1): the clamp is at the box edge.  No 256 x 256 intermediate.
+ *   colour    on the [0,1] value of the three channels behind the lerps, ops[0..3] in order, then clamp(v, 0, 1) where there
+ *             was an op, then (v - 0.5) * 2.  float32, every operation rounded on its own:
+ *             BRIGHTNESS v + brightness; SATURATION rgb -> hsv, s = clamp(s * saturation, 0, 1), hsv -> rgb; HUE rgb -> hsv,
+ *             h = frac(h + hue), hsv -> rgb; CONTRAST (v - mean_c) * contrast + mean_c, mean_c the channel's mean over the
+ *             image's out_h * out_w output pixels in the state in front of the contrast op.
+ *             rgb -> hsv: v = max, d = max - min, s = d / v (0 where v <= 0), h = 0 at d = 0, else (g-b)/d, 2 + (b-r)/d or
+ *             4 + (r-g)/d by the channel holding the maximum (red before green before blue), times float32(1/6), t - floor(t)
+ *             (0 where that gives 1).  hsv -> rgb, channel n = 5, 3, 1: k = n + 6h, less 6 where >= 6;
+ *             v - (v * s) * clamp(min(k, 4 - k), 0, 1).
+ *   mean_c    float32(double(sum) / (2^32 * out_h * out_w)), sum the int64 total of llrint(double(v) * 2^32): integers, so the
+ *             order of the additions (64-bit atomics of the workgroups) does not matter and a batch gives the same bytes twice.
+ * `contrast` != 0: some record holds a contrast op -- `aug_ws` (n * 3 int64, 8-byte aligned, the caller's) is cleared on the
+ * stream, a first launch forms every such image's sums (images without the op leave it at once), a second one writes dst.
+ * contrast == 0: ONE preprocessing launch, as the entries above. */
+enum { COMIC_AUG_LEGACY = 0, COMIC_AUG_BOX = 1 };
+enum { COMIC_AUG_OP_NONE = 0, COMIC_AUG_OP_BRIGHTNESS = 1, COMIC_AUG_OP_SATURATION = 2, COMIC_AUG_OP_HUE = 3,
+       COMIC_AUG_OP_CONTRAST = 4 };
+typedef struct comic_image_aug {
+  int32_t mode;          /* COMIC_AUG_LEGACY / COMIC_AUG_BOX */
+  int32_t cy, cx, ch, cw; /* the box, inside the source image (BOX) */
+  float sy, sx;          /* float32(ch / out_h), float32(cw / out_w) */
+  uint8_t ops[4];        /* COMIC_AUG_OP_*; every kind at most once */
+  float brightness, saturation, hue, contrast;
+} comic_image_aug;       /* 48 bytes */
+int comic_image_preprocess_aug(const uint8_t* blob, const void* desc, const void* aug, int contrast, void* aug_ws, int n,
+                               float* dst /* [n,out_h,out_w,3] */, int out_h, int out_w, int resize, void* stream);
+int comic_jpeg_preprocess_aug(const int16_t* coef, const void* infos, int n, int max_blocks, uint8_t* planes, const uint8_t* blob,
+                              const void* desc, const void* aug, int contrast, void* aug_ws, float* dst /* [n,out_h,out_w,3] */,
+                              int out_h, int out_w, int resize, void* stream);
+int comic_jpeg_preprocess_packed_aug(const uint16_t* packed, const void* infos, int n, int max_blocks, uint8_t* planes,
+                                     const uint8_t* blob, const void* desc, const void* aug, int contrast, void* aug_ws,
+                                     float* dst /* [n,out_h,out_w,3] */, int out_h, int out_w, int resize, void* stream);
+
 /* ---- cnn_finetune: backward of the plan (train.py:241-249; model_base.py:76,834-849) ------
  * The CNN variables (conv weights, BN beta) become trainable; BN stays in inference mode, so a
  * conv contributes d beta = sum(1[y>0] dy), d w (backward-weight) and d x (backward-data).

@@ -3,7 +3,8 @@
 CLI (reference src/train.py:25-312), driving the MI355X-native path.
 
 Differences (all additive): `--cnn_dtype {bf16,f16,f32,bf16x3}`, `--checkpoint_format {npz,tf}`, `--ema_decay`, `--prune_*`, `--label_smoothing`,
-`--distill_checkpoints / _weight / _top_k / _temperature / _weights`; launched under
+`--distill_checkpoints / _weight / _top_k / _temperature / _weights`,
+`--cnn_input_augment_crop {fixed,area}`, `--cnn_input_augment_area_min`, `--cnn_input_augment_color {none,fast,full}`; launched under
 `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel (one process
 per GPU, RCCL gradient all-reduce); the slim checkpoint is not downloaded (no network):
 pass `--checkpoint_path` (an .npz with slim variable names) or train the CNN from random init.
@@ -34,6 +35,15 @@ def create_parser():
     a('--cnn_name', type=str, default='inception_v1', help='The CNN model name.')
     a('--cnn_input_size', type=str, default='224,224', help='The network input size.')
     a('--cnn_input_augment', type=bool, default=True, help='Whether to augment input images.')
+    a('--cnn_input_augment_crop', type=str, default='fixed', choices=['fixed', 'area'],
+      help='Crop of the training images: `fixed`: the 224 window of the 256 x 256 resize (the reference); `area`: a box of random '
+           'area and aspect ratio (3/4 ... 4/3) cut from the source image and resized straight to the input size, on the device; '
+           'the run directory gets `_augA<area_min>`.')
+    a('--cnn_input_augment_area_min', type=float, default=0.35,
+      help='With --cnn_input_augment_crop area: the smallest share of the image a box covers, in (0, 1].')
+    a('--cnn_input_augment_color', type=str, default='none', choices=['none', 'fast', 'full'],
+      help='Colour distortion of the training images (slim distort_color), on the device: `fast` brightness and saturation, '
+           '`full` brightness, saturation, hue and contrast, in an order drawn per image; the run directory gets `_augC<mode>`.')
     a('--cnn_fm_attention', type=str, default='Mixed_4f', help='String, name of feature map for attention.')
     a('--cnn_fm_projection', type=str, default='tied', choices=['none', 'independent', 'tied'],
       help='String, feature map projection, from `none`, `independent`, `tied`.')
@@ -164,8 +174,9 @@ def build_kwargs(args):
     smooth, distil = soft_dir_suffixes(args)
     # a pruned run likewise, `_pr<s>[g]` right behind the name -- of the stage that prunes only: it starts from the
     # checkpoint of the plain earlier stage, and a later stage names the pruned one by `--name <name>_pr<s>`
-    from comic_amd import prune
-    pruned = name + prune.dir_suffix(args)
+    from comic_amd import augment, prune
+    # ... and one with --cnn_input_augment_crop area / --cnn_input_augment_color, `_aug[A<area_min>][C<mode>]`
+    pruned = name + prune.dir_suffix(args) + augment.dir_suffix(args)
     dec_dir = pjoin(log_root, '{}{}_run_{:02d}'.format(name, smooth, args.run))
     cnnft_dir = pjoin(log_root, '{}{}_cnnFT_run_{:02d}'.format(name, smooth, args.run))
     train_fn_name = 'train_fn'
@@ -210,6 +221,7 @@ def build_kwargs(args):
         for k in ('distill_checkpoints', 'distill_weight', 'distill_top_k', 'distill_temperature', 'distill_weights'):
             kwargs.pop(k, None)
     prune.pop_defaults(kwargs)                  # and the pruning flags
+    augment.pop_defaults(kwargs)                # and the augmentation flags
     check_supported(kwargs)
     return kwargs, train_fn_name, overwrite
 
@@ -235,6 +247,13 @@ def refuse_bad_prune_options(kw):
     before anything touches the GPU."""
     from comic_amd import prune
     prune.refuse_bad_prune_options(kw)
+
+
+def refuse_bad_augment_options(kw):
+    """--cnn_input_augment_crop / _color / _area_min with --cnn_input_augment False, --cnn_input_augment_area_min outside
+    (0, 1] or without `area`.  Called before anything touches the GPU."""
+    from comic_amd import augment
+    augment.refuse_bad_options(kw)
 
 
 def refuse_bad_soft_options(kw):
@@ -305,6 +324,7 @@ def check_supported(kw):
     refuse_bad_scst_options(kw)
     refuse_bad_soft_options(kw)
     refuse_bad_prune_options(kw)
+    refuse_bad_augment_options(kw)
     bad = []
     # --initialiser: `he` / `none` select TensorFlow's default initialiser in the reference (model_base.py:823-831:
     # every value but `xavier` returns None), which for these float variables is glorot_uniform == Xavier-uniform
@@ -320,6 +340,7 @@ def main(argv=None):
     refuse_bad_scst_options(vars(args))
     refuse_bad_soft_options(vars(args))
     refuse_bad_prune_options(vars(args))
+    refuse_bad_augment_options(vars(args))
     import torch
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
